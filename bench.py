@@ -1,6 +1,6 @@
 """Headline benchmark: training samples/sec of the encode-process-decode GNN on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 One "step" = one optimiser step on a batch of synthetic 6-hour samples (forward, weighted-MSE
 loss with residual add, backward, gradient all-reduce when N > 1, Adam), batch fixed PER GPU
@@ -9,6 +9,10 @@ wb2_64x32 (2048 grid nodes, 33 features, obs window 2, mesh levels [3,5]), 64 sa
 Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` for the mesh
 GCNConv aggregation kernel (HIP events on the launch stream, inside the timed region) and
 `cpu_baseline` = the CPU oracle (PyG op sequence, batch 1) timed on this box's host cores.
+`--dump-outputs DIR` also writes what the last timed step computed - its loss, the parameters after its Adam
+update and its gradients, each flattened in `model.parameters()` order - as float32 `DIR/<name>.npy`.  The
+inputs, the initial weights and the number of steps before that one are fixed by the arguments, so two builds
+can be compared output for output.
 """
 import argparse
 import json
@@ -76,6 +80,20 @@ def synthetic_batch(cfg, G, B, seed):
     X = torch.randn(B, G, cfg.data.obs_window_used * F, generator=g)
     y = X[..., -F:] + 0.1 * torch.randn(B, G, F, generator=g)
     return X, y
+
+
+def dump_outputs(dirname, arrays, limit_bytes=60 * 10**6):
+    """Write each 1-D float32 array as `dirname/<name>.npy`.  Arrays are written whole while all of them fit in
+    `limit_bytes` (the files then stay under 64 MB in all); otherwise each one above an equal share of the limit is
+    cut to that share by a fixed-seed sample of its elements (kept in index order), so runs with the same arguments
+    still write the same elements."""
+    os.makedirs(dirname, exist_ok=True)
+    share = limit_bytes // len(arrays) // 4
+    over = sum(a.nbytes for a in arrays.values()) > limit_bytes
+    for name, a in arrays.items():
+        if over and a.size > share:
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, share, replace=False))]
+        np.save(os.path.join(dirname, f"{name}.npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def cpu_baseline(cfg, model, grid, budget_s=12.0, max_steps=2000):
@@ -243,9 +261,13 @@ def main():
                     help="launch every kernel of the timed steps individually instead of replaying the captured "
                          "hipGraph (then the roofline events are recorded inside the timed region itself)")
     ap.add_argument("--graph", action="store_true", help="(default) kept for older command lines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (loss, updated parameters, gradients) to DIR/<name>.npy")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # no launcher: become the launcher (one child process per GPU; this process stays off the GPU)
@@ -262,6 +284,10 @@ def main():
         raise SystemExit(f"bench.py: rank {rank} wants GPU {local} but only {torch.cuda.device_count()} are visible")
     torch.cuda.set_device(local)
     dev = torch.device("cuda", local)
+    # The whole run - model set-up, settle, warm-up and timed steps - goes to a stream of its own: on the legacy default
+    # stream the replayed step computed gradients that differed from run to run (and from eager launches of the same
+    # steps) on MI355X; on a created stream it repeats bit for bit.
+    torch.cuda.set_stream(torch.cuda.Stream(dev))
 
     from graphcast_lite_amd import hip, models
     from graphcast_lite_amd.train import TrainStep, get_lat_weights
@@ -274,6 +300,10 @@ def main():
     X, y = X.to(dev), y.to(dev)                           # resident in HBM before the timed region
     step = TrainStep(model, lr=1e-3, lat_weights=get_lat_weights(grid[0], grid[1], dev), world_size=world,
                      use_graph=False if args.eager else None)
+    # the settle phase below runs a time-dependent number of optimiser steps; the weights and Adam state are put
+    # back after it, so the warm-up and timed steps start from the same state in every run with the same arguments
+    train_state = (step.flat.flat, step.opt.m, step.opt.v, step.opt.step_dev, step.opt.bc_dev)
+    initial_state = [t.clone() for t in train_state]
 
     # Untimed settle phase before the W official warm-up steps: a freshly acquired box can run the
     # first seconds several times slower (clock ramp / code-object and allocator warm-up).  Step until
@@ -292,6 +322,9 @@ def main():
         streak = streak + 1 if dt1 <= 1.15 * best else 0
         if world == 1 and settle >= 5 and streak >= 3:
             break
+    for dst, src in zip(train_state, initial_state):
+        dst.copy_(src)  # in place: a captured hipGraph keeps pointing at these buffers
+    del initial_state
     for _ in range(args.warmup):
         loss = step(X, y)
     is_gcn = cfg.pipeline.processor.gcn.layer_type.value == "conv_gcn"
@@ -339,6 +372,12 @@ def main():
     if world > 1:
         dist.barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        # copied now: the replays after the timed region overwrite the loss buffer, the weights and the gradients
+        params = step.flat.params
+        outputs = {"loss": loss.detach().float().cpu().numpy().reshape(1),
+                   "params": torch.cat([p.detach().reshape(-1) for p in params]).cpu().numpy(),
+                   "grads": torch.cat([p.grad.reshape(-1) for p in params]).cpu().numpy()}
     roof_steps, roof_ms = args.steps, None
     roof_pass = replayed
     if world > 1:  # the eager roofline pass contains collectives: every rank runs it if any rank needs it
@@ -510,6 +549,8 @@ def main():
                                    if roof_pass else "the timed steps themselves")
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(cfg, model, grid)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, outputs)
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.destroy_process_group()

@@ -170,6 +170,43 @@ def test_bench_never_reports_more_gpus_than_ranks():
     assert r.returncode != 0 and not lines
 
 
+@pytest.mark.gpu
+def test_bench_dump_outputs_are_reproducible(tmp_path):
+    """`--dump-outputs` writes what the last timed step computed: the same in two runs with the same arguments, the
+    same from the replayed hipGraph as from eager launches of the same steps, and different after one more step."""
+    def dump(name, *extra, steps=4):
+        d = tmp_path / name
+        r, lines = _run_bench(["--gpus", "1", "--steps", str(steps), "--warmup", "2", "--no-cpu-baseline",
+                               "--dump-outputs", str(d)] + list(extra), {}, timeout=600)
+        assert r.returncode == 0 and len(lines) == 1, r.stderr[-2000:]
+        assert lines[0]["steps"] == steps and lines[0]["ms_per_step"] > 0
+        assert sum(f.stat().st_size for f in d.iterdir()) <= 64 * 10**6
+        return {n: np.load(d / f"{n}.npy") for n in ("loss", "params", "grads")}
+
+    a, b, e, longer = dump("a"), dump("b"), dump("eager", "--eager"), dump("longer", steps=5)
+    for n, x in a.items():
+        assert x.dtype == np.float32 and x.size > 0 and np.all(np.isfinite(x)), n
+        assert np.array_equal(x, b[n]) and np.array_equal(x, e[n]), n
+        assert not np.array_equal(x, longer[n]), n
+
+
+def test_bench_dump_outputs_sample_above_the_limit(tmp_path):
+    """Arrays beyond the size limit are cut to a fixed-seed sample of their elements, in index order."""
+    import bench
+
+    arrays = {"loss": np.array([0.5], np.float32), "params": np.arange(1000, dtype=np.float32),
+              "grads": -np.arange(10, dtype=np.float32)}
+    bench.dump_outputs(str(tmp_path / "whole"), arrays)
+    for n, x in arrays.items():
+        assert np.array_equal(np.load(tmp_path / "whole" / f"{n}.npy"), x)
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), arrays, limit_bytes=1200)
+    p1, p2 = (np.load(tmp_path / d / "params.npy") for d in ("s1", "s2"))
+    assert p1.size == 1200 // 3 // 4 and np.array_equal(p1, p2)
+    assert np.all(np.diff(p1) > 0) and np.all(np.isin(p1, arrays["params"]))
+    assert np.array_equal(np.load(tmp_path / "s1" / "grads.npy"), arrays["grads"])  # under its share: whole
+
+
 # ------------------------------------------------------------------------------------------------
 # TrainStep with world_size 2 on the GPU box: two gloo ranks sharing device 0 (tests/helpers/dp_rank.py)
 # against the single-process step on the global batch.

@@ -281,7 +281,7 @@ def test_reduce_jobs_more_than_one_launch_with_an_empty_job(hip):
     assert rel(a1, a0) < 2e-6
 
 
-def test_linear_mfma_equals_valu(hip, monkeypatch):
+def test_linear_mfma_equals_valu(hip, monkeypatch, tmp_path):
     """The fp32 MFMA path and the plain VALU path of the same entry point agree (both fp32 FMA chains)."""
     import os
     import subprocess
@@ -297,7 +297,7 @@ def test_linear_mfma_equals_valu(hip, monkeypatch):
         "torch.save(y.cpu(), sys.argv[1])\n" % os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     outs = []
     for impl in ("mfma", "valu"):
-        path = f"/tmp/gcl_lin_{impl}.pt"
+        path = str(tmp_path / f"gcl_lin_{impl}.pt")
         env = dict(os.environ, GCL_LINEAR_IMPL=impl)
         subprocess.run([sys.executable, "-c", code, path], check=True, env=env)
         outs.append(torch.load(path))
