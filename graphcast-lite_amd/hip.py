@@ -97,6 +97,8 @@ _SIGNATURES = {
     "gcl_ar_advance": (C.c_int, [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32,
                                  _i32, _i32, _vp]),
     "gcl_gather2_rows": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp]),
+    "gcl_roi_gather_rows": (C.c_int, [_vp, _i32, _i32] + [_vp, _i64, _i64, _i32] * 3 + [_vp, _i64, _i64, _i32, _i32, _vp]),
+    "gcl_roi_compose": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _vp]),
 }
 
 
@@ -688,6 +690,39 @@ def gather2_rows(a3, map_a, b3, map_b, nd: int, B: int, sum_batch: bool = False,
     bsb = 0 if b3 is None else (b3.stride(0) if b3.shape[0] > 1 else 0)
     _check(lib().gcl_gather2_rows(_p(a3), a3.stride(1), bsa, _pi(map_a), _p(b3), 0 if b3 is None else b3.stride(1),
                                   bsb, _pi(map_b), _p(out), out.stride(1), out.stride(0), B, nd, F, flag, _stream()))
+    return out
+
+
+def roi_gather_rows(rows, rows_src: int, srcs, Fp: int, B: int, out=None):
+    """out[b, i] = [s0[b, rows[i]] | s1[b, rows[i]] | s2[b, rows[i]] | 0] (see gcl_roi_gather_rows).  `srcs`: up to three
+    [B | 1, rows_src, w] tensors with unit channel stride and any row / batch stride (batch 1 broadcasts); `rows`: int32
+    device indices (None = identity over the first `out.shape[1]` rows).  Returns [B, n, Fp] (or writes `out`)."""
+    n = rows.numel() if rows is not None else out.shape[1]
+    if out is None:
+        out = torch.empty(B, n, Fp, dtype=torch.float32, device=srcs[0].device)
+    assert out.shape == (B, n, Fp) and out.stride(2) == 1 and len(srcs) <= 3
+    args = []
+    for k in range(3):
+        t = srcs[k] if k < len(srcs) else None
+        if t is None or t.shape[-1] == 0:
+            args += [None, 0, 0, 0]
+            continue
+        assert t.dim() == 3 and t.stride(2) == 1 and t.shape[1] == rows_src and t.shape[0] in (1, B)
+        args += [_p(t), t.stride(1), t.stride(0) if t.shape[0] > 1 else 0, t.shape[2]]
+    _check(lib().gcl_roi_gather_rows(_pi(rows), n, rows_src, *args, _p(out), out.stride(1), out.stride(0), Fp, B,
+                                     _stream()))
+    return out
+
+
+def roi_compose(pred3, corr3, pos, out=None):
+    """out[b, g] = pred3[b, g] + corr3[b, pos[g]] where pos[g] >= 0, else pred3[b, g] (see gcl_roi_compose)."""
+    B, G, Cc = pred3.shape
+    assert corr3.dim() == 3 and corr3.shape[0] == B and corr3.shape[2] >= Cc and pos.numel() == G
+    assert pred3.stride(2) == 1 and corr3.stride(2) == 1
+    if out is None:
+        out = torch.empty(B, G, Cc, dtype=torch.float32, device=pred3.device)
+    _check(lib().gcl_roi_compose(_p(pred3), pred3.stride(1), pred3.stride(0), _p(corr3), corr3.stride(1), corr3.stride(0),
+                                 _pi(pos), _p(out), out.stride(1), out.stride(0), B, G, Cc, _stream()))
     return out
 
 

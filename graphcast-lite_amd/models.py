@@ -834,7 +834,12 @@ class WeatherPrediction(nn.Module):
         decoded = self.decoder.forward(X=dec_in, edge_index=c.dec_graph, **({"_out_rows": G} if gcn_dec else {}))
         out, grid_lat = (decoded if gcn_dec else decoded[:, :G, :]), enc_c[:, :G, :]
         if c.perm is not None and not self._want_prediction_only:
-            processed = processed.index_select(1, c.perm[1].to(processed.device))  # callers see reference row order
+            # callers see reference row order; the device copy of the row map is made once, so that a call inside a
+            # hipGraph capture (the ROI head's TrainStep runs this forward) issues no host-to-device copy
+            pos_dev = getattr(c, "perm_pos_dev", None)
+            if pos_dev is None or pos_dev.device != processed.device:
+                pos_dev = c.perm_pos_dev = c.perm[1].to(processed.device)
+            processed = processed.index_select(1, pos_dev)
         if squeeze:
             return out[0], grid_lat[0], processed[0]
         return out, grid_lat, processed

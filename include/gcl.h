@@ -443,6 +443,30 @@ int gcl_gather2_rows(const float* a, int64_t lda, int64_t bsa, const int32_t* ma
                      int64_t ldb, int64_t bsb, const int32_t* map_b, float* dst, int64_t ldd, int64_t bsd,
                      int32_t B, int32_t nd, int32_t F, int32_t sum_batch, gcl_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * ROI residual head (src/roi_residual.py): glue around the dense layers and the InteractionNet
+ * processor of the correction head.
+ * ------------------------------------------------------------------------------------------- */
+/* Row gather from up to three sources into one zero-padded row (src/roi_residual.py:165-169, the
+ * `torch.cat([X[roi], latent[roi], pred[roi]])` that builds the head's skip input):
+ *   dst[b, i, :] = [s0[b, g, :w0] | s1[b, g, :w1] | s2[b, g, :w2] | 0 ...]  for i < n, g = rows[i]
+ * (rows NULL: g = i), Fp columns in all, Fp % 4 == 0 (the dense kernels read 16-byte rows).  Each
+ * source has its own row stride ld* and batch stride bs* (0 broadcasts), so a column block of a
+ * wider tensor - the encoder's grid latents inside the compact pipeline's output - is read in place;
+ * a source with width 0 is unused (may be NULL).  An index outside [0, rows_src) gives a zero row.
+ * With one source this is also the backward of gcl_roi_compose: d_corr[b, i] = d_out[b, roi[i]]. */
+int gcl_roi_gather_rows(const int32_t* rows, int32_t n, int32_t rows_src, const float* s0, int64_t ld0,
+                        int64_t bs0, int32_t w0, const float* s1, int64_t ld1, int64_t bs1, int32_t w1,
+                        const float* s2, int64_t ld2, int64_t bs2, int32_t w2, float* dst, int64_t ldd,
+                        int64_t bsd, int32_t Fp, int32_t B, gcl_stream_t stream);
+/* Output composition (src/roi_residual.py:183-185, `pred + zeros_like(pred).index_add(0, roi, corr)`):
+ *   out[b, g, :] = pred[b, g, :] + corr[b, pos[g], :]  where pos[g] >= 0 (g is ROI row pos[g]),
+ *   out[b, g, :] = pred[b, g, :]                        elsewhere (a copy: bit-equal to pred).
+ * pos is an int32 device array of length G (the inverse of the ROI index list, -1 outside). */
+int gcl_roi_compose(const float* pred, int64_t ldp, int64_t bsp, const float* corr, int64_t ldc, int64_t bsc,
+                    const int32_t* pos, float* out, int64_t ldo, int64_t bso, int32_t B, int32_t G, int32_t C,
+                    gcl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
