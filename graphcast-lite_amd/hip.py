@@ -99,6 +99,10 @@ _SIGNATURES = {
     "gcl_gather2_rows": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp]),
     "gcl_roi_gather_rows": (C.c_int, [_vp, _i32, _i32] + [_vp, _i64, _i64, _i32] * 3 + [_vp, _i64, _i64, _i32, _i32, _vp]),
     "gcl_roi_compose": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _vp]),
+    "gcl_segment_wsum": (C.c_int, [_vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _i64, _i32,
+                                   _i32, _i32, _i32, _vp]),
+    "gcl_cross_update_fwd": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _i32, _i32,
+                                       _i32, _vp]),
 }
 
 
@@ -724,6 +728,42 @@ def roi_compose(pred3, corr3, pos, out=None):
     _check(lib().gcl_roi_compose(_p(pred3), pred3.stride(1), pred3.stride(0), _p(corr3), corr3.stride(1), corr3.stride(0),
                                  _pi(pos), _p(out), out.stride(1), out.stride(0), B, G, Cc, _stream()))
     return out
+
+
+def segment_wsum(src3, idx, w, rowptr, out3=None, addend3=None, act=ACT_NONE, accumulate: bool = False):
+    """out3[b, i] (+)= addend3[b, i] + sum_k w[k] act(src3[b, idx[k]]) over k in [rowptr[i], rowptr[i+1]) (see
+    gcl_segment_wsum).  src3 [B | 1, n_src, >= D] (batch 1 broadcasts), out3 / addend3 [B, n, D]: unit channel stride,
+    any row / batch stride (out3 may be a column block).  idx / rowptr int32, w float32 (None: idx = k, w = 1)."""
+    n = rowptr.numel() - 1
+    if out3 is None:
+        B = src3.shape[0] if addend3 is None else addend3.shape[0]
+        D = src3.shape[2] if addend3 is None else addend3.shape[2]
+        out3 = torch.empty(B, n, D, dtype=torch.float32, device=src3.device)
+    B, _, D = out3.shape
+    assert out3.shape[1] == n and src3.stride(2) == 1 and out3.stride(2) == 1 and src3.shape[2] >= D
+    assert src3.shape[0] in (1, B) and (addend3 is None or (addend3.shape == out3.shape and addend3.stride(2) == 1))
+    assert w is None or (w.is_cuda and w.dtype == torch.float32 and w.is_contiguous())
+    _check(lib().gcl_segment_wsum(_p(src3), src3.stride(1), src3.stride(0) if src3.shape[0] > 1 else 0, src3.shape[1],
+                                  int(act), _pi(idx), w.data_ptr() if w is not None else None, _pi(rowptr), _p(addend3),
+                                  addend3.stride(1) if addend3 is not None else 0,
+                                  addend3.stride(0) if addend3 is not None else 0, _p(out3), out3.stride(1),
+                                  out3.stride(0), 1 if accumulate else 0, B, n, D, _stream()))
+    return out3
+
+
+def cross_update_fwd(h3, msg3, rowptr, gamma, beta, eps=1e-5):
+    """(pre [B, n, D], y [B, n, D], stats [B * n, 2]): pre = h + per-receiver mean of msg rows (receiver-sorted, CSR
+    rowptr), y = node LayerNorm of pre (see gcl_cross_update_fwd)."""
+    B, n, D = h3.shape
+    assert h3.stride(2) == 1 and msg3.stride(2) == 1 and msg3.shape[0] == B and msg3.shape[2] == D
+    assert rowptr.numel() == n + 1
+    pre = torch.empty(B, n, D, dtype=torch.float32, device=h3.device)
+    y = torch.empty(B, n, D, dtype=torch.float32, device=h3.device)
+    stats = torch.empty(B * n, 2, dtype=torch.float32, device=h3.device)
+    _check(lib().gcl_cross_update_fwd(_p(h3), h3.stride(1), h3.stride(0), _p(msg3), msg3.stride(1), msg3.stride(0),
+                                      _pi(rowptr), _p(gamma), _p(beta), float(eps), _p(pre), _p(y), _p(stats), B, n, D,
+                                      _stream()))
+    return pre, y, stats
 
 
 def ar_advance(state4, delta3, y_step3, chan_kind, out3, out_off: int, residual: bool):

@@ -467,6 +467,34 @@ int gcl_roi_compose(const float* pred, int64_t ldp, int64_t bsp, const float* co
                     const int32_t* pos, float* out, int64_t ldo, int64_t bso, int32_t B, int32_t G, int32_t C,
                     gcl_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Dual-mesh regional model (src/dual_mesh.py): glue around the dense layers and the shared-step
+ * InteractionNet processor of the regional module.
+ * ------------------------------------------------------------------------------------------- */
+/* Weighted segment sum over a CSR (the RegionalEncoder mean, src/dual_mesh.py:421-425, and the
+ * RegionalDecoder inverse-distance sum, src/dual_mesh.py:464-468; their backward through the
+ * transposed CSR with the same weights):
+ *   out[b, i, :] (+)= addend[b, i, :] + sum_{k in [rowptr[i], rowptr[i+1])} w[k] * act(src[b, idx[k], :])
+ * idx NULL: k itself; w NULL: weight 1; addend NULL: none; accumulate != 0 adds to out.  act is
+ * GCL_ACT_NONE or GCL_ACT_SILU (applied to the source row as it is read).  An empty segment gives
+ * the addend (or 0).  src, addend and out have unit channel stride and any 16-B aligned row / batch
+ * stride, so out may be a column block of a wider row.  An index outside [0, n_src) contributes
+ * nothing.  D % 4 == 0. */
+int gcl_segment_wsum(const float* src, int64_t ld_src, int64_t bs_src, int32_t n_src, int32_t act,
+                     const int32_t* idx, const float* w, const int32_t* rowptr, const float* addend,
+                     int64_t ld_add, int64_t bs_add, float* out, int64_t ld_out, int64_t bs_out,
+                     int32_t accumulate, int32_t B, int32_t n, int32_t D, gcl_stream_t stream);
+/* Cross-message node update, global -> regional (src/dual_mesh.py:356-357,786-787):
+ *   pre[b, i, :] = h[b, i, :] + (1 / deg_i) sum_{k in [rowptr[i], rowptr[i+1])} msg[b, k, :]  (0 for deg 0)
+ *   y[b, i, :]   = LayerNorm_node(pre[b, i, :]) * gamma + beta,  stats[b * n + i] = (mean, rstd)
+ * msg rows are the cross edges in receiver-sorted (CSR) order.  pre, y are dense [B, n, D], stats
+ * [B * n, 2]; D % 4 == 0, D <= 256.  The backward is gcl_layernorm_bwd with x = pre, then
+ * d msg[k] = d pre[rcv_k] / deg (gcl_edge_combine). */
+int gcl_cross_update_fwd(const float* h, int64_t ld_h, int64_t bs_h, const float* msg, int64_t ld_msg,
+                         int64_t bs_msg, const int32_t* rowptr, const float* gamma, const float* beta,
+                         float eps, float* pre, float* y, float* stats, int32_t B, int32_t n, int32_t D,
+                         gcl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
