@@ -103,6 +103,15 @@ _SIGNATURES = {
                                    _i32, _i32, _i32, _vp]),
     "gcl_cross_update_fwd": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _i32, _i32,
                                        _i32, _vp]),
+    "gcl_nudge": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _f32, _f32, _i32, _vp, _i64, _i64, _i32, _i32, _i32,
+                            _vp]),
+    "gcl_oi_max_stations": (C.c_int, []),
+    "gcl_oi_station_cov": (C.c_int, [_vp, _vp, _i32, C.c_double, C.c_double, C.c_double, _vp, _vp]),
+    "gcl_oi_factor": (C.c_int, [_vp, _i32, _vp]),
+    "gcl_oi_solve": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _i32, _vp]),
+    "gcl_oi_innovation": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp]),
+    "gcl_oi_analysis": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp,
+                                  _vp, _i32, _f32, _f32, _f32, _f32, _i32, _vp]),
 }
 
 
@@ -930,3 +939,72 @@ def gcn_layer_fwd_tab(graph: Graph, x3, tab, act, slope, W, bias):
                                        _stream()))
     _probe_end(tok)
     return out[..., :Fout]
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# Data assimilation (csrc/assim.hip)
+# ------------------------------------------------------------------------------------------------------------------
+def _pd(t: torch.Tensor):
+    assert t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()
+    return t.data_ptr()
+
+
+def nudge(f3, o3, out3, c0: float, c1: float, form: int, chan_mask=None):
+    """out3 = nudged f3 (see gcl_nudge).  f3, o3, out3: [B, G, C] views with unit channel stride; chan_mask: uint8 [C]
+    device tensor or None.  out3 may be f3."""
+    B, G, Cc = f3.shape
+    assert o3.shape == f3.shape and out3.shape == f3.shape
+    assert f3.stride(2) == 1 and o3.stride(2) == 1 and out3.stride(2) == 1
+    if chan_mask is not None:
+        assert chan_mask.is_cuda and chan_mask.dtype == torch.uint8 and chan_mask.numel() == Cc
+    _check(lib().gcl_nudge(_p(f3), f3.stride(1), f3.stride(0), _p(o3), o3.stride(1), o3.stride(0),
+                           chan_mask.data_ptr() if chan_mask is not None else None, float(c0), float(c1), int(form),
+                           _p(out3), out3.stride(1), out3.stride(0), B, G, Cc, _stream()))
+    return out3
+
+
+def oi_max_stations() -> int:
+    return int(lib().gcl_oi_max_stations())
+
+
+def oi_factor(lat, lon, sb2: float, rl2: float, diag: float):
+    """float64 [m, m] factor of the station covariance of stations (lat, lon) (float64 radians, device)."""
+    m = lat.numel()
+    M = torch.empty(m, m, dtype=torch.float64, device=lat.device)
+    _check(lib().gcl_oi_station_cov(_pd(lat), _pd(lon), m, float(sb2), float(rl2), float(diag), M.data_ptr(), _stream()))
+    _check(lib().gcl_oi_factor(M.data_ptr(), m, _stream()))
+    return M
+
+
+def oi_solve(M, rhs, tmp, W):
+    """W [n, m] float32 = S^-1 rhs for rhs [n, m] float64 (tmp: float64 workspace of the same shape)."""
+    m = M.shape[0]
+    n = rhs.shape[0]
+    assert rhs.shape == (n, m) and tmp.shape == (n, m) and W.shape == (n, m) and W.is_contiguous()
+    _check(lib().gcl_oi_solve(_pd(M), m, _pd(rhs), _pd(tmp), _p(W), n, _stream()))
+    return W
+
+
+def oi_innovation(obs3, xb3, obs_row, node_row, chans, rhs):
+    """rhs[b * nch + q, k] = obs3[b, obs_row[k], chans[q]] - xb3[b, node_row[k], chans[q]] (float64)."""
+    B = xb3.shape[0]
+    m, nch = obs_row.numel(), chans.numel()
+    assert obs3.shape[0] == B and obs3.stride(2) == 1 and xb3.stride(2) == 1 and rhs.shape == (B * nch, m)
+    _check(lib().gcl_oi_innovation(_p(obs3), obs3.stride(1), obs3.stride(0), _p(xb3), xb3.stride(1), xb3.stride(0),
+                                   _pi(obs_row), _pi(node_row), _pi(chans), m, nch, B, _pd(rhs), _stream()))
+    return rhs
+
+
+def oi_analysis(xb3, xa3, chans, node_row, nodes, stations, W, sb2: float, rl2: float, th_cut: float, a_cut: float):
+    """xa3[b, node_row[i], chans[q]] = xb3[...] + sum_k sb2 K(i, k) W[b * nch + q, k] (see gcl_oi_analysis).
+    nodes / stations: (lat f64, lon f64, cos(lat) f32) device triples."""
+    B = xb3.shape[0]
+    nlat, nlon, ncos = nodes
+    slat, slon, scos = stations
+    m, nch = slat.numel(), chans.numel()
+    assert xb3.stride(2) == 1 and xa3.stride(2) == 1 and W.shape == (B * nch, m) and W.is_contiguous()
+    _check(lib().gcl_oi_analysis(_p(xb3), xb3.stride(1), xb3.stride(0), _p(xa3), xa3.stride(1), xa3.stride(0),
+                                 _pi(chans), nch, _pi(node_row), _pd(nlat), _pd(nlon), _p(ncos), nlat.numel(),
+                                 _pd(slat), _pd(slon), _p(scos), _p(W), m, float(sb2), float(rl2), float(th_cut),
+                                 float(a_cut), B, _stream()))
+    return xa3

@@ -495,6 +495,52 @@ int gcl_cross_update_fwd(const float* h, int64_t ld_h, int64_t bs_h, const float
                          float eps, float* pre, float* y, float* stats, int32_t B, int32_t n, int32_t D,
                          gcl_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Data assimilation (src/assimilation/): nudging and matrix-free optimal interpolation (OI).
+ * ------------------------------------------------------------------------------------------- */
+/* Nudging blend (src/assimilation/nudging.py:87-92 NudgingAssimilator.apply, form 0, and :201-206
+ * nudge_sequence_offline, form 1):
+ *   out[b, g, c] = f + c1 (o - f)   (form 0)  or  c0 f + c1 o   (form 1)   where o = obs[b, g, c] is
+ *   not NaN and chan_mask[c] != 0 (chan_mask NULL: every channel);  out = f elsewhere.
+ * float32 with one rounding per operation, no FMA: bit-equal to torch CPU for c0 = fl32(1 - alpha),
+ * c1 = fl32(alpha).  Strided [B, G, C] views (unit channel stride); out may alias f. */
+int gcl_nudge(const float* f, int64_t ldf, int64_t bsf, const float* obs, int64_t ldo, int64_t bso,
+              const uint8_t* chan_mask, float c0, float c1, int32_t form, float* out, int64_t ldt,
+              int64_t bst, int32_t B, int32_t G, int32_t C, gcl_stream_t stream);
+/* Largest station count the OI factor accepts. */
+int gcl_oi_max_stations(void);
+/* OI station covariance (the `H @ B @ H.T + R + 1e-5 I` of src/assimilation/optimal_interpolation.py:
+ * 120-126, built from coordinates instead of B): S[a, b] = sb2 exp(-rl2 theta_ab^2) + (a == b) diag,
+ * float64 row-major m x m, theta the haversine angle of stations a, b (lat / lon in radians). */
+int gcl_oi_station_cov(const double* lat, const double* lon, int32_t m, double sb2, double rl2,
+                       double diag, double* S, gcl_stream_t stream);
+/* In-place factor of S (m x m, float64) for gcl_oi_solve (replaces the per-channel
+ * `torch.linalg.inv` of optimal_interpolation.py:122-124): root-free Cholesky S = U^T D U with the
+ * unit factor inverted during the elimination; M then holds D on the diagonal, X = U^-T in the strict
+ * lower triangle and X^T in the strict upper one.  m launches; no pivoting (S is SPD by construction). */
+int gcl_oi_factor(double* M, int32_t m, gcl_stream_t stream);
+/* W = S^-1 rhs = X^T D^-1 X rhs (optimal_interpolation.py:125-128, K @ innovation without K):
+ * rhs, tmp float64 [n][m], W float32 [n][m] (station index contiguous).  Each column is independent
+ * of the others and of n. */
+int gcl_oi_solve(const double* M, int32_t m, const double* rhs, double* tmp, float* W, int32_t n,
+                 gcl_stream_t stream);
+/* Innovation gather (optimal_interpolation.py:127, `y_obs_val - H @ x_b`):
+ *   rhs[b * nch + q][k] = obs[b, obs_row[k], chans[q]] - x_b[b, node_row[k], chans[q]]  (float64). */
+int gcl_oi_innovation(const float* obs, int64_t ldo, int64_t bso, const float* xb, int64_t ldx,
+                      int64_t bsx, const int32_t* obs_row, const int32_t* node_row, const int32_t* chans,
+                      int32_t m, int32_t nch, int32_t B, double* rhs, gcl_stream_t stream);
+/* OI analysis (optimal_interpolation.py:128 and :143, `x_b + K @ innovation` with B's columns
+ * evaluated from coordinates): for every OI node i (grid row node_row[i], NULL: i) and column
+ * col = b * nch + q,
+ *   xa[b, row, chans[q]] = xb[b, row, chans[q]] + sum_k sb2 exp(-rl2 theta_ik^2) W[col][k]
+ * in float32; pairs with |dlat| > th_cut or haversine a > a_cut contribute 0 (their weight underflows).
+ * Only those entries are written: the caller copies the rest when xa != xb (xa may alias xb). */
+int gcl_oi_analysis(const float* xb, int64_t ldx, int64_t bsx, float* xa, int64_t lda, int64_t bsa,
+                    const int32_t* chans, int32_t nch, const int32_t* node_row, const double* nlat,
+                    const double* nlon, const float* ncos, int32_t n_nodes, const double* slat,
+                    const double* slon, const float* scos, const float* W, int32_t m, float sb2, float rl2,
+                    float th_cut, float a_cut, int32_t B, gcl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
