@@ -967,7 +967,7 @@ static int halo_layer_launch(const gcl_graph_t* g, const float* x, int64_t ldx, 
   *launched = false;
   const int32_t n = g->n;
   const int halo_on = env_int("GCL_GCN_HALO", 1);  // read per call: the parity test compares the two kernels
-  static const int x3_on = env_int("GCL_X3", 1) && env_int("GCL_X3_GCN", 1);
+  const int x3_on = env_int("GCL_X3", 1) && env_int("GCL_X3_GCN", 1);  // per call, as in gcl_gcn_layer_fwd_tab_ok
   const gcl_halo& hl = g->halo[0][0];
   const int hp4 = hl.T == 64 ? (int)gcl::cdiv((hl.smax - 64) / 4, 4) : 99;
   const int KPh = Fin + 2;
@@ -977,7 +977,8 @@ static int halo_layer_launch(const gcl_graph_t* g, const float* x, int64_t ldx, 
                            : ((int64_t)n * ldx * 4 < ((int64_t)1 << 31));
   // only where the gather is the bulk of the layer (>= 6 edges per row: the mesh graph has 7.4): on the decoder graph
   // of the 512x256 configs (3.3 edges per row) the per-edge kernel's twelve wave-independent pipelines run 1.6x faster
-  if (!(halo_on && x3_on && g->kind == GCL_GRAPH_GCN && hl.T == 64 && hp4 <= 8 && Fin % 16 == 0 && Fin > 32 && rows_out == n &&
+  // heavy rows (> kHeavy in-edges) have no records in the tile layout (build_halo_host): never this kernel
+  if (!(halo_on && x3_on && g->kind == GCL_GRAPH_GCN && g->n_heavy == 0 && hl.T == 64 && hp4 <= 8 && Fin % 16 == 0 && Fin > 32 && rows_out == n &&
         g->e >= 6 * (int64_t)n && ldsh <= 80 * 1024 && offs_ok && n < (1 << 24) && ldx * 4 < (1 << 24) &&
         (int64_t)n * ldy * 4 < ((int64_t)1 << 31)))
     return GCL_OK;
@@ -998,7 +999,7 @@ static int halo_layer_launch(const gcl_graph_t* g, const float* x, int64_t ldx, 
   // hp4 <= 4 (the icosphere meshes: <= 64 halo rows per tile): non-temporal stores straight from the accumulator and
   // the next item's DMA pieces issued between the k-steps of the dense part (in the step 111.5 -> 102.6 us per mesh
   // layer; GCL_GCN_HALO_FORM=0 selects the first form - DMA issue up front, staged 16-byte stores - for comparison)
-  static const int form_env = env_int("GCL_GCN_HALO_FORM", 1);
+  const int form_env = env_int("GCL_GCN_HALO_FORM", 1);
   if (tab)
     rc = act == GCL_ACT_PRELU  ? go(&gcn_halo_fwd_kernel<gcl::kActPrelu, 4, 2, true, true, true>)
          : act == GCL_ACT_SILU ? go(&gcn_halo_fwd_kernel<gcl::kActSilu, 4, 2, true, true, true>)
@@ -1058,7 +1059,7 @@ extern "C" int gcl_gcn_layer_fwd_rows(const gcl_graph_t* g, const float* x, int6
   const int NS = Fout_store > 32 ? 2 : 1;
   constexpr int NW12 = 12, NW8 = 8;
   const int KP = Fin + 2;
-  static const int x3_env = env_int("GCL_X3", 1) && env_int("GCL_X3_GCN", 1);
+  const int x3_env = env_int("GCL_X3", 1) && env_int("GCL_X3_GCN", 1);
   const size_t wave1_b = (size_t)wave_region_f(32 * (KP > NS * 32 ? KP : NS * 32)) * sizeof(float);
   // the split-operand variant holds its A fragments in registers: 8 waves per block (256 VGPRs each) instead of 12
   const bool x3 = x3_env != 0 && (Fin % 16 == 0);
@@ -1149,6 +1150,11 @@ extern "C" int gcl_gcn_layer_fwd_tab(const gcl_graph_t* g, const float* x, int64
   const int rc = halo_layer_launch(g, x, ldx, bsx, tab, x_rows, act, slope, W, bias, y, ldy, bsy, B, Fin, Fout, Fout_store,
                                    g->n, (hipStream_t)stream, &launched);
   if (rc) return rc;
+  if (!launched && g->n_heavy) {
+    gcl::set_error("gcn_layer_fwd_tab: the graph has %d heavy rows (more than %d in-edges), which the source-tile form "
+                   "does not compute", g->n_heavy, gcl::kHeavy);
+    return GCL_EUNSUPPORTED;
+  }
   if (!launched) {
     gcl::set_error("gcn_layer_fwd_tab: this graph / shape has no source-tile form (Fin=%d Fout=%d)", Fin, Fout);
     return GCL_EUNSUPPORTED;
@@ -1159,7 +1165,7 @@ extern "C" int gcl_gcn_layer_fwd_tab(const gcl_graph_t* g, const float* x, int64
 extern "C" int gcl_gcn_layer_fwd_tab_ok(const gcl_graph_t* g, int64_t ldx, int64_t bsx, int64_t x_rows, int32_t B,
                                         int32_t Fin, int32_t Fout) {
   if (!g || g->kind != GCL_GRAPH_GCN || g->n_heavy) return 0;
-  static const int x3_on = env_int("GCL_X3", 1) && env_int("GCL_X3_GCN", 1);
+  const int x3_on = env_int("GCL_X3", 1) && env_int("GCL_X3_GCN", 1);
   const gcl_halo& hl = g->halo[0][0];
   if (!env_int("GCL_GCN_HALO", 1) || !x3_on || hl.T != 64) return 0;
   const int hp4 = (int)gcl::cdiv((hl.smax - 64) / 4, 4);

@@ -399,7 +399,8 @@ extern "C" int gcl_graph_create(const int64_t* ei, int64_t E, int32_t n, int32_t
   // processing order of the per-edge kernels: only where one sample's rows cannot sit in an XCD's 4 MiB L2 anyway
   // (>= 32 Ki rows: 16 MB at 128 channels) and the graph has no source-tile layout
   {
-    static const int ord_env = [] { const char* e = getenv("GCL_AGG_ORDER"); return e ? atoi(e) : 1; }();
+    const char* oe = getenv("GCL_AGG_ORDER");  // read per graph (the dispatch tests build one graph each way)
+    const int ord_env = oe ? atoi(oe) : 1;
     if (!rc && ord_env && n >= 32768) {
       for (int d = 0; d < 2 && !rc; ++d) {
         if (g->halo[d][0].T) continue;
@@ -428,7 +429,7 @@ extern "C" int gcl_graph_halo_info(const gcl_graph_t* g, int32_t transpose, int3
   out4[0] = h.T;
   out4[1] = h.ntiles;
   out4[2] = h.smax;
-  out4[3] = 0;
+  out4[3] = g->order16[transpose ? 1 : 0] ? 1 : 0;
   return GCL_OK;
 }
 extern "C" int gcl_graph_export_edges(const gcl_graph_t* g, int64_t* out) {

@@ -1285,10 +1285,8 @@ int launch_linear(const float* X, int64_t ldx, const float* in_slope, const floa
 // K: contraction length, N: output width.  Measured on MI355X (tools/gemm_bench.py): the 128x128
 // tile kernel wins once the contraction is long or the output fills its 128 columns.
 bool panel_fits(int K, int N, bool vec_x, bool trans, bool w_ok) {
-  static const int impl = [] {
-    const char* e = getenv("GCL_DENSE_IMPL");
-    return !e ? 0 : strcmp(e, "tile") == 0 ? 1 : strcmp(e, "panel") == 0 ? 2 : 0;
-  }();
+  const char* ie = getenv("GCL_DENSE_IMPL");  // read per call (the dispatch tests switch it)
+  const int impl = !ie ? 0 : strcmp(ie, "tile") == 0 ? 1 : strcmp(ie, "panel") == 0 ? 2 : 0;
   const bool tile_ok = vec_x && w_ok && K % 4 == 0 && N % 4 == 0;
   if (impl == 1 && tile_ok) return false;
   if (impl == 0 && tile_ok && (K > 128 || (N >= 128 && (K >= 128 || trans)))) return false;
@@ -1311,8 +1309,8 @@ int launch_gemm(const float* X, int64_t ldx, int akind, const float* slope, cons
   GCL_CHECK_ARG((ldw % 4 == 0) && gcl::aligned16(W) && (!trans || N % 4 == 0), "dense: wide shapes need a 16-B aligned weight block (ldw=%lld N=%d)", (long long)ldw, N);
   GtGeom g = gt_geom(rows, N);
   // split-operand bf16 variant (gemm_tile_x3_kernel): non-transposed weights, 128-row tiles
-  static const int x3_tile = [] { const char* e = getenv("GCL_X3"); const char* f = getenv("GCL_X3_TILE");
-                                  return ((e && atoi(e) == 0) || (f && atoi(f) == 0)) ? 0 : 1; }();
+  const int x3_tile = [] { const char* e = getenv("GCL_X3"); const char* f = getenv("GCL_X3_TILE");  // read per call
+                           return ((e && atoi(e) == 0) || (f && atoi(f) == 0)) ? 0 : 1; }();
   if (x3_tile && !trans && g.mi == 2) {
     auto kern = gemm_tile_x3_kernel<EPI>;
     { const int lrc_ = gcl::ensure_dyn_lds((const void*)kern, 160 * 1024); if (lrc_) return lrc_; }
@@ -1553,11 +1551,8 @@ extern "C" int gcl_linear_bwd_dw(const float* dy, int64_t lddy, const float* x, 
 // Fused path geometry / workspace (see linear_bwd_fused_kernel)
 static bool fused_ok(const float* dy, int64_t lddy, const float* x, int64_t ldx, const float* dx, int64_t lddx,
                      int32_t Fin, int32_t Fout) {
-  static int off = -1;
-  if (off < 0) {
-    const char* e = getenv("GCL_NO_FUSED_BWD");
-    off = (e && atoi(e) != 0) ? 1 : 0;
-  }
+  const char* e = getenv("GCL_NO_FUSED_BWD");  // read per call (the dispatch tests switch it)
+  const int off = (e && atoi(e) != 0) ? 1 : 0;
   if (off || use_valu()) return false;
   // Fout need not be a multiple of 4 when the rows of dy are padded to one (lddy >= roundup(Fout, 4)): the 16-byte
   // loads then also fetch the padding columns, which meet zero weight rows (they must hold finite values)
@@ -1604,7 +1599,7 @@ static int bwd_all_impl(const float* dy, int64_t lddy, const float* W, const flo
   }
   const int NO = (Fout + 31) / 32, NC = (Fin + 31) / 32;
   const int FoP = NO * 32, FiP = NC * 32;
-  static const int no64 = [] { const char* e = getenv("GCL_NO_FUSED64"); return (e && atoi(e)) ? 1 : 0; }();
+  const int no64 = [] { const char* e = getenv("GCL_NO_FUSED64"); return (e && atoi(e)) ? 1 : 0; }();  // read per call
   const bool use64 = (NC == 2) && !no64;  // 64-row tiles, 3 blocks per CU
   // split-operand bf16 kernel (x3.h): same partial records, two blocks per CU
   const bool use_x3 = use64 && gcl::x3_linear_bwd_applicable(dy, lddy, x, ldx, dx, lddx, Fin, Fout);

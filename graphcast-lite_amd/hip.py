@@ -218,6 +218,12 @@ class Graph:
         _check(lib().gcl_graph_halo_info(self._h, 1 if transpose else 0, T, out))
         return (out[0], out[1], out[2]) if out[0] else None
 
+    def row_group_order(self, transpose: bool = False) -> bool:
+        """Do the per-edge aggregation kernels of this direction walk 16-row groups in a processing order (order16)?"""
+        out = (C.c_int32 * 4)()
+        _check(lib().gcl_graph_halo_info(self._h, 1 if transpose else 0, 64, out))
+        return bool(out[3])
+
     def edges_with_loops(self, device) -> torch.Tensor:
         key = str(torch.device(device))
         t = self._exported.get(key)

@@ -643,6 +643,13 @@ class WeatherPrediction(nn.Module):
             return c[2]
         order, _ = self._mesh_order()
         ref = order.to(tiled.device)[tiled]
+        # the list ends with the self-loops in tile order; the reference's ends with them ascending in node id
+        # (src/models.py:143-149): keep the prefix, sort the trailing run of loops by node id (no host sync)
+        E = ref.shape[1]
+        trail = (ref[0] == ref[1]).to(torch.int32).flip(0).cumprod(0).flip(0).bool()
+        col = torch.arange(E, device=ref.device)
+        key = torch.where(trail, (E - trail.sum()) + ref[0], col)
+        ref = ref[:, torch.argsort(key, stable=True)]
         self._proc_tiled = ((id(ref), ref._version), tiled, ref)
         return ref
 

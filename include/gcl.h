@@ -83,7 +83,8 @@ int gcl_graph_export_edges(const gcl_graph_t* g, int64_t* edge_index_out);
 const int32_t* gcl_graph_eperm_device(const gcl_graph_t* g);
 /* Source-tile ("halo") layout of one direction (transpose != 0: sender-sorted) for tile height T (64 or 32):
  * out4 = {T (0 when that layout was not built), tiles, largest staged source count per tile (rounded up to 8),
- * 0}.  gcl_graph_create builds it when a tile's edges share their sources well enough (>= 1.6 reads per staged
+ * 1 when the per-edge kernels of this direction run their 16-row groups in a processing order (GCL_AGG_ORDER, n >= 32768
+ * and no source-tile layout; independent of T) else 0}.  gcl_graph_create builds it when a tile's edges share their sources well enough (>= 1.6 reads per staged
  * row) - e.g. mesh nodes numbered tile by tile; gcl_aggregate then stages every source row of a tile once in
  * LDS instead of gathering it once per edge (the propagate of src/models.py:419). */
 int gcl_graph_halo_info(const gcl_graph_t* g, int32_t transpose, int32_t T, int32_t* out4);
