@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from . import hip
-from .predict import channel_kinds
+from .predict import CapturedRollout, channel_kinds
 
 EARTH_RADIUS_M = 6371000.0
 
@@ -475,59 +475,19 @@ def assimilated_rollout(model, X: torch.Tensor, ar_steps: int, obs: torch.Tensor
     return out[0] if squeeze else out
 
 
-class CapturedAssimilatedRollout:
-    """`assimilated_rollout` replayed from a hipGraph, following `predict.CapturedRollout`: two eager calls per input
-    signature (workspaces, graph handles, allocator pools), the third captures, later calls copy the inputs into the
-    captured buffers and replay."""
+class CapturedAssimilatedRollout(CapturedRollout):
+    """`assimilated_rollout` replayed from a hipGraph, as `predict.CapturedRollout` replays `rollout`."""
 
     def __init__(self, model, ar_steps: int, assimilator, k=None, static_channels=None, forcing_channels=None,
                  use_residual: bool = True):
-        self.model, self.ar_steps, self.assimilator, self.k = model, ar_steps, assimilator, k
-        self.static_channels, self.forcing_channels, self.use_residual = static_channels, forcing_channels, use_residual
-        self._sig, self._graph, self._calls, self.enabled = None, None, 0, True
-        self._kinds = None
+        super().__init__(model, ar_steps, static_channels, forcing_channels, use_residual)
+        self.assimilator, self.k = assimilator, k
 
-    def _eager(self, X, obs, y):
-        C = X.shape[-1] // self.model.obs_window
-        if self._kinds is None or self._kinds.numel() != C or self._kinds.device != X.device:
-            self._kinds = channel_kinds(C, self.static_channels, self.forcing_channels, X.device)
+    def _work(self, X, obs, y):
         return assimilated_rollout(self.model, X, self.ar_steps, obs, self.assimilator, k=self.k,
                                    use_residual=self.use_residual, static_channels=self.static_channels,
-                                   forcing_channels=self.forcing_channels, y=y, kinds=self._kinds)
+                                   forcing_channels=self.forcing_channels, y=y, kinds=self._channel_kinds(X))
 
     @torch.no_grad()
     def __call__(self, X: torch.Tensor, obs: torch.Tensor, y: Optional[torch.Tensor] = None) -> torch.Tensor:
-        if not self.enabled or getattr(self.model, "using_sparse_gat", False):
-            return self._eager(X, obs, y)
-        sig = (tuple(X.shape), tuple(obs.shape), None if y is None else tuple(y.shape))
-        if sig != self._sig:
-            self._sig, self._graph, self._calls = sig, None, 0
-        if self._graph is None:
-            if self._calls < 2:
-                self._calls += 1
-                return self._eager(X, obs, y)
-            try:
-                self._sX, self._sobs = X.clone(), obs.clone()
-                self._sy = y.clone() if y is not None else None
-                from . import models as _models
-
-                g = torch.cuda.CUDAGraph()
-                _models._graphs.pin = pinned = []
-                try:
-                    with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                        self._out = self._eager(self._sX, self._sobs, self._sy)
-                finally:
-                    _models._graphs.pin = None
-                self._graph, self._pinned = g, pinned
-            except Exception as e:  # capture is an optimisation, never a requirement
-                print(f"[CapturedAssimilatedRollout] hipGraph capture unavailable ({type(e).__name__}: "
-                      f"{str(e)[:200]}); staying eager", flush=True)
-                self.enabled, self._graph = False, None
-                torch.cuda.synchronize()
-                return self._eager(X, obs, y)
-        self._sX.copy_(X)
-        self._sobs.copy_(obs)
-        if y is not None:
-            self._sy.copy_(y)
-        self._graph.replay()
-        return self._out.clone()
+        return self._forecast(X, obs, y)

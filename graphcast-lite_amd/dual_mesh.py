@@ -39,7 +39,6 @@ What differs from the reference (new capability, nothing it computes changes):
   * `_get_global_latents` (src/dual_mesh.py:631-661) is not provided: nothing in the reference calls it, and
     `forward_with_latents` returns the same processed mesh latents.
 """
-import os
 import sys
 from typing import Tuple
 
@@ -49,6 +48,7 @@ import torch.nn as nn
 from scipy.spatial import cKDTree
 
 from . import hip
+from .capture import Captured, graph_enabled
 from .functional import InteractionNetFn, _Grads
 from .mesh import TriangularMesh, get_edges_from_faces, get_hierarchy_of_triangular_meshes_for_sphere
 from .models import InteractionNetLayer, InteractionNetProcessor, LayerNorm, _act_spec, _get_activation
@@ -606,7 +606,7 @@ class DualMeshModel(nn.Module):
         return out[0] if squeeze else out
 
 
-class DualMeshCachedStep:
+class DualMeshCachedStep(Captured):
     """One optimiser step of the reference's cached mode (scripts/train_dual_mesh.py:176-193): `forward_cached`, then
     `weighted_mse_loss(out_roi, y_roi, None)`, with `x_last_roi = roi_raw[..., -C:]` added to the output first when
     `use_residual`; backward and Adam over the regional parameters.  The global model never runs.
@@ -622,23 +622,9 @@ class DualMeshCachedStep:
         self.flat = FlatParams(model)
         self.opt = FusedAdam(self.flat, lr=lr)
         self.use_residual = use_residual
-        self._graph_required = use_graph is True
-        if use_graph is None:
-            use_graph = os.environ.get("GCL_NO_GRAPH", "0") in ("0", "")
-        self.use_graph = bool(use_graph)
-        self._graph, self._static, self._sloss, self._eager_calls, self.capture_error = None, None, None, 0, None
+        super().__init__(graph_enabled(use_graph), required=use_graph is True)
 
-    @property
-    def graph_active(self) -> bool:
-        return bool(self.use_graph and self._graph is not None)
-
-    @property
-    def launch_mode(self) -> str:
-        if self.graph_active:
-            return "hipGraph replay"
-        return "eager" + (f" (capture failed: {self.capture_error})" if self.capture_error else "")
-
-    def _fwd_bwd(self, roi_raw, pred, lat, cs, y):
+    def _work(self, roi_raw, pred, lat, cs, y):
         from .train import weighted_mse_loss
 
         self.flat.zero_grad()
@@ -648,49 +634,10 @@ class DualMeshCachedStep:
         x_last = r3[..., r3.shape[-1] - o3.shape[-1]:] if self.use_residual else None
         loss = weighted_mse_loss(o3, y3, x_last=x_last)
         loss.backward()
-        return loss.detach()
-
-    def _eager(self, args):
-        loss = self._fwd_bwd(*args)
         self.opt.step()
-        return loss
-
-    def _capture(self, args):
-        self._static = [a.clone() for a in args]
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, capture_error_mode="thread_local"):
-            self._sloss = self._fwd_bwd(*self._static)
-            self.opt.step()
-        self._graph = g
+        return loss.detach()
 
     def __call__(self, roi_raw, global_pred_roi, roi_grid_latent, cross_sender_feat, y_roi):
         dev = self.flat.flat.device
         args = [t.to(dev, torch.float32) for t in (roi_raw, global_pred_roi, roi_grid_latent, cross_sender_feat, y_roi)]
-        if not self.use_graph:
-            return self._eager(args)
-        if self._graph is None:
-            if self._eager_calls < 2:  # workspaces and kernel attributes get set up outside the capture
-                self._eager_calls += 1
-                return self._eager(args)
-            try:
-                self._capture(args)
-            except Exception as e:
-                self.capture_error = f"{type(e).__name__}: {str(e)[:300]}"
-                self.use_graph, self._graph = False, None
-                torch.cuda.synchronize()
-                if self._graph_required:
-                    raise RuntimeError(f"DualMeshCachedStep(use_graph=True): hipGraph capture failed "
-                                       f"({self.capture_error})") from e
-                import warnings
-
-                warnings.warn(f"[DualMeshCachedStep] hipGraph capture unavailable ({self.capture_error}); staying "
-                              f"eager (see .launch_mode / .graph_active)", RuntimeWarning)
-                return self._eager(args)
-            self._graph.replay()  # capture only records; the first replay performs this step
-            return self._sloss.detach()
-        if any(a.shape != s.shape for a, s in zip(args, self._static)):
-            return self._eager(args)
-        for a, s in zip(args, self._static):
-            s.copy_(a)
-        self._graph.replay()
-        return self._sloss.detach()
+        return self._run(*args).detach()

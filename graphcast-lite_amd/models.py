@@ -19,6 +19,7 @@ What is new relative to the reference (documented deviations, SURVEY.md Appendix
   * the three `summary()` forward passes of the constructor are skipped.
 Compute runs only on a GPU through `libgcl_hip.so`; there is no CPU path in this package.
 """
+import contextlib
 import math
 import os
 import sys
@@ -74,6 +75,15 @@ class _GraphCache:
         if len(self._d) > self._cap:
             self._d.popitem(last=False)
         return g
+
+    @contextlib.contextmanager
+    def pinning(self):
+        """`with _graphs.pinning() as pinned:` collects the handles looked up inside the block into `pinned`."""
+        self.pin = pinned = []
+        try:
+            yield pinned
+        finally:
+            self.pin = None
 
 
 _graphs = _GraphCache()

@@ -12,6 +12,7 @@ from typing import Optional, Sequence
 import torch
 
 from . import hip
+from .capture import Captured
 
 
 def channel_kinds(C: int, static_channels: Optional[Sequence[int]], forcing_channels: Optional[Sequence[int]], device):
@@ -54,59 +55,40 @@ def rollout(model, X: torch.Tensor, ar_steps: int, y: Optional[torch.Tensor] = N
     return out[0] if squeeze else out
 
 
-class CapturedRollout:
+class CapturedRollout(Captured):
     """`rollout` replayed from a hipGraph: the whole K-step autoregressive forecast (K model forwards
     + K window advances, a few hundred launches at batch 1) costs the host one graph launch.
 
     The first two calls for a given input signature run eagerly (graph handles, workspaces and
     allocator pools get set up), the third captures, later calls copy the inputs into the captured
-    buffers and replay.  Falls back to eager launches if capture is not possible."""
+    buffers and replay.  Falls back to eager launches if capture is not possible (see `.launch_mode`)."""
 
     def __init__(self, model, ar_steps: int, static_channels=None, forcing_channels=None, use_residual: bool = True):
         self.model, self.ar_steps = model, ar_steps
         self.static_channels, self.forcing_channels, self.use_residual = static_channels, forcing_channels, use_residual
-        self._sig, self._graph, self._sX, self._sy, self._out, self._calls, self.enabled = None, None, None, None, None, 0, True
         self._kinds = None
+        super().__init__(recapture=True)
 
-    def _eager(self, X, y):
+    enabled = property(lambda self: self.use_graph)  # False after a failed capture
+
+    def _channel_kinds(self, X):
+        """`channel_kinds`, uploaded once (outside the capture) and kept while X's channel count and device stay."""
         C = X.shape[-1] // self.model.obs_window
         if self._kinds is None or self._kinds.numel() != C or self._kinds.device != X.device:
             self._kinds = channel_kinds(C, self.static_channels, self.forcing_channels, X.device)
+        return self._kinds
+
+    def _work(self, X, y):
         return rollout(self.model, X, self.ar_steps, y=y, static_channels=self.static_channels,
-                       forcing_channels=self.forcing_channels, use_residual=self.use_residual, kinds=self._kinds)
+                       forcing_channels=self.forcing_channels, use_residual=self.use_residual,
+                       kinds=self._channel_kinds(X))
+
+    def _forecast(self, *args):
+        if getattr(self.model, "using_sparse_gat", False):
+            return self._work(*args)
+        out = self._run(*args)
+        return out.clone() if out is self._result else out  # the next replay overwrites the graph's output
 
     @torch.no_grad()
     def __call__(self, X: torch.Tensor, y: Optional[torch.Tensor] = None) -> torch.Tensor:
-        if not self.enabled or getattr(self.model, "using_sparse_gat", False):
-            return self._eager(X, y)
-        sig = (tuple(X.shape), None if y is None else tuple(y.shape))
-        if sig != self._sig:
-            self._sig, self._graph, self._calls = sig, None, 0
-        if self._graph is None:
-            if self._calls < 2:
-                self._calls += 1
-                return self._eager(X, y)
-            try:
-                self._sX = X.clone()
-                self._sy = y.clone() if y is not None else None
-                from . import models as _models
-
-                g = torch.cuda.CUDAGraph()
-                _models._graphs.pin = pinned = []  # keep the CSR handles of the captured kernels alive
-                try:
-                    with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                        self._out = self._eager(self._sX, self._sy)
-                finally:
-                    _models._graphs.pin = None
-                self._graph, self._pinned = g, pinned
-            except Exception as e:  # capture is an optimisation, never a requirement
-                print(f"[CapturedRollout] hipGraph capture unavailable ({type(e).__name__}: {str(e)[:200]}); staying eager",
-                      flush=True)
-                self.enabled, self._graph = False, None
-                torch.cuda.synchronize()
-                return self._eager(X, y)
-        self._sX.copy_(X)
-        if y is not None:
-            self._sy.copy_(y)
-        self._graph.replay()
-        return self._out.clone()
+        return self._forecast(X, y)

@@ -12,6 +12,7 @@ import torch
 import torch.distributed as dist
 
 from . import hip
+from .capture import Captured, graph_enabled
 from .functional import ARStepLossFn, WeightedMSEFn
 
 
@@ -360,7 +361,7 @@ class FusedAdam:
 _DEFER_REDUCTIONS = os.environ.get("GCL_NO_DEFER", "0") in ("0", "")
 
 
-class TrainStep:
+class TrainStep(Captured):
     """One optimiser step on a local batch: forward, loss, backward, [all-reduce], Adam.
 
     With `use_graph` (default) the launch-heavy part of the step - ~160 kernel launches - is captured
@@ -382,14 +383,9 @@ class TrainStep:
         self.static_channels, self.forcing_channels = static_channels, forcing_channels
         # use_graph=True: the caller REQUIRES the hipGraph path (a failed capture raises);
         # use_graph=None: replay when the capture works, fall back to eager launches with a warning
-        self._graph_required = use_graph is True
-        if use_graph is None:
-            use_graph = os.environ.get("GCL_NO_GRAPH", "0") in ("0", "")
-        self.use_graph = bool(use_graph)
+        super().__init__(graph_enabled(use_graph), required=use_graph is True)
         self._sparse = bool(getattr(model, "using_sparse_gat", False))
         self.split_finish = (world_size > 1) if split_finish is None else bool(split_finish or world_size > 1)
-        self._graph, self._sX, self._sy, self._sloss, self._eager_calls = None, None, None, None, 0
-        self.capture_error = None
         if world_size > 1:
             if not (dist.is_available() and dist.is_initialized()):
                 raise RuntimeError(f"TrainStep(world_size={world_size}) needs an initialised torch.distributed process group")
@@ -405,15 +401,10 @@ class TrainStep:
             dist.broadcast(t, src=0)
 
     @property
-    def graph_active(self) -> bool:
-        """True while steps are being replayed from a captured hipGraph."""
-        return bool(self.use_graph and self._graph is not None)
-
-    @property
     def launch_mode(self) -> str:
-        if self.graph_active:
-            return "hipGraph replay" + (" (fwd+bwd; all-reduce + Adam eager)" if self.split_finish else "")
-        return "eager" + (f" (capture failed: {self.capture_error})" if self.capture_error else "")
+        if self.graph_active and self.split_finish:
+            return "hipGraph replay (fwd+bwd; all-reduce + Adam eager)"
+        return super().launch_mode
 
     def _fwd_bwd(self, X, y, threshold=0.0, epoch=0, batch_num=1):
         self.flat.zero_grad()
@@ -444,69 +435,24 @@ class TrainStep:
         self._finish()
         return loss
 
-    def _capture(self, X, y):
-        self._sX, self._sy = X.clone(), y.clone()
-        from . import models as _models
-
-        g = torch.cuda.CUDAGraph()
-        _models._graphs.pin = pinned = []  # CSR handles the captured kernels point into
-        try:
-            # thread_local: other threads of the process (the RCCL watchdog) may touch the runtime meanwhile
-            with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                self._sloss = self._fwd_bwd(self._sX, self._sy)
-                if not self.split_finish:
-                    self._finish()
-        finally:
-            _models._graphs.pin = None
-        self._graph, self._pinned = g, pinned
-
-    def _replay(self):
-        self._graph.replay()
-        if self.split_finish:
-            self._finish()
-        return self._sloss.detach()
+    def _work(self, X, y, threshold=0.0, epoch=0, batch_num=1):
+        if self.split_finish:  # the all-reduce + Adam run after the replay, outside the graph
+            return self._fwd_bwd(X, y, threshold, epoch, batch_num)
+        return self._eager(X, y, threshold, epoch, batch_num)
 
     def __call__(self, X, y, threshold=0.0, epoch=0, batch_num=1):
-        if not self.use_graph:
-            return self._eager(X, y, threshold, epoch, batch_num)
         if self._sparse and batch_num == 0:
             # SparseGATConv prunes the mesh graph on this step (src/models.py:138-149): run it eagerly and
             # drop the captured graph, which was recorded over the old edge list; two eager steps follow so
             # that the CSR of the pruned list (and of its loop-completed form) exists before re-capturing
-            self._graph, self._eager_calls = None, 0
+            self.reset_graph()
             return self._eager(X, y, threshold, epoch, batch_num)
-        if self._graph is None:
-            # a few eager steps first: workspaces, CSR handles, kernel attributes and the RCCL
-            # communicator get set up outside the capture
-            if self._eager_calls < 2:
-                self._eager_calls += 1
-                return self._eager(X, y, threshold, epoch, batch_num)
-            try:
-                self._capture(X, y)
-            except Exception as e:
-                self.capture_error = f"{type(e).__name__}: {str(e)[:300]}"
-                self.use_graph, self._graph = False, None
-                torch.cuda.synchronize()
-                if self._graph_required:  # the caller asked for the graph path explicitly: no silent degradation
-                    raise RuntimeError(f"TrainStep(use_graph=True): hipGraph capture failed ({self.capture_error})") from e
-                import warnings
-
-                warnings.warn(f"[TrainStep] hipGraph capture unavailable ({self.capture_error}); staying eager "
-                              f"(see .launch_mode / .graph_active)", RuntimeWarning)
-                return self._eager(X, y, threshold, epoch, batch_num)
-            return self._replay()  # capture only records; the first replay performs this step
-        if X.shape != self._sX.shape:
-            return self._eager(X, y, threshold, epoch, batch_num)
-        # a producer that fills input_buffers() in place passes those tensors back and saves the two device copies
-        if X.data_ptr() != self._sX.data_ptr():
-            self._sX.copy_(X)
-        if y.data_ptr() != self._sy.data_ptr():
-            self._sy.copy_(y)
-        return self._replay()
+        loss = self._run(X, y, threshold=threshold, epoch=epoch, batch_num=batch_num)
+        if self.split_finish:
+            self._finish()
+        return loss.detach()
 
     def input_buffers(self):
         """(X, y) the captured graph reads its batch from, or None before the capture / on the eager path: fill them
         in place and pass them to the step to skip its per-step copy of the batch."""
-        if self.use_graph and self._graph is not None:
-            return self._sX, self._sy
-        return None
+        return tuple(self._static) if self.graph_active else None

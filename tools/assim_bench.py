@@ -79,7 +79,7 @@ def part_a(args, dev, lats, lons):
     o1 = obs[:, :, :C]
     t_oi = timed(lambda: net.apply_(xa, o1), args.steps * 10, args.warmup)
     return {"a_grid_points": G, "a_roi_nodes": int(len(roi)), "a_stations": int(len(st)), "a_channels": len(ch),
-            "a_ar_steps": P, "a_batch": 1, "a_captured": bool(assim._graph is not None and plain._graph is not None),
+            "a_ar_steps": P, "a_batch": 1, "a_captured": assim.graph_active and plain.graph_active,
             "a_rollout_ms": round(t_plain, 3), "a_rollout_repeat_ms": round(t_plain2, 3),
             "a_assim_rollout_ms": round(t_assim, 3), "a_assim_cost_ms": round(t_assim - min(t_plain, t_plain2), 3),
             "a_oi_apply_eager_ms": round(t_oi, 4)}
