@@ -112,6 +112,13 @@ _SIGNATURES = {
     "gcl_oi_innovation": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp]),
     "gcl_oi_analysis": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp,
                                   _vp, _i32, _f32, _f32, _f32, _f32, _i32, _vp]),
+    "gcl_verify_colstats_ws_bytes": (_sz, [_i32, _i32, _i32, _i32]),
+    "gcl_verify_colstats": (C.c_int, [_vp, _i64, _i64, _i32, _i32] + [_vp, _i64, _i64, _vp] * 4
+                            + [_vp, _i32, _i32, _vp, _vp, _sz, _vp]),
+    "gcl_verify_accumulate": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp]),
+    "gcl_regrid_blend": (C.c_int, [_vp, _i32, _i64, _i64, _i32, _vp, _vp, _i32, _i32, _vp, _i64, _i64, _vp, _vp, _i64,
+                                   _i64, _vp, _i64, _i64, _i32, _vp]),
+    "gcl_taper_blend": (C.c_int, [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _vp]),
 }
 
 
@@ -1014,3 +1021,77 @@ def oi_analysis(xb3, xa3, chans, node_row, nodes, stations, W, sb2: float, rl2: 
                                  _pd(slat), _pd(slon), _p(scos), _p(W), m, float(sb2), float(rl2), float(th_cut),
                                  float(a_cut), B, _stream()))
     return xa3
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# Forecast scoring and regional blending (csrc/verify.hip)
+# ------------------------------------------------------------------------------------------------------------------
+def _rows_view(t: torch.Tensor) -> torch.Tensor:
+    """A [B, rows, K] float32 view with unit column stride (copies only when the columns are strided)."""
+    if t.dtype != torch.float32:
+        t = t.float()
+    if t.stride(-1) != 1:
+        t = t.contiguous()
+    return t
+
+
+def verify_colstats(truth3, preds, rows, stats):
+    """Column statistics (see gcl_verify_colstats).  truth3 [B, G, >= K] float32 with unit column stride; preds: up to
+    four (tensor [B, G, W] with unit column stride, int32 column map [K] on the device or None); rows int32 [n] or None;
+    stats float64 [B, len(preds), K, 3].  K = stats.shape[2]."""
+    B, G, _ = truth3.shape
+    npred, K = stats.shape[1], stats.shape[2]
+    assert 1 <= npred <= 4 and len(preds) == npred and stats.shape == (B, npred, K, 3) and stats.is_contiguous()
+    n = rows.numel() if rows is not None else G
+    args = []
+    for q in range(4):
+        if q < npred:
+            p, m = preds[q]
+            assert p.shape[0] == B and p.stride(2) == 1 and (m is not None or p.shape[2] >= K)
+            assert m is None or (m.dtype == torch.int32 and m.numel() == K)
+            args += [_p(p), p.stride(1), p.stride(0), _pi(m)]
+        else:
+            args += [None, 0, 0, None]
+    nbytes = int(lib().gcl_verify_colstats_ws_bytes(n, K, npred, B))
+    ws = workspace(nbytes, truth3.device)
+    _check(lib().gcl_verify_colstats(_p(truth3), truth3.stride(1), truth3.stride(0), K, npred, *args, _pi(rows), n, B,
+                                     _pd(stats), ws.data_ptr(), ws.numel(), _stream()))
+    return stats
+
+
+def verify_accumulate(stats, jobs, state, masks=None):
+    """Add column statistics into metrics states (see gcl_verify_accumulate).  jobs int64 [njobs, 8] on the device."""
+    assert jobs.is_cuda and jobs.dtype == torch.int64 and jobs.is_contiguous() and jobs.shape[1] == 8
+    assert masks is None or (masks.is_cuda and masks.dtype == torch.uint8)
+    _check(lib().gcl_verify_accumulate(_pd(stats), jobs.data_ptr(), jobs.shape[0], _pd(state),
+                                       masks.data_ptr() if masks is not None else None, _stream()))
+
+
+def regrid_blend(src3, nlat: int, cell, w, K: int, g3=None, mask=None, r3=None, out3=None):
+    """g3[b, i, :K] = bilinear regrid of src3 [B, G_src, >= K] (float32 or float64) through the tables cell int32
+    [nt, 2] / w float64 [nt, 4]; with out3 also out3 = mask r3 + (1 - mask) g (see gcl_regrid_blend)."""
+    B = src3.shape[0]
+    nt = cell.shape[0]
+    assert src3.stride(2) == 1 and src3.dtype in (torch.float32, torch.float64) and src3.is_cuda
+    assert cell.dtype == torch.int32 and cell.is_contiguous() and w.shape == (nt, 4)
+    f64 = src3.dtype == torch.float64
+    for t in (g3, r3, out3):
+        assert t is None or (t.shape[0] == B and t.shape[1] == nt and t.shape[2] >= K and t.stride(2) == 1)
+    if out3 is not None:
+        assert mask is not None and r3 is not None and mask.numel() == nt and mask.is_contiguous()
+
+    def lb(t):
+        return (t.stride(1), t.stride(0)) if t is not None else (0, 0)
+    _check(lib().gcl_regrid_blend(src3.data_ptr(), int(f64), src3.stride(1), src3.stride(0), int(nlat), _pi(cell),
+                                  _pd(w), nt, int(K), _p(g3), *lb(g3), _p(mask), _p(r3), *lb(r3), _p(out3), *lb(out3),
+                                  B, _stream()))
+
+
+def taper_blend(mask, r3, g3, out3):
+    """out3 = mask r3 + (1 - mask) g3 (float32, see gcl_taper_blend); mask [nt] per row."""
+    B, nt, K = out3.shape
+    assert r3.shape == out3.shape and g3.shape == out3.shape and mask.numel() == nt and mask.is_contiguous()
+    assert r3.stride(2) == 1 and g3.stride(2) == 1 and out3.stride(2) == 1
+    _check(lib().gcl_taper_blend(_p(mask), _p(r3), r3.stride(1), r3.stride(0), _p(g3), g3.stride(1), g3.stride(0),
+                                 _p(out3), out3.stride(1), out3.stride(0), nt, K, B, _stream()))
+    return out3

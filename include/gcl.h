@@ -542,6 +542,51 @@ int gcl_oi_analysis(const float* xb, int64_t ldx, int64_t bsx, float* xa, int64_
                     const double* slon, const float* scos, const float* W, int32_t m, float sb2, float rl2,
                     float th_cut, float a_cut, int32_t B, gcl_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Forecast scoring and global -> regional blending (scripts/predict.py, scripts/predict_pipeline.py).
+ * ------------------------------------------------------------------------------------------- */
+/* Workspace of gcl_verify_colstats for n rows, K columns, npred predictions, B samples. */
+size_t gcl_verify_colstats_ws_bytes(int32_t n, int32_t K, int32_t npred, int32_t B);
+/* Column statistics of StreamingMetrics.update (scripts/predict.py:53-122, the per-column loop at
+ * :73-85 and the aggregate at :88-93; scripts/predict_pipeline.py:165-180): for every sample b,
+ * prediction q < npred (1..4) and column k < K, over the n rows r = rows[i] (rows NULL: r = i),
+ *   stats[((b * npred + q) * K + k) * 3 + 0] = sum (p - t)^2,   + 1 = sum |p - t|,
+ *   + 2 = sum (t - tm)(p - pm) / (||t - tm|| ||p - pm|| + 1e-8)     (float64)
+ * with t = truth[b * bst + r * ldt + k] and p = p_q[b * bs_q + r * ld_q + map_q[k]] (map_q NULL: k).
+ * Fixed-order two-stage reduction (two kernels, no atomics): a column's result depends only on its
+ * own data and n.  No allocation, no host synchronisation. */
+int gcl_verify_colstats(const float* truth, int64_t ldt, int64_t bst, int32_t K, int32_t npred,
+                        const float* p0, int64_t ld0, int64_t bs0, const int32_t* map0,
+                        const float* p1, int64_t ld1, int64_t bs1, const int32_t* map1,
+                        const float* p2, int64_t ld2, int64_t bs2, const int32_t* map2,
+                        const float* p3, int64_t ld3, int64_t bs3, const int32_t* map3,
+                        const int32_t* rows, int32_t n, int32_t B, double* stats, void* ws,
+                        size_t ws_bytes, gcl_stream_t stream);
+/* The accumulation of StreamingMetrics.update (scripts/predict.py:78-94): one job per metrics object,
+ * jobs int64 [njobs][8] = {stats offset of the object's first column for sample 0 (doubles), doubles
+ * between samples, columns, channels C, state offset (doubles), exclude-mask offset into masks
+ * (bytes, -1: none), rows per column, samples}.  The state of an object is float64
+ * [sum_se, sum_ae, n, total_elem, sum_se_per_ch[C], sum_acc[C], elem_per_ch[C], acc_count[C]];
+ * each sample adds in the reference's order.  One launch for all objects (their states disjoint). */
+int gcl_verify_accumulate(const double* stats, const int64_t* jobs, int32_t njobs, double* state,
+                          const uint8_t* masks, gcl_stream_t stream);
+/* Bilinear regrid (scripts/predict_pipeline.py:95-132 interpolate_global_to_region; scripts/
+ * interpolate_to_region.py:64-73; the RegularGridInterpolator of scripts/evaluate_full_pipeline.py:
+ * 134-145) with host-built tables: target i reads the source nodes n00 = cell[2i] * nlat +
+ * cell[2i+1], n00 + 1, n00 + nlat, n00 + nlat + 1 with the float64 weights w[4i..4i+3] and
+ *   g[b, i, k] = fp32(((v00 w0 + v01 w1) + v10 w2) + v11 w3)   (float64, each product rounded alone)
+ * src float32 (src_f64 = 0) or float64 rows of stride lds.  With out != NULL also the taper blend of
+ * scripts/predict_pipeline.py:326 in the same launch, out = m[i] r + (1 - m[i]) g (float32, no FMA);
+ * g may be NULL then. */
+int gcl_regrid_blend(const void* src, int32_t src_f64, int64_t lds, int64_t bss, int32_t nlat,
+                     const int32_t* cell, const double* w, int32_t nt, int32_t K, float* g, int64_t ldg,
+                     int64_t bsg, const float* mask, const float* r, int64_t ldr, int64_t bsr, float* out,
+                     int64_t ldo, int64_t bso, int32_t B, gcl_stream_t stream);
+/* Taper blend alone (scripts/predict_pipeline.py:326): out = m[i] r + (1 - m[i]) g, float32. */
+int gcl_taper_blend(const float* mask, const float* r, int64_t ldr, int64_t bsr, const float* g,
+                    int64_t ldg, int64_t bsg, float* out, int64_t ldo, int64_t bso, int32_t nt, int32_t K,
+                    int32_t B, gcl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
