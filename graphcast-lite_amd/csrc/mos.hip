@@ -1,0 +1,434 @@
+// MOS correction of 2 m temperature (src/postprocessing/mos_correction.py).
+//
+// Forest.  A HistGradientBoostingRegressor flattened into 16-byte nodes (see MosNode): a split holds its threshold, a
+// leaf its value.  sklearn's walk (_predictor.pyx): NaN follows missing_go_to_left, otherwise x <= threshold goes
+// left.  The raw prediction is ((baseline + v0) + v1) + ... in float64, tree order, as _raw_predict adds it.
+//
+// Station recurrence (gcl_mos_forest_predict, mos_correction.py:307-323).  One block per (sample, station group),
+// the steps in order: the lag features of step s are the group's corrected t2m of step s - 1.  Per step the block
+// builds every station's 20 features in LDS, walks every (station, tree) pair over its lanes into an LDS leaf table,
+// sums each station's leaves in tree order (one lane per station), and one lane averages the group in numpy's
+// pairwise order.
+//
+// IDW spread and apply (gcl_mos_idw_apply, mos_correction.py:176-241 and :325-338).  One thread per grid row.  The
+// station points' coordinates and a tile of their per-step biases sit in LDS.  The weights 1 / max(d, 0.1)^p of the
+// points within the radius are normalised by their numpy sum; the field is sum_k w_k b_k[s], added point by point in
+// float64 (numpy's axis-0 sum; a single step sums pairwise).  A station's own grid row takes its exact bias.
+//
+// hipcc contracts a product into the following add even through __dmul_rn, so every product whose rounding the
+// reference keeps passes through `rounded` (an empty asm volatile, as in assim.hip / verify.hip).
+#include <math.h>
+
+#include "common.h"
+
+namespace {
+
+__device__ __forceinline__ double rounded(double x) {
+  asm volatile("" : "+v"(x));
+  return x;
+}
+
+constexpr int kNumFeat = 20;   // FEATURE_COLUMNS of build_learned_mos.py
+constexpr int kNumTime = 8;    // host features per (sample, station, step): hour sin/cos, doy sin/cos, solar
+                               // elevation, station lat / lon / elev
+constexpr int kMaxPoints = 128;     // station groups (IDW points) and stations per group
+constexpr int kForestThreads = 256;
+constexpr int kLeafBudget = 48 * 1024;  // bytes of leaf table per pass of the forest kernel
+constexpr int kIdwThreads = 128;
+constexpr int kStepTile = 16;           // steps per LDS bias tile of the IDW kernel
+
+// One forest node: v = threshold (split) or value (leaf); a = left child; b = right child (bits 0-23), feature
+// (24-28), missing_go_to_left (29), is_leaf (30).  Child indices are global (into the whole forest).
+struct __attribute__((aligned(16))) MosNode {
+  double v;
+  uint32_t a, b;
+};
+
+__device__ __forceinline__ double walk_tree(const MosNode* __restrict__ nodes, int root, const double* f) {
+  int i = root;
+  for (;;) {
+    const MosNode n = nodes[i];
+    if (n.b & (1u << 30)) return n.v;
+    const double x = f[(n.b >> 24) & 31u];
+    const bool left = isnan(x) ? ((n.b >> 29) & 1u) != 0 : x <= n.v;
+    i = left ? (int)n.a : (int)(n.b & 0xFFFFFFu);
+  }
+}
+
+// numpy's float64 add.reduce of n (< 129) values streamed in order: sequential below 8, else eight interleaved
+// accumulators, combined in a fixed tree, then the remainder (pairwise_sum, n <= PW_BLOCKSIZE).
+struct NpSum {
+  double r[8];
+  double res;
+  int n, i, body;
+  __device__ explicit NpSum(int n_) : res(0.0), n(n_), i(0), body(n_ - n_ % 8) {
+    for (int j = 0; j < 8; ++j) r[j] = 0.0;
+  }
+  __device__ void add(double x) {
+    if (n < 8) {
+      res += x;
+    } else if (i < body) {
+      // a select per accumulator instead of a dynamic register index (no scratch)
+      const int lane = i & 7;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) r[j] = j == lane ? (i < 8 ? x : r[j] + x) : r[j];
+    } else {
+      if (i == body) res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+      res += x;
+    }
+    ++i;
+  }
+  __device__ double sum() const {
+    if (n >= 8 && body == n) return ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+    return 0.0 + res;  // numpy starts the reduction from the identity
+  }
+};
+
+__device__ __forceinline__ double load_val(const void* p, int f64, int64_t off) {
+  return f64 ? static_cast<const double*>(p)[off] : (double)static_cast<const float*>(p)[off];
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// Forest on feature rows (sklearn predict)
+// ------------------------------------------------------------------------------------------------------------------
+__global__ void forest_eval_kernel(const MosNode* __restrict__ nodes, const int32_t* __restrict__ roots, int ntrees,
+                                   double baseline, const double* __restrict__ X, int n, double* __restrict__ y) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= n) return;
+  double f[kNumFeat];
+#pragma unroll
+  for (int j = 0; j < kNumFeat; ++j) f[j] = X[(int64_t)r * kNumFeat + j];
+  double acc = baseline;
+  for (int t = 0; t < ntrees; ++t) {
+    int i = roots[t];
+    for (;;) {
+      const MosNode nd = nodes[i];
+      if (nd.b & (1u << 30)) break;
+      const int fi = (nd.b >> 24) & 31u;
+      double x = f[0];
+      // a select chain instead of a dynamic register index (no scratch)
+#pragma unroll
+      for (int j = 1; j < kNumFeat; ++j) x = fi == j ? f[j] : x;
+      const bool left = isnan(x) ? ((nd.b >> 29) & 1u) != 0 : x <= nd.v;
+      i = left ? (int)nd.a : (int)(nd.b & 0xFFFFFFu);
+    }
+    acc += nodes[i].v;
+  }
+  y[r] = acc;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// Station recurrence
+// ------------------------------------------------------------------------------------------------------------------
+struct Chans {
+  int t2m, u, v, sp, tp;
+};
+
+__global__ void __launch_bounds__(kForestThreads)
+forest_station_kernel(const MosNode* __restrict__ nodes, const int32_t* __restrict__ roots, int ntrees,
+                      double baseline, const void* __restrict__ pred, int f64, int64_t bs, int64_t gs, int64_t ss,
+                      int steps, Chans ch, const int32_t* __restrict__ grid_idx, const int32_t* __restrict__ gstart,
+                      int nst, const double* __restrict__ tfeat, double* __restrict__ bias, double* __restrict__ fout,
+                      int32_t* __restrict__ ncorr, int pass_max) {
+  extern __shared__ double smem[];
+  double* feat = smem;                            // [pass_max][kNumFeat]
+  double* leaves = feat + pass_max * kNumFeat;    // [pass_max][ntrees]
+  double* sbias = leaves + (size_t)pass_max * ntrees;  // [kMaxPoints]
+  __shared__ double prev_s;
+
+  const int g = blockIdx.x, b = blockIdx.y, ng = gridDim.x, tid = threadIdx.x;
+  const int s0 = gstart[g], gsize = gstart[g + 1] - s0;
+  if (g == 0 && tid == 0 && ncorr) ncorr[b] = 0;  // the IDW kernel that follows counts into it
+  const char* row = (const char*)pred + (size_t)(f64 ? 8 : 4) * (size_t)(b * bs + (int64_t)grid_idx[g] * gs);
+  const double qnan = __builtin_nan("");
+  if (tid == 0) prev_s = qnan;
+  __syncthreads();
+
+  for (int s = 0; s < steps; ++s) {
+    const int64_t so = s * ss;
+    for (int p0 = 0; p0 < gsize; p0 += pass_max) {
+      const int np = min(pass_max, gsize - p0);
+      if (tid < np) {
+        // _build_features_from_forecast (mos_correction.py:98-173), forecast part in float64
+        const int st = s0 + p0 + tid;
+        const double* tf = tfeat + (((int64_t)b * nst + st) * steps + s) * kNumTime;
+        const double prev = prev_s;
+        const double t2m_c = load_val(row, f64, so + ch.t2m) - 273.15;
+        const double u = ch.u >= 0 ? load_val(row, f64, so + ch.u) : qnan;
+        const double v = ch.v >= 0 ? load_val(row, f64, so + ch.v) : qnan;
+        double ws = qnan, wsin = qnan, wcos = qnan;
+        if (!isnan(u) && !isnan(v)) {
+          ws = sqrt(rounded(u * u) + rounded(v * v));
+          const double wd = atan2(-u, -v);
+          wsin = sin(wd);
+          wcos = cos(wd);
+        }
+        const double sp = ch.sp >= 0 ? load_val(row, f64, so + ch.sp) / 100.0 : qnan;
+        const double tp = ch.tp >= 0 ? load_val(row, f64, so + ch.tp) : qnan;
+        double* f = feat + tid * kNumFeat;
+        f[0] = t2m_c;   f[1] = qnan;  f[2] = ws;     f[3] = wsin;   f[4] = wcos;
+        f[5] = sp;      f[6] = qnan;  f[7] = qnan;   f[8] = tp;
+        f[9] = tf[0];   f[10] = tf[1]; f[11] = tf[2]; f[12] = tf[3]; f[13] = tf[4];
+        f[14] = qnan;   f[15] = prev;  f[16] = s == 0 ? qnan : t2m_c - prev;
+        f[17] = tf[5];  f[18] = tf[6]; f[19] = tf[7];
+        if (fout) {
+          double* o = fout + (((int64_t)b * nst + st) * steps + s) * kNumFeat;
+          for (int j = 0; j < kNumFeat; ++j) o[j] = f[j];
+        }
+      }
+      __syncthreads();
+      for (int idx = tid; idx < np * ntrees; idx += blockDim.x) {
+        const int q = idx / ntrees, t = idx - q * ntrees;
+        leaves[(size_t)q * ntrees + t] = walk_tree(nodes, roots[t], feat + q * kNumFeat);
+      }
+      __syncthreads();
+      if (tid < np) {
+        const double* lv = leaves + (size_t)tid * ntrees;
+        double acc = baseline;
+        for (int t = 0; t < ntrees; ++t) acc += lv[t];
+        sbias[p0 + tid] = acc;
+      }
+      __syncthreads();
+    }
+    if (tid == 0) {
+      // float(np.mean(biases)); prev_t2m_c = float(pred + bias) - 273.15 (mos_correction.py:320-322)
+      NpSum m(gsize);
+      for (int q = 0; q < gsize; ++q) m.add(sbias[q]);
+      const double mean = m.sum() / (double)gsize;
+      bias[((int64_t)b * ng + g) * steps + s] = mean;
+      prev_s = (load_val(row, f64, so + ch.t2m) + mean) - 273.15;
+    }
+    __syncthreads();
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// IDW spread and apply
+// ------------------------------------------------------------------------------------------------------------------
+// mos_correction.py:176-184, node (lat1, lon1) to point (lat2, lon2), float64, Python's operation order.
+__device__ __forceinline__ double haversine_km(double lat1, double lon1, double lat2, double lon2) {
+  const double d2r = 0.017453292519943295;  // math.radians: x * (pi / 180)
+  const double dlat = rounded((lat2 - lat1) * d2r), dlon = rounded((lon2 - lon1) * d2r);
+  const double sa = sin(dlat / 2), sb = sin(dlon / 2);
+  const double cc = rounded(rounded(cos(rounded(lat1 * d2r)) * cos(rounded(lat2 * d2r))) * rounded(sb * sb));
+  const double a = rounded(sa * sa) + cc;
+  return rounded(6371.0 * 2 * atan2(sqrt(a), sqrt(1 - a)));
+}
+
+__device__ __forceinline__ double idw_raw_weight(double d, double power) {
+  d = fmax(d, 0.1);
+  const double dp = power == 2.0 ? rounded(d * d) : (power == 1.0 ? d : pow(d, power));
+  return 1.0 / dp;
+}
+
+__global__ void __launch_bounds__(kIdwThreads)
+idw_apply_kernel(const void* __restrict__ in, int f64, int64_t bs, int64_t gs, int64_t ss, void* out, int64_t obs,
+                 int64_t ogs, int64_t oss, int copy, int G, int steps, int C, int t2m,
+                 const double* __restrict__ node_lat, const double* __restrict__ node_lon,
+                 const int32_t* __restrict__ pt_idx, int K, const double* __restrict__ bias, int idw, double power,
+                 double radius, int32_t* __restrict__ ncorr) {
+  __shared__ double plat[kMaxPoints], plon[kMaxPoints];
+  __shared__ int32_t pidx[kMaxPoints];
+  __shared__ double btile[kMaxPoints * kStepTile];
+  const int b = blockIdx.y, tid = threadIdx.x;
+  const int r0 = blockIdx.x * kIdwThreads, g = r0 + tid;
+  for (int k = tid; k < K; k += kIdwThreads) {
+    const int gi = pt_idx[k];
+    pidx[k] = gi;
+    plat[k] = node_lat[gi];
+    plon[k] = node_lon[gi];
+  }
+  // the other channels of the block's rows, coalesced over (row, step, channel)
+  if (copy) {
+    const int nr = min(kIdwThreads, G - r0);
+    const int per_row = steps * C;  // 32-bit index arithmetic: a block's rows hold < 2^31 elements
+    for (int e = tid; e < nr * per_row; e += kIdwThreads) {
+      const int rs = e / C, c = e - rs * C;
+      if (c == t2m) continue;
+      const int rr = rs / steps, s = rs - rr * steps;
+      const int64_t io = b * bs + (int64_t)(r0 + rr) * gs + s * ss + c;
+      const int64_t oo = b * obs + (int64_t)(r0 + rr) * ogs + s * oss + c;
+      if (f64) static_cast<double*>(out)[oo] = static_cast<const double*>(in)[io];
+      else static_cast<float*>(out)[oo] = static_cast<const float*>(in)[io];
+    }
+  }
+  __syncthreads();
+
+  const bool live = g < G;
+  int own = -1;
+  int nmask = 0;
+  double wsum = 0.0, glat = 0.0, glon = 0.0;
+  if (live) {
+    for (int k = 0; k < K; ++k)
+      if (pidx[k] == g) { own = k; break; }
+    if (own < 0 && idw) {
+      glat = node_lat[g];
+      glon = node_lon[g];
+      for (int k = 0; k < K; ++k) nmask += haversine_km(glat, glon, plat[k], plon[k]) < radius;
+      NpSum ws(nmask);
+      for (int k = 0; k < K; ++k) {
+        const double d = haversine_km(glat, glon, plat[k], plon[k]);
+        if (d < radius) ws.add(idw_raw_weight(d, power));
+      }
+      wsum = ws.sum();
+    }
+  }
+  const bool touched = live && (own >= 0 || idw);
+  bool any_big = false, any_nan = false;
+  for (int s0 = 0; s0 < steps; s0 += kStepTile) {
+    const int cnt = min(kStepTile, steps - s0);
+    __syncthreads();
+    for (int e = tid; e < K * kStepTile; e += kIdwThreads) {
+      const int k = e / kStepTile, j = e - k * kStepTile;
+      btile[e] = j < cnt ? bias[((int64_t)b * K + k) * steps + s0 + j] : 0.0;
+    }
+    __syncthreads();
+    if (!touched) continue;
+    double acc[kStepTile];
+    if (own >= 0) {
+#pragma unroll
+      for (int j = 0; j < kStepTile; ++j) acc[j] = btile[own * kStepTile + j];
+    } else if (steps == 1) {
+      // a (n, 1) sum reduces along its only non-trivial axis: pairwise
+      NpSum ps(nmask);
+      for (int k = 0; k < K && nmask; ++k) {
+        const double d = haversine_km(glat, glon, plat[k], plon[k]);
+        if (d < radius) ps.add(rounded((idw_raw_weight(d, power) / wsum) * btile[k * kStepTile]));
+      }
+#pragma unroll
+      for (int j = 0; j < kStepTile; ++j) acc[j] = 0.0;
+      acc[0] = nmask ? ps.sum() : 0.0;
+    } else {
+#pragma unroll
+      for (int j = 0; j < kStepTile; ++j) acc[j] = 0.0;
+      for (int k = 0; k < K && nmask; ++k) {
+        const double d = haversine_km(glat, glon, plat[k], plon[k]);
+        if (!(d < radius)) continue;
+        const double w = idw_raw_weight(d, power) / wsum;
+#pragma unroll
+        for (int j = 0; j < kStepTile; ++j) acc[j] += rounded(w * btile[k * kStepTile + j]);
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < kStepTile; ++j) {
+      if (j >= cnt) break;
+      const double f = acc[j];
+      any_nan |= isnan(f);
+      any_big |= fabs(f) > 1e-6;
+      const int64_t io = b * bs + (int64_t)g * gs + (int64_t)(s0 + j) * ss + t2m;
+      const int64_t oo = b * obs + (int64_t)g * ogs + (int64_t)(s0 + j) * oss + t2m;
+      const double y = load_val(in, f64, io) + f;
+      if (f64) static_cast<double*>(out)[oo] = y;
+      else static_cast<float*>(out)[oo] = (float)y;
+    }
+  }
+  if (live && !touched && copy) {
+    for (int s = 0; s < steps; ++s) {
+      const int64_t io = b * bs + (int64_t)g * gs + (int64_t)s * ss + t2m;
+      const int64_t oo = b * obs + (int64_t)g * ogs + (int64_t)s * oss + t2m;
+      if (f64) static_cast<double*>(out)[oo] = static_cast<const double*>(in)[io];
+      else static_cast<float*>(out)[oo] = static_cast<const float*>(in)[io];
+    }
+  }
+  // n_corrected: IDW counts rows whose max |bias| > 1e-6 (a NaN makes numpy's max NaN); station-only counts points
+  if (ncorr && live && (idw ? (any_big && !any_nan) : own >= 0)) atomicAdd(ncorr + b, 1);
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// Table MOS
+// ------------------------------------------------------------------------------------------------------------------
+__global__ void table_apply_kernel(const void* __restrict__ in, int f64, int64_t bs, int64_t gs, int64_t ss, void* out,
+                                   int64_t obs, int64_t ogs, int64_t oss, int copy, int G, int steps, int C, int t2m,
+                                   const double* __restrict__ tb, int nvalid, int B) {
+  const int64_t per = copy ? (int64_t)steps * C : steps;
+  const int64_t total = (int64_t)B * G * per;
+  for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t bg = e / per;
+    const int64_t w = e - bg * per;
+    const int s = copy ? (int)(w / C) : (int)w;
+    const int c = copy ? (int)(w - (int64_t)s * C) : t2m;
+    const int64_t b = bg / G, g = bg - b * G;
+    const int64_t io = b * bs + g * gs + s * ss + c, oo = b * obs + g * ogs + s * oss + c;
+    const bool add = c == t2m && s < nvalid;
+    if (f64) {
+      const double x = static_cast<const double*>(in)[io];
+      static_cast<double*>(out)[oo] = add ? x + tb[s] : x;
+    } else {
+      const float x = static_cast<const float*>(in)[io];
+      static_cast<float*>(out)[oo] = add ? x + (float)tb[s] : x;
+    }
+  }
+}
+
+}  // namespace
+
+extern "C" int gcl_mos_forest_eval(const void* nodes, const int32_t* roots, int32_t ntrees, double baseline,
+                                   const double* X, int32_t n, double* y, gcl_stream_t stream) {
+  GCL_CHECK_ARG(nodes && roots && X && y, "mos_forest_eval: null argument");
+  GCL_CHECK_ARG(ntrees > 0 && n >= 0, "mos_forest_eval: bad shape (ntrees=%d, n=%d)", ntrees, n);
+  if (n == 0) return GCL_OK;
+  hipLaunchKernelGGL(forest_eval_kernel, dim3((n + 127) / 128), dim3(128), 0, (hipStream_t)stream,
+                     (const MosNode*)nodes, roots, ntrees, baseline, X, n, y);
+  GCL_CHECK_LAUNCH();
+  return GCL_OK;
+}
+
+extern "C" int gcl_mos_forest_predict(const void* nodes, const int32_t* roots, int32_t ntrees, double baseline,
+                                      const void* pred, int32_t pred_f64, int64_t bs, int64_t gs, int64_t ss,
+                                      int32_t steps, int32_t c_t2m, int32_t c_u, int32_t c_v, int32_t c_sp,
+                                      int32_t c_tp, const int32_t* grid_idx, const int32_t* group_start,
+                                      int32_t ngroups, int32_t nst, const double* tfeat, double* bias,
+                                      double* feat_out, int32_t* n_corrected, int32_t B, gcl_stream_t stream) {
+  GCL_CHECK_ARG(nodes && roots && pred && grid_idx && group_start && tfeat && bias, "mos_forest_predict: null argument");
+  GCL_CHECK_ARG(ntrees > 0 && steps > 0 && B > 0 && B <= 65535, "mos_forest_predict: bad shape (ntrees=%d, "
+                "steps=%d, B=%d)", ntrees, steps, B);
+  GCL_CHECK_ARG(ngroups > 0 && ngroups <= kMaxPoints && nst >= ngroups, "mos_forest_predict: %d groups of %d "
+                "stations (at most %d groups)", ngroups, nst, kMaxPoints);
+  GCL_CHECK_ARG(c_t2m >= 0, "mos_forest_predict: no t2m channel");
+  const int pass_max = max(1, min(kMaxPoints, kLeafBudget / (8 * ntrees)));
+  const size_t lds = ((size_t)pass_max * kNumFeat + (size_t)pass_max * ntrees + kMaxPoints) * sizeof(double);
+  GCL_CHECK_ARG(lds <= 64 * 1024, "mos_forest_predict: %d trees exceed the LDS leaf table", ntrees);
+  const Chans ch{c_t2m, c_u, c_v, c_sp, c_tp};
+  hipLaunchKernelGGL(forest_station_kernel, dim3(ngroups, B), dim3(kForestThreads), lds, (hipStream_t)stream,
+                     (const MosNode*)nodes, roots, ntrees, baseline, pred, pred_f64, bs, gs, ss, steps, ch, grid_idx,
+                     group_start, nst, tfeat, bias, feat_out, n_corrected, pass_max);
+  GCL_CHECK_LAUNCH();
+  return GCL_OK;
+}
+
+extern "C" int gcl_mos_idw_apply(const void* in, int32_t f64, int64_t bs, int64_t gs, int64_t ss, void* out,
+                                 int64_t obs, int64_t ogs, int64_t oss, int32_t G, int32_t steps, int32_t C,
+                                 int32_t t2m, const double* node_lat, const double* node_lon, const int32_t* pt_idx,
+                                 int32_t K, const double* bias, int32_t idw, double power, double radius,
+                                 int32_t* n_corrected, int32_t B, gcl_stream_t stream) {
+  GCL_CHECK_ARG(in && out && pt_idx && bias, "mos_idw_apply: null argument");
+  GCL_CHECK_ARG(!idw || (node_lat && node_lon), "mos_idw_apply: IDW needs the node coordinates");
+  GCL_CHECK_ARG(G > 0 && steps > 0 && C > 0 && t2m >= 0 && t2m < C && B > 0 && B <= 65535,
+                "mos_idw_apply: bad shape (G=%d, steps=%d, C=%d, t2m=%d, B=%d)", G, steps, C, t2m, B);
+  GCL_CHECK_ARG(K > 0 && K <= kMaxPoints, "mos_idw_apply: %d station points (1..%d)", K, kMaxPoints);
+  GCL_CHECK_ARG((int64_t)kIdwThreads * steps * C < (1ll << 31), "mos_idw_apply: steps x C = %d x %d too large",
+                steps, C);
+  const int copy = in != out;
+  hipLaunchKernelGGL(idw_apply_kernel, dim3((G + kIdwThreads - 1) / kIdwThreads, B), dim3(kIdwThreads), 0,
+                     (hipStream_t)stream, in, f64, bs, gs, ss, out, obs, ogs, oss, copy, G, steps, C, t2m, node_lat,
+                     node_lon, pt_idx, K, bias, idw, power, radius, n_corrected);
+  GCL_CHECK_LAUNCH();
+  return GCL_OK;
+}
+
+extern "C" int gcl_mos_table_apply(const void* in, int32_t f64, int64_t bs, int64_t gs, int64_t ss, void* out,
+                                   int64_t obs, int64_t ogs, int64_t oss, int32_t G, int32_t steps, int32_t C,
+                                   int32_t t2m, const double* step_bias, int32_t nvalid, int32_t B,
+                                   gcl_stream_t stream) {
+  GCL_CHECK_ARG(in && out && (step_bias || nvalid == 0), "mos_table_apply: null argument");
+  GCL_CHECK_ARG(G >= 0 && steps > 0 && C > 0 && t2m >= 0 && t2m < C && B > 0 && nvalid >= 0 && nvalid <= steps,
+                "mos_table_apply: bad shape (G=%d, steps=%d, C=%d, t2m=%d, nvalid=%d)", G, steps, C, t2m, nvalid);
+  const int copy = in != out;
+  const int64_t total = (int64_t)B * G * (copy ? (int64_t)steps * C : steps);
+  if (total == 0) return GCL_OK;
+  const int64_t nb = (total + 255) / 256;
+  hipLaunchKernelGGL(table_apply_kernel, dim3((unsigned)(nb > 8192 ? 8192 : nb)), dim3(256), 0, (hipStream_t)stream,
+                     in, f64, bs, gs, ss, out, obs, ogs, oss, copy, G, steps, C, t2m, step_bias, nvalid, B);
+  GCL_CHECK_LAUNCH();
+  return GCL_OK;
+}

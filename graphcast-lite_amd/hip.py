@@ -119,6 +119,13 @@ _SIGNATURES = {
     "gcl_regrid_blend": (C.c_int, [_vp, _i32, _i64, _i64, _i32, _vp, _vp, _i32, _i32, _vp, _i64, _i64, _vp, _vp, _i64,
                                    _i64, _vp, _i64, _i64, _i32, _vp]),
     "gcl_taper_blend": (C.c_int, [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _vp]),
+    "gcl_mos_forest_eval": (C.c_int, [_vp, _vp, _i32, C.c_double, _vp, _i32, _vp, _vp]),
+    "gcl_mos_forest_predict": (C.c_int, [_vp, _vp, _i32, C.c_double, _vp, _i32, _i64, _i64, _i64, _i32] + [_i32] * 5
+                               + [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp]),
+    "gcl_mos_idw_apply": (C.c_int, [_vp, _i32, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _vp,
+                                    _vp, _vp, _i32, _vp, _i32, C.c_double, C.c_double, _vp, _i32, _vp]),
+    "gcl_mos_table_apply": (C.c_int, [_vp, _i32, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _vp,
+                                      _i32, _i32, _vp]),
 }
 
 

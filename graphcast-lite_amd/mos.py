@@ -1,0 +1,490 @@
+"""MOS (model output statistics) correction of 2 m temperature on the HIP path: drop-in for
+`src/postprocessing/mos_correction.py`.
+
+* `load_mos_table`, `get_t2m_bias`, `apply_mos_t2m` (`:18-69`): the per-(month, hour) bias table.  The lookup is on the
+  host; the add runs on the device (`gcl_mos_table_apply`).
+* `load_learned_mos` (`:93-95`): joblib, as in the reference (sklearn is needed only to unpickle the bundle).
+* `MOSForest`: the bundle's `HistGradientBoostingRegressor` flattened for the device; `save` / `load` keep it in an npz
+  so a machine without sklearn can run it.
+* `apply_learned_mos_t2m` (`:244-340`) with the reference's signature and return convention: `(corrected,
+  n_corrected)` when `t2m` is present, the input itself otherwise.  `LearnedMOS` prepares the station groups, the
+  forest and the IDW points once; its `apply` neither synchronises nor allocates after the first call, and
+  `CapturedLearnedMOS` replays it from a hipGraph.
+
+Predictions are device tensors `[G, steps, C]` or `[B, G, steps, C]`, float32 or float64, in physical units (t2m in
+Kelvin).  Coordinates are host arrays.  The host-side features (valid time and station) are computed with Python's
+`math` exactly as the reference computes them and uploaded as one small float64 tensor, so new valid times need no
+re-capture.
+
+Kernels: csrc/mos.hip.
+"""
+import json
+import math
+from datetime import datetime
+from typing import Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import hip
+from .capture import Captured
+
+NUM_FEATURES = 20  # FEATURE_COLUMNS of the reference's build_learned_mos.py
+NUM_TIME_FEATURES = 8  # hour sin/cos, doy sin/cos, solar elevation, station lat/lon/elev
+MAX_POINTS = 128  # station groups and stations per group (csrc/mos.hip kMaxPoints)
+_ALT_NAMES = {"u10": "10u", "10u": "u10", "v10": "10v", "10v": "v10"}
+DEFAULT_STATION = {"lat": 56.173, "lon": 92.493, "elev": 287.0, "name": "default"}
+
+
+# ======================================================================================================================
+# Table MOS (mos_correction.py:18-69)
+# ======================================================================================================================
+def load_mos_table(path) -> dict:
+    """The bias table JSON as a dict."""
+    with open(path, "r", encoding="utf-8") as f:
+        return json.load(f)
+
+
+def get_t2m_bias(mos_table: dict, valid_time: datetime) -> float:
+    """The additive t2m correction (degC) for a UTC valid time: `bias_table[month][hour]`, 0.0 when either key is
+    missing."""
+    return mos_table["bias_table"].get(str(valid_time.month), {}).get(str(valid_time.hour), 0.0)
+
+
+# ======================================================================================================================
+# Learned MOS: the forest
+# ======================================================================================================================
+def load_learned_mos(path) -> dict:
+    """The learned-MOS bundle (a dict with the fitted model under "model"), unpickled with joblib."""
+    import joblib
+
+    return joblib.load(path)
+
+
+class MOSForest:
+    """A `HistGradientBoostingRegressor` as flat arrays: per node `feature`, `value` (threshold of a split, value of a
+    leaf), `left`, `right` (indices into the whole forest), `missing_left`, `is_leaf`; `roots[t]` is tree t's first
+    node; `baseline` the model's baseline prediction.  `to(device)` packs the nodes into the kernels' 16-byte layout."""
+
+    _FIELDS = ("feature", "value", "left", "right", "missing_left", "is_leaf", "roots")
+
+    def __init__(self, feature, value, left, right, missing_left, is_leaf, roots, baseline: float,
+                 n_features: int = NUM_FEATURES):
+        self.feature = np.ascontiguousarray(feature, dtype=np.int32)
+        self.value = np.ascontiguousarray(value, dtype=np.float64)
+        self.left = np.ascontiguousarray(left, dtype=np.int64)
+        self.right = np.ascontiguousarray(right, dtype=np.int64)
+        self.missing_left = np.ascontiguousarray(missing_left, dtype=np.uint8)
+        self.is_leaf = np.ascontiguousarray(is_leaf, dtype=np.uint8)
+        self.roots = np.ascontiguousarray(roots, dtype=np.int32)
+        self.baseline = float(baseline)
+        self.n_features = int(n_features)
+        self._validate()
+        self._dev = {}
+
+    def _validate(self):
+        n = self.value.shape[0]
+        if n == 0 or n >= (1 << 24):
+            raise ValueError(f"MOSForest: {n} nodes (1 .. 2^24 - 1 supported)")
+        if self.n_features > 32:
+            raise ValueError(f"MOSForest: {self.n_features} features (at most 32)")
+        for a in (self.feature, self.left, self.right, self.missing_left, self.is_leaf):
+            if a.shape != (n,):
+                raise ValueError("MOSForest: node arrays of different lengths")
+        split = self.is_leaf == 0
+        idx = np.arange(n)
+        # children come after their parent: every walk ends at a leaf
+        if np.any((self.left[split] <= idx[split]) | (self.right[split] <= idx[split])
+                  | (self.left[split] >= n) | (self.right[split] >= n)):
+            raise ValueError("MOSForest: a split's children must follow it in the node array")
+        if np.any((self.feature[split] < 0) | (self.feature[split] >= self.n_features)):
+            raise ValueError("MOSForest: split feature outside the feature vector")
+        if self.roots.size == 0 or np.any((self.roots < 0) | (self.roots >= n)):
+            raise ValueError("MOSForest: bad tree roots")
+
+    @property
+    def num_trees(self) -> int:
+        return int(self.roots.size)
+
+    @property
+    def num_nodes(self) -> int:
+        return int(self.value.size)
+
+    @classmethod
+    def from_sklearn(cls, model) -> "MOSForest":
+        """Flatten a fitted `HistGradientBoostingRegressor`.  Raises ValueError for categorical splits, more than one
+        tree per iteration (classifiers with several classes) and a loss whose link is not the identity."""
+        if getattr(model, "n_trees_per_iteration_", 1) != 1:
+            raise ValueError(f"MOSForest: {model.n_trees_per_iteration_} trees per iteration (only 1 is supported)")
+        link = getattr(getattr(model, "_loss", None), "link", None)
+        if link is None or type(link).__name__ != "IdentityLink":
+            raise ValueError(f"MOSForest: loss link {type(link).__name__} is not the identity")
+        if getattr(model, "_preprocessor", None) is not None or (
+                getattr(model, "is_categorical_", None) is not None and np.any(model.is_categorical_)):
+            raise ValueError("MOSForest: categorical features are not supported")
+        cols = {k: [] for k in ("feature", "value", "left", "right", "missing_left", "is_leaf")}
+        roots, off = [], 0
+        for it in model._predictors:
+            nodes = it[0].nodes
+            if np.any(nodes["is_categorical"]):
+                raise ValueError("MOSForest: categorical splits are not supported")
+            leaf = nodes["is_leaf"].astype(np.uint8)
+            roots.append(off)
+            cols["feature"].append(np.where(leaf, 0, nodes["feature_idx"]))
+            cols["value"].append(np.where(leaf, nodes["value"], nodes["num_threshold"]))
+            cols["left"].append(np.where(leaf, 0, nodes["left"].astype(np.int64) + off))
+            cols["right"].append(np.where(leaf, 0, nodes["right"].astype(np.int64) + off))
+            cols["missing_left"].append(nodes["missing_go_to_left"])
+            cols["is_leaf"].append(leaf)
+            off += len(nodes)
+        base = np.asarray(model._baseline_prediction, dtype=np.float64).reshape(-1)
+        return cls(*(np.concatenate(cols[k]) for k in cols), np.asarray(roots), float(base[0]),
+                   n_features=int(model.n_features_in_))
+
+    def save(self, path):
+        np.savez_compressed(path, baseline=np.float64(self.baseline), n_features=np.int32(self.n_features),
+                            **{k: getattr(self, k) for k in self._FIELDS})
+
+    @classmethod
+    def load(cls, path) -> "MOSForest":
+        z = np.load(path)
+        return cls(*(z[k] for k in cls._FIELDS), float(z["baseline"]), int(z["n_features"]))
+
+    def predict_host(self, X: np.ndarray) -> np.ndarray:
+        """The same forest walked with numpy on the host (a restatement for checks; the product path is
+        `predict`)."""
+        X = np.asarray(X, dtype=np.float64)
+        out = np.full(X.shape[0], self.baseline)
+        rows = np.arange(X.shape[0])
+        for r in self.roots:
+            node = np.full(X.shape[0], r, dtype=np.int64)
+            active = self.is_leaf[node] == 0
+            while active.any():
+                a = node[active]
+                x = X[rows[active], self.feature[a]]
+                go_left = np.where(np.isnan(x), self.missing_left[a] != 0, x <= self.value[a])
+                node[active] = np.where(go_left, self.left[a], self.right[a])
+                active = self.is_leaf[node] == 0
+            out = out + self.value[node]
+        return out
+
+    def to(self, device):
+        """(packed nodes uint8 [N * 16], roots int32) on `device`, uploaded once per device."""
+        key = str(torch.device(device))
+        t = self._dev.get(key)
+        if t is None:
+            packed = np.zeros(self.num_nodes, dtype=[("v", "<f8"), ("a", "<u4"), ("b", "<u4")])
+            packed["v"] = self.value
+            packed["a"] = self.left.astype(np.uint32)
+            packed["b"] = (self.right.astype(np.uint32) | (self.feature.astype(np.uint32) << 24)
+                           | (self.missing_left.astype(np.uint32) << 29) | (self.is_leaf.astype(np.uint32) << 30))
+            nodes = torch.from_numpy(packed.view(np.uint8).copy()).to(device)
+            roots = torch.from_numpy(self.roots.copy()).to(device)
+            t = self._dev[key] = (nodes, roots)
+        return t
+
+    def predict(self, X: torch.Tensor) -> torch.Tensor:
+        """sklearn's `predict` on float64 device rows X [n, 20] (gcl_mos_forest_eval)."""
+        if not X.is_cuda:
+            raise RuntimeError("MOSForest.predict needs a GPU tensor (there is no CPU fallback)")
+        if X.dim() != 2 or X.shape[1] != NUM_FEATURES:
+            raise ValueError(f"MOSForest.predict: X must be [n, {NUM_FEATURES}], got {tuple(X.shape)}")
+        X = X.to(torch.float64).contiguous()
+        nodes, roots = self.to(X.device)
+        y = torch.empty(X.shape[0], dtype=torch.float64, device=X.device)
+        hip._check(hip.lib().gcl_mos_forest_eval(nodes.data_ptr(), roots.data_ptr(), self.num_trees, self.baseline,
+                                                 X.data_ptr(), X.shape[0], y.data_ptr(), hip._stream()))
+        return y
+
+
+_FORESTS = {}
+
+
+def _forest_of(forest_or_bundle) -> MOSForest:
+    """A MOSForest from a MOSForest, a bundle dict or a fitted model; flattened once per model object."""
+    if isinstance(forest_or_bundle, MOSForest):
+        return forest_or_bundle
+    model = forest_or_bundle["model"] if isinstance(forest_or_bundle, dict) else forest_or_bundle
+    hit = _FORESTS.get(id(model))
+    if hit is None or hit[0] is not model:
+        hit = _FORESTS[id(model)] = (model, MOSForest.from_sklearn(model))
+    return hit[1]
+
+
+# ======================================================================================================================
+# Host features (mos_correction.py:74-90, :152-160, :172)
+# ======================================================================================================================
+def solar_elevation(lat_deg: float, lon_deg: float, dt: datetime) -> float:
+    """Solar elevation in degrees after Spencer (1971), in the reference's operation order."""
+    doy = dt.timetuple().tm_yday
+    hour = dt.hour + dt.minute / 60.0
+    g = 2 * math.pi * (doy - 1) / 365.0
+    decl = (0.006918 - 0.399912 * math.cos(g) + 0.070257 * math.sin(g)
+            - 0.006758 * math.cos(2 * g) + 0.000907 * math.sin(2 * g))
+    eqt = 229.18 * (0.000075 + 0.001868 * math.cos(g) - 0.032077 * math.sin(g)
+                    - 0.014615 * math.cos(2 * g) - 0.04089 * math.sin(2 * g))
+    ha = math.radians((hour * 60 + eqt + 4 * lon_deg) / 4.0 - 180.0)
+    la = math.radians(lat_deg)
+    s = math.sin(la) * math.sin(decl) + math.cos(la) * math.cos(decl) * math.cos(ha)
+    return math.degrees(math.asin(max(-1.0, min(1.0, s))))
+
+
+def time_station_features(valid_time: datetime, st: dict) -> list:
+    """The 8 host features of one (station, valid time): hour sin/cos, day-of-year sin/cos, solar elevation, station
+    lat / lon / elev (features 9-13 and 17-19 of the reference's vector)."""
+    h = valid_time.hour
+    doy = valid_time.timetuple().tm_yday
+    return [math.sin(2 * math.pi * h / 24), math.cos(2 * math.pi * h / 24),
+            math.sin(2 * math.pi * doy / 365.25), math.cos(2 * math.pi * doy / 365.25),
+            solar_elevation(st["lat"], st["lon"], valid_time), float(st["lat"]), float(st["lon"]),
+            float(st["elev"])]
+
+
+def group_stations(stations: Sequence[dict], latitudes, longitudes):
+    """Map each station to its nearest grid index (the reference's squared-degree argmin, in the coordinates' own
+    dtype) and group the stations that share one.  Returns `[(grid_idx, [station, ...]), ...]` in first-seen order."""
+    lat, lon = np.asarray(latitudes), np.asarray(longitudes)
+    groups = {}
+    for st in stations:
+        gi = int(np.argmin((lat - st["lat"]) ** 2 + (lon - st["lon"]) ** 2))
+        groups.setdefault(gi, []).append(st)
+    return list(groups.items())
+
+
+def _channel(var_order: Sequence[str], name: str) -> int:
+    if name in var_order:
+        return list(var_order).index(name)
+    alt = _ALT_NAMES.get(name)
+    if alt is not None and alt in var_order:
+        return list(var_order).index(alt)
+    return -1
+
+
+def _as4(pred: torch.Tensor, who: str) -> torch.Tensor:
+    if not isinstance(pred, torch.Tensor) or not pred.is_cuda:
+        raise RuntimeError(f"{who} needs a GPU tensor (there is no CPU fallback)")
+    if pred.dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"{who}: prediction must be float32 or float64, got {pred.dtype}")
+    if pred.dim() not in (3, 4):
+        raise ValueError(f"{who}: prediction must be [G, steps, C] or [B, G, steps, C], got {tuple(pred.shape)}")
+    p4 = pred if pred.dim() == 4 else pred.unsqueeze(0)
+    if p4.stride(3) != 1:
+        p4 = p4.contiguous()
+    return p4
+
+
+def _times_2d(valid_times, B: int):
+    """valid_times as B lists (one list, or one per sample)."""
+    vt = list(valid_times)
+    if vt and isinstance(vt[0], (list, tuple)):
+        if len(vt) != B:
+            raise ValueError(f"{len(vt)} lists of valid times for a batch of {B}")
+        return [list(v) for v in vt]
+    return [vt] * B
+
+
+# ======================================================================================================================
+# Table MOS on the device
+# ======================================================================================================================
+def apply_mos_t2m(prediction_phys: torch.Tensor, var_order: list, mos_table: dict, forecast_valid_times):
+    """`corrected[..., s, t2m] += get_t2m_bias(mos_table, valid_times[s])` for the first len(valid_times) steps, in the
+    reference's arithmetic (float32 input: f32(x + f32(bias)); float64: exact adds).  Returns a new tensor, or the
+    input itself when `t2m` is not in var_order.  `forecast_valid_times` may be one list per sample for a batch."""
+    if "t2m" not in var_order:
+        return prediction_phys
+    p4 = _as4(prediction_phys, "apply_mos_t2m")
+    B, G, S, C = p4.shape
+    times = _times_2d(forecast_valid_times, B)
+    n = len(times[0])
+    if any(len(t) != n for t in times) or n > S:
+        raise IndexError(f"{n} valid times for {S} forecast steps")
+    out = torch.empty(p4.shape, dtype=p4.dtype, device=p4.device)
+    if n == 0:
+        out.copy_(p4)
+        return out if prediction_phys.dim() == 4 else out[0]
+    t2m = list(var_order).index("t2m")
+    f64 = int(p4.dtype == torch.float64)
+    shared = all(ts is times[0] for ts in times)
+    parts = [(p4, out, times[0])] if shared else [(p4[b:b + 1], out[b:b + 1], times[b]) for b in range(B)]
+    for src, dst, ts in parts:  # one launch per bias vector
+        tb = torch.tensor([get_t2m_bias(mos_table, t) for t in ts], dtype=torch.float64).to(p4.device)
+        hip._check(hip.lib().gcl_mos_table_apply(
+            src.data_ptr(), f64, src.stride(0), src.stride(1), src.stride(2), dst.data_ptr(), dst.stride(0),
+            dst.stride(1), dst.stride(2), G, S, C, t2m, tb.data_ptr(), n, src.shape[0], hip._stream()))
+    return out if prediction_phys.dim() == 4 else out[0]
+
+
+# ======================================================================================================================
+# Learned MOS on the device
+# ======================================================================================================================
+class LearnedMOS:
+    """The learned-MOS correction of one station set on one grid, prepared once.
+
+    forest_or_bundle: a `MOSForest`, the bundle dict of `load_learned_mos` or the fitted model.  stations: list of
+    {"lat", "lon", "elev"} dicts (None: the reference's single default station).  latitudes / longitudes: per grid node
+    (G,).  With `spatial_idw` and at least two distinct station grid points the biases are spread to every node by
+    inverse-distance weighting (`power`, `radius` km); otherwise only the station grid points change.
+
+    `time_features(valid_times)` builds the float64 device tensor of the host features; `apply(pred, tfeat)` runs
+    the two kernels.  After the first call per shape `apply` neither synchronises nor allocates: its bias, count and
+    (when `out` is not given) output buffers are reused by the next call."""
+
+    def __init__(self, forest_or_bundle, var_order: Sequence[str], latitudes, longitudes,
+                 stations: Optional[Sequence[dict]] = None, spatial_idw: bool = False, power: float = 2.0,
+                 radius: float = 300.0, device=None):
+        self.var_order = list(var_order)
+        self.has_t2m = "t2m" in self.var_order
+        self.forest = _forest_of(forest_or_bundle)
+        if self.forest.n_features != NUM_FEATURES:
+            raise ValueError(f"the learned MOS model takes {self.forest.n_features} features, not {NUM_FEATURES}")
+        self.latitudes, self.longitudes = np.asarray(latitudes), np.asarray(longitudes)
+        if self.latitudes.shape != self.longitudes.shape or self.latitudes.ndim != 1:
+            raise ValueError("latitudes and longitudes must be 1-d arrays of the same length (one entry per node)")
+        self.stations = [dict(DEFAULT_STATION)] if stations is None else list(stations)
+        if not self.stations:
+            raise ValueError("LearnedMOS: no stations")
+        self.groups = group_stations(self.stations, self.latitudes, self.longitudes)
+        if len(self.groups) > MAX_POINTS or max(len(g[1]) for g in self.groups) > MAX_POINTS:
+            raise ValueError(f"LearnedMOS: at most {MAX_POINTS} station grid points and {MAX_POINTS} stations each")
+        self.grid_idx = [g for g, _ in self.groups]
+        self.ordered_stations = [st for _, sts in self.groups for st in sts]
+        self.idw = bool(spatial_idw) and len(self.groups) >= 2
+        self.power, self.radius = float(power), float(radius)
+        self.chans = tuple(_channel(self.var_order, n) for n in ("t2m", "u10", "v10", "sp", "tp"))
+        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        dev = self.device
+        self._nodes, self._roots = self.forest.to(dev)
+        self._gidx = torch.tensor(self.grid_idx, dtype=torch.int32, device=dev)
+        starts = np.cumsum([0] + [len(s) for _, s in self.groups]).astype(np.int32)
+        self._gstart = torch.from_numpy(starts).to(dev)
+        self._lat = torch.from_numpy(self.latitudes.astype(np.float64)).to(dev)
+        self._lon = torch.from_numpy(self.longitudes.astype(np.float64)).to(dev)
+        self._bufs = {}
+
+    @property
+    def num_points(self) -> int:
+        return len(self.groups)
+
+    def time_features(self, valid_times) -> torch.Tensor:
+        """float64 device tensor [B, stations, steps, 8] of the host features; valid_times is [steps] (B = 1) or one
+        list per sample."""
+        vt = list(valid_times)
+        per_sample = [list(v) for v in vt] if vt and isinstance(vt[0], (list, tuple)) else [vt]
+        arr = np.array([[[time_station_features(t, st) for t in ts] for st in self.ordered_stations]
+                        for ts in per_sample], dtype=np.float64)
+        return torch.from_numpy(arr).to(self.device)
+
+    def _buffers(self, B: int, S: int, dtype, shape, with_out: bool):
+        key = (B, S)
+        bufs = self._bufs.get(key)
+        if bufs is None:
+            bufs = self._bufs[key] = {
+                "bias": torch.empty(B, self.num_points, S, dtype=torch.float64, device=self.device),
+                "n": torch.zeros(B, dtype=torch.int32, device=self.device)}
+        if with_out:
+            o = bufs.get(("out", dtype, tuple(shape)))
+            if o is None:
+                o = bufs[("out", dtype, tuple(shape))] = torch.empty(shape, dtype=dtype, device=self.device)
+            return bufs, o
+        return bufs, None
+
+    def apply(self, pred: torch.Tensor, tfeat: torch.Tensor, out: Optional[torch.Tensor] = None,
+              inplace: bool = False, feat_out: Optional[torch.Tensor] = None):
+        """(corrected, n_corrected int32 device tensor [B]) for pred [G, steps, C] / [B, G, steps, C]; pred itself
+        and None when t2m is absent.  `out` receives the result (same shape and dtype); `inplace` corrects pred.
+        `feat_out` (float64 [B, stations, steps, 20], optional) receives the station features (for checks)."""
+        if not self.has_t2m:
+            return pred, None
+        p4 = _as4(pred, "LearnedMOS.apply")
+        if inplace and p4.data_ptr() != pred.data_ptr():
+            raise ValueError("LearnedMOS.apply(inplace=True) needs a prediction with unit channel stride")
+        B, G, S, C = p4.shape
+        if G != self.latitudes.shape[0]:
+            raise ValueError(f"prediction has {G} grid rows, the coordinates {self.latitudes.shape[0]}")
+        if C != len(self.var_order):
+            raise ValueError(f"prediction has {C} channels, var_order {len(self.var_order)}")
+        if tfeat.shape != (B, len(self.ordered_stations), S, NUM_TIME_FEATURES) or tfeat.dtype != torch.float64 \
+                or not tfeat.is_cuda or not tfeat.is_contiguous():
+            raise ValueError(f"tfeat must be contiguous float64 [{B}, {len(self.ordered_stations)}, {S}, "
+                             f"{NUM_TIME_FEATURES}] on the device (time_features), got {tuple(tfeat.shape)}")
+        if inplace:
+            o4, bufs = p4, self._buffers(B, S, p4.dtype, p4.shape, False)[0]
+        elif out is not None:
+            if out.shape != pred.shape or out.dtype != pred.dtype or not out.is_cuda:
+                raise ValueError("out must match the prediction's shape, dtype and device")
+            o4 = out if out.dim() == 4 else out.unsqueeze(0)
+            if o4.stride(3) != 1:
+                raise ValueError("out needs unit channel stride")
+            bufs = self._buffers(B, S, p4.dtype, p4.shape, False)[0]
+        else:
+            bufs, o4 = self._buffers(B, S, p4.dtype, p4.shape, True)
+        if feat_out is not None:
+            assert feat_out.shape == (B, len(self.ordered_stations), S, NUM_FEATURES) and feat_out.is_contiguous()
+            assert feat_out.dtype == torch.float64 and feat_out.is_cuda
+        f64 = int(p4.dtype == torch.float64)
+        L, st = hip.lib(), hip._stream()
+        bias, ncorr = bufs["bias"], bufs["n"]
+        hip._check(L.gcl_mos_forest_predict(
+            self._nodes.data_ptr(), self._roots.data_ptr(), self.forest.num_trees, self.forest.baseline,
+            p4.data_ptr(), f64, p4.stride(0), p4.stride(1), p4.stride(2), S, *self.chans, self._gidx.data_ptr(),
+            self._gstart.data_ptr(), self.num_points, len(self.ordered_stations), tfeat.data_ptr(), bias.data_ptr(),
+            feat_out.data_ptr() if feat_out is not None else None, ncorr.data_ptr(), B, st))
+        hip._check(L.gcl_mos_idw_apply(
+            p4.data_ptr(), f64, p4.stride(0), p4.stride(1), p4.stride(2), o4.data_ptr(), o4.stride(0), o4.stride(1),
+            o4.stride(2), G, S, C, self.chans[0], self._lat.data_ptr(), self._lon.data_ptr(), self._gidx.data_ptr(),
+            self.num_points, bias.data_ptr(), int(self.idw), self.power, self.radius, ncorr.data_ptr(), B, st))
+        res = pred if inplace else (out if out is not None else (o4 if pred.dim() == 4 else o4[0]))
+        return res, ncorr
+
+    @property
+    def station_bias(self) -> torch.Tensor:
+        """The last call's per-point biases, float64 [B, points, steps] (of the most recently used shape)."""
+        return next(reversed(self._bufs.values()))["bias"]
+
+
+class CapturedLearnedMOS(LearnedMOS, Captured):
+    """`LearnedMOS.apply` replayed from a hipGraph (capture.Captured): the forecast and the time features are the
+    graph's arguments, so a new forecast or new valid times replay the same graph.  Returns the graph's output buffers
+    (overwritten by the next call)."""
+
+    def __init__(self, *args, use_graph: bool = True, **kw):
+        LearnedMOS.__init__(self, *args, **kw)
+        Captured.__init__(self, use_graph=use_graph, recapture=True)
+
+    def _work(self, pred, tfeat):
+        return LearnedMOS.apply(self, pred, tfeat)
+
+    def __call__(self, pred: torch.Tensor, tfeat: torch.Tensor):
+        if not self.has_t2m:
+            return pred, None
+        return self._run(pred, tfeat)
+
+
+def apply_learned_mos_t2m(prediction_phys: torch.Tensor, var_order: list, model_bundle, latitudes, longitudes,
+                          forecast_valid_times, station_lat: float = 56.173, station_lon: float = 92.493,
+                          station_elev: float = 287.0, stations: Optional[list] = None, spatial_idw: bool = False,
+                          idw_power: float = 2.0, idw_max_radius_km: float = 300.0):
+    """The reference's `apply_learned_mos_t2m` on the device: `(corrected, n_corrected)` when t2m is present (a list
+    of ints for a batched prediction), the input itself otherwise.  Synchronises once, for the count."""
+    if "t2m" not in var_order:
+        return prediction_phys
+    if stations is None:
+        stations = [{"lat": station_lat, "lon": station_lon, "elev": station_elev, "name": "default"}]
+    p = prediction_phys
+    dev = p.device if isinstance(p, torch.Tensor) and p.is_cuda else None
+    if dev is None:
+        raise RuntimeError("apply_learned_mos_t2m needs a GPU tensor (there is no CPU fallback)")
+    mos = LearnedMOS(model_bundle, var_order, latitudes, longitudes, stations, spatial_idw, idw_power,
+                     idw_max_radius_km, device=dev)
+    B = p.shape[0] if p.dim() == 4 else 1
+    steps = p.shape[-2]
+    times = _times_2d(forecast_valid_times, B)
+    if any(len(t) != steps for t in times):
+        raise ValueError(f"{len(times[0])} valid times for {steps} forecast steps")
+    tfeat = mos.time_features(times if p.dim() == 4 else times[0])
+    if tfeat.shape[0] != B:
+        tfeat = tfeat.expand(B, -1, -1, -1).contiguous()
+    out = torch.empty_like(p, memory_format=torch.contiguous_format)
+    corrected, n = mos.apply(p, tfeat, out=out)
+    counts = n.cpu().tolist()
+    return corrected, (counts if p.dim() == 4 else counts[0])

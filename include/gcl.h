@@ -587,6 +587,45 @@ int gcl_taper_blend(const float* mask, const float* r, int64_t ldr, int64_t bsr,
                     int64_t ldg, int64_t bsg, float* out, int64_t ldo, int64_t bso, int32_t nt, int32_t K,
                     int32_t B, gcl_stream_t stream);
 
+/* ---- MOS correction of t2m (csrc/mos.hip; src/postprocessing/mos_correction.py) ----
+ * Forests are flattened HistGradientBoostingRegressors: 16-byte nodes {double v; uint32 left; uint32 meta}, meta =
+ * right (bits 0-23) | feature << 24 | missing_go_to_left << 29 | is_leaf << 30, v the threshold or the leaf value;
+ * roots[t] is the node index of tree t.  Predictions are rows pred[b * bs + g * gs + s * ss + c], float32 or float64
+ * (f64 = 1), channels contiguous. */
+/* sklearn's HistGradientBoostingRegressor.predict on n float64 rows X[n, 20] (the `model.predict` of
+ * mos_correction.py:319): y[r] = ((baseline + v0) + v1) + ..., NaN follows missing_go_to_left. */
+int gcl_mos_forest_eval(const void* nodes, const int32_t* roots, int32_t ntrees, double baseline, const double* X,
+                        int32_t n, double* y, gcl_stream_t stream);
+/* Station bias recurrence of apply_learned_mos_t2m (mos_correction.py:307-323 with the features of
+ * _build_features_from_forecast :98-173): for every sample b and group q (stations group_start[q] ..
+ * group_start[q+1] - 1 sharing grid row grid_idx[q]) and step s in order, each station's features (forecast ones
+ * from channels c_* of the row, -1 = absent; host ones tfeat[b, station, s, 0..7] = hour sin / cos, doy sin / cos,
+ * solar elevation, station lat / lon / elev; lags from the group's previous corrected t2m) go through the forest,
+ * and bias[b, q, s] = numpy mean of the group.  feat_out[b, station, s, 20] (optional) receives the features.
+ * n_corrected[b] (optional) is set to 0 for gcl_mos_idw_apply to count into.  At most 128 groups and 128 stations
+ * per group. */
+int gcl_mos_forest_predict(const void* nodes, const int32_t* roots, int32_t ntrees, double baseline,
+                           const void* pred, int32_t pred_f64, int64_t bs, int64_t gs, int64_t ss, int32_t steps,
+                           int32_t c_t2m, int32_t c_u, int32_t c_v, int32_t c_sp, int32_t c_tp,
+                           const int32_t* grid_idx, const int32_t* group_start, int32_t ngroups, int32_t nst,
+                           const double* tfeat, double* bias, double* feat_out, int32_t* n_corrected, int32_t B,
+                           gcl_stream_t stream);
+/* Spread and apply (mos_correction.py:187-241 _idw_interpolate_bias and :325-338): out[.., t2m] = in + field in
+ * float64, rounded to the input's type.  idw = 1: field = the IDW of bias[b, k, s] over the K points pt_idx[k]
+ * (haversine km from node_lat / node_lon, points within `radius`, weights 1 / max(d, 0.1)^power normalised; a
+ * point's own row takes its bias), n_corrected[b] += rows with max |field| > 1e-6.  idw = 0: only the K point rows
+ * change, n_corrected[b] += K.  out != in also copies every other element. */
+int gcl_mos_idw_apply(const void* in, int32_t f64, int64_t bs, int64_t gs, int64_t ss, void* out, int64_t obs,
+                      int64_t ogs, int64_t oss, int32_t G, int32_t steps, int32_t C, int32_t t2m,
+                      const double* node_lat, const double* node_lon, const int32_t* pt_idx, int32_t K,
+                      const double* bias, int32_t idw, double power, double radius, int32_t* n_corrected, int32_t B,
+                      gcl_stream_t stream);
+/* Table MOS (mos_correction.py:34-69 apply_mos_t2m): out[.., s, t2m] = in + step_bias[s] for s < nvalid, float32
+ * f32(x + f32(b)) (numpy's weak Python-float scalar) or float64 x + b.  out != in also copies every other element. */
+int gcl_mos_table_apply(const void* in, int32_t f64, int64_t bs, int64_t gs, int64_t ss, void* out, int64_t obs,
+                        int64_t ogs, int64_t oss, int32_t G, int32_t steps, int32_t C, int32_t t2m,
+                        const double* step_bias, int32_t nvalid, int32_t B, gcl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
