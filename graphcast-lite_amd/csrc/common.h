@@ -62,6 +62,27 @@ __device__ __forceinline__ float dsilu_f(float z) {
   return s * (1.f + z * (1.f - s));
 }
 
+// One element of torch.optim.Adam (no amsgrad, no maximize), src/main.py:212: the update of gcl_adam_step and
+// gcl_adam_step_groups, written once so that both round identically.  hipcc may contract a product into the add that
+// follows it, and does so differently in a scalar and a float4 loop; `adam_rounded` (an empty asm volatile) pins
+// every product so that no contraction depends on the loop shape.  The rounding is the one the scalar loop always
+// had: every product and sum rounded on its own, the final `p - step * ratio` one fused multiply-add.
+__device__ __forceinline__ float adam_rounded(float x) {
+  asm volatile("" : "+v"(x));
+  return x;
+}
+__device__ __forceinline__ void adam_elem(float& p, float g, float& m, float& v, float lr, float b1, float b2, float eps,
+                                          float wd, float bc1, float bc2_sqrt, float gscale) {
+  float gi = adam_rounded(g * gscale);
+  if (wd != 0.f) gi += adam_rounded(wd * p);
+  const float mi = adam_rounded(b1 * m) + adam_rounded((1.f - b1) * gi);
+  const float vi = adam_rounded(b2 * v) + adam_rounded(adam_rounded((1.f - b2) * gi) * gi);
+  m = mi;
+  v = vi;
+  const float denom = sqrtf(vi) / bc2_sqrt + eps;
+  p = __builtin_fmaf(-(lr / bc1), mi / denom, p);
+}
+
 // out[i*ldo + j] (+)= sum_p part[p*pstride + i*pld + j], i < R, j < C (parallel over partials, fixed order)
 int launch_reduce_parts(const float* part, int nparts, int64_t pstride, int pld, float* out, int ldo, int R, int C,
                         int accumulate, hipStream_t st);

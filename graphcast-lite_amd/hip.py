@@ -77,6 +77,8 @@ _SIGNATURES = {
     "gcl_wmse_ws_bytes": (_sz, [_i32, _i32, _i32]),
     "gcl_adam_step": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _f32, _i32, _f32, _vp]),
     "gcl_adam_step_dev": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _f32, _vp, _vp, _f32, _vp]),
+    "gcl_adam_step_groups": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _f32, _f32, _f32, _f32,
+                                       _f32, _vp]),
     "gcl_copy_rows": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _vp]),
     "gcl_dense_fwd": (C.c_int, [_vp, _i64, _i32, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _vp]),
     "gcl_dense_bwd_dx": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i32, _i32,
@@ -690,6 +692,18 @@ def adam_step_dev(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step_dev, bc_
     assert step_dev.dtype == torch.int32 and step_dev.is_cuda
     _check(lib().gcl_adam_step_dev(_p(p), _p(g), _p(m), _p(v), p.numel(), lr, beta1, beta2, eps, weight_decay,
                                    step_dev.data_ptr(), _p(bc_dev), float(grad_scale), _stream()))
+
+
+def adam_step_groups(p, g, m, v, chunk_param, active, lr, step, bc, beta1, beta2, eps, weight_decay, grad_scale=1.0):
+    """Grouped Adam over a flat bucket (see gcl.h): per-parameter `active` / `step` (int32), `lr` (float32) and `bc`
+    (float32 [P, 2] scratch) and the chunk -> parameter map `chunk_param` (int32 [p.numel() / 64]), all on the device."""
+    P = step.numel()
+    assert p.is_cuda and p.numel() % 64 == 0 and chunk_param.numel() == p.numel() // 64
+    assert step.dtype == active.dtype == chunk_param.dtype == torch.int32 and lr.dtype == bc.dtype == torch.float32
+    assert active.numel() == lr.numel() == P and bc.numel() == 2 * P
+    _check(lib().gcl_adam_step_groups(_p(p), _p(g), _p(m), _p(v), p.numel(), _pi(chunk_param), P, _pi(active),
+                                      _p(lr), _pi(step), _p(bc), beta1, beta2, eps, weight_decay, float(grad_scale),
+                                      _stream()))
 
 
 def copy_rows(src3, dst3):

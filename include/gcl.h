@@ -336,6 +336,18 @@ int gcl_adam_step_dev(float* p, const float* g, float* m, float* v, int64_t coun
                       float beta2, float eps, float weight_decay, int32_t* step_dev, float* bc_dev,
                       float grad_scale, gcl_stream_t stream);
 
+/* torch.optim.Adam with parameter groups (src/main.py:190-211) over the flat bucket, every table on the device so
+ * that a captured hipGraph replays it.  count: bucket length, a multiple of 64 (p, g, m, v 16-byte aligned); each
+ * parameter owns whole 64-float chunks and chunk_param[count / 64] names the owner of each chunk.  Per parameter
+ * (num_params entries): active (0 = frozen: its p, m, v and step are neither read nor written), lr, step (int32,
+ * incremented by the call for active parameters) and bc (2 floats of scratch: the bias corrections of its step,
+ * computed in double).  beta1, beta2, eps, weight_decay are shared by all groups; grad_scale multiplies the gradient
+ * first.  With every parameter active at one step the result is bit-equal to gcl_adam_step.  Two launches. */
+int gcl_adam_step_groups(float* p, const float* g, float* m, float* v, int64_t count, const int32_t* chunk_param,
+                         int32_t num_params, const int32_t* active, const float* lr, int32_t* step, float* bc,
+                         float beta1, float beta2, float eps, float weight_decay, float grad_scale,
+                         gcl_stream_t stream);
+
 /* Strided row copy  dst[b, i, 0:F] = src[b, i, 0:F]  (stage glue: src/models.py:837-838,860-862). */
 int gcl_copy_rows(const float* src, int64_t lds, int64_t bss, float* dst, int64_t ldd, int64_t bsd,
                   int32_t B, int32_t rows, int32_t F, gcl_stream_t stream);
