@@ -16,8 +16,6 @@
 // b&7 names an XCD group.  All row-blocks of sample s are given ids congruent to s mod 8: one
 // sample's h (2.6 MB at 64x32/F=64) then lives in ONE 4 MiB L2 and the ~7x neighbour re-reads
 // never leave the XCD.  Placement is a speed choice only; results do not depend on it.
-#include <stdlib.h>
-
 #include <algorithm>
 
 #include "common.h"
@@ -497,11 +495,6 @@ extern "C" int gcl_debug_read_agg_stamps(unsigned long long* host_out, int count
 }
 #endif
 
-int agg_env(const char* name, int dflt) {
-  const char* e = getenv(name);
-  return e ? atoi(e) : dflt;
-}
-
 struct AggArgs {
   const int32_t *rowptr, *col, *ecol, *heavy;
   const float *w, *ew;
@@ -515,10 +508,10 @@ struct AggArgs {
 template <int LPR>
 int launch_agg_halo(const AggArgs& ga, const float* h, int64_t ldh, int64_t bsh, const float* bias, float* y,
                     int64_t ldy, int64_t bsy, int32_t n, int32_t B, int32_t F, hipStream_t st) {
-  const int enabled = agg_env("GCL_AGG_HALO", 1);  // read per call: the parity tests switch it to compare the two kernels
-  static const int force_t = agg_env("GCL_AGG_HALO_T", 0);    // tuning: tile height
-  static const int bpc_env = agg_env("GCL_AGG_HALO_BPC", 0);  // tuning: blocks per CU
-  static const int nt = agg_env("GCL_AGG_NT", 1);
+  const int enabled = gcl::env_int("GCL_AGG_HALO", 1);  // read per call: the parity tests switch it to compare the two kernels
+  static const int force_t = gcl::env_int("GCL_AGG_HALO_T", 0);    // tuning: tile height
+  static const int bpc_env = gcl::env_int("GCL_AGG_HALO_BPC", 0);  // tuning: blocks per CU
+  static const int nt = gcl::env_int("GCL_AGG_NT", 1);
   if (!enabled || ga.ell_width != 8) return -1;  // the arithmetic below is that of agg_kernel<.., EW = 8>
   if ((int64_t)n * ldh * 4 >= (int64_t)1 << 31 || ldh * 4 >= (int64_t)1 << 24 || n >= 1 << 24) return -1;  // 32-bit row offsets
   constexpr int RPW = 64 / LPR;
@@ -537,13 +530,12 @@ int launch_agg_halo(const AggArgs& ga, const float* h, int64_t ldh, int64_t bsh,
   // tile-ordered graph is as fast, 79 vs 82 us - the whole batch sits in the Infinity Cache then; inside the training
   // step it is not, and the staged form wins, 88 vs 102 us per launch, so there is no batch-size switch here.)
   // persistent blocks, as many per CU as LDS allows; every block walks its share of the (tile, sample) items of its XCD group
-  const int per_cu = (int)std::min<int64_t>(8, (160 * 1024) / lds);
+  const int per_cu = (int)std::min<int64_t>(8, gcl::kLdsBytes / lds);
   const int J = 32 * (bpc_env > 0 ? bpc_env : per_cu);  // blocks per XCD
   const int mpw = (int)gcl::cdiv((hl->smax - hl->T) / RPW, 4);  // halo pieces per wave of the fullest tile
   dim3 grid((unsigned)(gcl::kNumXCD * J)), block(256);
   auto go = [&](auto kern) -> int {
-    const int rc = gcl::ensure_dyn_lds(reinterpret_cast<const void*>(kern), (size_t)lds);
-    if (rc) return rc;
+    GCL_ENSURE_DYN_LDS(kern, (size_t)lds);
     hipLaunchKernelGGL(kern, grid, block, (size_t)lds, st, hl->list, hl->cnt, reinterpret_cast<const int2*>(hl->rec),
                        ga.rowptr, hl->opos, ga.w, hl->smax, h, ldh, bsh, bias, y, ldy, bsy, n, B, F, hl->ntiles, nt);
     return GCL_OK;
@@ -593,9 +585,9 @@ int launch_agg(const AggArgs& ga, const float* h, int64_t ldh, int64_t bsh, cons
       }
     }
   }
-  static const int iter_env = agg_env("GCL_AGG_ITER", 0);  // tuning overrides (0 = per-graph default)
-  static const int ew_env = agg_env("GCL_AGG_EW", 0);
-  static const int nt = agg_env("GCL_AGG_NT", 1);  // non-temporal output stores (measured: -7..-12 %)
+  static const int iter_env = gcl::env_int("GCL_AGG_ITER", 0);  // tuning overrides (0 = per-graph default)
+  static const int ew_env = gcl::env_int("GCL_AGG_EW", 0);
+  static const int nt = gcl::env_int("GCL_AGG_NT", 1);  // non-temporal output stores (measured: -7..-12 %)
   int ewidth = ew_env > 0 ? ew_env : ga.ell_width;
   if (ewidth > EL) ewidth = EL;
   ewidth = ewidth >= 8 ? 8 : ewidth >= 4 ? 4 : ewidth >= 2 ? 2 : 1;

@@ -15,14 +15,9 @@ constexpr int kMaxStations = 16384;  // one float64 m x m factor: 2 GiB at the l
 
 // ---------------------------------------------------------------------------------------------------------------
 // Nudging.  Both of the reference's formulas, evaluated exactly as torch CPU does in float32: one rounding per
-// operation, never contracted into an FMA.  hipcc builds with -ffp-contract=fast, which fuses a product into the
-// following add even through `__fmul_rn` / `__fadd_rn` and ignores `#pragma clang fp contract`, so every product
-// passes through an empty asm statement: the add then sees an opaque, already rounded value.
+// operation, never contracted into an FMA: every product passes through gcl::rounded (common.h), so the add sees an
+// opaque, already rounded value.
 // ---------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float rounded(float x) {
-  asm volatile("" : "+v"(x));
-  return x;
-}
 
 __global__ __launch_bounds__(256) void nudge_kernel(const float* __restrict__ f, int64_t ldf, int64_t bsf,
                                                    const float* __restrict__ o, int64_t ldo, int64_t bso,
@@ -41,9 +36,9 @@ __global__ __launch_bounds__(256) void nudge_kernel(const float* __restrict__ f,
     float v = fv;
     if (!__builtin_isnan(ov) && (!mask || mask[c])) {
       if (form == 0)
-        v = fv + rounded(c1 * (ov - fv));  // f + alpha (o - f)               (nudging.py:91-92)
+        v = fv + gcl::rounded(c1 * (ov - fv));  // f + alpha (o - f)               (nudging.py:91-92)
       else
-        v = rounded(c0 * fv) + rounded(c1 * ov);  // (1 - alpha) f + alpha o  (nudging.py:205)
+        v = gcl::rounded(c0 * fv) + gcl::rounded(c1 * ov);  // (1 - alpha) f + alpha o  (nudging.py:205)
     }
     out[b * bst + (int64_t)g * ldt + c] = v;
   }
@@ -119,12 +114,6 @@ __global__ __launch_bounds__(256) void oi_mirror_kernel(double* __restrict__ M, 
 // then a fixed butterfly), independent of n and of the other columns.
 constexpr int kRhs = 8;
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
 template <bool FWD, typename TO>
 __global__ __launch_bounds__(256) void oi_tri_kernel(const double* __restrict__ M, int32_t m,
                                                      const double* __restrict__ in, TO* __restrict__ out, int32_t n) {
@@ -145,7 +134,7 @@ __global__ __launch_bounds__(256) void oi_tri_kernel(const double* __restrict__ 
       if (q < nq) acc[q] = fma(x, in[(int64_t)(q0 + q) * m + c], acc[q]);
   }
 #pragma unroll
-  for (int q = 0; q < kRhs; ++q) acc[q] = wave_sum(acc[q]);
+  for (int q = 0; q < kRhs; ++q) acc[q] = gcl::wave_sum(acc[q]);
   if (lane < nq) {
     double v = 0.0;
 #pragma unroll
@@ -260,11 +249,6 @@ int launch_analysis(hipStream_t st, int nblk, int ncol, const float* xb, int64_t
   return GCL_OK;
 }
 
-inline unsigned grid_cap(int64_t total) {
-  const int64_t nb = gcl::cdiv(total > 0 ? total : 1, 256);
-  return (unsigned)(nb > 4096 ? 4096 : nb);
-}
-
 }  // namespace
 
 extern "C" int gcl_oi_max_stations(void) { return kMaxStations; }
@@ -277,7 +261,7 @@ extern "C" int gcl_nudge(const float* f, int64_t ldf, int64_t bsf, const float* 
   GCL_CHECK_ARG(B > 0 && G >= 0 && C > 0 && ldf >= C && ldo >= C && ldt >= C, "nudge: bad shape");
   const int64_t total = (int64_t)B * G * C;
   if (total == 0) return GCL_OK;
-  hipLaunchKernelGGL(nudge_kernel, dim3(grid_cap(total)), dim3(256), 0, (hipStream_t)stream, f, ldf, bsf, o, ldo, bso,
+  hipLaunchKernelGGL(nudge_kernel, dim3(gcl::grid_for(total, 4096)), dim3(256), 0, (hipStream_t)stream, f, ldf, bsf, o, ldo, bso,
                      chan_mask, c0, c1, form, out, ldt, bst, B, G, C);
   GCL_CHECK_LAUNCH();
   return GCL_OK;
@@ -328,7 +312,7 @@ extern "C" int gcl_oi_innovation(const float* obs, int64_t ldo, int64_t bso, con
   GCL_CHECK_ARG(obs && xb && obs_row && node_row && chans && rhs, "oi_innovation: null argument");
   GCL_CHECK_ARG(m > 0 && nch > 0 && B > 0, "oi_innovation: bad shape");
   const int64_t total = (int64_t)B * nch * m;
-  hipLaunchKernelGGL(oi_innov_kernel, dim3(grid_cap(total)), dim3(256), 0, (hipStream_t)stream, obs, ldo, bso, xb, ldx,
+  hipLaunchKernelGGL(oi_innov_kernel, dim3(gcl::grid_for(total, 4096)), dim3(256), 0, (hipStream_t)stream, obs, ldo, bso, xb, ldx,
                      bsx, obs_row, node_row, chans, m, nch, B, rhs);
   GCL_CHECK_LAUNCH();
   return GCL_OK;

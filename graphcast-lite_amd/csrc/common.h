@@ -4,6 +4,8 @@
 #include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
 
 #include "../../include/gcl.h"
 
@@ -37,12 +39,36 @@ void set_error(const char* fmt, ...);
     }                                                                          \
   } while (0)
 
+// Raise the dynamic-LDS limit of kernel `kern` to `bytes` (gcl::ensure_dyn_lds); on failure, return its error code.
+#define GCL_ENSURE_DYN_LDS(kern, bytes)                                   \
+  do {                                                                    \
+    const int _rc = gcl::ensure_dyn_lds((const void*)(kern), (bytes));    \
+    if (_rc) return _rc;                                                  \
+  } while (0)
+
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
+// blocks of 256 threads for `total` items, at most `cap` of them (grid-stride loops beyond)
+inline unsigned grid_for(int64_t total, int cap = 4096) {
+  int64_t nb = cdiv(total > 0 ? total : 1, 256);
+  return (unsigned)(nb > cap ? cap : nb);
+}
+
+// Environment switches: an integer (`dflt` when unset), and whether a string switch is set to `value`.  Each call
+// site decides when it reads its switch (once per process in a function-local static, per graph or per call).
+inline int env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : dflt;
+}
+inline bool env_is(const char* name, const char* value) {
+  const char* e = getenv(name);
+  return e && strcmp(e, value) == 0;
+}
 
 constexpr int kWave = 64;     // CDNA wavefront
 constexpr int kNumXCD = 8;    // MI355X: 8 XCDs, blocks are dealt round-robin over them
 constexpr int kNumCU = 256;
+constexpr int kLdsBytes = 160 * 1024;  // LDS of one CU
 constexpr int kEll = 8;      // stride of the ELL prefix arrays
 constexpr int kHeavy = 64;   // rows with more edges than this get a whole block
 constexpr int kHaloRec = 16;             // edge records per row held in registers (one per lane of a 16-lane row group)
@@ -62,21 +88,46 @@ __device__ __forceinline__ float dsilu_f(float z) {
   return s * (1.f + z * (1.f - s));
 }
 
-// One element of torch.optim.Adam (no amsgrad, no maximize), src/main.py:212: the update of gcl_adam_step and
-// gcl_adam_step_groups, written once so that both round identically.  hipcc may contract a product into the add that
-// follows it, and does so differently in a scalar and a float4 loop; `adam_rounded` (an empty asm volatile) pins
-// every product so that no contraction depends on the loop shape.  The rounding is the one the scalar loop always
-// had: every product and sum rounded on its own, the final `p - step * ratio` one fused multiply-add.
-__device__ __forceinline__ float adam_rounded(float x) {
+// Exact rounding: a value passed through here is opaque to the optimiser (an empty asm volatile), so a product is
+// rounded on its own and cannot be contracted into the add that follows.  hipcc builds with -ffp-contract=fast, which
+// fuses even through __fmul_rn / __dmul_rn and ignores `#pragma clang fp contract`.  This is what keeps the kernels
+// that promise torch's CPU results bit for bit (nudging, regrid, blend, MOS) and the two Adam steps in agreement.
+__device__ __forceinline__ float rounded(float x) {
   asm volatile("" : "+v"(x));
   return x;
 }
+__device__ __forceinline__ double rounded(double x) {
+  asm volatile("" : "+v"(x));
+  return x;
+}
+
+// sum over the 64 lanes of a wave, in a fixed butterfly order (every lane gets the sum)
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+
+__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
+__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
+__device__ __forceinline__ float4 add4(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
+
+// One element of torch.optim.Adam (no amsgrad, no maximize), src/main.py:212: the update of gcl_adam_step and
+// gcl_adam_step_groups, written once so that both round identically.  hipcc may contract a product into the add that
+// follows it, and does so differently in a scalar and a float4 loop; `rounded` pins every product so that no
+// contraction depends on the loop shape.  The rounding is the one the scalar loop always had: every product and sum
+// rounded on its own, the final `p - step * ratio` one fused multiply-add.
 __device__ __forceinline__ void adam_elem(float& p, float g, float& m, float& v, float lr, float b1, float b2, float eps,
                                           float wd, float bc1, float bc2_sqrt, float gscale) {
-  float gi = adam_rounded(g * gscale);
-  if (wd != 0.f) gi += adam_rounded(wd * p);
-  const float mi = adam_rounded(b1 * m) + adam_rounded((1.f - b1) * gi);
-  const float vi = adam_rounded(b2 * v) + adam_rounded(adam_rounded((1.f - b2) * gi) * gi);
+  float gi = rounded(g * gscale);
+  if (wd != 0.f) gi += rounded(wd * p);
+  const float mi = rounded(b1 * m) + rounded((1.f - b1) * gi);
+  const float vi = rounded(b2 * v) + rounded(rounded((1.f - b2) * gi) * gi);
   m = mi;
   v = vi;
   const float denom = sqrtf(vi) / bc2_sqrt + eps;

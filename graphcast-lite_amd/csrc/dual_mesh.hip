@@ -14,9 +14,9 @@
 
 namespace {
 
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
-__device__ __forceinline__ float4 add4(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
+using gcl::add4;  // float4 helpers (common.h)
+using gcl::ld4;
+using gcl::st4;
 __device__ __forceinline__ float4 silu4(float4 v) {
   return make_float4(gcl::silu_f(v.x), gcl::silu_f(v.y), gcl::silu_f(v.z), gcl::silu_f(v.w));
 }
@@ -56,12 +56,6 @@ __global__ __launch_bounds__(256) void segment_wsum_kernel(const float* __restri
 
 // One wave per row (D <= 256: 4 columns per lane).  The statistics follow ln_fwd_kernel (norm.hip): mean, then the
 // biased variance of the deviations, rstd = 1 / sqrt(var + eps).
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
 __global__ __launch_bounds__(256) void cross_update_fwd_kernel(const float* __restrict__ h, int64_t ldh, int64_t bsh,
                                                                const float* __restrict__ msg, int64_t ldm, int64_t bsm,
                                                                const int32_t* __restrict__ rowptr,
@@ -90,7 +84,7 @@ __global__ __launch_bounds__(256) void cross_update_fwd_kernel(const float* __re
       x = make_float4(hv.x + acc.x * inv, hv.y + acc.y * inv, hv.z + acc.z * inv, hv.w + acc.w * inv);
       st4(pre + row * D + c0, x);
     }
-    const float mean = wave_sum(x.x + x.y + x.z + x.w) * invD;
+    const float mean = gcl::wave_sum(x.x + x.y + x.z + x.w) * invD;
     const float d0 = on ? x.x - mean : 0.f, d1 = on ? x.y - mean : 0.f, d2 = on ? x.z - mean : 0.f,
                 d3 = on ? x.w - mean : 0.f;
     float sq;
@@ -99,7 +93,7 @@ __global__ __launch_bounds__(256) void cross_update_fwd_kernel(const float* __re
       const float q0 = d0 * d0, q1 = d1 * d1, q2 = d2 * d2, q3 = d3 * d3;
       sq = (q0 + q1) + (q2 + q3);
     }
-    const float var = wave_sum(sq) * invD;
+    const float var = gcl::wave_sum(sq) * invD;
     const float rstd = 1.0f / sqrtf(var + eps);
     if (on)
       st4(y + row * D + c0, make_float4(d0 * rstd * g.x + bt.x, d1 * rstd * g.y + bt.y, d2 * rstd * g.z + bt.z,

@@ -11,7 +11,6 @@
 // the only shuffles are the head-mean in the epilogue (forward) and the C-channel dot products
 // (backward).  Constraints per launch: C % 4 == 0, C <= 256; other head counts / widths run as head chunks (gat_check).
 #include <math.h>
-#include <stdlib.h>
 
 #include <algorithm>
 #include <vector>
@@ -1216,21 +1215,20 @@ static int gat_fwd_impl(const gcl_graph_t* g, const float* h, int64_t ldh, int64
   hipStream_t st = (hipStream_t)stream;
   {
     // one head on a graph with a tile layout: everything of the layer from one LDS image per tile (gat_halo_fwd_kernel)
-    const char* ev = getenv("GCL_GAT_HALO");  // read per call: the parity test compares the two forms
+    const int halo_on = gcl::env_int("GCL_GAT_HALO", 1);  // read per call: the parity test compares the two forms
     const gcl_halo& hl = g->halo[0][0];
     const int lprh = C / 4;
     const int64_t ldsb = (int64_t)(hl.smax + 1) * lprh * 16 + (int64_t)(hl.smax + 1 + 64) * 4;
-    if (!(ev && atoi(ev) == 0) && H == 1 && (C == 64 || C == 128) && hl.T == 64 && g->n_heavy == 0 && ldsb <= 80 * 1024 &&
+    if (halo_on && H == 1 && (C == 64 || C == 128) && hl.T == 64 && g->n_heavy == 0 && ldsb <= 80 * 1024 &&
         (int64_t)g->n * ldh * 4 < ((int64_t)1 << 31) && ldh * 4 < (1 << 24) && g->n < (1 << 24) && gcl::aligned16(att_src) &&
         gcl::aligned16(att_dst) && (!bias || gcl::aligned16(bias))) {
       const int rpw = 64 / lprh;
       const int mpw = (int)gcl::cdiv((hl.smax - 64) / rpw, 4);
       if (mpw <= 16) {
-        const int per_cu = (int)std::min<int64_t>(8, (160 * 1024) / ldsb);
+        const int per_cu = (int)std::min<int64_t>(8, gcl::kLdsBytes / ldsb);
         dim3 grid((unsigned)(gcl::kNumXCD * 32 * per_cu));
         auto go = [&](auto kern) -> int {
-          const int rc2 = gcl::ensure_dyn_lds((const void*)kern, (size_t)ldsb);
-          if (rc2) return rc2;
+          GCL_ENSURE_DYN_LDS(kern, (size_t)ldsb);
           hipLaunchKernelGGL(kern, grid, dim3(256), (size_t)ldsb, st, hl.list, hl.cnt, reinterpret_cast<const int2*>(hl.rec),
                              g->rowptr, hl.opos, hl.smax, h, ldh, bsh, att_src, att_dst, bias, a_src, a_dst, alpha, y, ldy,
                              bsy, g->n, g->e, B, C, hl.ntiles, tab);
@@ -1301,8 +1299,7 @@ extern "C" int gcl_gat_fwd_tab(const gcl_graph_t* g, const float* h, int64_t ldh
 
 extern "C" int gcl_gat_tab_ok(const gcl_graph_t* g, int64_t ldh, int32_t H, int32_t C) {
   if (!g || g->kind != GCL_GRAPH_GAT || H != 1 || !(C == 64 || C == 128) || g->n_heavy || g->n_theavy) return 0;
-  const char* ev = getenv("GCL_GAT_HALO");
-  if (ev && atoi(ev) == 0) return 0;
+  if (!gcl::env_int("GCL_GAT_HALO", 1)) return 0;
   const gcl_halo& hf = g->halo[0][0];
   const gcl_halo& ht = g->halo[1][0];
   if (hf.T != 64 || ht.T != 64) return 0;
@@ -1357,13 +1354,13 @@ static int gat_bwd_impl(const gcl_graph_t* g, const float* dy, int64_t lddy, int
   int halo_bparts = 0;  // partial records of d_bias (column sums of dy) written by the staged src-side kernel
   {
     // one head on a graph with tile layouts in both directions: both edge passes from LDS images (gat_halo_bwd_*_kernel)
-    const char* ev = getenv("GCL_GAT_HALO");
+    const int halo_on = gcl::env_int("GCL_GAT_HALO", 1);
     const gcl_halo& hf = g->halo[0][0];
     const gcl_halo& ht = g->halo[1][0];
     const int lprh = C / 4;
     const int64_t ldsd = (int64_t)(hf.smax + 1) * lprh * 16 + (int64_t)(64 + 128 + 8) * 4;  // image + a_s of up to 64 + 128 staged rows
     const int64_t ldss = (int64_t)(ht.smax + 1) * lprh * 16;
-    if (!(ev && atoi(ev) == 0) && H == 1 && (C == 64 || C == 128) && hf.T == 64 && ht.T == 64 && g->n_heavy == 0 &&
+    if (halo_on && H == 1 && (C == 64 || C == 128) && hf.T == 64 && ht.T == 64 && g->n_heavy == 0 &&
         g->n_theavy == 0 && hf.smax - 64 <= 128 && ldsd <= 80 * 1024 && ldss <= 80 * 1024 && vdy &&
         (int64_t)g->n * ldh * 4 < ((int64_t)1 << 31) && ldh * 4 < (1 << 24) && (int64_t)g->n * lddy * 4 < ((int64_t)1 << 31) &&
         lddy * 4 < (1 << 24) && g->n < (1 << 24) && gcl::aligned16(att_src) && gcl::aligned16(att_dst)) {
@@ -1371,9 +1368,8 @@ static int gat_bwd_impl(const gcl_graph_t* g, const float* dy, int64_t lddy, int
       const int mpd = (int)gcl::cdiv((hf.smax - 64) / rpw, 4), mps = (int)gcl::cdiv((ht.smax - 64) / rpw, 4);
       if (mpd <= 16 && mps <= 16) {
         auto god = [&](auto kern) -> int {
-          const int rc2 = gcl::ensure_dyn_lds((const void*)kern, (size_t)ldsd);
-          if (rc2) return rc2;
-          const int per_cu = (int)std::min<int64_t>(8, (160 * 1024) / ldsd);
+          GCL_ENSURE_DYN_LDS(kern, (size_t)ldsd);
+          const int per_cu = (int)std::min<int64_t>(8, gcl::kLdsBytes / ldsd);
           hipLaunchKernelGGL(kern, dim3((unsigned)(gcl::kNumXCD * 32 * per_cu)), dim3(256), (size_t)ldsd, st, hf.list, hf.cnt,
                              reinterpret_cast<const int2*>(hf.rec), g->rowptr, hf.opos, hf.smax, dy, lddy, bsdy, h, ldh, bsh,
                              a_src, a_dst, alpha, de, dad, part, g->n, g->e, B, C, hf.ntiles, tab);
@@ -1381,9 +1377,8 @@ static int gat_bwd_impl(const gcl_graph_t* g, const float* dy, int64_t lddy, int
           return GCL_OK;
         };
         auto gos = [&](auto kern) -> int {
-          const int rc2 = gcl::ensure_dyn_lds((const void*)kern, (size_t)ldss);
-          if (rc2) return rc2;
-          const int per_cu = (int)std::min<int64_t>(8, (160 * 1024) / ldss);
+          GCL_ENSURE_DYN_LDS(kern, (size_t)ldss);
+          const int per_cu = (int)std::min<int64_t>(8, gcl::kLdsBytes / ldss);
           hipLaunchKernelGGL(kern, dim3((unsigned)(gcl::kNumXCD * 32 * per_cu)), dim3(256), (size_t)ldss, st, ht.list, ht.cnt,
                              reinterpret_cast<const int2*>(ht.rec), g->trowptr, ht.opos, g->tslot, ht.smax, dy, lddy, bsdy, alpha,
                              de, dad, att_src, att_dst, das, dh, lddh, bsdh, d_bias ? cs_ws : nullptr, g->n, g->e, B, C, ht.ntiles);

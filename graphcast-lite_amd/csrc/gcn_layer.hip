@@ -22,33 +22,14 @@
 //   * Rows with more in-edges than the ELL prefix finish in a per-tile fix-up loop (read-modify-write of
 //     the wave's LDS tile) so the main path stays branch-free; sums keep PyG edge order either way.
 // Shapes: Fin % 4 == 0, Fin <= 64, Fout <= 64, graphs without heavy rows (in-degree <= 64).
-#include <stdlib.h>
-
 #include "common.h"
 #include "halo.h"
+#include "mfma_io.h"
 #include "x3.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr unsigned kOOB = 0x80000000u;
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, int64_t nbytes) {
-  const int64_t cap = 0x7FFFFF00;
-  const int n = (int)(nbytes < 0 ? 0 : (nbytes > cap ? cap : nbytes));
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, n, 0x00020000);
-}
-template <int AUX = 0>  // cache-policy bits: 2 = non-temporal
-__device__ __forceinline__ void buf_st4(__amdgpu_buffer_rsrc_t r, unsigned off, float4 v) {
-  u32x4 u = {__builtin_bit_cast(unsigned, v.x), __builtin_bit_cast(unsigned, v.y), __builtin_bit_cast(unsigned, v.z),
-             __builtin_bit_cast(unsigned, v.w)};
-  __builtin_amdgcn_raw_buffer_store_b128(u, r, off, 0, AUX);
-}
-__device__ float4 gl_zero4[1];
-
-__device__ __forceinline__ int d_row(int reg, int lane) { return (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5); }
-
+using namespace gcl::mfma_io;  // f32x16, d_row, buffer stores, zero4 (mfma_io.h)
 using gcl::x3::bf16x8;  // exact 3-way bf16 operand split: x3.h
 using gcl::x3::Pk3;
 using gcl::x3::split2;
@@ -116,7 +97,7 @@ __device__ __forceinline__ void stage_panel(float* Wl, const float* __restrict__
       const int j = idx / KE, k = idx - j * KE;
       const bool ok = (idx < total) && (j < N) && (k < K);
       const float* src = ok ? (TR ? W + (int64_t)k * ldw + j : W + (int64_t)j * ldw + k)
-                            : reinterpret_cast<const float*>(gl_zero4);
+                            : reinterpret_cast<const float*>(zero4);
       wv[u] = *src;
     }
 #pragma unroll
@@ -941,11 +922,6 @@ __global__ __launch_bounds__(256, 3) void gcn_halo_fwd_kernel(
 #endif
 }
 
-int env_int(const char* name, int dflt) {
-  const char* e = getenv(name);
-  return e ? atoi(e) : dflt;
-}
-
 }  // namespace
 
 #ifdef GCL_STAMPS
@@ -966,8 +942,8 @@ static int halo_layer_launch(const gcl_graph_t* g, const float* x, int64_t ldx, 
                              int32_t rows_out, hipStream_t st, bool* launched) {
   *launched = false;
   const int32_t n = g->n;
-  const int halo_on = env_int("GCL_GCN_HALO", 1);  // read per call: the parity test compares the two kernels
-  const int x3_on = env_int("GCL_X3", 1) && env_int("GCL_X3_GCN", 1);  // per call, as in gcl_gcn_layer_fwd_tab_ok
+  const int halo_on = gcl::env_int("GCL_GCN_HALO", 1);  // read per call: the parity test compares the two kernels
+  const int x3_on = gcl::env_int("GCL_X3", 1) && gcl::env_int("GCL_X3_GCN", 1);  // per call, as in gcl_gcn_layer_fwd_tab_ok
   const gcl_halo& hl = g->halo[0][0];
   const int hp4 = hl.T == 64 ? (int)gcl::cdiv((hl.smax - 64) / 4, 4) : 99;
   const int KPh = Fin + 2;
@@ -983,13 +959,12 @@ static int halo_layer_launch(const gcl_graph_t* g, const float* x, int64_t ldx, 
         (int64_t)n * ldy * 4 < ((int64_t)1 << 31)))
     return GCL_OK;
   if (tab && hp4 > 4) return GCL_OK;  // the table variant exists for the interleaved-issue form only
-  static const int bpc_env = env_int("GCL_GCN_HALO_BPC", 0);
-  const int per_cu = (int)((160 * 1024) / ldsh);
+  static const int bpc_env = gcl::env_int("GCL_GCN_HALO_BPC", 0);
+  const int per_cu = (int)(gcl::kLdsBytes / ldsh);
   const int Jx = 32 * (bpc_env > 0 ? bpc_env : per_cu);
   dim3 grid((unsigned)(gcl::kNumXCD * Jx));
   auto go = [&](auto kern) -> int {
-    const int rc = gcl::ensure_dyn_lds((const void*)kern, ldsh);
-    if (rc) return rc;
+    GCL_ENSURE_DYN_LDS(kern, ldsh);
     hipLaunchKernelGGL(kern, grid, dim3(256), ldsh, st, hl.list, hl.cnt, reinterpret_cast<const int2*>(hl.rec), g->rowptr,
                        hl.opos, g->w, hl.smax, x, ldx, bsx, slope, W, bias, y, ldy, bsy, n, B, Fin, Fout, Fout_store,
                        hl.ntiles, tab);
@@ -999,7 +974,7 @@ static int halo_layer_launch(const gcl_graph_t* g, const float* x, int64_t ldx, 
   // hp4 <= 4 (the icosphere meshes: <= 64 halo rows per tile): non-temporal stores straight from the accumulator and
   // the next item's DMA pieces issued between the k-steps of the dense part (in the step 111.5 -> 102.6 us per mesh
   // layer; GCL_GCN_HALO_FORM=0 selects the first form - DMA issue up front, staged 16-byte stores - for comparison)
-  const int form_env = env_int("GCL_GCN_HALO_FORM", 1);
+  const int form_env = gcl::env_int("GCL_GCN_HALO_FORM", 1);
   if (tab)
     rc = act == GCL_ACT_PRELU  ? go(&gcn_halo_fwd_kernel<gcl::kActPrelu, 4, 2, true, true, true>)
          : act == GCL_ACT_SILU ? go(&gcn_halo_fwd_kernel<gcl::kActSilu, 4, 2, true, true, true>)
@@ -1059,7 +1034,7 @@ extern "C" int gcl_gcn_layer_fwd_rows(const gcl_graph_t* g, const float* x, int6
   const int NS = Fout_store > 32 ? 2 : 1;
   constexpr int NW12 = 12, NW8 = 8;
   const int KP = Fin + 2;
-  const int x3_env = env_int("GCL_X3", 1) && env_int("GCL_X3_GCN", 1);
+  const int x3_env = gcl::env_int("GCL_X3", 1) && gcl::env_int("GCL_X3_GCN", 1);
   const size_t wave1_b = (size_t)wave_region_f(32 * (KP > NS * 32 ? KP : NS * 32)) * sizeof(float);
   // the split-operand variant holds its A fragments in registers: 8 waves per block (256 VGPRs each) instead of 12
   const bool x3 = x3_env != 0 && (Fin % 16 == 0);
@@ -1081,7 +1056,7 @@ extern "C" int gcl_gcn_layer_fwd_rows(const gcl_graph_t* g, const float* x, int6
   do {                                                                                                              \
     constexpr int NW = X3_ ? NW8 : NW12;                                                                            \
     auto kern = gcn_fwd_kernel<NS_, ACT_, EW_, NW, false, X3_>;                                                              \
-    { const int lrc_ = gcl::ensure_dyn_lds((const void*)kern, 160 * 1024); if (lrc_) return lrc_; } \
+    GCL_ENSURE_DYN_LDS(kern, gcl::kLdsBytes);                                                                       \
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(NW * 64), lds, st, g->rowptr, g->col, g->w, g->ecol, g->ew, x, \
                        ldx, bsx, slope, W, bias, y, ldy, bsy, n, B, Fin, Fout, Fout_store, nRT, rows_out);                     \
   } while (0)
@@ -1108,12 +1083,12 @@ extern "C" int gcl_gcn_layer_fwd_rows(const gcl_graph_t* g, const float* x, int6
     if (B >= gcl::kNumXCD) grid = gcl::cdiv(grid, gcl::kNumXCD) * gcl::kNumXCD;
     if (NS == 2) {
       auto kern = gcn_fwd_kernel<2, gcl::kActNone, 8, NW, true, false>;
-      { const int lrc_ = gcl::ensure_dyn_lds((const void*)kern, 160 * 1024); if (lrc_) return lrc_; }
+      GCL_ENSURE_DYN_LDS(kern, gcl::kLdsBytes);
       hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(NW * 64), lds, st, g->rowptr, g->col, g->w, g->ecol, g->ew, x, ldx,
                          bsx, slope, W, bias, y, ldy, bsy, n, B, Fin, Fout, Fout_store, nRT, rows_out);
     } else {
       auto kern = gcn_fwd_kernel<1, gcl::kActNone, 8, NW, true, false>;
-      { const int lrc_ = gcl::ensure_dyn_lds((const void*)kern, 160 * 1024); if (lrc_) return lrc_; }
+      GCL_ENSURE_DYN_LDS(kern, gcl::kLdsBytes);
       hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(NW * 64), lds, st, g->rowptr, g->col, g->w, g->ecol, g->ew, x, ldx,
                          bsx, slope, W, bias, y, ldy, bsy, n, B, Fin, Fout, Fout_store, nRT, rows_out);
     }
@@ -1165,9 +1140,9 @@ extern "C" int gcl_gcn_layer_fwd_tab(const gcl_graph_t* g, const float* x, int64
 extern "C" int gcl_gcn_layer_fwd_tab_ok(const gcl_graph_t* g, int64_t ldx, int64_t bsx, int64_t x_rows, int32_t B,
                                         int32_t Fin, int32_t Fout) {
   if (!g || g->kind != GCL_GRAPH_GCN || g->n_heavy) return 0;
-  const int x3_on = env_int("GCL_X3", 1) && env_int("GCL_X3_GCN", 1);
+  const int x3_on = gcl::env_int("GCL_X3", 1) && gcl::env_int("GCL_X3_GCN", 1);
   const gcl_halo& hl = g->halo[0][0];
-  if (!env_int("GCL_GCN_HALO", 1) || !x3_on || hl.T != 64) return 0;
+  if (!gcl::env_int("GCL_GCN_HALO", 1) || !x3_on || hl.T != 64) return 0;
   const int hp4 = (int)gcl::cdiv((hl.smax - 64) / 4, 4);
   const size_t ldsh = (size_t)2 * (32 * (Fin + 2) > 2048 ? 32 * (Fin + 2) : 2048) * 4 + (size_t)(hl.smax + 1) * 256;
   return hp4 <= 4 && Fin % 16 == 0 && Fin > 32 && Fin <= 64 && Fout >= 1 && Fout <= 64 && g->e >= 6 * (int64_t)g->n &&

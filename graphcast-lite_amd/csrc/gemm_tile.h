@@ -14,8 +14,17 @@
 //   fragments are 8-byte LDS reads (two k-steps each) at row stride 34 (stride/2 odd: conflict-free).
 // Tiles are dealt XCD-aware: the column tiles of one row tile get consecutive slots of the SAME
 // XCD, so the second read of an X tile hits that XCD's L2.
-// Included by linear.hip (same translation unit: shares its helpers and launch plumbing).
+// Included by linear.hip (same translation unit: shares its launch plumbing).
 #pragma once
+#include "common.h"
+#include "mfma_io.h"
+#include "x3.h"
+
+enum { EPI_BIAS = 0, EPI_DX = 1 };
+
+#ifndef GCL_ST_AUX
+#define GCL_ST_AUX 0  // cache-policy bits of the streamed-out stores (2 = nt)
+#endif
 
 constexpr int kGtTN = 128, kGtKC = 32, kGtKP = kGtKC + 2;
 // MI = 32-row MFMA tiles per wave: the block tile is (64*MI) x 128.  MI = 1 (64-row tiles) is used when
@@ -31,6 +40,7 @@ __global__ __launch_bounds__(256, (MI == 1 ? 3 : 2)) void gemm_tile_kernel(
     const float* __restrict__ W, int64_t ldw, const float* __restrict__ bias, float* __restrict__ Y, int64_t ldy,
     int64_t rows, int32_t K, int32_t N, const float* __restrict__ Z, int64_t ldz, const float* __restrict__ add,
     int64_t ldadd, double* __restrict__ slope_part, int32_t nt, int64_t total, int32_t per_xcd) {
+  using namespace gcl::mfma_io;
   constexpr int TM = 64 * MI, TN = kGtTN, KC = kGtKC, KP = kGtKP;
   constexpr int NX = 2 * MI;  // float4 loads per thread for the X chunk
   extern __shared__ __align__(16) float smem[];
@@ -53,7 +63,7 @@ __global__ __launch_bounds__(256, (MI == 1 ? 3 : 2)) void gemm_tile_kernel(
   const bool has_add = add != nullptr;
 
   float4 pre[NX + 4];  // [0..NX) X, [NX..NX+4) W of the next chunk
-  const float4* zero = gcl_zero4;
+  const float4* zero = zero4;
   auto issue = [&](int64_t r0, int n0, int k0) {
 #pragma unroll
     for (int i = 0; i < NX; ++i) {
@@ -216,7 +226,7 @@ __global__ __launch_bounds__(256, (MI == 1 ? 3 : 2)) void gemm_tile_kernel(
             v += bj;
           }
           v += av[r];
-          buf_st1(ry, jok ? (unsigned)((rr * ldy + col) * 4) : kOOB, v);
+          buf_st1<GCL_ST_AUX>(ry, jok ? (unsigned)((rr * ldy + col) * 4) : kOOB, v);
         }
         __builtin_amdgcn_sched_barrier(0);  // keep the four slabs' Z / addend loads from piling up in registers
       }
@@ -253,6 +263,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tile_x3_kernel(
     const float* __restrict__ W, int64_t ldw, const float* __restrict__ bias, float* __restrict__ Y, int64_t ldy,
     int64_t rows, int32_t K, int32_t N, const float* __restrict__ Z, int64_t ldz, const float* __restrict__ add,
     int64_t ldadd, double* __restrict__ slope_part, int32_t nt, int64_t total, int32_t per_xcd) {
+  using namespace gcl::mfma_io;
   using namespace gcl::x3;
   constexpr int TM = 128, TN = 128, KC = kX3KC, RB = kX3RowB;
   constexpr int IMG = 256 * RB;  // one piece of one buffer: X rows 0..127, W rows 128..255
@@ -277,7 +288,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tile_x3_kernel(
 
   // staging map: a row chunk is 16 floats = 4 float4; 128 rows x 4 = 512 float4 per operand, 2 per thread
   float4 pre[4];  // [0..2) X, [2..4) W of the next chunk
-  const float4* zero = gcl_zero4;
+  const float4* zero = zero4;
   auto issue = [&](int64_t r0, int n0, int k0) {
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
@@ -399,7 +410,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tile_x3_kernel(
             v += bj;
           }
           v += av[r];
-          buf_st1(ry, jok ? (unsigned)((rr * ldy + col) * 4) : kOOB, v);
+          buf_st1<GCL_ST_AUX>(ry, jok ? (unsigned)((rr * ldy + col) * 4) : kOOB, v);
         }
         __builtin_amdgcn_sched_barrier(0);
       }
@@ -430,7 +441,7 @@ static inline GtGeom gt_geom(int64_t rows, int N) {
   g.nt = (N + kGtTN - 1) / kGtTN;
   // 128-row tiles unless they would give the 512 persistent blocks fewer than ~3 tiles each
   g.mi = (gcl::cdiv(rows, 128) * g.nt < 3 * 2 * gcl::kNumCU) ? 1 : 2;  // env GCL_GT_MI overrides (experiments)
-  static const int force = [] { const char* e = getenv("GCL_GT_MI"); return e ? atoi(e) : 0; }();
+  static const int force = gcl::env_int("GCL_GT_MI", 0);
   if (force == 1 || force == 2) g.mi = force;
   const int TM = 64 * g.mi;
   g.total = gcl::cdiv(rows, TM) * g.nt;

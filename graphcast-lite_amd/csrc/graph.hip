@@ -399,8 +399,7 @@ extern "C" int gcl_graph_create(const int64_t* ei, int64_t E, int32_t n, int32_t
   // processing order of the per-edge kernels: only where one sample's rows cannot sit in an XCD's 4 MiB L2 anyway
   // (>= 32 Ki rows: 16 MB at 128 channels) and the graph has no source-tile layout
   {
-    const char* oe = getenv("GCL_AGG_ORDER");  // read per graph (the dispatch tests build one graph each way)
-    const int ord_env = oe ? atoi(oe) : 1;
+    const int ord_env = gcl::env_int("GCL_AGG_ORDER", 1);  // read per graph (the dispatch tests build one graph each way)
     if (!rc && ord_env && n >= 32768) {
       for (int d = 0; d < 2 && !rc; ++d) {
         if (g->halo[d][0].T) continue;

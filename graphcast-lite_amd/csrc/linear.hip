@@ -11,55 +11,15 @@
 // Operand layouts of v_mfma_f32_32x32x2_f32 (cdna_hip_programming.md §3):
 //   A: lane l holds A[i = l&31][k = l>>5]      B: lane l holds B[k = l>>5][j = l&31]
 //   D: lane l, reg r holds D[i = (r&3) + 8*(r>>2) + 4*(l>>5)][j = l&31]
-#include <stdlib.h>
-#include <string.h>
-
 #include "common.h"
+#include "mfma_io.h"
 #include "x3.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using namespace gcl::mfma_io;  // f32x16, d_row, buffer loads / stores, zero4 (mfma_io.h)
 
-__device__ __forceinline__ int d_row(int reg, int lane) { return (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5); }
-
-enum { EPI_BIAS = 0, EPI_DX = 1 };
-
-// Raw buffer access (hardware range check): loads beyond num_records return 0, stores are dropped.
-// Keeping every global access UNCONDITIONAL keeps the kernels free of divergent branches, which is
-// what lets hipcc emit counted s_waitcnt vmcnt(N) (CDNA counts loads and stores in one in-order
-// counter; a branch around a store forces vmcnt(0) and serialises the whole store stream).
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-constexpr unsigned kOOB = 0x80000000u;  // offset that is out of range for every descriptor we build
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, int64_t nbytes) {
-  const int64_t cap = 0x7FFFFF00;
-  const int n = (int)(nbytes < 0 ? 0 : (nbytes > cap ? cap : nbytes));
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, n, 0x00020000);
-}
-__device__ __forceinline__ float buf_ld1(__amdgpu_buffer_rsrc_t r, unsigned off) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, off, 0, 0));
-}
-__device__ __forceinline__ float4 buf_ld4(__amdgpu_buffer_rsrc_t r, unsigned off) {
-  const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0);
-  return make_float4(__builtin_bit_cast(float, v.x), __builtin_bit_cast(float, v.y), __builtin_bit_cast(float, v.z),
-                     __builtin_bit_cast(float, v.w));
-}
-#ifndef GCL_ST_AUX
-#define GCL_ST_AUX 0  // cache-policy bits of the streamed-out stores (2 = nt)
-#endif
-__device__ __forceinline__ void buf_st1(__amdgpu_buffer_rsrc_t r, unsigned off, float v) {
-  __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, off, 0, GCL_ST_AUX);
-}
-// Zero page for masked loads: an out-of-range lane reads from here instead of branching around
-// its load (pointer select + unconditional plain load keeps global_load_dwordx4 and no branch).
-__device__ float4 gcl_zero4[1];
-
-// bytes of a [nrows x F] window with row stride ld (last row counted only up to F)
-__device__ __forceinline__ int64_t win_bytes(int64_t nrows, int64_t ld, int F) {
-  return nrows > 0 ? ((nrows - 1) * ld + F) * 4 : 0;
-}
-
-#include "gemm_tile.h"
+#include "gemm_tile.h"  // also EPI_BIAS / EPI_DX and GCL_ST_AUX
 
 // A/B switch while tuning (kernel argument `abl` bit 8 = keep the per-tile block barriers of round 1)
 #define gcl_lin_sync() ((abl & 8) != 0)
@@ -113,7 +73,7 @@ __global__ __launch_bounds__(256, lin_min_waves(NS, KT)) void linear_mfma_kernel
       const int j = idx / KE, k = idx - j * KE;
       const bool ok = (idx < NS * 32 * KE) && (j < N) && (k < K);
       const float* src = ok ? (trans ? W + (int64_t)k * ldw + j : W + (int64_t)j * ldw + k)
-                            : reinterpret_cast<const float*>(gcl_zero4);
+                            : reinterpret_cast<const float*>(zero4);
       wv[u] = *src;
     }
 #pragma unroll
@@ -150,12 +110,12 @@ __global__ __launch_bounds__(256, lin_min_waves(NS, KT)) void linear_mfma_kernel
       const int c = csub + 64 * (it % IPR);
       if (VEC) {
         const bool ok = (c * 4 < K) && (row < rows_ld);
-        const float4* p = ok ? reinterpret_cast<const float4*>(X + row * ldx + c * 4) : gcl_zero4;
+        const float4* p = ok ? reinterpret_cast<const float4*>(X + row * ldx + c * 4) : zero4;
         const float4 v = *p;
         pre[4 * it] = v.x; pre[4 * it + 1] = v.y; pre[4 * it + 2] = v.z; pre[4 * it + 3] = v.w;
       } else {
         const bool ok = (c < K) && (row < rows_ld);
-        const float* p = ok ? X + row * ldx + c : reinterpret_cast<const float*>(gcl_zero4);
+        const float* p = ok ? X + row * ldx + c : reinterpret_cast<const float*>(zero4);
         pre[it] = *p;
       }
     }
@@ -283,13 +243,13 @@ __global__ __launch_bounds__(256, lin_min_waves(NS, KT)) void linear_mfma_kernel
             slope_acc += neg ? (double)(v * zv[r]) : 0.0;
             v = neg ? v * zs : v;
           }
-          buf_st1(ry, jok ? (unsigned)((rr * ldy + j) * 4) : kOOB, v);
+          buf_st1<GCL_ST_AUX>(ry, jok ? (unsigned)((rr * ldy + j) * 4) : kOOB, v);
         }
       } else {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int rr = wave * 32 + d_row(r, lane);
-          buf_st1(ry, jok ? (unsigned)((rr * ldy + j) * 4) : kOOB, acc[s][r] + bj[s]);
+          buf_st1<GCL_ST_AUX>(ry, jok ? (unsigned)((rr * ldy + j) * 4) : kOOB, acc[s][r] + bj[s]);
         }
       }
     }
@@ -426,7 +386,7 @@ __global__ __launch_bounds__(256, (DwCfg<NO, NC>::min_waves)) void dw_mfma_kerne
   const float* xbase = X + rb * ldx;
   auto ld_slot = [&](const float* base, int rr, int c4, int64_t ld, int F) -> float4 {
     const bool ok = rr < nrows;
-    const float* z = reinterpret_cast<const float*>(gcl_zero4);
+    const float* z = reinterpret_cast<const float*>(zero4);
     const float* src = base + (int64_t)rr * ld + c4;
     if (VEC) return *reinterpret_cast<const float4*>((ok && c4 < F) ? src : z);
     float4 v;
@@ -583,7 +543,7 @@ __global__ __launch_bounds__(256, 1) void linear_bwd_fused_kernel(
 
   const int ysub = lane / CY, ycol = lane % CY, psub = lane / CP, pcol = lane % CP;
   float4 pre[NY + NP];
-  const float4* zero = gcl_zero4;
+  const float4* zero = zero4;
   auto issue = [&](int64_t tile) {
     const int64_t r0 = tile * TM + wave * 32;
 #pragma unroll
@@ -676,7 +636,7 @@ __global__ __launch_bounds__(256, 1) void linear_bwd_fused_kernel(
         slope_acc += neg ? (double)(v * zv[r]) : 0.0;
         v = neg ? v * slope : v;
         cs[s2] += v;
-        buf_st1(rx, jok ? (unsigned)((rr * lddx + j) * 4) : kOOB, v);
+        buf_st1<GCL_ST_AUX>(rx, jok ? (unsigned)((rr * lddx + j) * 4) : kOOB, v);
       }
     }
 
@@ -799,7 +759,7 @@ __global__ __launch_bounds__(256, 3) void linear_bwd_fused64_kernel(
 
   const int ysub = lane / CY, ycol = lane % CY, psub = lane / CP, pcol = lane % CP;
   float4 pre[NY + NP];
-  const float4* zero = gcl_zero4;
+  const float4* zero = zero4;
   auto issue = [&](int64_t tile) {
     const int64_t r0 = tile * TM + wave * 16;
 #pragma unroll
@@ -877,7 +837,7 @@ __global__ __launch_bounds__(256, 3) void linear_bwd_fused64_kernel(
         slope_acc += neg ? (double)(v * zv[r]) : 0.0;
         v = neg ? v * slope : v;
         cs += v;
-        buf_st1(rx, jok ? (unsigned)((rr * lddx + j) * 4) : kOOB, v);
+        buf_st1<GCL_ST_AUX>(rx, jok ? (unsigned)((rr * lddx + j) * 4) : kOOB, v);
       }
     }
 
@@ -1179,17 +1139,13 @@ int gcl_ablate() {  // GCL_ABLATE: timing-only experiments (tools/ablate.sh) - h
 #ifndef GCL_STAMPS
   return 0;  // the product library never turns stores / MFMA / loads off, whatever the environment says
 #endif
-  static const int v = [] { const char* e = getenv("GCL_ABLATE"); return e ? atoi(e) : 0; }();
+  static const int v = gcl::env_int("GCL_ABLATE", 0);
   return v;
 }
 
 bool use_valu() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("GCL_LINEAR_IMPL");
-    v = (e && strcmp(e, "valu") == 0) ? 1 : 0;
-  }
-  return v == 1;
+  static const bool v = gcl::env_is("GCL_LINEAR_IMPL", "valu");
+  return v;
 }
 
 constexpr int kDwBlocks = 512;
@@ -1212,13 +1168,13 @@ int lin_geom(int64_t rows, int K, int N, bool vec_x, LinGeom* g) {
   const int KP = ((K + 3) & ~3) + 2;
   g->waves = 4;
   g->lds = ((size_t)g->NS * 32 + 128) * KP * sizeof(float) + 64;
-  if (g->lds > 160 * 1024) {  // wide panels: 64-row tiles (2 waves) keep the weight panel resident
+  if (g->lds > gcl::kLdsBytes) {  // wide panels: 64-row tiles (2 waves) keep the weight panel resident
     g->waves = 2;
     g->lds = ((size_t)g->NS * 32 + 64) * KP * sizeof(float) + 64;
   }
-  GCL_CHECK_ARG(g->lds <= 160 * 1024, "linear: K=%d N=%d needs %zu B of LDS (>160 KiB)", K, N, g->lds);
+  GCL_CHECK_ARG(g->lds <= gcl::kLdsBytes, "linear: K=%d N=%d needs %zu B of LDS (>160 KiB)", K, N, g->lds);
   // persistent grid = what is resident at once (LDS- and register-limited), so no partial last wave
-  int bpc = (int)((160 * 1024) / g->lds);
+  int bpc = (int)(gcl::kLdsBytes / g->lds);
   const int by_regs = lin_min_waves(g->NS, g->KT) * 4 / g->waves;
   if (bpc > by_regs) bpc = by_regs;
   if (bpc < 1) bpc = 1;
@@ -1252,7 +1208,7 @@ int launch_linear(const float* X, int64_t ldx, const float* in_slope, const floa
 #define GCL_LIN3(NS_, KT_, V_)                                                                                    \
   do {                                                                                                            \
     auto kern = linear_mfma_kernel<NS_, EPI, KT_, V_>;                                                            \
-    { const int lrc_ = gcl::ensure_dyn_lds((const void*)kern, 160 * 1024); if (lrc_) return lrc_; } \
+    GCL_ENSURE_DYN_LDS(kern, gcl::kLdsBytes);                                                                     \
     hipLaunchKernelGGL(kern, dim3(g.grid), dim3(g.waves * 64), g.lds, st, X, ldx, in_slope, W, ldw, trans, bias,  \
                        Y, ldy, rows, K, N, Z, ldz, z_slope, slope_part, akind, gcl_ablate());                     \
   } while (0)
@@ -1285,8 +1241,8 @@ int launch_linear(const float* X, int64_t ldx, const float* in_slope, const floa
 // K: contraction length, N: output width.  Measured on MI355X (tools/gemm_bench.py): the 128x128
 // tile kernel wins once the contraction is long or the output fills its 128 columns.
 bool panel_fits(int K, int N, bool vec_x, bool trans, bool w_ok) {
-  const char* ie = getenv("GCL_DENSE_IMPL");  // read per call (the dispatch tests switch it)
-  const int impl = !ie ? 0 : strcmp(ie, "tile") == 0 ? 1 : strcmp(ie, "panel") == 0 ? 2 : 0;
+  // read per call (the dispatch tests switch it)
+  const int impl = gcl::env_is("GCL_DENSE_IMPL", "tile") ? 1 : gcl::env_is("GCL_DENSE_IMPL", "panel") ? 2 : 0;
   const bool tile_ok = vec_x && w_ok && K % 4 == 0 && N % 4 == 0;
   if (impl == 1 && tile_ok) return false;
   if (impl == 0 && tile_ok && (K > 128 || (N >= 128 && (K >= 128 || trans)))) return false;
@@ -1296,7 +1252,7 @@ bool panel_fits(int K, int N, bool vec_x, bool trans, bool w_ok) {
   if (NS == 3) NS = 4;
   if (NS > 4) NS = 8;
   const int KP = ((K + 3) & ~3) + 2;
-  return ((size_t)NS * 32 + 64) * KP * sizeof(float) + 64 <= 160 * 1024;
+  return ((size_t)NS * 32 + 64) * KP * sizeof(float) + 64 <= gcl::kLdsBytes;
 }
 
 template <int EPI>
@@ -1309,11 +1265,10 @@ int launch_gemm(const float* X, int64_t ldx, int akind, const float* slope, cons
   GCL_CHECK_ARG((ldw % 4 == 0) && gcl::aligned16(W) && (!trans || N % 4 == 0), "dense: wide shapes need a 16-B aligned weight block (ldw=%lld N=%d)", (long long)ldw, N);
   GtGeom g = gt_geom(rows, N);
   // split-operand bf16 variant (gemm_tile_x3_kernel): non-transposed weights, 128-row tiles
-  const int x3_tile = [] { const char* e = getenv("GCL_X3"); const char* f = getenv("GCL_X3_TILE");  // read per call
-                           return ((e && atoi(e) == 0) || (f && atoi(f) == 0)) ? 0 : 1; }();
+  const int x3_tile = gcl::env_int("GCL_X3", 1) != 0 && gcl::env_int("GCL_X3_TILE", 1) != 0;  // read per call
   if (x3_tile && !trans && g.mi == 2) {
     auto kern = gemm_tile_x3_kernel<EPI>;
-    { const int lrc_ = gcl::ensure_dyn_lds((const void*)kern, 160 * 1024); if (lrc_) return lrc_; }
+    GCL_ENSURE_DYN_LDS(kern, gcl::kLdsBytes);
     hipLaunchKernelGGL(kern, dim3(g.grid), dim3(256), gtx3_lds(), st, X, ldx, akind, slope, W, ldw, bias, Y, ldy, rows, K, N,
                        Z, ldz, add, ldadd, slope_part, g.nt, g.total, g.per_xcd);
     GCL_CHECK_LAUNCH();
@@ -1323,7 +1278,7 @@ int launch_gemm(const float* X, int64_t ldx, int akind, const float* slope, cons
 #define GCL_GT(T_, MI_)                                                                                           \
   do {                                                                                                            \
     auto kern = gemm_tile_kernel<EPI, T_, MI_>;                                                                   \
-    { const int lrc_ = gcl::ensure_dyn_lds((const void*)kern, 160 * 1024); if (lrc_) return lrc_; } \
+    GCL_ENSURE_DYN_LDS(kern, gcl::kLdsBytes);                                                                     \
     hipLaunchKernelGGL(kern, dim3(g.grid), dim3(256), gt_lds(MI_), st, X, ldx, akind, slope, W, ldw, bias, Y, ldy, \
                        rows, K, N, Z, ldz, add, ldadd, slope_part, g.nt, g.total, g.per_xcd);                     \
   } while (0)
@@ -1476,7 +1431,7 @@ static int dw_block(const float* dy, int64_t lddy, const float* x, int64_t ldx, 
 #define GCL_DW3(NO_, NC_, V_)                                                                                     \
   do {                                                                                                            \
     auto kern = dw_mfma_kernel<NO_, NC_, V_>;                                                                     \
-    { const int lrc_ = gcl::ensure_dyn_lds((const void*)kern, 160 * 1024); if (lrc_) return lrc_; } \
+    GCL_ENSURE_DYN_LDS(kern, gcl::kLdsBytes);                                                                     \
     hipLaunchKernelGGL(kern, dim3((unsigned)nblk, (unsigned)nct), dim3(256), lds, st, dy, lddy, x, ldx, in_slope, part, \
                        db ? dbpart : nullptr, rows, Fin, Fout, rpb, akind, tile_stride);                          \
   } while (0)
@@ -1551,8 +1506,7 @@ extern "C" int gcl_linear_bwd_dw(const float* dy, int64_t lddy, const float* x, 
 // Fused path geometry / workspace (see linear_bwd_fused_kernel)
 static bool fused_ok(const float* dy, int64_t lddy, const float* x, int64_t ldx, const float* dx, int64_t lddx,
                      int32_t Fin, int32_t Fout) {
-  const char* e = getenv("GCL_NO_FUSED_BWD");  // read per call (the dispatch tests switch it)
-  const int off = (e && atoi(e) != 0) ? 1 : 0;
+  const int off = gcl::env_int("GCL_NO_FUSED_BWD", 0) != 0;  // read per call (the dispatch tests switch it)
   if (off || use_valu()) return false;
   // Fout need not be a multiple of 4 when the rows of dy are padded to one (lddy >= roundup(Fout, 4)): the 16-byte
   // loads then also fetch the padding columns, which meet zero weight rows (they must hold finite values)
@@ -1599,7 +1553,7 @@ static int bwd_all_impl(const float* dy, int64_t lddy, const float* W, const flo
   }
   const int NO = (Fout + 31) / 32, NC = (Fin + 31) / 32;
   const int FoP = NO * 32, FiP = NC * 32;
-  const int no64 = [] { const char* e = getenv("GCL_NO_FUSED64"); return (e && atoi(e)) ? 1 : 0; }();  // read per call
+  const int no64 = gcl::env_int("GCL_NO_FUSED64", 0) != 0;  // read per call
   const bool use64 = (NC == 2) && !no64;  // 64-row tiles, 3 blocks per CU
   // split-operand bf16 kernel (x3.h): same partial records, two blocks per CU
   const bool use_x3 = use64 && gcl::x3_linear_bwd_applicable(dy, lddy, x, ldx, dx, lddx, Fin, Fout);
@@ -1633,7 +1587,7 @@ static int bwd_all_impl(const float* dy, int64_t lddy, const float* W, const flo
 #define GCL_FB(NO_, NC_)                                                                                          \
   do {                                                                                                            \
     auto kern = linear_bwd_fused_kernel<NO_, NC_>;                                                                \
-    { const int lrc_ = gcl::ensure_dyn_lds((const void*)kern, 160 * 1024); if (lrc_) return lrc_; } \
+    GCL_ENSURE_DYN_LDS(kern, gcl::kLdsBytes);                                                                     \
     hipLaunchKernelGGL(kern, dim3(nblk), dim3(256), lds, st, dy, lddy, W, x, ldx, in_slope, dx, lddx, rows, Fin,  \
                        Fout, part_dw, db ? part_db : nullptr, colsum_dx ? part_cs : nullptr,                      \
                        want_slope ? part_sl : nullptr);                                                           \

@@ -6,31 +6,17 @@
 // Operand maps of v_mfma_f32_32x32x16_bf16 (cdna_hip_programming.md §3), lane l: r = l & 31, h = l >> 5:
 //   A: A[row r][k = 8h + j], j = 0..7      B: B[k = 8h + j][col r]      D: reg q -> D[(q&3) + 8(q>>2) + 4h][col r]
 // so both fragments are 16 contiguous bytes of a [row | col][k] bf16 image: one ds_read_b128 each.
-#include <stdlib.h>
-
+#include "mfma_io.h"
 #include "x3.h"
 
 namespace {
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 #ifndef GCL_X3_ST_AUX
 #define GCL_X3_ST_AUX 2  // cache-policy bits of the streamed-out stores: 2 = non-temporal (measured +1.1 % end to end: the outputs are
                          // consumed by a LATER kernel, keeping them out of the producer XCD's L2 leaves it to the inputs); 0 = default
 #endif
-constexpr unsigned kOOB = 0x80000000u;
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, int64_t nbytes) {
-  const int64_t cap = 0x7FFFFF00;
-  const int n = (int)(nbytes < 0 ? 0 : (nbytes > cap ? cap : nbytes));
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, n, 0x00020000);
-}
-__device__ __forceinline__ void buf_st4(__amdgpu_buffer_rsrc_t r, unsigned off, float4 v) {
-  u32x4 u = {__builtin_bit_cast(unsigned, v.x), __builtin_bit_cast(unsigned, v.y), __builtin_bit_cast(unsigned, v.z),
-             __builtin_bit_cast(unsigned, v.w)};
-  __builtin_amdgcn_raw_buffer_store_b128(u, r, off, 0, GCL_X3_ST_AUX);
-}
-__device__ float4 x3_zero4[1];
 // rows that this kernel reads exactly once: non-temporal loads (measured +0.7 % end to end; -DGCL_X3_LD_PLAIN: plain)
 __device__ __forceinline__ float4 ld_stream(const float4* p) {
 #ifndef GCL_X3_LD_PLAIN
@@ -41,8 +27,7 @@ __device__ __forceinline__ float4 ld_stream(const float4* p) {
   return *p;
 #endif
 }
-__device__ __forceinline__ int d_row(int reg, int lane) { return (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5); }
-
+using namespace gcl::mfma_io;  // f32x16, d_row, buffer stores, zero4 (mfma_io.h)
 using namespace gcl::x3;  // pk_bf16, Pk3, split2, mfma_lo / _mid / _hi, bf16x8 (x3.h)
 
 // LDS image of a [32 rows][64 k] bf16 piece: 144-byte rows (128 + 16): the 16 lanes one ds_read_b128 cycle
@@ -148,7 +133,7 @@ __global__ __launch_bounds__(256, 2) void linear_x3_fwd_kernel(const float* __re
 #pragma unroll
     for (int it = 0; it < 8; ++it) {
       const int64_t row = r0 + it * 4 + rsub;
-      const float4* p = (cok && row < rows_ld) ? reinterpret_cast<const float4*>(X + row * ldx + csub * 4) : x3_zero4;
+      const float4* p = (cok && row < rows_ld) ? reinterpret_cast<const float4*>(X + row * ldx + csub * 4) : zero4;
       pre[it] = ld_stream(p);
     }
   };
@@ -244,7 +229,7 @@ __global__ __launch_bounds__(256, 2) void linear_x3_fwd_kernel(const float* __re
       const int i = p * RPP + orow;
       float4 v = *reinterpret_cast<const float4*>(Ot + i * OS + ocol);
       v.x += bq.x; v.y += bq.y; v.z += bq.z; v.w += bq.w;
-      buf_st4(ry, (ocol < N) ? (unsigned)((i * ldy + ocol) * 4) : kOOB, v);
+      buf_st4<GCL_X3_ST_AUX>(ry, (ocol < N) ? (unsigned)((i * ldy + ocol) * 4) : kOOB, v);
     }
     X3_STAMP(5);
   }
@@ -354,8 +339,8 @@ __global__ __launch_bounds__(256, 2) void linear_x3_bwd_kernel(
     for (int it = 0; it < 4; ++it) {
       const int64_t row = r0 + it * 4 + rsub;
       const bool rok = row < rows;
-      pre_y[it] = ld_stream((yok && rok) ? reinterpret_cast<const float4*>(dY + row * lddy + csub * 4) : x3_zero4);
-      pre_p[it] = ld_stream((pok && rok) ? reinterpret_cast<const float4*>(P + row * ldp + csub * 4) : x3_zero4);
+      pre_y[it] = ld_stream((yok && rok) ? reinterpret_cast<const float4*>(dY + row * lddy + csub * 4) : zero4);
+      pre_p[it] = ld_stream((pok && rok) ? reinterpret_cast<const float4*>(P + row * ldp + csub * 4) : zero4);
     }
   };
 
@@ -482,7 +467,7 @@ __global__ __launch_bounds__(256, 2) void linear_x3_bwd_kernel(
         slope_acc += (double)(((nx ? v.x * z.x : 0.f) + (ny ? v.y * z.y : 0.f)) + ((nz ? v.z * z.z : 0.f) + (nw ? v.w * z.w : 0.f)));
         v.x = nx ? v.x * slope : v.x; v.y = ny ? v.y * slope : v.y; v.z = nz ? v.z * slope : v.z; v.w = nw ? v.w * slope : v.w;
         cs4.x += v.x; cs4.y += v.y; cs4.z += v.z; cs4.w += v.w;
-        buf_st4(rx, pok ? (unsigned)((row * lddx + csub * 4) * 4) : kOOB, v);
+        buf_st4<GCL_X3_ST_AUX>(rx, pok ? (unsigned)((row * lddx + csub * 4) * 4) : kOOB, v);
       }
     }
     X3_STAMP(7);
@@ -528,13 +513,8 @@ int x3_ablate() {  // GCL_ABLATE: timing-only experiments (tools/ablate.sh) - ho
 #ifndef GCL_STAMPS
   return 0;
 #endif
-  static const int v = [] { const char* e = getenv("GCL_ABLATE"); return e ? atoi(e) : 0; }();
+  static const int v = gcl::env_int("GCL_ABLATE", 0);
   return v;
-}
-
-int x3_enabled() {  // read per call: the dispatch tests compare GCL_X3=0 (fp32-operand kernels) with the default
-  const char* e = getenv("GCL_X3");
-  return (e && atoi(e) == 0) ? 0 : 1;
 }
 
 }  // namespace
@@ -551,7 +531,7 @@ extern "C" int gcl_debug_read_stamps_x3(unsigned long long* host_out, int count)
 namespace gcl {
 
 bool x3_linear_fwd_applicable(const float* x, int64_t ldx, const float* y, int64_t ldy, int K, int N, int akind) {
-  if (!x3_enabled()) return false;
+  if (!env_int("GCL_X3", 1)) return false;  // read per call: the dispatch tests compare GCL_X3=0 with the default
   if (K < 1 || K > 64 || N < 4 || N > 64 || (N & 3)) return false;
   if ((ldx & 3) || (ldy & 3) || !aligned16(x) || !aligned16(y)) return false;
   if (ldx * 4 * 35 >= ((int64_t)1 << 31) || ldy * 4 * 35 >= ((int64_t)1 << 31)) return false;  // 32-bit offsets inside a tile
@@ -587,7 +567,7 @@ int x3_linear_fwd(const float* x, int64_t ldx, int akind, const float* slope, co
 
 bool x3_linear_bwd_applicable(const float* dy, int64_t lddy, const float* x, int64_t ldx, const float* dx, int64_t lddx,
                               int Fin, int Fout) {
-  if (!x3_enabled()) return false;
+  if (!env_int("GCL_X3", 1)) return false;  // read per call: the dispatch tests compare GCL_X3=0 with the default
   if (Fin < 33 || Fin > 64 || (Fin & 3) || Fout < 1 || Fout > 64) return false;
   if (lddy < ((Fout + 3) & ~3) || (lddy & 3) || (ldx & 3) || (lddx & 3) || lddx < Fin) return false;
   if (!aligned16(dy) || !aligned16(x) || !aligned16(dx)) return false;
@@ -607,7 +587,7 @@ int x3_linear_bwd(const float* dy, int64_t lddy, const float* W, const float* x,
 #define GCL_X3B(NO_)                                                                                              \
   do {                                                                                                            \
     auto kern = linear_x3_bwd_kernel<NO_>;                                                                        \
-    { const int lrc_ = gcl::ensure_dyn_lds((const void*)kern, 160 * 1024); if (lrc_) return lrc_; } \
+    GCL_ENSURE_DYN_LDS(kern, gcl::kLdsBytes);                                                                     \
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, dy, lddy, W, x, ldx, in_slope, dx, lddx, rows, Fin, Fout, \
                        part_dw, part_db, part_cs, part_slope);                                                    \
   } while (0)

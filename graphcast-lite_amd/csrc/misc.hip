@@ -352,10 +352,7 @@ __global__ __launch_bounds__(256) void pad_rows_kernel(const float* __restrict__
   }
 }
 
-inline unsigned grid_for(int64_t total, int cap = 4096) {
-  int64_t nb = gcl::cdiv(total > 0 ? total : 1, 256);
-  return (unsigned)(nb > cap ? cap : nb);
-}
+using gcl::grid_for;
 constexpr int kLossBlocks = 1024;
 
 }  // namespace

@@ -23,10 +23,7 @@
 
 namespace {
 
-__device__ __forceinline__ double rounded(double x) {
-  asm volatile("" : "+v"(x));
-  return x;
-}
+using gcl::rounded;  // products rounded on their own, never contracted (common.h)
 
 constexpr int kNumFeat = 20;   // FEATURE_COLUMNS of build_learned_mos.py
 constexpr int kNumTime = 8;    // host features per (sample, station, step): hour sin/cos, doy sin/cos, solar

@@ -47,12 +47,6 @@ __global__ __launch_bounds__(256) void adam_groups_kernel(float4* __restrict__ p
   }
 }
 
-// Guideline 11 (memory-bound): one lane per float4 up to 2048 blocks of 256, grid-stride beyond
-inline unsigned stream_grid(int64_t n4) {
-  const int64_t nb = gcl::cdiv(n4 > 0 ? n4 : 1, 256);
-  return (unsigned)(nb > 2048 ? 2048 : nb);
-}
-
 }  // namespace
 
 extern "C" int gcl_adam_step_groups(float* p, const float* g, float* m, float* v, int64_t count,
@@ -70,8 +64,8 @@ extern "C" int gcl_adam_step_groups(float* p, const float* g, float* m, float* v
   hipLaunchKernelGGL(adam_groups_tick_kernel, dim3((unsigned)gcl::cdiv(num_params, 256)), dim3(256), 0, st, active,
                      step, (float2*)bc, num_params, beta1, beta2);
   const int64_t n4 = count / 4;
-  if (n4 > 0)
-    hipLaunchKernelGGL(adam_groups_kernel, dim3(stream_grid(n4)), dim3(256), 0, st, (float4*)p, (const float4*)g,
+  if (n4 > 0)  // one lane per float4 up to 2048 blocks, grid-stride beyond
+    hipLaunchKernelGGL(adam_groups_kernel, dim3(gcl::grid_for(n4, 2048)), dim3(256), 0, st, (float4*)p, (const float4*)g,
                        (float4*)m, (float4*)v, n4, chunk_param, active, lr, (const float2*)bc, beta1, beta2, eps,
                        weight_decay, grad_scale);
   GCL_CHECK_LAUNCH();

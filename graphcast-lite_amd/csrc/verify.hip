@@ -20,16 +20,7 @@
 
 namespace {
 
-// Opaque to the optimiser: a product passed through here is rounded on its own and cannot be contracted into the
-// following add (hipcc fuses even through __fmul_rn / __dmul_rn; see assim.hip).
-__device__ __forceinline__ float rounded(float x) {
-  asm volatile("" : "+v"(x));
-  return x;
-}
-__device__ __forceinline__ double rounded(double x) {
-  asm volatile("" : "+v"(x));
-  return x;
-}
+using gcl::rounded;  // products rounded on their own, never contracted (common.h)
 
 constexpr int kMaxPred = 4;
 constexpr int kColTile = 32;     // columns per block of the partial kernel
@@ -274,11 +265,6 @@ __global__ __launch_bounds__(256) void blend_kernel(const float* __restrict__ ma
   }
 }
 
-inline unsigned grid_cap(int64_t total) {
-  const int64_t nb = gcl::cdiv(total > 0 ? total : 1, 256);
-  return (unsigned)(nb > 8192 ? 8192 : nb);
-}
-
 template <int NP>
 int launch_colstats(hipStream_t st, const float* T, int64_t ldt, int64_t bst, const Preds& P, const int32_t* rows,
                     int32_t n, int32_t K, int32_t B, double* stats, double* part) {
@@ -350,10 +336,10 @@ extern "C" int gcl_regrid_blend(const void* src, int32_t src_f64, int64_t lds, i
   if (total == 0) return GCL_OK;
   const hipStream_t st = (hipStream_t)stream;
   if (src_f64)
-    hipLaunchKernelGGL(regrid_kernel<double>, dim3(grid_cap(total)), dim3(256), 0, st, (const double*)src, lds, bss,
+    hipLaunchKernelGGL(regrid_kernel<double>, dim3(gcl::grid_for(total, 8192)), dim3(256), 0, st, (const double*)src, lds, bss,
                        nlat, cell, w, nt, K, g, ldg, bsg, mask, r, ldr, bsr, out, ldo, bso, B);
   else
-    hipLaunchKernelGGL(regrid_kernel<float>, dim3(grid_cap(total)), dim3(256), 0, st, (const float*)src, lds, bss,
+    hipLaunchKernelGGL(regrid_kernel<float>, dim3(gcl::grid_for(total, 8192)), dim3(256), 0, st, (const float*)src, lds, bss,
                        nlat, cell, w, nt, K, g, ldg, bsg, mask, r, ldr, bsr, out, ldo, bso, B);
   GCL_CHECK_LAUNCH();
   return GCL_OK;
@@ -366,7 +352,7 @@ extern "C" int gcl_taper_blend(const float* mask, const float* r, int64_t ldr, i
   GCL_CHECK_ARG(nt >= 0 && K > 0 && B > 0, "taper_blend: bad shape");
   const int64_t total = (int64_t)B * nt * K;
   if (total == 0) return GCL_OK;
-  hipLaunchKernelGGL(blend_kernel, dim3(grid_cap(total)), dim3(256), 0, (hipStream_t)stream, mask, r, ldr, bsr, g, ldg,
+  hipLaunchKernelGGL(blend_kernel, dim3(gcl::grid_for(total, 8192)), dim3(256), 0, (hipStream_t)stream, mask, r, ldr, bsr, g, ldg,
                      bsg, out, ldo, bso, nt, K, B);
   GCL_CHECK_LAUNCH();
   return GCL_OK;

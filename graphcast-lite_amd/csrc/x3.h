@@ -32,10 +32,12 @@ int x3_linear_bwd(const float* dy, int64_t lddy, const float* W, const float* x,
 
 #ifdef __HIPCC__
 // ---- device side: the split and the MFMA passes shared by linear_x3.hip, gcn_layer.hip and gemm_tile.h ----
+#include "mfma_io.h"
+
 namespace gcl {
 namespace x3 {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using mfma_io::f32x16;
 typedef short bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
 typedef float f32x2_t __attribute__((ext_vector_type(2)));
