@@ -32,6 +32,18 @@ __device__ __forceinline__ void load4(const float* p, int c0, int F, bool vec, f
     d = (c0 + 3 < F) ? p[3] : 0.f;
   }
 }
+// load4 of a row whose F columns may be followed by padding (ld >= roundup(F, 4)): a 16-byte load also reads columns
+// F .. roundup(F, 4) - 1, which are set to 0 here so that the padding, whatever it holds (NaN included), never enters
+// a row sum.  V: the row is read in the instantiation that needs F % 4 == 0, nothing to mask.
+template <bool V>
+__device__ __forceinline__ void load4_row(const float* p, int c0, int F, bool vec, float& a, float& b, float& c, float& d) {
+  load4(p, c0, F, vec, a, b, c, d);
+  if (!V && vec) {
+    b = (c0 + 1 < F) ? b : 0.f;
+    c = (c0 + 2 < F) ? c : 0.f;
+    d = (c0 + 3 < F) ? d : 0.f;
+  }
+}
 __device__ __forceinline__ void store4(float* p, int c0, int F, bool vec, float a, float b, float c, float d) {
   if (vec) {
     *reinterpret_cast<float4*>(p) = make_float4(a, b, c, d);
@@ -68,7 +80,7 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ X
   }
   for (int64_t row = (int64_t)blockIdx.x * RPB + wave * (64 / LPR) + sub; row < rows; row += (int64_t)gridDim.x * RPB) {
     float x0 = 0, x1 = 0, x2 = 0, x3 = 0;
-    if (c0 < F) load4(X + row * ldx + c0, c0, F, vx, x0, x1, x2, x3);
+    if (c0 < F) load4_row<V>(X + row * ldx + c0, c0, F, vx, x0, x1, x2, x3);
     const float mean = group_sum<LPR>(x0 + x1 + x2 + x3) * invF;
     const float d0 = (c0 < F) ? x0 - mean : 0.f, d1 = (c0 + 1 < F) ? x1 - mean : 0.f;
     const float d2 = (c0 + 2 < F) ? x2 - mean : 0.f, d3 = (c0 + 3 < F) ? x3 - mean : 0.f;
@@ -137,14 +149,14 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ d
   for (int64_t row = row_first; row < rows; row += row_step) {
     float x0 = 0, x1 = 0, x2 = 0, x3 = 0, y0 = 0, y1 = 0, y2 = 0, y3 = 0;
     if (c0 < F) {
-      load4(X + row * ldx + c0, c0, F, vx, x0, x1, x2, x3);
+      load4_row<V>(X + row * ldx + c0, c0, F, vx, x0, x1, x2, x3);
       if (MAP) {
         // unmapped rows issue no load at all: this kernel is bound by its load INSTRUCTIONS (a wave-instruction serves
         // only four rows), so a dummy load for them costs more than the divergent branch around the real one
         const int pj = pos[mi];
-        if (pj >= 0) load4(dY + mb * bsdy + (int64_t)pj * lddy + c0, c0, F, vdy, y0, y1, y2, y3);
+        if (pj >= 0) load4_row<V>(dY + mb * bsdy + (int64_t)pj * lddy + c0, c0, F, vdy, y0, y1, y2, y3);
       } else {
-        load4(dY + row * lddy + c0, c0, F, vdy, y0, y1, y2, y3);
+        load4_row<V>(dY + row * lddy + c0, c0, F, vdy, y0, y1, y2, y3);
       }
     }
     if (MAP) {

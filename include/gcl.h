@@ -244,6 +244,9 @@ size_t gcl_gat_prune_ws_bytes(int64_t e_prime);
 /* ---------------------------------------------------------------------------------------------
  * PyG LayerNorm(mode="node")  (src/models.py:102-104,368-374): per row, eps inside the sqrt.
  * stats [rows,2] receives (mean, rstd) for the backward.  x may carry an activation (in_slope).
+ * Padding: every row argument (x, dy, y, dx) may have a row stride ld > F and any float-aligned base.  The columns past F
+ * of x and dy are ignored, whatever their value (NaN and Inf included), and the columns past F of y and dx are not
+ * written.  This holds for all the LayerNorm entry points below, mapped forms included.
  * ------------------------------------------------------------------------------------------- */
 int gcl_layernorm_fwd(const float* x, int64_t ldx, const float* gamma, const float* beta, float eps,
                       float* y, int64_t ldy, float* stats, int64_t rows, int32_t F,
