@@ -128,6 +128,14 @@ _SIGNATURES = {
                                     _vp, _vp, _i32, _vp, _i32, C.c_double, C.c_double, _vp, _i32, _vp]),
     "gcl_mos_table_apply": (C.c_int, [_vp, _i32, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _vp,
                                       _i32, _i32, _vp]),
+    "gcl_multires_window_pack": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, _i64, _i32, _i32, _i32, _vp, _i32, _i32, _vp,
+                                           _vp, _vp, _i64, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32,
+                                           _vp]),
+    "gcl_pipeline_roi_phys": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i32, _i32, _i32, _vp, _vp, _i32, _i32, C.c_double,
+                                        _i32, _vp, _vp, _vp]),
+    "gcl_pipeline_lapse": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, C.c_double, _i32, _vp]),
+    "gcl_pipeline_station_obs": (C.c_int, [_vp, _i64, _vp, _i32, _i32, _i32, _vp, _vp]),
+    "gcl_pipeline_sqerr": (C.c_int, [_vp, _i64, _i64, _i32, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
 }
 
 
@@ -1116,3 +1124,81 @@ def taper_blend(mask, r3, g3, out3):
     _check(lib().gcl_taper_blend(_p(mask), _p(r3), r3.stride(1), r3.stride(0), _p(g3), g3.stride(1), g3.stride(0),
                                  _p(out3), out3.stride(1), out3.stride(0), nt, K, B, _stream()))
     return out3
+
+
+def multires_window_pack(gseries, rseries, rank, n_kept: int, n_reg: int, corner, w, t0, off_g: int, off_r: int, mean,
+                         std, C: int, obs: int, pred: int, quantize: bool = True, out=None, out_f16: bool = False):
+    """Windows of the flat multires node set (see gcl_multires_window_pack).  gseries fp16 [Tg, n_lon, n_lat, Ct];
+    rseries fp16 [Tr, rn_lon, rn_lat, Ct] (merge mode) or None (interpolate mode: corner int32 [n_reg, 4], w float64
+    [n_reg, 4]); rank int32 [n_lat * n_lon]; t0 int64 [B] on the GPU; mean / std float32 [>= C] or both None.  Returns
+    X [B, N, obs*C] and Y [B, N, pred*C] (None when pred == 0), float32 or (out_f16) float16; out = (X, Y) fills
+    contiguous buffers of those shapes in place."""
+    for s in (gseries, rseries):
+        assert s is None or (s.is_cuda and s.dtype == torch.float16 and s.is_contiguous() and s.dim() == 4)
+    assert t0.is_cuda and t0.dtype == torch.int64 and t0.is_contiguous()
+    Tg, n_lon, n_lat, Ctg = gseries.shape
+    Tr, rn_lon, rn_lat, Ctr = rseries.shape if rseries is not None else (0, 0, 0, 0)
+    assert rank.numel() == n_lon * n_lat
+    if rseries is None and n_reg:
+        assert corner.shape == (n_reg, 4) and w.shape == (n_reg, 4)
+    B, N = t0.numel(), n_kept + n_reg
+    dt = torch.float16 if out_f16 else torch.float32
+    if out is not None:
+        X, Y = out
+        assert X.is_contiguous() and X.shape == (B, N, obs * C) and X.dtype == dt and X.device == gseries.device
+        assert pred == 0 or (Y.is_contiguous() and Y.shape == (B, N, pred * C) and Y.dtype == dt and Y.device == X.device)
+    else:
+        X = torch.empty(B, N, obs * C, dtype=dt, device=gseries.device)
+        Y = torch.empty(B, N, pred * C, dtype=dt, device=gseries.device) if pred > 0 else None
+    _check(lib().gcl_multires_window_pack(
+        gseries.data_ptr(), Tg, n_lon, n_lat, Ctg, rseries.data_ptr() if rseries is not None else None, Tr, rn_lon,
+        rn_lat, Ctr, _pi(rank), int(n_kept), int(n_reg), _pi(corner), _pd(w) if w is not None else None, t0.data_ptr(),
+        int(off_g), int(off_r), _p(mean), _p(std), int(C), int(obs), int(pred), int(bool(quantize)), int(out_f16),
+        X.data_ptr(), Y.data_ptr() if pred > 0 else None, B, _stream()))
+    return X, Y
+
+
+def pipeline_roi_phys(pred2, x_last2, rows, row0: int, G: int, mean, std, t_idx: int, z_idx: int, elev: float,
+                      lapse_f64: bool, raw, lapse=None):
+    """raw / lapse [G, C] from the model output pred2 [N, >= C] (see gcl_pipeline_roi_phys)."""
+    C = raw.shape[1]
+    assert pred2.dim() == 2 and pred2.stride(1) == 1 and pred2.shape[1] >= C and raw.shape == (G, C) and raw.is_contiguous()
+    assert x_last2 is None or (x_last2.dim() == 2 and x_last2.stride(1) == 1 and x_last2.shape[0] == pred2.shape[0])
+    assert lapse is None or (lapse.shape == raw.shape and lapse.is_contiguous())
+    assert (rows.numel() == G) if rows is not None else (0 <= row0 and row0 + G <= pred2.shape[0])
+    _check(lib().gcl_pipeline_roi_phys(_p(pred2), pred2.stride(0), _p(x_last2), x_last2.stride(0) if x_last2 is not None
+                                       else 0, _pi(rows), int(row0), int(G), C, _p(mean), _p(std), int(t_idx), int(z_idx),
+                                       float(elev), int(bool(lapse_f64)), _p(raw), _p(lapse), _stream()))
+    return raw, lapse
+
+
+def pipeline_lapse(x3, t_idx: int, z_idx: int, elev: float, lapse_f64: bool):
+    """The lapse-corrected copy of contiguous x3 [G, S, C] (see gcl_pipeline_lapse)."""
+    assert x3.dim() == 3 and x3.is_contiguous()
+    G, S, C = x3.shape
+    out = torch.empty_like(x3)
+    _check(lib().gcl_pipeline_lapse(_p(x3), _p(out), G, S, C, int(t_idx), int(z_idx), float(elev), int(bool(lapse_f64)),
+                                    _stream()))
+    return out
+
+
+def pipeline_station_obs(truth2, stn, out=None):
+    """NaN field [G, C] with the rows stn (int32, device) of truth2 [G, C] (see gcl_pipeline_station_obs)."""
+    G, C = truth2.shape
+    assert truth2.stride(1) == 1
+    if out is None:
+        out = torch.empty(G, C, dtype=torch.float32, device=truth2.device)
+    assert out.shape == (G, C) and out.is_contiguous()
+    _check(lib().gcl_pipeline_station_obs(_p(truth2), truth2.stride(0), _pi(stn), stn.numel(), G, C, _p(out), _stream()))
+    return out
+
+
+def pipeline_sqerr(preds3, truth2, stn, h: int, acc_grid, acc_stn=None):
+    """acc_grid[v, h, :] += column sums of (preds3[v] - truth2)^2, acc_stn the same over the rows stn (see
+    gcl_pipeline_sqerr).  preds3 [V, G, C] with unit column stride, accumulators float64 [V, H, C]."""
+    V, G, C = preds3.shape
+    assert preds3.stride(2) == 1 and truth2.shape == (G, C) and truth2.stride(1) == 1
+    assert acc_grid.shape[0] == V and acc_grid.shape[2] == C and (acc_stn is None or acc_stn.shape == acc_grid.shape)
+    _check(lib().gcl_pipeline_sqerr(_p(preds3), preds3.stride(0), preds3.stride(1), V, _p(truth2), truth2.stride(0),
+                                    _pi(stn), stn.numel() if stn is not None else 0, G, C, acc_grid.shape[1], int(h),
+                                    _pd(acc_grid), _pd(acc_stn) if acc_stn is not None else None, _stream()))

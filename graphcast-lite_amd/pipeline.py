@@ -1,0 +1,275 @@
+"""The full-pipeline evaluation of `scripts/evaluate_full_pipeline.py` (with `--skip-unet`) on the HIP path:
+multires rollout -> ROI rows in physical units -> lapse-rate correction -> learned MOS (stations only / with IDW) ->
+OI against simulated station observations, every variant scored per horizon and channel on the regional grid and at the
+stations, against persistence.
+
+The expensive stages are the existing device code (`predict.rollout`, `mos.LearnedMOS`, `assimilation.OINetwork`); this
+module adds the glue between them (csrc/pipeline.hip) so that a sample never returns to the host:
+
+* `denormalize`, `apply_lapse`, `simulate_station_obs`: the script's helpers with their names and signatures, device
+  tensors in and out.
+* `evaluation_sample_starts`: the script's sample selection (`:371-387`).
+* `FullPipelineEvaluator`: the sample loop of `:449-666` and the tables of `:678-766`.
+"""
+from typing import Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import hip
+from .mos import LearnedMOS
+from .predict import rollout
+
+VARIANTS = ("GNN", "GNN+lapse", "GNN+MOS", "GNN+lapse+MOS", "GNN+lapse+MOS+IDW", "GNN+lapse+MOS+IDW+OI", "Persistence")
+
+
+def _dev_f32(a, device) -> torch.Tensor:
+    if isinstance(a, torch.Tensor):
+        return a.to(device, torch.float32).contiguous()
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(device)
+
+
+def _need_gpu(t, who: str):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise RuntimeError(f"{who} needs a GPU tensor (there is no CPU fallback)")
+    if t.dtype != torch.float32:
+        raise ValueError(f"{who}: float32 expected, got {t.dtype}")
+
+
+def denormalize(data_norm: torch.Tensor, mean, std) -> torch.Tensor:
+    """`physical = normalized * std + mean` (`:147-149`) on the device, float32, the product and the sum rounded
+    separately as numpy rounds them.  data_norm [..., C]; mean / std [C] (arrays or tensors)."""
+    _need_gpu(data_norm, "denormalize")
+    C = data_norm.shape[-1]
+    x2 = data_norm.reshape(-1, C)
+    if x2.stride(1) != 1:
+        x2 = x2.contiguous()
+    raw = torch.empty(x2.shape[0], C, dtype=torch.float32, device=x2.device)
+    hip.pipeline_roi_phys(x2, None, None, 0, x2.shape[0], _dev_f32(mean, x2.device), _dev_f32(std, x2.device), -1, -1,
+                          0.0, False, raw)
+    return raw.view(data_norm.shape)
+
+
+def lapse_in_float64(target_elevation) -> bool:
+    """Does numpy 2 evaluate `float32_array - target_elevation` in float64?  A Python scalar is weak (the array's
+    float32 wins); a numpy scalar or 0-d array is strong and promotes by its own dtype."""
+    if isinstance(target_elevation, (np.generic, np.ndarray)):
+        return np.result_type(np.float32, np.asarray(target_elevation).dtype) == np.float64
+    if isinstance(target_elevation, torch.Tensor):
+        raise TypeError("target_elevation must be a host scalar")
+    return False
+
+
+def apply_lapse(pred_phys: torch.Tensor, var_order: Sequence[str], target_elevation) -> torch.Tensor:
+    """Lapse-rate correction of t2m (`:184-200`): `t2m += (z_surf - target_elevation) * 6.5e-3` on pred_phys [G, C]
+    or [G, steps, C] (z_surf of step 0 corrects every step).  Returns a new tensor, or pred_phys itself when `t2m` or
+    `z_surf` is not in var_order.
+
+    The arithmetic follows the TYPE of target_elevation as numpy 2 does: with a Python float (the script's
+    `--lapse-elev 250`) every step is float32; with an `np.float64` (the script's default, `np.mean(...)`) or a 0-d
+    float64 array the difference and the product are float64 and only the final add rounds to float32.  The two
+    differ in the last bit of t2m in roughly one row in 170."""
+    if "t2m" not in var_order or "z_surf" not in var_order:
+        return pred_phys
+    _need_gpu(pred_phys, "apply_lapse")
+    if pred_phys.dim() not in (2, 3) or pred_phys.shape[-1] != len(var_order):
+        raise ValueError(f"apply_lapse: [G, C] or [G, steps, C] with C = {len(var_order)} expected, got "
+                         f"{tuple(pred_phys.shape)}")
+    x3 = (pred_phys if pred_phys.dim() == 3 else pred_phys.unsqueeze(1)).contiguous()
+    out = hip.pipeline_lapse(x3, list(var_order).index("t2m"), list(var_order).index("z_surf"), float(target_elevation),
+                             lapse_in_float64(target_elevation))
+    return out if pred_phys.dim() == 3 else out[:, 0, :]
+
+
+def station_rows(r_lats, r_lons, stations: Sequence[dict], float32: bool = False) -> np.ndarray:
+    """int64 [len(stations)]: the nearest node of the (lat, lon)-major regional grid for every station - the
+    squared-degree argmin of the reference, duplicates kept.  float32=False: the float64 search of
+    `simulate_station_obs` (`:213-219`); True: the search on float32 coordinates that picks the SCORING rows
+    (`:402-410`).  The two can disagree for a station near a cell boundary; the script uses both, so both are kept."""
+    lo_m, la_m = np.meshgrid(r_lons, r_lats)
+    flat_lats, flat_lons = la_m.ravel(), lo_m.ravel()
+    if float32:
+        flat_lats, flat_lons = flat_lats.astype(np.float32), flat_lons.astype(np.float32)
+    return np.array([int(np.argmin((flat_lats - st["lat"]) ** 2 + (flat_lons - st["lon"]) ** 2)) for st in stations],
+                    dtype=np.int64)
+
+
+def simulate_station_obs(ground_truth_phys: torch.Tensor, r_lats, r_lons, stations: Sequence[dict],
+                         var_order: Sequence[str]) -> torch.Tensor:
+    """Synthetic station observations for OI (`:203-222`): float32 [G, C], NaN everywhere except the rows of each
+    station's nearest grid point, which hold the truth.  r_lats / r_lons are the regional AXES; G = len(r_lats) *
+    len(r_lons).  (The reference sizes its field by len(r_lats) alone and fails with an IndexError for a station
+    beyond the first len(r_lats) nodes; where it runs, its output is the head of this field.)"""
+    _need_gpu(ground_truth_phys, "simulate_station_obs")
+    G, C = len(r_lats) * len(r_lons), len(var_order)
+    if tuple(ground_truth_phys.shape) != (G, C):
+        raise ValueError(f"simulate_station_obs: truth must be [{G}, {C}], got {tuple(ground_truth_phys.shape)}")
+    rows = torch.from_numpy(station_rows(r_lats, r_lons, stations).astype(np.int32)).to(ground_truth_phys.device)
+    truth = ground_truth_phys if ground_truth_phys.stride(1) == 1 else ground_truth_phys.contiguous()
+    return hip.pipeline_station_obs(truth, rows)
+
+
+def evaluation_sample_starts(T_overlap: int, obs: int, ar: int, max_samples: int) -> list:
+    """The script's test samples (`:371-387`): the last 20 % of the overlap, its second half (the first is the
+    validation part), every start whose obs + ar frames fit, thinned evenly to at most max_samples."""
+    n_test_total = int(T_overlap * 0.2)
+    test_start = T_overlap - n_test_total + n_test_total // 2
+    valid = list(range(test_start, T_overlap - (obs + ar) + 1))
+    n = min(max_samples, len(valid))
+    if n < len(valid):
+        step = len(valid) // n
+        return [valid[i * step] for i in range(n)]
+    return valid[:n]
+
+
+class FullPipelineEvaluator:
+    """The evaluation loop of `scripts/evaluate_full_pipeline.py:392-766` without the U-Net cascade.
+
+    model: the one-step forecaster on the multires node set (`model(X=..., attention_threshold=...)`, `.obs_window`).
+    dataset: a `MultiresChunkDataset(quantize=False)` - the script normalises the float32 frames (`:452-468`).
+    regional_series: fp16 device tensor (T, lon, lat, C), the truth and the persistence baseline in physical units
+    (None: the dataset's own regional series, merge mode).  var_order: the C channel names.  y_mean / y_std: the
+    scalers.  stations: {"lat", "lon", "elev"} dicts.  lapse_elev: the target elevation; its TYPE selects the
+    arithmetic, see `apply_lapse`.  mos: a `mos.MOSForest`, the bundle of `mos.load_learned_mos` or its model (None:
+    no MOS variants).  oi: an `assimilation.OptimalInterpolation` on the regional axes (None: no OI variant; the OI
+    variant also needs mos, its input is the IDW variant).  idw_power / idw_radius_km: the script's 2.0 / 300.0.
+    base_time: forecast start; step h is valid at base_time + 6 h * (h + 1) (`:413`, `:490-493`).
+
+    `update(sample_starts)` runs every sample on the device and adds its squared errors into device accumulators; it
+    makes no host synchronisation of its own.  `results()` copies them to the host once."""
+
+    def __init__(self, model, dataset, regional_series, var_order: Sequence[str], y_mean, y_std,
+                 stations: Sequence[dict], ar_steps: int, lapse_elev, mos=None, oi=None, use_residual: bool = False,
+                 idw_power: float = 2.0, idw_radius_km: float = 300.0, base_time=None, static_names=("z_surf", "lsm")):
+        from datetime import datetime, timedelta, timezone
+
+        self.model, self.ds, self.var_order = model, dataset, list(var_order)
+        self.device = dataset.device
+        self.obs, self.ar, self.use_residual = int(model.obs_window), int(ar_steps), bool(use_residual)
+        self.C = len(self.var_order)
+        if dataset.n_feat != self.C:
+            raise ValueError(f"the dataset serves {dataset.n_feat} features, var_order names {self.C}")
+        self.rs = regional_series if regional_series is not None else dataset.region_series
+        if self.rs is None:
+            raise ValueError("regional_series is needed (the dataset holds none in interpolate mode)")
+        if not (self.rs.is_cuda and self.rs.dtype == torch.float16 and self.rs.dim() == 4 and self.rs.is_contiguous()):
+            raise ValueError("regional_series must be a contiguous fp16 device tensor (T, lon, lat, C)")
+        r_lats, r_lons = dataset.r_lats, dataset.r_lons
+        if tuple(self.rs.shape[1:3]) != (len(r_lons), len(r_lats)) or self.rs.shape[3] < self.C:
+            raise ValueError(f"regional_series {tuple(self.rs.shape)} does not match the dataset's regional axes")
+        self.G, self.n_kept = dataset.n_regional, dataset.n_global_kept
+        self.mean, self.std = _dev_f32(y_mean, self.device), _dev_f32(y_std, self.device)
+        self._zeros = torch.zeros(self.C, dtype=torch.float32, device=self.device)
+        self._ones = torch.ones(self.C, dtype=torch.float32, device=self.device)
+        self.stations = list(stations)
+        self.lapse_elev, self.lapse_f64 = float(lapse_elev), lapse_in_float64(lapse_elev)
+        has_lapse = "t2m" in self.var_order and "z_surf" in self.var_order
+        self.t_idx = self.var_order.index("t2m") if has_lapse else -1
+        self.z_idx = self.var_order.index("z_surf") if has_lapse else -1
+        self.static_channels = {self.var_order.index(n) for n in static_names if n in self.var_order}
+
+        self.score_rows = station_rows(r_lats, r_lons, self.stations, float32=True)
+        self._score = torch.from_numpy(self.score_rows.astype(np.int32)).to(self.device)
+        self.variants = ["GNN", "GNN+lapse"]
+        self._mos_stn = self._mos_idw = self._oi_net = None
+        if mos is not None and "t2m" in self.var_order:
+            lo_m, la_m = np.meshgrid(r_lons, r_lats)
+            lat32, lon32 = la_m.ravel().astype(np.float32), lo_m.ravel().astype(np.float32)  # :402-404
+            self._mos_stn = LearnedMOS(mos, self.var_order, lat32, lon32, self.stations, False, device=self.device)
+            self._mos_idw = LearnedMOS(mos, self.var_order, lat32, lon32, self.stations, True, idw_power,
+                                       idw_radius_km, device=self.device)
+            base = base_time if base_time is not None else datetime(2020, 6, 1, 0, 0, 0, tzinfo=timezone.utc)
+            # one valid time per step (:550), uploaded once
+            self._tfeat = [self._mos_stn.time_features([base + timedelta(hours=6 * (h + 1))]) for h in range(self.ar)]
+            self.variants += ["GNN+MOS", "GNN+lapse+MOS", "GNN+lapse+MOS+IDW"]
+            if oi is not None:
+                self.sim_rows = station_rows(r_lats, r_lons, self.stations)
+                self._sim = torch.from_numpy(self.sim_rows.astype(np.int32)).to(self.device)
+                self._oi_net = oi.prepare_network(self.sim_rows)
+                self._oi_net.prepare(self.C)
+                self._obs = torch.empty(self.G, self.C, dtype=torch.float32, device=self.device)
+                self.variants.append("GNN+lapse+MOS+IDW+OI")
+        self.variants.append("Persistence")
+        V = len(self.variants)
+        self._buf = torch.empty(V - 1, self.G, self.C, dtype=torch.float32, device=self.device)
+        self._acc_grid = torch.zeros(V, self.ar, self.C, dtype=torch.float64, device=self.device)
+        self._acc_stn = torch.zeros(V, self.ar, self.C, dtype=torch.float64, device=self.device)
+        self.count_grid, self.count_stn = [0] * self.ar, [0] * self.ar
+
+    def reset(self):
+        self._acc_grid.zero_()
+        self._acc_stn.zero_()
+        self.count_grid, self.count_stn = [0] * self.ar, [0] * self.ar
+
+    def _step(self, pred2: torch.Tensor, truth2: torch.Tensor, h: int):
+        """Every model variant of one step from the normalised output rows pred2 [N, C] into self._buf."""
+        buf = self._buf
+        hip.pipeline_roi_phys(pred2, None, None, self.n_kept, self.G, self.mean, self.std, self.t_idx, self.z_idx,
+                              self.lapse_elev, self.lapse_f64, buf[0], buf[1])
+        if self._mos_stn is not None:
+            tf = self._tfeat[h]
+            as3 = lambda t: t.view(self.G, 1, self.C)  # noqa: E731  ((G, 1, C): one step per call, :536-539)
+            self._mos_stn.apply(as3(buf[0]), tf, out=as3(buf[2]))
+            self._mos_stn.apply(as3(buf[1]), tf, out=as3(buf[3]))
+            self._mos_idw.apply(as3(buf[1]), tf, out=as3(buf[4]))
+            if self._oi_net is not None:
+                hip.pipeline_station_obs(truth2, self._sim, out=self._obs)
+                self._oi_net.apply(buf[4], self._obs, out=buf[5])
+
+    @torch.no_grad()
+    def update(self, sample_starts: Sequence[int], keep: bool = False):
+        """Run the samples starting at the frames `sample_starts` (`:449-666`).  keep=True also returns, per sample and
+        step, a copy of the variant stack [V, G, C] (the order of `self.variants`) and of the truth [G, C]."""
+        starts = [int(t) for t in sample_starts]
+        T = min(self.ds.total_time, self.rs.shape[0])
+        if any(t < 0 or t + self.obs + self.ar > T for t in starts):
+            raise ValueError(f"a sample needs {self.obs + self.ar} frames inside the {T} common ones")
+        t0_all = torch.tensor(starts, dtype=torch.int64).to(self.device)
+        C, ar, V = self.C, self.ar, len(self.variants)
+        kept = []
+        for i in range(len(starts)):
+            t0 = t0_all[i:i + 1]
+            X, _ = self.ds.windows(t0, self.obs, 0, C)
+            out = rollout(self.model, X, ar, use_residual=self.use_residual)  # [1, N, ar * C], the script's gnn_out
+            # the last observed regional frame and the ar truths, physical units, (lat, lon)-major: (x - 0) / 1 is exact
+            phys, _ = hip.window_pack(self.rs, t0 + (self.obs - 1), self._zeros, self._ones, C, 1 + ar, 0)
+            persist = phys[:, :, :C]
+            for h in range(ar):
+                truth = phys[0, :, (1 + h) * C:(2 + h) * C]
+                self._step(out[0, :, h * C:(h + 1) * C], truth, h)
+                hip.pipeline_sqerr(self._buf, truth, self._score, h, self._acc_grid[:V - 1], self._acc_stn[:V - 1])
+                hip.pipeline_sqerr(persist, truth, self._score, h, self._acc_grid[V - 1:], self._acc_stn[V - 1:])
+                self.count_grid[h] += self.G
+                self.count_stn[h] += len(self.score_rows)
+                if keep:
+                    kept.append((i, h, torch.cat([self._buf, persist]), truth.clone()))
+        return kept if keep else None
+
+    def results(self) -> dict:
+        """The accumulated sums and the script's tables (`:678-766`, `:811-827`), host values:
+        mse_grid / mse_stn [variant][h] -> float64 [C] sums of squared errors, count_grid / count_stn [h],
+        rmse_grid / rmse_stn [variant] -> [ar, C], t2m_rmse_grid / t2m_rmse_stn [variant] -> the ar horizons and their
+        mean, skill [variant] -> percent against persistence averaged over the non-static channels, the ar horizons and
+        their mean."""
+        grid, stn = self._acc_grid.cpu().numpy(), self._acc_stn.cpu().numpy()
+        ng = np.maximum(np.array(self.count_grid, dtype=np.float64), 1)[:, None]
+        ns = np.maximum(np.array(self.count_stn, dtype=np.float64), 1)[:, None]
+        res = {"variants": list(self.variants), "count_grid": list(self.count_grid), "count_stn": list(self.count_stn),
+               "mse_grid": {}, "mse_stn": {}, "rmse_grid": {}, "rmse_stn": {}, "t2m_rmse_grid": {}, "t2m_rmse_stn": {},
+               "skill": {}}
+        for v, name in enumerate(self.variants):
+            res["mse_grid"][name], res["mse_stn"][name] = list(grid[v]), list(stn[v])
+            res["rmse_grid"][name], res["rmse_stn"][name] = np.sqrt(grid[v] / ng), np.sqrt(stn[v] / ns)
+            if "t2m" in self.var_order:
+                t = self.var_order.index("t2m")
+                for key in ("rmse_grid", "rmse_stn"):
+                    vals = [float(x) for x in res[key][name][:, t]]
+                    res["t2m_" + key][name] = vals + [float(np.mean(vals))]
+        dyn = [c for c in range(self.C) if c not in self.static_channels]
+        rp = res["rmse_grid"]["Persistence"]
+        for name in self.variants[:-1]:
+            rm = res["rmse_grid"][name]
+            vals = [float(np.mean([(1.0 - rm[h, c] / rp[h, c]) * 100 if rp[h, c] > 1e-8 else 0 for c in dyn]))
+                    for h in range(self.ar)]
+            res["skill"][name] = vals + [float(np.mean(vals))]
+        return res

@@ -354,6 +354,29 @@ def regrid_tables(src_lats, src_lons, dst_lats, dst_lons):
     return cell.reshape(-1, 2), w.reshape(-1, 4)
 
 
+def regrid_tables_latlon(src_lats, src_lons, dst_lats, dst_lons):
+    """`regrid_tables` for an interpolator whose axes are (lats, lons) (scripts/build_multires_dataset.py:220-224),
+    targets (dst_lats[i], dst_lons[j]) numbered latitude-major (i * len(dst_lons) + j): int32 [nt, 2] cells (lat, lon)
+    and float64 [nt, 4] weights of the corners (lat, lon), (lat, lon+1), (lat+1, lon), (lat+1, lon+1), each formed as
+    (1 * w_lat) * w_lon.  The products equal those of `regrid_tables`; the ORDER of the corners is what differs, and
+    with it the float64 sum."""
+    ilat, ylat = find_cells(src_lats, dst_lats)
+    ilon, ylon = find_cells(src_lons, dst_lons)
+    ni, nj = len(ilat), len(ilon)
+    cell = np.empty((ni, nj, 2), dtype=np.int32)
+    cell[..., 0] = ilat[:, None]
+    cell[..., 1] = ilon[None, :]
+    one = np.float64(1.0)
+    lat_w = ((one * (1 - ylat))[:, None], (one * ylat)[:, None])
+    lon_w = ((1 - ylon)[None, :], ylon[None, :])
+    w = np.empty((ni, nj, 4), dtype=np.float64)
+    w[..., 0] = lat_w[0] * lon_w[0]
+    w[..., 1] = lat_w[0] * lon_w[1]
+    w[..., 2] = lat_w[1] * lon_w[0]
+    w[..., 3] = lat_w[1] * lon_w[1]
+    return cell.reshape(-1, 2), w.reshape(-1, 4)
+
+
 _TABLES = {}
 
 

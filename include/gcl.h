@@ -641,6 +641,52 @@ int gcl_mos_table_apply(const void* in, int32_t f64, int64_t bs, int64_t gs, int
                         int64_t ogs, int64_t oss, int32_t G, int32_t steps, int32_t C, int32_t t2m,
                         const double* step_bias, int32_t nvalid, int32_t B, gcl_stream_t stream);
 
+/* ---- Multi-resolution input (csrc/multires.hip) ----
+ * Windows of the flat multires node set - the n_kept global points outside the box in (lat, lon)-major order, then
+ * n_reg regional points - packed from the device-resident fp16 series without the flat series ever existing.  Replaces
+ * scripts/build_multires_dataset.py:151-234 (build_interpolate_mode) / :270-345 (build_merge_mode) followed by the
+ * flat branch of src/data/dataloader_chunked.py:186-200, and scripts/evaluate_full_pipeline.py:113-144
+ * (build_multires_frame) with the z-score of :463.
+ *   gseries (Tg, n_lon, n_lat, Ctg); rank[lat * n_lon + lon] = output row of a global point or -1 (removed).
+ *   rseries != NULL (merge): regional rows are rseries (Tr, rn_lon, rn_lat, Ctr) in (lat, lon)-major order.
+ *   rseries == NULL (interpolate): regional row i is the bilinear value of the global frame at its four corners
+ *     corner[i, 0..3] (positions lon * n_lat + lat) with float64 weights w[i, 0..3], added in that order onto 0.0 in
+ *     float64 with every product rounded on its own (scipy RegularGridInterpolator((lats, lons)), float32 values), then
+ *     rounded to float32 and, with quantize = 1, through float16 (what the builder stores and the loader reads back).
+ *   Window b holds the frames t0[b] + off_g (global) / t0[b] + off_r (regional) + 0 .. obs + pred - 1; a frame outside
+ *   its series comes back as NaN.  mean / stdv (both or neither): (x - mean[c]) / std[c] in float32 on the first C
+ *   channels.  out_f16 = 1: X / Y are binary16 buffers.  X [B, n_kept + n_reg, obs * C], Y [.., pred * C] or NULL. */
+int gcl_multires_window_pack(const uint16_t* gseries, int64_t Tg, int32_t n_lon, int32_t n_lat, int32_t Ctg,
+                             const uint16_t* rseries, int64_t Tr, int32_t rn_lon, int32_t rn_lat, int32_t Ctr,
+                             const int32_t* rank, int32_t n_kept, int32_t n_reg, const int32_t* corner,
+                             const double* w, const int64_t* t0, int64_t off_g, int64_t off_r, const float* mean,
+                             const float* stdv, int32_t C, int32_t obs, int32_t pred, int32_t quantize,
+                             int32_t out_f16, void* X, void* Y, int32_t B, gcl_stream_t stream);
+
+/* ---- Full-pipeline evaluation glue (csrc/pipeline.hip; scripts/evaluate_full_pipeline.py:449-666) ----
+ * ROI rows in physical units (:502-511, :545): raw[g, c] = v * std[c] + mean[c] in float32, product and sum rounded
+ * separately, v = pred[r, c] (+ x_last[r, c] first when x_last is given), r = rows[g] or row0 + g when rows is NULL;
+ * lapse (optional) = raw with column t_idx replaced by t2m + (z_surf - elev) * 6.5e-3 from the row's own z_idx column
+ * (t_idx = z_idx = -1: plain copy).  lapse_f64 = 0: every step in float32 (numpy with a Python-float elevation);
+ * 1: difference and product in float64, (double) t2m + delta rounded to float32 once (an np.float64 elevation). */
+int gcl_pipeline_roi_phys(const float* pred, int64_t ldp, const float* x_last, int64_t ldx, const int32_t* rows,
+                          int32_t row0, int32_t G, int32_t C, const float* mean, const float* stdv, int32_t t_idx,
+                          int32_t z_idx, double elev, int32_t lapse_f64, float* raw, float* lapse,
+                          gcl_stream_t stream);
+/* apply_lapse (:184-200) on contiguous in [G, S, C] -> out (must not alias): column t_idx of every step corrected
+ * with z_idx of step 0; lapse_f64 as above. */
+int gcl_pipeline_lapse(const float* in, float* out, int32_t G, int32_t S, int32_t C, int32_t t_idx, int32_t z_idx,
+                       double elev, int32_t lapse_f64, gcl_stream_t stream);
+/* simulate_station_obs (:203-222): obs [G, C] = truth rows at the S grid points stn[], NaN elsewhere. */
+int gcl_pipeline_station_obs(const float* truth, int64_t ldt, const int32_t* stn, int32_t S, int32_t G, int32_t C,
+                             float* obs, gcl_stream_t stream);
+/* Error sums of V variants preds[v * vs + g * ldp + c] against truth (:644-652) at horizon h:
+ * acc_grid[v, h, c] += sum_g (p - t)^2, acc_stn[v, h, c] (optional) += the same over the rows stn[0..S) as listed.
+ * Difference and square in float32, sums in float64 in a fixed order (no atomics); C <= 256. */
+int gcl_pipeline_sqerr(const float* preds, int64_t vs, int64_t ldp, int32_t V, const float* truth, int64_t ldt,
+                       const int32_t* stn, int32_t S, int32_t G, int32_t C, int32_t H, int32_t h, double* acc_grid,
+                       double* acc_stn, gcl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
