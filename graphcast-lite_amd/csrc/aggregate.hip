@@ -20,6 +20,7 @@
 
 #include "common.h"
 #include "halo.h"
+#include "mfma_io.h"
 
 namespace {
 
@@ -28,14 +29,17 @@ namespace {
 // (one round trip, prefetched one batch ahead) -> EW neighbour rows issued together -> store.
 // Rows with more than EW in-edges finish in a CSR loop (wave-uniform test).  Padded slots load a
 // valid row and are masked with a select (not a multiply), so non-finite values cannot leak.
-template <int LPR, bool VL, bool VS, int EW, int ITER>
+// PRES: source rows with present[j] < 0 count as zero rows and are never read - their loads go to the zero page through
+// a pointer select, so the instruction stream and the arithmetic are those of the plain kernel (gcl_aggregate_present).
+template <int LPR, bool VL, bool VS, int EW, int ITER, bool PRES = false>
 __global__ __launch_bounds__(256) void agg_kernel(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
                                                   const float* __restrict__ w, const int32_t* __restrict__ ecol,
                                                   const float* __restrict__ ew, const float* __restrict__ H,
                                                   int64_t ldh, int64_t bsh, const float* __restrict__ bias,
                                                   float* __restrict__ Y, int64_t ldy, int64_t bsy, int32_t n,
                                                   int32_t B, int32_t F, int32_t nRB, int32_t xcd_map,
-                                                  int32_t nt_store, const int32_t* __restrict__ order16) {
+                                                  int32_t nt_store, const int32_t* __restrict__ order16,
+                                                  const int32_t* __restrict__ present = nullptr) {
   constexpr int RPW = 64 / LPR;
   constexpr int EL = LPR < gcl::kEll ? LPR : gcl::kEll;  // ELL entries a lane group can hold
   static_assert(EW <= EL, "ELL width exceeds the lanes of a row group");
@@ -76,6 +80,7 @@ __global__ __launch_bounds__(256) void agg_kernel(const int32_t* __restrict__ ro
 
   auto ld4 = [&](int j, float& x0, float& x1, float& x2, float& x3) {
     const float* p = Hb + (int64_t)j * ldh + cc;
+    if (PRES) p = j >= 0 ? p : reinterpret_cast<const float*>(gcl::mfma_io::zero4);  // absent sources carry index -1
     if (VL) {
       const float4 v = *reinterpret_cast<const float4*>(p);
       x0 = v.x; x1 = v.y; x2 = v.z; x3 = v.w;
@@ -95,6 +100,7 @@ __global__ __launch_bounds__(256) void agg_kernel(const int32_t* __restrict__ ro
     end = rowptr[rc + 1];
     cj = ecol[(int64_t)rc * gcl::kEll + (l & (EL - 1))];
     wj = ew[(int64_t)rc * gcl::kEll + (l & (EL - 1))];
+    if (PRES) cj = present[cj] >= 0 ? cj : -1;
   };
   int start, end, cj;
   float wj;
@@ -139,6 +145,7 @@ __global__ __launch_bounds__(256) void agg_kernel(const int32_t* __restrict__ ro
         if (mine < end) {
           oj = col[mine];
           ow = w[mine];
+          if (PRES) oj = present[oj] >= 0 ? oj : -1;
         }
         const int cnt = min(LPR, end - base);
         for (int k = 0; k < cnt; k += 4) {
@@ -191,13 +198,14 @@ __global__ __launch_bounds__(256) void agg_kernel(const int32_t* __restrict__ ro
 // in flight each) and are combined through LDS in a fixed order.  Only rows with more than kHeavy
 // edges take this path (polar mesh nodes of E_G2M / E_M2G at 512x256: up to 943 edges), so a
 // single wave no longer serialises hundreds of dependent gathers at the tail of the launch.
-template <int LPR, bool VL, bool VS>
+template <int LPR, bool VL, bool VS, bool PRES = false>
 __global__ __launch_bounds__(256) void agg_heavy_kernel(const int32_t* __restrict__ rows_heavy,
                                                         const int32_t* __restrict__ rowptr,
                                                         const int32_t* __restrict__ col, const float* __restrict__ w,
                                                         const float* __restrict__ H, int64_t ldh, int64_t bsh,
                                                         const float* __restrict__ bias, float* __restrict__ Y,
-                                                        int64_t ldy, int64_t bsy, int32_t F) {
+                                                        int64_t ldy, int64_t bsy, int32_t F,
+                                                        const int32_t* __restrict__ present = nullptr) {
   constexpr int NG = 256 / LPR;
   __shared__ float red[NG][LPR * 4 + 1];
   const int row = rows_heavy[blockIdx.x];
@@ -211,6 +219,7 @@ __global__ __launch_bounds__(256) void agg_heavy_kernel(const int32_t* __restric
   float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
   auto ld4 = [&](int j, float& x0, float& x1, float& x2, float& x3) {
     const float* p = Hb + (int64_t)j * ldh + cc;
+    if (PRES) p = present[j] >= 0 ? p : reinterpret_cast<const float*>(gcl::mfma_io::zero4);
     if (VL) {
       const float4 v = *reinterpret_cast<const float4*>(p);
       x0 = v.x; x1 = v.y; x2 = v.z; x3 = v.w;
@@ -314,14 +323,19 @@ __device__ unsigned long long agg_stamps[8 * 4096];  // diagnostic builds only (
 // stores of one item are still in flight while the loads of the next are issued.  One image per block, two
 // barriers per item (loaded / free again).
 // ---------------------------------------------------------------------------------------------------------
-template <int LPR, int T, int MAXPW>
+// PRES: source rows with present[j] < 0 count as zero rows and are never read.  The table is applied once per tile, to
+// the wave's own rows and to its list entries (an absent one becomes -1), and kept in registers across the samples of
+// the XCD group; an absent row's DMA reads the zero page (all lanes of the row the same 16 bytes) through a pointer
+// select, so the image holds the zeros the caller would otherwise have had to store, and the sums are untouched.
+template <int LPR, int T, int MAXPW, bool PRES = false>
 __global__ __launch_bounds__(256) void agg_halo_loop_kernel(const int32_t* __restrict__ list, const int32_t* __restrict__ cnt,
                                                             const int2* __restrict__ rec, const int32_t* __restrict__ rowptr,
                                                             const int32_t* __restrict__ opos, const float* __restrict__ w,
                                                             int32_t smax, const float* __restrict__ H, int64_t ldh,
                                                             int64_t bsh, const float* __restrict__ bias,
                                                             float* __restrict__ Y, int64_t ldy, int64_t bsy, int32_t n,
-                                                            int32_t B, int32_t F, int32_t ntiles, int32_t nt_store) {
+                                                            int32_t B, int32_t F, int32_t ntiles, int32_t nt_store,
+                                                            const int32_t* __restrict__ present = nullptr) {
   extern __shared__ float4 img[];  // (smax + 1) * LPR float4: own rows, halo rows, zero row
   constexpr int RPW = 64 / LPR;
   constexpr int NW = 4;              // waves per block
@@ -370,11 +384,13 @@ __global__ __launch_bounds__(256) void agg_halo_loop_kernel(const int32_t* __res
         const int jr = tl[e0 + r];
         j = sub == r ? jr : j;
       }
-      jj[q] = j;
+      jj[q] = (PRES && present[j] < 0) ? -1 : j;
     }
   };
   int jj[MAXPW], nhalo = 0, tile = -1;
   int2 rc[NIT];
+  bool own[PRES ? NIT : 1];  // PRES: presence of the wave's own rows
+  const char* const zpage = reinterpret_cast<const char*>(gcl::mfma_io::zero4);
 #ifdef GCL_STAMPS
   unsigned long long st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, st_last = __builtin_amdgcn_s_memtime();
 #endif
@@ -387,6 +403,13 @@ __global__ __launch_bounds__(256) void agg_halo_loop_kernel(const int32_t* __res
     if (newtile) {
       tile = tnew;
       fetch_list(tile, jj, nhalo);
+      if (PRES) {
+#pragma unroll
+        for (int it = 0; it < NIT; ++it) {
+          const int row = tile * T + wave * (T / NW) + sub + it * RPW;
+          own[it] = present[row < n ? row : n - 1] >= 0;
+        }
+      }
     }
     GCL_AGG_STAMP(0)  // new tile: list + records
     const char* Hc = reinterpret_cast<const char*>(H + (int64_t)b * bsh);
@@ -397,6 +420,7 @@ __global__ __launch_bounds__(256) void agg_halo_loop_kernel(const int32_t* __res
     for (int it = 0; it < NIT; ++it) {
       const int row = row0 + it * RPW;
       const char* src = Hc + (__umul24(row < n ? row : n - 1, ldb) + cb);
+      if (PRES) src = own[PRES ? it : 0] ? src : zpage;
       __builtin_amdgcn_global_load_lds((gcl_gptr_t)src, (gcl_lptr_t)(img + (wave * (T / NW) + it * RPW) * LPR), 16, 0, 0);
     }
 #pragma unroll
@@ -404,6 +428,7 @@ __global__ __launch_bounds__(256) void agg_halo_loop_kernel(const int32_t* __res
       const int p = wave + NW * q;
       if (p < nhalo) {
         const char* src = Hc + (__umul24(jj[q], ldb) + cb);
+        if (PRES) src = jj[q] >= 0 ? src : zpage;
         __builtin_amdgcn_global_load_lds((gcl_gptr_t)src, (gcl_lptr_t)(img + (T + p * RPW) * LPR), 16, 0, 0);
       }
     }
@@ -507,7 +532,8 @@ struct AggArgs {
 // Source-tile path: returns GCL_OK after launching, or -1 when this call is not eligible (agg_kernel runs instead).
 template <int LPR>
 int launch_agg_halo(const AggArgs& ga, const float* h, int64_t ldh, int64_t bsh, const float* bias, float* y,
-                    int64_t ldy, int64_t bsy, int32_t n, int32_t B, int32_t F, hipStream_t st) {
+                    int64_t ldy, int64_t bsy, int32_t n, int32_t B, int32_t F, hipStream_t st,
+                    const int32_t* present = nullptr) {
   const int enabled = gcl::env_int("GCL_AGG_HALO", 1);  // read per call: the parity tests switch it to compare the two kernels
   static const int force_t = gcl::env_int("GCL_AGG_HALO_T", 0);    // tuning: tile height
   static const int bpc_env = gcl::env_int("GCL_AGG_HALO_BPC", 0);  // tuning: blocks per CU
@@ -537,11 +563,17 @@ int launch_agg_halo(const AggArgs& ga, const float* h, int64_t ldh, int64_t bsh,
   auto go = [&](auto kern) -> int {
     GCL_ENSURE_DYN_LDS(kern, (size_t)lds);
     hipLaunchKernelGGL(kern, grid, block, (size_t)lds, st, hl->list, hl->cnt, reinterpret_cast<const int2*>(hl->rec),
-                       ga.rowptr, hl->opos, ga.w, hl->smax, h, ldh, bsh, bias, y, ldy, bsy, n, B, F, hl->ntiles, nt);
+                       ga.rowptr, hl->opos, ga.w, hl->smax, h, ldh, bsh, bias, y, ldy, bsy, n, B, F, hl->ntiles, nt, present);
     return GCL_OK;
   };
   int rc;
-  if (hl->T == 64)
+  if (present && hl->T == 64)
+    rc = mpw <= 4 ? go(&agg_halo_loop_kernel<LPR, 64, 4, true>) : mpw <= 8 ? go(&agg_halo_loop_kernel<LPR, 64, 8, true>)
+       : mpw <= 16 ? go(&agg_halo_loop_kernel<LPR, 64, 16, true>) : go(&agg_halo_loop_kernel<LPR, 64, 32, true>);
+  else if (present)
+    rc = mpw <= 4 ? go(&agg_halo_loop_kernel<LPR, 32, 4, true>) : mpw <= 8 ? go(&agg_halo_loop_kernel<LPR, 32, 8, true>)
+       : mpw <= 16 ? go(&agg_halo_loop_kernel<LPR, 32, 16, true>) : go(&agg_halo_loop_kernel<LPR, 32, 32, true>);
+  else if (hl->T == 64)
     rc = mpw <= 4 ? go(&agg_halo_loop_kernel<LPR, 64, 4>) : mpw <= 8 ? go(&agg_halo_loop_kernel<LPR, 64, 8>)
        : mpw <= 16 ? go(&agg_halo_loop_kernel<LPR, 64, 16>) : go(&agg_halo_loop_kernel<LPR, 64, 32>);
   else
@@ -554,11 +586,24 @@ int launch_agg_halo(const AggArgs& ga, const float* h, int64_t ldh, int64_t bsh,
 
 template <int LPR>
 int launch_agg_heavy(const AggArgs& ga, const float* h, int64_t ldh, int64_t bsh, const float* bias, float* y,
-                     int64_t ldy, int64_t bsy, int32_t B, int32_t F, bool vl, bool vs, hipStream_t st) {
+                     int64_t ldy, int64_t bsy, int32_t B, int32_t F, bool vl, bool vs, hipStream_t st,
+                     const int32_t* present = nullptr) {
   dim3 hgrid((unsigned)ga.n_heavy, (unsigned)B), block(256);
+  if (present) {
+#define GCL_AGGH(VL_, VS_)                                                                                       \
+  hipLaunchKernelGGL((agg_heavy_kernel<LPR, VL_, VS_, true>), hgrid, block, 0, st, ga.heavy, ga.rowptr, ga.col, ga.w, \
+                     h, ldh, bsh, bias, y, ldy, bsy, F, present)
+    if (vl && vs) GCL_AGGH(true, true);
+    else if (vl) GCL_AGGH(true, false);
+    else if (vs) GCL_AGGH(false, true);
+    else GCL_AGGH(false, false);
+#undef GCL_AGGH
+    GCL_CHECK_LAUNCH();
+    return GCL_OK;
+  }
 #define GCL_AGGH(VL_, VS_)                                                                                       \
   hipLaunchKernelGGL((agg_heavy_kernel<LPR, VL_, VS_>), hgrid, block, 0, st, ga.heavy, ga.rowptr, ga.col, ga.w, h, \
-                     ldh, bsh, bias, y, ldy, bsy, F)
+                     ldh, bsh, bias, y, ldy, bsy, F, (const int32_t*)nullptr)
   if (vl && vs) GCL_AGGH(true, true);
   else if (vl) GCL_AGGH(true, false);
   else if (vs) GCL_AGGH(false, true);
@@ -570,7 +615,7 @@ int launch_agg_heavy(const AggArgs& ga, const float* h, int64_t ldh, int64_t bsh
 
 template <int LPR>
 int launch_agg(const AggArgs& ga, const float* h, int64_t ldh, int64_t bsh, const float* bias, float* y, int64_t ldy,
-               int64_t bsy, int32_t n, int32_t B, int32_t F, hipStream_t st) {
+               int64_t bsy, int32_t n, int32_t B, int32_t F, hipStream_t st, const int32_t* present = nullptr) {
   constexpr int RPW = 64 / LPR;
   constexpr int EL = LPR < gcl::kEll ? LPR : gcl::kEll;
   // vector loads need 16-B aligned rows and a padded tail (ldh >= roundup(F,4))
@@ -578,10 +623,10 @@ int launch_agg(const AggArgs& ga, const float* h, int64_t ldh, int64_t bsh, cons
   const bool vs = (ldy % 4 == 0) && (bsy % 4 == 0) && gcl::aligned16(y) && (F % 4 == 0);
   if constexpr (LPR >= 16) {
     if (vl && vs && (!bias || gcl::aligned16(bias))) {
-      const int hr = launch_agg_halo<LPR>(ga, h, ldh, bsh, bias, y, ldy, bsy, n, B, F, st);
+      const int hr = launch_agg_halo<LPR>(ga, h, ldh, bsh, bias, y, ldy, bsy, n, B, F, st, present);
       if (hr >= 0) {
         if (hr != GCL_OK || ga.n_heavy == 0) return hr;
-        return launch_agg_heavy<LPR>(ga, h, ldh, bsh, bias, y, ldy, bsy, B, F, true, true, st);
+        return launch_agg_heavy<LPR>(ga, h, ldh, bsh, bias, y, ldy, bsy, B, F, true, true, st, present);
       }
     }
   }
@@ -593,8 +638,9 @@ int launch_agg(const AggArgs& ga, const float* h, int64_t ldh, int64_t bsh, cons
   ewidth = ewidth >= 8 ? 8 : ewidth >= 4 ? 4 : ewidth >= 2 ? 2 : 1;
   // measured on MI355X (profiles/r01_c_*): dense prefixes (mesh) run best with one batch per wave,
   // near-diagonal bipartite graphs with two (next batch's metadata prefetched)
-  const int iter = (iter_env == 1 || iter_env == 2 || iter_env == 4 || iter_env == 8) ? iter_env
-                                                                                       : (ewidth >= 4 ? 1 : 2);
+  // (the variant with absent sources exists for the per-graph default only)
+  const int iter = (!present && (iter_env == 1 || iter_env == 2 || iter_env == 4 || iter_env == 8)) ? iter_env
+                                                                                                     : (ewidth >= 4 ? 1 : 2);
   int32_t nRB = (int32_t)gcl::cdiv(n, RPW * 4 * iter);
   if (ga.order16 && RPW * 4 * iter <= 16) nRB = ga.n_order16 * (16 / (RPW * 4 * iter));  // whole 16-row groups (rows >= n are masked)
   const int xcd_map = B >= gcl::kNumXCD ? 1 : 0;
@@ -604,9 +650,16 @@ int launch_agg(const AggArgs& ga, const float* h, int64_t ldh, int64_t bsh, cons
   const int32_t* order16 = (RPW * 4 * iter <= 16) ? ga.order16 : nullptr;
 #define GCL_AGG4(VL_, VS_, EW_, IT_)                                                                             \
   hipLaunchKernelGGL((agg_kernel<LPR, VL_, VS_, EW_, IT_>), grid, block, 0, st, ga.rowptr, ga.col, ga.w, ga.ecol, \
-                     ga.ew, h, ldh, bsh, bias, y, ldy, bsy, n, B, F, nRB, xcd_map, nt, order16)
+                     ga.ew, h, ldh, bsh, bias, y, ldy, bsy, n, B, F, nRB, xcd_map, nt, order16, (const int32_t*)nullptr)
+#define GCL_AGGP(VL_, VS_, EW_, IT_)                                                                                   \
+  hipLaunchKernelGGL((agg_kernel<LPR, VL_, VS_, EW_, IT_, true>), grid, block, 0, st, ga.rowptr, ga.col, ga.w, ga.ecol, \
+                     ga.ew, h, ldh, bsh, bias, y, ldy, bsy, n, B, F, nRB, xcd_map, nt, order16, present)
 #define GCL_AGG3(VL_, VS_, EW_)              \
   do {                                       \
+    if (present) {                           \
+      if (EW_ >= 4) GCL_AGGP(VL_, VS_, EW_, 1); \
+      else GCL_AGGP(VL_, VS_, EW_, 2);       \
+    } else                                   \
     if (iter == 8) GCL_AGG4(VL_, VS_, EW_, 8); \
     else if (iter == 4) GCL_AGG4(VL_, VS_, EW_, 4); \
     else if (iter == 2) GCL_AGG4(VL_, VS_, EW_, 2); \
@@ -626,16 +679,17 @@ int launch_agg(const AggArgs& ga, const float* h, int64_t ldh, int64_t bsh, cons
 #undef GCL_AGG2
 #undef GCL_AGG3
 #undef GCL_AGG4
+#undef GCL_AGGP
   GCL_CHECK_LAUNCH();
-  if (ga.n_heavy > 0) return launch_agg_heavy<LPR>(ga, h, ldh, bsh, bias, y, ldy, bsy, B, F, vl, vs, st);
+  if (ga.n_heavy > 0) return launch_agg_heavy<LPR>(ga, h, ldh, bsh, bias, y, ldy, bsy, B, F, vl, vs, st, present);
   return GCL_OK;
 }
 
 }  // namespace
 
-extern "C" int gcl_aggregate(const gcl_graph_t* g, int32_t transpose, const float* h, int64_t ldh, int64_t bsh,
-                             const float* bias, float* y, int64_t ldy, int64_t bsy, int32_t B, int32_t F,
-                             gcl_stream_t stream) {
+static int aggregate_impl(const gcl_graph_t* g, int32_t transpose, const float* h, int64_t ldh, int64_t bsh,
+                          const int32_t* present, const float* bias, float* y, int64_t ldy, int64_t bsy, int32_t B,
+                          int32_t F, gcl_stream_t stream) {
   GCL_CHECK_ARG(g && h && y, "aggregate: null argument");
   GCL_CHECK_ARG(B > 0 && F > 0 && F <= 256, "aggregate: unsupported B=%d F=%d (F must be in 1..256)", B, F);
   GCL_CHECK_ARG(ldh >= F && ldy >= F, "aggregate: leading dimension smaller than F");
@@ -656,9 +710,22 @@ extern "C" int gcl_aggregate(const gcl_graph_t* g, int32_t transpose, const floa
   GCL_CHECK_ARG(B <= 65535 || ga.n_heavy == 0, "aggregate: batch too large for the heavy-row launch");
   hipStream_t st = (hipStream_t)stream;
   const int lanes = (F + 3) / 4;
-  if (lanes <= 4) return launch_agg<4>(ga, h, ldh, bsh, bias, y, ldy, bsy, g->n, B, F, st);
-  if (lanes <= 8) return launch_agg<8>(ga, h, ldh, bsh, bias, y, ldy, bsy, g->n, B, F, st);
-  if (lanes <= 16) return launch_agg<16>(ga, h, ldh, bsh, bias, y, ldy, bsy, g->n, B, F, st);
-  if (lanes <= 32) return launch_agg<32>(ga, h, ldh, bsh, bias, y, ldy, bsy, g->n, B, F, st);
-  return launch_agg<64>(ga, h, ldh, bsh, bias, y, ldy, bsy, g->n, B, F, st);
+  if (lanes <= 4) return launch_agg<4>(ga, h, ldh, bsh, bias, y, ldy, bsy, g->n, B, F, st, present);
+  if (lanes <= 8) return launch_agg<8>(ga, h, ldh, bsh, bias, y, ldy, bsy, g->n, B, F, st, present);
+  if (lanes <= 16) return launch_agg<16>(ga, h, ldh, bsh, bias, y, ldy, bsy, g->n, B, F, st, present);
+  if (lanes <= 32) return launch_agg<32>(ga, h, ldh, bsh, bias, y, ldy, bsy, g->n, B, F, st, present);
+  return launch_agg<64>(ga, h, ldh, bsh, bias, y, ldy, bsy, g->n, B, F, st, present);
+}
+
+extern "C" int gcl_aggregate(const gcl_graph_t* g, int32_t transpose, const float* h, int64_t ldh, int64_t bsh,
+                             const float* bias, float* y, int64_t ldy, int64_t bsy, int32_t B, int32_t F,
+                             gcl_stream_t stream) {
+  return aggregate_impl(g, transpose, h, ldh, bsh, nullptr, bias, y, ldy, bsy, B, F, stream);
+}
+
+extern "C" int gcl_aggregate_present(const gcl_graph_t* g, int32_t transpose, const float* h, int64_t ldh, int64_t bsh,
+                                     const int32_t* present, const float* bias, float* y, int64_t ldy, int64_t bsy,
+                                     int32_t B, int32_t F, gcl_stream_t stream) {
+  GCL_CHECK_ARG(present, "aggregate_present: null presence table");
+  return aggregate_impl(g, transpose, h, ldh, bsh, present, bias, y, ldy, bsy, B, F, stream);
 }

@@ -657,13 +657,20 @@ __device__ __forceinline__ void mfma_half_x3(f32x16& acc, const float* __restric
 // row list otherwise (the compact pipeline's mesh latents: models.py::_forward_compact, functional.MeshLatFn - 81 % of
 // the mesh rows at 64x32 are batch-invariant and then come from a 2 MB region that stays in the L2).  The table is
 // applied once per tile (list entries and own rows), so an item costs two more vector instructions per DMA piece.
-template <int ACT, int MAXPW, int STAUX = 0, bool DIRECT = false, bool INTER = false, bool TAB = false>
+// PRED (DIRECT only): an output-row predicate - row i is stored only when present[i] >= 0 (a stage boundary behind this
+// layer drops the other rows and nobody reads them).  The tile's 64 entries go through a small LDS table (two tiles deep:
+// the next tile's entries arrive while this item's stores still read this tile's) and are folded into the store offsets:
+// an absent row's offset is out of range, which the buffer store drops - no branch around the stores, no live registers
+// across the dense part.  The sums and the dense part are computed for every row as before.
+template <int ACT, int MAXPW, int STAUX = 0, bool DIRECT = false, bool INTER = false, bool TAB = false, bool PRED = false>
 __global__ __launch_bounds__(256, 3) void gcn_halo_fwd_kernel(
     const int32_t* __restrict__ list, const int32_t* __restrict__ cnt, const int2* __restrict__ rec,
     const int32_t* __restrict__ rowptr, const int32_t* __restrict__ opos, const float* __restrict__ w, int32_t smax,
     const float* __restrict__ X, int64_t ldx, int64_t bsx, const float* __restrict__ slope_p, const float* __restrict__ W,
     const float* __restrict__ bias, float* __restrict__ Y, int64_t ldy, int64_t bsy, int32_t n, int32_t B, int32_t K,
-    int32_t N, int32_t Nst, int32_t ntiles, const int32_t* __restrict__ tab = nullptr) {
+    int32_t N, int32_t Nst, int32_t ntiles, const int32_t* __restrict__ tab = nullptr,
+    const int32_t* __restrict__ present = nullptr) {
+  static_assert(!PRED || DIRECT, "the row predicate is folded into the direct stores");
   using gcl::halo::glds16;
   using gcl::halo::row_bcast;
   extern __shared__ __align__(16) float smem[];
@@ -675,6 +682,7 @@ __global__ __launch_bounds__(256, 3) void gcn_halo_fwd_kernel(
   float* At = smem;                                                   // [2][AtF]
   float* imgf = At + 2 * AtF;                                         // [(smax + 1) * 16] float4
   float4* img = reinterpret_cast<float4*>(imgf);
+  int* ptab = reinterpret_cast<int*>(imgf + (size_t)(smax + 1) * 64);  // PRED: [2][64] presence of the rows of a tile
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int sub = lane >> 4, l = lane & 15, c0 = l * 4;
@@ -711,8 +719,13 @@ __global__ __launch_bounds__(256, 3) void gcn_halo_fwd_kernel(
   int jj[MAXPW], nhalo = 0, tile = -1;
   int own[TAB ? NIT : 1];  // TAB: table entries of the wave's own rows
   int2 rc[NIT];
+  int pv = 0;  // PRED: entry of row (tile, wave * 16 + lane & 15), on its way into the LDS table
   auto new_tile = [&](int t) {  // list entries (scalar loads) and edge records of tile t: kept for all samples of the group
     tile = t;
+    if (PRED) {
+      const int row = t * T + wave * 16 + (lane & 15);
+      pv = present[row < n ? row : n - 1];
+    }
     nhalo = cnt[t] / RPW;
     const int32_t* __restrict__ tl = list + (int64_t)t * hstride;
 #pragma unroll
@@ -770,6 +783,7 @@ __global__ __launch_bounds__(256, 3) void gcn_halo_fwd_kernel(
     }
   };
   new_tile(m / nsamp);
+  if (PRED && lane < 16) ptab[(tile & 1) * 64 + wave * 16 + lane] = pv;  // read after the barriers of the first item
 #pragma unroll
   for (int it = 0; it < NIT; ++it) asm volatile("" : "+v"(rc[it].x), "+v"(rc[it].y));  // records are in before any DMA is issued
   if (TAB) {
@@ -856,9 +870,10 @@ __global__ __launch_bounds__(256, 3) void gcn_halo_fwd_kernel(
     GCL_STAMP(2);  // barrier
     // ---- the next item's DMA: in flight under the dense part and the stores of this one
     const bool more = m + 1 < mend;
+    bool fresh = false;  // PRED: a new tile's entries are on their way
     if (more) {
       const int tn = (m + 1) / nsamp;
-      if (tn != tile) new_tile(tn);
+      if (tn != tile) { new_tile(tn); fresh = true; }
       if (!INTER) stage(m + 1);
       else if (TAB) Xn = reinterpret_cast<const char*>(X), sbn = (unsigned)(xcd + gcl::kNumXCD * (m + 1 - tile * nsamp)) * (unsigned)bsx * 4u;
       else Xn = reinterpret_cast<const char*>(X + (int64_t)(xcd + gcl::kNumXCD * (m + 1 - tile * nsamp)) * bsx);
@@ -890,9 +905,20 @@ __global__ __launch_bounds__(256, 3) void gcn_halo_fwd_kernel(
       const __amdgpu_buffer_rsrc_t ry = make_rsrc(Yb, nr > 0 ? ((int64_t)(nr - 1) * ldy + Nst) * 4 : 0);
       const unsigned cofs = col < Nst ? (unsigned)col * 4u : kOOB;
       const unsigned ldyb = (unsigned)ldy * 4u;
+      // PRED: the next tile's entries go into the other half of the table, this item's come from the half of its own
+      // tile.  The half being overwritten was last read in the store section of an EARLIER item (the previous one when a
+      // tile has a single sample), and every wave has passed both barriers of the current item since - those barriers,
+      // not the distance in tiles, make the overwrite safe; the new half is read after the barriers of the next item.  Registers 4q .. 4q + 3 hold rows 8q + 4 (lane >> 5) + 0 .. 3.
+      if (PRED && fresh && lane < 16) ptab[(tile & 1) * 64 + wave * 16 + lane] = pv;
+      const int4* pt4 = reinterpret_cast<const int4*>(ptab + ((trow >> 6) & 1) * 64 + pair * 32 + 4 * (lane >> 5));
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const unsigned off = (unsigned)d_row(r, lane) * ldyb + cofs;
+        unsigned off = (unsigned)d_row(r, lane) * ldyb + cofs;
+        if (PRED) {
+          const int4 e = pt4[2 * (r >> 2)];
+          const int er = (r & 3) == 0 ? e.x : (r & 3) == 1 ? e.y : (r & 3) == 2 ? e.z : e.w;
+          off = er >= 0 ? off : kOOB;
+        }
         __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, acc[r] + bcol), ry, off, 0, STAUX);
       }
       GCL_STAMP(6);
@@ -939,7 +965,7 @@ extern "C" int gcl_debug_read_stamps(unsigned long long* host_out, int count) {
 static int halo_layer_launch(const gcl_graph_t* g, const float* x, int64_t ldx, int64_t bsx, const int32_t* tab,
                              int64_t x_rows, int32_t act, const float* slope, const float* W, const float* bias, float* y,
                              int64_t ldy, int64_t bsy, int32_t B, int32_t Fin, int32_t Fout, int32_t Fout_store,
-                             int32_t rows_out, hipStream_t st, bool* launched) {
+                             int32_t rows_out, hipStream_t st, bool* launched, const int32_t* present = nullptr) {
   *launched = false;
   const int32_t n = g->n;
   const int halo_on = gcl::env_int("GCL_GCN_HALO", 1);  // read per call: the parity test compares the two kernels
@@ -947,7 +973,7 @@ static int halo_layer_launch(const gcl_graph_t* g, const float* x, int64_t ldx, 
   const gcl_halo& hl = g->halo[0][0];
   const int hp4 = hl.T == 64 ? (int)gcl::cdiv((hl.smax - 64) / 4, 4) : 99;
   const int KPh = Fin + 2;
-  const size_t ldsh = (size_t)2 * (32 * KPh > 2048 ? 32 * KPh : 2048) * 4 + (size_t)(hl.smax + 1) * 256;
+  const size_t ldsh = (size_t)2 * (32 * KPh > 2048 ? 32 * KPh : 2048) * 4 + (size_t)(hl.smax + 1) * 256 + (present ? 512 : 0);
   // 32-bit byte offsets: inside one sample without a table, inside the whole of X with one
   const bool offs_ok = tab ? (x_rows * ldx * 4 < ((int64_t)1 << 32) && (int64_t)B * bsx * 4 < ((int64_t)1 << 32) && x_rows < (1 << 24))
                            : ((int64_t)n * ldx * 4 < ((int64_t)1 << 31));
@@ -959,6 +985,7 @@ static int halo_layer_launch(const gcl_graph_t* g, const float* x, int64_t ldx, 
         (int64_t)n * ldy * 4 < ((int64_t)1 << 31)))
     return GCL_OK;
   if (tab && hp4 > 4) return GCL_OK;  // the table variant exists for the interleaved-issue form only
+  if (present && (tab || hp4 > 4 || !gcl::env_int("GCL_GCN_HALO_FORM", 1))) return GCL_OK;  // so does the row predicate
   static const int bpc_env = gcl::env_int("GCL_GCN_HALO_BPC", 0);
   const int per_cu = (int)(gcl::kLdsBytes / ldsh);
   const int Jx = 32 * (bpc_env > 0 ? bpc_env : per_cu);
@@ -967,7 +994,7 @@ static int halo_layer_launch(const gcl_graph_t* g, const float* x, int64_t ldx, 
     GCL_ENSURE_DYN_LDS(kern, ldsh);
     hipLaunchKernelGGL(kern, grid, dim3(256), ldsh, st, hl.list, hl.cnt, reinterpret_cast<const int2*>(hl.rec), g->rowptr,
                        hl.opos, g->w, hl.smax, x, ldx, bsx, slope, W, bias, y, ldy, bsy, n, B, Fin, Fout, Fout_store,
-                       hl.ntiles, tab);
+                       hl.ntiles, tab, present);
     return GCL_OK;
   };
   int rc;
@@ -975,7 +1002,11 @@ static int halo_layer_launch(const gcl_graph_t* g, const float* x, int64_t ldx, 
   // the next item's DMA pieces issued between the k-steps of the dense part (in the step 111.5 -> 102.6 us per mesh
   // layer; GCL_GCN_HALO_FORM=0 selects the first form - DMA issue up front, staged 16-byte stores - for comparison)
   const int form_env = gcl::env_int("GCL_GCN_HALO_FORM", 1);
-  if (tab)
+  if (present)
+    rc = act == GCL_ACT_PRELU  ? go(&gcn_halo_fwd_kernel<gcl::kActPrelu, 4, 2, true, true, false, true>)
+         : act == GCL_ACT_SILU ? go(&gcn_halo_fwd_kernel<gcl::kActSilu, 4, 2, true, true, false, true>)
+                               : go(&gcn_halo_fwd_kernel<gcl::kActNone, 4, 2, true, true, false, true>);
+  else if (tab)
     rc = act == GCL_ACT_PRELU  ? go(&gcn_halo_fwd_kernel<gcl::kActPrelu, 4, 2, true, true, true>)
          : act == GCL_ACT_SILU ? go(&gcn_halo_fwd_kernel<gcl::kActSilu, 4, 2, true, true, true>)
                                : go(&gcn_halo_fwd_kernel<gcl::kActNone, 4, 2, true, true, true>);
@@ -1005,10 +1036,10 @@ extern "C" int gcl_gcn_layer_fwd(const gcl_graph_t* g, const float* x, int64_t l
                                 g ? g->n : 0, stream);
 }
 
-extern "C" int gcl_gcn_layer_fwd_rows(const gcl_graph_t* g, const float* x, int64_t ldx, int64_t bsx, int32_t act,
-                                      const float* slope, const float* W, const float* bias, float* y, int64_t ldy,
-                                      int64_t bsy, int32_t B, int32_t Fin, int32_t Fout, int32_t Fout_store,
-                                      int32_t rows_out, gcl_stream_t stream) {
+static int layer_fwd_impl(const gcl_graph_t* g, const float* x, int64_t ldx, int64_t bsx, int32_t act,
+                          const float* slope, const float* W, const float* bias, float* y, int64_t ldy, int64_t bsy,
+                          int32_t B, int32_t Fin, int32_t Fout, int32_t Fout_store, int32_t rows_out,
+                          const int32_t* present, gcl_stream_t stream) {
   GCL_CHECK_ARG(g && x && W && y, "gcn_layer_fwd: null argument");
   GCL_CHECK_ARG(g->kind == GCL_GRAPH_GCN || g->kind == GCL_GRAPH_MEAN, "gcn_layer_fwd: graph carries no edge weights");
   GCL_CHECK_ARG(B > 0 && Fin >= 4 && Fin <= 64 && Fin % 4 == 0 && Fout >= 1 && Fout <= 64,
@@ -1024,6 +1055,12 @@ extern "C" int gcl_gcn_layer_fwd_rows(const gcl_graph_t* g, const float* x, int6
   const int32_t n = g->n;
   GCL_CHECK_ARG(rows_out >= 1 && rows_out <= n, "gcn_layer_fwd: rows_out=%d outside [1, n=%d]", rows_out, n);
   hipStream_t st = (hipStream_t)stream;
+  if (present) {  // the form with the output-row predicate, where it exists; storing every row is always right too
+    bool launched = false;
+    const int rc = halo_layer_launch(g, x, ldx, bsx, nullptr, 0, act, slope, W, bias, y, ldy, bsy, B, Fin, Fout, Fout_store,
+                                     rows_out, st, &launched, present);
+    if (rc || launched) return rc;
+  }
   {
     bool launched = false;
     const int rc = halo_layer_launch(g, x, ldx, bsx, nullptr, 0, act, slope, W, bias, y, ldy, bsy, B, Fin, Fout, Fout_store,
@@ -1100,6 +1137,22 @@ extern "C" int gcl_gcn_layer_fwd_rows(const gcl_graph_t* g, const float* x, int6
 #undef GCL_GF5
   GCL_CHECK_LAUNCH();
   return GCL_OK;
+}
+
+extern "C" int gcl_gcn_layer_fwd_rows(const gcl_graph_t* g, const float* x, int64_t ldx, int64_t bsx, int32_t act,
+                                      const float* slope, const float* W, const float* bias, float* y, int64_t ldy,
+                                      int64_t bsy, int32_t B, int32_t Fin, int32_t Fout, int32_t Fout_store,
+                                      int32_t rows_out, gcl_stream_t stream) {
+  return layer_fwd_impl(g, x, ldx, bsx, act, slope, W, bias, y, ldy, bsy, B, Fin, Fout, Fout_store, rows_out, nullptr, stream);
+}
+
+extern "C" int gcl_gcn_layer_fwd_present(const gcl_graph_t* g, const float* x, int64_t ldx, int64_t bsx, int32_t act,
+                                         const float* slope, const float* W, const float* bias, float* y, int64_t ldy,
+                                         int64_t bsy, const int32_t* present, int32_t B, int32_t Fin, int32_t Fout,
+                                         int32_t Fout_store, gcl_stream_t stream) {
+  GCL_CHECK_ARG(present, "gcn_layer_fwd_present: null presence table");
+  return layer_fwd_impl(g, x, ldx, bsx, act, slope, W, bias, y, ldy, bsy, B, Fin, Fout, Fout_store, g ? g->n : 0, present,
+                        stream);
 }
 
 // The layer with its input rows read through a row table (gcn_halo_fwd_kernel<.., TAB>): row i of sample b is row

@@ -61,13 +61,18 @@ __device__ __forceinline__ void store4(float* p, int c0, int F, bool vec, float 
 // MAP: the output goes through a row map - row (b, i) of the [B][n_per] row space is written to
 // Y[b * bsy + pos[i] * ldy] when pos[i] >= 0 and not at all otherwise (a LayerNorm whose output is only consumed through a
 // row gather writes the gathered rows straight into the consumer's input: src/models.py:860-862 for the processor).
-template <int LPR, bool V, bool MAP = false>
+// LIST: only the rows of a list are normalised - item (b, u) of the [B][n_list] item space is row (b, rlist[u]) of the
+// [B][n_per] row space; a row that is not listed is neither read nor given statistics (a row whose output the map drops
+// has no reader left when the backward skips it too: gcl_layernorm_bwd_map_skip).  There is no sum across rows, so a
+// listed row gets the same bits whichever way the rows are enumerated.
+template <int LPR, bool V, bool MAP = false, bool LIST = false>
 __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ X, int64_t ldx,
                                                      const float* __restrict__ gamma, const float* __restrict__ beta,
                                                      float eps, float* __restrict__ Y, int64_t ldy,
                                                      float* __restrict__ stats, int64_t rows, int32_t F, int32_t vx,
                                                      int32_t vy, const int32_t* __restrict__ pos = nullptr,
-                                                     int64_t bsy = 0, int32_t n_per = 1) {
+                                                     int64_t bsy = 0, int32_t n_per = 1,
+                                                     const int32_t* __restrict__ rlist = nullptr, int32_t n_list = 1) {
   if (V) vx = vy = 1;
   constexpr int RPB = (64 / LPR) * 4;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -78,7 +83,29 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ X
     load4(gamma + c0, c0, F, false, g0, g1, g2, g3);
     load4(beta + c0, c0, F, false, b0, b1, b2, b3);
   }
-  for (int64_t row = (int64_t)blockIdx.x * RPB + wave * (64 / LPR) + sub; row < rows; row += (int64_t)gridDim.x * RPB) {
+  // LIST: (sample, list index) of this lane group's item, advanced with the grid stride (no division per row)
+  const int64_t item_first = (int64_t)blockIdx.x * RPB + wave * (64 / LPR) + sub, item_step = (int64_t)gridDim.x * RPB;
+  int64_t lb = 0, lsb = 0;
+  int li = 0, lsi = 0;
+  if (LIST) {
+    lb = item_first / n_list;
+    li = (int)(item_first - lb * n_list);
+    lsb = item_step / n_list;
+    lsi = (int)(item_step - lsb * n_list);
+  }
+  for (int64_t item = item_first; item < rows; item += item_step) {
+    int64_t row = item;  // LIST: `rows` counts items
+    int pl = 0;          // LIST: the row's map entry and sample (known without a second division)
+    int64_t lbq = 0;
+    if (LIST) {
+      const int r = rlist[li];
+      lbq = lb;
+      row = lb * n_per + r;
+      pl = pos[r];
+      li += lsi;
+      lb += lsb;
+      if (li >= n_list) { li -= n_list; ++lb; }
+    }
     float x0 = 0, x1 = 0, x2 = 0, x3 = 0;
     if (c0 < F) load4_row<V>(X + row * ldx + c0, c0, F, vx, x0, x1, x2, x3);
     const float mean = group_sum<LPR>(x0 + x1 + x2 + x3) * invF;
@@ -96,8 +123,8 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ X
     const float var = group_sum<LPR>(sq) * invF;
     const float rstd = 1.0f / sqrtf(var + eps);
     if (MAP) {
-      const int64_t bq = row / n_per;
-      const int pj = pos[(int)(row - bq * n_per)];
+      const int64_t bq = LIST ? lbq : row / n_per;
+      const int pj = LIST ? pl : pos[(int)(row - bq * n_per)];
       if (c0 < F && pj >= 0)
         store4(Y + bq * bsy + (int64_t)pj * ldy + c0, c0, F, vy, d0 * rstd * g0 + b0, d1 * rstd * g1 + b1,
                d2 * rstd * g2 + b2, d3 * rstd * g3 + b3);
@@ -116,7 +143,11 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ X
 // MAP: dY is given through a row map instead of densely - row (b, i) of the [B][n] row space reads
 // dY[b * bsdy + pos[i] * lddy] when pos[i] >= 0 and is zero otherwise (the gradient of a layer whose output was only
 // consumed through a row gather: no zero-filled dense gradient has to exist).
-template <int LPR, bool V, bool CS, bool MAP>
+// SKIP (with MAP): a row the map drops is not touched at all - no load of its x or statistics (they need not exist: see
+// ln_fwd_kernel LIST), no store of its dx (exactly zero; the consumer takes the zero from the map: gcl_aggregate_present).
+// Such a row adds exact zeros to every partial sum when it is computed, so leaving it out changes no sum; the rows keep
+// their places (row -> block, lane group, trip), so the partial sums add the same terms in the same order.
+template <int LPR, bool V, bool CS, bool MAP, bool SKIP = false>
 __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ dY, int64_t lddy,
                                                      const float* __restrict__ X, int64_t ldx,
                                                      const float* __restrict__ gamma, const float* __restrict__ stats,
@@ -148,7 +179,18 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ d
   }
   for (int64_t row = row_first; row < rows; row += row_step) {
     float x0 = 0, x1 = 0, x2 = 0, x3 = 0, y0 = 0, y1 = 0, y2 = 0, y3 = 0;
-    if (c0 < F) {
+    if (SKIP) {
+      const int pj = pos[mi];
+      const int64_t mb_row = mb;
+      mi += msi;
+      mb += msb;
+      if (mi >= n_per) { mi -= n_per; ++mb; }
+      if (pj < 0) continue;  // all lanes of the row's group together (the shuffles below stay inside a group)
+      if (c0 < F) {
+        load4_row<V>(X + row * ldx + c0, c0, F, vx, x0, x1, x2, x3);
+        load4_row<V>(dY + mb_row * bsdy + (int64_t)pj * lddy + c0, c0, F, vdy, y0, y1, y2, y3);
+      }
+    } else if (c0 < F) {
       load4_row<V>(X + row * ldx + c0, c0, F, vx, x0, x1, x2, x3);
       if (MAP) {
         // unmapped rows issue no load at all: this kernel is bound by its load INSTRUCTIONS (a wave-instruction serves
@@ -159,7 +201,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ d
         load4_row<V>(dY + row * lddy + c0, c0, F, vdy, y0, y1, y2, y3);
       }
     }
-    if (MAP) {
+    if (MAP && !SKIP) {
       mi += msi;
       mb += msb;
       if (mi >= n_per) { mi -= n_per; ++mb; }
@@ -310,6 +352,34 @@ extern "C" int gcl_layernorm_fwd_map(const float* x, int64_t ldx, const float* g
   return GCL_OK;
 }
 
+extern "C" int gcl_layernorm_fwd_map_skip(const float* x, int64_t ldx, const float* gamma, const float* beta, float eps,
+                                          float* y, int64_t ldy, int64_t bsy, const int32_t* pos, int32_t n_per,
+                                          const int32_t* rlist, int32_t n_list, float* stats, int64_t rows, int32_t F,
+                                          gcl_stream_t stream) {
+  GCL_CHECK_ARG(x && gamma && beta && y && pos && stats && rlist, "layernorm_fwd_map_skip: null argument");
+  GCL_CHECK_ARG(F >= 1 && F <= 256 && ldx >= F && ldy >= F, "layernorm_fwd_map_skip: bad shape F=%d", F);
+  GCL_CHECK_ARG(n_per > 0 && rows % n_per == 0, "layernorm_fwd_map_skip: rows must be B * n_per");
+  GCL_CHECK_ARG(n_list >= 0 && n_list <= n_per, "layernorm_fwd_map_skip: bad list length %d", n_list);
+  const int64_t items = rows / n_per * n_list;
+  if (items == 0) return GCL_OK;
+  const int lpr = lpr_for(F);
+  const int rpb = (64 / lpr) * 4;
+  int64_t nb = gcl::cdiv(items, rpb);
+  if (nb > 8192) nb = 8192;
+  const int vx = vec_ok(x, ldx, F), vy = vec_store_ok(y, ldy, F) && (bsy % 4 == 0);
+#define CALL(L)                                                                                                       \
+  if (vx && vy)                                                                                                       \
+    hipLaunchKernelGGL((ln_fwd_kernel<L, true, true, true>), dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, x, \
+                       ldx, gamma, beta, eps, y, ldy, stats, items, F, vx, vy, pos, bsy, n_per, rlist, n_list);       \
+  else                                                                                                                \
+    hipLaunchKernelGGL((ln_fwd_kernel<L, false, true, true>), dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream,  \
+                       x, ldx, gamma, beta, eps, y, ldy, stats, items, F, vx, vy, pos, bsy, n_per, rlist, n_list)
+  GCL_DISPATCH_LPR(lpr, CALL)
+#undef CALL
+  GCL_CHECK_LAUNCH();
+  return GCL_OK;
+}
+
 extern "C" size_t gcl_layernorm_bwd_ws_bytes(int64_t rows, int32_t F) {
   (void)rows;
   const size_t FP = (size_t)((F + 3) / 4) * 4;
@@ -324,10 +394,10 @@ extern "C" int gcl_layernorm_bwd_cs(const float* dy, int64_t lddy, const float* 
                                rows, F, ws, ws_bytes, stream);
 }
 
-extern "C" int gcl_layernorm_bwd_map(const float* dy, int64_t lddy, int64_t bsdy, const int32_t* pos, int32_t n_per,
-                                     const float* x, int64_t ldx, const float* gamma, const float* stats, float* dx,
-                                     int64_t lddx, float* dgamma, float* dbeta, float* colsum_dx, int32_t accumulate,
-                                     int64_t rows, int32_t F, void* ws, size_t ws_bytes, gcl_stream_t stream) {
+static int layernorm_bwd_impl(const float* dy, int64_t lddy, int64_t bsdy, const int32_t* pos, int32_t n_per,
+                              const float* x, int64_t ldx, const float* gamma, const float* stats, float* dx,
+                              int64_t lddx, float* dgamma, float* dbeta, float* colsum_dx, int32_t accumulate,
+                              int64_t rows, int32_t F, void* ws, size_t ws_bytes, gcl_stream_t stream, bool skip) {
   GCL_CHECK_ARG(dy && x && gamma && stats && dx && dgamma && dbeta, "layernorm_bwd: null argument");
   GCL_CHECK_ARG(!pos || (n_per > 0 && rows % n_per == 0), "layernorm_bwd: mapped dy needs rows = B * n_per");
   GCL_CHECK_ARG(F >= 1 && F <= 256 && ldx >= F && lddy >= F && lddx >= F, "layernorm_bwd: bad shape F=%d", F);
@@ -346,10 +416,13 @@ extern "C" int gcl_layernorm_bwd_map(const float* dy, int64_t lddy, int64_t bsdy
 #define CALL4(L, V_, CS_, MAP_)                                                                                       \
   hipLaunchKernelGGL((ln_bwd_kernel<L, V_, CS_, MAP_>), dim3((unsigned)nb), dim3(256), 0, st, dy, lddy, x, ldx, gamma, \
                      stats, dx, lddx, part, rows, F, FP, vdy, vx, vdx, pos, bsdy, n_per)
-#define CALL3(L, V_, CS_)            \
-  do {                               \
-    if (pos) CALL4(L, V_, CS_, true); \
-    else CALL4(L, V_, CS_, false);   \
+#define CALL3(L, V_, CS_)                                                                                              \
+  do {                                                                                                                 \
+    if (skip)                                                                                                          \
+      hipLaunchKernelGGL((ln_bwd_kernel<L, V_, CS_, true, true>), dim3((unsigned)nb), dim3(256), 0, st, dy, lddy, x, ldx, \
+                         gamma, stats, dx, lddx, part, rows, F, FP, vdy, vx, vdx, pos, bsdy, n_per);                   \
+    else if (pos) CALL4(L, V_, CS_, true);                                                                             \
+    else CALL4(L, V_, CS_, false);                                                                                     \
   } while (0)
 #define CALL(L)                                     \
   if (vdy && vx && vdx) {                           \
@@ -366,6 +439,24 @@ extern "C" int gcl_layernorm_bwd_map(const float* dy, int64_t lddy, int64_t bsdy
   GCL_CHECK_LAUNCH();
   if (!colsum_dx) return gcl::launch_reduce_parts2(part, (int)nb, 2 * FP, FP, FP, dgamma, dbeta, F, acc_p, st);
   return gcl::launch_reduce_parts3(part, (int)nb, 3 * FP, FP, dgamma, acc_p, dbeta, acc_p, colsum_dx, acc_cs, F, st);
+}
+
+extern "C" int gcl_layernorm_bwd_map(const float* dy, int64_t lddy, int64_t bsdy, const int32_t* pos, int32_t n_per,
+                                     const float* x, int64_t ldx, const float* gamma, const float* stats, float* dx,
+                                     int64_t lddx, float* dgamma, float* dbeta, float* colsum_dx, int32_t accumulate,
+                                     int64_t rows, int32_t F, void* ws, size_t ws_bytes, gcl_stream_t stream) {
+  return layernorm_bwd_impl(dy, lddy, bsdy, pos, n_per, x, ldx, gamma, stats, dx, lddx, dgamma, dbeta, colsum_dx, accumulate,
+                            rows, F, ws, ws_bytes, stream, false);
+}
+
+extern "C" int gcl_layernorm_bwd_map_skip(const float* dy, int64_t lddy, int64_t bsdy, const int32_t* pos, int32_t n_per,
+                                          const float* x, int64_t ldx, const float* gamma, const float* stats, float* dx,
+                                          int64_t lddx, float* dgamma, float* dbeta, float* colsum_dx,
+                                          int32_t accumulate, int64_t rows, int32_t F, void* ws, size_t ws_bytes,
+                                          gcl_stream_t stream) {
+  GCL_CHECK_ARG(pos, "layernorm_bwd_map_skip: the row map is required");
+  return layernorm_bwd_impl(dy, lddy, bsdy, pos, n_per, x, ldx, gamma, stats, dx, lddx, dgamma, dbeta, colsum_dx, accumulate,
+                            rows, F, ws, ws_bytes, stream, true);
 }
 
 extern "C" int gcl_layernorm_bwd(const float* dy, int64_t lddy, const float* x, int64_t ldx, const float* gamma,

@@ -126,6 +126,12 @@ _LN_COLSUM = os.environ.get("GCL_NO_LN_COLSUM", "0") in ("0", "")
 _ROWS_OUT = os.environ.get("GCL_NO_ROWS_OUT", "0") in ("0", "")
 
 
+def _row_skip() -> bool:
+    """Rows that a stage boundary drops are neither written nor read (GCL_NO_ROW_SKIP=1: today's dense launches).  Read
+    per call, so a test can compare the two."""
+    return os.environ.get("GCL_NO_ROW_SKIP", "0") in ("0", "")
+
+
 def _lat_first_layer_bwd(lat, enc3, dz3, W, dW, acc_dw: bool, want_dx: bool, Pc=None, enc_shape=None):
     """Dense backward of a first processor layer whose input was read through a LatSource: dz3 [B, M, D'] is the
     gradient of the layer's transformed mesh rows (GCN: A^T dp, GAT: dh).  Returns the gradient of the encoder output
@@ -221,6 +227,19 @@ class GCNStackFn(torch.autograd.Function):
         ps = []  # pre-activation outputs of every conv
         cur = x3
         pad_last = None
+        # The stack's LayerNorm writes only the rows the decoder-input gather takes (GradLanding.dec_buf) and nothing else
+        # sees its output: the other rows of the last conv's output, of the statistics and of the LayerNorm's dx have no
+        # reader that needs them, so they are neither stored nor loaded - the last conv stores only present rows, the
+        # LayerNorm pair skips the rest, and the transposed aggregation takes their (zero) gradient from the table.
+        # Taken only when every reader of those tensors honours the table: the LayerNorm backward emits the bias
+        # gradient's column sums itself (_LN_COLSUM), 16-byte rows, and rows are actually dropped.
+        land0 = getattr(owner, "_grad_src", None)
+        F_last = params[2 * (L - 1)].shape[0]
+        skip = None
+        if (has_ln and land0 is not None and land0.dec_buf is not None and getattr(land0, "dec_rows", None) is not None
+                and not (out_rows and out_rows < n) and not squeeze and _LN_COLSUM and F_last % 4 == 0
+                and land0.dec_buf.shape[2] == F_last and land0.dec_rows.numel() < n and _row_skip()):
+            skip = (land0.dec_map, land0.dec_rows)
         for k in range(L):
             W, b = params[2 * k].detach(), params[2 * k + 1].detach()
             Fout = W.shape[0]
@@ -239,7 +258,8 @@ class GCNStackFn(torch.autograd.Function):
                 # with zero padding columns, so the layer and its backward stay on 16-byte rows
                 # the last conv of a stack whose caller keeps only the first rows (decoder: grid rows) computes only those
                 last_rows = int(out_rows) if (k == L - 1 and out_rows and out_rows < n and not has_ln and _ROWS_OUT) else None
-                p = hip.gcn_layer_fwd(graph, cur, act_k, slope_k, W, b, rows_out=last_rows)
+                p = hip.gcn_layer_fwd(graph, cur, act_k, slope_k, W, b, rows_out=last_rows,
+                                      present=skip[0] if (skip is not None and k == L - 1) else None)
                 if k == L - 1 and ldh != Fout and not has_ln:
                     pad_last = (ldh, Fout, None)
                 elif ldh != Fout:
@@ -277,13 +297,19 @@ class GCNStackFn(torch.autograd.Function):
             if land is not None and land.dec_buf is not None and cur.is_contiguous() and land.dec_buf.shape[2] == cur.shape[2]:
                 # the output is only consumed by the decoder-input gather: the rows it takes are written straight into
                 # the decoder's input, the others not at all (GradLanding.dec_buf); autograd sees a stride-0 token
-                stats = hip.layernorm_fwd_map(cur.view(B * n, -1), params[-2].detach(), params[-1].detach(), eps,
-                                              land.dec_buf, land.dec_map)
+                if skip is not None:
+                    stats = hip.layernorm_fwd_map_skip(cur.view(B * n, -1), params[-2].detach(), params[-1].detach(), eps,
+                                                       land.dec_buf, skip[0], skip[1])
+                else:
+                    stats = hip.layernorm_fwd_map(cur.view(B * n, -1), params[-2].detach(), params[-1].detach(), eps,
+                                                  land.dec_buf, land.dec_map)
                 land.dec_filled = True
                 out = cur.new_zeros(()).expand(B, n, cur.shape[2])
             else:
+                assert skip is None, "rows were skipped upstream of a dense LayerNorm"
                 o2, stats = hip.layernorm_fwd(cur.view(B * n, -1), params[-2].detach(), params[-1].detach(), eps)
                 out = o2.view(B, n, -1)
+        ctx.skip = skip
         ctx.owner, ctx.graph, ctx.L, ctx.has_ln = owner, graph, L, has_ln
         ctx.x3, ctx.ps, ctx.stats, ctx.params, ctx.squeeze = x3, ps, stats, params, squeeze
         ctx.n_rows, ctx.out_rows = n, (int(out_rows) if out_rows and out_rows < n else 0)
@@ -328,9 +354,13 @@ class GCNStackFn(torch.autograd.Function):
             dbet = G.dst[bi] if G.dst[bi] is not None else torch.zeros_like(params[bi])
             # the LayerNorm backward also sums its dx over the rows: that IS the bias gradient of the last conv
             cs = G.dst[bi_last] if (pad is None and _LN_COLSUM) else None
+            if ctx.skip is not None and dy_map is None:
+                raise RuntimeError("the processor's output received a gradient from outside the decoder-input gather, but its "
+                                   "dropped rows were not kept (set GCL_NO_ROW_SKIP=1 to keep them)")
             dp = hip.layernorm_bwd(None if dy_map is not None else dy3.view(B * n, -1), ps[-1].view(B * n, -1),
                                    params[gi].detach(), ctx.stats, dgam, dbet, G.acc[gi] and G.acc[bi], colsum_dx=cs,
-                                   acc_colsum=bool(cs is not None and G.acc[bi_last]), dy_map=dy_map).view(B, n, -1)
+                                   acc_colsum=bool(cs is not None and G.acc[bi_last]), dy_map=dy_map,
+                                   skip=ctx.skip is not None).view(B, n, -1)
             cs_done = cs is not None
         else:
             dp = dy3
@@ -353,7 +383,11 @@ class GCNStackFn(torch.autograd.Function):
             W = params[2 * k].detach()
             wi = 2 * k
             inp = (ctx.x3 if k == 0 else ps[k - 1]).view(-1, (ctx.x3 if k == 0 else ps[k - 1]).shape[-1])
-            dh2 = hip.aggregate(graph, dp, None, transpose=True).view(B * n, -1)
+            if k == L - 1 and ctx.skip is not None:
+                # the dropped rows of dp were not written: their zeros come from the table
+                dh2 = hip.aggregate_present(graph, dp, ctx.skip[0], transpose=True).view(B * n, -1)
+            else:
+                dh2 = hip.aggregate(graph, dp, None, transpose=True).view(B * n, -1)
             if k == L - 1 and Fp != Fo:
                 dh2 = dh2[:, :Fo]  # [rows, Fout] view with row stride Fp
             dW = G.dst[wi] if G.dst[wi] is not None else torch.zeros_like(params[wi])
@@ -695,7 +729,9 @@ class GradLanding:
         # third channel (forward): the decoder-input buffer [B, head + U, D], allocated by the model before the processor
         # runs, and the map mesh row -> row of that buffer (or -1).  The processor's final LayerNorm writes the rows
         # the decoder reads straight into it (gcl_layernorm_fwd_map) and the gather then only copies the head rows.
+        # dec_rows: the mesh rows with dec_map >= 0 as a list (the rows of the processor's output that have a reader)
         self.dec_buf, self.dec_map, self.dec_filled = None, None, False
+        self.dec_rows = None
 
 
 class MeshLatFn(torch.autograd.Function):

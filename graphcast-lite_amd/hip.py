@@ -44,6 +44,7 @@ _SIGNATURES = {
     "gcl_reduce_jobs": (C.c_int, [_vp, _i32, _vp]),
     "gcl_linear_bwd_all_ws_bytes": (_sz, [_i64, _i32, _i32]),
     "gcl_aggregate": (C.c_int, [_vp, _i32, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i32, _i32, _vp]),
+    "gcl_aggregate_present": (C.c_int, [_vp, _i32, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _vp]),
     "gcl_gat_fwd": (C.c_int, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _vp]),
     "gcl_gat_bwd": (C.c_int, [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64,
                               _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _sz, _vp]),
@@ -60,6 +61,10 @@ _SIGNATURES = {
     "gcl_layernorm_bwd_cs": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _i64, _i32, _vp, _sz, _vp]),
     "gcl_layernorm_bwd_map": (C.c_int, [_vp, _i64, _i64, _vp, _i32, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _i64,
                                         _i32, _vp, _sz, _vp]),
+    "gcl_layernorm_fwd_map_skip": (C.c_int, [_vp, _i64, _vp, _vp, _f32, _vp, _i64, _i64, _vp, _i32, _vp, _i32, _vp, _i64, _i32,
+                                             _vp]),
+    "gcl_layernorm_bwd_map_skip": (C.c_int, [_vp, _i64, _i64, _vp, _i32, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i32,
+                                             _i64, _i32, _vp, _sz, _vp]),
     "gcl_layernorm_bwd_ws_bytes": (_sz, [_i64, _i32]),
     "gcl_graphnorm_fwd": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _f32, _vp, _i64, _i64, _vp, _i32, _i32, _i32, _vp, _sz, _vp]),
     "gcl_graphnorm_bwd": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _f32, _vp, _i64, _i64, _vp, _vp,
@@ -87,6 +92,8 @@ _SIGNATURES = {
                                    C.c_size_t, _vp]),
     "gcl_gcn_layer_fwd": (C.c_int, [_vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp]),
     "gcl_gcn_layer_fwd_rows": (C.c_int, [_vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "gcl_gcn_layer_fwd_present": (C.c_int, [_vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _i32, _i32, _i32, _i32,
+                                            _vp]),
     "gcl_layernorm_fwd_map": (C.c_int, [_vp, _i64, _vp, _vp, _f32, _vp, _i64, _i64, _vp, _i32, _vp, _i64, _i32, _vp]),
     "gcl_gcn_layer_fwd_tab": (C.c_int, [_vp, _vp, _i64, _i64, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp]),
     "gcl_gcn_layer_fwd_tab_ok": (C.c_int, [_vp, _i64, _i64, _i64, _i32, _i32, _i32]),
@@ -515,6 +522,21 @@ def aggregate(graph: Graph, h3, bias, transpose=False, out=None):
     return out
 
 
+def aggregate_present(graph: Graph, h3, present, bias=None, transpose=False, out=None):
+    """hip.aggregate with absent source rows: present int32 [n], entry < 0 = that row of h3 counts as zeros and is never
+    read (it may be uninitialised memory).  Reported to the launch probe under a kind of its own."""
+    B, n, F = h3.shape
+    assert n == graph.n, f"graph has {graph.n} nodes, features have {n} rows"
+    assert h3.stride(2) == 1 and present.dtype == torch.int32 and present.numel() == n and present.is_contiguous()
+    if out is None:
+        out = torch.empty(B, n, F, dtype=torch.float32, device=h3.device)
+    tok = _probe_begin("aggregate_present", graph=graph, transpose=bool(transpose), B=B, F=F)
+    _check(lib().gcl_aggregate_present(graph.handle, 1 if transpose else 0, _p(h3), h3.stride(1), h3.stride(0),
+                                       _pi(present), _p(bias), _p(out), out.stride(1), out.stride(0), B, F, _stream()))
+    _probe_end(tok)
+    return out
+
+
 def layernorm_fwd(x, gamma, beta, eps=1e-5):
     rows, F = x.shape
     y = torch.empty(rows, F, dtype=torch.float32, device=x.device)
@@ -535,8 +557,21 @@ def layernorm_fwd_map(x, gamma, beta, eps, out3, pos):
     return stats
 
 
+def layernorm_fwd_map_skip(x, gamma, beta, eps, out3, pos, rlist):
+    """layernorm_fwd_map for a LayerNorm whose dropped rows nobody reads: rlist int32 = the rows i with pos[i] >= 0.  Only
+    those rows of x are read; the statistics of the others are uninitialised (layernorm_bwd(..., skip=True) ignores them)."""
+    rows, F = x.shape
+    n_per = pos.numel()
+    assert out3.stride(2) == 1 and rows % n_per == 0 and out3.shape[0] == rows // n_per and rlist.stride(0) == 1
+    stats = torch.empty(rows, 2, dtype=torch.float32, device=x.device)
+    _check(lib().gcl_layernorm_fwd_map_skip(_p(x), _ld(x), _p(gamma), _p(beta), float(eps), _p(out3), out3.stride(1),
+                                            out3.stride(0), _pi(pos), n_per, _pi(rlist), rlist.numel(), _p(stats), rows, F,
+                                            _stream()))
+    return stats
+
+
 def layernorm_bwd(dy, x, gamma, stats, dgamma, dbeta, accumulate: bool, colsum_dx=None, acc_colsum: bool = False,
-                  dy_map=None):
+                  dy_map=None, skip: bool = False):
     """dx of the node LayerNorm (+ dgamma, dbeta); `colsum_dx` also receives the column sums of dx (the bias
     gradient of the layer below) from the same pass.  dy_map = (src3 [B, m, F'], pos int32 [n]): dy is not dense -
     row (b, i) reads src3[b, pos[i], :F] (zero where pos[i] < 0); x then holds B * n rows."""
@@ -548,10 +583,13 @@ def layernorm_bwd(dy, x, gamma, stats, dgamma, dbeta, accumulate: bool, colsum_d
     if dy_map is not None:
         src3, pos = dy_map
         assert src3.stride(2) == 1 and src3.shape[2] >= F and rows % pos.numel() == 0 and src3.shape[0] == rows // pos.numel()
-        _check(lib().gcl_layernorm_bwd_map(_p(src3), src3.stride(1), src3.stride(0), _pi(pos), pos.numel(), _p(x), _ld(x),
+        # skip: rows with pos < 0 are not touched - their x / statistics are not read, their dx (zero) is not written
+        fn = lib().gcl_layernorm_bwd_map_skip if skip else lib().gcl_layernorm_bwd_map
+        _check(fn(_p(src3), src3.stride(1), src3.stride(0), _pi(pos), pos.numel(), _p(x), _ld(x),
                                            _p(gamma), _p(stats), _p(dx), F, _p(dgamma), _p(dbeta), _p(colsum_dx), acc, rows, F,
                                            ws.data_ptr(), ws.numel(), _stream()))
         return dx
+    assert not skip, "skip needs the mapped gradient"
     _check(lib().gcl_layernorm_bwd_cs(_p(dy), _ld(dy), _p(x), _ld(x), _p(gamma), _p(stats), _p(dx), F, _p(dgamma),
                                       _p(dbeta), _p(colsum_dx), acc, rows, F, ws.data_ptr(), ws.numel(), _stream()))
     return dx
@@ -941,10 +979,11 @@ def gcn_layer_fusable(graph: Graph, x3, Fin: int, Fout: int) -> bool:
             and x3.stride(2) == 1 and x3.stride(1) % 4 == 0 and x3.stride(0) % 4 == 0 and x3.data_ptr() % 16 == 0)
 
 
-def gcn_layer_fwd(graph: Graph, x3, act, slope, W, bias, out=None, rows_out=None):
+def gcn_layer_fwd(graph: Graph, x3, act, slope, W, bias, out=None, rows_out=None, present=None):
     """y = (A_hat act(x)) W^T + bias for x3 [B, n, Fin] -> [B, n, Fout] (one kernel).  The result is a view of
     a [B, n, roundup(Fout, 4)] buffer whose padding columns are zero.  rows_out: only the first rows_out rows of every
-    sample are computed (the others stay unwritten)."""
+    sample are computed (the others stay unwritten).  present int32 [n]: rows with a negative entry may stay unwritten
+    too (gcl_gcn_layer_fwd_present; reported to the launch probe under a kind of its own)."""
     B, n, Fin = x3.shape
     assert n == graph.n
     Fout = W.shape[0]
@@ -952,6 +991,14 @@ def gcn_layer_fwd(graph: Graph, x3, act, slope, W, bias, out=None, rows_out=None
     if out is None:
         out = torch.empty(B, n, Fst, dtype=torch.float32, device=x3.device)
     assert out.shape[2] >= Fst or out.stride(1) >= Fst
+    if present is not None:
+        assert not rows_out and present.numel() == n
+        tok = _probe_begin("gcn_layer_fwd_present", graph=graph, B=B, Fin=Fin, Fout=Fout)
+        _check(lib().gcl_gcn_layer_fwd_present(graph.handle, _p(x3), x3.stride(1), x3.stride(0), int(act), _p(slope),
+                                               _p(W.contiguous()), _p(bias), _p(out), out.stride(1), out.stride(0),
+                                               _pi(present), B, Fin, Fout, Fst, _stream()))
+        _probe_end(tok)
+        return out[..., :Fout]
     tok = _probe_begin("gcn_layer_fwd", graph=graph, B=B, Fin=Fin, Fout=Fout)
     _check(lib().gcl_gcn_layer_fwd_rows(graph.handle, _p(x3), x3.stride(1), x3.stride(0), int(act), _p(slope),
                                         _p(W.contiguous()), _p(bias), _p(out), out.stride(1), out.stride(0), B, Fin, Fout,

@@ -838,6 +838,7 @@ class WeatherPrediction(nn.Module):
                 # rows the decoder reads straight into the decoder's input (functional.GradLanding.dec_buf)
                 land.dec_buf = torch.empty(B, G + c.U, enc_c.shape[-1], dtype=torch.float32, device=enc_c.device)
                 land.dec_map = maps_dec[3]
+                land.dec_rows = maps_dec[1][G:]  # the U mesh rows the decoder reads (a view of the set-up's device table)
             if lat_src is not None:
                 # the first GCNConv reads the mesh latents THROUGH the row table from the encoder output: they are never
                 # materialised, and its backward works on the compact rows (functional.GCNStackFn, LatSource)

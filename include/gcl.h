@@ -190,6 +190,12 @@ int gcl_dense_bwd_dw(const float* dy, int64_t lddy, const float* x, int64_t ldx,
 int gcl_aggregate(const gcl_graph_t* g, int32_t transpose, const float* h, int64_t ldh, int64_t bsh,
                   const float* bias, float* y, int64_t ldy, int64_t bsy, int32_t B, int32_t F,
                   gcl_stream_t stream);
+/* The same with ABSENT source rows: present [n] has one entry per node, >= 0 = the row of h exists, < 0 = it counts as a
+ * row of zeros and is never read, whatever the memory behind it holds (a stage boundary that drops rows: the producer of
+ * h need not store them).  Bit-equal to gcl_aggregate on a copy of h whose absent rows are zero. */
+int gcl_aggregate_present(const gcl_graph_t* g, int32_t transpose, const float* h, int64_t ldh, int64_t bsh,
+                          const int32_t* present /*[n]*/, const float* bias, float* y, int64_t ldy, int64_t bsy,
+                          int32_t B, int32_t F, gcl_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * GATConv(heads=H, concat=False) attention + aggregation  (src/models.py:425; SparseGATConv :135)
@@ -277,6 +283,20 @@ int gcl_layernorm_bwd_map(const float* dy, int64_t lddy, int64_t bsdy, const int
                           const float* x, int64_t ldx, const float* gamma, const float* stats, float* dx,
                           int64_t lddx, float* dgamma, float* dbeta, float* colsum_dx, int32_t accumulate,
                           int64_t rows, int32_t F, void* ws, size_t ws_bytes, gcl_stream_t stream);
+/* The mapped pair for a LayerNorm whose dropped rows (pos[i] < 0) have no reader at all: such a row is neither loaded nor
+ * stored by either call.  Forward: rlist [n_list] lists the rows i with pos[i] >= 0; only those rows of every sample are
+ * read, normalised, written through the map and given statistics (the same bits as gcl_layernorm_fwd_map gives them); the
+ * statistics of the other rows are left as they were.  Backward: x, the statistics and dx of a dropped row are not
+ * touched (its dx is exactly zero - the consumer takes the zero from the map, see gcl_aggregate_present); dx of the kept
+ * rows, dgamma, dbeta and colsum_dx are bit-equal to gcl_layernorm_bwd_map on the same rows. */
+int gcl_layernorm_fwd_map_skip(const float* x, int64_t ldx, const float* gamma, const float* beta, float eps, float* y,
+                               int64_t ldy, int64_t bsy, const int32_t* pos /*[n_per]*/, int32_t n_per,
+                               const int32_t* rlist /*[n_list]*/, int32_t n_list, float* stats, int64_t rows, int32_t F,
+                               gcl_stream_t stream);
+int gcl_layernorm_bwd_map_skip(const float* dy, int64_t lddy, int64_t bsdy, const int32_t* pos, int32_t n_per,
+                               const float* x, int64_t ldx, const float* gamma, const float* stats, float* dx,
+                               int64_t lddx, float* dgamma, float* dbeta, float* colsum_dx, int32_t accumulate,
+                               int64_t rows, int32_t F, void* ws, size_t ws_bytes, gcl_stream_t stream);
 size_t gcl_layernorm_bwd_ws_bytes(int64_t rows, int32_t F);
 /* PyG LayerNorm(mode="graph"): statistics over all n*F elements of each sample, eps added to the
  * std.  stats [B,2] = (mean, 1/(std+eps)). */
@@ -373,6 +393,13 @@ int gcl_gcn_layer_fwd_rows(const gcl_graph_t* g, const float* x, int64_t ldx, in
                            const float* slope, const float* W /*[Fout,Fin]*/, const float* bias, float* y,
                            int64_t ldy, int64_t bsy, int32_t B, int32_t Fin, int32_t Fout, int32_t Fout_store,
                            int32_t rows_out, gcl_stream_t stream);
+/* The layer with an OUTPUT-ROW predicate: rows i with present[i] < 0 may be left unwritten (a stage boundary behind the
+ * layer drops them); rows with present[i] >= 0 get the bits gcl_gcn_layer_fwd gives them.  The source-tile form of the
+ * layer folds the table into its stores; every other form stores all rows, which honours the same contract. */
+int gcl_gcn_layer_fwd_present(const gcl_graph_t* g, const float* x, int64_t ldx, int64_t bsx, int32_t act,
+                              const float* slope, const float* W, const float* bias, float* y, int64_t ldy, int64_t bsy,
+                              const int32_t* present /*[n]*/, int32_t B, int32_t Fin, int32_t Fout, int32_t Fout_store,
+                              gcl_stream_t stream);
 /* Same layer with its input rows read THROUGH a row table instead of from a materialised [B, n, Fin] tensor (the
  * stage split of src/models.py:837-838 - `mesh_node_features = encoded[..., G:, :]` - folded into the first processor
  * layer's loads): input row i of sample b is row tab[i] of sample b of x when tab[i] >= 0, and row ~tab[i] of x viewed
