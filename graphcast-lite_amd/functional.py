@@ -43,6 +43,10 @@ class _Grads:
         return tuple(None if r else d for d, r in zip(self.dst, self.ret_none))
 
 
+def _token(like: torch.Tensor, shape):  # a stride-0 zero: stands in autograd's graph for rows that travel through a GradLanding
+    return like.new_zeros(()).expand(shape)
+
+
 def _flat3(x: torch.Tensor):
     """[B,n,F] (or [n,F]) -> contiguous [B,n,F]."""
     if x.dim() == 2:
@@ -132,6 +136,15 @@ def _row_skip() -> bool:
     return os.environ.get("GCL_NO_ROW_SKIP", "0") in ("0", "")
 
 
+def _fold_sum(g3, inv_fold, r: int, B: int, dst):
+    """The batch sums of g3's folded rows (MeshLatFn: inv_fold) land r to a sample in dst [B, r, F]."""
+    if r > 1:
+        hip.gather2_rows(g3, inv_fold, None, None, B * r, B, sum_batch=True, out=dst, deal=r)
+    elif r == 1:
+        tmp = hip.gather2_rows(g3, inv_fold, None, None, B * r, B, sum_batch=True)
+        hip.copy_rows(tmp.view(B, r, g3.shape[-1]), dst)
+
+
 def _lat_first_layer_bwd(lat, enc3, dz3, W, dW, acc_dw: bool, want_dx: bool, Pc=None, enc_shape=None):
     """Dense backward of a first processor layer whose input was read through a LatSource: dz3 [B, M, D'] is the
     gradient of the layer's transformed mesh rows (GCN: A^T dp, GAT: dh).  Returns the gradient of the encoder output
@@ -147,31 +160,21 @@ def _lat_first_layer_bwd(lat, enc3, dz3, W, dW, acc_dw: bool, want_dx: bool, Pc=
     dzc = torch.empty(B, nc, Fo, dtype=torch.float32, device=dz3.device)
     if Md > 0:
         hip.gather2_rows(dz3, inv_a[G: G + Md], None, None, Md, B, out=dzc[:, :Md])
-    if r > 1:
-        hip.gather2_rows(dz3, inv_fold, None, None, B * r, B, sum_batch=True, out=dzc[:, Md:], deal=r)
-    elif r == 1:
-        tmp = hip.gather2_rows(dz3, inv_fold, None, None, B * r, B, sum_batch=True)
-        hip.copy_rows(tmp.view(B, r, Fo), dzc[:, Md:])
+    _fold_sum(dz3, inv_fold, r, B, dzc[:, Md:])
     if Pc is None:  # the encoder rows behind the mesh latents
         Pc = hip.copy_rows(enc3[:, G:, :], torch.empty(B, nc, D, dtype=torch.float32, device=dz3.device))
-    land = lat.landing
-    shared = land is not None and land.buf is not None
     if not want_dx:
         hip.linear_bwd_dw(dzc.view(B * nc, Fo), Pc.view(B * nc, D), None, dW, None, acc_dw)
         dxc = None
     else:
         dxc = hip.linear_bwd_all(dzc.view(B * nc, Fo), W, Pc.view(B * nc, D), None, None, dW, None, None, acc_dw,
                                  act=hip.ACT_NONE).view(B, nc, D)
-    if shared:
-        if dxc is not None:
-            hip.copy_rows(dxc, land.buf[:, G:])  # head rows: written by the decoder-input gather's backward
-        land.buf, land.mesh_pending, land.handed_over = None, False, False
-        return None
+    buf, _ = GradLanding.tail(lat.landing)
     if dxc is None:
         return None
-    out = torch.zeros(B, ne, D, dtype=torch.float32, device=dz3.device)
-    hip.copy_rows(dxc, out[:, G:])
-    return out
+    out = buf if buf is not None else torch.zeros(B, ne, D, dtype=torch.float32, device=dz3.device)
+    hip.copy_rows(dxc, out[:, G:])  # (shared buffer: the head rows were written by the decoder-input gather's backward)
+    return None if buf is not None else out
 
 
 class LatSource:
@@ -203,21 +206,19 @@ class LatSource:
 
 class GCNStackFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, owner, graph, L: int, has_ln: bool, eps: float, out_rows: int, *params):
-        """out_rows > 0: only the first `out_rows` rows are returned (the decoder keeps the grid rows,
+    def forward(ctx, x, owner, graph, L: int, has_ln: bool, eps: float, out_rows: int, land, lat, *params):
+        """land: GradLanding or None.  lat: LatSource or None (x is then the encoder output).
+        out_rows > 0: only the first `out_rows` rows are returned (the decoder keeps the grid rows,
         src/models.py:870-872); the slice is part of this Function so that its backward receives the gradient of
         the slice and widens it with ONE pass of gcl_pad_rows (no zero-fill + copy by autograd)."""
         squeeze = x.dim() == 2
         x3 = _flat3(x.detach())
         B, n, _ = x3.shape
-        lat = getattr(owner, "_lat_src", None)
         if lat is not None:
-            owner._lat_src = None
             n = lat.M  # x is the encoder output [B, ne, D]; the stack runs on the M mesh rows it is read into
             if not x3.is_contiguous():
                 x3 = x3.contiguous()
-            if lat.landing is not None:
-                lat.landing.mesh_pending = True  # this Function's backward fills the tail rows of the shared buffer (as MeshLatFn)
+            GradLanding.expect_tail(lat.landing)  # this Function's backward fills the shared buffer's tail rows (as MeshLatFn)
         ctx.lat = lat
         slope_p = params[2 * L]
         # activation between the convs: learnable PReLU slope (params[2L]), SiLU, or ReLU as a PReLU
@@ -227,19 +228,20 @@ class GCNStackFn(torch.autograd.Function):
         ps = []  # pre-activation outputs of every conv
         cur = x3
         pad_last = None
-        # The stack's LayerNorm writes only the rows the decoder-input gather takes (GradLanding.dec_buf) and nothing else
-        # sees its output: the other rows of the last conv's output, of the statistics and of the LayerNorm's dx have no
-        # reader that needs them, so they are neither stored nor loaded - the last conv stores only present rows, the
-        # LayerNorm pair skips the rest, and the transposed aggregation takes their (zero) gradient from the table.
-        # Taken only when every reader of those tensors honours the table: the LayerNorm backward emits the bias
-        # gradient's column sums itself (_LN_COLSUM), 16-byte rows, and rows are actually dropped.
-        land0 = getattr(owner, "_grad_src", None)
+        # The landing serves a stack whose whole LayerNorm output goes to the decoder-input gather.  Where that output goes
+        # is decided here, once, because the last conv needs the answer too: dense, through the row map into the decoder's
+        # input (`mapped`), or mapped with the rows that have no reader neither stored nor loaded (`present`: the last conv
+        # stores only present rows, the LayerNorm pair skips the rest, and the transposed aggregation takes their zero
+        # gradient from the table).  Rows are skipped only when every reader of those tensors honours the table: the
+        # LayerNorm backward emits the bias gradient's column sums itself (_LN_COLSUM) and rows are whole 16-byte units.  (The
+        # LayerNorm's input is contiguous on every branch of the loop below: odd widths are copied dense.)
+        if not (has_ln and not (out_rows and out_rows < n) and not squeeze):
+            land = None
         F_last = params[2 * (L - 1)].shape[0]
-        skip = None
-        if (has_ln and land0 is not None and land0.dec_buf is not None and getattr(land0, "dec_rows", None) is not None
-                and not (out_rows and out_rows < n) and not squeeze and _LN_COLSUM and F_last % 4 == 0
-                and land0.dec_buf.shape[2] == F_last and land0.dec_rows.numel() < n and _row_skip()):
-            skip = (land0.dec_map, land0.dec_rows)
+        mapped, present = False, None
+        if land is not None:
+            land.expect_mapped_reader()
+            mapped, present = land.ln_plan(n, F_last, _LN_COLSUM and F_last % 4 == 0 and _row_skip())
         for k in range(L):
             W, b = params[2 * k].detach(), params[2 * k + 1].detach()
             Fout = W.shape[0]
@@ -259,7 +261,7 @@ class GCNStackFn(torch.autograd.Function):
                 # the last conv of a stack whose caller keeps only the first rows (decoder: grid rows) computes only those
                 last_rows = int(out_rows) if (k == L - 1 and out_rows and out_rows < n and not has_ln and _ROWS_OUT) else None
                 p = hip.gcn_layer_fwd(graph, cur, act_k, slope_k, W, b, rows_out=last_rows,
-                                      present=skip[0] if (skip is not None and k == L - 1) else None)
+                                      present=present if k == L - 1 else None)
                 if k == L - 1 and ldh != Fout and not has_ln:
                     pad_last = (ldh, Fout, None)
                 elif ldh != Fout:
@@ -285,31 +287,14 @@ class GCNStackFn(torch.autograd.Function):
             cur = p
         ctx.akind, ctx.slope_t, ctx.pad_last = akind, slope_t, pad_last
         out, stats = cur, None
-        ctx.land = getattr(owner, "_grad_src", None)
-        if ctx.land is not None:
-            owner._grad_src = None
-            if has_ln and not (out_rows and out_rows < n) and not squeeze:
-                ctx.land.proc_ready = True
-            else:
-                ctx.land = None
-        if has_ln:
-            land = ctx.land
-            if land is not None and land.dec_buf is not None and cur.is_contiguous() and land.dec_buf.shape[2] == cur.shape[2]:
-                # the output is only consumed by the decoder-input gather: the rows it takes are written straight into
-                # the decoder's input, the others not at all (GradLanding.dec_buf); autograd sees a stride-0 token
-                if skip is not None:
-                    stats = hip.layernorm_fwd_map_skip(cur.view(B * n, -1), params[-2].detach(), params[-1].detach(), eps,
-                                                       land.dec_buf, skip[0], skip[1])
-                else:
-                    stats = hip.layernorm_fwd_map(cur.view(B * n, -1), params[-2].detach(), params[-1].detach(), eps,
-                                                  land.dec_buf, land.dec_map)
-                land.dec_filled = True
-                out = cur.new_zeros(()).expand(B, n, cur.shape[2])
-            else:
-                assert skip is None, "rows were skipped upstream of a dense LayerNorm"
-                o2, stats = hip.layernorm_fwd(cur.view(B * n, -1), params[-2].detach(), params[-1].detach(), eps)
-                out = o2.view(B, n, -1)
-        ctx.skip = skip
+        if mapped:
+            # the rows the decoder-input gather takes go straight into the decoder's input, the others nowhere
+            stats = land.ln_write(cur.view(B * n, -1), params[-2].detach(), params[-1].detach(), eps, present is not None)
+            out = _token(cur, (B, n, cur.shape[2]))
+        elif has_ln:
+            o2, stats = hip.layernorm_fwd(cur.view(B * n, -1), params[-2].detach(), params[-1].detach(), eps)
+            out = o2.view(B, n, -1)
+        ctx.land, ctx.present = land, present
         ctx.owner, ctx.graph, ctx.L, ctx.has_ln = owner, graph, L, has_ln
         ctx.x3, ctx.ps, ctx.stats, ctx.params, ctx.squeeze = x3, ps, stats, params, squeeze
         ctx.n_rows, ctx.out_rows = n, (int(out_rows) if out_rows and out_rows < n else 0)
@@ -320,26 +305,10 @@ class GCNStackFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         params, L, graph = ctx.params, ctx.L, ctx.graph
-        needs = list(ctx.needs_input_grad[7:])
+        needs = list(ctx.needs_input_grad[9:])
         G = _Grads(list(params), needs)
-        land = ctx.land
-        dy_map = None
-        if land is not None and land.proc_src is not None:
-            if all(st == 0 for st in dy.stride()):
-                # the incoming `dy` is the gather's stride-0 token: the real gradient is the gather's own incoming
-                # gradient, read through its row map
-                dy_map = (land.proc_src, land.proc_map)
-                dy3 = dy
-            else:
-                # something ELSE also sent gradient to the processor's output (a hook, a second consumer): autograd has
-                # summed it with the token into a real tensor, so the shortcut would drop it - materialise the gather's
-                # part and take the ordinary path
-                src, pmap = land.proc_src, land.proc_map
-                dy3 = _flat3(dy) + hip.gather2_rows(src, pmap, None, None, dy.shape[-2], src.shape[0])
-            land.proc_src = land.proc_map = None
-            land.proc_ready = False
-        else:
-            dy3 = _flat3(dy)
+        dy, dy_map = GradLanding.claim(ctx.land, dy)
+        dy3 = dy if dy_map is not None else _flat3(dy)  # (with a map `dy` is the token: only its shape is used)
         B, n = dy3.shape[0], ctx.n_rows
         ps = ctx.ps
         pad = ctx.pad_last
@@ -354,13 +323,13 @@ class GCNStackFn(torch.autograd.Function):
             dbet = G.dst[bi] if G.dst[bi] is not None else torch.zeros_like(params[bi])
             # the LayerNorm backward also sums its dx over the rows: that IS the bias gradient of the last conv
             cs = G.dst[bi_last] if (pad is None and _LN_COLSUM) else None
-            if ctx.skip is not None and dy_map is None:
+            if ctx.present is not None and dy_map is None:
                 raise RuntimeError("the processor's output received a gradient from outside the decoder-input gather, but its "
                                    "dropped rows were not kept (set GCL_NO_ROW_SKIP=1 to keep them)")
             dp = hip.layernorm_bwd(None if dy_map is not None else dy3.view(B * n, -1), ps[-1].view(B * n, -1),
                                    params[gi].detach(), ctx.stats, dgam, dbet, G.acc[gi] and G.acc[bi], colsum_dx=cs,
                                    acc_colsum=bool(cs is not None and G.acc[bi_last]), dy_map=dy_map,
-                                   skip=ctx.skip is not None).view(B, n, -1)
+                                   skip=ctx.present is not None).view(B, n, -1)
             cs_done = cs is not None
         else:
             dp = dy3
@@ -383,9 +352,9 @@ class GCNStackFn(torch.autograd.Function):
             W = params[2 * k].detach()
             wi = 2 * k
             inp = (ctx.x3 if k == 0 else ps[k - 1]).view(-1, (ctx.x3 if k == 0 else ps[k - 1]).shape[-1])
-            if k == L - 1 and ctx.skip is not None:
+            if k == L - 1 and ctx.present is not None:
                 # the dropped rows of dp were not written: their zeros come from the table
-                dh2 = hip.aggregate_present(graph, dp, ctx.skip[0], transpose=True).view(B * n, -1)
+                dh2 = hip.aggregate_present(graph, dp, ctx.present, transpose=True).view(B * n, -1)
             else:
                 dh2 = hip.aggregate(graph, dp, None, transpose=True).view(B * n, -1)
             if k == L - 1 and Fp != Fo:
@@ -405,7 +374,7 @@ class GCNStackFn(torch.autograd.Function):
                 hip.linear_bwd_dw(dh2, inp, None, dW, None, G.acc[wi])
         if dx is not None and ctx.squeeze:
             dx = dx[0]
-        return (dx, None, None, None, None, None, None) + G.out()
+        return (dx,) + (None,) * 8 + G.out()
 
 
 # ------------------------------------------------------------------------------------------------
@@ -416,19 +385,17 @@ class GATLayerFn(torch.autograd.Function):
     """One GATConv (with the shared PReLU applied to its input on load)."""
 
     @staticmethod
-    def forward(ctx, x, owner, graph, H: int, want_alpha: bool, slope, W, att_src, att_dst, bias):
+    def forward(ctx, x, owner, graph, H: int, want_alpha: bool, act, lat, slope, W, att_src, att_dst, bias):
+        """act: kind of the activation applied to x on load (None: PReLU when a slope is given); lat: LatSource or None."""
         squeeze = x.dim() == 2
         x3 = _flat3(x.detach())
         B, n, _ = x3.shape
         Cc = W.shape[0] // H
         sl = slope.detach() if slope is not None else None
-        act = getattr(owner, "_in_act", None)  # None: PReLU when a slope is given
-        lat = getattr(owner, "_lat_src", None)
         ctx.lat = ctx.tab = None
         if lat is not None:
             # x is the encoder output [B, ne, D] (LatSource): only its compact mesh rows are transformed, the attention
             # kernels read the transformed rows through the table - no [B, M, D] latents, no [B, M, H*C] transform
-            owner._lat_src = None
             assert sl is None, "a LatSource feeds the first layer of a stack (no input activation)"
             if not x3.is_contiguous():
                 x3 = x3.contiguous()
@@ -438,8 +405,7 @@ class GATLayerFn(torch.autograd.Function):
             h = hip.linear_fwd(Pc.view(B * nc, D), W.detach(), None, None, act=act).view(B, nc, H * Cc)
             ctx.lat, ctx.tab, ctx.enc_shape = lat, lat.compact_tab(ne), x3.shape
             x3 = Pc
-            if lat.landing is not None:
-                lat.landing.mesh_pending = True
+            GradLanding.expect_tail(lat.landing)
         else:
             h = hip.linear_fwd(x3.view(B * n, -1), W.detach(), None, sl, act=act).view(B, n, H * Cc)
         ctx.act = act
@@ -455,7 +421,7 @@ class GATLayerFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy, _dalpha):
         slope, W, att_src, att_dst, bias = ctx.params
-        needs = list(ctx.needs_input_grad[5:])
+        needs = list(ctx.needs_input_grad[7:])
         G = _Grads([slope, W, att_src, att_dst, bias], needs)
         graph, H, Cc = ctx.graph, ctx.H, ctx.Cc
         dy3 = _flat3(dy)
@@ -480,7 +446,7 @@ class GATLayerFn(torch.autograd.Function):
             dW = G.dst[1] if G.dst[1] is not None else torch.zeros_like(W)
             dx = _lat_first_layer_bwd(ctx.lat, None, dh, W.detach(), dW, G.acc[1], ctx.needs_input_grad[0], Pc=ctx.x3,
                                       enc_shape=tuple(ctx.enc_shape))
-            return (dx, None, None, None, None) + G.out()
+            return (dx,) + (None,) * 6 + G.out()
         dh2 = dh.view(B * n, -1)
         inp = ctx.x3.view(B * n, -1)
         sl = slope.detach() if slope is not None else None
@@ -498,54 +464,39 @@ class GATLayerFn(torch.autograd.Function):
             dx = dx.view(B, n, -1)
             if ctx.squeeze:
                 dx = dx[0]
-        return (dx, None, None, None, None) + G.out()
+        return (dx,) + (None,) * 6 + G.out()
 
 
 class LayerNormFn(torch.autograd.Function):
-    """Node-mode LayerNorm.  When the owner carries a GradLanding (`_grad_src`: the final LayerNorm of a GAT processor
-    inside WeatherPrediction.forward) it takes part in the same two channels as GCNStackFn's fused LayerNorm: the
-    output rows the decoder reads go straight into the decoder's input (dec_buf), and the backward reads its gradient
-    through the decoder-input gather's row map instead of a zero-filled dense tensor."""
+    """Node-mode LayerNorm.  Given a GradLanding (the final LayerNorm of a GAT processor inside
+    WeatherPrediction.forward) it takes part in the same two channels as GCNStackFn's fused LayerNorm: the output rows
+    the decoder reads go straight into the decoder's input, and the backward reads its gradient through the
+    decoder-input gather's row map instead of a zero-filled dense tensor."""
 
     @staticmethod
-    def forward(ctx, x, owner, eps, gamma, beta):
+    def forward(ctx, x, owner, eps, land, gamma, beta):
         x2 = hip.rows2d(x.detach())
-        land = getattr(owner, "_grad_src", None)
-        ctx.land = None
+        if x.dim() != 3:
+            land = None
+        ctx.land, ctx.params, ctx.x2 = land, (gamma, beta), x2
         if land is not None:
-            owner._grad_src = None
-            if x.dim() == 3:
-                ctx.land = land
-                land.proc_ready = True
-        ctx.params = (gamma, beta)
-        if ctx.land is not None and land.dec_buf is not None and land.dec_buf.shape[2] == x.shape[-1]:
-            B, n, F = x.shape
-            stats = hip.layernorm_fwd_map(x2, gamma.detach(), beta.detach(), eps, land.dec_buf, land.dec_map)
-            land.dec_filled = True
-            ctx.x2, ctx.stats = x2, stats
-            return x2.new_zeros(()).expand(B, n, F)
-        y, stats = hip.layernorm_fwd(x2, gamma.detach(), beta.detach(), eps)
-        ctx.x2, ctx.stats = x2, stats
+            land.expect_mapped_reader()
+            if land.ln_plan(x.shape[1], x.shape[2], False)[0]:
+                ctx.stats = land.ln_write(x2, gamma.detach(), beta.detach(), eps, False)
+                return _token(x2, x.shape)
+        y, ctx.stats = hip.layernorm_fwd(x2, gamma.detach(), beta.detach(), eps)
         return y.view(x.shape)
 
     @staticmethod
     def backward(ctx, dy):
         gamma, beta = ctx.params
-        G = _Grads([gamma, beta], list(ctx.needs_input_grad[3:]))
+        G = _Grads([gamma, beta], list(ctx.needs_input_grad[4:]))
         dg = G.dst[0] if G.dst[0] is not None else torch.zeros_like(gamma)
         db = G.dst[1] if G.dst[1] is not None else torch.zeros_like(beta)
-        land, dy_map = ctx.land, None
-        if land is not None and land.proc_src is not None:
-            if all(st == 0 for st in dy.stride()):
-                dy_map = (land.proc_src, land.proc_map)  # the token: the gradient is the gather's, through its row map
-            else:  # someone else also sent gradient here: materialise the gather's part and add (see GCNStackFn.backward)
-                src, pmap = land.proc_src, land.proc_map
-                dy = _flat3(dy) + hip.gather2_rows(src, pmap, None, None, dy.shape[-2], src.shape[0])
-            land.proc_src = land.proc_map = None
-            land.proc_ready = False
+        dy, dy_map = GradLanding.claim(ctx.land, dy)
         dx = hip.layernorm_bwd(None if dy_map is not None else hip.rows2d(dy), ctx.x2, gamma.detach(), ctx.stats, dg, db,
                                G.acc[0] and G.acc[1], dy_map=dy_map)
-        return (dx.view(dy.shape), None, None) + G.out()
+        return (dx.view(dy.shape), None, None, None) + G.out()
 
 
 class GraphNormFn(torch.autograd.Function):
@@ -670,15 +621,9 @@ class Gather2Fn(torch.autograd.Function):
             a3 = a3.contiguous()
         ctx.maps, ctx.B, ctx.landing = maps, B, landing
         ctx.sa, ctx.sb = a3.shape, (b.shape if b is not None else None)
-        if landing is not None and landing.dec_filled:
-            # the rows of source b are already in place (written by the producer's LayerNorm through the row map, b itself
-            # is a stride-0 token): only the head rows of source a are copied
-            landing.dec_filled = False
-            buf, landing.dec_buf = landing.dec_buf, None
-            hip.copy_rows(a3[:, : landing.head, :], buf[:, : landing.head, :])
+        buf = landing.take_decoder_input(a3) if landing is not None else None
+        if buf is not None:  # the rows of source b are already in place (b itself is a stride-0 token)
             return buf
-        if landing is not None:
-            landing.dec_buf = None
         b3 = b.detach() if b is not None else None
         if b3 is not None and not b3.is_contiguous():
             b3 = b3.contiguous()
@@ -689,49 +634,130 @@ class Gather2Fn(torch.autograd.Function):
         map_a, map_b, inv_a, inv_b = ctx.maps
         g = g.contiguous()
         da = db = None
+        land = ctx.landing
         if ctx.needs_input_grad[0]:
             bc = ctx.sa[0] == 1 and ctx.B > 1
-            land = ctx.landing
-            if land is not None and land.mesh_pending and not bc:
-                # GradLanding: this call fills the head rows of the shared gradient buffer and hands the WHOLE buffer to
-                # autograd; MeshLatFn.backward (always later: it needs the processor's backward, which needs db below)
-                # fills the tail rows in place and returns None - no zero-filled halves, no add of two full tensors
-                land.buf = torch.empty(ctx.sa, dtype=torch.float32, device=g.device)
-                hip.gather2_rows(g, inv_a, None, None, land.head, ctx.B, out=land.buf[:, : land.head])
-                da = land.buf
-                land.handed_over = True  # MeshLatFn.backward must run and fill the tail rows (checked there / by callers)
-            else:
+            if land is not None and not bc:
+                da = land.head_grad(g, inv_a, ctx.sa, ctx.B)  # the shared buffer with its head rows filled, or None
+            if da is None:
                 da = hip.gather2_rows(g, inv_a, None, None, ctx.sa[1], ctx.B, sum_batch=bc)
         if ctx.sb is not None and ctx.needs_input_grad[1]:
             bc = ctx.sb[0] == 1 and ctx.B > 1
-            land = ctx.landing
-            if land is not None and land.proc_ready and not bc:
-                land.proc_src, land.proc_map = g, inv_b
-                db = g.new_zeros(()).expand(ctx.sb)  # a stride-0 token: the consumer reads land.proc_src instead
-            else:
+            if land is not None and not bc:
+                db = land.offer(g, inv_b, ctx.sb)  # the token when the consumer reads (g, inv_b) itself, or None
+            if db is None:
                 db = hip.gather2_rows(g, inv_b, None, None, ctx.sb[1], ctx.B, sum_batch=bc)
         return da, db, None, None, None, None
 
 
 class GradLanding:
-    """One gradient buffer shared by the two consumers of the compact encoder output [B, ne, D]: the decoder-input
-    gather only ever sends gradient to the first `head` (grid) rows, the mesh-latent gather only to the rest.  See
-    Gather2Fn.backward / MeshLatFn.backward; used only when nothing else consumes the encoder output with a gradient
-    (WeatherPrediction.forward, not forward_with_latents)."""
+    """The hand-offs of one WeatherPrediction.forward call between the Functions around its processor (`head` = the
+    number of grid rows).  The model makes one per call and gives it to MeshLatFn (or the LatSource), to the processor's
+    final LayerNorm (GCNStackFn / LayerNormFn) and to the decoder-input gather (Gather2Fn): only those use the encoder output.
+
+    Encoder-output gradient.  The compact encoder output [B, ne, D] has two consumers: the decoder-input gather sends
+    gradient only to the first `head` rows, the mesh side (MeshLatFn, or a first processor layer reading through a
+    LatSource) only to the rest.  They share one buffer instead of autograd adding two zero-filled tensors:
+      forward   mesh side: expect_tail()
+      backward  Gather2Fn: head_grad() - fills the head rows and returns the WHOLE buffer to autograd (None when no tail
+                writer was announced: the caller gathers densely)
+                mesh side (always later: its gradient comes through the processor from the gather): tail() - the buffer,
+                to be filled in place from row `head` (its backward then returns None), or (None, 0): write a fresh
+                tensor from row 0.  The landing lets go of the buffer here; autograd already owns it.
+
+    Processor-output gradient.  The processor's output is consumed by the decoder-input gather alone, so its gradient is
+    the gather's incoming gradient seen through a row map; the final LayerNorm's backward reads it that way
+    (gcl_layernorm_bwd_map) instead of a zero-filled dense [B, M, D] tensor:
+      forward   LayerNorm: expect_mapped_reader()
+      backward  Gather2Fn: offer(g, inv_b) - keeps the pair and returns a stride-0 token for autograd to carry (None
+                when no reader was announced: the caller gathers densely)
+                LayerNorm: claim(dy) - the map, or, when something else also sent gradient to the processor's output (a
+                hook, a second consumer: autograd has summed it with the token into a real tensor, so the shortcut
+                would drop it), the dense gradient with the gather's share added.  Clears the offer.
+
+    Decoder input (forward).  Nobody sees the processor's output, so its final LayerNorm writes the rows the decoder
+    reads straight into the decoder's input [B, head + U, D] and the gather only copies the head rows:
+      model      open_decoder_input(), before the processor runs: the buffer, the map mesh row -> row of the buffer (or
+                 -1) and, optionally, the mesh rows with a reader as a list (lets the producer skip the others)
+      LayerNorm  ln_plan() - does the output go through the map, and are the unread rows skipped? - then ln_write()
+      Gather2Fn  take_decoder_input(): the filled buffer with the head rows copied in; a buffer nobody filled is dropped
+                 (None: the caller gathers both sources)."""
 
     def __init__(self, head: int):
         self.head, self.buf, self.mesh_pending = head, None, False
-        self.handed_over = False  # True between Gather2Fn.backward handing the buffer out and MeshLatFn.backward filling its tail
-        # second channel: the processor's output is only consumed by the decoder-input gather, so its gradient is the
-        # gather's incoming gradient seen through a row map - the processor's LayerNorm backward reads it that way
-        # (gcl_layernorm_bwd_map) instead of a zero-filled dense [B, M, D] tensor
         self.proc_ready, self.proc_src, self.proc_map = False, None, None
-        # third channel (forward): the decoder-input buffer [B, head + U, D], allocated by the model before the processor
-        # runs, and the map mesh row -> row of that buffer (or -1).  The processor's final LayerNorm writes the rows
-        # the decoder reads straight into it (gcl_layernorm_fwd_map) and the gather then only copies the head rows.
-        # dec_rows: the mesh rows with dec_map >= 0 as a list (the rows of the processor's output that have a reader)
-        self.dec_buf, self.dec_map, self.dec_filled = None, None, False
-        self.dec_rows = None
+        self.dec_buf, self.dec_map, self.dec_rows, self.dec_filled = None, None, None, False
+
+    # encoder-output gradient (the static methods take the landing as it reaches their caller: it may be None)
+    @staticmethod
+    def expect_tail(land):
+        if land is not None:
+            land.mesh_pending = True
+
+    def head_grad(self, g, inv_a, shape, B: int):
+        if not self.mesh_pending:
+            return None
+        self.buf = torch.empty(shape, dtype=torch.float32, device=g.device)
+        hip.gather2_rows(g, inv_a, None, None, self.head, B, out=self.buf[:, : self.head])
+        return self.buf
+
+    @staticmethod
+    def tail(land):
+        if land is None or land.buf is None:
+            return None, 0
+        buf, land.buf, land.mesh_pending = land.buf, None, False
+        return buf, land.head
+
+    # processor-output gradient
+    def expect_mapped_reader(self):
+        self.proc_ready = True
+
+    def offer(self, g, inv_b, shape):
+        if not self.proc_ready:
+            return None
+        self.proc_src, self.proc_map = g, inv_b
+        return _token(g, shape)
+
+    @staticmethod
+    def claim(land, dy):
+        """-> (dy, dy_map): dy_map = (src3, pos) for hip.layernorm_bwd when `dy` is the token, else None and `dy` dense."""
+        if land is None or land.proc_src is None:
+            return dy, None
+        src, pmap = land.proc_src, land.proc_map
+        land.proc_src = land.proc_map = None
+        land.proc_ready = False
+        if all(st == 0 for st in dy.stride()):
+            return dy, (src, pmap)
+        return _flat3(dy) + hip.gather2_rows(src, pmap, None, None, dy.shape[-2], src.shape[0]), None
+
+    # decoder input
+    def open_decoder_input(self, B: int, rows: int, width: int, device, dec_map, dec_rows=None):
+        self.dec_buf = torch.empty(B, rows, width, dtype=torch.float32, device=device)
+        self.dec_map, self.dec_rows = dec_map, dec_rows
+
+    def ln_plan(self, n: int, F: int, may_skip: bool):
+        """For a LayerNorm over n rows per sample, F wide: (mapped?, the `present` table when unread rows are skipped)."""
+        if self.dec_buf is None or self.dec_buf.shape[2] != F:
+            return False, None
+        skip = may_skip and self.dec_rows is not None and self.dec_rows.numel() < n
+        return True, (self.dec_map if skip else None)
+
+    def ln_write(self, x2, gamma, beta, eps: float, skip: bool):
+        """The mapped LayerNorm of x2 [B * n, F] into the decoder input; returns the row statistics."""
+        if skip:
+            stats = hip.layernorm_fwd_map_skip(x2, gamma, beta, eps, self.dec_buf, self.dec_map, self.dec_rows)
+        else:
+            stats = hip.layernorm_fwd_map(x2, gamma, beta, eps, self.dec_buf, self.dec_map)
+        self.dec_filled = True
+        return stats
+
+    def take_decoder_input(self, a3):
+        buf, filled = self.dec_buf, self.dec_filled
+        self.dec_buf, self.dec_filled = None, False
+        if not filled:
+            return None
+        hip.copy_rows(a3[:, : self.head, :], buf[:, : self.head, :])
+        return buf
 
 
 class MeshLatFn(torch.autograd.Function):
@@ -751,8 +777,7 @@ class MeshLatFn(torch.autograd.Function):
             e3 = e3.contiguous()
         B, ne, D = e3.shape
         ctx.maps, ctx.shape, ctx.gmd, ctx.r, ctx.landing = maps, (B, ne, D), gmd, r, landing
-        if landing is not None:
-            landing.mesh_pending = True
+        GradLanding.expect_tail(landing)
         return hip.gather2_rows(e3, map_a, e3.view(1, B * ne, D), map_b, M, B)
 
     @staticmethod
@@ -760,20 +785,11 @@ class MeshLatFn(torch.autograd.Function):
         _, _, inv_a, inv_fold = ctx.maps
         B, ne, D = ctx.shape
         g = g.contiguous()
-        land = ctx.landing
-        shared = land is not None and land.buf is not None
-        out = land.buf if shared else torch.empty(B, ne, D, dtype=torch.float32, device=g.device)
-        h = land.head if shared else 0  # rows below `head` were written by the decoder-input gather's backward
+        buf, h = GradLanding.tail(ctx.landing)  # rows below h were written by the decoder-input gather's backward
+        out = buf if buf is not None else torch.empty(B, ne, D, dtype=torch.float32, device=g.device)
         hip.gather2_rows(g, inv_a[h:], None, None, ctx.gmd - h, B, out=out[:, h: ctx.gmd])
-        if ctx.r > 1:  # the batch sums land r to a sample, straight in the tail rows
-            hip.gather2_rows(g, inv_fold, None, None, B * ctx.r, B, sum_batch=True, out=out[:, ctx.gmd:], deal=ctx.r)
-        elif ctx.r == 1:
-            tmp = hip.gather2_rows(g, inv_fold, None, None, B * ctx.r, B, sum_batch=True)
-            hip.copy_rows(tmp.view(B, ctx.r, D), out[:, ctx.gmd:])
-        if shared:
-            land.buf, land.mesh_pending, land.handed_over = None, False, False
-            return None, None, None, None, None, None
-        return out, None, None, None, None, None
+        _fold_sum(g, inv_fold, ctx.r, B, out[:, ctx.gmd:])  # straight in the tail rows
+        return (None if buf is not None else out), None, None, None, None, None
 
 
 # ------------------------------------------------------------------------------------------------

@@ -108,9 +108,9 @@ class LayerNorm(nn.Module):
         self.weight = nn.Parameter(torch.ones(in_channels))
         self.bias = nn.Parameter(torch.zeros(in_channels))
 
-    def forward(self, x):
+    def forward(self, x, landing=None):  # landing: functional.GradLanding, for a processor's final node LayerNorm
         if self.mode == "node":
-            return LayerNormFn.apply(x, self, self.eps, self.weight, self.bias)
+            return LayerNormFn.apply(x, self, self.eps, landing, self.weight, self.bias)
         if self.mode == "graph":
             return GraphNormFn.apply(x, self, self.eps, self.weight, self.bias)
         raise ValueError(f"Unknown normalization mode: {self.mode}")
@@ -128,7 +128,7 @@ class GCNConv(nn.Module):
 
     def forward(self, x, edge_index):
         g = _graphs.get(edge_index, _num_nodes(x), hip.GRAPH_GCN)
-        return GCNStackFn.apply(x, self, g, 1, False, 1e-5, 0, self.lin.weight, self.bias, None)
+        return GCNStackFn.apply(x, self, g, 1, False, 1e-5, 0, None, None, self.lin.weight, self.bias, None)
 
 
 class GATConv(nn.Module):
@@ -150,10 +150,9 @@ class GATConv(nn.Module):
         _glorot_(self.att_dst)
 
     def _run(self, x, edge_index, slope, want_alpha, act=None, lat_src=None):
+        """lat_src: functional.LatSource - x is then the encoder output."""
         g = _graphs.get(edge_index, lat_src.M if lat_src is not None else _num_nodes(x), hip.GRAPH_GAT)
-        self._in_act = act
-        self._lat_src = lat_src  # functional.LatSource (picked up by GATLayerFn): x is the encoder output
-        y, alpha = GATLayerFn.apply(x, self, g, self.heads, want_alpha, slope, self.lin.weight, self.att_src,
+        y, alpha = GATLayerFn.apply(x, self, g, self.heads, want_alpha, act, lat_src, slope, self.lin.weight, self.att_src,
                                     self.att_dst, self.bias)
         return y, alpha, g
 
@@ -413,7 +412,9 @@ class GraphLayer(nn.Module):
             if edge_attr is None:
                 raise ValueError("InteractionNet requires edge_attr (edge features)")
             return self.layers(x=X, edge_index=edge_index, edge_attr_raw=edge_attr)
-        lat_src = kwargs.get("_lat_src") if self.layer_type in (GraphLayerType.ConvGCN, GraphLayerType.GATConv) else None
+        # _land: functional.GradLanding for the final node LayerNorm; _lat: functional.LatSource (X is then the encoder output)
+        land = kwargs.get("_land")
+        lat_src = kwargs.get("_lat") if self.layer_type in (GraphLayerType.ConvGCN, GraphLayerType.GATConv) else None
         n = lat_src.M if lat_src is not None else _num_nodes(X)  # with a LatSource X is the encoder output, the graph the mesh
         ln = self._final_ln()
         fuse_ln = ln is not None and ln.mode == "node"
@@ -428,13 +429,12 @@ class GraphLayer(nn.Module):
                 params += [ln.weight, ln.bias]
             g = _graphs.get(edge_index, n, hip.GRAPH_GCN)
             out_rows = int(kwargs.get("_out_rows") or 0)  # the caller keeps only the first rows (decoder: grid rows)
-            self._grad_src = kwargs.get("_grad_src") if fuse_ln else None  # functional.GradLanding (picked up by GCNStackFn)
-            self._lat_src = lat_src  # functional.LatSource (picked up by GCNStackFn): X is read through a row table
             if ln is not None and not fuse_ln:
-                X = GCNStackFn.apply(X, self, g, len(convs), False, 1e-5, 0, *params)
+                X = GCNStackFn.apply(X, self, g, len(convs), False, 1e-5, 0, None, lat_src, *params)
                 X = ln(X)
                 return X[..., :out_rows, :] if out_rows else X
-            return GCNStackFn.apply(X, self, g, len(convs), fuse_ln, ln.eps if fuse_ln else 1e-5, out_rows, *params)
+            return GCNStackFn.apply(X, self, g, len(convs), fuse_ln, ln.eps if fuse_ln else 1e-5, out_rows,
+                                    land if fuse_ln else None, lat_src, *params)
 
         if self.layer_type == GraphLayerType.GATConv:
             slope, act = None, hip.ACT_NONE
@@ -446,9 +446,7 @@ class GraphLayer(nn.Module):
                     slope = self._slope if self._slope is not None else self.const_slope
                     act = self.act_kind
                 elif isinstance(layer, LayerNorm):
-                    if layer is ln and fuse_ln:
-                        layer._grad_src = kwargs.get("_grad_src")  # functional.GradLanding (picked up by LayerNormFn)
-                    X = layer(X)
+                    X = layer(X, land if layer is ln and fuse_ln else None)
             return X
 
         if self.layer_type == GraphLayerType.SparseGATConv:
@@ -456,9 +454,7 @@ class GraphLayer(nn.Module):
                 if isinstance(layer, SparseGATConv):
                     X, (edge_index, _) = layer.forward(X, edge_index, attention_threshold, **kwargs)
                 elif isinstance(layer, LayerNorm):
-                    if layer is ln and fuse_ln:
-                        layer._grad_src = kwargs.get("_grad_src")  # functional.GradLanding (picked up by LayerNormFn)
-                    X = layer(X)
+                    X = layer(X, land if layer is ln and fuse_ln else None)
             return X, edge_index
         raise NotImplementedError(f"Layer type {self.layer_type} not supported.")
 
@@ -781,7 +777,10 @@ class WeatherPrediction(nn.Module):
         c.fold[B] = f
         return f
 
-    def _forward_compact(self, X: torch.Tensor, attention_threshold=0.0, **kwargs):
+    def _forward_compact(self, X: torch.Tensor, attention_threshold=0.0, _landing=False, _latents_discarded=False, **kwargs):
+        """_landing: the caller keeps only the prediction, or takes the processor's rows in tile order: the encoder
+        output's two gradient consumers may share one buffer (functional.GradLanding).  _latents_discarded: nobody sees the
+        processor's output at all (forward()), so its final LayerNorm may write only the rows the decoder reads."""
         G, M = self._num_grid_nodes, self._num_mesh_nodes
         squeeze = X.dim() == 2 or (X.dim() == 3 and X.shape[0] == 1)
         X3 = X if X.dim() == 3 else X.unsqueeze(0)
@@ -802,13 +801,12 @@ class WeatherPrediction(nn.Module):
             else:
                 x_c = AssembleFn.apply(X3, self.init_grid_features, f.mstat, f.x_fold if f.r > 0 else None)  # [B, G+Md+r, C]
                 enc_c = self.encoder.forward(X=x_c, edge_index=c.enc_graph)         # [B, G+Md+r, D]
-            land = GradLanding(G) if kwargs.pop("_landing", False) and self._grad_landing else None
+            land = GradLanding(G) if _landing and self._grad_landing else None
             lat_src = self._lat_source(c, f, enc_c, land)
             if lat_src is None:
                 mesh_lat = MeshLatFn.apply(enc_c, f.maps, M, G + c.Md, f.r, land)   # [B, M, D]
             maps_dec = f.maps_dec
         else:
-            kwargs.pop("_landing", None)
             land = None
             lat_src = None
             maps_dec = c.maps_dec
@@ -816,14 +814,17 @@ class WeatherPrediction(nn.Module):
             enc_c = self.encoder.forward(X=x_c, edge_index=c.enc_graph)                 # [B, G+Md, D]
             inv = self.encoder.forward(X=c.x_inv, edge_index=c.empty_graph) if c.Mi > 0 else None  # [1, Mi, D]
             mesh_lat = Gather2Fn.apply(enc_c, inv, c.maps_mesh, M, B)                   # [B, M, D]
+        gl_type = self.processor.graph_layer.layer_type
+        if (land is not None and self._ln_into_decoder_input and _latents_discarded and not squeeze
+                and gl_type in (GraphLayerType.ConvGCN, GraphLayerType.GATConv, GraphLayerType.SparseGATConv)):
+            # the processor's output is only consumed by the decoder-input gather: its final LayerNorm writes the rows the
+            # decoder reads straight into the decoder's input.  maps_dec[1][G:]: the U mesh rows the decoder reads (a view
+            # of the set-up's device table), for a producer that can skip the others
+            land.open_decoder_input(B, G + c.U, enc_c.shape[-1], enc_c.device, maps_dec[3], maps_dec[1][G:])
         if self.using_sparse_gat:
             pg = self._processing_graph_tiled() if c.perm is not None else self.processing_graph
-            if land is not None and self._ln_into_decoder_input and self._latents_discarded and not squeeze:
-                land.dec_buf = torch.empty(B, G + c.U, enc_c.shape[-1], dtype=torch.float32, device=enc_c.device)
-                land.dec_map = maps_dec[3]
             processed, new_edge_index = self.processor.forward(
-                X=mesh_lat, edge_index=pg, attention_threshold=attention_threshold,
-                **({"_grad_src": land} if land is not None else {}), **kwargs)
+                X=mesh_lat, edge_index=pg, attention_threshold=attention_threshold, _land=land, **kwargs)
             self.processing_graph = self._processing_graph_from_tiled(new_edge_index) if c.perm is not None else new_edge_index
         elif self.using_interaction_net:
             processed = self.processor.forward(X=mesh_lat, edge_index=self.processing_graph,
@@ -831,27 +832,15 @@ class WeatherPrediction(nn.Module):
                                                edge_attr=self._processing_edge_features)
         else:
             pg = self._processing_graph_tiled() if c.perm is not None else self.processing_graph
-            if (land is not None and self._ln_into_decoder_input and self._latents_discarded
-                    and self.processor.graph_layer.layer_type in (GraphLayerType.ConvGCN, GraphLayerType.GATConv)
-                    and not squeeze):
-                # the processor's output is only consumed by the decoder-input gather: its final LayerNorm writes the
-                # rows the decoder reads straight into the decoder's input (functional.GradLanding.dec_buf)
-                land.dec_buf = torch.empty(B, G + c.U, enc_c.shape[-1], dtype=torch.float32, device=enc_c.device)
-                land.dec_map = maps_dec[3]
-                land.dec_rows = maps_dec[1][G:]  # the U mesh rows the decoder reads (a view of the set-up's device table)
-            if lat_src is not None:
-                # the first GCNConv reads the mesh latents THROUGH the row table from the encoder output: they are never
-                # materialised, and its backward works on the compact rows (functional.GCNStackFn, LatSource)
-                processed = self.processor.forward(X=enc_c, edge_index=pg, attention_threshold=attention_threshold,
-                                                   _lat_src=lat_src, **({"_grad_src": land} if land is not None else {}))
-            else:
-                processed = self.processor.forward(X=mesh_lat, edge_index=pg, attention_threshold=attention_threshold,
-                                                   **({"_grad_src": land} if land is not None else {}))
+            # with a LatSource the first conv reads the mesh latents THROUGH the row table from the encoder output: they are
+            # never materialised, and its backward works on the compact rows (functional.GCNStackFn, LatSource)
+            processed = self.processor.forward(X=enc_c if lat_src is not None else mesh_lat, edge_index=pg,
+                                               attention_threshold=attention_threshold, _lat=lat_src, _land=land)
         dec_in = Gather2Fn.apply(enc_c, processed, maps_dec, G + c.U, B, land)      # [B, G+U, D]
         gcn_dec = self.decoder.graph_layer.layer_type == GraphLayerType.ConvGCN
         decoded = self.decoder.forward(X=dec_in, edge_index=c.dec_graph, **({"_out_rows": G} if gcn_dec else {}))
         out, grid_lat = (decoded if gcn_dec else decoded[:, :G, :]), enc_c[:, :G, :]
-        if c.perm is not None and not self._want_prediction_only:
+        if c.perm is not None and not _landing:  # (_landing: the mesh latents are dropped or wanted in tile order)
             # callers see reference row order; the device copy of the row map is made once, so that a call inside a
             # hipGraph capture (the ROI head's TrainStep runs this forward) issues no host-to-device copy
             pos_dev = getattr(c, "perm_pos_dev", None)
@@ -865,7 +854,6 @@ class WeatherPrediction(nn.Module):
     _lat_through_table = os.environ.get("GCL_NO_LAT_TABLE", "0") in ("0", "")
     _mlp_on_folded_rows = os.environ.get("GCL_NO_MLP_FOLD", "0") in ("0", "")
     _ln_into_decoder_input = os.environ.get("GCL_NO_LN_MAP", "0") in ("0", "")
-    _latents_discarded = False  # True only inside forward(): nobody sees the processor's output
 
     def _lat_source(self, c, f, enc_c, land):
         """functional.LatSource when the processor's first layer can read the mesh latents through the row table
@@ -891,13 +879,11 @@ class WeatherPrediction(nn.Module):
             return None
         return LatSource(f.tab, f.maps, self._num_mesh_nodes, self._num_grid_nodes, c.Md, f.r, land)
 
-    _want_prediction_only = False
-
-    def forward_with_latents(self, X: torch.Tensor, attention_threshold=0.0, **kwargs):
-        landing = kwargs.pop("_landing", False)
-        self._want_prediction_only = landing  # forward(): the mesh latents are dropped, so they stay in tile order
+    def forward_with_latents(self, X: torch.Tensor, attention_threshold=0.0, _landing=False, _latents_discarded=False,
+                             **kwargs):
+        """_landing, _latents_discarded: see _forward_compact (the general path has no use for either)."""
         if self._compact_eligible():
-            return self._forward_compact(X, attention_threshold, _landing=landing, **kwargs)
+            return self._forward_compact(X, attention_threshold, _landing, _latents_discarded, **kwargs)
         G = self._num_grid_nodes
         if X.dim() == 3 and X.shape[0] == 1:
             X = X.squeeze(0)  # reference: X.squeeze() with batch 1 (src/models.py:822)
@@ -933,8 +919,4 @@ class WeatherPrediction(nn.Module):
         # they may share one gradient buffer (functional.GradLanding)
         # ... and the processor's output itself is never seen by the caller, so its LayerNorm may write only the rows the
         # decoder reads, straight into the decoder's input (the `processed` the inner call returns is then a zero token)
-        self._latents_discarded = True
-        try:
-            return self.forward_with_latents(X, attention_threshold, _landing=True, **kwargs)[0]
-        finally:
-            self._latents_discarded = False
+        return self.forward_with_latents(X, attention_threshold, _landing=True, _latents_discarded=True, **kwargs)[0]

@@ -187,7 +187,7 @@ def test_latents_through_row_table_equal_materialised(name, levels, B):
 @pytest.mark.parametrize("name", ["baseline", "attention"])
 def test_processor_layernorm_into_decoder_input_equals_gather(name):
     """forward(): nobody sees the processor's output, so its final LayerNorm writes only the rows the decoder reads,
-    straight into the decoder's input (gcl_layernorm_fwd_map, functional.GradLanding.dec_buf) and the gather copies
+    straight into the decoder's input (gcl_layernorm_fwd_map, functional.GradLanding.ln_write) and the gather copies
     just the grid rows.  Against the same model with the dense LayerNorm + gather: prediction bit-identical, gradients
     identical too (the backward is the same code on the same saved tensors)."""
     from graphcast_lite_amd.train import batch_loss
@@ -351,6 +351,35 @@ def test_second_consumer_of_the_processor_output_keeps_its_gradient(name):
     for n_, g in grads[1].items():
         d = float((grads[0][n_].double() - g.double()).norm())
         assert d <= 1e-5 * float(g.double().norm()) + 1e-7 * gn, n_
+
+
+@pytest.mark.parametrize("name", ["baseline", "attention"])
+def test_two_forwards_in_flight_share_no_state(name):
+    """Two forward() calls of one model before a single backward: each call's hand-offs (functional.GradLanding, the
+    LatSource) travel as arguments of the autograd Functions, so the second forward cannot disturb the first one's
+    pending backward and nothing is parked on a module.  Against a twin without the landing (plain autograd
+    accumulation): outputs bit-identical, gradients equal to summation order."""
+    cfg, m1, _ = make_pair(name, [1, 2])
+    _, m2, _ = make_pair(name, [1, 2])
+    X1, _ = data(cfg, m1._num_grid_nodes, 3)
+    X2, _ = data(cfg, m1._num_grid_nodes, 3, seed=4321)
+    assert m1._grad_landing and m1._compact_eligible()
+    m2._grad_landing = False
+    outs, grads = [], []
+    for m in (m1, m2):
+        out1 = m(X1.to(DEV))
+        out2 = m(X2.to(DEV))
+        (out1.pow(2).mean() + out2.pow(2).mean()).backward()
+        outs.append((out1.detach(), out2.detach()))
+        grads.append({n_: p.grad.clone() for n_, p in m.named_parameters()})
+    assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
+    gn = float(torch.sqrt(sum((g.double() ** 2).sum() for g in grads[1].values())))
+    for n_, g in grads[1].items():
+        d = float((grads[0][n_].double() - g.double()).norm())
+        assert d <= 1e-5 * float(g.double().norm()) + 1e-7 * gn, n_
+    for mod_name, mod in m1.named_modules():
+        for attr in ("_grad_src", "_lat_src", "_in_act"):
+            assert not hasattr(mod, attr), f"{mod_name or 'model'} carries {attr}"
 
 
 def test_graph_captured_step_equals_eager():
