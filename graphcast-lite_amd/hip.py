@@ -143,6 +143,13 @@ _SIGNATURES = {
     "gcl_pipeline_lapse": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, C.c_double, _i32, _vp]),
     "gcl_pipeline_station_obs": (C.c_int, [_vp, _i64, _vp, _i32, _i32, _i32, _vp, _vp]),
     "gcl_pipeline_sqerr": (C.c_int, [_vp, _i64, _i64, _i32, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "gcl_maps_colstats_ws_bytes": (_sz, [_i32, _i32, _i32]),
+    "gcl_maps_colstats": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _sz,
+                                    _vp]),
+    "gcl_maps_accumulate": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _vp,
+                                      _i32, _vp, _vp, _vp]),
+    "gcl_maps_finalize": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i64, _i32, _vp, _vp, _i32, _i32, _vp, _vp]),
+    "gcl_maps_convert": (C.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _vp]),
 }
 
 
@@ -1249,3 +1256,69 @@ def pipeline_sqerr(preds3, truth2, stn, h: int, acc_grid, acc_stn=None):
     _check(lib().gcl_pipeline_sqerr(_p(preds3), preds3.stride(0), preds3.stride(1), V, _p(truth2), truth2.stride(0),
                                     _pi(stn), stn.numel() if stn is not None else 0, G, C, acc_grid.shape[1], int(h),
                                     _pd(acc_grid), _pd(acc_stn) if acc_stn is not None else None, _stream()))
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# Per-grid-point error maps (csrc/maps.hip)
+# ------------------------------------------------------------------------------------------------------------------
+MAPS_SUM_E, MAPS_SUM_SQ, MAPS_SUM_ABS, MAPS_SUM_PT = 1, 2, 4, 8
+MAPS_RMSE, MAPS_MAE, MAPS_BIAS, MAPS_ACC, MAPS_SKILL = 0, 1, 2, 3, 4
+
+
+def _maps_layout(truth3, pred3, pmap, rows, conv, flags, K: int):
+    B, G, W = truth3.shape
+    assert truth3.is_cuda and truth3.stride(2) == 1 and W >= K
+    assert pred3.shape[0] == B and pred3.shape[1] == G and pred3.stride(2) == 1 and (pmap is not None or pred3.shape[2] >= K)
+    assert pmap is None or pmap.numel() == K
+    assert (conv is None) == (flags is None)
+    assert conv is None or (conv.shape == (K, 4) and conv.is_contiguous() and flags.numel() == K)
+    return B, (rows.numel() if rows is not None else G)
+
+
+def maps_colstats(truth3, pred3, pmap, rows, conv, flags, cs):
+    """Per-sample field mean and unbiased std of the converted prediction and truth (see gcl_maps_colstats).  truth3
+    [B, G, >= K] and pred3 [B, G, W] float32 with unit column stride; pmap int32 [K] or None; rows int32 [n] or None;
+    conv float32 [K, 4] with flags int32 [K], or both None; cs float64 [B, K, 4]."""
+    K = cs.shape[1]
+    B, n = _maps_layout(truth3, pred3, pmap, rows, conv, flags, K)
+    assert cs.shape == (B, K, 4)
+    ws = workspace(int(lib().gcl_maps_colstats_ws_bytes(n, K, B)), truth3.device)
+    _check(lib().gcl_maps_colstats(_p(truth3), truth3.stride(1), truth3.stride(0), _p(pred3), pred3.stride(1),
+                                   pred3.stride(0), _pi(pmap), K, _p(conv), _pi(flags), _pi(rows), n, B, _pd(cs),
+                                   ws.data_ptr(), ws.numel(), _stream()))
+    return cs
+
+
+def maps_accumulate(truth3, pred3, pmap, rows, conv, flags, cs, sums: int, C: int, state, count):
+    """Add a batch into the float64 map state [leads, nsums, n * C] and B into count (int64 [1], on the device); see
+    gcl_maps_accumulate.  cs: the result of `maps_colstats` (None without the ACC sum)."""
+    leads, nsums, nE = state.shape
+    assert nsums == bin(sums).count("1") and count.is_cuda and count.dtype == torch.int64 and count.numel() == 1
+    B, n = _maps_layout(truth3, pred3, pmap, rows, conv, flags, leads * C)
+    assert nE == n * C
+    _check(lib().gcl_maps_accumulate(_p(truth3), truth3.stride(1), truth3.stride(0), _p(pred3), pred3.stride(1),
+                                     pred3.stride(0), _pi(pmap), leads, C, _p(conv), _pi(flags), _pi(rows), n, B,
+                                     _pd(cs) if cs is not None else None, int(sums), _pd(state), count.data_ptr(),
+                                     _stream()))
+
+
+def maps_finalize(state, count, plane: int, kind: int, out, ref_state=None, ref_count=None, ref_plane: int = 0):
+    """out float32 [leads, n * C] = the map of `kind` from sum `plane` of the state (see gcl_maps_finalize)."""
+    leads, nsums, nE = state.shape
+    assert out.is_contiguous() and out.numel() == leads * nE
+    assert ref_state is None or (ref_state.shape[0] == leads and ref_state.shape[2] == nE)
+    _check(lib().gcl_maps_finalize(_pd(state), count.data_ptr(), int(plane), nsums, leads, nE, int(kind),
+                                   _pd(ref_state) if ref_state is not None else None,
+                                   ref_count.data_ptr() if ref_count is not None else None, int(ref_plane),
+                                   ref_state.shape[1] if ref_state is not None else 0, _p(out), _stream()))
+    return out
+
+
+def maps_convert(x, conv, flags):
+    """A new tensor: x [..., K] float32 converted column by column (see gcl_maps_convert)."""
+    K = conv.shape[0]
+    assert conv.shape == (K, 4) and conv.is_contiguous() and flags.numel() == K and x.shape[-1] == K
+    x = x.contiguous()
+    out = torch.empty_like(x)
+    _check(lib().gcl_maps_convert(_p(x), _p(out), x.numel(), K, _p(conv), _pi(flags), _stream()))
+    return out

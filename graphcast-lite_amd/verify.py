@@ -15,8 +15,14 @@ reference's inference scripts.
 * `build_taper_mask_2d` (`scripts/predict_pipeline.py:135-149`), `taper_blend` (`:326`).
 * `GlobalRegionalForecast` (`scripts/predict_pipeline.py:300-329`) and its hipGraph-captured form
   `CapturedGlobalRegionalForecast`.
+* `load_scaler_stats`, `inverse_standardize`, `unit_label`, `apply_units`, `compute_stat`
+  (`scripts/metrics_maps.py:29-90`): same names and signatures, device tensors; the unit conversion is bit-equal to
+  the reference's CPU arithmetic.
+* `MetricMaps`, `CapturedMetricMaps`, `metric_maps`: the per-grid-point RMSE / MAE / bias / ACC maps of that script
+  (`:143-176`), accumulated batch by batch in a float64 device state, per lead time, optionally on a row subset and
+  against persistence.
 
-Kernels: csrc/verify.hip.
+Kernels: csrc/verify.hip, csrc/maps.hip.
 """
 from typing import Optional, Sequence
 
@@ -537,3 +543,363 @@ class CapturedGlobalRegionalForecast(GlobalRegionalForecast, Captured):
             return self._work(gX, rX)
         out = self._run(gX, rX)
         return tuple(t.clone() for t in out) if out is self._result else out
+
+
+# ======================================================================================================================
+# Per-grid-point error maps (scripts/metrics_maps.py)
+# ======================================================================================================================
+_MAP_STATS = ("rmse", "mae", "bias", "acc")
+_STAT_SUM = {"bias": hip.MAPS_SUM_E, "rmse": hip.MAPS_SUM_SQ, "mae": hip.MAPS_SUM_ABS, "acc": hip.MAPS_SUM_PT}
+_STAT_KIND = {"rmse": hip.MAPS_RMSE, "mae": hip.MAPS_MAE, "bias": hip.MAPS_BIAS, "acc": hip.MAPS_ACC}
+_CONV_DENORM, _CONV_ZDIV = 1, 2
+
+_UNITS_BY_NAME = {"t2m": ("K", 1.0, 0.0, None), "msl": ("hPa", 1 / 100.0, 0.0, None),
+                  "tp": ("mm/6h", 1000.0, 0.0, None)}
+_UNITS_BY_NAME.update({w: ("m/s", 1.0, 0.0, None) for w in ("10u", "10v", "u@850", "u@500", "v@850", "v@500")})
+_UNITS_BY_PREFIX = (("t@", ("K", 1.0, 0.0, None)), ("z@", ("m", 1.0, 0.0, "z_to_m")),
+                    ("q@", ("g/kg", 1000.0, 0.0, "q_to_gkg")))
+
+
+def unit_label(name: str):
+    """(label, factor, offset, special) of a variable (`scripts/metrics_maps.py:46-63`): the physical value is
+    `value * factor + offset`, after a division by g0 when special is 'z_to_m' (geopotential -> metres); 'q_to_gkg'
+    only names the factor 1000.  Unknown names: ("", 1.0, 0.0, None)."""
+    hit = _UNITS_BY_NAME.get(name)
+    if hit is not None:
+        return hit
+    for prefix, units in _UNITS_BY_PREFIX:
+        if name.startswith(prefix):
+            return units
+    return ("", 1.0, 0.0, None)
+
+
+def load_scaler_stats(dataset_dir):
+    """The target scalers of a data set directory (`scripts/metrics_maps.py:29-38`): {"y_mean", "y_scale"} read from
+    its `scalers.npz`, or None when the directory has none - `MetricMaps` then scores in standardised units, and a
+    RuntimeWarning says so."""
+    import os
+    import warnings
+
+    path = os.path.join(os.fspath(dataset_dir), "scalers.npz")
+    try:
+        with np.load(path) as scalers:
+            return {key: scalers[key] for key in ("y_mean", "y_scale")}
+    except FileNotFoundError:
+        warnings.warn(f"{path} is missing: the error maps stay in standardised units", RuntimeWarning)
+        return None
+
+
+def _conv_rows(var_order, y_mean, y_scale, K: int):
+    """float32 [K, 4] {scale, mean, factor, offset} and int32 [K] flags of gcl_maps_*; var_order / y_mean / y_scale
+    already of length K or None."""
+    conv = np.zeros((K, 4), dtype=np.float32)
+    conv[:, 0], conv[:, 2] = 1.0, 1.0
+    flags = np.zeros(K, dtype=np.int32)
+    if y_mean is not None:
+        conv[:, 0], conv[:, 1] = np.asarray(y_scale, dtype=np.float32), np.asarray(y_mean, dtype=np.float32)
+        flags |= _CONV_DENORM
+    if var_order is not None:
+        for k, name in enumerate(var_order):
+            _, factor, offset, special = unit_label(name)
+            conv[k, 2], conv[k, 3] = np.float32(factor), np.float32(offset)
+            if special == "z_to_m":
+                flags[k] |= _CONV_ZDIV
+    return conv, flags
+
+
+def _device_conv(conv: np.ndarray, flags: np.ndarray, device):
+    key = ("conv", conv.tobytes(), flags.tobytes(), str(device))
+    t = _JOB_CACHE.get(key)
+    if t is None:
+        t = (torch.from_numpy(conv).to(device), torch.from_numpy(flags).to(device))
+        _JOB_CACHE[key] = t
+    return t
+
+
+def _upload_i32(values, device) -> torch.Tensor:
+    arr = np.ascontiguousarray(np.asarray(values, dtype=np.int32))
+    key = ("i32", arr.tobytes(), str(device))
+    t = _JOB_CACHE.get(key)
+    if t is None:
+        t = torch.from_numpy(arr).to(device)
+        _JOB_CACHE[key] = t
+    return t
+
+
+def _need_gpu_f32(t, who: str):
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise ValueError(f"{who} needs a tensor on the GPU (there is no CPU path)")
+    if t.dtype != torch.float32:
+        raise ValueError(f"{who}: float32 expected, got {t.dtype}")
+
+
+def inverse_standardize(Y: torch.Tensor, y_mean: np.ndarray, y_scale: np.ndarray) -> torch.Tensor:
+    """`Y * y_scale + y_mean` over the last dimension of a float32 device tensor (`scripts/metrics_maps.py:40-44`),
+    the product and the sum each rounded to float32 (gcl_maps_convert)."""
+    _need_gpu_f32(Y, "inverse_standardize")
+    K = Y.shape[-1]
+    if np.size(y_mean) != K or np.size(y_scale) != K:
+        raise ValueError(f"y_mean / y_scale of {np.size(y_mean)} / {np.size(y_scale)} entries for {K} columns")
+    conv, flags = _device_conv(*_conv_rows(None, np.reshape(y_mean, -1), np.reshape(y_scale, -1), K), Y.device)
+    return hip.maps_convert(Y, conv, flags)
+
+
+def apply_units(arr: torch.Tensor, var_name: str):
+    """(arr in the physical units of `var_name`, label) (`scripts/metrics_maps.py:65-73`): a true division by g0 for
+    z@..., then `* factor + offset`, each rounded on its own, on a float32 device tensor (gcl_maps_convert; bit for bit
+    the reference's CPU result)."""
+    _need_gpu_f32(arr, "apply_units")
+    label = unit_label(var_name)[0]
+    conv, flags = _device_conv(*_conv_rows([var_name], None, None, 1), arr.device)
+    return hip.maps_convert(arr.reshape(-1, 1), conv, flags).view(arr.shape), label
+
+
+def _persistence_map(F: int, C: int, K: int, device) -> torch.Tensor:
+    return _upload_i32(F - C + np.arange(K) % C, device)
+
+
+class MetricMaps:
+    """RMSE / MAE / bias / ACC at every grid node, per channel and lead time, in physical units: the maps
+    `scripts/metrics_maps.py` draws (`compute_stat`, :75-90), accumulated batch by batch in a float64 device state
+    instead of stacking the test set on the host.
+
+    `update(y_true, y_pred)` takes device tensors [B, G, leads * C] (or [G, leads * C]); `y_pred` may be a
+    `Persistence`.  Every value is de-normalised (`y_mean` / `y_scale`, per channel or per column; None: standardised
+    units, the script without --denorm) and converted with `unit_label(var_order[c])` (None: as it is) in float32 exactly
+    as the reference does, differences and sums are float64, and `update` never synchronises, so it can be replayed
+    from a hipGraph (`CapturedMetricMaps`): the sample count is device state too.  Only the sums of the requested
+    `stats` are kept.  `rows` (grid indices, e.g. `region_node_indices`) restricts the maps - and the field statistics
+    of ACC - to those rows, in the order given.
+
+    `maps(stat)` -> float32 [leads, rows, C] on the device; `map(stat, channel, lead)` -> [rows]; `skill(reference)`
+    -> `1 - rmse / max(rmse_ref, 1e-9)` per element; `units`: the label of every channel; `n`: samples so far."""
+
+    def __init__(self, num_channels: int, num_nodes: int, leads: int = 1, stats: Sequence[str] = _MAP_STATS,
+                 var_order: Optional[Sequence[str]] = None, y_mean=None, y_scale=None, rows=None, device=None):
+        self.C, self.G, self.leads = int(num_channels), int(num_nodes), int(leads)
+        if self.C < 1 or self.G < 1 or self.leads < 1:
+            raise ValueError(f"MetricMaps needs positive sizes, got C={self.C}, nodes={self.G}, leads={self.leads}")
+        self.K = self.leads * self.C
+        stats = (stats,) if isinstance(stats, str) else tuple(stats)
+        for s in stats:
+            if s not in _MAP_STATS:
+                raise ValueError(f"unknown statistic {s!r}: one of {_MAP_STATS}")
+        if not stats:
+            raise ValueError("MetricMaps needs at least one statistic")
+        self.stats = tuple(dict.fromkeys(stats))
+        self._sums = 0
+        for s in self.stats:
+            self._sums |= _STAT_SUM[s]
+        self._plane = {s: bin(self._sums & (_STAT_SUM[s] - 1)).count("1") for s in self.stats}
+        if var_order is not None and len(var_order) != self.C:
+            raise ValueError(f"var_order names {len(var_order)} channels, the maps have {self.C}")
+        if (y_mean is None) != (y_scale is None):
+            raise ValueError("y_mean and y_scale go together")
+        if y_mean is not None:
+            y_mean, y_scale = np.reshape(np.asarray(y_mean), -1), np.reshape(np.asarray(y_scale), -1)
+            if y_mean.size != y_scale.size or y_mean.size not in (self.C, self.K):
+                raise ValueError(f"y_mean / y_scale of {y_mean.size} / {y_scale.size} entries: expected {self.C} "
+                                 f"(per channel) or {self.K} (per column)")
+            if y_mean.size == self.C:
+                y_mean, y_scale = np.tile(y_mean, self.leads), np.tile(y_scale, self.leads)
+        self.var_order = None if var_order is None else list(var_order)
+        self.units = [unit_label(v)[0] for v in self.var_order] if self.var_order is not None else [""] * self.C
+        self._conv_host = None
+        if var_order is not None or y_mean is not None:
+            names = None if self.var_order is None else self.var_order * self.leads
+            self._conv_host = _conv_rows(names, y_mean, y_scale, self.K)
+        self.rows = None
+        if rows is not None:
+            self.rows = np.asarray(rows, dtype=np.int64).reshape(-1)
+            if self.rows.size == 0 or self.rows.min() < 0 or self.rows.max() >= self.G:
+                raise ValueError(f"rows must be a non-empty list of grid indices below {self.G}")
+        self.num_rows = self.G if self.rows is None else int(self.rows.size)
+        self.device = None
+        self._state = self._count = self._conv = self._flags = self._rows_dev = None
+        self._scratch = {}
+        if device is not None:
+            self._ensure(torch.device(device))
+
+    # -- device state --------------------------------------------------------------------------------------------------
+    def _ensure(self, device):
+        if self.device is None:
+            if device.type != "cuda":
+                raise ValueError(f"MetricMaps lives on the GPU (there is no CPU path), got device {device}")
+            self.device = device
+            self._state = torch.zeros(self.leads, len(self._plane), self.num_rows * self.C, dtype=torch.float64,
+                                      device=device)
+            self._count = torch.zeros(1, dtype=torch.int64, device=device)
+            if self._conv_host is not None:
+                self._conv, self._flags = _device_conv(*self._conv_host, device)
+            if self.rows is not None:
+                self._rows_dev = _upload_i32(self.rows, device)
+        elif device != self.device:
+            raise ValueError(f"MetricMaps lives on {self.device}, got tensors on {device}")
+
+    def reset(self):
+        """Zero every sum and the sample count (in place: a captured update keeps pointing at them)."""
+        if self._state is not None:
+            self._state.zero_()
+            self._count.zero_()
+
+    @property
+    def n(self) -> int:
+        """Samples accumulated so far, read from the device."""
+        return 0 if self._count is None else int(self._count.item())
+
+    def _inputs(self, y_true, y_pred):
+        """(truth [B, G, K], prediction or window [B, G, W], column map or None), validated once."""
+        persist = isinstance(y_pred, Persistence)
+        src = y_pred.X if persist else y_pred
+        for name, t in (("y_true", y_true), ("y_pred", src)):
+            if not torch.is_tensor(t) or t.dim() not in (2, 3):
+                raise ValueError(f"MetricMaps.update: {name} must be a tensor [B, G, K] or [G, K], got "
+                                 f"{tuple(t.shape) if torch.is_tensor(t) else type(t).__name__}")
+        T3 = y_true if y_true.dim() == 3 else y_true.unsqueeze(0)
+        P3 = src if src.dim() == 3 else src.unsqueeze(0)
+        width_ok = (P3.shape[2] >= self.C and y_pred.C == self.C) if persist else P3.shape[2] == self.K
+        if T3.shape[1:] != (self.G, self.K) or P3.shape[:2] != T3.shape[:2] or not width_ok:
+            raise ValueError(f"MetricMaps.update: truth {tuple(y_true.shape)} and prediction {tuple(src.shape)}, "
+                             f"expected {self.G} rows of {self.leads} leads x {self.C} channels = {self.K} columns"
+                             + (f" (persistence window of {y_pred.C} channels)" if persist else ""))
+        if not (T3.is_cuda and P3.is_cuda):
+            raise ValueError("MetricMaps.update: y_true and y_pred must be on the GPU (there is no CPU path)")
+        T3, P3 = hip._rows_view(T3), hip._rows_view(P3)
+        return T3, P3, (_persistence_map(P3.shape[2], self.C, self.K, T3.device) if persist else None)
+
+    def _update3(self, T3, P3, cmap):
+        cs = None
+        if self._sums & hip.MAPS_SUM_PT:
+            B = T3.shape[0]
+            cs = self._scratch.get(B)
+            if cs is None:
+                cs = self._scratch[B] = torch.empty(B, self.K, 4, dtype=torch.float64, device=T3.device)
+            hip.maps_colstats(T3, P3, cmap, self._rows_dev, self._conv, self._flags, cs)
+        hip.maps_accumulate(T3, P3, cmap, self._rows_dev, self._conv, self._flags, cs, self._sums, self.C, self._state,
+                            self._count)
+
+    def update(self, y_true: torch.Tensor, y_pred):
+        """Add the B samples of y_true / y_pred [B, G, leads * C] (or one, [G, leads * C]) in order.  No host
+        synchronisation."""
+        T3, P3, cmap = self._inputs(y_true, y_pred)
+        self._ensure(T3.device)
+        self._update3(T3, P3, cmap)
+
+    # -- results -------------------------------------------------------------------------------------------------------
+    def _need(self, stat: str):
+        if stat not in _MAP_STATS:
+            raise ValueError(f"unknown statistic {stat!r}: one of {_MAP_STATS}")
+        if stat not in self._plane:
+            raise ValueError(f"statistic {stat!r} was not accumulated (stats={self.stats})")
+
+    def maps(self, stat: str) -> torch.Tensor:
+        """float32 [leads, rows, C]: the statistic at every scored node (zeros before the first update)."""
+        self._need(stat)
+        out = torch.zeros(self.leads, self.num_rows, self.C, dtype=torch.float32, device=self.device)
+        if self._state is not None:
+            hip.maps_finalize(self._state, self._count, self._plane[stat], _STAT_KIND[stat], out)
+        return out
+
+    def map(self, stat: str, channel: int, lead: int = 0) -> torch.Tensor:
+        """[rows]: one channel's field, the `stat_map` the script hands to `plot_field`."""
+        return self.maps(stat)[lead, :, channel]
+
+    def skill(self, reference_maps: "MetricMaps") -> torch.Tensor:
+        """float32 [leads, rows, C]: `1 - rmse / max(rmse_ref, 1e-9)` per element against another accumulator (e.g.
+        persistence), from the two float32 RMSE maps."""
+        self._need("rmse")
+        reference_maps._need("rmse")
+        if (reference_maps.leads, reference_maps.num_rows, reference_maps.C) != (self.leads, self.num_rows, self.C):
+            raise ValueError("skill: the two accumulators have different shapes")
+        if self._state is None or reference_maps._state is None:
+            raise ValueError("skill: both accumulators need at least one update")
+        out = torch.empty(self.leads, self.num_rows, self.C, dtype=torch.float32, device=self.device)
+        hip.maps_finalize(self._state, self._count, self._plane["rmse"], hip.MAPS_SKILL, out,
+                          ref_state=reference_maps._state, ref_count=reference_maps._count,
+                          ref_plane=reference_maps._plane["rmse"])
+        return out
+
+    @staticmethod
+    def to_grid(field, num_lon: int, num_lat: int) -> np.ndarray:
+        """The [lat, lon] array `plot_field` hands to imshow (`scripts/metrics_maps.py:94`) for a field [G] numbered
+        longitude-major.  Copies to the host; plotting itself is not provided."""
+        arr = field.detach().cpu().numpy() if torch.is_tensor(field) else np.asarray(field)
+        return arr.reshape(num_lon, num_lat).T
+
+
+class CapturedMetricMaps(MetricMaps, Captured):
+    """`MetricMaps` whose update (field statistics + accumulate) is replayed from a hipGraph (capture.Captured): the
+    first two updates of a shape run eagerly, the third captures, later ones copy their inputs into the captured
+    buffers and replay.  The sums and the sample count are device state, so a replay counts like an eager update and
+    gives the same bits.  Falls back to eager launches if capture is not possible (see `.launch_mode`)."""
+
+    def __init__(self, *args, use_graph: bool = True, **kw):
+        MetricMaps.__init__(self, *args, **kw)
+        Captured.__init__(self, use_graph=use_graph, recapture=True)
+        self._cmap, self._cmap_key = None, None
+
+    def _work(self, T3, P3):
+        MetricMaps._update3(self, T3, P3, self._cmap)
+
+    def _update3(self, T3, P3, cmap):
+        key = None if cmap is None else cmap.data_ptr()
+        if key != self._cmap_key:  # tensor prediction <-> persistence window: another set of launches
+            self.reset_graph()
+            self._cmap, self._cmap_key = cmap, key
+        self._run(T3, P3)
+
+
+def compute_stat(pred: torch.Tensor, true: torch.Tensor, stat: str) -> torch.Tensor:
+    """The one-shot form of `scripts/metrics_maps.py:75-90`: pred / true [N, G] device tensors already in physical
+    units -> the statistic at every node [G] (float32), through the kernels of `MetricMaps` (N samples of one
+    channel)."""
+    if stat not in _MAP_STATS:
+        raise ValueError(stat)
+    if pred.dim() != 2 or pred.shape != true.shape:
+        raise ValueError(f"compute_stat: pred {tuple(pred.shape)} and true {tuple(true.shape)}, expected two [N, G]")
+    mm = MetricMaps(1, pred.shape[1], stats=(stat,))
+    mm.update(true.unsqueeze(-1), pred.unsqueeze(-1))
+    return mm.maps(stat)[0, :, 0]
+
+
+def metric_maps(model, dataset, indices=None, ar_steps: int = 1, batch_size: int = 8, use_residual: bool = True,
+                static_channels=None, forcing_channels=None, persistence: bool = False, captured: bool = True,
+                **maps_kw):
+    """The evaluation loop of `scripts/metrics_maps.py:143-176` without its host side: for every batch of `indices`
+    (None: the whole data set) `dataset.batch(...)` -> `predict.rollout` over `ar_steps` (a `CapturedRollout` with
+    `captured`) -> `MetricMaps.update` against the first `ar_steps` steps of the truth.  `maps_kw` go to `MetricMaps`
+    (stats, var_order, y_mean, y_scale, rows); channels, nodes and leads come from the data.  Returns the accumulator,
+    or with `persistence` the pair (model, persistence) - the second fed by `Persistence` views of the input window.
+    Nothing crosses to the host before a map or `n` is read."""
+    from . import predict
+
+    idx = list(range(len(dataset))) if indices is None else [int(i) for i in indices]
+    if not idx:
+        raise ValueError("metric_maps: no samples to score")
+    if batch_size < 1 or ar_steps < 1:
+        raise ValueError(f"metric_maps: batch_size={batch_size}, ar_steps={ar_steps}")
+    cls = CapturedMetricMaps if captured else MetricMaps
+    roll = predict.CapturedRollout(model, ar_steps, static_channels=static_channels, forcing_channels=forcing_channels,
+                                   use_residual=use_residual) if captured else None
+    mm = base = None
+    with torch.no_grad():
+        for s in range(0, len(idx), batch_size):
+            X, Y = dataset.batch(idx[s:s + batch_size])
+            C = X.shape[-1] // model.obs_window
+            if mm is None:
+                if Y.shape[-1] < ar_steps * C:
+                    raise ValueError(f"metric_maps: the data set's truth covers {Y.shape[-1] // C} steps, "
+                                     f"ar_steps={ar_steps}")
+                mm = cls(C, X.shape[1], leads=ar_steps, **maps_kw)
+                base = cls(C, X.shape[1], leads=ar_steps, **maps_kw) if persistence else None
+            truth = Y[..., :ar_steps * C]
+            yf = Y if forcing_channels else None
+            if captured:
+                pred = roll(X, yf)
+            else:
+                pred = predict.rollout(model, X, ar_steps, y=yf, static_channels=static_channels,
+                                       forcing_channels=forcing_channels, use_residual=use_residual)
+            mm.update(truth, pred)
+            if base is not None:
+                base.update(truth, Persistence(X, C))
+    return (mm, base) if persistence else mm

@@ -714,6 +714,51 @@ int gcl_pipeline_sqerr(const float* preds, int64_t vs, int64_t ldp, int32_t V, c
                        const int32_t* stn, int32_t S, int32_t G, int32_t C, int32_t H, int32_t h, double* acc_grid,
                        double* acc_stn, gcl_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Per-grid-point error maps (csrc/maps.hip; scripts/metrics_maps.py).
+ * Shared arguments: truth[b * bst + r * ldt + k] and pred[b * bsp + r * ldp + pmap[k]] (pmap NULL: k)
+ * for the n scored rows r = rows[i] (rows NULL: r = i) and the columns k = lead * C + c.  Every value
+ * is converted to physical units on its own in float32, in the order of inverse_standardize
+ * (scripts/metrics_maps.py:40-44) and apply_units (:65-73), each operation rounded alone:
+ *   v = x * conv[4k];  v = v + conv[4k+1]   (flags[k] & 1)
+ *   v = v / 9.80665f                        (flags[k] & 2, true division)
+ *   v = v * conv[4k+2];  v = v + conv[4k+3]
+ * conv == NULL (then flags == NULL too): values are used as they are.
+ * ------------------------------------------------------------------------------------------- */
+/* Workspace of gcl_maps_colstats for n rows, K columns, B samples. */
+size_t gcl_maps_colstats_ws_bytes(int32_t n, int32_t K, int32_t B);
+/* The per-sample field statistics of compute_stat's ACC branch (scripts/metrics_maps.py:84-89,
+ * `pred.mean(dim=1)` / `pred.std(dim=1)`): cs[(b * K + k) * 4 + {0: mean_p, 1: std_p, 2: mean_t,
+ * 3: std_t}] over the n scored rows of the converted values, float64, std unbiased (n == 1: NaN, as
+ * torch.std).  Sums shifted by the column's first scored row; two kernels, fixed order, no atomics: a
+ * column's result depends only on its own data and n. */
+int gcl_maps_colstats(const float* truth, int64_t ldt, int64_t bst, const float* pred, int64_t ldp,
+                      int64_t bsp, const int32_t* pmap, int32_t K, const float* conv, const int32_t* flags,
+                      const int32_t* rows, int32_t n, int32_t B, double* cs, void* ws, size_t ws_bytes,
+                      gcl_stream_t stream);
+/* The sums behind compute_stat (scripts/metrics_maps.py:75-90), streamed: for every element (lead, i,
+ * c) the B samples are added in sample order into state[(lead * nsums + s) * n * C + i * C + c]
+ * (float64), s counting the set bits of `sums` in ascending order: 1 sum e, 2 sum e^2, 4 sum |e|,
+ * 8 sum p^ t^ with e = (double)vp - (double)vt, p^ = (vp - mean_p) / (std_p + 1e-8), t^ likewise (cs
+ * of gcl_maps_colstats, needed only with bit 8).  At most 2^31 - 1 elements (leads * n * C) per call.  *count (device) += B.  One thread owns an element:
+ * no atomics; 16-byte loads when rows are exactly K floats, unmapped and aligned. */
+int gcl_maps_accumulate(const float* truth, int64_t ldt, int64_t bst, const float* pred, int64_t ldp,
+                        int64_t bsp, const int32_t* pmap, int32_t leads, int32_t C, const float* conv,
+                        const int32_t* flags, const int32_t* rows, int32_t n, int32_t B, const double* cs,
+                        int32_t sums, double* state, int64_t* count, gcl_stream_t stream);
+/* State -> float32 map out[lead * nelem + e] from sum `plane` of `nsums` (scripts/metrics_maps.py:
+ * 78-89 with N = *count): kind 0 rmse = sqrt(S / N), 1 mae, 2 bias, 3 acc = S / N; N == 0 gives 0.
+ * kind 4: skill = 1 - rmse / max(rmse_ref, 1e-9) per element from the two float32 RMSE values (the
+ * clip of scripts/eval_real_freeze6.py:178-180), `plane` / `ref_plane` being the sum-e^2 planes. */
+int gcl_maps_finalize(const double* state, const int64_t* count, int32_t plane, int32_t nsums,
+                      int32_t leads, int64_t nelem, int32_t kind, const double* ref_state,
+                      const int64_t* ref_count, int32_t ref_plane, int32_t ref_nsums, float* out,
+                      gcl_stream_t stream);
+/* inverse_standardize / apply_units alone (scripts/metrics_maps.py:40-44, :65-73) on `total`
+ * contiguous values whose column is index % K: out = converted x (out may alias x). */
+int gcl_maps_convert(const float* x, float* out, int64_t total, int32_t K, const float* conv,
+                     const int32_t* flags, gcl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
