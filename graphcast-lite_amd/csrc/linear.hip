@@ -1064,10 +1064,16 @@ inline void launch_reduce_multi(const float* part, int nparts, int64_t pstride, 
                        pstride, s0, s1, s2, sp, ns, sout);
 }
 
-// Final pass of up to 16 fused backward calls in ONE launch (gcl_reduce_jobs): block -> (job, block of the job).
-// The scalar (PReLU slope) partials of ALL jobs are summed by the last block, job after job, so jobs that share a
-// slope parameter add to it in a fixed order.
-constexpr int kJobsPerLaunch = 16;
+// Final pass of up to 24 deferred calls in ONE launch (gcl_reduce_jobs): block -> (job, block of the job).
+// The scalar (PReLU slope) partials of ALL jobs are summed by one extra block: its four waves take a job each (and loop
+// when there are more), every wave forming its job's total exactly as one wave used to (stride 64 over the partials,
+// then the shuffle tree); the totals meet in LDS and ONE thread adds them to their destinations job after job, so jobs
+// that share a slope parameter still add to it in a fixed order.  The extra block is block 0, the first one dispatched:
+// what is left of its chain of memory latencies runs under the body blocks.  (As the LAST block, with one wave walking
+// the jobs one after the other, it set the duration of the whole launch: 71 us against 30 us without it,
+// tools/reduce_bench.py.)
+// 24 jobs of 144 bytes stay inside the 4 KB of kernel arguments.
+constexpr int kJobsPerLaunch = 24;
 struct RedJobK {
   const float* part;
   int64_t pstride;
@@ -1078,20 +1084,36 @@ struct RedJobK {
 };
 struct RedJobsK {
   RedJobK j[kJobsPerLaunch];
-  int32_t n, nblk;
+  int32_t n, sblk;  // sblk: 1 when block 0 is the scalar block (the body blocks follow it), else 0
 };
+static_assert(sizeof(RedJobsK) <= 4096, "the job table is passed by value: kernel arguments are limited to 4 KB");
 __global__ __launch_bounds__(256) void reduce_jobs_kernel(RedJobsK J) {
-  const int blk = blockIdx.x;
-  if (blk == J.nblk) {  // the extra block: scalar partials, in job order
-    if (threadIdx.x < 64) {
-      for (int q = 0; q < J.n; ++q) {
-        if (!J.j[q].spart) continue;
-        double t = 0.0;
-        for (int p = threadIdx.x; p < J.j[q].ns; p += 64) t += J.j[q].spart[p];
-        for (int off = 32; off > 0; off >>= 1) t += __shfl_down(t, off, 64);
-        if (threadIdx.x == 0) *J.j[q].sout += (float)t;
+  const int blk = (int)blockIdx.x - J.sblk;
+  if (blk < 0) {  // the extra block: scalar partials
+    __shared__ double tot[kJobsPerLaunch];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int q = wave; q < J.n; q += 4) {  // uniform per wave
+      if (!J.j[q].spart) continue;
+      // a lane's partials are LOADED twelve at a time (one memory latency for up to 768 of them, not one per partial:
+      // under the body blocks' traffic a dependent load takes over a microsecond) and added in the same order
+      const double* sp = J.j[q].spart;
+      const int ns = J.j[q].ns;
+      double t = 0.0;
+      for (int base = lane; base < ns; base += 64 * 12) {
+        double v[12];
+#pragma unroll
+        for (int k = 0; k < 12; ++k) v[k] = (base + 64 * k < ns) ? sp[base + 64 * k] : 0.0;
+#pragma unroll
+        for (int k = 0; k < 12; ++k)
+          if (base + 64 * k < ns) t += v[k];
       }
+      for (int off = 32; off > 0; off >>= 1) t += __shfl_down(t, off, 64);
+      if (lane == 0) tot[q] = t;
     }
+    __syncthreads();
+    if (threadIdx.x == 0)
+      for (int q = 0; q < J.n; ++q)  // in job order
+        if (J.j[q].spart) *J.j[q].sout += (float)tot[q];
     return;
   }
   int q = 0;
@@ -1407,7 +1429,7 @@ extern "C" int gcl_linear_bwd_dx(const float* dy, int64_t lddy, const float* W, 
 // chunks (dY is re-read once per chunk), then one partial reduction per chunk
 static int dw_block(const float* dy, int64_t lddy, const float* x, int64_t ldx, int akind, const float* in_slope,
                     float* dW, int64_t lddw, float* db, int64_t rows, int32_t Fin, int32_t Fout, int32_t accumulate,
-                    void* ws, hipStream_t st) {
+                    void* ws, hipStream_t st, gcl_reduce_job* job = nullptr) {
   const int nct = (Fin + 127) / 128;                      // input chunks
   const int NC = nct > 1 ? 4 : (Fin + 31) / 32;           // slabs of the (widest) chunk
   int NO = (Fout + 31) / 32;
@@ -1459,6 +1481,38 @@ static int dw_block(const float* dy, int64_t lddy, const float* x, int64_t ldx, 
 #undef GCL_DW2
 #undef GCL_DW3
   GCL_CHECK_LAUNCH();
+  // deferred (job[0]: the dW tiles, job[1]: db - they are two partial buffers): only when the immediate passes below
+  // are ONE launch for dW and both take the 16-byte reducer, which is the only one the queue has
+  const bool defer = job && nct <= 3 && nblk >= 64 && gcl::aligned16(part) && gcl::aligned16(dbpart) &&
+                     tile_stride % 4 == 0 && 2 * tile_stride < ((int64_t)1 << 31);
+  if (defer) {
+    job[0].part = part;
+    job[0].pstride = (int64_t)FoutP * FinP;
+    job[0].nparts = (int32_t)nblk;
+    for (int c = 0; c < nct; ++c) {
+      const int fi = Fin - c * 128 < 128 ? Fin - c * 128 : 128;
+      job[0].seg[c].out = dW + c * 128;
+      job[0].seg[c].poff = (int32_t)(c * tile_stride);
+      job[0].seg[c].count = Fout * FinP;
+      job[0].seg[c].pld = FinP;
+      job[0].seg[c].cols = fi;
+      job[0].seg[c].ldo = (int32_t)lddw;
+      job[0].seg[c].acc = accumulate ? 1 : 0;
+    }
+    if (db) {
+      job[1].part = dbpart;
+      job[1].pstride = FoutP;
+      job[1].nparts = (int32_t)nblk;
+      job[1].seg[0].out = db;
+      job[1].seg[0].poff = 0;
+      job[1].seg[0].count = FoutP;
+      job[1].seg[0].pld = FoutP;
+      job[1].seg[0].cols = Fout;
+      job[1].seg[0].ldo = Fout;
+      job[1].seg[0].acc = accumulate ? 1 : 0;
+    }
+    return GCL_OK;
+  }
   // final pass: the input chunks of a wide layer three to a launch (one segment each: chunk ct's records start
   // ct * tile_stride floats into the workspace) - a 256-wide layer used to end in two of these launches per call
   for (int ct = 0; ct < nct; ct += 3) {
@@ -1476,9 +1530,12 @@ static int dw_block(const float* dy, int64_t lddy, const float* x, int64_t ldx, 
   return GCL_OK;
 }
 
-extern "C" int gcl_dense_bwd_dw(const float* dy, int64_t lddy, const float* x, int64_t ldx, int32_t act,
-                                const float* slope, float* dW, int64_t lddw, float* db, int64_t rows, int32_t Fin,
-                                int32_t Fout, int32_t accumulate, void* ws, size_t ws_bytes, gcl_stream_t stream) {
+static int dense_bwd_dw_impl(const float* dy, int64_t lddy, const float* x, int64_t ldx, int32_t act,
+                             const float* slope, float* dW, int64_t lddw, float* db, int64_t rows, int32_t Fin,
+                             int32_t Fout, int32_t accumulate, void* ws, size_t ws_bytes, gcl_stream_t stream,
+                             gcl_reduce_job* job) {
+  if (job) memset(job, 0, 2 * sizeof(*job));
+  if (Fout > 256) job = nullptr;  // several launches share the workspace: each reduces on the spot
   GCL_CHECK_ARG(dy && x && dW, "dense_bwd_dw: null argument");
   GCL_CHECK_ARG(lddy >= Fout && ldx >= Fin && lddw >= Fin, "dense_bwd_dw: leading dimension too small");
   GCL_CHECK_ARG(Fin >= 1 && Fout >= 1, "dense_bwd_dw: bad shape");
@@ -1490,10 +1547,35 @@ extern "C" int gcl_dense_bwd_dw(const float* dy, int64_t lddy, const float* x, i
   for (int o0 = 0; o0 < Fout; o0 += 256) {
     const int fo = Fout - o0 < 256 ? Fout - o0 : 256;
     int rc = dw_block(dy + o0, lddy, x, ldx, act, sl, dW + (int64_t)o0 * lddw, lddw, db ? db + o0 : nullptr, rows, Fin,
-                      fo, accumulate, ws, (hipStream_t)stream);
+                      fo, accumulate, ws, (hipStream_t)stream, job);
     if (rc) return rc;
   }
   return GCL_OK;
+}
+
+extern "C" int gcl_dense_bwd_dw(const float* dy, int64_t lddy, const float* x, int64_t ldx, int32_t act,
+                                const float* slope, float* dW, int64_t lddw, float* db, int64_t rows, int32_t Fin,
+                                int32_t Fout, int32_t accumulate, void* ws, size_t ws_bytes, gcl_stream_t stream) {
+  return dense_bwd_dw_impl(dy, lddy, x, ldx, act, slope, dW, lddw, db, rows, Fin, Fout, accumulate, ws, ws_bytes, stream,
+                           nullptr);
+}
+
+extern "C" int gcl_dense_bwd_dw_deferred(const float* dy, int64_t lddy, const float* x, int64_t ldx, int32_t act,
+                                         const float* slope, float* dW, int64_t lddw, float* db, int64_t rows,
+                                         int32_t Fin, int32_t Fout, int32_t accumulate, void* ws, size_t ws_bytes,
+                                         gcl_stream_t stream, gcl_reduce_job* job) {
+  GCL_CHECK_ARG(job, "dense_bwd_dw_deferred: null job");
+  return dense_bwd_dw_impl(dy, lddy, x, ldx, act, slope, dW, lddw, db, rows, Fin, Fout, accumulate, ws, ws_bytes, stream,
+                           job);
+}
+
+extern "C" int gcl_linear_bwd_dw_deferred(const float* dy, int64_t lddy, const float* x, int64_t ldx,
+                                          const float* in_slope, float* dW, float* db, int64_t rows, int32_t Fin,
+                                          int32_t Fout, int32_t accumulate, void* ws, size_t ws_bytes,
+                                          gcl_stream_t stream, gcl_reduce_job* job) {
+  GCL_CHECK_ARG(job, "linear_bwd_dw_deferred: null job");
+  return dense_bwd_dw_impl(dy, lddy, x, ldx, in_slope ? GCL_ACT_PRELU : GCL_ACT_NONE, in_slope, dW, Fin, db, rows, Fin, Fout,
+                           accumulate, ws, ws_bytes, stream, job);
 }
 
 extern "C" int gcl_linear_bwd_dw(const float* dy, int64_t lddy, const float* x, int64_t ldx, const float* in_slope,
@@ -1658,8 +1740,8 @@ extern "C" int gcl_linear_bwd_all_deferred(const float* dy, int64_t lddy, const 
 extern "C" int gcl_reduce_jobs(const gcl_reduce_job* jobs, int32_t n, gcl_stream_t stream) {
   GCL_CHECK_ARG(n >= 0 && (jobs || n == 0), "reduce_jobs: null argument");
   hipStream_t st = (hipStream_t)stream;
-  // the running index is carried ACROSS launches: skipped (empty) jobs do not count towards the 16 of a launch, so
-  // restarting at base + 16 would reduce the jobs behind a skipped one twice
+  // the running index is carried ACROSS launches: skipped (empty) jobs do not count towards the 24 of a launch, so
+  // restarting at base + 24 would reduce the jobs behind a skipped one twice
   for (int32_t q = 0; q < n;) {
     RedJobsK J;
     memset(&J, 0, sizeof(J));
@@ -1692,7 +1774,7 @@ extern "C" int gcl_reduce_jobs(const gcl_reduce_job* jobs, int32_t n, gcl_stream
     }
     if (cnt == 0) continue;
     J.n = cnt;
-    J.nblk = nb;
+    J.sblk = any_slope ? 1 : 0;
     hipLaunchKernelGGL(reduce_jobs_kernel, dim3((unsigned)nb + (any_slope ? 1u : 0u)), dim3(256), 0, st, J);
     GCL_CHECK_LAUNCH();
   }

@@ -138,6 +138,25 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ X
   }
 }
 
+// the arithmetic, the store and the partial sums of one row: ONE text for the single-trip and the batched body, so
+// both add the same terms in the same order
+#define LN_BWD_ROW(ROW_, MEAN_, RSTD_, X0_, X1_, X2_, X3_, Y0_, Y1_, Y2_, Y3_) \
+  do { \
+      const float h0 = (c0 < F) ? (X0_ - MEAN_) * RSTD_ : 0.f, h1 = (c0 + 1 < F) ? (X1_ - MEAN_) * RSTD_ : 0.f; \
+      const float h2 = (c0 + 2 < F) ? (X2_ - MEAN_) * RSTD_ : 0.f, h3 = (c0 + 3 < F) ? (X3_ - MEAN_) * RSTD_ : 0.f; \
+      const float q0 = Y0_ * g0, q1 = Y1_ * g1, q2 = Y2_ * g2, q3 = Y3_ * g3; \
+      const float m1 = group_sum<LPR>(q0 + q1 + q2 + q3) * invF; \
+      const float m2 = group_sum<LPR>(q0 * h0 + q1 * h1 + q2 * h2 + q3 * h3) * invF; \
+      const float o0 = RSTD_ * (q0 - m1 - h0 * m2), o1 = RSTD_ * (q1 - m1 - h1 * m2), o2 = RSTD_ * (q2 - m1 - h2 * m2), \
+                  o3 = RSTD_ * (q3 - m1 - h3 * m2); \
+      if (c0 < F) store4(dX + (ROW_) * lddx + c0, c0, F, vdx, o0, o1, o2, o3); \
+      if (CS) { \
+        cs0 += (c0 < F) ? o0 : 0.f; cs1 += (c0 + 1 < F) ? o1 : 0.f; cs2 += (c0 + 2 < F) ? o2 : 0.f; cs3 += (c0 + 3 < F) ? o3 : 0.f; \
+      } \
+      dg0 += Y0_ * h0; dg1 += Y1_ * h1; dg2 += Y2_ * h2; dg3 += Y3_ * h3; \
+      db0 += Y0_; db1 += Y1_; db2 += Y2_; db3 += Y3_; \
+  } while (0)
+
 // dx = rstd * (g - mean(g) - xhat * mean(g*xhat)),  g = dy*gamma;  partial dgamma/dbeta per block
 // CS: also the column sums of dX (the bias gradient of the layer below: dX is that layer's dY) as a third vector
 // MAP: dY is given through a row map instead of densely - row (b, i) of the [B][n] row space reads
@@ -147,7 +166,14 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ X
 // ln_fwd_kernel LIST), no store of its dx (exactly zero; the consumer takes the zero from the map: gcl_aggregate_present).
 // Such a row adds exact zeros to every partial sum when it is computed, so leaving it out changes no sum; the rows keep
 // their places (row -> block, lane group, trip), so the partial sums add the same terms in the same order.
-template <int LPR, bool V, bool CS, bool MAP, bool SKIP = false>
+// BATCH (with SKIP): kLnBwdBatch consecutive trips of a lane group are served together - first their map entries, then
+// the loads of the present ones (x, dY and the statistics as one 8-byte load), then the arithmetic and the stores in
+// trip order.  The single-trip body pays two dependent load latencies per trip (map entry, then the rows) with nothing
+// in flight across trips; here a lane group has up to 3 * kLnBwdBatch loads outstanding.  Rows keep their places and
+// every lane adds its terms in the same order, so the partial records are bit-equal to the single-trip kernel's.  The
+// trips left over at the end (fewer than kLnBwdBatch) take the single-trip body.
+constexpr int kLnBwdBatch = 4;
+template <int LPR, bool V, bool CS, bool MAP, bool SKIP = false, bool BATCH = false>
 __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ dY, int64_t lddy,
                                                      const float* __restrict__ X, int64_t ldx,
                                                      const float* __restrict__ gamma, const float* __restrict__ stats,
@@ -177,7 +203,45 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ d
     msb = row_step / n_per;
     msi = (int)(row_step - msb * n_per);
   }
-  for (int64_t row = row_first; row < rows; row += row_step) {
+  int64_t row = row_first;
+  if (SKIP && BATCH) {
+    constexpr int U = kLnBwdBatch;
+    for (; row + (U - 1) * row_step < rows; row += U * row_step) {
+      int pj[U];
+      int64_t mbr[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        pj[u] = pos[mi];
+        mbr[u] = mb;
+        mi += msi;
+        mb += msb;
+        if (mi >= n_per) { mi -= n_per; ++mb; }
+      }
+      float bx[U][4], by[U][4];
+      float2 st[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        bx[u][0] = bx[u][1] = bx[u][2] = bx[u][3] = 0.f;
+        by[u][0] = by[u][1] = by[u][2] = by[u][3] = 0.f;
+        st[u] = make_float2(0.f, 0.f);
+        if (pj[u] >= 0) {  // all lanes of the row's group together
+          const int64_t r = row + u * row_step;
+          if (c0 < F) {
+            load4_row<V>(X + r * ldx + c0, c0, F, vx, bx[u][0], bx[u][1], bx[u][2], bx[u][3]);
+            load4_row<V>(dY + mbr[u] * bsdy + (int64_t)pj[u] * lddy + c0, c0, F, vdy, by[u][0], by[u][1], by[u][2], by[u][3]);
+          }
+          st[u] = *reinterpret_cast<const float2*>(stats + 2 * r);  // (mean, rstd): the caller checked the alignment
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        if (pj[u] < 0) continue;
+        LN_BWD_ROW(row + u * row_step, st[u].x, st[u].y, bx[u][0], bx[u][1], bx[u][2], bx[u][3], by[u][0], by[u][1], by[u][2],
+                   by[u][3]);
+      }
+    }
+  }
+  for (; row < rows; row += row_step) {
     float x0 = 0, x1 = 0, x2 = 0, x3 = 0, y0 = 0, y1 = 0, y2 = 0, y3 = 0;
     if (SKIP) {
       const int pj = pos[mi];
@@ -207,19 +271,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ d
       if (mi >= n_per) { mi -= n_per; ++mb; }
     }
     const float mean = stats[2 * row], rstd = stats[2 * row + 1];
-    const float h0 = (c0 < F) ? (x0 - mean) * rstd : 0.f, h1 = (c0 + 1 < F) ? (x1 - mean) * rstd : 0.f;
-    const float h2 = (c0 + 2 < F) ? (x2 - mean) * rstd : 0.f, h3 = (c0 + 3 < F) ? (x3 - mean) * rstd : 0.f;
-    const float q0 = y0 * g0, q1 = y1 * g1, q2 = y2 * g2, q3 = y3 * g3;
-    const float m1 = group_sum<LPR>(q0 + q1 + q2 + q3) * invF;
-    const float m2 = group_sum<LPR>(q0 * h0 + q1 * h1 + q2 * h2 + q3 * h3) * invF;
-    const float o0 = rstd * (q0 - m1 - h0 * m2), o1 = rstd * (q1 - m1 - h1 * m2), o2 = rstd * (q2 - m1 - h2 * m2),
-                o3 = rstd * (q3 - m1 - h3 * m2);
-    if (c0 < F) store4(dX + row * lddx + c0, c0, F, vdx, o0, o1, o2, o3);
-    if (CS) {
-      cs0 += (c0 < F) ? o0 : 0.f; cs1 += (c0 + 1 < F) ? o1 : 0.f; cs2 += (c0 + 2 < F) ? o2 : 0.f; cs3 += (c0 + 3 < F) ? o3 : 0.f;
-    }
-    dg0 += y0 * h0; dg1 += y1 * h1; dg2 += y2 * h2; dg3 += y3 * h3;
-    db0 += y0; db1 += y1; db2 += y2; db3 += y3;
+    LN_BWD_ROW(row, mean, rstd, x0, x1, x2, x3, y0, y1, y2, y3);
   }
   // reduce the RPB row groups of this block -> part[block][2*FP]  (dgamma | dbeta)
   const int g = wave * RPW + sub;
@@ -292,6 +344,20 @@ inline int lpr_for(int F) {
 }
 inline bool vec_ok(const float* p, int64_t ld, int F) { return (ld % 4 == 0) && gcl::aligned16(p) && ld >= ((F + 3) / 4) * 4; }
 inline bool vec_store_ok(const float* p, int64_t ld, int F) { return (ld % 4 == 0) && gcl::aligned16(p) && (F % 4 == 0); }
+
+// Deferred final pass (gcl_reduce_jobs): only what the immediate pass would give to the 16-byte reducer is deferred -
+// the queue has no other - so a deferred call adds the same records in the same order as an immediate one.
+inline bool reduce_job_ok(const float* part, int nparts) { return nparts >= 64 && gcl::aligned16(part); }
+// one vector of `pld` (padded) floats per record, `cols` of them valid
+inline void set_seg(gcl_reduce_job* job, int q, float* out, int poff, int pld, int cols, int acc) {
+  job->seg[q].out = out;
+  job->seg[q].poff = poff;
+  job->seg[q].count = pld;
+  job->seg[q].pld = pld;
+  job->seg[q].cols = cols;
+  job->seg[q].ldo = cols;
+  job->seg[q].acc = acc;
+}
 
 }  // namespace
 
@@ -397,7 +463,9 @@ extern "C" int gcl_layernorm_bwd_cs(const float* dy, int64_t lddy, const float* 
 static int layernorm_bwd_impl(const float* dy, int64_t lddy, int64_t bsdy, const int32_t* pos, int32_t n_per,
                               const float* x, int64_t ldx, const float* gamma, const float* stats, float* dx,
                               int64_t lddx, float* dgamma, float* dbeta, float* colsum_dx, int32_t accumulate,
-                              int64_t rows, int32_t F, void* ws, size_t ws_bytes, gcl_stream_t stream, bool skip) {
+                              int64_t rows, int32_t F, void* ws, size_t ws_bytes, gcl_stream_t stream, bool skip,
+                              gcl_reduce_job* job = nullptr) {
+  if (job) memset(job, 0, sizeof(*job));
   GCL_CHECK_ARG(dy && x && gamma && stats && dx && dgamma && dbeta, "layernorm_bwd: null argument");
   GCL_CHECK_ARG(!pos || (n_per > 0 && rows % n_per == 0), "layernorm_bwd: mapped dy needs rows = B * n_per");
   GCL_CHECK_ARG(F >= 1 && F <= 256 && ldx >= F && lddy >= F && lddx >= F, "layernorm_bwd: bad shape F=%d", F);
@@ -413,12 +481,17 @@ static int layernorm_bwd_impl(const float* dy, int64_t lddy, int64_t bsdy, const
   const int vdy = vec_ok(dy, lddy, F) && (bsdy % 4 == 0), vx = vec_ok(x, ldx, F), vdx = vec_store_ok(dx, lddx, F);
   // dgamma / dbeta share GCL_ACC_DW, the column sums have their own bit (they belong to another parameter)
   const int acc_p = (accumulate & GCL_ACC_DW) ? 1 : 0, acc_cs = (accumulate & GCL_ACC_COLSUM) ? 1 : 0;
+  // GCL_LN_BWD_BATCH=0: the single-trip kernel for the mapped + skip case too (read per call: the tests compare the two)
+  const bool batch = skip && gcl::env_int("GCL_LN_BWD_BATCH", 1) != 0 && ((uintptr_t)stats % 8 == 0);
 #define CALL4(L, V_, CS_, MAP_)                                                                                       \
   hipLaunchKernelGGL((ln_bwd_kernel<L, V_, CS_, MAP_>), dim3((unsigned)nb), dim3(256), 0, st, dy, lddy, x, ldx, gamma, \
                      stats, dx, lddx, part, rows, F, FP, vdy, vx, vdx, pos, bsdy, n_per)
 #define CALL3(L, V_, CS_)                                                                                              \
   do {                                                                                                                 \
-    if (skip)                                                                                                          \
+    if (skip && batch)                                                                                                 \
+      hipLaunchKernelGGL((ln_bwd_kernel<L, V_, CS_, true, true, true>), dim3((unsigned)nb), dim3(256), 0, st, dy, lddy, x, \
+                         ldx, gamma, stats, dx, lddx, part, rows, F, FP, vdy, vx, vdx, pos, bsdy, n_per);              \
+    else if (skip)                                                                                                     \
       hipLaunchKernelGGL((ln_bwd_kernel<L, V_, CS_, true, true>), dim3((unsigned)nb), dim3(256), 0, st, dy, lddy, x, ldx, \
                          gamma, stats, dx, lddx, part, rows, F, FP, vdy, vx, vdx, pos, bsdy, n_per);                   \
     else if (pos) CALL4(L, V_, CS_, true);                                                                             \
@@ -437,6 +510,16 @@ static int layernorm_bwd_impl(const float* dy, int64_t lddy, int64_t bsdy, const
 #undef CALL3
 #undef CALL4
   GCL_CHECK_LAUNCH();
+  if (job && reduce_job_ok(part, (int)nb)) {
+    // deferred: describe the final pass (dgamma | dbeta | colsum dX, FP floats each) instead of launching it
+    job->part = part;
+    job->pstride = (colsum_dx ? 3 : 2) * FP;
+    job->nparts = (int32_t)nb;
+    set_seg(job, 0, dgamma, 0, FP, F, acc_p);
+    set_seg(job, 1, dbeta, FP, FP, F, acc_p);
+    if (colsum_dx) set_seg(job, 2, colsum_dx, 2 * FP, FP, F, acc_cs);
+    return GCL_OK;
+  }
   if (!colsum_dx) return gcl::launch_reduce_parts2(part, (int)nb, 2 * FP, FP, FP, dgamma, dbeta, F, acc_p, st);
   return gcl::launch_reduce_parts3(part, (int)nb, 3 * FP, FP, dgamma, acc_p, dbeta, acc_p, colsum_dx, acc_cs, F, st);
 }
@@ -459,6 +542,17 @@ extern "C" int gcl_layernorm_bwd_map_skip(const float* dy, int64_t lddy, int64_t
                             rows, F, ws, ws_bytes, stream, true);
 }
 
+extern "C" int gcl_layernorm_bwd_deferred(const float* dy, int64_t lddy, int64_t bsdy, const int32_t* pos, int32_t n_per,
+                                          int32_t skip, const float* x, int64_t ldx, const float* gamma,
+                                          const float* stats, float* dx, int64_t lddx, float* dgamma, float* dbeta,
+                                          float* colsum_dx, int32_t accumulate, int64_t rows, int32_t F, void* ws,
+                                          size_t ws_bytes, gcl_stream_t stream, gcl_reduce_job* job) {
+  GCL_CHECK_ARG(job, "layernorm_bwd_deferred: null job");
+  GCL_CHECK_ARG(pos || !skip, "layernorm_bwd_deferred: skip needs the row map");
+  return layernorm_bwd_impl(dy, lddy, pos ? bsdy : 0, pos, pos ? n_per : 0, x, ldx, gamma, stats, dx, lddx, dgamma, dbeta,
+                            colsum_dx, accumulate, rows, F, ws, ws_bytes, stream, skip != 0, job);
+}
+
 extern "C" int gcl_layernorm_bwd(const float* dy, int64_t lddy, const float* x, int64_t ldx, const float* gamma,
                                  const float* stats, float* dx, int64_t lddx, float* dgamma, float* dbeta,
                                  int32_t accumulate, int64_t rows, int32_t F, void* ws, size_t ws_bytes,
@@ -472,8 +566,9 @@ extern "C" size_t gcl_colsum_ws_bytes(int64_t rows, int32_t F) {
   return (size_t)kNormBlocks * (size_t)(((F + 3) / 4) * 4) * sizeof(float);
 }
 
-extern "C" int gcl_colsum(const float* x, int64_t ldx, int64_t rows, int32_t F, float* out, int32_t accumulate,
-                          void* ws, size_t ws_bytes, gcl_stream_t stream) {
+static int colsum_impl(const float* x, int64_t ldx, int64_t rows, int32_t F, float* out, int32_t accumulate, void* ws,
+                       size_t ws_bytes, gcl_stream_t stream, gcl_reduce_job* job) {
+  if (job) memset(job, 0, sizeof(*job));
   GCL_CHECK_ARG(x && out, "colsum: null argument");
   GCL_CHECK_ARG(F >= 1 && F <= 256 && ldx >= F, "colsum: bad shape F=%d", F);
   GCL_CHECK_ARG(ws && ws_bytes >= gcl_colsum_ws_bytes(rows, F), "colsum: workspace too small");
@@ -491,5 +586,23 @@ extern "C" int gcl_colsum(const float* x, int64_t ldx, int64_t rows, int32_t F, 
   GCL_DISPATCH_LPR(lpr, CALL)
 #undef CALL
   GCL_CHECK_LAUNCH();
+  if (job && reduce_job_ok(part, (int)nb)) {
+    job->part = part;
+    job->pstride = FP;
+    job->nparts = (int32_t)nb;
+    set_seg(job, 0, out, 0, FP, F, accumulate ? 1 : 0);
+    return GCL_OK;
+  }
   return gcl::launch_reduce_parts(part, (int)nb, FP, FP, out, F, 1, F, accumulate, st);
+}
+
+extern "C" int gcl_colsum(const float* x, int64_t ldx, int64_t rows, int32_t F, float* out, int32_t accumulate,
+                          void* ws, size_t ws_bytes, gcl_stream_t stream) {
+  return colsum_impl(x, ldx, rows, F, out, accumulate, ws, ws_bytes, stream, nullptr);
+}
+
+extern "C" int gcl_colsum_deferred(const float* x, int64_t ldx, int64_t rows, int32_t F, float* out, int32_t accumulate,
+                                   void* ws, size_t ws_bytes, gcl_stream_t stream, gcl_reduce_job* job) {
+  GCL_CHECK_ARG(job, "colsum_deferred: null job");
+  return colsum_impl(x, ldx, rows, F, out, accumulate, ws, ws_bytes, stream, job);
 }

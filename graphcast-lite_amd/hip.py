@@ -42,6 +42,13 @@ _SIGNATURES = {
     "gcl_linear_bwd_all_deferred": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i32,
                                               _i32, _i32, _vp, _sz, _vp, _vp]),
     "gcl_reduce_jobs": (C.c_int, [_vp, _i32, _vp]),
+    "gcl_layernorm_bwd_deferred": (C.c_int, [_vp, _i64, _i64, _vp, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp,
+                                             _i32, _i64, _i32, _vp, _sz, _vp, _vp]),
+    "gcl_colsum_deferred": (C.c_int, [_vp, _i64, _i64, _i32, _vp, _i32, _vp, _sz, _vp, _vp]),
+    "gcl_linear_bwd_dw_deferred": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _sz, _vp,
+                                             _vp]),
+    "gcl_dense_bwd_dw_deferred": (C.c_int, [_vp, _i64, _vp, _i64, _i32, _vp, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _vp,
+                                            C.c_size_t, _vp, _vp]),
     "gcl_linear_bwd_all_ws_bytes": (_sz, [_i64, _i32, _i32]),
     "gcl_aggregate": (C.c_int, [_vp, _i32, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i32, _i32, _vp]),
     "gcl_aggregate_present": (C.c_int, [_vp, _i32, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _vp]),
@@ -398,6 +405,11 @@ def dense_bwd_dw(dy, x, dW, db, accumulate: bool, act=ACT_NONE, slope=None):
                 db.zero_()
         return
     nb = lib().gcl_linear_bwd_ws_bytes(rows, Fin, Fout)
+    if _deferred.active:
+        _queue(nb, dy.device, (dW, db), 2, lambda ws, jobs: lib().gcl_dense_bwd_dw_deferred(
+            _p(dy), _ld(dy), _p(x), _ld(x), int(act), _p(slope), _p(dW), dW.stride(0), _p(db), rows, Fin, Fout,
+            1 if accumulate else 0, ws.data_ptr(), ws.numel(), _stream(), C.cast(jobs, C.c_void_p)))
+        return
     ws = workspace(nb, dy.device)
     _check(lib().gcl_dense_bwd_dw(_p(dy), _ld(dy), _p(x), _ld(x), int(act), _p(slope), _p(dW), dW.stride(0), _p(db), rows,
                                   Fin, Fout, 1 if accumulate else 0, ws.data_ptr(), ws.numel(), _stream()))
@@ -418,8 +430,9 @@ class ReduceJob(C.Structure):
 
 
 class _Deferred:
-    """Pending final passes of the fused dense backward (gcl_linear_bwd_all_deferred): a training step opens the
-    queue before its backward and flushes it once afterwards - one launch per 16 layers instead of one per layer.
+    """Pending final passes of the calls that end in a sum over per-block partial records (the fused dense backward, the
+    dW kernel, the LayerNorm backward, the column sums: gcl_*_deferred): a training step opens the queue before its
+    backward and flushes it once afterwards - one launch per 24 calls instead of one per call.
     Every pending call owns a workspace from a pool that persists across steps (a replayed hipGraph keeps using it)."""
 
     def __init__(self):
@@ -464,6 +477,31 @@ def defer_flush(close: bool = True, drop: bool = False):
         d.jobs, d.dests, d.used, d.keep = [], set(), 0, []
         if close:
             d.active = False
+
+
+def _queue(nbytes, device, dests, njobs, call):
+    """Make one deferred call with the queue open: `call(ws, jobs)` runs the main kernel with a workspace of the pool
+    (not the shared scratch buffer, which the next call overwrites) and fills `jobs`; what it left to do is queued.
+    Two pending passes must not write the same destination (a layer that runs twice in one backward, e.g. an
+    autoregressive rollout): what is queued is flushed first."""
+    d = _deferred
+    ptrs = {t.data_ptr() for t in dests if t is not None}
+    if ptrs & d.dests:
+        defer_flush(close=False)
+    ws = d.ws(nbytes, device)
+    jobs = (ReduceJob * njobs)()
+    try:
+        _check(call(ws, jobs))
+    except BaseException:
+        d.used -= 1
+        raise
+    pending = [j for j in jobs if j.nparts > 0]
+    if pending:
+        d.jobs.extend(pending)
+        d.dests |= ptrs
+        d.keep.append(tuple(dests) + (ws, jobs))
+    else:
+        d.used -= 1  # reduced on the spot: the workspace slot is free again
 
 
 def linear_bwd_all(dy, W, x, in_slope, d_in_slope, dW, db, colsum_dx, acc_dW: bool, acc_db=None, acc_colsum=None,
@@ -585,18 +623,29 @@ def layernorm_bwd(dy, x, gamma, stats, dgamma, dbeta, accumulate: bool, colsum_d
     rows, F = x.shape
     dx = torch.empty(rows, F, dtype=torch.float32, device=x.device)
     nb = lib().gcl_layernorm_bwd_ws_bytes(rows, F)
-    ws = workspace(nb, x.device)
     acc = (ACC_DW if accumulate else 0) | (ACC_COLSUM if acc_colsum else 0)
     if dy_map is not None:
         src3, pos = dy_map
         assert src3.stride(2) == 1 and src3.shape[2] >= F and rows % pos.numel() == 0 and src3.shape[0] == rows // pos.numel()
+    else:
+        assert not skip, "skip needs the mapped gradient"
+    if _deferred.active:
+        if dy_map is not None:
+            a = (_p(src3), src3.stride(1), src3.stride(0), _pi(pos), pos.numel(), 1 if skip else 0)
+        else:
+            a = (_p(dy), _ld(dy), 0, None, 0, 0)
+        _queue(nb, x.device, (dgamma, dbeta, colsum_dx), 1, lambda ws, jobs: lib().gcl_layernorm_bwd_deferred(
+            *a, _p(x), _ld(x), _p(gamma), _p(stats), _p(dx), F, _p(dgamma), _p(dbeta), _p(colsum_dx), acc, rows, F,
+            ws.data_ptr(), ws.numel(), _stream(), C.cast(jobs, C.c_void_p)))
+        return dx
+    ws = workspace(nb, x.device)
+    if dy_map is not None:
         # skip: rows with pos < 0 are not touched - their x / statistics are not read, their dx (zero) is not written
         fn = lib().gcl_layernorm_bwd_map_skip if skip else lib().gcl_layernorm_bwd_map
         _check(fn(_p(src3), src3.stride(1), src3.stride(0), _pi(pos), pos.numel(), _p(x), _ld(x),
                                            _p(gamma), _p(stats), _p(dx), F, _p(dgamma), _p(dbeta), _p(colsum_dx), acc, rows, F,
                                            ws.data_ptr(), ws.numel(), _stream()))
         return dx
-    assert not skip, "skip needs the mapped gradient"
     _check(lib().gcl_layernorm_bwd_cs(_p(dy), _ld(dy), _p(x), _ld(x), _p(gamma), _p(stats), _p(dx), F, _p(dgamma),
                                       _p(dbeta), _p(colsum_dx), acc, rows, F, ws.data_ptr(), ws.numel(), _stream()))
     return dx
@@ -627,6 +676,11 @@ def graphnorm_bwd(dy3, x3, gamma, stats, dgamma, dbeta, accumulate: bool, eps=1e
 def colsum(x, out, accumulate: bool):
     rows, F = x.shape
     nb = lib().gcl_colsum_ws_bytes(rows, F)
+    if _deferred.active:
+        _queue(nb, x.device, (out,), 1, lambda ws, jobs: lib().gcl_colsum_deferred(
+            _p(x), _ld(x), rows, F, _p(out), 1 if accumulate else 0, ws.data_ptr(), ws.numel(), _stream(),
+            C.cast(jobs, C.c_void_p)))
+        return out
     ws = workspace(nb, x.device)
     _check(lib().gcl_colsum(_p(x), _ld(x), rows, F, _p(out), 1 if accumulate else 0, ws.data_ptr(), ws.numel(), _stream()))
     return out

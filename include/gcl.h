@@ -132,7 +132,7 @@ size_t gcl_linear_bwd_all_ws_bytes(int64_t rows, int32_t Fin, int32_t Fout);
 /* Deferred final pass.  A training step calls gcl_linear_bwd_all once per layer, and each call ends in a small launch
  * that sums its per-block partial records into dW / db / colsum_dx / the slope gradient.  The _deferred form runs the
  * main kernel only and DESCRIBES that pass in *job; gcl_reduce_jobs later runs the passes of many calls in one launch
- * per 16 jobs (the gradients of one optimiser step, src/train.py:232-233, are only read after the whole backward).
+ * per 24 jobs (the gradients of one optimiser step, src/train.py:232-233, are only read after the whole backward).
  * Rules: every deferred call needs its OWN workspace, alive until gcl_reduce_jobs has run; two pending jobs must not
  * write the same dW / db / colsum_dx (flush first; a shared slope gradient is fine: slopes are summed job after job);
  * job->nparts == 0 means the call took the non-fused path and has already reduced on the spot. */
@@ -153,6 +153,26 @@ int gcl_linear_bwd_all_deferred(const float* dy, int64_t lddy, const float* W, c
                                 int32_t accumulate, void* ws, size_t ws_bytes, gcl_stream_t stream,
                                 gcl_reduce_job* job);
 int gcl_reduce_jobs(const gcl_reduce_job* jobs, int32_t n, gcl_stream_t stream);
+/* Deferred forms of the other calls that end in such a pass, under the same rules (declared here because they share
+ * gcl_reduce_job; the calls themselves are described further down).  Each behaves as its immediate form up to the final
+ * pass and fills *job; a call whose immediate pass would not take the 16-byte reducer (fewer than 64 partial records)
+ * reduces on the spot and leaves nparts == 0.  The dW forms fill job[0] (dW) and job[1] (db; nparts == 0 without db):
+ * `job` must have room for two.
+ * gcl_layernorm_bwd_deferred covers gcl_layernorm_bwd / _cs (pos NULL), _map (skip 0) and _map_skip (skip 1). */
+int gcl_layernorm_bwd_deferred(const float* dy, int64_t lddy, int64_t bsdy, const int32_t* pos, int32_t n_per,
+                               int32_t skip, const float* x, int64_t ldx, const float* gamma, const float* stats,
+                               float* dx, int64_t lddx, float* dgamma, float* dbeta, float* colsum_dx,
+                               int32_t accumulate, int64_t rows, int32_t F, void* ws, size_t ws_bytes,
+                               gcl_stream_t stream, gcl_reduce_job* job);
+int gcl_colsum_deferred(const float* x, int64_t ldx, int64_t rows, int32_t F, float* out, int32_t accumulate, void* ws,
+                        size_t ws_bytes, gcl_stream_t stream, gcl_reduce_job* job);
+int gcl_linear_bwd_dw_deferred(const float* dy, int64_t lddy, const float* x, int64_t ldx, const float* in_slope,
+                               float* dW, float* db, int64_t rows, int32_t Fin, int32_t Fout, int32_t accumulate,
+                               void* ws, size_t ws_bytes, gcl_stream_t stream, gcl_reduce_job* job /* [2] */);
+int gcl_dense_bwd_dw_deferred(const float* dy, int64_t lddy, const float* x, int64_t ldx, int32_t act,
+                              const float* slope, float* dW, int64_t lddw, float* db, int64_t rows, int32_t Fin,
+                              int32_t Fout, int32_t accumulate, void* ws, size_t ws_bytes, gcl_stream_t stream,
+                              gcl_reduce_job* job /* [2] */);
 
 /* General form of the three calls above, for wide layers and fused operands (the InteractionNet
  * processor, src/models.py:185-233, and the 256-wide MLPs): any Fin / Fout, the weight may be a
