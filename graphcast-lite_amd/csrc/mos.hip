@@ -33,6 +33,10 @@ constexpr int kForestThreads = 256;
 constexpr int kLeafBudget = 48 * 1024;  // bytes of leaf table per pass of the forest kernel
 constexpr int kIdwThreads = 128;
 constexpr int kStepTile = 16;           // steps per LDS bias tile of the IDW kernel
+constexpr int kSweepRows = 64;          // grid rows per block of the sweep kernel: one per lane of a wave
+constexpr int kSweepThreads = 256;      // its block: four waves share the distances, wave 0 walks the settings
+constexpr int kSweepMaxConfigs = 64;    // settings per launch
+constexpr int kSweepFinalThreads = 256;
 
 // One forest node: v = threshold (split) or value (leaf); a = left child; b = right child (bits 0-23), feature
 // (24-28), missing_go_to_left (29), is_leaf (30).  Child indices are global (into the whole forest).
@@ -218,6 +222,54 @@ __device__ __forceinline__ double idw_raw_weight(double d, double power) {
   return 1.0 / dp;
 }
 
+// The per-row IDW field, shared by idw_apply_kernel and idw_sweep_kernel so that the two cannot drift apart.  `dist(k)`
+// is the row's haversine distance to point k, `wgt(k, d)` its raw weight idw_raw_weight(d, power); a kernel may
+// compute them on the spot or read them back from where it kept them: the values, and so the bits, are the same.
+//
+// The points within the radius and the numpy sum of their raw weights, in point order (mos_correction.py:225-231).
+template <class Dist, class Wgt>
+__device__ __forceinline__ double idw_weight_sum(Dist dist, Wgt wgt, int K, double radius, int& nmask) {
+  nmask = 0;
+  for (int k = 0; k < K; ++k) nmask += dist(k) < radius;
+  NpSum ws(nmask);
+  for (int k = 0; k < K; ++k) {
+    const double d = dist(k);
+    if (d < radius) ws.add(wgt(k, d));
+  }
+  return ws.sum();
+}
+
+// acc[j] = the bias field of one row for a tile of steps, from bias(k, j): a point's own row (own >= 0) takes its
+// exact bias; otherwise sum_k (w_k / wsum) bias(k, j) over the points within the radius, pairwise for a single step
+// (a (n, 1) sum reduces along its only non-trivial axis) and point by point for several (numpy's axis-0 sum).
+template <class Dist, class Wgt, class Bias>
+__device__ __forceinline__ void idw_row_field(Dist dist, Wgt wgt, Bias bias, int K, double radius, int own, int nmask,
+                                              double wsum, int steps, double (&acc)[kStepTile]) {
+  if (own >= 0) {
+#pragma unroll
+    for (int j = 0; j < kStepTile; ++j) acc[j] = bias(own, j);
+  } else if (steps == 1) {
+    NpSum ps(nmask);
+    for (int k = 0; k < K && nmask; ++k) {
+      const double d = dist(k);
+      if (d < radius) ps.add(rounded((wgt(k, d) / wsum) * bias(k, 0)));
+    }
+#pragma unroll
+    for (int j = 0; j < kStepTile; ++j) acc[j] = 0.0;
+    acc[0] = nmask ? ps.sum() : 0.0;
+  } else {
+#pragma unroll
+    for (int j = 0; j < kStepTile; ++j) acc[j] = 0.0;
+    for (int k = 0; k < K && nmask; ++k) {
+      const double d = dist(k);
+      if (!(d < radius)) continue;
+      const double w = wgt(k, d) / wsum;
+#pragma unroll
+      for (int j = 0; j < kStepTile; ++j) acc[j] += rounded(w * bias(k, j));
+    }
+  }
+}
+
 __global__ void __launch_bounds__(kIdwThreads)
 idw_apply_kernel(const void* __restrict__ in, int f64, int64_t bs, int64_t gs, int64_t ss, void* out, int64_t obs,
                  int64_t ogs, int64_t oss, int copy, int G, int steps, int C, int t2m,
@@ -255,19 +307,16 @@ idw_apply_kernel(const void* __restrict__ in, int f64, int64_t bs, int64_t gs, i
   int own = -1;
   int nmask = 0;
   double wsum = 0.0, glat = 0.0, glon = 0.0;
+  const auto dist = [&](int k) { return haversine_km(glat, glon, plat[k], plon[k]); };
+  const auto wgt = [&](int, double d) { return idw_raw_weight(d, power); };
+  const auto tile = [&](int k, int j) { return btile[k * kStepTile + j]; };
   if (live) {
     for (int k = 0; k < K; ++k)
       if (pidx[k] == g) { own = k; break; }
     if (own < 0 && idw) {
       glat = node_lat[g];
       glon = node_lon[g];
-      for (int k = 0; k < K; ++k) nmask += haversine_km(glat, glon, plat[k], plon[k]) < radius;
-      NpSum ws(nmask);
-      for (int k = 0; k < K; ++k) {
-        const double d = haversine_km(glat, glon, plat[k], plon[k]);
-        if (d < radius) ws.add(idw_raw_weight(d, power));
-      }
-      wsum = ws.sum();
+      wsum = idw_weight_sum(dist, wgt, K, radius, nmask);
     }
   }
   const bool touched = live && (own >= 0 || idw);
@@ -282,30 +331,7 @@ idw_apply_kernel(const void* __restrict__ in, int f64, int64_t bs, int64_t gs, i
     __syncthreads();
     if (!touched) continue;
     double acc[kStepTile];
-    if (own >= 0) {
-#pragma unroll
-      for (int j = 0; j < kStepTile; ++j) acc[j] = btile[own * kStepTile + j];
-    } else if (steps == 1) {
-      // a (n, 1) sum reduces along its only non-trivial axis: pairwise
-      NpSum ps(nmask);
-      for (int k = 0; k < K && nmask; ++k) {
-        const double d = haversine_km(glat, glon, plat[k], plon[k]);
-        if (d < radius) ps.add(rounded((idw_raw_weight(d, power) / wsum) * btile[k * kStepTile]));
-      }
-#pragma unroll
-      for (int j = 0; j < kStepTile; ++j) acc[j] = 0.0;
-      acc[0] = nmask ? ps.sum() : 0.0;
-    } else {
-#pragma unroll
-      for (int j = 0; j < kStepTile; ++j) acc[j] = 0.0;
-      for (int k = 0; k < K && nmask; ++k) {
-        const double d = haversine_km(glat, glon, plat[k], plon[k]);
-        if (!(d < radius)) continue;
-        const double w = idw_raw_weight(d, power) / wsum;
-#pragma unroll
-        for (int j = 0; j < kStepTile; ++j) acc[j] += rounded(w * btile[k * kStepTile + j]);
-      }
-    }
+    idw_row_field(dist, wgt, tile, K, radius, own, nmask, wsum, steps, acc);
 #pragma unroll
     for (int j = 0; j < kStepTile; ++j) {
       if (j >= cnt) break;
@@ -329,6 +355,152 @@ idw_apply_kernel(const void* __restrict__ in, int f64, int64_t bs, int64_t gs, i
   }
   // n_corrected: IDW counts rows whose max |bias| > 1e-6 (a NaN makes numpy's max NaN); station-only counts points
   if (ncorr && live && (idw ? (any_big && !any_nan) : own >= 0)) atomicAdd(ncorr + b, 1);
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// IDW parameter sweep: the squared t2m error of P (power, radius) settings in one launch
+// ------------------------------------------------------------------------------------------------------------------
+// One block per 64 grid rows of one sample, one row per lane.  All four waves fill dist[k][lane], the row's distance
+// to every point, once; wave 0 then walks the settings.  Per distinct power it fills wgt[k][lane] (pow and the
+// division once per (row, point), not once per setting and pass), per setting it forms the field with the functions
+// idw_apply_kernel uses, reading both back from LDS, and adds the lanes' squared errors in a fixed butterfly order
+// into ws[p, s, block].  idw_sweep_final_kernel adds the blocks in a fixed order onto acc.  No floating-point
+// atomics anywhere.
+//
+// A point further north or south than the largest radius is skipped without its haversine: with both latitudes in
+// [-90, 90], a >= sin^2(dlat / 2), so d = 2 R asin(sqrt(a)) >= R |dlat| = 111.19 km per degree; 111 km per degree
+// leaves a relative margin of 1.7e-3.  Such a point is outside every setting's radius either way.
+__global__ void __launch_bounds__(kSweepThreads)
+idw_sweep_kernel(const void* __restrict__ in, int f64, int64_t bs, int64_t gs, int64_t ss,
+                 const void* __restrict__ truth, int64_t tbs, int64_t tgs, int64_t tss, int G, int steps, int t2m,
+                 const double* __restrict__ node_lat, const double* __restrict__ node_lon,
+                 const int32_t* __restrict__ pt_idx, int K, const double* __restrict__ bias, int idw,
+                 const double* __restrict__ power, const double* __restrict__ radius, int P, void* fields,
+                 int32_t* __restrict__ ncorr, double* __restrict__ ws) {
+  extern __shared__ double sweep_lds[];
+  double* dists = sweep_lds;                    // [K][kSweepRows]
+  double* wgts = sweep_lds + K * kSweepRows;    // [K][kSweepRows]
+  __shared__ double plat[kMaxPoints], plon[kMaxPoints];
+  __shared__ int32_t pidx[kMaxPoints];
+  const int tid = threadIdx.x, lane = tid % kSweepRows, q = tid / kSweepRows;
+  const int b = blockIdx.y, B = gridDim.y;
+  const int64_t nblk = (int64_t)gridDim.x * B, blk = (int64_t)b * gridDim.x + blockIdx.x;
+  const int g = blockIdx.x * kSweepRows + lane;
+  const bool live = g < G;
+  for (int k = tid; k < K; k += kSweepThreads) {
+    const int gi = pt_idx[k];
+    pidx[k] = gi;
+    plat[k] = node_lat ? node_lat[gi] : 0.0;
+    plon[k] = node_lon ? node_lon[gi] : 0.0;
+  }
+  __syncthreads();
+  double rmax = 0.0;
+  for (int p = 0; p < P; ++p) rmax = fmax(rmax, radius[p]);
+  if (idw) {
+    const double glat = live ? node_lat[g] : 0.0, glon = live ? node_lon[g] : 0.0;
+    const double inf = __builtin_inf();
+    for (int k = q; k < K; k += kSweepThreads / kSweepRows) {
+      const double pl = plat[k];
+      const bool far = fabs(glat) <= 90.0 && fabs(pl) <= 90.0 && rounded(fabs(pl - glat) * 111.0) > rmax;
+      dists[k * kSweepRows + lane] = live && !far ? haversine_km(glat, glon, pl, plon[k]) : inf;
+    }
+  }
+  __syncthreads();
+  if (q) return;
+
+  int own = -1;
+  if (live)
+    for (int k = 0; k < K; ++k)
+      if (pidx[k] == g) { own = k; break; }
+  const bool touched = live && (own >= 0 || idw);
+  const auto dist = [&](int k) { return dists[k * kSweepRows + lane]; };
+  const auto wgt = [&](int k, double) { return wgts[k * kSweepRows + lane]; };
+  const int64_t in0 = b * bs + (int64_t)g * gs + t2m, tr0 = b * tbs + (int64_t)g * tgs;
+  double cur_power = 0.0;
+  bool have_power = false;
+  for (int p = 0; p < P; ++p) {
+    const double pw = power[p], rad = radius[p];
+    if (idw && !(have_power && pw == cur_power)) {
+      for (int k = 0; k < K; ++k) {
+        const double d = dists[k * kSweepRows + lane];
+        wgts[k * kSweepRows + lane] = d < rmax ? idw_raw_weight(d, pw) : 0.0;
+      }
+      cur_power = pw;
+      have_power = true;
+    }
+    int nmask = 0;
+    double wsum = 0.0;
+    if (live && own < 0 && idw) wsum = idw_weight_sum(dist, wgt, K, rad, nmask);
+    // a row that no point reaches keeps x: its field is not evaluated
+    const bool eval = touched && (own >= 0 || nmask > 0);
+    bool any_big = false, any_nan = false;
+    for (int s0 = 0; s0 < steps; s0 += kStepTile) {
+      const int cnt = min(kStepTile, steps - s0);
+      const double* bp = bias + (int64_t)b * K * steps + s0;
+      const auto bvals = [&](int k, int j) { return j < cnt ? bp[(int64_t)k * steps + j] : 0.0; };
+      double acc[kStepTile];
+#pragma unroll
+      for (int j = 0; j < kStepTile; ++j) acc[j] = 0.0;
+      if (eval) idw_row_field(dist, wgt, bvals, K, rad, own, nmask, wsum, steps, acc);
+#pragma unroll
+      for (int j = 0; j < kStepTile; ++j) {
+        if (j >= cnt) continue;  // uniform; no break, so that the loop unrolls around the wave sum
+        const int s = s0 + j;
+        double e = 0.0;
+        if (live) {
+          const double f = acc[j];
+          any_nan |= isnan(f);
+          any_big |= fabs(f) > 1e-6;
+          const int64_t io = in0 + (int64_t)s * ss, to = tr0 + (int64_t)s * tss;
+          const int64_t fo = (((int64_t)p * B + b) * G + g) * steps + s;
+          // idw_apply_kernel's output: x + field in float64, rounded to the forecast's type; then sqerr_kernel's
+          // error: difference and square in that type, each rounded on its own
+          if (f64) {
+            const double x = static_cast<const double*>(in)[io];
+            const double y = touched ? x + f : x;
+            if (fields) static_cast<double*>(fields)[fo] = y;
+            const double d = y - static_cast<const double*>(truth)[to];
+            e = rounded(d * d);
+          } else {
+            const float x = static_cast<const float*>(in)[io];
+            const float y = touched ? (float)((double)x + f) : x;
+            if (fields) static_cast<float*>(fields)[fo] = y;
+            const float d = y - static_cast<const float*>(truth)[to];
+            e = (double)rounded(d * d);
+          }
+        }
+        const double tot = gcl::wave_sum(e);
+        if (lane == 0) ws[((int64_t)p * steps + s) * nblk + blk] = tot;
+      }
+    }
+    if (ncorr) {
+      const bool counted = live && (idw ? (any_big && !any_nan) : own >= 0);
+      const int n = __popcll(__ballot(counted));
+      if (lane == 0 && n) atomicAdd(ncorr + (int64_t)p * B + b, n);
+    }
+  }
+}
+
+// acc[p, h0 + s] += the sum of the nblk block partials of (p, s): thread t adds partials t, t + 256, ... in order,
+// then the 256 thread sums are added in a fixed tree.
+__global__ void __launch_bounds__(kSweepFinalThreads)
+idw_sweep_final_kernel(const double* __restrict__ ws, int64_t nblk, int steps, int H, int h0,
+                       double* __restrict__ acc) {
+  __shared__ double part[kSweepFinalThreads];
+  const int ps = blockIdx.x, tid = threadIdx.x;
+  const double* w = ws + (int64_t)ps * nblk;
+  double s = 0.0;
+  for (int64_t i = tid; i < nblk; i += kSweepFinalThreads) s += w[i];
+  part[tid] = s;
+  __syncthreads();
+  for (int o = kSweepFinalThreads / 2; o > 0; o >>= 1) {
+    if (tid < o) part[tid] += part[tid + o];
+    __syncthreads();
+  }
+  if (tid == 0) {
+    const int p = ps / steps, st = ps - p * steps;
+    acc[(int64_t)p * H + h0 + st] += part[0];
+  }
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -409,6 +581,44 @@ extern "C" int gcl_mos_idw_apply(const void* in, int32_t f64, int64_t bs, int64_
   hipLaunchKernelGGL(idw_apply_kernel, dim3((G + kIdwThreads - 1) / kIdwThreads, B), dim3(kIdwThreads), 0,
                      (hipStream_t)stream, in, f64, bs, gs, ss, out, obs, ogs, oss, copy, G, steps, C, t2m, node_lat,
                      node_lon, pt_idx, K, bias, idw, power, radius, n_corrected);
+  GCL_CHECK_LAUNCH();
+  return GCL_OK;
+}
+
+static inline int64_t sweep_blocks(int32_t G, int32_t B) { return gcl::cdiv(G, kSweepRows) * (int64_t)B; }
+
+extern "C" size_t gcl_mos_idw_sweep_ws_bytes(int32_t G, int32_t P, int32_t steps, int32_t B) {
+  if (G <= 0 || P <= 0 || steps <= 0 || B <= 0) return 0;
+  return (size_t)sweep_blocks(G, B) * (size_t)P * (size_t)steps * sizeof(double);
+}
+
+extern "C" int gcl_mos_idw_sweep_max_configs(void) { return kSweepMaxConfigs; }
+
+extern "C" int gcl_mos_idw_sweep(const void* in, int32_t f64, int64_t bs, int64_t gs, int64_t ss, const void* truth,
+                                 int64_t tbs, int64_t tgs, int64_t tss, int32_t G, int32_t steps, int32_t t2m,
+                                 const double* node_lat, const double* node_lon, const int32_t* pt_idx, int32_t K,
+                                 const double* bias, int32_t idw, const double* power, const double* radius,
+                                 int32_t P, double* acc, int32_t H, int32_t h0, void* fields_out,
+                                 int32_t* n_corrected, void* ws, size_t ws_bytes, int32_t B, gcl_stream_t stream) {
+  GCL_CHECK_ARG(in && truth && pt_idx && bias && power && radius && acc && ws, "mos_idw_sweep: null argument");
+  GCL_CHECK_ARG(!idw || (node_lat && node_lon), "mos_idw_sweep: IDW needs the node coordinates");
+  GCL_CHECK_ARG(G > 0 && steps > 0 && t2m >= 0 && B > 0 && B <= 65535,
+                "mos_idw_sweep: bad shape (G=%d, steps=%d, t2m=%d, B=%d)", G, steps, t2m, B);
+  GCL_CHECK_ARG(K > 0 && K <= kMaxPoints, "mos_idw_sweep: %d station points (1..%d)", K, kMaxPoints);
+  GCL_CHECK_ARG(P > 0 && P <= kSweepMaxConfigs, "mos_idw_sweep: %d settings (1..%d per call)", P, kSweepMaxConfigs);
+  GCL_CHECK_ARG(H > 0 && h0 >= 0 && (int64_t)h0 + steps <= H, "mos_idw_sweep: steps %d..%d outside the %d columns of "
+                "acc", h0, h0 + steps - 1, H);
+  GCL_CHECK_ARG((int64_t)P * steps < (1ll << 31), "mos_idw_sweep: P x steps = %d x %d too large", P, steps);
+  GCL_CHECK_ARG(ws_bytes >= gcl_mos_idw_sweep_ws_bytes(G, P, steps, B), "mos_idw_sweep: workspace of %zu bytes, %zu "
+                "needed", ws_bytes, gcl_mos_idw_sweep_ws_bytes(G, P, steps, B));
+  const size_t lds = idw ? 2 * (size_t)K * kSweepRows * sizeof(double) : 0;
+  if (lds > 64 * 1024) GCL_ENSURE_DYN_LDS(idw_sweep_kernel, lds);
+  hipLaunchKernelGGL(idw_sweep_kernel, dim3((unsigned)gcl::cdiv(G, kSweepRows), B), dim3(kSweepThreads), lds,
+                     (hipStream_t)stream, in, f64, bs, gs, ss, truth, tbs, tgs, tss, G, steps, t2m, node_lat, node_lon,
+                     pt_idx, K, bias, idw, power, radius, P, fields_out, n_corrected, (double*)ws);
+  GCL_CHECK_LAUNCH();
+  hipLaunchKernelGGL(idw_sweep_final_kernel, dim3(P * steps), dim3(kSweepFinalThreads), 0, (hipStream_t)stream,
+                     (const double*)ws, sweep_blocks(G, B), steps, H, h0, acc);
   GCL_CHECK_LAUNCH();
   return GCL_OK;
 }

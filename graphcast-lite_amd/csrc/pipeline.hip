@@ -58,6 +58,26 @@ __global__ __launch_bounds__(256) void lapse_kernel(const float* __restrict__ in
   }
 }
 
+// out = in [G, S, C] with the t2m column of every step corrected by the lapse formula of scripts/mos_idw_sweep_v2.py
+// (apply_lapse_correction, :73-84): z_surf of step 0 is a geopotential, every operand a float32 array or a weak Python
+// float, so every step is float32: t2m + f32(6.5e-3 * f32(f32(z / 9.80665) - elev)).
+__global__ __launch_bounds__(256) void lapse_geopotential_kernel(const float* __restrict__ in, float* __restrict__ out,
+                                                                 int32_t G, int32_t S, int32_t C, int32_t t_idx,
+                                                                 int32_t z_idx, float elev) {
+  const int64_t total = (int64_t)G * S * C;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int32_t c = (int32_t)(i % C);
+    const int64_t g = i / ((int64_t)S * C);
+    const float v = in[i];
+    if (c == t_idx) {
+      const float dh = rounded(in[g * S * C + z_idx] / 9.80665f) - elev;
+      out[i] = v + rounded((float)kLapseRate * dh);
+    } else {
+      out[i] = v;
+    }
+  }
+}
+
 // obs[g, :] = truth[g, :] where g is a station's grid point, NaN elsewhere (:210-220)
 __global__ __launch_bounds__(256) void station_obs_kernel(const float* __restrict__ truth, int64_t ldt,
                                                           const int32_t* __restrict__ stn, int32_t S, int32_t G,
@@ -134,6 +154,17 @@ extern "C" int gcl_pipeline_lapse(const float* in, float* out, int32_t G, int32_
                 "pipeline_lapse: bad shape");
   hipLaunchKernelGGL(lapse_kernel, dim3(gcl::grid_for((int64_t)G * S * C)), dim3(256), 0, (hipStream_t)stream, in, out,
                      G, S, C, t_idx, z_idx, elev, lapse_f64);
+  GCL_CHECK_LAUNCH();
+  return GCL_OK;
+}
+
+extern "C" int gcl_pipeline_lapse_geopotential(const float* in, float* out, int32_t G, int32_t S, int32_t C,
+                                               int32_t t_idx, int32_t z_idx, double elev, gcl_stream_t stream) {
+  GCL_CHECK_ARG(in && out && in != out, "pipeline_lapse_geopotential: null or aliased argument");
+  GCL_CHECK_ARG(G > 0 && S > 0 && C > 0 && t_idx >= 0 && t_idx < C && z_idx >= 0 && z_idx < C && t_idx != z_idx,
+                "pipeline_lapse_geopotential: bad shape (G=%d S=%d C=%d t2m=%d z_surf=%d)", G, S, C, t_idx, z_idx);
+  hipLaunchKernelGGL(lapse_geopotential_kernel, dim3(gcl::grid_for((int64_t)G * S * C)), dim3(256), 0,
+                     (hipStream_t)stream, in, out, G, S, C, t_idx, z_idx, (float)elev);
   GCL_CHECK_LAUNCH();
   return GCL_OK;
 }

@@ -140,6 +140,10 @@ _SIGNATURES = {
                                + [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp]),
     "gcl_mos_idw_apply": (C.c_int, [_vp, _i32, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _vp,
                                     _vp, _vp, _i32, _vp, _i32, C.c_double, C.c_double, _vp, _i32, _vp]),
+    "gcl_mos_idw_sweep_ws_bytes": (_sz, [_i32, _i32, _i32, _i32]),
+    "gcl_mos_idw_sweep_max_configs": (C.c_int, []),
+    "gcl_mos_idw_sweep": (C.c_int, [_vp, _i32, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _vp, _vp, _vp,
+                                    _i32, _vp, _i32, _vp, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _sz, _i32, _vp]),
     "gcl_mos_table_apply": (C.c_int, [_vp, _i32, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _vp,
                                       _i32, _i32, _vp]),
     "gcl_multires_window_pack": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, _i64, _i32, _i32, _i32, _vp, _i32, _i32, _vp,
@@ -148,6 +152,7 @@ _SIGNATURES = {
     "gcl_pipeline_roi_phys": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i32, _i32, _i32, _vp, _vp, _i32, _i32, C.c_double,
                                         _i32, _vp, _vp, _vp]),
     "gcl_pipeline_lapse": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, C.c_double, _i32, _vp]),
+    "gcl_pipeline_lapse_geopotential": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, C.c_double, _vp]),
     "gcl_pipeline_station_obs": (C.c_int, [_vp, _i64, _vp, _i32, _i32, _i32, _vp, _vp]),
     "gcl_pipeline_sqerr": (C.c_int, [_vp, _i64, _i64, _i32, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "gcl_maps_colstats_ws_bytes": (_sz, [_i32, _i32, _i32]),
@@ -1290,6 +1295,19 @@ def pipeline_lapse(x3, t_idx: int, z_idx: int, elev: float, lapse_f64: bool):
     return out
 
 
+def pipeline_lapse_geopotential(x3, t_idx: int, z_idx: int, elev: float, out=None):
+    """The copy of contiguous x3 [G, S, C] corrected by the lapse formula of scripts/mos_idw_sweep_v2.py (see
+    gcl_pipeline_lapse_geopotential)."""
+    assert x3.dim() == 3 and x3.is_contiguous()
+    G, S, C = x3.shape
+    if out is None:
+        out = torch.empty_like(x3)
+    assert out.shape == x3.shape and out.is_contiguous()
+    _check(lib().gcl_pipeline_lapse_geopotential(_p(x3), _p(out), G, S, C, int(t_idx), int(z_idx), float(elev),
+                                                 _stream()))
+    return out
+
+
 def pipeline_station_obs(truth2, stn, out=None):
     """NaN field [G, C] with the rows stn (int32, device) of truth2 [G, C] (see gcl_pipeline_station_obs)."""
     G, C = truth2.shape
@@ -1310,6 +1328,38 @@ def pipeline_sqerr(preds3, truth2, stn, h: int, acc_grid, acc_stn=None):
     _check(lib().gcl_pipeline_sqerr(_p(preds3), preds3.stride(0), preds3.stride(1), V, _p(truth2), truth2.stride(0),
                                     _pi(stn), stn.numel() if stn is not None else 0, G, C, acc_grid.shape[1], int(h),
                                     _pd(acc_grid), _pd(acc_stn) if acc_stn is not None else None, _stream()))
+
+
+def mos_idw_sweep_max_configs() -> int:
+    """The most (power, radius) settings one gcl_mos_idw_sweep call takes."""
+    return int(lib().gcl_mos_idw_sweep_max_configs())
+
+
+def mos_idw_sweep(pred4, truth3, t2m: int, node_lat, node_lon, pt_idx, bias, idw: bool, power, radius, acc, h0: int = 0,
+                  fields_out=None, n_out=None, ws=None):
+    """acc[p, h0 + s] += sum over b, g of (y_p[b, g, s] - truth3[b, g, s])^2 for the P settings (power[p], radius[p]),
+    y_p the t2m that gcl_mos_idw_apply writes for setting p (see gcl_mos_idw_sweep).  pred4 [B, G, steps, C] float32 or
+    float64 with unit channel stride; truth3 [B, G, steps] of the same dtype, any strides; bias float64 [B, K, steps];
+    power / radius float64 device tensors [P]; acc float64 [P, H].  fields_out [P, B, G, steps] (pred4's dtype) and
+    n_out int32 [P, B] (zeroed by the caller) are optional.  ws: a uint8 workspace (default: the shared one)."""
+    B, G, S, _ = pred4.shape
+    P, K = power.numel(), pt_idx.numel()
+    assert pred4.is_cuda and pred4.dtype in (torch.float32, torch.float64) and pred4.stride(3) == 1
+    assert truth3.is_cuda and truth3.dtype == pred4.dtype and truth3.shape == (B, G, S)
+    assert bias.shape == (B, K, S) and radius.numel() == P and acc.dim() == 2 and acc.shape[0] == P
+    assert fields_out is None or (fields_out.shape == (P, B, G, S) and fields_out.dtype == pred4.dtype
+                                  and fields_out.is_cuda and fields_out.is_contiguous())
+    assert n_out is None or n_out.shape == (P, B)
+    need = int(lib().gcl_mos_idw_sweep_ws_bytes(G, P, S, B))
+    if ws is None:
+        ws = workspace(need, pred4.device)
+    _check(lib().gcl_mos_idw_sweep(
+        pred4.data_ptr(), int(pred4.dtype == torch.float64), pred4.stride(0), pred4.stride(1), pred4.stride(2),
+        truth3.data_ptr(), truth3.stride(0), truth3.stride(1), truth3.stride(2), G, S, int(t2m),
+        _pd(node_lat) if node_lat is not None else None, _pd(node_lon) if node_lon is not None else None, _pi(pt_idx),
+        K, _pd(bias), int(bool(idw)), _pd(power), _pd(radius), P, _pd(acc), acc.shape[1], int(h0),
+        fields_out.data_ptr() if fields_out is not None else None, _pi(n_out), ws.data_ptr(), ws.numel(), B, _stream()))
+    return acc
 
 
 # ------------------------------------------------------------------------------------------------------------------

@@ -34,6 +34,12 @@ NUM_TIME_FEATURES = 8  # hour sin/cos, doy sin/cos, solar elevation, station lat
 MAX_POINTS = 128  # station groups and stations per group (csrc/mos.hip kMaxPoints)
 _ALT_NAMES = {"u10": "10u", "10u": "u10", "v10": "10v", "10v": "v10"}
 DEFAULT_STATION = {"lat": 56.173, "lon": 92.493, "elev": 287.0, "name": "default"}
+# The (idw_power, idw_max_radius_km, label) grid of scripts/mos_idw_sweep_v2.py:192-203 (mos_idw_sweep.py:164-176 has the
+# same ten in another order); the first is the reference's default.
+IDW_SWEEP_CONFIGS = (
+    (2.0, 300.0, "p2.0_r300"), (2.0, 200.0, "p2.0_r200"), (2.0, 150.0, "p2.0_r150"), (2.0, 100.0, "p2.0_r100"),
+    (2.0, 50.0, "p2.0_r50"), (3.0, 300.0, "p3.0_r300"), (3.0, 150.0, "p3.0_r150"), (3.0, 100.0, "p3.0_r100"),
+    (1.5, 300.0, "p1.5_r300"), (1.5, 150.0, "p1.5_r150"))
 
 
 # ======================================================================================================================
@@ -360,6 +366,7 @@ class LearnedMOS:
         self._lat = torch.from_numpy(self.latitudes.astype(np.float64)).to(dev)
         self._lon = torch.from_numpy(self.longitudes.astype(np.float64)).to(dev)
         self._bufs = {}
+        self._sweep_cfg = {}  # config list -> [(power, radius) device tensors per launch]
 
     @property
     def num_points(self) -> int:
@@ -435,6 +442,89 @@ class LearnedMOS:
             self.num_points, bias.data_ptr(), int(self.idw), self.power, self.radius, ncorr.data_ptr(), B, st))
         res = pred if inplace else (out if out is not None else (o4 if pred.dim() == 4 else o4[0]))
         return res, ncorr
+
+    def _sweep_configs(self, configs):
+        """The (power, radius) device tensors of a config list, one pair per chunk of at most the kernel's cap,
+        uploaded at first use."""
+        key = tuple((float(c[0]), float(c[1])) for c in configs)
+        if not key:
+            raise ValueError("LearnedMOS.sweep: no settings")
+        cache = self._sweep_cfg
+        hit = cache.get(key)
+        if hit is None:
+            cap = hip.mos_idw_sweep_max_configs()
+            hit = cache[key] = [
+                (torch.tensor([c[0] for c in key[i:i + cap]], dtype=torch.float64).to(self.device),
+                 torch.tensor([c[1] for c in key[i:i + cap]], dtype=torch.float64).to(self.device))
+                for i in range(0, len(key), cap)]
+        return hit
+
+    def sweep(self, pred: torch.Tensor, tfeat: torch.Tensor, truth_t2m: torch.Tensor, configs, acc: torch.Tensor,
+              h: int = 0, fields_out: Optional[torch.Tensor] = None, n_out: Optional[torch.Tensor] = None):
+        """The squared t2m error of every IDW setting of `configs` ((power, radius_km[, label]) tuples, e.g.
+        `IDW_SWEEP_CONFIGS`) in one pass (scripts/mos_idw_sweep.py:260-272): `acc[p, h + s] += sum over b, g of
+        (y_p - truth_t2m)^2`, where y_p is the t2m `LearnedMOS(..., True, power_p, radius_p).apply(pred, tfeat)` would
+        give, with the difference and the square in the forecast's dtype and the sums in float64.  The station forest
+        runs once (the biases do not depend on the setting), then one kernel serves all settings; the instance's own
+        `power` / `radius` are not used, its station set decides whether IDW applies at all (fewer than two distinct
+        points: every setting is the station-only correction).
+
+        pred [G, steps, C] / [B, G, steps, C]; truth_t2m [G, steps] / [B, G, steps] in pred's dtype (any strides); acc
+        float64 [len(configs), H] on the device.  fields_out ([P, B, G, steps], pred's dtype) receives every y_p and
+        n_out (int32 [P, B]) the n_corrected of every setting; both optional.  No host sync; nothing is allocated
+        after the first call per shape and config list.  Returns acc."""
+        if not self.has_t2m:
+            raise ValueError("LearnedMOS.sweep: var_order has no t2m")
+        p4 = _as4(pred, "LearnedMOS.sweep")
+        B, G, S, C = p4.shape
+        if G != self.latitudes.shape[0] or C != len(self.var_order):
+            raise ValueError(f"prediction [{G} rows, {C} channels] does not match the coordinates "
+                             f"({self.latitudes.shape[0]}) / var_order ({len(self.var_order)})")
+        if tfeat.shape != (B, len(self.ordered_stations), S, NUM_TIME_FEATURES) or tfeat.dtype != torch.float64 \
+                or not tfeat.is_cuda or not tfeat.is_contiguous():
+            raise ValueError(f"tfeat must be contiguous float64 [{B}, {len(self.ordered_stations)}, {S}, "
+                             f"{NUM_TIME_FEATURES}] on the device (time_features), got {tuple(tfeat.shape)}")
+        if not isinstance(truth_t2m, torch.Tensor) or not truth_t2m.is_cuda:
+            raise RuntimeError("LearnedMOS.sweep needs GPU tensors (there is no CPU fallback)")
+        t3 = truth_t2m if truth_t2m.dim() == 3 else truth_t2m.unsqueeze(0)
+        if t3.shape != (B, G, S) or t3.dtype != p4.dtype:
+            raise ValueError(f"truth_t2m must be {p4.dtype} [{B}, {G}, {S}], got {truth_t2m.dtype} "
+                             f"{tuple(truth_t2m.shape)}")
+        chunks = self._sweep_configs(configs)
+        P = sum(c[0].numel() for c in chunks)
+        if not acc.is_cuda or acc.dtype != torch.float64 or acc.dim() != 2 or acc.shape[0] != P \
+                or not acc.is_contiguous() or not 0 <= h <= acc.shape[1] - S:
+            raise ValueError(f"acc must be contiguous float64 [{P}, H >= {h + S}] on the device, got "
+                             f"{acc.dtype} {tuple(acc.shape)}")
+        if fields_out is not None and (fields_out.shape != (P, B, G, S) or fields_out.dtype != p4.dtype
+                                       or not fields_out.is_cuda or not fields_out.is_contiguous()):
+            raise ValueError(f"fields_out must be contiguous {p4.dtype} [{P}, {B}, {G}, {S}] on the device")
+        if n_out is not None and (n_out.shape != (P, B) or n_out.dtype != torch.int32 or not n_out.is_cuda
+                                  or not n_out.is_contiguous()):
+            raise ValueError(f"n_out must be contiguous int32 [{P}, {B}] on the device")
+        bufs = self._buffers(B, S, p4.dtype, p4.shape, False)[0]
+        cap = chunks[0][0].numel()
+        ws = bufs.get(("sweep_ws", cap))
+        if ws is None:
+            need = int(hip.lib().gcl_mos_idw_sweep_ws_bytes(G, cap, S, B))
+            ws = bufs[("sweep_ws", cap)] = torch.empty(need, dtype=torch.uint8, device=self.device)
+        f64 = int(p4.dtype == torch.float64)
+        bias = bufs["bias"]
+        hip._check(hip.lib().gcl_mos_forest_predict(
+            self._nodes.data_ptr(), self._roots.data_ptr(), self.forest.num_trees, self.forest.baseline,
+            p4.data_ptr(), f64, p4.stride(0), p4.stride(1), p4.stride(2), S, *self.chans, self._gidx.data_ptr(),
+            self._gstart.data_ptr(), self.num_points, len(self.ordered_stations), tfeat.data_ptr(), bias.data_ptr(),
+            None, None, B, hip._stream()))
+        if n_out is not None:
+            hip.zero_(n_out)
+        p0 = 0
+        for power, radius in chunks:
+            n = power.numel()
+            hip.mos_idw_sweep(p4, t3, self.chans[0], self._lat, self._lon, self._gidx, bias, self.idw, power, radius,
+                              acc[p0:p0 + n], h, fields_out[p0:p0 + n] if fields_out is not None else None,
+                              n_out[p0:p0 + n] if n_out is not None else None, ws)
+            p0 += n
+        return acc
 
     @property
     def station_bias(self) -> torch.Tensor:

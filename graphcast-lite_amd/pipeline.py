@@ -10,6 +10,8 @@ module adds the glue between them (csrc/pipeline.hip) so that a sample never ret
   tensors in and out.
 * `evaluation_sample_starts`: the script's sample selection (`:371-387`).
 * `FullPipelineEvaluator`: the sample loop of `:449-666` and the tables of `:678-766`.
+* `MosIdwSweep`: the IDW parameter sweeps of `scripts/mos_idw_sweep.py` (multires frames, AR rollout) and
+  `scripts/mos_idw_sweep_v2.py` (merged data set, +6 h), every setting scored by one kernel (`LearnedMOS.sweep`).
 """
 from typing import Optional, Sequence
 
@@ -17,7 +19,7 @@ import numpy as np
 import torch
 
 from . import hip
-from .mos import LearnedMOS
+from .mos import IDW_SWEEP_CONFIGS, LearnedMOS
 from .predict import rollout
 
 VARIANTS = ("GNN", "GNN+lapse", "GNN+MOS", "GNN+lapse+MOS", "GNN+lapse+MOS+IDW", "GNN+lapse+MOS+IDW+OI", "Persistence")
@@ -273,3 +275,189 @@ class FullPipelineEvaluator:
                     for h in range(self.ar)]
             res["skill"][name] = vals + [float(np.mean(vals))]
         return res
+
+
+SWEEP_BASE_VARIANTS = ("Persistence", "GNN_raw", "GNN+lapse", "GNN+lapse+MOS_station")
+
+
+def sweep_variant_names(configs=IDW_SWEEP_CONFIGS) -> list:
+    """The rows of the sweep scripts' tables (`all_cfgs`, mos_idw_sweep.py:303-304): persistence, the three variants
+    without IDW, then one per setting."""
+    return list(SWEEP_BASE_VARIANTS) + [f"GNN+lapse+MOS+IDW_{c[2]}" for c in configs]
+
+
+def sweep_tables(se: dict, count: Sequence[int], configs=IDW_SWEEP_CONFIGS) -> dict:
+    """The tables the sweep scripts print (mos_idw_sweep.py:293-357, mos_idw_sweep_v2.py:319-375) from the t2m
+    squared-error sums `se[variant][h]` and the counts `count[h]`: rmse [variant] -> the horizons and their mean,
+    skill [variant] -> percent against persistence, the horizons and their mean, best [h] -> (label, rmse) of the IDW
+    setting with the smallest RMSE (the first one on a tie)."""
+    names = sweep_variant_names(configs)
+    H = len(count)
+    rmse = {n: [float(np.sqrt(se[n][h] / max(count[h], 1))) for h in range(H)] for n in names}
+    res = {"variants": names, "count": list(count), "se_t2m": {n: [float(v) for v in se[n]] for n in names},
+           "rmse": {n: v + [float(np.mean(v))] for n, v in rmse.items()}, "skill": {}, "best": []}
+    pr = rmse["Persistence"]
+    for n in names[1:]:
+        vals = [float((1.0 - rmse[n][h] / pr[h]) * 100) if pr[h] > 1e-8 else 0.0 for h in range(H)]
+        res["skill"][n] = vals + [float(np.mean(vals))]
+    for h in range(H):
+        best, best_rmse = None, 9999.0
+        for c in configs:
+            r = rmse[f"GNN+lapse+MOS+IDW_{c[2]}"][h]
+            if r < best_rmse:
+                best, best_rmse = c[2], r
+        res["best"].append((best, best_rmse))
+    return res
+
+
+class MosIdwSweep:
+    """The MOS/IDW parameter sweep of the reference's two scripts on the device: per sample and horizon the t2m squared
+    error on the regional rows of persistence, the raw forecast, the lapse-corrected one, the station-only MOS and
+    every IDW setting of `configs` ((power, radius_km, label), default `mos.IDW_SWEEP_CONFIGS`).  The station forest
+    runs once for all settings and one kernel scores them (`LearnedMOS.sweep`); no corrected field is stored.
+
+    mode="multires" (`scripts/mos_idw_sweep.py:196-282`): dataset is a `MultiresChunkDataset(quantize=False)`,
+    regional_series the fp16 device series (T, lon, lat, C) that gives truth and persistence in physical units (None:
+    the dataset's own, merge mode); an AR rollout of `ar_steps`; the lapse is `apply_lapse` (the TYPE of lapse_elev
+    selects its arithmetic); the MOS coordinates are the (lat, lon)-major regional grid in float32.
+
+    mode="merged" (`scripts/mos_idw_sweep_v2.py:229-304`): dataset is any `batch(indices) -> (X, Y)` data set of the
+    merged node set (z-scored `[B, N, obs * C]`, `[B, N, >= C]`), region_rows the indices of the regional rows (default:
+    `dataset.is_regional`), coordinates the per-node (lats, lons) (default: `dataset.coordinates`), used in float32.
+    Truth and persistence are Y and the last X frame de-normalised, one horizon; the lapse is v2's formula
+    `t2m + 6.5e-3 * (z_surf / 9.80665 - lapse_elev)` in float32 with the forecast's own z_surf.
+
+    `update(samples)` (frame starts in multires mode, data-set indices in merged mode) makes no host synchronisation;
+    `results()` copies the sums to the host once and returns `sweep_tables` of them."""
+
+    def __init__(self, model, dataset, var_order: Sequence[str], y_mean, y_std, stations: Sequence[dict], lapse_elev,
+                 mos, mode: str = "multires", regional_series=None, ar_steps: int = 1, region_rows=None,
+                 coordinates=None, configs=IDW_SWEEP_CONFIGS, use_residual: bool = False, base_time=None):
+        from datetime import datetime, timedelta, timezone
+
+        if mode not in ("multires", "merged"):
+            raise ValueError(f"Unknown mode: {mode}")
+        self.mode, self.model, self.ds, self.var_order = mode, model, dataset, list(var_order)
+        if "t2m" not in self.var_order:
+            raise ValueError("MosIdwSweep scores t2m: it is not in var_order")
+        self.configs = [(float(c[0]), float(c[1]), str(c[2])) for c in configs]
+        if not self.configs or len({c[2] for c in self.configs}) != len(self.configs):
+            raise ValueError("MosIdwSweep: the settings need distinct labels (and at least one)")
+        self.device = torch.device(dataset.device)
+        self.obs, self.use_residual = int(model.obs_window), bool(use_residual)
+        self.C = len(self.var_order)
+        self.ar = int(ar_steps) if mode == "multires" else 1
+        if mode == "merged" and int(ar_steps) != 1:
+            raise ValueError("merged mode scores one horizon (+6 h): the data set holds no later truth")
+        self.t_idx = self.var_order.index("t2m")
+        self.z_idx = self.var_order.index("z_surf") if "z_surf" in self.var_order else -1
+        self.lapse_elev = float(lapse_elev)
+        self.mean, self.std = _dev_f32(y_mean, self.device), _dev_f32(y_std, self.device)
+        if self.mean.numel() != self.C or self.std.numel() != self.C:
+            raise ValueError(f"y_mean / y_std must hold {self.C} values")
+        self.stations = list(stations)
+        if mode == "multires":
+            if dataset.n_feat != self.C:
+                raise ValueError(f"the dataset serves {dataset.n_feat} features, var_order names {self.C}")
+            self.rs = regional_series if regional_series is not None else dataset.region_series
+            if self.rs is None:
+                raise ValueError("regional_series is needed (the dataset holds none in interpolate mode)")
+            if not (self.rs.is_cuda and self.rs.dtype == torch.float16 and self.rs.dim() == 4 and self.rs.is_contiguous()):
+                raise ValueError("regional_series must be a contiguous fp16 device tensor (T, lon, lat, C)")
+            r_lats, r_lons = dataset.r_lats, dataset.r_lons
+            if tuple(self.rs.shape[1:3]) != (len(r_lons), len(r_lats)) or self.rs.shape[3] < self.C:
+                raise ValueError(f"regional_series {tuple(self.rs.shape)} does not match the dataset's regional axes")
+            self.G, self.n_kept, self._rows = dataset.n_regional, dataset.n_global_kept, None
+            self.lapse_f64 = lapse_in_float64(lapse_elev)
+            lo_m, la_m = np.meshgrid(r_lons, r_lats)
+            lat32, lon32 = la_m.ravel().astype(np.float32), lo_m.ravel().astype(np.float32)  # mos_idw_sweep.py:111-113
+            self._zeros = torch.zeros(self.C, dtype=torch.float32, device=self.device)
+            self._ones = torch.ones(self.C, dtype=torch.float32, device=self.device)
+        else:
+            lats, lons = coordinates if coordinates is not None else dataset.coordinates
+            rows = np.asarray(region_rows if region_rows is not None else np.where(np.asarray(dataset.is_regional))[0])
+            if rows.ndim != 1 or rows.size == 0 or rows.min() < 0 or rows.max() >= len(lats):
+                raise ValueError("region_rows must be a non-empty list of node indices")
+            lat32 = np.asarray(lats).astype(np.float32)[rows]  # mos_idw_sweep_v2.py:119-120, :217-218
+            lon32 = np.asarray(lons).astype(np.float32)[rows]
+            self.G, self.n_kept = int(rows.size), 0
+            self._rows = torch.from_numpy(rows.astype(np.int32)).to(self.device)
+            self.lapse_f64 = False
+        forest = mos
+        self._mos_stn = LearnedMOS(forest, self.var_order, lat32, lon32, self.stations, False, device=self.device)
+        self._mos_idw = LearnedMOS(forest, self.var_order, lat32, lon32, self.stations, True, device=self.device)
+        base = base_time if base_time is not None else datetime(2020, 6, 1, 0, 0, 0, tzinfo=timezone.utc)
+        self._tfeat = [self._mos_stn.time_features([base + timedelta(hours=6 * (h + 1))]) for h in range(self.ar)]
+        self.variants = sweep_variant_names(self.configs)
+        G, C = self.G, self.C
+        self._buf = torch.empty(3, G, C, dtype=torch.float32, device=self.device)  # raw, lapse, station MOS
+        self._truth = torch.empty(2, G, C, dtype=torch.float32, device=self.device)  # merged mode: persistence, truth
+        self._acc = torch.zeros(4, self.ar, C, dtype=torch.float64, device=self.device)  # raw, lapse, MOS, persistence
+        self._acc_idw = torch.zeros(len(self.configs), self.ar, dtype=torch.float64, device=self.device)
+        self.count = [0] * self.ar
+
+    def reset(self):
+        self._acc.zero_()
+        self._acc_idw.zero_()
+        self.count = [0] * self.ar
+
+    def _score(self, truth2: torch.Tensor, persist2: torch.Tensor, h: int):
+        """Station MOS, the error sums of the four plain variants and the sweep, from self._buf[0:2]."""
+        buf, G, C = self._buf, self.G, self.C
+        tf = self._tfeat[h]
+        as3 = lambda t: t.view(G, 1, C)  # noqa: E731  ((G, 1, C): one step per call)
+        self._mos_stn.apply(as3(buf[1]), tf, out=as3(buf[2]))
+        hip.pipeline_sqerr(buf, truth2, None, h, self._acc[:3])
+        hip.pipeline_sqerr(persist2.unsqueeze(0), truth2, None, h, self._acc[3:])
+        self._mos_idw.sweep(as3(buf[1]), tf, truth2[:, self.t_idx:self.t_idx + 1], self.configs, self._acc_idw, h)
+        self.count[h] += G
+
+    @torch.no_grad()
+    def update(self, samples: Sequence[int]):
+        """Add the samples: frame starts (multires; a sample needs obs + ar_steps frames) or data-set indices (merged)."""
+        C, ar, buf = self.C, self.ar, self._buf
+        ids = [int(t) for t in samples]
+        if self.mode == "merged":
+            if any(i < 0 or i >= len(self.ds) for i in ids):
+                raise ValueError(f"a sample index outside the {len(self.ds)} samples of the data set")
+            for i in ids:
+                X, Y = self.ds.batch([i])
+                out = rollout(self.model, X, 1, use_residual=self.use_residual)  # [1, N, C]
+                hip.pipeline_roi_phys(out[0, :, :C], None, self._rows, 0, self.G, self.mean, self.std, -1, -1, 0.0,
+                                      False, buf[0])
+                if self.z_idx >= 0:
+                    hip.pipeline_lapse_geopotential(buf[0].view(self.G, 1, C), self.t_idx, self.z_idx, self.lapse_elev,
+                                                    out=buf[1].view(self.G, 1, C))
+                else:
+                    buf[1].copy_(buf[0])
+                hip.pipeline_roi_phys(X[0, :, (self.obs - 1) * C:self.obs * C], None, self._rows, 0, self.G, self.mean,
+                                      self.std, -1, -1, 0.0, False, self._truth[0])
+                hip.pipeline_roi_phys(Y[0, :, :C], None, self._rows, 0, self.G, self.mean, self.std, -1, -1, 0.0, False,
+                                      self._truth[1])
+                self._score(self._truth[1], self._truth[0], 0)
+            return
+        T = min(self.ds.total_time, self.rs.shape[0])
+        if any(t < 0 or t + self.obs + ar > T for t in ids):
+            raise ValueError(f"a sample needs {self.obs + ar} frames inside the {T} common ones")
+        t0_all = torch.tensor(ids, dtype=torch.int64).to(self.device)
+        z = self.z_idx
+        for i in range(len(ids)):
+            t0 = t0_all[i:i + 1]
+            X, _ = self.ds.windows(t0, self.obs, 0, C)
+            out = rollout(self.model, X, ar, use_residual=self.use_residual)
+            phys, _ = hip.window_pack(self.rs, t0 + (self.obs - 1), self._zeros, self._ones, C, 1 + ar, 0)
+            persist = phys[0, :, :C]
+            for h in range(ar):
+                truth = phys[0, :, (1 + h) * C:(2 + h) * C]
+                hip.pipeline_roi_phys(out[0, :, h * C:(h + 1) * C], None, None, self.n_kept, self.G, self.mean, self.std,
+                                      self.t_idx if z >= 0 else -1, z, self.lapse_elev, self.lapse_f64, buf[0], buf[1])
+                self._score(truth, persist, h)
+
+    def results(self) -> dict:
+        """`sweep_tables` of the accumulated sums (host values): variants, count [h], se_t2m / rmse / skill [variant]
+        and best [h] -> (label, rmse)."""
+        plain, idw = self._acc.cpu().numpy()[:, :, self.t_idx], self._acc_idw.cpu().numpy()
+        se = {"GNN_raw": plain[0], "GNN+lapse": plain[1], "GNN+lapse+MOS_station": plain[2], "Persistence": plain[3]}
+        for p, c in enumerate(self.configs):
+            se[f"GNN+lapse+MOS+IDW_{c[2]}"] = idw[p]
+        return sweep_tables(se, self.count, self.configs)

@@ -682,6 +682,24 @@ int gcl_mos_idw_apply(const void* in, int32_t f64, int64_t bs, int64_t gs, int64
                       const double* node_lat, const double* node_lon, const int32_t* pt_idx, int32_t K,
                       const double* bias, int32_t idw, double power, double radius, int32_t* n_corrected, int32_t B,
                       gcl_stream_t stream);
+/* IDW parameter sweep (mos_correction.py:187-241, :326-338 as called by scripts/mos_idw_sweep.py:260-272 and
+ * scripts/mos_idw_sweep_v2.py:288-299): the squared t2m error of P settings (power[p], radius[p]) - float64 device
+ * arrays - in one launch, without the corrected forecasts.  For every setting p and row (b, g, s) the corrected value
+ * y_p is bit for bit what gcl_mos_idw_apply writes for that setting (idw = 0: the station-only result for every p);
+ * acc[p, h0 + s] += sum over b, g of (y_p - truth[b * tbs + g * tgs + s * tss])^2 with the difference and the square
+ * in the forecast's type, each rounded on its own, and the sum in float64 in a fixed order (no floating-point atomics:
+ * block partials in ws, then one fixed-order sum), so a repeated call repeats its bits.  acc is float64 [P, H].
+ * fields_out (optional) [P, B, G, steps] in the forecast's type receives y_p; n_corrected (optional) int32 [P, B],
+ * zeroed by the caller, counts as gcl_mos_idw_apply does.  ws holds gcl_mos_idw_sweep_ws_bytes(G, P, steps, B) bytes.
+ * P above gcl_mos_idw_sweep_max_configs() and K above 128 are argument errors. */
+size_t gcl_mos_idw_sweep_ws_bytes(int32_t G, int32_t P, int32_t steps, int32_t B);
+int gcl_mos_idw_sweep_max_configs(void);
+int gcl_mos_idw_sweep(const void* in, int32_t f64, int64_t bs, int64_t gs, int64_t ss, const void* truth, int64_t tbs,
+                      int64_t tgs, int64_t tss, int32_t G, int32_t steps, int32_t t2m, const double* node_lat,
+                      const double* node_lon, const int32_t* pt_idx, int32_t K, const double* bias, int32_t idw,
+                      const double* power, const double* radius, int32_t P, double* acc, int32_t H, int32_t h0,
+                      void* fields_out, int32_t* n_corrected, void* ws, size_t ws_bytes, int32_t B,
+                      gcl_stream_t stream);
 /* Table MOS (mos_correction.py:34-69 apply_mos_t2m): out[.., s, t2m] = in + step_bias[s] for s < nvalid, float32
  * f32(x + f32(b)) (numpy's weak Python-float scalar) or float64 x + b.  out != in also copies every other element. */
 int gcl_mos_table_apply(const void* in, int32_t f64, int64_t bs, int64_t gs, int64_t ss, void* out, int64_t obs,
@@ -724,6 +742,11 @@ int gcl_pipeline_roi_phys(const float* pred, int64_t ldp, const float* x_last, i
  * with z_idx of step 0; lapse_f64 as above. */
 int gcl_pipeline_lapse(const float* in, float* out, int32_t G, int32_t S, int32_t C, int32_t t_idx, int32_t z_idx,
                        double elev, int32_t lapse_f64, gcl_stream_t stream);
+/* apply_lapse_correction of scripts/mos_idw_sweep_v2.py:73-84 on contiguous in [G, S, C] -> out (must not alias):
+ * column t_idx of every step becomes t2m + f32(6.5e-3 * f32(f32(z / 9.80665) - elev)), z the geopotential in column
+ * z_idx of step 0, elev a Python float there: every operation float32, each rounded on its own. */
+int gcl_pipeline_lapse_geopotential(const float* in, float* out, int32_t G, int32_t S, int32_t C, int32_t t_idx,
+                                    int32_t z_idx, double elev, gcl_stream_t stream);
 /* simulate_station_obs (:203-222): obs [G, C] = truth rows at the S grid points stn[], NaN elsewhere. */
 int gcl_pipeline_station_obs(const float* truth, int64_t ldt, const int32_t* stn, int32_t S, int32_t G, int32_t C,
                              float* obs, gcl_stream_t stream);
