@@ -127,6 +127,10 @@ __global__ __launch_bounds__(256, 2) void linear_x3_fwd_kernel(const float* __re
   // staging map: 16 lanes x float4 = one 64-float row, 4 rows per wave-instruction, 8 instructions per tile
   const int rsub = lane >> 4, csub = lane & 15;
   const bool cok = csub * 4 < K;
+  // K % 4 != 0: the 16 bytes of the last loading lane end in the row's padding (columns K.. of a 16-byte row), which
+  // is not data: it is cleared before the split, whatever it holds (a NaN there would meet the zero weight and still
+  // poison the row).  Block-uniform test: nothing changes for K % 4 == 0.
+  const int kleft = K - csub * 4;  // data columns in this lane's float4
   float4 pre[8];
   auto issue = [&](int64_t tile) {
     const int64_t r0 = tile * 128 + wave * 32;
@@ -141,6 +145,9 @@ __global__ __launch_bounds__(256, 2) void linear_x3_fwd_kernel(const float* __re
 #pragma unroll
     for (int it = 0; it < 8; ++it) {
       float4 v = pre[it];
+      if (K & 3) {
+        v.y = kleft > 1 ? v.y : 0.f; v.z = kleft > 2 ? v.z : 0.f; v.w = kleft > 3 ? v.w : 0.f;
+      }
       if (SILU) {
         v.x = gcl::silu_f(v.x); v.y = gcl::silu_f(v.y); v.z = gcl::silu_f(v.z); v.w = gcl::silu_f(v.w);
       } else {  // PReLU and "none" (pa = 1) share one branch-free form

@@ -94,6 +94,19 @@ int gcl_graph_halo_info(const gcl_graph_t* g, int32_t transpose, int32_t T, int3
  * Replaces nn.Linear (+ the preceding nn.PReLU) inside MLP.forward (src/models.py:106-109) and the
  * `lin` GEMM inside every GCNConv/GATConv (src/models.py:419,425).  fp32 in, fp32 accumulate
  * (v_mfma_f32_32x32x2_f32: exact fp32 FMA chain in k order).
+ * Padding and strides: every row argument of the dense entry points below (x, z, dy, addend, y, dx; W and dW with their
+ * ldw / lddw) may have a row stride larger than its width, sit at a column offset inside wider rows, and start at any
+ * float-aligned address.  The columns of an INPUT past its width and everything between its rows are ignored, whatever
+ * they hold (NaN and Inf included): the result is bit-equal to the result with zeros there.  The columns of an OUTPUT
+ * past its width (Fout of y, Fin of dx and of dW's rows) and everything between its rows are never written.  One
+ * exception: gcl_linear_bwd_all with Fout % 4 != 0 needs FINITE padding in dy up to roundup(Fout, 4) (see there).  The
+ * layout only selects the kernel: rows with ld % 4 == 0 on a 16-byte aligned base are read 16 bytes at a time, all
+ * others element by element.
+ * Refused with GCL_EINVAL (nothing is written): a leading dimension smaller than its width; and every call that falls
+ * to the 128x128 tile kernel (ldw != Fin, an addend, a contraction or an output wider than 256, a weight panel beyond
+ * the LDS, or a contraction longer than 128 on rows that are not 16-byte ones) whose contraction length is no multiple
+ * of 4 or whose input rows or weight rows are not 16-byte ones; gcl_dense_bwd_dx on that kernel also needs Fin % 4 == 0
+ * unless it can transpose W into the workspace first (Fout % 4 == 0 and rows >= 4096).
  * ------------------------------------------------------------------------------------------- */
 int gcl_linear_fwd(const float* x, int64_t ldx, const float* in_slope, const float* W /*[Fout,Fin]*/,
                    const float* bias /*[Fout] or NULL*/, float* y, int64_t ldy, int64_t rows,
@@ -206,6 +219,17 @@ int gcl_dense_bwd_dw(const float* dy, int64_t lddy, const float* x, int64_t ldx,
  * Replaces the index_select -> multiply -> scatter_add_ of PyG propagate for GCNConv
  * (src/models.py:419) and SimpleConv mean (src/models.py:414).  transpose != 0 walks the
  * sender-sorted CSR instead (the backward: dh = A_hat^T dy).
+ * Padding and strides: h and y of gcl_aggregate / gcl_aggregate_present may have any row stride >= F, any batch stride
+ * and any float-aligned base; 16-byte rows (ld % 4 == 0, bs % 4 == 0, aligned base; for h: ldh >= roundup(F, 4), which
+ * such rows always have) are read and, when F % 4 == 0 too, written 16 bytes at a time.  The columns of h past F, the
+ * space between its rows and between its samples are ignored, whatever they hold (NaN and Inf included; the vector loads
+ * do fetch columns F .. roundup(F, 4) and drop them); the columns of y past F, rows past n and the space between samples
+ * are never written.  The same holds for the graph layers further down, which only take 16-byte rows and refuse others
+ * with GCL_EINVAL: gcl_gcn_layer_fwd* (x: columns past Fin ignored; y: columns [Fout, Fout_store) written as zeros,
+ * columns past Fout_store and rows past rows_out never written), gcl_gat_fwd / gcl_gat_bwd (h, dy: columns past H * C / C
+ * ignored; y, dh: columns past C / H * C never written; dy must be row-contiguous across the batch), gcl_segment_reduce
+ * and gcl_edge_combine (strided src / A / C; strided out of the former).
+ * Refused with GCL_EINVAL (nothing is written): a leading dimension smaller than F, h == y, a GCL_GRAPH_GAT graph.
  * ------------------------------------------------------------------------------------------- */
 int gcl_aggregate(const gcl_graph_t* g, int32_t transpose, const float* h, int64_t ldh, int64_t bsh,
                   const float* bias, float* y, int64_t ldy, int64_t bsy, int32_t B, int32_t F,

@@ -1,0 +1,153 @@
+"""Row layouts for the kernel contract tests (test_norm_glue, test_dense_layouts, test_sparse_layouts): operands as
+views inside buffers the test owns, whose other elements hold a known value - NaN around an input (a kernel that
+reads its padding poisons the result), a sentinel around an output (a kernel that writes outside its view changes
+it) - plus the element-wise bound check and the launched-kernel queries the tests share."""
+import math
+
+import torch
+
+DEV = "cuda:0"
+U = 2.0 ** -24  # fp32 unit roundoff
+SENT = -7.25  # what an output buffer holds outside the part a kernel may write
+NAN = float("nan")
+
+
+def randn(*shape, seed):
+    return torch.randn(*shape, generator=torch.Generator(device=DEV).manual_seed(seed), device=DEV)
+
+
+def rand(*shape, seed):
+    return torch.rand(*shape, generator=torch.Generator(device=DEV).manual_seed(seed), device=DEV)
+
+
+def within(got, ref, tol, what):
+    """|got - ref| <= tol element-wise (a NaN anywhere fails)."""
+    got, ref = got.double(), ref.double()
+    tol = torch.as_tensor(tol, dtype=torch.float64, device=ref.device)
+    err = (got - ref).abs()
+    bad = ~(err <= tol)
+    if bad.any():
+        ratio = torch.where(bad, (err / tol).nan_to_num(nan=math.inf), torch.full_like(err, -1.0))
+        k = int(ratio.flatten().argmax())
+        raise AssertionError(f"{what}: {int(bad.sum())} of {bad.numel()} elements outside the bound; worst at flat index "
+                             f"{k}: got {got.flatten()[k].item()!r}, want {ref.flatten()[k].item()!r}, "
+                             f"bound {tol.expand_as(err).flatten()[k].item():.3e}")
+
+
+def same_bits(a, b):
+    """Bit-equal, NaN payloads included (torch.equal calls NaN != NaN)."""
+    return a.shape == b.shape and bool((a.contiguous().view(torch.int32) == b.contiguous().view(torch.int32)).all())
+
+
+COLBLOCK_LEAD = 8  # the column block starts at column 4 * 2 of its wider row
+
+
+def geometry(F, layout, role="in", ld=None):
+    """(row stride, offset of the base from the buffer's start, column offset inside the row) of a layout, in floats."""
+    F4 = (F + 3) // 4 * 4
+    off = lead = 0
+    if layout == "contig":
+        ld = F
+    elif layout == "odd_ld":
+        ld = F + 1 if F % 2 == 0 else F + 2
+    else:
+        if layout == "colblock":
+            lead = COLBLOCK_LEAD
+        ld = lead + (F4 if layout == "tight" else F4 + 4 if ld is None else ld)
+        off = 1 if layout == "offset" or (layout == "mixed" and role == "out") else 0
+    assert ld >= lead + F
+    return ld, off, lead
+
+
+class Geom:
+    """What the launch code sees of a layout, without a buffer behind it."""
+
+    def __init__(self, F, layout, role="in"):
+        self.ld, self.off, _ = geometry(F, layout, role)
+
+    def aligned(self):
+        return self.ld % 4 == 0 and self.off == 0
+
+
+class Rows:
+    """A [rows, F] view (or, with B, a [B, rows, F] view) inside a flat buffer, laid out as `layout` says; the rest of
+    the buffer holds `fill`.
+      contig    row stride F
+      pad_1e3   row stride roundup(F, 4) + 4 (16-byte rows), padding 1e3
+      pad_nan   the same, padding NaN
+      pad_zero  the same, padding zero
+      tight     row stride roundup(F, 4): the tightest 16-byte rows (19 floats on rows of 20), padding NaN
+      colblock  16-byte rows; the view sits at column offset 8 of rows that are roundup(F, 4) + 4 wider than that:
+                `fill` on both sides
+      odd_ld    an odd row stride, padding NaN
+      offset    16-byte row stride, base one float past a 16-byte boundary (the scalar path), padding NaN
+      mixed     inputs as pad_nan, outputs as offset (vector loads, scalar stores)
+    `ld` overrides the row stride of the padded layouts.  With B the samples are bs = rows * ld + gap apart, gap > 0
+    (8 where rows are 16-byte ones, else 5), and the gap holds `fill`."""
+
+    def __init__(self, rows, F, layout, fill, role="in", ld=None, B=None):
+        ld, off, lead = geometry(F, layout, role, ld)
+        self.ld = ld
+        nb = 1 if B is None else B
+        self.bs = rows * ld + (0 if B is None else 8 if ld % 4 == 0 else 5)
+        self.buf = torch.full((off + nb * self.bs + 3,), fill, device=DEV)
+        self.ptr = self.buf.data_ptr() + 4 * (off + lead)  # (an empty view's data_ptr() is 0)
+        self.inside = torch.zeros(self.buf.shape, dtype=torch.bool, device=DEV)
+        if B is None:
+            self.view = self.buf[off:off + rows * ld].view(rows, ld)[:, lead:lead + F]
+            self.inside[off:off + rows * ld].view(rows, ld)[:, lead:lead + F] = True
+        else:
+            self.view = torch.as_strided(self.buf, (B, rows, F), (self.bs, ld, 1), off + lead)
+            torch.as_strided(self.inside, (B, rows, F), (self.bs, ld, 1), off + lead).fill_(True)
+
+    @classmethod
+    def of(cls, src, layout, fill, role="in", ld=None):
+        """The layout holding a copy of src ([rows, F] or [B, rows, F])."""
+        B = src.shape[0] if src.dim() == 3 else None
+        r = cls(src.shape[-2], src.shape[-1], layout, fill, role, ld, B)
+        r.view.copy_(src)
+        return r
+
+    def untouched(self, fill):
+        return bool((self.buf[~self.inside] == fill).all())
+
+    def aligned(self):
+        """16-byte rows: what the vector paths of the kernels ask for."""
+        return self.ld % 4 == 0 and self.bs % 4 == 0 and self.ptr % 16 == 0
+
+
+def input_fill(layout):
+    return {"pad_1e3": 1e3, "pad_zero": 0.0}.get(layout, NAN)
+
+
+def launched(fn):
+    """(result of fn(), names of the GPU kernels it launched)."""
+    from torch.profiler import ProfilerActivity, profile
+
+    torch.cuda.synchronize()
+    with profile(activities=[ProfilerActivity.CUDA]) as prof:
+        out = fn()
+        torch.cuda.synchronize()
+    names = sorted({e.name for e in prof.events()})
+    assert names, "the profiler recorded no kernel"
+    return out, names
+
+
+def has(names, kern):
+    return any(kern in n for n in names)
+
+
+def targs(names, kern):
+    """Template argument lists of every launched instance of `kern` (demangled names: `kern<a, b, ..>(...)`)."""
+    out = []
+    for n in names:
+        i = n.find(kern + "<")
+        if i < 0:
+            continue
+        j = k = i + len(kern) + 1
+        depth = 1
+        while depth:
+            depth += {"<": 1, ">": -1}.get(n[k], 0)
+            k += 1
+        out.append([a.strip() for a in n[j:k - 1].split(",")])
+    return out

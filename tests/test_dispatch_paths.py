@@ -7,6 +7,9 @@ SparseGAT pruning on the compact pipeline.
 Every test proves that the path it names ran: kernel names from torch.profiler (HIP kernel names on ROCm) or a query
 of the library.  Small-integer inputs on constant-degree graphs make every path BIT-equal to float64; random inputs
 are held to the suite's 1e-5 of a float64 reference."""
+import os
+import sys
+
 import numpy as np
 import pytest
 import torch
@@ -14,6 +17,9 @@ import torch
 from conftest import build_graphs, experiment
 from oracle import pyg_ops as P
 from oracle import train_step as T
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+from layouts import has, launched, targs  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -55,39 +61,6 @@ def env(monkeypatch):
             else:
                 monkeypatch.setenv(k, str(v))
     return set_
-
-
-def launched(fn):
-    """(result of fn(), names of the GPU kernels it launched)."""
-    from torch.profiler import ProfilerActivity, profile
-
-    torch.cuda.synchronize()
-    with profile(activities=[ProfilerActivity.CUDA]) as prof:
-        out = fn()
-        torch.cuda.synchronize()
-    names = sorted({e.name for e in prof.events()})
-    assert names, "the profiler recorded no kernel"
-    return out, names
-
-
-def has(names, kern):
-    return any(kern in n for n in names)
-
-
-def targs(names, kern):
-    """Template argument lists of every launched instance of `kern` (demangled names: `kern<a, b, ..>(...)`)."""
-    out = []
-    for n in names:
-        i = n.find(kern + "<")
-        if i < 0:
-            continue
-        j = k = i + len(kern) + 1
-        depth = 1
-        while depth:
-            depth += {"<": 1, ">": -1}.get(n[k], 0)
-            k += 1
-        out.append([a.strip() for a in n[j:k - 1].split(",")])
-    return out
 
 
 def ring(n, offs):

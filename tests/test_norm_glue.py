@@ -8,6 +8,8 @@ Error bounds follow what fp32 arithmetic can promise, in units of the fp32 round
 with the condition |mean| / std of the normalisation, and every reduction is held to a multiple of the sum of |terms|.
 A kernel that drops, repeats or misplaces a single term is far outside them."""
 import math
+import os
+import sys
 
 import pytest
 import torch
@@ -15,12 +17,11 @@ import torch.nn.functional as Fn
 
 from oracle import pyg_ops as P
 
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+from layouts import DEV, NAN, SENT, U, Rows, input_fill, rand, randn, within  # noqa: E402
+
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-U = 2.0 ** -24  # fp32 unit roundoff
 EPS = 1e-5
-SENT = -7.25  # what an output buffer holds outside the part a kernel may write
-NAN = float("nan")
 
 
 @pytest.fixture(scope="module")
@@ -30,71 +31,9 @@ def hip(lib_built):
     return H
 
 
-def randn(*shape, seed):
-    return torch.randn(*shape, generator=torch.Generator(device=DEV).manual_seed(seed), device=DEV)
-
-
-def rand(*shape, seed):
-    return torch.rand(*shape, generator=torch.Generator(device=DEV).manual_seed(seed), device=DEV)
-
-
-def within(got, ref, tol, what):
-    """|got - ref| <= tol element-wise (a NaN anywhere fails)."""
-    got, ref = got.double(), ref.double()
-    tol = torch.as_tensor(tol, dtype=torch.float64, device=ref.device)
-    err = (got - ref).abs()
-    bad = ~(err <= tol)
-    if bad.any():
-        ratio = torch.where(bad, (err / tol).nan_to_num(nan=math.inf), torch.full_like(err, -1.0))
-        k = int(ratio.flatten().argmax())
-        raise AssertionError(f"{what}: {int(bad.sum())} of {bad.numel()} elements outside the bound; worst at flat index "
-                             f"{k}: got {got.flatten()[k].item()!r}, want {ref.flatten()[k].item()!r}, "
-                             f"bound {tol.expand_as(err).flatten()[k].item():.3e}")
-
-
 def lpr_for(F):
     lanes = (F + 3) // 4
     return 4 if lanes <= 4 else 8 if lanes <= 8 else 16 if lanes <= 16 else 32 if lanes <= 32 else 64
-
-
-class Rows:
-    """A [rows, F] view inside a flat buffer, laid out as `layout` says; the rest of the buffer holds `fill`.
-      contig    row stride F
-      pad_1e3   row stride roundup(F, 4) + 4 (16-byte rows), padding 1e3
-      pad_nan   the same, padding NaN
-      odd_ld    an odd row stride, padding NaN
-      offset    16-byte row stride, base one float past a 16-byte boundary (the scalar path), padding NaN
-      mixed     inputs as pad_nan, outputs as offset (vector loads, scalar stores)"""
-
-    def __init__(self, rows, F, layout, fill, role="in"):
-        F4 = (F + 3) // 4 * 4
-        off = 0
-        if layout == "contig":
-            ld = F
-        elif layout == "odd_ld":
-            ld = F + 1 if F % 2 == 0 else F + 2
-        else:
-            ld = F4 + 4
-            off = 1 if layout == "offset" or (layout == "mixed" and role == "out") else 0
-        self.ld = ld
-        self.buf = torch.full((off + rows * ld + 3,), fill, device=DEV)
-        self.ptr = self.buf.data_ptr() + 4 * off  # (an empty view's data_ptr() is 0)
-        self.view = self.buf[off:off + rows * ld].view(rows, ld)[:, :F]
-        self.inside = torch.zeros(self.buf.shape, dtype=torch.bool, device=DEV)
-        self.inside[off:off + rows * ld].view(rows, ld)[:, :F] = True
-
-    @classmethod
-    def of(cls, src, layout, fill, role="in"):
-        r = cls(src.shape[0], src.shape[1], layout, fill, role)
-        r.view.copy_(src)
-        return r
-
-    def untouched(self, fill):
-        return bool((self.buf[~self.inside] == fill).all())
-
-
-def input_fill(layout):
-    return 1e3 if layout == "pad_1e3" else NAN
 
 
 # ------------------------------------------------------------------------------------------------------------------
