@@ -14,8 +14,13 @@ interpolation), plus a captured assimilated rollout.
 
 Beyond the reference: `OptimalInterpolation.prepare_network` (a fixed station network, capture-safe),
 `assimilated_rollout` (`predict.rollout` with assimilation after each step) and `CapturedAssimilatedRollout`.
+
+The DA grid search (`scripts/da_grid_search.sh`, `da_experiments_v2.sh`, `_v3.sh`, `_merge.sh`: one `predict.py` run
+per setting): `DASetting`, `da_grid`, `station_network` and `DASweepAssimilator`, which assimilates every batch row of
+one rollout with another setting (`gcl_nudge_rows`, `gcl_oi_analysis_rows`); `pipeline.DaSweep` scores the rows.
 """
 import math
+from dataclasses import dataclass
 from typing import Optional, Sequence
 
 import numpy as np
@@ -435,6 +440,236 @@ class OINetwork:
 
 
 # ======================================================================================================================
+# The DA grid search: one setting per batch row
+# ======================================================================================================================
+@dataclass(frozen=True)
+class DASetting:
+    """One run of the grid search: `predict.py --assim-method {method} --nudging-alpha {alpha} --oi-sigma-b {sigma_b}
+    --oi-sigma-o {sigma_o} --oi-corr-len {corr_len} --obs-sparsity {sparsity}` (defaults as `predict.py:157-162`)."""
+    method: str = "none"
+    alpha: float = 0.25
+    sigma_b: float = 0.8
+    sigma_o: float = 0.5
+    corr_len: float = 10000.0
+    sparsity: Optional[float] = None
+    label: str = ""
+
+    def __post_init__(self):
+        if self.method not in ("none", "nudging", "oi"):
+            raise ValueError(f"Unknown assimilation method: {self.method}")
+        if self.method != "none" and (self.sparsity is None or not self.sparsity > 0):
+            raise ValueError(f"setting {self.label!r}: {self.method} needs a station density (sparsity > 0)")
+
+
+def _density_tag(sparsity: float) -> str:
+    return f"{sparsity * 100:g}"  # 0.1 -> "10", 0.01 -> "1": parse_da_results.py's oi10 / oi1 / nudg10 / nudg1
+
+
+def da_grid(nudging_alphas: Sequence[float] = (0.01, 0.05, 0.1, 0.3),
+            corr_lens: Sequence[float] = (5000.0, 10000.0, 50000.0), sigma_os: Sequence[float] = (0.3, 0.5),
+            sparsities: Sequence[float] = (0.01, 0.1), sigma_b: float = 0.8, oi: Optional[Sequence[tuple]] = None,
+            baseline: bool = False) -> list:
+    """The settings of the shell drivers, in their order; the defaults are `da_grid_search.sh`'s 8 nudging + 12 OI
+    runs: every (density, alpha), then every (density, corr_len, sigma_o).  `oi`: explicit (sparsity, corr_len, sigma_o)
+    triples in place of the product (the `run_oi` lists of `da_experiments_v2.sh`, `_v3.sh`, `_merge.sh`); `baseline`
+    puts the no-DA run first.  Labels are the names `parse_da_results.py` groups by: `baseline`,
+    `nudg{density}_a{alpha}`, `oi{density}_c{corr_len in km}_s{sigma_o}` with the density in percent."""
+    out = [DASetting(label="baseline")] if baseline else []
+    for sp in sparsities:
+        for a in nudging_alphas:
+            out.append(DASetting("nudging", alpha=float(a), sparsity=float(sp), label=f"nudg{_density_tag(sp)}_a{a:g}"))
+    triples = oi if oi is not None else [(sp, c, so) for sp in sparsities for c in corr_lens for so in sigma_os]
+    for sp, c, so in triples:
+        out.append(DASetting("oi", sigma_b=float(sigma_b), sigma_o=float(so), corr_len=float(c), sparsity=float(sp),
+                             label=f"oi{_density_tag(sp)}_c{c / 1000.0:g}_s{so:g}"))
+    return out
+
+
+def station_network(pool, sparsity: float, seed: int = 42) -> np.ndarray:
+    """The inline station draw of `scripts/predict.py:397-406`: max(1, int(len(pool) * sparsity)) grid indices drawn
+    from `pool` without replacement by a fresh `RandomState(seed)`, ascending."""
+    pool = np.asarray(pool)
+    rng = np.random.RandomState(seed)
+    n = max(1, int(len(pool) * sparsity))
+    st = rng.choice(pool, n, replace=False)
+    st.sort()
+    return st
+
+
+def sweep_row_order(settings: Sequence[DASetting]) -> list:
+    """The batch rows of a sweep as indices into `settings`: the no-DA rows, the nudging rows, then the OI rows
+    grouped by station density (in order of first appearance) and sorted by corr_len inside a group; ties keep the
+    order of `settings`."""
+    idx = range(len(settings))
+    dens = []
+    for s in settings:
+        if s.method == "oi" and s.sparsity not in dens:
+            dens.append(s.sparsity)
+    order = [i for i in idx if settings[i].method == "none"] + [i for i in idx if settings[i].method == "nudging"]
+    for d in dens:
+        order += sorted((i for i in idx if settings[i].method == "oi" and settings[i].sparsity == d),
+                        key=lambda i: settings[i].corr_len)
+    return order
+
+
+class DASweepAssimilator:
+    """Assimilates batch row `row_of[label]` of a [S, G, C] step with setting `label`, all rows against one truth.
+
+    oi_grid: (lats, lons) as `OptimalInterpolation` takes them (`flat_grid`, `roi_idx` likewise).  pool: the grid
+    indices stations are drawn from; every distinct `sparsity` is one `station_network(pool, sparsity, seed)`, shared
+    by the nudging and OI settings of that density.  channels: the observed channels (None: all).  Rows are ordered by
+    `sweep_row_order`; `settings_by_row[r]` is the setting of row r.
+
+    `apply_(step3, truth3)`: step3 [S, G, C] in place, truth3 [1, G, C] (or [S, G, C]) the unmasked truth - it is read
+    at stations and observed channels only.  One `gcl_nudge_rows` covers the nudging rows; per OI density one
+    innovation, one solve per setting (against the factor of its (sigma_b, sigma_o, corr_len), cached by the
+    `OptimalInterpolation` of that triple) and one `gcl_oi_analysis_rows`.  Every row gets the bits of its own
+    `NudgingAssimilator` / `OINetwork` at batch 1 on NaN-masked observations; `per_setting=True` runs exactly those
+    instead (A/B and fallback).  No host sync after `prepare(C)` (implied by the first call), so calls can be
+    captured."""
+
+    broadcast_obs = True  # assimilated_rollout: observations of batch 1 serve every row
+
+    def __init__(self, oi_grid, settings: Sequence[DASetting], pool, seed: int = 42, channels=None,
+                 flat_grid: bool = False, roi_idx=None, device="cuda", per_setting: bool = False):
+        self.settings = list(settings)
+        labels = [s.label for s in self.settings]
+        if not labels or len(set(labels)) != len(labels):
+            raise ValueError("DASweepAssimilator: the settings need distinct labels (and at least one)")
+        self.device = device
+        self.channels = None if channels is None else [int(c) for c in channels]
+        self.per_setting = bool(per_setting)
+        self.order = sweep_row_order(self.settings)
+        self.settings_by_row = [self.settings[i] for i in self.order]
+        self.row_of = {s.label: r for r, s in enumerate(self.settings_by_row)}
+        self.S = len(self.settings)
+        self._oi_args = (oi_grid[0], oi_grid[1], bool(flat_grid), roi_idx)
+        self.G = len(oi_grid[0]) if flat_grid else len(oi_grid[0]) * len(oi_grid[1])
+        rows = self.settings_by_row
+        # one station network per density, shared by nudging and OI
+        self.densities = []
+        for s in rows:
+            if s.method != "none" and s.sparsity not in self.densities:
+                self.densities.append(s.sparsity)
+        self.networks = {d: station_network(pool, d, seed) for d in self.densities}
+        for st in self.networks.values():
+            if st.min() < 0 or st.max() >= self.G:
+                raise ValueError("station index outside the grid")
+        self._nud = [r for r, s in enumerate(rows) if s.method == "nudging"]  # contiguous by construction
+        self._groups = []  # OI rows of one density: contiguous, corr_len ascending
+        for d in self.densities:
+            grp = [r for r, s in enumerate(rows) if s.method == "oi" and s.sparsity == d]
+            if grp:
+                self._groups.append({"r0": grp[0], "n": len(grp), "density": d})
+        self.nudgers, self.oi_nets, self._oi, self._C = {}, {}, {}, None
+
+    def prepare(self, C: int) -> None:
+        """Factor the station covariances (one per distinct (network, sigma_b, sigma_o, corr_len), through one
+        `OptimalInterpolation` per parameter triple), upload the tables and allocate the workspaces for C channels."""
+        if self._C == C:
+            return
+        dev = torch.device(self.device)
+        if dev.type == "cuda" and dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        rows = self.settings_by_row
+        chans = list(range(C)) if self.channels is None else self.channels
+        if any(c < 0 or c >= C for c in chans):
+            raise ValueError(f"observed channel outside [0, {C})")
+        self._chan_mask, chan_sel = None, None
+        if self.channels is not None:
+            chan_sel = torch.zeros(C, dtype=torch.bool)
+            chan_sel[chans] = True
+            self._chan_mask = chan_sel.to(dev, torch.uint8)
+        mask = np.zeros((max(len(self.densities), 1), self.G), dtype=np.uint8)
+        for n, d in enumerate(self.densities):
+            mask[n, self.networks[d]] = 1
+        self._station_mask = torch.from_numpy(mask).to(dev)
+        if self._nud:
+            self._nud_rows = (self._nud[0], self._nud[-1] + 1)
+            self._nud_net = torch.tensor([self.densities.index(rows[r].sparsity) for r in self._nud],
+                                         dtype=torch.int32).to(dev)
+            self._nud_alpha = torch.from_numpy(np.array([_nudge_coeffs(rows[r].alpha)[1] for r in self._nud],
+                                                        dtype=np.float32)).to(dev)
+            self.nudgers = {r: NudgingAssimilator(alpha=rows[r].alpha, device=dev, feature_mask_flat=chan_sel)
+                            for r in self._nud}
+            for nud in self.nudgers.values():
+                nud.prepare(C, dev)
+        lats, lons, flat_grid, roi_idx = self._oi_args
+        nch = len(chans)
+        for g in self._groups:
+            r0, n = g["r0"], g["n"]
+            for r in range(r0, r0 + n):
+                if r in self.oi_nets:
+                    continue
+                s = rows[r]
+                key = (s.sigma_b, s.sigma_o, s.corr_len)
+                if key not in self._oi:
+                    self._oi[key] = OptimalInterpolation(lats, lons, s.sigma_b, s.sigma_o, s.corr_len, dev,
+                                                         flat_grid=flat_grid, roi_idx=roi_idx)
+                self.oi_nets[r] = self._oi[key].prepare_network(self.networks[g["density"]], self.channels)
+            nets = [self.oi_nets[r] for r in range(r0, r0 + n)]
+            fac = nets[0].fac  # the station set, hence obs_row / node_row / stations, is the group's
+            widest = max(nets, key=lambda t: t.oi.L).oi
+            g.update(nets=nets, fac=fac, nodes=widest._nodes, node_row=widest._node_row,
+                     th_cut=widest._th_cut, a_cut=widest._a_cut,
+                     chans=torch.tensor(chans, dtype=torch.int32).to(dev),
+                     sb2=torch.from_numpy(np.array([t.oi._sb2 for t in nets], dtype=np.float32)).to(dev),
+                     rl2=torch.from_numpy(np.array([t.oi._rl2 for t in nets], dtype=np.float32)).to(dev),
+                     rhs=torch.empty(n * nch, fac.m, dtype=torch.float64, device=dev),
+                     tmp=torch.empty(n * nch, fac.m, dtype=torch.float64, device=dev),
+                     W=torch.empty(n * nch, fac.m, dtype=torch.float32, device=dev))
+            for t in nets:
+                t.prepare(C, 1)
+        # per_setting: the NaN-masked observations each density's nudgers expect (OI reads stations only)
+        self._masked = {}
+        if self.per_setting and self._nud:
+            self._masked = {d: torch.empty(1, self.G, C, dtype=torch.float32, device=dev) for d in self.densities}
+            self._nan = torch.full((1, 1, 1), float("nan"), dtype=torch.float32, device=dev)
+        self._C = C
+
+    def _apply_per_setting(self, f3, o3):
+        for n, d in enumerate(self.densities):
+            if d in self._masked:
+                assert o3.shape[0] == 1, "per_setting takes one truth for all rows"
+                torch.where(self._station_mask[n].bool().view(1, -1, 1), o3, self._nan, out=self._masked[d])
+        for r in self._nud:
+            self.nudgers[r].apply_(f3[r:r + 1], self._masked[self.settings_by_row[r].sparsity])
+        for r, net in self.oi_nets.items():
+            net.apply_(f3[r:r + 1], o3 if o3.shape[0] == 1 else o3[r:r + 1])
+        return f3
+
+    def apply_(self, f3: torch.Tensor, o3: torch.Tensor) -> torch.Tensor:
+        S, G, C = f3.shape
+        if S != self.S or G != self.G:
+            raise RuntimeError(f"a sweep of {self.S} settings on {self.G} nodes got a step of shape {tuple(f3.shape)}")
+        if o3.shape[0] not in (1, S) or tuple(o3.shape[1:]) != (G, C):
+            raise RuntimeError(f"observations {tuple(o3.shape)} do not match the step {tuple(f3.shape)}")
+        self.prepare(C)
+        if self.per_setting:
+            return self._apply_per_setting(f3, o3)
+        rows_of = (lambda a, b: o3) if o3.shape[0] == 1 else (lambda a, b: o3[a:b])  # noqa: E731
+        if self._nud:
+            a, b = self._nud_rows
+            hip.nudge_rows(f3[a:b], rows_of(a, b), f3[a:b], self._station_mask, self._nud_net, self._nud_alpha,
+                           self._chan_mask)
+        for g in self._groups:
+            if not g["chans"].numel():
+                continue
+            a, n = g["r0"], g["n"]
+            nch = g["chans"].numel()
+            fac, fg = g["fac"], f3[a:a + n]
+            obs = rows_of(a, a + n)
+            hip.oi_innovation(obs.expand(n, G, C) if obs.shape[0] != n else obs, fg, fac.obs_row, fac.node_row,
+                              g["chans"], g["rhs"])
+            for j, net in enumerate(g["nets"]):
+                sl = slice(j * nch, (j + 1) * nch)
+                hip.oi_solve(net.fac.M, g["rhs"][sl], g["tmp"][sl], g["W"][sl])
+            hip.oi_analysis_rows(fg, fg, g["chans"], g["node_row"], g["nodes"], fac.stations, g["W"], g["sb2"],
+                                 g["rl2"], g["th_cut"], g["a_cut"])
+        return f3
+
+
+# ======================================================================================================================
 # Assimilated rollout
 # ======================================================================================================================
 @torch.no_grad()
@@ -444,7 +679,8 @@ def assimilated_rollout(model, X: torch.Tensor, ar_steps: int, obs: torch.Tensor
     """`predict.rollout` with assimilation: each completed step (after the residual, the static carry-forward and the
     forcing) is assimilated against `obs[..., s*C:(s+1)*C]` while `k is None or s < k`, then stored and shifted into
     the window.  `assimilator`: a `NudgingAssimilator` or an `OINetwork`.  X [B, G, obs*C] (or [G, obs*C]), obs
-    [B, G, ar_steps*C] on the GPU -> [B, G, ar_steps*C] on the GPU.
+    [B, G, ar_steps*C] on the GPU -> [B, G, ar_steps*C] on the GPU.  With a `DASweepAssimilator` B is its number of
+    settings (X the same window in every row) and obs may be the truth once, [1, G, ar_steps*C].
 
     With use_residual=False and no static or forcing channels this is the reference's sequential-nudging loop
     (nudging.py:159-194) and OI loop (scripts/predict.py:499-510)."""
@@ -455,7 +691,8 @@ def assimilated_rollout(model, X: torch.Tensor, ar_steps: int, obs: torch.Tensor
     B, G, _ = X.shape
     nobs = model.obs_window
     C = X.shape[-1] // nobs
-    if obs.shape[0] != B or obs.shape[1] != G or obs.shape[2] < ar_steps * C:
+    one_obs = obs.shape[0] == 1 and getattr(assimilator, "broadcast_obs", False)  # one truth for all rows of a sweep
+    if (obs.shape[0] != B and not one_obs) or obs.shape[1] != G or obs.shape[2] < ar_steps * C:
         raise ValueError(f"observations {tuple(obs.shape)} do not cover {ar_steps} steps of [{B}, {G}, {C}]")
     state = X.reshape(B, G, nobs, C).contiguous()
     if kinds is None:

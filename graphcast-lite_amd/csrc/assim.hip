@@ -9,6 +9,8 @@
 // hot kernel, evaluates the kernel in float32 from float64 coordinate differences and accumulates in float32.
 #include "common.h"
 
+#include <initializer_list>
+
 namespace {
 
 constexpr int kMaxStations = 16384;  // one float64 m x m factor: 2 GiB at the limit
@@ -39,6 +41,37 @@ __global__ __launch_bounds__(256) void nudge_kernel(const float* __restrict__ f,
         v = fv + gcl::rounded(c1 * (ov - fv));  // f + alpha (o - f)               (nudging.py:91-92)
       else
         v = gcl::rounded(c0 * fv) + gcl::rounded(c1 * ov);  // (1 - alpha) f + alpha o  (nudging.py:205)
+    }
+    out[b * bst + (int64_t)g * ldt + c] = v;
+  }
+}
+
+// The sequential form with one setting per batch row: row b is nudged with alpha[b] at the stations of network
+// net_of_row[b] (station_mask [n_net][G]; net < 0: the row is not nudged).  Observations are read only at stations, so
+// the truth can be passed as it is (bso = 0 broadcasts it); in place (out == f) only nudged values are touched.
+__global__ __launch_bounds__(256) void nudge_rows_kernel(const float* f, int64_t ldf, int64_t bsf,
+                                                        const float* __restrict__ o, int64_t ldo, int64_t bso,
+                                                        const uint8_t* __restrict__ station_mask,
+                                                        const int32_t* __restrict__ net_of_row,
+                                                        const float* __restrict__ alpha,
+                                                        const uint8_t* __restrict__ mask, float* out, int64_t ldt,
+                                                        int64_t bst, int32_t B, int32_t G, int32_t C) {
+  const int64_t total = (int64_t)B * G * C;
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  const bool in_place = out == f;
+  for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < total; t += stride) {
+    const int c = (int)(t % C);
+    const int64_t r = t / C;
+    const int g = (int)(r % G);
+    const int64_t b = r / G;
+    const int net = net_of_row[b];
+    const bool at_station = net >= 0 && station_mask[(int64_t)net * G + g] && (!mask || mask[c]);
+    if (!at_station && in_place) continue;
+    const float fv = f[b * bsf + (int64_t)g * ldf + c];
+    float v = fv;
+    if (at_station) {
+      const float ov = o[b * bso + (int64_t)g * ldo + c];
+      if (!__builtin_isnan(ov)) v = fv + gcl::rounded(alpha[b] * (ov - fv));  // nudge_kernel, form 0
     }
     out[b * bst + (int64_t)g * ldt + c] = v;
   }
@@ -174,6 +207,20 @@ __global__ __launch_bounds__(256) void oi_innov_kernel(const float* __restrict__
 // ---------------------------------------------------------------------------------------------------------------
 constexpr int kTile = 128;
 
+// The pair geometry of both analysis kernels: the haversine angle theta of node (la, lo, ci = cos la) and station
+// (sla, slo, sc), false when the pair is beyond the cut (theta is then not computed).
+__device__ __forceinline__ bool oi_pair_theta(double la, double lo, float ci, double sla, double slo, float sc,
+                                              float th_cut, float a_cut, float& th) {
+  const float dlat = (float)(la - sla);
+  if (!(fabsf(dlat) <= th_cut)) return false;
+  const float dlon = (float)(lo - slo);
+  const float s1 = sinf(0.5f * dlat), s2 = sinf(0.5f * dlon);
+  const float a = s1 * s1 + (ci * sc) * (s2 * s2);
+  if (!(a <= a_cut)) return false;
+  th = 2.f * asinf(sqrtf(fminf(a, 1.f)));
+  return true;
+}
+
 template <int NCH>
 __global__ __launch_bounds__(256) void oi_analysis_kernel(
     const float* xb, int64_t ldx, int64_t bsx, float* xa, int64_t lda, int64_t bsa, const int32_t* __restrict__ chans,
@@ -208,17 +255,9 @@ __global__ __launch_bounds__(256) void oi_analysis_kernel(
     }
     __syncthreads();
     for (int k = 0; k < nk; ++k) {
-      const float dlat = (float)(la - s_lat[k]);
-      float w = 0.f;
-      if (live && fabsf(dlat) <= th_cut) {
-        const float dlon = (float)(lo - s_lon[k]);
-        const float s1 = sinf(0.5f * dlat), s2 = sinf(0.5f * dlon);
-        const float a = s1 * s1 + (ci * s_cos[k]) * (s2 * s2);
-        if (a <= a_cut) {
-          const float th = 2.f * asinf(sqrtf(fminf(a, 1.f)));
-          w = sb2 * expf(-rl2 * (th * th));
-        }
-      }
+      float w = 0.f, th;
+      if (live && oi_pair_theta(la, lo, ci, s_lat[k], s_lon[k], s_cos[k], th_cut, a_cut, th))
+        w = sb2 * expf(-rl2 * (th * th));
       if (__any(w != 0.f)) {
 #pragma unroll
         for (int q = 0; q < NCH; ++q) acc[q] = fmaf(w, s_w[k][q], acc[q]);
@@ -249,6 +288,109 @@ int launch_analysis(hipStream_t st, int nblk, int ncol, const float* xb, int64_t
   return GCL_OK;
 }
 
+// The analysis with one (sb2, rl2) per sample.  A block column is NS consecutive samples x CC of their nch
+// channels (the same channel chunk of every sample), so which accumulator belongs to which sample is known at compile
+// time.  The pair geometry is computed once for the NS * CC columns; expf once per run of equal rl2 among the NS
+// samples (the caller orders the samples so that equal rl2 are adjacent), w = sb2 e once per sample.  (th_cut, a_cut)
+// are those of the longest correlation length: inside them a sample of a shorter one gets e == 0 from the underflow
+// of expf itself, and a wave whose lanes all have e == 0 for a sample skips that sample's CC FMAs.  The settings of
+// the NS samples are block-uniform (scalar registers, scalar branches).
+template <int NS, int CC>
+__global__ __launch_bounds__(256) void oi_analysis_rows_kernel(
+    const float* xb, int64_t ldx, int64_t bsx, float* xa, int64_t lda, int64_t bsa, const int32_t* __restrict__ chans,
+    int32_t nch, const int32_t* __restrict__ node_row, const double* __restrict__ nlat,
+    const double* __restrict__ nlon, const float* __restrict__ ncos, int32_t n_nodes, const double* __restrict__ slat,
+    const double* __restrict__ slon, const float* __restrict__ scos, const float* __restrict__ W, int32_t m,
+    int32_t B, int32_t nchunk, const float* __restrict__ sb2_row, const float* __restrict__ rl2_row, float th_cut,
+    float a_cut) {
+  constexpr int NCOL = NS * CC;
+  __shared__ double s_lat[kTile], s_lon[kTile];
+  __shared__ float s_cos[kTile];
+  __shared__ float s_w[kTile][NCOL];
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  const int b0 = (blockIdx.y / nchunk) * NS;   // first sample
+  const int c0 = (blockIdx.y % nchunk) * CC;   // first channel (position in chans)
+  const int nb = B - b0 < NS ? B - b0 : NS;
+  const int nc = nch - c0 < CC ? nch - c0 : CC;
+  const bool live = i < n_nodes;
+  const double la = live ? nlat[i] : 0.0, lo = live ? nlon[i] : 0.0;
+  const float ci = live ? ncos[i] : 0.f;
+  float sb2[NS], rl2[NS];
+#pragma unroll
+  for (int s = 0; s < NS; ++s) {
+    const int b = b0 + (s < nb ? s : nb - 1);  // padding samples repeat the last one (their W is 0)
+    sb2[s] = sb2_row[b];
+    rl2[s] = rl2_row[b];
+  }
+  float acc[NS][CC];
+#pragma unroll
+  for (int s = 0; s < NS; ++s)
+#pragma unroll
+    for (int c = 0; c < CC; ++c) acc[s][c] = 0.f;
+  for (int k0 = 0; k0 < m; k0 += kTile) {
+    const int nk = m - k0 < kTile ? m - k0 : kTile;
+    __syncthreads();
+    for (int t = threadIdx.x; t < kTile; t += 256) {
+      const bool ok = t < nk;
+      s_lat[t] = ok ? slat[k0 + t] : 0.0;
+      s_lon[t] = ok ? slon[k0 + t] : 0.0;
+      s_cos[t] = ok ? scos[k0 + t] : 0.f;
+    }
+    for (int t = threadIdx.x; t < kTile * NCOL; t += 256) {
+      const int q = t / kTile, k = t % kTile;  // consecutive threads: consecutive stations of one W row
+      const int s = q / CC, c = q % CC;
+      s_w[k][q] = (s < nb && c < nc && k < nk) ? W[((int64_t)(b0 + s) * nch + c0 + c) * m + k0 + k] : 0.f;
+    }
+    __syncthreads();
+    for (int k = 0; k < nk; ++k) {
+      float th = 0.f;
+      const bool near = live && oi_pair_theta(la, lo, ci, s_lat[k], s_lon[k], s_cos[k], th_cut, a_cut, th);
+      if (!__any(near)) continue;
+      const float th2 = th * th;
+      float e = 0.f;
+      bool any_e = false;
+#pragma unroll
+      for (int s = 0; s < NS; ++s) {
+        if (s == 0 || rl2[s] != rl2[s - 1]) {
+          e = near ? expf(-rl2[s] * th2) : 0.f;
+          any_e = __any(e != 0.f);
+        }
+        if (any_e) {
+          const float w = sb2[s] * e;
+#pragma unroll
+          for (int c = 0; c < CC; ++c) acc[s][c] = fmaf(w, s_w[k][s * CC + c], acc[s][c]);
+        }
+      }
+    }
+  }
+  if (!live) return;
+  const int64_t g = node_row ? node_row[i] : i;
+#pragma unroll
+  for (int s = 0; s < NS; ++s)
+#pragma unroll
+    for (int c = 0; c < CC; ++c)
+      if (s < nb && c < nc) {
+        const int ch = chans[c0 + c];
+        const int64_t b = b0 + s;
+        const float v = xb[b * bsx + g * ldx + ch];
+        xa[b * bsa + g * lda + ch] = v + acc[s][c];
+      }
+}
+
+template <int NS, int CC>
+int launch_analysis_rows(hipStream_t st, int nblk, const float* xb, int64_t ldx, int64_t bsx, float* xa, int64_t lda,
+                         int64_t bsa, const int32_t* chans, int32_t nch, const int32_t* node_row, const double* nlat,
+                         const double* nlon, const float* ncos, int32_t n_nodes, const double* slat,
+                         const double* slon, const float* scos, const float* W, int32_t m, int32_t B,
+                         const float* sb2_row, const float* rl2_row, float th_cut, float a_cut) {
+  const int nchunk = (int)gcl::cdiv(nch, CC);
+  hipLaunchKernelGGL((oi_analysis_rows_kernel<NS, CC>), dim3(nblk, (unsigned)(gcl::cdiv(B, NS) * nchunk)), dim3(256),
+                     0, st, xb, ldx, bsx, xa, lda, bsa, chans, nch, node_row, nlat, nlon, ncos, n_nodes, slat, slon,
+                     scos, W, m, B, nchunk, sb2_row, rl2_row, th_cut, a_cut);
+  GCL_CHECK_LAUNCH();
+  return GCL_OK;
+}
+
 }  // namespace
 
 extern "C" int gcl_oi_max_stations(void) { return kMaxStations; }
@@ -263,6 +405,20 @@ extern "C" int gcl_nudge(const float* f, int64_t ldf, int64_t bsf, const float* 
   if (total == 0) return GCL_OK;
   hipLaunchKernelGGL(nudge_kernel, dim3(gcl::grid_for(total, 4096)), dim3(256), 0, (hipStream_t)stream, f, ldf, bsf, o, ldo, bso,
                      chan_mask, c0, c1, form, out, ldt, bst, B, G, C);
+  GCL_CHECK_LAUNCH();
+  return GCL_OK;
+}
+
+extern "C" int gcl_nudge_rows(const float* f, int64_t ldf, int64_t bsf, const float* o, int64_t ldo, int64_t bso,
+                              const uint8_t* station_mask, int32_t n_net, const int32_t* net_of_row,
+                              const float* alpha, const uint8_t* chan_mask, float* out, int64_t ldt, int64_t bst,
+                              int32_t B, int32_t G, int32_t C, gcl_stream_t stream) {
+  GCL_CHECK_ARG(f && o && out && station_mask && net_of_row && alpha, "nudge_rows: null argument");
+  GCL_CHECK_ARG(B > 0 && G >= 0 && C > 0 && n_net > 0 && ldf >= C && ldo >= C && ldt >= C, "nudge_rows: bad shape");
+  const int64_t total = (int64_t)B * G * C;
+  if (total == 0) return GCL_OK;
+  hipLaunchKernelGGL(nudge_rows_kernel, dim3(gcl::grid_for(total, 4096)), dim3(256), 0, (hipStream_t)stream, f, ldf,
+                     bsf, o, ldo, bso, station_mask, net_of_row, alpha, chan_mask, out, ldt, bst, B, G, C);
   GCL_CHECK_LAUNCH();
   return GCL_OK;
 }
@@ -340,4 +496,46 @@ extern "C" int gcl_oi_analysis(const float* xb, int64_t ldx, int64_t bsx, float*
                                n_nodes, slat, slon, scos, W, m, sb2, rl2, th_cut, a_cut);
   return launch_analysis<32>(st, nblk, ncol, xb, ldx, bsx, xa, lda, bsa, chans, nch, node_row, nlat, nlon, ncos,
                              n_nodes, slat, slon, scos, W, m, sb2, rl2, th_cut, a_cut);
+}
+
+extern "C" int gcl_oi_analysis_rows(const float* xb, int64_t ldx, int64_t bsx, float* xa, int64_t lda, int64_t bsa,
+                                    const int32_t* chans, int32_t nch, const int32_t* node_row, const double* nlat,
+                                    const double* nlon, const float* ncos, int32_t n_nodes, const double* slat,
+                                    const double* slon, const float* scos, const float* W, int32_t m,
+                                    const float* sb2_row, const float* rl2_row, float th_cut, float a_cut, int32_t B,
+                                    gcl_stream_t stream) {
+  GCL_CHECK_ARG(xb && xa && chans && nlat && nlon && ncos && slat && slon && scos && W && sb2_row && rl2_row,
+                "oi_analysis_rows: null argument");
+  GCL_CHECK_ARG(n_nodes >= 0 && m > 0 && nch > 0 && B > 0, "oi_analysis_rows: bad shape");
+  if (n_nodes == 0) return GCL_OK;
+  const hipStream_t st = (hipStream_t)stream;
+  const int nblk = (int)gcl::cdiv(n_nodes, 256);
+  // samples per block (ascending widths): the fewest sample groups, i.e. evaluations of the pair geometry, then the
+  // narrowest block; a padding sample costs FMAs on zeros only
+  const auto pick = [B](std::initializer_list<int> widths) {
+    int best = 0;
+    int64_t best_groups = 0;
+    for (int ns : widths) {
+      const int64_t groups = gcl::cdiv(B, ns);
+      if (best == 0 || groups < best_groups) best = ns, best_groups = groups;
+    }
+    return best;
+  };
+#define GCL_ROWS(NS, CC)                                                                                             \
+  return launch_analysis_rows<NS, CC>(st, nblk, xb, ldx, bsx, xa, lda, bsa, chans, nch, node_row, nlat, nlon, ncos, \
+                                      n_nodes, slat, slon, scos, W, m, B, sb2_row, rl2_row, th_cut, a_cut)
+  if (nch <= 4) {
+    switch (pick({2, 4, 8})) {
+      case 2: GCL_ROWS(2, 4);
+      case 4: GCL_ROWS(4, 4);
+      default: GCL_ROWS(8, 4);
+    }
+  }
+  switch (pick({1, 2, 4, 6})) {
+    case 1: GCL_ROWS(1, 8);
+    case 2: GCL_ROWS(2, 8);
+    case 4: GCL_ROWS(4, 8);
+    default: GCL_ROWS(6, 8);
+  }
+#undef GCL_ROWS
 }

@@ -121,6 +121,8 @@ _SIGNATURES = {
                                        _i32, _vp]),
     "gcl_nudge": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _f32, _f32, _i32, _vp, _i64, _i64, _i32, _i32, _i32,
                             _vp]),
+    "gcl_nudge_rows": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32,
+                                 _i32, _vp]),
     "gcl_oi_max_stations": (C.c_int, []),
     "gcl_oi_station_cov": (C.c_int, [_vp, _vp, _i32, C.c_double, C.c_double, C.c_double, _vp, _vp]),
     "gcl_oi_factor": (C.c_int, [_vp, _i32, _vp]),
@@ -128,6 +130,8 @@ _SIGNATURES = {
     "gcl_oi_innovation": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp]),
     "gcl_oi_analysis": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp,
                                   _vp, _i32, _f32, _f32, _f32, _f32, _i32, _vp]),
+    "gcl_oi_analysis_rows": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp,
+                                       _vp, _vp, _i32, _vp, _vp, _f32, _f32, _i32, _vp]),
     "gcl_verify_colstats_ws_bytes": (_sz, [_i32, _i32, _i32, _i32]),
     "gcl_verify_colstats": (C.c_int, [_vp, _i64, _i64, _i32, _i32] + [_vp, _i64, _i64, _vp] * 4
                             + [_vp, _i32, _i32, _vp, _vp, _sz, _vp]),
@@ -1118,6 +1122,26 @@ def nudge(f3, o3, out3, c0: float, c1: float, form: int, chan_mask=None):
     return out3
 
 
+def nudge_rows(f3, o3, out3, station_mask, net_of_row, alpha, chan_mask=None):
+    """out3 = f3 nudged row by row (see gcl_nudge_rows): row b with alpha[b] (float32 [B]) at the stations of network
+    net_of_row[b] (int32 [B], -1: not nudged) of station_mask (uint8 [n_net, G]).  o3 is [B, G, C] or [1, G, C] (one
+    truth for every row).  out3 may be f3."""
+    B, G, Cc = f3.shape
+    assert out3.shape == f3.shape and o3.shape[1:] == f3.shape[1:] and o3.shape[0] in (1, B)
+    assert f3.stride(2) == 1 and o3.stride(2) == 1 and out3.stride(2) == 1
+    assert station_mask.is_cuda and station_mask.dtype == torch.uint8 and station_mask.is_contiguous()
+    assert station_mask.dim() == 2 and station_mask.shape[1] == G
+    assert net_of_row.dtype == torch.int32 and net_of_row.numel() == B and alpha.numel() == B
+    if chan_mask is not None:
+        assert chan_mask.is_cuda and chan_mask.dtype == torch.uint8 and chan_mask.numel() == Cc
+    _check(lib().gcl_nudge_rows(_p(f3), f3.stride(1), f3.stride(0), _p(o3), o3.stride(1),
+                                o3.stride(0) if o3.shape[0] == B and B > 1 else 0, station_mask.data_ptr(),
+                                station_mask.shape[0], _pi(net_of_row), _p(alpha),
+                                chan_mask.data_ptr() if chan_mask is not None else None, _p(out3), out3.stride(1),
+                                out3.stride(0), B, G, Cc, _stream()))
+    return out3
+
+
 def oi_max_stations() -> int:
     return int(lib().gcl_oi_max_stations())
 
@@ -1162,6 +1186,22 @@ def oi_analysis(xb3, xa3, chans, node_row, nodes, stations, W, sb2: float, rl2: 
                                  _pi(chans), nch, _pi(node_row), _pd(nlat), _pd(nlon), _p(ncos), nlat.numel(),
                                  _pd(slat), _pd(slon), _p(scos), _p(W), m, float(sb2), float(rl2), float(th_cut),
                                  float(a_cut), B, _stream()))
+    return xa3
+
+
+def oi_analysis_rows(xb3, xa3, chans, node_row, nodes, stations, W, sb2_row, rl2_row, th_cut: float, a_cut: float):
+    """`oi_analysis` with one (sb2, rl2) per sample: float32 device tables [B] (see gcl_oi_analysis_rows); th_cut /
+    a_cut those of the longest correlation length."""
+    B = xb3.shape[0]
+    nlat, nlon, ncos = nodes
+    slat, slon, scos = stations
+    m, nch = slat.numel(), chans.numel()
+    assert xb3.stride(2) == 1 and xa3.stride(2) == 1 and W.shape == (B * nch, m) and W.is_contiguous()
+    assert sb2_row.numel() == B and rl2_row.numel() == B
+    _check(lib().gcl_oi_analysis_rows(_p(xb3), xb3.stride(1), xb3.stride(0), _p(xa3), xa3.stride(1), xa3.stride(0),
+                                      _pi(chans), nch, _pi(node_row), _pd(nlat), _pd(nlon), _p(ncos), nlat.numel(),
+                                      _pd(slat), _pd(slon), _p(scos), _p(W), m, _p(sb2_row), _p(rl2_row),
+                                      float(th_cut), float(a_cut), B, _stream()))
     return xa3
 
 

@@ -12,6 +12,8 @@ module adds the glue between them (csrc/pipeline.hip) so that a sample never ret
 * `FullPipelineEvaluator`: the sample loop of `:449-666` and the tables of `:678-766`.
 * `MosIdwSweep`: the IDW parameter sweeps of `scripts/mos_idw_sweep.py` (multires frames, AR rollout) and
   `scripts/mos_idw_sweep_v2.py` (merged data set, +6 h), every setting scored by one kernel (`LearnedMOS.sweep`).
+* `DaSweep`, `da_sweep_tables`: the DA grid search of `scripts/da_grid_search.sh` / `da_experiments_v*.sh` and the tables
+  of `scripts/parse_da_results.py`: every nudging / OI setting is one batch row of one assimilated rollout.
 """
 from typing import Optional, Sequence
 
@@ -21,6 +23,7 @@ import torch
 from . import hip
 from .mos import IDW_SWEEP_CONFIGS, LearnedMOS
 from .predict import rollout
+from .verify import ForecastVerifier, Persistence
 
 VARIANTS = ("GNN", "GNN+lapse", "GNN+MOS", "GNN+lapse+MOS", "GNN+lapse+MOS+IDW", "GNN+lapse+MOS+IDW+OI", "Persistence")
 
@@ -461,3 +464,154 @@ class MosIdwSweep:
         for p, c in enumerate(self.configs):
             se[f"GNN+lapse+MOS+IDW_{c[2]}"] = idw[p]
         return sweep_tables(se, self.count, self.configs)
+
+
+# ======================================================================================================================
+# The DA grid search (scripts/da_grid_search.sh, da_experiments_v2.sh / _v3.sh / _merge.sh, parse_da_results.py)
+# ======================================================================================================================
+def _scores(pred, base) -> dict:
+    """The figures `predict.py` prints for one pair of StreamingMetrics (`:636`, `:651-652`, `:723-740`)."""
+    sp, sb = pred._split(), base._split()
+    rmse = float(np.sqrt(sp["sum_se"] / max(sp["total_elem"], 1)))
+    base_rmse = float(np.sqrt(sb["sum_se"] / max(sb["total_elem"], 1)))
+    dyn = [c for c in range(pred.C) if c not in pred.exclude_channels]
+
+    def acc(s):
+        apc = s["sum_acc"] / np.maximum(s["acc_count"], 1)
+        return float(apc[dyn].mean()) if dyn else 0.0
+
+    return {"rmse": rmse, "base_rmse": base_rmse, "skill": float((1.0 - rmse / (base_rmse + 1e-12)) * 100),
+            "acc": acc(sp), "base_acc": acc(sb),
+            "rmse_per_channel": [float(v) for v in np.sqrt(sp["sum_se_per_ch"] / np.maximum(sp["elem_per_ch"], 1))]}
+
+
+def da_sweep_tables(verifiers: Sequence[ForecastVerifier], settings) -> dict:
+    """The tables of the grid search from one `ForecastVerifier` (methods "pred", "base") per setting, in the order of
+    `settings` (host only).
+
+    per_setting[label]: the setting's fields, `global` (overall scores; `global["skill"]` is `predict.py`'s "Skill"),
+    `global_horizon` [h], and with a region `region`, `region_horizon` [h] - each a dict of rmse, base_rmse, skill
+    (percent against persistence), acc, base_acc and rmse_per_channel - plus `skill_6h`: the skill of the first
+    horizon on the region (the whole grid without one; the overall figure when there is a single horizon), the
+    figure `parse_da_results.py` tabulates.
+    oi_tables[density]: its corr_len x sigma_o table of skill_6h (`make_oi_table`): corr_lens_km and sigma_os
+    ascending, `skill[i][j]` or None where that pair was not run (the last one run wins when a pair repeats).
+    best[(method, density)]: the label with the largest skill_6h, the first on a tie.  Densities are percent strings
+    ("10", "1") as in the labels."""
+    from .assimilation import _density_tag
+
+    settings = list(settings)
+    if len(verifiers) != len(settings):
+        raise ValueError(f"{len(verifiers)} verifiers for {len(settings)} settings")
+    res = {"settings": [s.label for s in settings], "per_setting": {}, "oi_tables": {}, "best": {}}
+    for s, v in zip(settings, verifiers):
+        row = {"method": s.method, "sparsity": s.sparsity, "alpha": s.alpha, "sigma_b": s.sigma_b,
+               "sigma_o": s.sigma_o, "corr_len": s.corr_len,
+               "global": _scores(v.overall["pred"], v.overall["base"]),
+               "global_horizon": [_scores(p, b) for p, b in zip(v.horizon["pred"], v.horizon["base"])]}
+        scope, scope_h = row["global"], row["global_horizon"]
+        if v.region["pred"] is not None:
+            row["region"] = scope = _scores(v.region["pred"], v.region["base"])
+            row["region_horizon"] = scope_h = [_scores(p, b) for p, b in
+                                               zip(v.region_horizon["pred"], v.region_horizon["base"])]
+        row["skill_6h"] = (scope_h[0] if scope_h else scope)["skill"]
+        res["per_setting"][s.label] = row
+    for s in settings:
+        if s.method == "none":
+            continue
+        d, skill = _density_tag(s.sparsity), res["per_setting"][s.label]["skill_6h"]
+        best = res["best"].get((s.method, d))
+        if best is None or skill > res["per_setting"][best]["skill_6h"]:
+            res["best"][(s.method, d)] = s.label
+    for d in dict.fromkeys(_density_tag(s.sparsity) for s in settings if s.method == "oi"):
+        mine = [s for s in settings if s.method == "oi" and _density_tag(s.sparsity) == d]
+        corr = sorted({s.corr_len / 1000.0 for s in mine})
+        sig = sorted({s.sigma_o for s in mine})
+        table = [[None] * len(sig) for _ in corr]
+        for s in mine:
+            table[corr.index(s.corr_len / 1000.0)][sig.index(s.sigma_o)] = res["per_setting"][s.label]["skill_6h"]
+        res["oi_tables"][d] = {"corr_lens_km": corr, "sigma_os": sig, "skill": table}
+    return res
+
+
+class DaSweep:
+    """The DA grid search on the device: per sample ONE assimilated rollout whose batch rows are the settings (the
+    input window replicated, the truth passed once as the observations), every row scored by its own
+    `verify.ForecastVerifier` against the truth and persistence - the reference starts `scripts/predict.py` once per
+    setting and rolls the same samples through the same network each time.
+
+    dataset: any `batch(indices) -> (X [B, G, obs*C], Y [B, G, >= ar_steps*C])` data set on the GPU.  settings:
+    `assimilation.DASetting`s (`assimilation.da_grid`).  pool: the grid indices stations are drawn from
+    (`--obs-roi-only`: region_idxs); region_idxs: the scored region and, as in `predict.py:382-386`, the OI nodes.
+    exclude_channels: left out of the aggregate metrics (static + forcing); obs_channels: the observed channel
+    indices (None: all); k: assimilate the first k steps only.  coordinates: the (lats, lons) of the grid in the
+    `OptimalInterpolation` convention (default `dataset.coordinates`), flat_grid: per-node coordinates (default
+    `dataset.flat_grid`, else False).  capture: replay the rollout from a hipGraph.
+
+    `update(sample_indices)` makes no host synchronisation; `results()` copies the sums to the host and returns
+    `da_sweep_tables`."""
+
+    def __init__(self, model, dataset, settings, ar_steps: int, pool, region_idxs=None, exclude_channels=None,
+                 obs_channels=None, k=None, use_residual: bool = False, static_channels=None, forcing_channels=None,
+                 seed: int = 42, capture: bool = True, coordinates=None, flat_grid=None):
+        from .assimilation import CapturedAssimilatedRollout, DASweepAssimilator
+
+        self.model, self.ds, self.settings, self.ar = model, dataset, list(settings), int(ar_steps)
+        self.device = torch.device(dataset.device)
+        self.obs = int(model.obs_window)
+        self.k, self.use_residual = k, bool(use_residual)
+        self.static_channels, self.forcing_channels = static_channels, forcing_channels
+        coords = coordinates if coordinates is not None else dataset.coordinates
+        flat = bool(getattr(dataset, "flat_grid", False)) if flat_grid is None else bool(flat_grid)
+        self.region_idxs = None if region_idxs is None else np.asarray(region_idxs, dtype=np.int64)
+        self.assimilator = DASweepAssimilator(coords, self.settings, pool, seed, channels=obs_channels, flat_grid=flat,
+                                              roi_idx=self.region_idxs, device=self.device)
+        self.S = len(self.settings)
+        self._rows = [self.assimilator.row_of[s.label] for s in self.settings]
+        self._rollout = CapturedAssimilatedRollout(model, self.ar, self.assimilator, k=k,
+                                                   static_channels=static_channels,
+                                                   forcing_channels=forcing_channels, use_residual=self.use_residual)
+        self._rollout.use_graph = bool(capture)
+        self._exclude = exclude_channels
+        self.verifiers, self._persist, self.n = None, None, 0
+
+    @property
+    def graph_active(self) -> bool:
+        return self._rollout.graph_active
+
+    def reset(self):
+        self.n = 0
+        for v in self.verifiers or []:
+            v.reset()
+
+    @torch.no_grad()
+    def update(self, sample_indices: Sequence[int]):
+        """Add the samples (data-set indices), one rollout of all settings each."""
+        ids = [int(i) for i in sample_indices]
+        if any(i < 0 or i >= len(self.ds) for i in ids):
+            raise ValueError(f"a sample index outside the {len(self.ds)} samples of the data set")
+        for i in ids:
+            X, Y = self.ds.batch([i])
+            C = X.shape[-1] // self.obs
+            if Y.shape[-1] < self.ar * C:
+                raise ValueError(f"the data set holds {Y.shape[-1] // C} target steps, the sweep assimilates {self.ar}")
+            if self.verifiers is None:
+                self.verifiers = [ForecastVerifier(C, self.ar, exclude_channels=self._exclude,
+                                                   region_idxs=self.region_idxs, device=self.device)
+                                  for _ in self.settings]
+                self._persist = Persistence(X[0], C)
+            truth = Y[:, :, :self.ar * C]
+            XS = X.expand(self.S, -1, -1)
+            yS = Y.expand(self.S, -1, -1) if self.forcing_channels else None
+            out = self._rollout(XS, truth, yS)
+            self._persist.X = X[0]
+            for v, r in zip(self.verifiers, self._rows):
+                v.update(truth[0], pred=out[r], base=self._persist)
+            self.n += 1
+
+    def results(self) -> dict:
+        if self.verifiers is None:
+            raise RuntimeError("DaSweep.results() before any update()")
+        res = da_sweep_tables(self.verifiers, self.settings)
+        res["n"] = self.n
+        return res

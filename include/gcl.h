@@ -594,6 +594,17 @@ int gcl_cross_update_fwd(const float* h, int64_t ld_h, int64_t bs_h, const float
 int gcl_nudge(const float* f, int64_t ldf, int64_t bsf, const float* obs, int64_t ldo, int64_t bso,
               const uint8_t* chan_mask, float c0, float c1, int32_t form, float* out, int64_t ldt,
               int64_t bst, int32_t B, int32_t G, int32_t C, gcl_stream_t stream);
+/* The sequential form (form 0) of gcl_nudge with one setting per batch row (the DA grid search: every row of
+ * one rollout carries another setting).  alpha[B] float32 (c1 of gcl_nudge, already rounded), net_of_row[B]
+ * the row's station network or -1 (the row is copied to out, or left untouched when out == f); station_mask
+ * uint8 [n_net][G], 1 = grid row g is a station of that network.  A value is nudged iff its row has a network,
+ * station_mask[net][g] != 0, chan_mask[c] != 0 (NULL: every channel) and the observation is not NaN;
+ * observations are read at stations only, so the truth can be passed once with bso = 0.  Same arithmetic
+ * as gcl_nudge. */
+int gcl_nudge_rows(const float* f, int64_t ldf, int64_t bsf, const float* obs, int64_t ldo, int64_t bso,
+                   const uint8_t* station_mask, int32_t n_net, const int32_t* net_of_row, const float* alpha,
+                   const uint8_t* chan_mask, float* out, int64_t ldt, int64_t bst, int32_t B, int32_t G,
+                   int32_t C, gcl_stream_t stream);
 /* Largest station count the OI factor accepts. */
 int gcl_oi_max_stations(void);
 /* OI station covariance (the `H @ B @ H.T + R + 1e-5 I` of src/assimilation/optimal_interpolation.py:
@@ -627,6 +638,17 @@ int gcl_oi_analysis(const float* xb, int64_t ldx, int64_t bsx, float* xa, int64_
                     const double* nlon, const float* ncos, int32_t n_nodes, const double* slat,
                     const double* slon, const float* scos, const float* W, int32_t m, float sb2, float rl2,
                     float th_cut, float a_cut, int32_t B, gcl_stream_t stream);
+/* gcl_oi_analysis with one (sb2, rl2) per sample: sb2_row[B], rl2_row[B] float32 device tables, sample
+ * b = col / nch.  (th_cut, a_cut) are those of the longest correlation length among the samples; samples
+ * with equal rl2 should be adjacent (the exponential is evaluated once per run of equal rl2 inside a block
+ * of columns, the pair geometry once per block).  Every sample gets the bits gcl_oi_analysis gives it with
+ * its own (sb2, rl2, th_cut, a_cut). */
+int gcl_oi_analysis_rows(const float* xb, int64_t ldx, int64_t bsx, float* xa, int64_t lda, int64_t bsa,
+                         const int32_t* chans, int32_t nch, const int32_t* node_row, const double* nlat,
+                         const double* nlon, const float* ncos, int32_t n_nodes, const double* slat,
+                         const double* slon, const float* scos, const float* W, int32_t m,
+                         const float* sb2_row, const float* rl2_row, float th_cut, float a_cut, int32_t B,
+                         gcl_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Forecast scoring and global -> regional blending (scripts/predict.py, scripts/predict_pipeline.py).
