@@ -31,7 +31,10 @@ namespace {
 // valid row and are masked with a select (not a multiply), so non-finite values cannot leak.
 // PRES: source rows with present[j] < 0 count as zero rows and are never read - their loads go to the zero page through
 // a pointer select, so the instruction stream and the arithmetic are those of the plain kernel (gcl_aggregate_present).
-template <int LPR, bool VL, bool VS, int EW, int ITER, bool PRES = false>
+// SPLIT: the source rows live in two tensors - row j of sample b is H + b * bsh + j * ldh for j < head, else
+// H2 + b * bsh2 + (j - head) * ldh2 (gcl_aggregate_split).  The kernel computes one address per gathered row anyway, so
+// the choice is a pointer select on the row index: no table, no extra load, the sums are those of the plain kernel.
+template <int LPR, bool VL, bool VS, int EW, int ITER, bool PRES = false, bool SPLIT = false>
 __global__ __launch_bounds__(256) void agg_kernel(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
                                                   const float* __restrict__ w, const int32_t* __restrict__ ecol,
                                                   const float* __restrict__ ew, const float* __restrict__ H,
@@ -39,7 +42,10 @@ __global__ __launch_bounds__(256) void agg_kernel(const int32_t* __restrict__ ro
                                                   float* __restrict__ Y, int64_t ldy, int64_t bsy, int32_t n,
                                                   int32_t B, int32_t F, int32_t nRB, int32_t xcd_map,
                                                   int32_t nt_store, const int32_t* __restrict__ order16,
-                                                  const int32_t* __restrict__ present = nullptr) {
+                                                  const int32_t* __restrict__ present = nullptr,
+                                                  const float* __restrict__ H2 = nullptr, int64_t ldh2 = 0,
+                                                  int64_t bsh2 = 0, int32_t head = 0) {
+  static_assert(!(PRES && SPLIT), "absent rows and a two-part source are not combined");
   constexpr int RPW = 64 / LPR;
   constexpr int EL = LPR < gcl::kEll ? LPR : gcl::kEll;  // ELL entries a lane group can hold
   static_assert(EW <= EL, "ELL width exceeds the lanes of a row group");
@@ -68,6 +74,7 @@ __global__ __launch_bounds__(256) void agg_kernel(const int32_t* __restrict__ ro
   const bool cactive = c0 < F;
   const int cc = cactive ? c0 : 0;  // inactive channel lanes re-read channel 0 (never stored)
   const float* __restrict__ Hb = H + (int64_t)b * bsh;
+  const float* __restrict__ H2b = SPLIT ? H2 + (int64_t)b * bsh2 : nullptr;
   float* __restrict__ Yb = Y + (int64_t)b * bsy;
 
   float bz0 = 0.f, bz1 = 0.f, bz2 = 0.f, bz3 = 0.f;
@@ -81,6 +88,7 @@ __global__ __launch_bounds__(256) void agg_kernel(const int32_t* __restrict__ ro
   auto ld4 = [&](int j, float& x0, float& x1, float& x2, float& x3) {
     const float* p = Hb + (int64_t)j * ldh + cc;
     if (PRES) p = j >= 0 ? p : reinterpret_cast<const float*>(gcl::mfma_io::zero4);  // absent sources carry index -1
+    if (SPLIT) p = j < head ? p : H2b + (int64_t)(j - head) * ldh2 + cc;
     if (VL) {
       const float4 v = *reinterpret_cast<const float4*>(p);
       x0 = v.x; x1 = v.y; x2 = v.z; x3 = v.w;
@@ -198,14 +206,16 @@ __global__ __launch_bounds__(256) void agg_kernel(const int32_t* __restrict__ ro
 // in flight each) and are combined through LDS in a fixed order.  Only rows with more than kHeavy
 // edges take this path (polar mesh nodes of E_G2M / E_M2G at 512x256: up to 943 edges), so a
 // single wave no longer serialises hundreds of dependent gathers at the tail of the launch.
-template <int LPR, bool VL, bool VS, bool PRES = false>
+template <int LPR, bool VL, bool VS, bool PRES = false, bool SPLIT = false>
 __global__ __launch_bounds__(256) void agg_heavy_kernel(const int32_t* __restrict__ rows_heavy,
                                                         const int32_t* __restrict__ rowptr,
                                                         const int32_t* __restrict__ col, const float* __restrict__ w,
                                                         const float* __restrict__ H, int64_t ldh, int64_t bsh,
                                                         const float* __restrict__ bias, float* __restrict__ Y,
                                                         int64_t ldy, int64_t bsy, int32_t F,
-                                                        const int32_t* __restrict__ present = nullptr) {
+                                                        const int32_t* __restrict__ present = nullptr,
+                                                        const float* __restrict__ H2 = nullptr, int64_t ldh2 = 0,
+                                                        int64_t bsh2 = 0, int32_t head = 0) {
   constexpr int NG = 256 / LPR;
   __shared__ float red[NG][LPR * 4 + 1];
   const int row = rows_heavy[blockIdx.x];
@@ -215,11 +225,13 @@ __global__ __launch_bounds__(256) void agg_heavy_kernel(const int32_t* __restric
   const bool cactive = c0 < F;
   const int cc = cactive ? c0 : 0;
   const float* __restrict__ Hb = H + (int64_t)b * bsh;
+  const float* __restrict__ H2b = SPLIT ? H2 + (int64_t)b * bsh2 : nullptr;
   const int start = rowptr[row], end = rowptr[row + 1];
   float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
   auto ld4 = [&](int j, float& x0, float& x1, float& x2, float& x3) {
     const float* p = Hb + (int64_t)j * ldh + cc;
     if (PRES) p = present[j] >= 0 ? p : reinterpret_cast<const float*>(gcl::mfma_io::zero4);
+    if (SPLIT) p = j < head ? p : H2b + (int64_t)(j - head) * ldh2 + cc;
     if (VL) {
       const float4 v = *reinterpret_cast<const float4*>(p);
       x0 = v.x; x1 = v.y; x2 = v.z; x3 = v.w;
@@ -327,7 +339,11 @@ __device__ unsigned long long agg_stamps[8 * 4096];  // diagnostic builds only (
 // the wave's own rows and to its list entries (an absent one becomes -1), and kept in registers across the samples of
 // the XCD group; an absent row's DMA reads the zero page (all lanes of the row the same 16 bytes) through a pointer
 // select, so the image holds the zeros the caller would otherwise have had to store, and the sums are untouched.
-template <int LPR, int T, int MAXPW, bool PRES = false>
+// SMAP: a store map, one int per row, applied once per tile and kept in registers across the samples of the XCD group as
+// the presence table is: an entry >= 0 is the row of the compact destination Yc this row is stored to INSTEAD of Y (its
+// consumer wants those rows dense: gcl_aggregate_compact), an entry < 0 stores to Y as always.  Every row is written
+// exactly once, to one place; image and sums are untouched.
+template <int LPR, int T, int MAXPW, bool PRES = false, bool SMAP = false>
 __global__ __launch_bounds__(256) void agg_halo_loop_kernel(const int32_t* __restrict__ list, const int32_t* __restrict__ cnt,
                                                             const int2* __restrict__ rec, const int32_t* __restrict__ rowptr,
                                                             const int32_t* __restrict__ opos, const float* __restrict__ w,
@@ -335,7 +351,10 @@ __global__ __launch_bounds__(256) void agg_halo_loop_kernel(const int32_t* __res
                                                             int64_t bsh, const float* __restrict__ bias,
                                                             float* __restrict__ Y, int64_t ldy, int64_t bsy, int32_t n,
                                                             int32_t B, int32_t F, int32_t ntiles, int32_t nt_store,
-                                                            const int32_t* __restrict__ present = nullptr) {
+                                                            const int32_t* __restrict__ present = nullptr,
+                                                            const int32_t* __restrict__ smap = nullptr,
+                                                            float* __restrict__ Yc = nullptr, int64_t ldc = 0,
+                                                            int64_t bsc = 0) {
   extern __shared__ float4 img[];  // (smax + 1) * LPR float4: own rows, halo rows, zero row
   constexpr int RPW = 64 / LPR;
   constexpr int NW = 4;              // waves per block
@@ -390,6 +409,7 @@ __global__ __launch_bounds__(256) void agg_halo_loop_kernel(const int32_t* __res
   int jj[MAXPW], nhalo = 0, tile = -1;
   int2 rc[NIT];
   bool own[PRES ? NIT : 1];  // PRES: presence of the wave's own rows
+  int sm[SMAP ? NIT : 1];    // SMAP: store-map entries of the wave's own rows
   const char* const zpage = reinterpret_cast<const char*>(gcl::mfma_io::zero4);
 #ifdef GCL_STAMPS
   unsigned long long st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, st_last = __builtin_amdgcn_s_memtime();
@@ -408,6 +428,13 @@ __global__ __launch_bounds__(256) void agg_halo_loop_kernel(const int32_t* __res
         for (int it = 0; it < NIT; ++it) {
           const int row = tile * T + wave * (T / NW) + sub + it * RPW;
           own[it] = present[row < n ? row : n - 1] >= 0;
+        }
+      }
+      if (SMAP) {
+#pragma unroll
+        for (int it = 0; it < NIT; ++it) {
+          const int row = tile * T + wave * (T / NW) + sub + it * RPW;
+          sm[it] = smap[row < n ? row : n - 1];
         }
       }
     }
@@ -493,6 +520,10 @@ __global__ __launch_bounds__(256) void agg_halo_loop_kernel(const int32_t* __res
       if (row < n && cactive && !(last & gcl::kHaloSkip)) {
         a0 += bz0; a1 += bz1; a2 += bz2; a3 += bz3;
         float* __restrict__ yp = Yb + (int64_t)row * ldy + c0;
+        if (SMAP) {
+          const int cr = sm[SMAP ? it : 0];
+          yp = cr >= 0 ? Yc + (int64_t)b * bsc + (int64_t)cr * ldc + c0 : yp;
+        }
         v4f v = {a0, a1, a2, a3};
         if (nt_store) __builtin_nontemporal_store(v, reinterpret_cast<v4f*>(yp));
         else *reinterpret_cast<v4f*>(yp) = v;
@@ -527,6 +558,16 @@ struct AggArgs {
   const gcl_halo* halo;  // [2]: T = 64, T = 32 (T == 0: not built)
   const int32_t* order16 = nullptr;  // processing order of 16-row groups (common.h), or nullptr
   int32_t n_order16 = 0;
+  // gcl_aggregate_split: rows >= head of the source come from h2 (h2 == nullptr: one source)
+  const float* h2 = nullptr;
+  int64_t ldh2 = 0, bsh2 = 0;
+  int32_t head = 0;
+  // gcl_aggregate_compact: rows with smap[row] >= 0 are stored to yc instead (source-tile kernel only); dry: only say
+  // whether the source-tile kernel would take the call
+  const int32_t* smap = nullptr;
+  float* yc = nullptr;
+  int64_t ldc = 0, bsc = 0;
+  bool dry = false;
 };
 
 // Source-tile path: returns GCL_OK after launching, or -1 when this call is not eligible (agg_kernel runs instead).
@@ -551,6 +592,7 @@ int launch_agg_halo(const AggArgs& ga, const float* h, int64_t ldh, int64_t bsh,
     break;
   }
   if (!hl) return -1;
+  if (ga.dry) return GCL_OK;
   const int64_t lds = (int64_t)(hl->smax + 1) * LPR * 16;
   // (wide rows, F = 128: 66 KB images, two blocks per CU.  Launched back to back at B = 8 the per-edge kernel on the same
   // tile-ordered graph is as fast, 79 vs 82 us - the whole batch sits in the Infinity Cache then; inside the training
@@ -563,11 +605,18 @@ int launch_agg_halo(const AggArgs& ga, const float* h, int64_t ldh, int64_t bsh,
   auto go = [&](auto kern) -> int {
     GCL_ENSURE_DYN_LDS(kern, (size_t)lds);
     hipLaunchKernelGGL(kern, grid, block, (size_t)lds, st, hl->list, hl->cnt, reinterpret_cast<const int2*>(hl->rec),
-                       ga.rowptr, hl->opos, ga.w, hl->smax, h, ldh, bsh, bias, y, ldy, bsy, n, B, F, hl->ntiles, nt, present);
+                       ga.rowptr, hl->opos, ga.w, hl->smax, h, ldh, bsh, bias, y, ldy, bsy, n, B, F, hl->ntiles, nt, present,
+                       ga.smap, ga.yc, ga.ldc, ga.bsc);
     return GCL_OK;
   };
   int rc;
-  if (present && hl->T == 64)
+  if (ga.smap && hl->T == 64)
+    rc = mpw <= 4 ? go(&agg_halo_loop_kernel<LPR, 64, 4, false, true>) : mpw <= 8 ? go(&agg_halo_loop_kernel<LPR, 64, 8, false, true>)
+       : mpw <= 16 ? go(&agg_halo_loop_kernel<LPR, 64, 16, false, true>) : go(&agg_halo_loop_kernel<LPR, 64, 32, false, true>);
+  else if (ga.smap)
+    rc = mpw <= 4 ? go(&agg_halo_loop_kernel<LPR, 32, 4, false, true>) : mpw <= 8 ? go(&agg_halo_loop_kernel<LPR, 32, 8, false, true>)
+       : mpw <= 16 ? go(&agg_halo_loop_kernel<LPR, 32, 16, false, true>) : go(&agg_halo_loop_kernel<LPR, 32, 32, false, true>);
+  else if (present && hl->T == 64)
     rc = mpw <= 4 ? go(&agg_halo_loop_kernel<LPR, 64, 4, true>) : mpw <= 8 ? go(&agg_halo_loop_kernel<LPR, 64, 8, true>)
        : mpw <= 16 ? go(&agg_halo_loop_kernel<LPR, 64, 16, true>) : go(&agg_halo_loop_kernel<LPR, 64, 32, true>);
   else if (present)
@@ -589,6 +638,12 @@ int launch_agg_heavy(const AggArgs& ga, const float* h, int64_t ldh, int64_t bsh
                      int64_t ldy, int64_t bsy, int32_t B, int32_t F, bool vl, bool vs, hipStream_t st,
                      const int32_t* present = nullptr) {
   dim3 hgrid((unsigned)ga.n_heavy, (unsigned)B), block(256);
+  if (ga.h2) {  // (only 16-byte rows reach here: gcl_aggregate_split refuses others)
+    hipLaunchKernelGGL((agg_heavy_kernel<LPR, true, true, false, true>), hgrid, block, 0, st, ga.heavy, ga.rowptr, ga.col,
+                       ga.w, h, ldh, bsh, bias, y, ldy, bsy, F, (const int32_t*)nullptr, ga.h2, ga.ldh2, ga.bsh2, ga.head);
+    GCL_CHECK_LAUNCH();
+    return GCL_OK;
+  }
   if (present) {
 #define GCL_AGGH(VL_, VS_)                                                                                       \
   hipLaunchKernelGGL((agg_heavy_kernel<LPR, VL_, VS_, true>), hgrid, block, 0, st, ga.heavy, ga.rowptr, ga.col, ga.w, \
@@ -618,18 +673,20 @@ int launch_agg(const AggArgs& ga, const float* h, int64_t ldh, int64_t bsh, cons
                int64_t bsy, int32_t n, int32_t B, int32_t F, hipStream_t st, const int32_t* present = nullptr) {
   constexpr int RPW = 64 / LPR;
   constexpr int EL = LPR < gcl::kEll ? LPR : gcl::kEll;
+  if ((ga.smap || ga.dry) && ga.n_heavy > 0) return -1;  // (the one-block-per-row kernel has no store map)
   // vector loads need 16-B aligned rows and a padded tail (ldh >= roundup(F,4))
   const bool vl = (ldh % 4 == 0) && (bsh % 4 == 0) && gcl::aligned16(h) && ldh >= ((F + 3) / 4) * 4;
   const bool vs = (ldy % 4 == 0) && (bsy % 4 == 0) && gcl::aligned16(y) && (F % 4 == 0);
   if constexpr (LPR >= 16) {
-    if (vl && vs && (!bias || gcl::aligned16(bias))) {
+    if (!ga.h2 && vl && vs && (!bias || gcl::aligned16(bias))) {  // (the source tiles stage ONE tensor's rows)
       const int hr = launch_agg_halo<LPR>(ga, h, ldh, bsh, bias, y, ldy, bsy, n, B, F, st, present);
       if (hr >= 0) {
-        if (hr != GCL_OK || ga.n_heavy == 0) return hr;
+        if (hr != GCL_OK || ga.n_heavy == 0 || ga.dry) return hr;
         return launch_agg_heavy<LPR>(ga, h, ldh, bsh, bias, y, ldy, bsy, B, F, true, true, st, present);
       }
     }
   }
+  if (ga.smap || ga.dry) return -1;  // the store map lives in the source-tile kernel only: the caller asked first
   static const int iter_env = gcl::env_int("GCL_AGG_ITER", 0);  // tuning overrides (0 = per-graph default)
   static const int ew_env = gcl::env_int("GCL_AGG_EW", 0);
   static const int nt = gcl::env_int("GCL_AGG_NT", 1);  // non-temporal output stores (measured: -7..-12 %)
@@ -639,7 +696,7 @@ int launch_agg(const AggArgs& ga, const float* h, int64_t ldh, int64_t bsh, cons
   // measured on MI355X (profiles/r01_c_*): dense prefixes (mesh) run best with one batch per wave,
   // near-diagonal bipartite graphs with two (next batch's metadata prefetched)
   // (the variant with absent sources exists for the per-graph default only)
-  const int iter = (!present && (iter_env == 1 || iter_env == 2 || iter_env == 4 || iter_env == 8)) ? iter_env
+  const int iter = (!present && !ga.h2 && (iter_env == 1 || iter_env == 2 || iter_env == 4 || iter_env == 8)) ? iter_env
                                                                                                      : (ewidth >= 4 ? 1 : 2);
   int32_t nRB = (int32_t)gcl::cdiv(n, RPW * 4 * iter);
   if (ga.order16 && RPW * 4 * iter <= 16) nRB = ga.n_order16 * (16 / (RPW * 4 * iter));  // whole 16-row groups (rows >= n are masked)
@@ -654,6 +711,21 @@ int launch_agg(const AggArgs& ga, const float* h, int64_t ldh, int64_t bsh, cons
 #define GCL_AGGP(VL_, VS_, EW_, IT_)                                                                                   \
   hipLaunchKernelGGL((agg_kernel<LPR, VL_, VS_, EW_, IT_, true>), grid, block, 0, st, ga.rowptr, ga.col, ga.w, ga.ecol, \
                      ga.ew, h, ldh, bsh, bias, y, ldy, bsy, n, B, F, nRB, xcd_map, nt, order16, present)
+#define GCL_AGGS(EW_, IT_)                                                                                              \
+  hipLaunchKernelGGL((agg_kernel<LPR, true, true, EW_, IT_, false, true>), grid, block, 0, st, ga.rowptr, ga.col, ga.w,  \
+                     ga.ecol, ga.ew, h, ldh, bsh, bias, y, ldy, bsy, n, B, F, nRB, xcd_map, nt, order16,                \
+                     (const int32_t*)nullptr, ga.h2, ga.ldh2, ga.bsh2, ga.head)
+  if (ga.h2) {  // two-part source: the per-graph default of the plain kernel, 16-byte rows only
+    if constexpr (EL >= 8) {
+      if (ewidth == 8) GCL_AGGS(8, 1);
+    }
+    if (ewidth == 4) GCL_AGGS(4, 1);
+    else if (ewidth == 2) GCL_AGGS(2, 2);
+    else if (ewidth == 1) GCL_AGGS(1, 2);
+    GCL_CHECK_LAUNCH();
+    if (ga.n_heavy > 0) return launch_agg_heavy<LPR>(ga, h, ldh, bsh, bias, y, ldy, bsy, B, F, true, true, st, nullptr);
+    return GCL_OK;
+  }
 #define GCL_AGG3(VL_, VS_, EW_)              \
   do {                                       \
     if (present) {                           \
@@ -680,6 +752,7 @@ int launch_agg(const AggArgs& ga, const float* h, int64_t ldh, int64_t bsh, cons
 #undef GCL_AGG3
 #undef GCL_AGG4
 #undef GCL_AGGP
+#undef GCL_AGGS
   GCL_CHECK_LAUNCH();
   if (ga.n_heavy > 0) return launch_agg_heavy<LPR>(ga, h, ldh, bsh, bias, y, ldy, bsy, B, F, vl, vs, st, present);
   return GCL_OK;
@@ -689,13 +762,16 @@ int launch_agg(const AggArgs& ga, const float* h, int64_t ldh, int64_t bsh, cons
 
 static int aggregate_impl(const gcl_graph_t* g, int32_t transpose, const float* h, int64_t ldh, int64_t bsh,
                           const int32_t* present, const float* bias, float* y, int64_t ldy, int64_t bsy, int32_t B,
-                          int32_t F, gcl_stream_t stream) {
-  GCL_CHECK_ARG(g && h && y, "aggregate: null argument");
+                          int32_t F, gcl_stream_t stream, const float* h2 = nullptr, int64_t ldh2 = 0, int64_t bsh2 = 0,
+                          int32_t head = 0, const AggArgs* compact = nullptr) {
+  const bool dry = compact && compact->dry;
+  GCL_CHECK_ARG(g && (dry || (h && y)), "aggregate: null argument");
   GCL_CHECK_ARG(B > 0 && F > 0 && F <= 256, "aggregate: unsupported B=%d F=%d (F must be in 1..256)", B, F);
   GCL_CHECK_ARG(ldh >= F && ldy >= F, "aggregate: leading dimension smaller than F");
   GCL_CHECK_ARG(g->kind != GCL_GRAPH_GAT, "aggregate: GAT graphs carry no edge weights; use gcl_gat_fwd");
-  GCL_CHECK_ARG(h != y, "aggregate: in-place aggregation is not supported");
+  GCL_CHECK_ARG(dry || h != y, "aggregate: in-place aggregation is not supported");
   AggArgs ga;
+  if (compact) ga = *compact;
   ga.rowptr = transpose ? g->trowptr : g->rowptr;
   ga.col = transpose ? g->tcol : g->col;
   ga.w = transpose ? g->tw : g->w;
@@ -707,6 +783,10 @@ static int aggregate_impl(const gcl_graph_t* g, int32_t transpose, const float* 
   ga.heavy = transpose ? g->theavy : g->heavy;
   ga.n_heavy = transpose ? g->n_theavy : g->n_heavy;
   ga.halo = g->halo[transpose ? 1 : 0];
+  ga.h2 = h2;
+  ga.ldh2 = ldh2;
+  ga.bsh2 = bsh2;
+  ga.head = head;
   GCL_CHECK_ARG(B <= 65535 || ga.n_heavy == 0, "aggregate: batch too large for the heavy-row launch");
   hipStream_t st = (hipStream_t)stream;
   const int lanes = (F + 3) / 4;
@@ -728,4 +808,48 @@ extern "C" int gcl_aggregate_present(const gcl_graph_t* g, int32_t transpose, co
                                      int32_t B, int32_t F, gcl_stream_t stream) {
   GCL_CHECK_ARG(present, "aggregate_present: null presence table");
   return aggregate_impl(g, transpose, h, ldh, bsh, present, bias, y, ldy, bsy, B, F, stream);
+}
+
+extern "C" int gcl_aggregate_split(const gcl_graph_t* g, int32_t transpose, const float* h, int64_t ldh, int64_t bsh,
+                                   const float* h2, int64_t ldh2, int64_t bsh2, int32_t head, const float* bias, float* y,
+                                   int64_t ldy, int64_t bsy, int32_t B, int32_t F, gcl_stream_t stream) {
+  GCL_CHECK_ARG(g && y, "aggregate_split: null argument");
+  GCL_CHECK_ARG(head >= 0 && head <= g->n, "aggregate_split: head=%d outside [0, n=%d]", head, g->n);
+  GCL_CHECK_ARG((h || head == 0) && (h2 || head == g->n), "aggregate_split: null source part");
+  if (head == 0) h = h2;  // (one part only: the select never takes the other pointer)
+  GCL_CHECK_ARG(F > 0 && F % 4 == 0 && ldh >= F && ldh2 >= F && ldh % 4 == 0 && bsh % 4 == 0 && ldh2 % 4 == 0 &&
+                    bsh2 % 4 == 0 && ldy % 4 == 0 && bsy % 4 == 0 && gcl::aligned16(h) && gcl::aligned16(h2) &&
+                    gcl::aligned16(y),
+                "aggregate_split: both source parts and y need 16-byte rows (F %% 4 == 0, aligned bases and strides)");
+  GCL_CHECK_ARG(h2 != y, "aggregate: in-place aggregation is not supported");
+  return aggregate_impl(g, transpose, h, ldh, bsh, nullptr, bias, y, ldy, bsy, B, F, stream, h2, ldh2, bsh2, head);
+}
+
+// 1 when gcl_aggregate_compact can take a call with these strides (the source-tile kernel runs it: GCL_AGG_HALO, a graph
+// with source tiles in that direction and no heavy rows, 16-byte rows of more than 32 columns), else 0.
+extern "C" int gcl_aggregate_compact_ok(const gcl_graph_t* g, int32_t transpose, int64_t ldh, int64_t bsh, int64_t ldy,
+                                        int64_t bsy, int32_t B, int32_t F) {
+  if (!g || g->kind == GCL_GRAPH_GAT || B <= 0 || F <= 32 || F > 256 || F % 4 != 0 || ldh < F || ldy < F) return 0;
+  AggArgs ca;
+  ca.dry = true;
+  return aggregate_impl(g, transpose, nullptr, ldh, bsh, nullptr, nullptr, nullptr, ldy, bsy, B, F, nullptr, nullptr, 0, 0, 0,
+                        &ca) == GCL_OK ? 1 : 0;
+}
+
+extern "C" int gcl_aggregate_compact(const gcl_graph_t* g, int32_t transpose, const float* h, int64_t ldh, int64_t bsh,
+                                     const int32_t* smap, float* y, int64_t ldy, int64_t bsy, float* yc, int64_t ldc,
+                                     int64_t bsc, int32_t B, int32_t F, gcl_stream_t stream) {
+  GCL_CHECK_ARG(g && smap, "aggregate_compact: null argument");  // (yc may be null when no entry of the map is >= 0)
+  GCL_CHECK_ARG(F % 4 == 0 && ldc >= F && ldc % 4 == 0 && bsc % 4 == 0 && gcl::aligned16(yc),
+                "aggregate_compact: the compact destination needs 16-byte rows");
+  GCL_CHECK_ARG(gcl_aggregate_compact_ok(g, transpose, ldh, bsh, ldy, bsy, B, F) && gcl::aligned16(h) && gcl::aligned16(y),
+                "aggregate_compact: the source-tile kernel cannot take this call (ask gcl_aggregate_compact_ok first)");
+  AggArgs ca;
+  ca.smap = smap;
+  ca.yc = yc;
+  ca.ldc = ldc;
+  ca.bsc = bsc;
+  const int rc = aggregate_impl(g, transpose, h, ldh, bsh, nullptr, nullptr, y, ldy, bsy, B, F, stream, nullptr, 0, 0, 0, &ca);
+  GCL_CHECK_ARG(rc != -1, "aggregate_compact: the source-tile kernel cannot take this call");
+  return rc;
 }

@@ -336,6 +336,67 @@ __global__ __launch_bounds__(256) void colsum_kernel(const float* __restrict__ X
   }
 }
 
+// colsum_kernel<LPR, true> over the rows of a TWO-PART source [B, n, F]: row i of sample b is A + b * bsa + i * lda for
+// i < head, else Bp + b * bsb + (i - head) * ldb (gcl_colsum_split).  The same (block, lane group, trip) enumeration of
+// the flat rows b * n + i, the same four rows in flight and the same two-stage partials, so the sums are those of
+// colsum_kernel on the materialised tensor bit for bit; (b, i) is kept incrementally (one division per thread).
+template <int LPR>
+__global__ __launch_bounds__(256) void colsum_split_kernel(const float* __restrict__ A, int64_t lda, int64_t bsa,
+                                                           const float* __restrict__ Bp, int64_t ldb, int64_t bsb,
+                                                           int32_t head, int32_t n, float* __restrict__ part,
+                                                           int64_t rows, int32_t F, int32_t FP) {
+  constexpr int RPW = 64 / LPR;
+  constexpr int RPB = RPW * 4;
+  __shared__ float red[RPB][LPR * 4 + 1];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int sub = lane / LPR, l = lane % LPR, c0 = l * 4;
+  float s0 = 0, s1 = 0, s2 = 0, s3 = 0;
+  if (c0 < F) {
+    const int64_t step = (int64_t)gridDim.x * RPB;
+    int64_t row = (int64_t)blockIdx.x * RPB + wave * RPW + sub;
+    int64_t b = row / n;
+    int i = (int)(row - b * n);
+    const int64_t sb = step / n;
+    const int si = (int)(step - sb * n);
+    auto addr = [&]() {  // the current row's address, then one step on
+      const float* p = i < head ? A + b * bsa + (int64_t)i * lda + c0 : Bp + b * bsb + (int64_t)(i - head) * ldb + c0;
+      i += si;
+      b += sb;
+      if (i >= n) { i -= n; ++b; }
+      return p;
+    };
+    for (; row + 3 * step < rows; row += 4 * step) {
+      float a0, a1, a2, a3, b0, b1, b2, b3, c1_, c2_, c3_, c4_, d0, d1, d2, d3;
+      const float* pa = addr();
+      const float* pb = addr();
+      const float* pc = addr();
+      const float* pd = addr();
+      load4(pa, c0, F, true, a0, a1, a2, a3);
+      load4(pb, c0, F, true, b0, b1, b2, b3);
+      load4(pc, c0, F, true, c1_, c2_, c3_, c4_);
+      load4(pd, c0, F, true, d0, d1, d2, d3);
+      s0 += a0; s1 += a1; s2 += a2; s3 += a3;
+      s0 += b0; s1 += b1; s2 += b2; s3 += b3;
+      s0 += c1_; s1 += c2_; s2 += c3_; s3 += c4_;
+      s0 += d0; s1 += d1; s2 += d2; s3 += d3;
+    }
+    for (; row < rows; row += step) {
+      float x0, x1, x2, x3;
+      load4(addr(), c0, F, true, x0, x1, x2, x3);
+      s0 += x0; s1 += x1; s2 += x2; s3 += x3;
+    }
+  }
+  float* r = red[wave * RPW + sub];
+  r[c0] = s0; r[c0 + 1] = s1; r[c0 + 2] = s2; r[c0 + 3] = s3;
+  __syncthreads();
+  for (int c = threadIdx.x; c < F; c += 256) {
+    float s = 0.f;
+#pragma unroll
+    for (int q = 0; q < RPB; ++q) s += red[q][c];
+    part[(size_t)blockIdx.x * FP + c] = s;
+  }
+}
+
 constexpr int kNormBlocks = 1024;  // 4 blocks per CU (measured: 512 -> 1024 +1.8 % end to end, 2048 the same, 4096 less)
 
 inline int lpr_for(int F) {
@@ -605,4 +666,52 @@ extern "C" int gcl_colsum_deferred(const float* x, int64_t ldx, int64_t rows, in
                                    void* ws, size_t ws_bytes, gcl_stream_t stream, gcl_reduce_job* job) {
   GCL_CHECK_ARG(job, "colsum_deferred: null job");
   return colsum_impl(x, ldx, rows, F, out, accumulate, ws, ws_bytes, stream, job);
+}
+
+static int colsum_split_impl(const float* a, int64_t lda, int64_t bsa, const float* b, int64_t ldb, int64_t bsb,
+                             int32_t head, int32_t n, int32_t B, int32_t F, float* out, int32_t accumulate, void* ws,
+                             size_t ws_bytes, gcl_stream_t stream, gcl_reduce_job* job) {
+  if (job) memset(job, 0, sizeof(*job));
+  GCL_CHECK_ARG(out && n > 0 && B > 0, "colsum_split: null argument or empty shape");
+  GCL_CHECK_ARG(head >= 0 && head <= n && (a || head == 0) && (b || head == n), "colsum_split: head=%d outside [0, n=%d] or a null part", head, n);
+  GCL_CHECK_ARG(F >= 4 && F <= 256 && F % 4 == 0 && lda >= F && ldb >= F, "colsum_split: bad shape F=%d", F);
+  GCL_CHECK_ARG(lda % 4 == 0 && bsa % 4 == 0 && ldb % 4 == 0 && bsb % 4 == 0 && gcl::aligned16(a) && gcl::aligned16(b),
+                "colsum_split: both parts need 16-byte rows");
+  const int64_t rows = (int64_t)B * n;
+  GCL_CHECK_ARG(ws && ws_bytes >= gcl_colsum_ws_bytes(rows, F), "colsum_split: workspace too small");
+  hipStream_t st = (hipStream_t)stream;
+  const int lpr = lpr_for(F);
+  const int rpb = (64 / lpr) * 4;
+  const int FP = F;
+  int64_t nb = gcl::cdiv(rows, rpb);  // (the grid and the records of colsum_impl)
+  if (nb > kNormBlocks) nb = kNormBlocks;
+  float* part = (float*)ws;
+#define CALL(L)                                                                                                        \
+  hipLaunchKernelGGL((colsum_split_kernel<L>), dim3((unsigned)nb), dim3(256), 0, st, a, lda, bsa, b, ldb, bsb, head, n, \
+                     part, rows, F, FP)
+  GCL_DISPATCH_LPR(lpr, CALL)
+#undef CALL
+  GCL_CHECK_LAUNCH();
+  if (job && reduce_job_ok(part, (int)nb)) {
+    job->part = part;
+    job->pstride = FP;
+    job->nparts = (int32_t)nb;
+    set_seg(job, 0, out, 0, FP, F, accumulate ? 1 : 0);
+    return GCL_OK;
+  }
+  return gcl::launch_reduce_parts(part, (int)nb, FP, FP, out, F, 1, F, accumulate, st);
+}
+
+extern "C" int gcl_colsum_split(const float* a, int64_t lda, int64_t bsa, const float* b, int64_t ldb, int64_t bsb,
+                                int32_t head, int32_t n, int32_t B, int32_t F, float* out, int32_t accumulate, void* ws,
+                                size_t ws_bytes, gcl_stream_t stream) {
+  return colsum_split_impl(a, lda, bsa, b, ldb, bsb, head, n, B, F, out, accumulate, ws, ws_bytes, stream, nullptr);
+}
+
+extern "C" int gcl_colsum_split_deferred(const float* a, int64_t lda, int64_t bsa, const float* b, int64_t ldb,
+                                         int64_t bsb, int32_t head, int32_t n, int32_t B, int32_t F, float* out,
+                                         int32_t accumulate, void* ws, size_t ws_bytes, gcl_stream_t stream,
+                                         gcl_reduce_job* job) {
+  GCL_CHECK_ARG(job, "colsum_split_deferred: null job");
+  return colsum_split_impl(a, lda, bsa, b, ldb, bsb, head, n, B, F, out, accumulate, ws, ws_bytes, stream, job);
 }

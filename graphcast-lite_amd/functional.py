@@ -136,6 +136,18 @@ def _row_skip() -> bool:
     return os.environ.get("GCL_NO_ROW_SKIP", "0") in ("0", "")
 
 
+def _split_grad() -> bool:
+    """The encoder stack's backward reads its incoming gradient where its two producers left it (GCL_NO_SPLIT_GRAD=1:
+    they copy it into one buffer first).  Read per call."""
+    return os.environ.get("GCL_NO_SPLIT_GRAD", "0") in ("0", "")
+
+
+def _compact_store() -> bool:
+    """The first processor layer's transposed aggregation stores the batch-dependent rows of its output compact
+    (GCL_NO_COMPACT_STORE=1: it writes them in place and a gather launch copies them).  Read per call."""
+    return os.environ.get("GCL_NO_COMPACT_STORE", "0") in ("0", "")
+
+
 def _fold_sum(g3, inv_fold, r: int, B: int, dst):
     """The batch sums of g3's folded rows (MeshLatFn: inv_fold) land r to a sample in dst [B, r, F]."""
     if r > 1:
@@ -145,11 +157,13 @@ def _fold_sum(g3, inv_fold, r: int, B: int, dst):
         hip.copy_rows(tmp.view(B, r, g3.shape[-1]), dst)
 
 
-def _lat_first_layer_bwd(lat, enc3, dz3, W, dW, acc_dw: bool, want_dx: bool, Pc=None, enc_shape=None):
+def _lat_first_layer_bwd(lat, enc3, dz3, W, dW, acc_dw: bool, want_dx: bool, Pc=None, enc_shape=None, dzc=None):
     """Dense backward of a first processor layer whose input was read through a LatSource: dz3 [B, M, D'] is the
     gradient of the layer's transformed mesh rows (GCN: A^T dp, GAT: dh).  Returns the gradient of the encoder output
     [B, ne, D] (or None when the shared landing buffer took it / no gradient is wanted); dW is written / accumulated in
-    place.  Pc: the compact encoder rows [B, Md + r, D] when the forward already copied them."""
+    place.  Pc: the compact encoder rows [B, Md + r, D] when the forward already copied them.  dzc: the compact gradient
+    rows [B, Md + r, D'] with the Md dependent rows already in place (hip.aggregate_compact stored them there: those rows
+    of dz3 are then unwritten), the folded rows still to be summed from dz3."""
     _, _, inv_a, inv_fold = lat.maps
     B, ne, D = enc_shape if enc3 is None else enc3.shape  # (enc3 may be None when Pc is given: only its shape is needed)
     G, Md, r = lat.G, lat.Md, lat.r
@@ -157,9 +171,10 @@ def _lat_first_layer_bwd(lat, enc3, dz3, W, dW, acc_dw: bool, want_dx: bool, Pc=
     Fo = dz3.shape[-1]
     dz3 = dz3 if dz3.is_contiguous() else dz3.contiguous()
     # compact gradient rows [B, Md + r, Fo]: dependent rows gathered, folded rows summed over the batch
-    dzc = torch.empty(B, nc, Fo, dtype=torch.float32, device=dz3.device)
-    if Md > 0:
-        hip.gather2_rows(dz3, inv_a[G: G + Md], None, None, Md, B, out=dzc[:, :Md])
+    if dzc is None:
+        dzc = torch.empty(B, nc, Fo, dtype=torch.float32, device=dz3.device)
+        if Md > 0:
+            hip.gather2_rows(dz3, inv_a[G: G + Md], None, None, Md, B, out=dzc[:, :Md])
     _fold_sum(dz3, inv_fold, r, B, dzc[:, Md:])
     if Pc is None:  # the encoder rows behind the mesh latents
         Pc = hip.copy_rows(enc3[:, G:, :], torch.empty(B, nc, D, dtype=torch.float32, device=dz3.device))
@@ -169,6 +184,8 @@ def _lat_first_layer_bwd(lat, enc3, dz3, W, dW, acc_dw: bool, want_dx: bool, Pc=
     else:
         dxc = hip.linear_bwd_all(dzc.view(B * nc, Fo), W, Pc.view(B * nc, D), None, None, dW, None, None, acc_dw,
                                  act=hip.ACT_NONE).view(B, nc, D)
+    if GradLanding.keep_tail(lat.landing, dxc):  # the encoder stack's backward reads dxc where it is
+        return None
     buf, _ = GradLanding.tail(lat.landing)
     if dxc is None:
         return None
@@ -186,8 +203,11 @@ class LatSource:
     (sum_b dz[b, i]) W and its dW term (sum_b dz[b, i])^T enc_row, so 81 % of the rows (64x32 grid) cost one batch sum
     instead of B dense rows.  maps = MeshLatFn's (map_a, map_b, inv_a, inv_fold)."""
 
-    def __init__(self, tab, maps, M: int, G: int, Md: int, r: int, landing=None):
+    def __init__(self, tab, maps, M: int, G: int, Md: int, r: int, landing=None, smap=None):
+        """smap: int32 [M], mesh row -> its row among the Md dependent rows of the compact gradient, or -1 (the inverse of
+        inv_a[G: G + Md]; None when that is no one-to-one map)."""
         self.tab, self.maps, self.M, self.G, self.Md, self.r, self.landing = tab, maps, M, G, Md, r, landing
+        self.smap = smap
         self._compact = {}
 
     def compact_tab(self, ne: int):
@@ -206,8 +226,10 @@ class LatSource:
 
 class GCNStackFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, owner, graph, L: int, has_ln: bool, eps: float, out_rows: int, land, lat, *params):
+    def forward(ctx, x, owner, graph, L: int, has_ln: bool, eps: float, out_rows: int, land, lat, split, *params):
         """land: GradLanding or None.  lat: LatSource or None (x is then the encoder output).
+        split: GradLanding or None - this stack's OUTPUT is the encoder output whose gradient arrives in two parts (head
+        rows from the decoder-input gather, the rest from the mesh side): its backward reads both where they are.
         out_rows > 0: only the first `out_rows` rows are returned (the decoder keeps the grid rows,
         src/models.py:870-872); the slice is part of this Function so that its backward receives the gradient of
         the slice and widens it with ONE pass of gcl_pad_rows (no zero-fill + copy by autograd)."""
@@ -220,6 +242,13 @@ class GCNStackFn(torch.autograd.Function):
                 x3 = x3.contiguous()
             GradLanding.expect_tail(lat.landing)  # this Function's backward fills the shared buffer's tail rows (as MeshLatFn)
         ctx.lat = lat
+        # what the two-part reader assumes: the gradient goes straight to the last conv (no LayerNorm, no row slice, no
+        # padded width) in whole 16-byte rows
+        ctx.split = None
+        if (split is not None and not has_ln and not out_rows and not squeeze and lat is None
+                and params[2 * (L - 1)].shape[0] % 4 == 0 and _split_grad()):
+            split.expect_split_reader()
+            ctx.split = split
         slope_p = params[2 * L]
         # activation between the convs: learnable PReLU slope (params[2L]), SiLU, or ReLU as a PReLU
         # with the owner's constant zero slope (src/models.py:154-163, :316)
@@ -305,10 +334,12 @@ class GCNStackFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         params, L, graph = ctx.params, ctx.L, ctx.graph
-        needs = list(ctx.needs_input_grad[9:])
+        needs = list(ctx.needs_input_grad[10:])
         G = _Grads(list(params), needs)
+        dy, parts = GradLanding.claim_parts(ctx.split, dy)  # parts: (head rows [B, head, F], tail rows [B, n - head, F])
         dy, dy_map = GradLanding.claim(ctx.land, dy)
-        dy3 = dy if dy_map is not None else _flat3(dy)  # (with a map `dy` is the token: only its shape is used)
+        # (with a map or with parts `dy` is the token: only its shape is used)
+        dy3 = dy if (dy_map is not None or parts is not None) else _flat3(dy)
         B, n = dy3.shape[0], ctx.n_rows
         ps = ctx.ps
         pad = ctx.pad_last
@@ -347,7 +378,12 @@ class GCNStackFn(torch.autograd.Function):
             dp = hip.pad_rows(dy_rows if not ctx.has_ln else dp, n, Fp)
         if G.dst[bi_last] is not None and not cs_done:  # bias of the last conv: its dp comes from outside this stack
             src = dy_rows if not ctx.has_ln else dp[..., :Fo]
-            hip.colsum(src.reshape(-1, Fo), G.dst[bi_last], G.acc[bi_last])
+            if parts is not None:
+                hip.colsum_split(parts[0], parts[1], G.dst[bi_last], G.acc[bi_last])
+            else:
+                hip.colsum(src.reshape(-1, Fo), G.dst[bi_last], G.acc[bi_last])
+        dzc = None
+        assert ctx.present is None or parts is None  # (with parts `dp` is the token: only aggregate_split may read "it")
         for k in range(L - 1, -1, -1):
             W = params[2 * k].detach()
             wi = 2 * k
@@ -355,6 +391,14 @@ class GCNStackFn(torch.autograd.Function):
             if k == L - 1 and ctx.present is not None:
                 # the dropped rows of dp were not written: their zeros come from the table
                 dh2 = hip.aggregate_present(graph, dp, ctx.present, transpose=True).view(B * n, -1)
+            elif k == L - 1 and parts is not None:
+                dh2 = hip.aggregate_split(graph, parts[0], parts[1], transpose=True).view(B * n, -1)
+            elif (k == 0 and ctx.lat is not None and ctx.lat.smap is not None and ctx.lat.Md > 0 and _compact_store()
+                  and dp.is_contiguous() and hip.aggregate_compact_ok(graph, dp, transpose=True)):
+                # the Md batch-dependent rows go straight into the compact gradient of _lat_first_layer_bwd, the others
+                # (their batch sums are taken from there) to their usual place: every row is written once
+                dzc = torch.empty(B, ctx.lat.Md + ctx.lat.r, dp.shape[2], dtype=torch.float32, device=dp.device)
+                dh2 = hip.aggregate_compact(graph, dp, ctx.lat.smap, dzc, transpose=True).view(B * n, -1)
             else:
                 dh2 = hip.aggregate(graph, dp, None, transpose=True).view(B * n, -1)
             if k == L - 1 and Fp != Fo:
@@ -366,7 +410,8 @@ class GCNStackFn(torch.autograd.Function):
                 dp = hip.linear_bwd_all(dh2, W, inp, slope_t, dsl, dW, None, G.dst[2 * k - 1], G.acc[wi],
                                         acc_colsum=G.acc[2 * k - 1], act=akind).view(B, n, -1)
             elif ctx.lat is not None:
-                dx = _lat_first_layer_bwd(ctx.lat, ctx.x3, dh2.reshape(B, n, -1), W, dW, G.acc[wi], ctx.needs_input_grad[0])
+                dx = _lat_first_layer_bwd(ctx.lat, ctx.x3, dh2.reshape(B, n, -1), W, dW, G.acc[wi], ctx.needs_input_grad[0],
+                                          dzc=dzc)
             elif ctx.needs_input_grad[0]:
                 dx = hip.linear_bwd_all(dh2, W, inp, None, None, dW, None, None, G.acc[wi],
                                         act=hip.ACT_NONE).view(B, n, -1)
@@ -374,7 +419,7 @@ class GCNStackFn(torch.autograd.Function):
                 hip.linear_bwd_dw(dh2, inp, None, dW, None, G.acc[wi])
         if dx is not None and ctx.squeeze:
             dx = dx[0]
-        return (dx,) + (None,) * 8 + G.out()
+        return (dx,) + (None,) * 9 + G.out()
 
 
 # ------------------------------------------------------------------------------------------------
@@ -664,6 +709,15 @@ class GradLanding:
                 mesh side (always later: its gradient comes through the processor from the gather): tail() - the buffer,
                 to be filled in place from row `head` (its backward then returns None), or (None, 0): write a fresh
                 tensor from row 0.  The landing lets go of the buffer here; autograd already owns it.
+    Where the producer of the encoder output is a GCN stack that can read a two-part gradient (GCNStackFn `split`: the
+    model makes the landing before the encoder runs and hands it in), neither part is copied at all:
+      forward   encoder stack: expect_split_reader()
+      backward  Gather2Fn: head_grad() keeps the gather's incoming gradient g - its first `head` rows ARE the head rows
+                (`head_identity`: inv_a[:head] is the identity) - and returns a stride-0 token
+                mesh side: keep_tail(dxc) keeps its compact rows (its backward then returns None)
+                encoder stack: claim_parts(dy) - the two parts when `dy` is the token; when something else also sent
+                gradient to the encoder output (a hook, the grid latents forward_with_latents returns) autograd has
+                summed it with the token into a real tensor, and the parts are copied into one buffer and added to it.
 
     Processor-output gradient.  The processor's output is consumed by the decoder-input gather alone, so its gradient is
     the gather's incoming gradient seen through a row map; the final LayerNorm's backward reads it that way
@@ -683,8 +737,9 @@ class GradLanding:
       Gather2Fn  take_decoder_input(): the filled buffer with the head rows copied in; a buffer nobody filled is dropped
                  (None: the caller gathers both sources)."""
 
-    def __init__(self, head: int):
+    def __init__(self, head: int, head_identity: bool = False):
         self.head, self.buf, self.mesh_pending = head, None, False
+        self.head_identity, self.split_ready, self.part_head, self.part_tail = head_identity, False, None, None
         self.proc_ready, self.proc_src, self.proc_map = False, None, None
         self.dec_buf, self.dec_map, self.dec_rows, self.dec_filled = None, None, None, False
 
@@ -694,9 +749,17 @@ class GradLanding:
         if land is not None:
             land.mesh_pending = True
 
+    def expect_split_reader(self):
+        self.split_ready = True
+
     def head_grad(self, g, inv_a, shape, B: int):
         if not self.mesh_pending:
             return None
+        if (self.split_ready and self.head_identity and g.dim() == 3 and g.shape[1] >= self.head and g.shape[2] == shape[2]
+                and g.shape[2] % 4 == 0 and g.stride(2) == 1 and g.stride(1) % 4 == 0 and g.stride(0) % 4 == 0
+                and g.data_ptr() % 16 == 0):  # whole 16-byte rows, as gcl_aggregate_split / gcl_colsum_split need
+            self.part_head = g[:, : self.head]
+            return _token(g, shape)
         self.buf = torch.empty(shape, dtype=torch.float32, device=g.device)
         hip.gather2_rows(g, inv_a, None, None, self.head, B, out=self.buf[:, : self.head])
         return self.buf
@@ -707,6 +770,37 @@ class GradLanding:
             return None, 0
         buf, land.buf, land.mesh_pending = land.buf, None, False
         return buf, land.head
+
+    @staticmethod
+    def keep_tail(land, tail3) -> bool:
+        """Mesh side, before tail(): with a two-part reader waiting, keep the compact tail rows [B, ne - head, F] (None: the
+        mesh side sends no gradient, the rows are zero) and say so."""
+        if land is None or land.part_head is None:
+            return False
+        land.part_tail, land.mesh_pending = tail3, False
+        return True
+
+    @staticmethod
+    def claim_parts(land, dy):
+        """-> (dy, parts): parts = (head rows, tail rows) when `dy` is the token, else None and `dy` dense (with the
+        kept parts added, if any were kept)."""
+        if land is None or land.part_head is None:
+            return dy, None
+        a3, b3 = land.part_head, land.part_tail
+        land.part_head = land.part_tail = None
+        land.split_ready = False
+        if b3 is not None and all(st == 0 for st in dy.stride()):
+            return dy, (a3, b3)
+        # the old way: one dense buffer (head rows copied, tail rows copied or zero), plus what else arrived
+        B, ne, F = dy.shape
+        buf = torch.empty(B, ne, F, dtype=torch.float32, device=a3.device) if b3 is not None else \
+            torch.zeros(B, ne, F, dtype=torch.float32, device=a3.device)
+        hip.copy_rows(a3, buf[:, : land.head])
+        if b3 is not None:
+            hip.copy_rows(b3, buf[:, land.head:])
+        if all(st == 0 for st in dy.stride()):
+            return buf, None
+        return _flat3(dy) + buf, None
 
     # processor-output gradient
     def expect_mapped_reader(self):
@@ -785,6 +879,14 @@ class MeshLatFn(torch.autograd.Function):
         _, _, inv_a, inv_fold = ctx.maps
         B, ne, D = ctx.shape
         g = g.contiguous()
+        land = ctx.landing
+        if land is not None and land.part_head is not None:  # a two-part reader waits: write the tail rows compact
+            h = land.head
+            t3 = torch.empty(B, ne - h, D, dtype=torch.float32, device=g.device)
+            hip.gather2_rows(g, inv_a[h:], None, None, ctx.gmd - h, B, out=t3[:, : ctx.gmd - h])
+            _fold_sum(g, inv_fold, ctx.r, B, t3[:, ctx.gmd - h:])
+            GradLanding.keep_tail(land, t3)
+            return None, None, None, None, None, None
         buf, h = GradLanding.tail(ctx.landing)  # rows below h were written by the decoder-input gather's backward
         out = buf if buf is not None else torch.empty(B, ne, D, dtype=torch.float32, device=g.device)
         hip.gather2_rows(g, inv_a[h:], None, None, ctx.gmd - h, B, out=out[:, h: ctx.gmd])

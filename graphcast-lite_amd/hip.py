@@ -45,6 +45,8 @@ _SIGNATURES = {
     "gcl_layernorm_bwd_deferred": (C.c_int, [_vp, _i64, _i64, _vp, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp,
                                              _i32, _i64, _i32, _vp, _sz, _vp, _vp]),
     "gcl_colsum_deferred": (C.c_int, [_vp, _i64, _i64, _i32, _vp, _i32, _vp, _sz, _vp, _vp]),
+    "gcl_colsum_split_deferred": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _sz,
+                                            _vp, _vp]),
     "gcl_linear_bwd_dw_deferred": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _sz, _vp,
                                              _vp]),
     "gcl_dense_bwd_dw_deferred": (C.c_int, [_vp, _i64, _vp, _i64, _i32, _vp, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _vp,
@@ -52,6 +54,10 @@ _SIGNATURES = {
     "gcl_linear_bwd_all_ws_bytes": (_sz, [_i64, _i32, _i32]),
     "gcl_aggregate": (C.c_int, [_vp, _i32, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i32, _i32, _vp]),
     "gcl_aggregate_present": (C.c_int, [_vp, _i32, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _vp]),
+    "gcl_aggregate_compact_ok": (C.c_int, [_vp, _i32, _i64, _i64, _i64, _i64, _i32, _i32]),
+    "gcl_aggregate_compact": (C.c_int, [_vp, _i32, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _i64, _i64, _i32, _i32, _vp]),
+    "gcl_aggregate_split": (C.c_int, [_vp, _i32, _vp, _i64, _i64, _vp, _i64, _i64, _i32, _vp, _vp, _i64, _i64, _i32, _i32,
+                                      _vp]),
     "gcl_gat_fwd": (C.c_int, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _vp]),
     "gcl_gat_bwd": (C.c_int, [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64,
                               _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _sz, _vp]),
@@ -79,6 +85,7 @@ _SIGNATURES = {
     "gcl_graphnorm_ws_bytes": (_sz, [_i32, _i32, _i32]),
     "gcl_colsum": (C.c_int, [_vp, _i64, _i64, _i32, _vp, _i32, _vp, _sz, _vp]),
     "gcl_colsum_ws_bytes": (_sz, [_i64, _i32]),
+    "gcl_colsum_split": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _sz, _vp]),
     "gcl_assemble_input": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp]),
     "gcl_assemble_input_tail": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp]),
     "gcl_wmse_fwd_bwd": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _f32, _f32, _vp,
@@ -591,6 +598,46 @@ def aggregate_present(graph: Graph, h3, present, bias=None, transpose=False, out
     return out
 
 
+def aggregate_compact_ok(graph: Graph, h3, transpose=False) -> bool:
+    """Can aggregate_compact take h3 [B, n, F] (output dense [B, n, F])?"""
+    B, n, F = h3.shape
+    return bool(lib().gcl_aggregate_compact_ok(graph.handle, 1 if transpose else 0, h3.stride(1), h3.stride(0), F, n * F, B, F))
+
+
+def aggregate_compact(graph: Graph, h3, smap, outc, transpose=False, out=None):
+    """hip.aggregate with a store map: int32 smap [n], entry >= 0 = that row goes to row smap[i] of outc [B, *, F] instead
+    of `out` (whose rows with such an entry stay unwritten).  Reported to the launch probe under a kind of its own."""
+    B, n, F = h3.shape
+    assert n == graph.n and h3.stride(2) == 1 and outc.stride(2) == 1 and outc.shape[0] == B and outc.shape[2] == F
+    assert smap.dtype == torch.int32 and smap.numel() == n and smap.is_contiguous()
+    if out is None:
+        out = torch.empty(B, n, F, dtype=torch.float32, device=h3.device)
+    tok = _probe_begin("aggregate_compact", graph=graph, transpose=bool(transpose), B=B, F=F)
+    _check(lib().gcl_aggregate_compact(graph.handle, 1 if transpose else 0, _p(h3), h3.stride(1), h3.stride(0), _pi(smap),
+                                       _p(out), out.stride(1), out.stride(0), _p(outc), outc.stride(1), outc.stride(0), B, F,
+                                       _stream()))
+    _probe_end(tok)
+    return out
+
+
+def aggregate_split(graph: Graph, a3, b3, transpose=False, out=None):
+    """hip.aggregate over the rows of TWO tensors: a3 [B, head, F] are rows < head of every sample, b3 [B, n - head, F] the
+    rest (any row / batch strides that keep rows whole 16-byte units).  Reported to the launch probe under a kind of its
+    own."""
+    B, head, F = a3.shape
+    n = head + b3.shape[1]
+    assert n == graph.n, f"graph has {graph.n} nodes, the two parts have {n} rows"
+    assert b3.shape[0] == B and b3.shape[2] == F and a3.stride(2) == 1 and b3.stride(2) == 1
+    if out is None:
+        out = torch.empty(B, n, F, dtype=torch.float32, device=a3.device)
+    tok = _probe_begin("aggregate_split", graph=graph, transpose=bool(transpose), B=B, F=F)
+    _check(lib().gcl_aggregate_split(graph.handle, 1 if transpose else 0, _p(a3), a3.stride(1), a3.stride(0), _p(b3),
+                                     b3.stride(1), b3.stride(0), head, None, _p(out), out.stride(1), out.stride(0), B, F,
+                                     _stream()))
+    _probe_end(tok)
+    return out
+
+
 def layernorm_fwd(x, gamma, beta, eps=1e-5):
     rows, F = x.shape
     y = torch.empty(rows, F, dtype=torch.float32, device=x.device)
@@ -692,6 +739,23 @@ def colsum(x, out, accumulate: bool):
         return out
     ws = workspace(nb, x.device)
     _check(lib().gcl_colsum(_p(x), _ld(x), rows, F, _p(out), 1 if accumulate else 0, ws.data_ptr(), ws.numel(), _stream()))
+    return out
+
+
+def colsum_split(a3, b3, out, accumulate: bool):
+    """hip.colsum over the B * n rows of a two-part source (see aggregate_split)."""
+    B, head, F = a3.shape
+    n = head + b3.shape[1]
+    assert b3.shape[0] == B and b3.shape[2] == F and a3.stride(2) == 1 and b3.stride(2) == 1
+    nb = lib().gcl_colsum_ws_bytes(B * n, F)
+    args = (_p(a3), a3.stride(1), a3.stride(0), _p(b3), b3.stride(1), b3.stride(0), head, n, B, F, _p(out),
+            1 if accumulate else 0)
+    if _deferred.active:
+        _queue(nb, a3.device, (out,), 1, lambda ws, jobs: lib().gcl_colsum_split_deferred(
+            *args, ws.data_ptr(), ws.numel(), _stream(), C.cast(jobs, C.c_void_p)))
+        return out
+    ws = workspace(nb, a3.device)
+    _check(lib().gcl_colsum_split(*args, ws.data_ptr(), ws.numel(), _stream()))
     return out
 
 

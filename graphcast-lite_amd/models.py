@@ -128,7 +128,7 @@ class GCNConv(nn.Module):
 
     def forward(self, x, edge_index):
         g = _graphs.get(edge_index, _num_nodes(x), hip.GRAPH_GCN)
-        return GCNStackFn.apply(x, self, g, 1, False, 1e-5, 0, None, None, self.lin.weight, self.bias, None)
+        return GCNStackFn.apply(x, self, g, 1, False, 1e-5, 0, None, None, None, self.lin.weight, self.bias, None)
 
 
 class GATConv(nn.Module):
@@ -413,6 +413,7 @@ class GraphLayer(nn.Module):
                 raise ValueError("InteractionNet requires edge_attr (edge features)")
             return self.layers(x=X, edge_index=edge_index, edge_attr_raw=edge_attr)
         # _land: functional.GradLanding for the final node LayerNorm; _lat: functional.LatSource (X is then the encoder output)
+        # _split: functional.GradLanding of a stack whose output is the encoder output (its gradient arrives in two parts)
         land = kwargs.get("_land")
         lat_src = kwargs.get("_lat") if self.layer_type in (GraphLayerType.ConvGCN, GraphLayerType.GATConv) else None
         n = lat_src.M if lat_src is not None else _num_nodes(X)  # with a LatSource X is the encoder output, the graph the mesh
@@ -430,11 +431,11 @@ class GraphLayer(nn.Module):
             g = _graphs.get(edge_index, n, hip.GRAPH_GCN)
             out_rows = int(kwargs.get("_out_rows") or 0)  # the caller keeps only the first rows (decoder: grid rows)
             if ln is not None and not fuse_ln:
-                X = GCNStackFn.apply(X, self, g, len(convs), False, 1e-5, 0, None, lat_src, *params)
+                X = GCNStackFn.apply(X, self, g, len(convs), False, 1e-5, 0, None, lat_src, None, *params)
                 X = ln(X)
                 return X[..., :out_rows, :] if out_rows else X
             return GCNStackFn.apply(X, self, g, len(convs), fuse_ln, ln.eps if fuse_ln else 1e-5, out_rows,
-                                    land if fuse_ln else None, lat_src, *params)
+                                    land if fuse_ln else None, lat_src, kwargs.get("_split"), *params)
 
         if self.layer_type == GraphLayerType.GATConv:
             slope, act = None, hip.ACT_NONE
@@ -743,6 +744,14 @@ class WeatherPrediction(nn.Module):
             map_b = map_b[c.perm[0]]
             inv_fold[:Mi] = c.perm[1][c.mi]
         f.maps = (c.maps_mesh[0], i32(map_b), c.maps_mesh[2], i32(inv_fold))
+        # store map of the first processor layer's transposed aggregation (functional.LatSource.smap): mesh row -> its
+        # place among the Md dependent rows of the compact gradient, when inv_a[G: G + Md] is one-to-one
+        dep = c.maps_mesh[2].cpu().to(torch.int64)[G: G + Md]
+        f.smap = None
+        if Md > 0 and int(dep.min()) >= 0 and int(dep.max()) < M and torch.unique(dep).numel() == Md:
+            smap = torch.full((M,), -1, dtype=torch.int64)
+            smap[dep] = torch.arange(Md)
+            f.smap = i32(smap)
         # the same two maps as ONE row table for consumers that read the mesh latents through it (gcl_gcn_layer_fwd_tab):
         # entry >= 0: row of the sample's own encoder output, entry < 0: ~(flat row of the batch-invariant list)
         f.tab = torch.where(f.maps[0] >= 0, f.maps[0], -f.maps[1] - 1).to(torch.int32).contiguous()
@@ -774,6 +783,9 @@ class WeatherPrediction(nn.Module):
         # decoder-input maps: the encoder output now has ne rows per sample, the folded ones feed nothing there
         dinv_a = torch.cat([c.maps_dec[2], torch.full((r,), -1, dtype=torch.int32, device=device)]).contiguous()
         f.maps_dec = (c.maps_dec[0], c.maps_dec[1], dinv_a, c.maps_dec[3])
+        # the decoder-input gather takes its first G rows from the first G encoder rows in order: what the two-part reader
+        # of the encoder-output gradient assumes (functional.GradLanding.head_grad), checked here once
+        f.dec_head_identity = bool(torch.equal(dinv_a[:G].cpu().to(torch.int64), torch.arange(G)))
         c.fold[B] = f
         return f
 
@@ -793,15 +805,18 @@ class WeatherPrediction(nn.Module):
             # (every mesh node has grid senders, e.g. 512x256) the same path runs with r = 0, so the two gradient
             # consumers of the encoder output still share one landing buffer instead of autograd adding two full tensors
             f = c.fold.get(B) or self._fold_setup(c, B, X3.device)
+            # made before the encoder runs: its GCN stack, when it can read a gradient in two parts, announces that to the
+            # landing it is given (functional.GCNStackFn `split`).  head_identity: checked on the map in _fold_setup
+            land = GradLanding(G, head_identity=f.dec_head_identity) if _landing and self._grad_landing else None
+            ekw = {"_split": land} if (land is not None and self.encoder.graph_layer.layer_type == GraphLayerType.ConvGCN) else {}
             if self._mlp_on_folded_rows and self.encoder.mlp is not None and f.rd > 0:
                 x_m = AssembleFn.apply(X3, self.init_grid_features, f.mstat2, f.x_tail2)   # [B, G+r+rd, C]
                 h_m = self.encoder.mlp(X=x_m)                                              # [B, G+r+rd, D']
                 x_g = MeshLatFn.apply(h_m, f.maps_e, f.ne, G + f.r, f.rd, None)            # [B, G+Md+r, D']
-                enc_c = self.encoder.graph_layer(X=x_g, edge_index=c.enc_graph)            # [B, G+Md+r, D]
+                enc_c = self.encoder.graph_layer(X=x_g, edge_index=c.enc_graph, **ekw)     # [B, G+Md+r, D]
             else:
                 x_c = AssembleFn.apply(X3, self.init_grid_features, f.mstat, f.x_fold if f.r > 0 else None)  # [B, G+Md+r, C]
-                enc_c = self.encoder.forward(X=x_c, edge_index=c.enc_graph)         # [B, G+Md+r, D]
-            land = GradLanding(G) if _landing and self._grad_landing else None
+                enc_c = self.encoder.forward(X=x_c, edge_index=c.enc_graph, **ekw)  # [B, G+Md+r, D]
             lat_src = self._lat_source(c, f, enc_c, land)
             if lat_src is None:
                 mesh_lat = MeshLatFn.apply(enc_c, f.maps, M, G + c.Md, f.r, land)   # [B, M, D]
@@ -868,7 +883,7 @@ class WeatherPrediction(nn.Module):
             g = _graphs.get(self._processing_graph_tiled(), self._num_mesh_nodes, hip.GRAPH_GAT)
             if not hip.gat_tab_ok(g, 1, first.lin.weight.shape[0]):
                 return None
-            return LatSource(f.tab, f.maps, self._num_mesh_nodes, self._num_grid_nodes, c.Md, f.r, land)
+            return LatSource(f.tab, f.maps, self._num_mesh_nodes, self._num_grid_nodes, c.Md, f.r, land, smap=f.smap)
         if gl.layer_type != GraphLayerType.ConvGCN:
             return None
         convs = [m for m in gl.layers if isinstance(m, GCNConv)]
@@ -877,7 +892,7 @@ class WeatherPrediction(nn.Module):
         g = _graphs.get(self._processing_graph_tiled(), self._num_mesh_nodes, hip.GRAPH_GCN)
         if not hip.gcn_layer_tab_ok(g, enc_c, convs[0].lin.weight.shape[0]):
             return None
-        return LatSource(f.tab, f.maps, self._num_mesh_nodes, self._num_grid_nodes, c.Md, f.r, land)
+        return LatSource(f.tab, f.maps, self._num_mesh_nodes, self._num_grid_nodes, c.Md, f.r, land, smap=f.smap)
 
     def forward_with_latents(self, X: torch.Tensor, attention_threshold=0.0, _landing=False, _latents_discarded=False,
                              **kwargs):

@@ -179,6 +179,9 @@ int gcl_layernorm_bwd_deferred(const float* dy, int64_t lddy, int64_t bsdy, cons
                                gcl_stream_t stream, gcl_reduce_job* job);
 int gcl_colsum_deferred(const float* x, int64_t ldx, int64_t rows, int32_t F, float* out, int32_t accumulate, void* ws,
                         size_t ws_bytes, gcl_stream_t stream, gcl_reduce_job* job);
+int gcl_colsum_split_deferred(const float* a, int64_t lda, int64_t bsa, const float* b, int64_t ldb, int64_t bsb,
+                              int32_t head, int32_t n, int32_t B, int32_t F, float* out, int32_t accumulate, void* ws,
+                              size_t ws_bytes, gcl_stream_t stream, gcl_reduce_job* job);
 int gcl_linear_bwd_dw_deferred(const float* dy, int64_t lddy, const float* x, int64_t ldx, const float* in_slope,
                                float* dW, float* db, int64_t rows, int32_t Fin, int32_t Fout, int32_t accumulate,
                                void* ws, size_t ws_bytes, gcl_stream_t stream, gcl_reduce_job* job /* [2] */);
@@ -240,6 +243,23 @@ int gcl_aggregate(const gcl_graph_t* g, int32_t transpose, const float* h, int64
 int gcl_aggregate_present(const gcl_graph_t* g, int32_t transpose, const float* h, int64_t ldh, int64_t bsh,
                           const int32_t* present /*[n]*/, const float* bias, float* y, int64_t ldy, int64_t bsy,
                           int32_t B, int32_t F, gcl_stream_t stream);
+/* The same with the source rows in TWO tensors: row j of sample b is h + b * bsh + j * ldh for j < head and
+ * h2 + b * bsh2 + (j - head) * ldh2 otherwise (a gradient whose head and tail rows were left in two places by their
+ * producers).  Both parts and y need 16-byte rows (F % 4 == 0, strides % 4 == 0, aligned bases), else GCL_EINVAL; a part
+ * with no rows (head == 0 / head == n) may be NULL.  Bit-equal to gcl_aggregate on the two parts copied into one tensor. */
+int gcl_aggregate_split(const gcl_graph_t* g, int32_t transpose, const float* h, int64_t ldh, int64_t bsh,
+                        const float* h2, int64_t ldh2, int64_t bsh2, int32_t head, const float* bias, float* y,
+                        int64_t ldy, int64_t bsy, int32_t B, int32_t F, gcl_stream_t stream);
+/* gcl_aggregate with a STORE map: smap [n] has one entry per row, >= 0 = that row of every sample is stored to row
+ * smap[i] of the compact destination yc [B, *, F] INSTEAD of y, < 0 = stored to y as always.  Each row is written once,
+ * to one place, with gcl_aggregate's bits; the rows of y with an entry >= 0 are not touched.  Only the source-tile kernel
+ * has the map: gcl_aggregate_compact_ok says (1 / 0) whether a call with these strides is taken, otherwise
+ * gcl_aggregate_compact returns GCL_EINVAL and writes nothing. */
+int gcl_aggregate_compact_ok(const gcl_graph_t* g, int32_t transpose, int64_t ldh, int64_t bsh, int64_t ldy, int64_t bsy,
+                             int32_t B, int32_t F);
+int gcl_aggregate_compact(const gcl_graph_t* g, int32_t transpose, const float* h, int64_t ldh, int64_t bsh,
+                          const int32_t* smap /*[n]*/, float* y, int64_t ldy, int64_t bsy, float* yc, int64_t ldc,
+                          int64_t bsc, int32_t B, int32_t F, gcl_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * GATConv(heads=H, concat=False) attention + aggregation  (src/models.py:425; SparseGATConv :135)
@@ -357,6 +377,11 @@ size_t gcl_graphnorm_ws_bytes(int32_t B, int32_t n, int32_t F);
 int gcl_colsum(const float* x, int64_t ldx, int64_t rows, int32_t F, float* out, int32_t accumulate,
                void* ws, size_t ws_bytes, gcl_stream_t stream);
 size_t gcl_colsum_ws_bytes(int64_t rows, int32_t F);
+/* Column sums over the B * n rows of a two-part source (see gcl_aggregate_split; the same conditions): bit-equal to
+ * gcl_colsum on the two parts copied into one [B * n, F] tensor.  Workspace: gcl_colsum_ws_bytes(B * n, F). */
+int gcl_colsum_split(const float* a, int64_t lda, int64_t bsa, const float* b, int64_t ldb, int64_t bsb, int32_t head,
+                     int32_t n, int32_t B, int32_t F, float* out, int32_t accumulate, void* ws, size_t ws_bytes,
+                     gcl_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Input assembly (src/models.py:776-806): out[b] = [ x[b] | grid_static ; 0 | mesh_static ],
