@@ -18,11 +18,102 @@
 // never leave the XCD.  Placement is a speed choice only; results do not depend on it.
 #include <algorithm>
 
+#include <atomic>
+
 #include "common.h"
 #include "halo.h"
 #include "mfma_io.h"
 
 namespace {
+
+// One block per (heavy row, sample): the 256/LPR lane groups stride over the row's edges (4 loads
+// in flight each) and are combined through LDS in a fixed order.  Only rows with more than kHeavy
+// edges take this path (polar mesh nodes of E_G2M / E_M2G at 512x256: up to 943 edges), so a
+// single wave no longer serialises hundreds of dependent gathers at the tail of the launch.
+// One text for both homes of such a block: agg_heavy_kernel (a launch of its own) and the first blocks of
+// agg_kernel<.., HV> - the same lane-group stride and the same fixed-order combine, so the same bits.
+template <int LPR, bool VL, bool VS, bool PRES, bool SPLIT>
+__device__ __forceinline__ void agg_heavy_row(const int row, const int b, const int32_t* __restrict__ rowptr,
+                                              const int32_t* __restrict__ col, const float* __restrict__ w,
+                                              const float* __restrict__ H, int64_t ldh, int64_t bsh,
+                                              const float* __restrict__ bias, float* __restrict__ Y, int64_t ldy,
+                                              int64_t bsy, int32_t F, const int32_t* __restrict__ present,
+                                              const float* __restrict__ H2, int64_t ldh2, int64_t bsh2, int32_t head) {
+  constexpr int NG = 256 / LPR;
+  __shared__ float red[NG][LPR * 4 + 1];
+  const int g = threadIdx.x / LPR, l = threadIdx.x % LPR;
+  const int c0 = l * 4;
+  const bool cactive = c0 < F;
+  const int cc = cactive ? c0 : 0;
+  const float* __restrict__ Hb = H + (int64_t)b * bsh;
+  const float* __restrict__ H2b = SPLIT ? H2 + (int64_t)b * bsh2 : nullptr;
+  const int start = rowptr[row], end = rowptr[row + 1];
+  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+  auto ld4 = [&](int j, float& x0, float& x1, float& x2, float& x3) {
+    const float* p = Hb + (int64_t)j * ldh + cc;
+    if (PRES) p = present[j] >= 0 ? p : reinterpret_cast<const float*>(gcl::mfma_io::zero4);
+    if (SPLIT) p = j < head ? p : H2b + (int64_t)(j - head) * ldh2 + cc;
+    if (VL) {
+      const float4 v = *reinterpret_cast<const float4*>(p);
+      x0 = v.x; x1 = v.y; x2 = v.z; x3 = v.w;
+    } else {
+      x0 = p[0];
+      x1 = (cc + 1 < F) ? p[1] : 0.f;
+      x2 = (cc + 2 < F) ? p[2] : 0.f;
+      x3 = (cc + 3 < F) ? p[3] : 0.f;
+    }
+  };
+  for (int e = start + g; e < end; e += 4 * NG) {
+    const int e1 = e + NG, e2 = e + 2 * NG, e3 = e + 3 * NG;
+    const int j0 = col[e], j1 = col[e1 < end ? e1 : e], j2 = col[e2 < end ? e2 : e], j3 = col[e3 < end ? e3 : e];
+    const float w0 = w[e], w1 = e1 < end ? w[e1] : 0.f, w2 = e2 < end ? w[e2] : 0.f, w3 = e3 < end ? w[e3] : 0.f;
+    float p0, p1, p2, p3, q0, q1, q2, q3, r0, r1, r2, r3, s0, s1, s2, s3;
+    ld4(j0, p0, p1, p2, p3);
+    ld4(j1, q0, q1, q2, q3);
+    ld4(j2, r0, r1, r2, r3);
+    ld4(j3, s0, s1, s2, s3);
+    a0 += w0 * p0; a1 += w0 * p1; a2 += w0 * p2; a3 += w0 * p3;
+    if (e1 < end) { a0 += w1 * q0; a1 += w1 * q1; a2 += w1 * q2; a3 += w1 * q3; }
+    if (e2 < end) { a0 += w2 * r0; a1 += w2 * r1; a2 += w2 * r2; a3 += w2 * r3; }
+    if (e3 < end) { a0 += w3 * s0; a1 += w3 * s1; a2 += w3 * s2; a3 += w3 * s3; }
+  }
+  red[g][c0] = a0; red[g][c0 + 1] = a1; red[g][c0 + 2] = a2; red[g][c0 + 3] = a3;
+  __syncthreads();
+  if (g == 0 && cactive) {
+    float t0 = 0.f, t1 = 0.f, t2 = 0.f, t3 = 0.f;
+#pragma unroll
+    for (int q = 0; q < NG; ++q) { t0 += red[q][c0]; t1 += red[q][c0 + 1]; t2 += red[q][c0 + 2]; t3 += red[q][c0 + 3]; }
+    if (bias) {
+      t0 += bias[c0];
+      if (c0 + 1 < F) t1 += bias[c0 + 1];
+      if (c0 + 2 < F) t2 += bias[c0 + 2];
+      if (c0 + 3 < F) t3 += bias[c0 + 3];
+    }
+    float* yp = Y + (int64_t)b * bsy + (int64_t)row * ldy + c0;
+    if (VS) {
+      *reinterpret_cast<float4*>(yp) = make_float4(t0, t1, t2, t3);
+    } else {
+      yp[0] = t0;
+      if (c0 + 1 < F) yp[1] = t1;
+      if (c0 + 2 < F) yp[2] = t2;
+      if (c0 + 3 < F) yp[3] = t3;
+    }
+  }
+}
+
+template <int LPR, bool VL, bool VS, bool PRES = false, bool SPLIT = false>
+__global__ __launch_bounds__(256) void agg_heavy_kernel(const int32_t* __restrict__ rows_heavy,
+                                                        const int32_t* __restrict__ rowptr,
+                                                        const int32_t* __restrict__ col, const float* __restrict__ w,
+                                                        const float* __restrict__ H, int64_t ldh, int64_t bsh,
+                                                        const float* __restrict__ bias, float* __restrict__ Y,
+                                                        int64_t ldy, int64_t bsy, int32_t F,
+                                                        const int32_t* __restrict__ present = nullptr,
+                                                        const float* __restrict__ H2 = nullptr, int64_t ldh2 = 0,
+                                                        int64_t bsh2 = 0, int32_t head = 0) {
+  agg_heavy_row<LPR, VL, VS, PRES, SPLIT>(rows_heavy[blockIdx.x], blockIdx.y, rowptr, col, w, H, ldh, bsh, bias, Y, ldy, bsy, F,
+                                          present, H2, ldh2, bsh2, head);
+}
 
 // EW = number of ELL-prefix neighbours every row reads unconditionally (1, 2, 4 or 8; chosen per
 // graph so that most rows fit).  Per batch the dependency chain is: {rowptr pair, ELL entries}
@@ -34,7 +125,10 @@ namespace {
 // SPLIT: the source rows live in two tensors - row j of sample b is H + b * bsh + j * ldh for j < head, else
 // H2 + b * bsh2 + (j - head) * ldh2 (gcl_aggregate_split).  The kernel computes one address per gathered row anyway, so
 // the choice is a pointer select on the row index: no table, no extra load, the sums are those of the plain kernel.
-template <int LPR, bool VL, bool VS, int EW, int ITER, bool PRES = false, bool SPLIT = false>
+// HV: the launch carries n_hb = n_heavy * B extra blocks in front (padded to n_hb_pad, a multiple of the XCD count, so
+// the body blocks keep their XCDs); block k < n_hb runs heavy row k % n_heavy of sample k / n_heavy (agg_heavy_row)
+// under the body blocks instead of in a launch of its own after them.  Instantiations without HV are the old text.
+template <int LPR, bool VL, bool VS, int EW, int ITER, bool PRES = false, bool SPLIT = false, bool HV = false>
 __global__ __launch_bounds__(256) void agg_kernel(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
                                                   const float* __restrict__ w, const int32_t* __restrict__ ecol,
                                                   const float* __restrict__ ew, const float* __restrict__ H,
@@ -44,12 +138,23 @@ __global__ __launch_bounds__(256) void agg_kernel(const int32_t* __restrict__ ro
                                                   int32_t nt_store, const int32_t* __restrict__ order16,
                                                   const int32_t* __restrict__ present = nullptr,
                                                   const float* __restrict__ H2 = nullptr, int64_t ldh2 = 0,
-                                                  int64_t bsh2 = 0, int32_t head = 0) {
+                                                  int64_t bsh2 = 0, int32_t head = 0,
+                                                  const int32_t* __restrict__ rows_heavy = nullptr, int32_t n_heavy = 0,
+                                                  int32_t n_hb = 0, int32_t n_hb_pad = 0) {
   static_assert(!(PRES && SPLIT), "absent rows and a two-part source are not combined");
   constexpr int RPW = 64 / LPR;
   constexpr int EL = LPR < gcl::kEll ? LPR : gcl::kEll;  // ELL entries a lane group can hold
   static_assert(EW <= EL, "ELL width exceeds the lanes of a row group");
-  const int bid = blockIdx.x;
+  int bid = blockIdx.x;
+  if (HV) {
+    if (bid < n_hb) {
+      agg_heavy_row<LPR, VL, VS, PRES, SPLIT>(rows_heavy[bid % n_heavy], bid / n_heavy, rowptr, col, w, H, ldh, bsh, bias, Y, ldy,
+                                              bsy, F, present, H2, ldh2, bsh2, head);
+      return;
+    }
+    if (bid < n_hb_pad) return;
+    bid -= n_hb_pad;
+  }
   int b, rb;
   if (xcd_map) {
     const int xcd = bid & (gcl::kNumXCD - 1);
@@ -199,84 +304,6 @@ __global__ __launch_bounds__(256) void agg_kernel(const int32_t* __restrict__ ro
       }
     }
     start = nstart; end = nend; cj = ncj; wj = nwj;
-  }
-}
-
-// One block per (heavy row, sample): the 256/LPR lane groups stride over the row's edges (4 loads
-// in flight each) and are combined through LDS in a fixed order.  Only rows with more than kHeavy
-// edges take this path (polar mesh nodes of E_G2M / E_M2G at 512x256: up to 943 edges), so a
-// single wave no longer serialises hundreds of dependent gathers at the tail of the launch.
-template <int LPR, bool VL, bool VS, bool PRES = false, bool SPLIT = false>
-__global__ __launch_bounds__(256) void agg_heavy_kernel(const int32_t* __restrict__ rows_heavy,
-                                                        const int32_t* __restrict__ rowptr,
-                                                        const int32_t* __restrict__ col, const float* __restrict__ w,
-                                                        const float* __restrict__ H, int64_t ldh, int64_t bsh,
-                                                        const float* __restrict__ bias, float* __restrict__ Y,
-                                                        int64_t ldy, int64_t bsy, int32_t F,
-                                                        const int32_t* __restrict__ present = nullptr,
-                                                        const float* __restrict__ H2 = nullptr, int64_t ldh2 = 0,
-                                                        int64_t bsh2 = 0, int32_t head = 0) {
-  constexpr int NG = 256 / LPR;
-  __shared__ float red[NG][LPR * 4 + 1];
-  const int row = rows_heavy[blockIdx.x];
-  const int b = blockIdx.y;
-  const int g = threadIdx.x / LPR, l = threadIdx.x % LPR;
-  const int c0 = l * 4;
-  const bool cactive = c0 < F;
-  const int cc = cactive ? c0 : 0;
-  const float* __restrict__ Hb = H + (int64_t)b * bsh;
-  const float* __restrict__ H2b = SPLIT ? H2 + (int64_t)b * bsh2 : nullptr;
-  const int start = rowptr[row], end = rowptr[row + 1];
-  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-  auto ld4 = [&](int j, float& x0, float& x1, float& x2, float& x3) {
-    const float* p = Hb + (int64_t)j * ldh + cc;
-    if (PRES) p = present[j] >= 0 ? p : reinterpret_cast<const float*>(gcl::mfma_io::zero4);
-    if (SPLIT) p = j < head ? p : H2b + (int64_t)(j - head) * ldh2 + cc;
-    if (VL) {
-      const float4 v = *reinterpret_cast<const float4*>(p);
-      x0 = v.x; x1 = v.y; x2 = v.z; x3 = v.w;
-    } else {
-      x0 = p[0];
-      x1 = (cc + 1 < F) ? p[1] : 0.f;
-      x2 = (cc + 2 < F) ? p[2] : 0.f;
-      x3 = (cc + 3 < F) ? p[3] : 0.f;
-    }
-  };
-  for (int e = start + g; e < end; e += 4 * NG) {
-    const int e1 = e + NG, e2 = e + 2 * NG, e3 = e + 3 * NG;
-    const int j0 = col[e], j1 = col[e1 < end ? e1 : e], j2 = col[e2 < end ? e2 : e], j3 = col[e3 < end ? e3 : e];
-    const float w0 = w[e], w1 = e1 < end ? w[e1] : 0.f, w2 = e2 < end ? w[e2] : 0.f, w3 = e3 < end ? w[e3] : 0.f;
-    float p0, p1, p2, p3, q0, q1, q2, q3, r0, r1, r2, r3, s0, s1, s2, s3;
-    ld4(j0, p0, p1, p2, p3);
-    ld4(j1, q0, q1, q2, q3);
-    ld4(j2, r0, r1, r2, r3);
-    ld4(j3, s0, s1, s2, s3);
-    a0 += w0 * p0; a1 += w0 * p1; a2 += w0 * p2; a3 += w0 * p3;
-    if (e1 < end) { a0 += w1 * q0; a1 += w1 * q1; a2 += w1 * q2; a3 += w1 * q3; }
-    if (e2 < end) { a0 += w2 * r0; a1 += w2 * r1; a2 += w2 * r2; a3 += w2 * r3; }
-    if (e3 < end) { a0 += w3 * s0; a1 += w3 * s1; a2 += w3 * s2; a3 += w3 * s3; }
-  }
-  red[g][c0] = a0; red[g][c0 + 1] = a1; red[g][c0 + 2] = a2; red[g][c0 + 3] = a3;
-  __syncthreads();
-  if (g == 0 && cactive) {
-    float t0 = 0.f, t1 = 0.f, t2 = 0.f, t3 = 0.f;
-#pragma unroll
-    for (int q = 0; q < NG; ++q) { t0 += red[q][c0]; t1 += red[q][c0 + 1]; t2 += red[q][c0 + 2]; t3 += red[q][c0 + 3]; }
-    if (bias) {
-      t0 += bias[c0];
-      if (c0 + 1 < F) t1 += bias[c0 + 1];
-      if (c0 + 2 < F) t2 += bias[c0 + 2];
-      if (c0 + 3 < F) t3 += bias[c0 + 3];
-    }
-    float* yp = Y + (int64_t)b * bsy + (int64_t)row * ldy + c0;
-    if (VS) {
-      *reinterpret_cast<float4*>(yp) = make_float4(t0, t1, t2, t3);
-    } else {
-      yp[0] = t0;
-      if (c0 + 1 < F) yp[1] = t1;
-      if (c0 + 2 < F) yp[2] = t2;
-      if (c0 + 3 < F) yp[3] = t3;
-    }
   }
 }
 
@@ -568,6 +595,7 @@ struct AggArgs {
   float* yc = nullptr;
   int64_t ldc = 0, bsc = 0;
   bool dry = false;
+  bool heavy_inside = false;  // GCL_AGG_HEAVY_INSIDE: heavy rows as the first blocks of agg_kernel's launch
 };
 
 // Source-tile path: returns GCL_OK after launching, or -1 when this call is not eligible (agg_kernel runs instead).
@@ -633,10 +661,13 @@ int launch_agg_halo(const AggArgs& ga, const float* h, int64_t ldh, int64_t bsh,
   return GCL_OK;
 }
 
+std::atomic<long long> g_heavy_launches{0};  // launches of agg_heavy_kernel (gcl_aggregate_heavy_launches)
+
 template <int LPR>
 int launch_agg_heavy(const AggArgs& ga, const float* h, int64_t ldh, int64_t bsh, const float* bias, float* y,
                      int64_t ldy, int64_t bsy, int32_t B, int32_t F, bool vl, bool vs, hipStream_t st,
                      const int32_t* present = nullptr) {
+  g_heavy_launches.fetch_add(1, std::memory_order_relaxed);
   dim3 hgrid((unsigned)ga.n_heavy, (unsigned)B), block(256);
   if (ga.h2) {  // (only 16-byte rows reach here: gcl_aggregate_split refuses others)
     hipLaunchKernelGGL((agg_heavy_kernel<LPR, true, true, false, true>), hgrid, block, 0, st, ga.heavy, ga.rowptr, ga.col,
@@ -703,7 +734,13 @@ int launch_agg(const AggArgs& ga, const float* h, int64_t ldh, int64_t bsh, cons
   const int xcd_map = B >= gcl::kNumXCD ? 1 : 0;
   const int64_t nb = xcd_map ? (int64_t)gcl::kNumXCD * gcl::cdiv(B, gcl::kNumXCD) * nRB : (int64_t)B * nRB;
   GCL_CHECK_ARG(nb < (int64_t)INT32_MAX, "aggregate: grid too large");
-  dim3 grid((unsigned)nb), block(256);
+  // heavy rows as the first blocks of this launch where the caller asked for it (16-byte rows, the per-graph default shape of the kernel;
+  // GCL_AGG_HEAVY_SEPARATE=1, read per call: the launch of their own behind it)
+  const bool hv = ga.heavy_inside && ga.n_heavy > 0 && vl && vs && iter == (ewidth >= 4 ? 1 : 2) && !gcl::env_int("GCL_AGG_HEAVY_SEPARATE", 0);
+  const int32_t n_hb = hv ? ga.n_heavy * B : 0;
+  const int32_t n_hb_pad = (int32_t)(gcl::cdiv(n_hb, gcl::kNumXCD) * gcl::kNumXCD);
+  GCL_CHECK_ARG(nb + n_hb_pad < (int64_t)INT32_MAX, "aggregate: grid too large");
+  dim3 grid((unsigned)nb), block(256), gridh((unsigned)(nb + n_hb_pad));
   const int32_t* order16 = (RPW * 4 * iter <= 16) ? ga.order16 : nullptr;
 #define GCL_AGG4(VL_, VS_, EW_, IT_)                                                                             \
   hipLaunchKernelGGL((agg_kernel<LPR, VL_, VS_, EW_, IT_>), grid, block, 0, st, ga.rowptr, ga.col, ga.w, ga.ecol, \
@@ -711,11 +748,34 @@ int launch_agg(const AggArgs& ga, const float* h, int64_t ldh, int64_t bsh, cons
 #define GCL_AGGP(VL_, VS_, EW_, IT_)                                                                                   \
   hipLaunchKernelGGL((agg_kernel<LPR, VL_, VS_, EW_, IT_, true>), grid, block, 0, st, ga.rowptr, ga.col, ga.w, ga.ecol, \
                      ga.ew, h, ldh, bsh, bias, y, ldy, bsy, n, B, F, nRB, xcd_map, nt, order16, present)
+#define GCL_AGGH(EW_, IT_)                                                                                              \
+  hipLaunchKernelGGL((agg_kernel<LPR, true, true, EW_, IT_, false, false, true>), gridh, block, 0, st, ga.rowptr, ga.col, \
+                     ga.w, ga.ecol, ga.ew, h, ldh, bsh, bias, y, ldy, bsy, n, B, F, nRB, xcd_map, nt, order16,           \
+                     (const int32_t*)nullptr, (const float*)nullptr, (int64_t)0, (int64_t)0, 0, ga.heavy, ga.n_heavy, n_hb, \
+                     n_hb_pad)
+#define GCL_AGGHP(EW_, IT_)                                                                                             \
+  hipLaunchKernelGGL((agg_kernel<LPR, true, true, EW_, IT_, true, false, true>), gridh, block, 0, st, ga.rowptr, ga.col,  \
+                     ga.w, ga.ecol, ga.ew, h, ldh, bsh, bias, y, ldy, bsy, n, B, F, nRB, xcd_map, nt, order16, present,  \
+                     (const float*)nullptr, (int64_t)0, (int64_t)0, 0, ga.heavy, ga.n_heavy, n_hb, n_hb_pad)
+#define GCL_AGGHS(EW_, IT_)                                                                                             \
+  hipLaunchKernelGGL((agg_kernel<LPR, true, true, EW_, IT_, false, true, true>), gridh, block, 0, st, ga.rowptr, ga.col,  \
+                     ga.w, ga.ecol, ga.ew, h, ldh, bsh, bias, y, ldy, bsy, n, B, F, nRB, xcd_map, nt, order16,           \
+                     (const int32_t*)nullptr, ga.h2, ga.ldh2, ga.bsh2, ga.head, ga.heavy, ga.n_heavy, n_hb, n_hb_pad)
 #define GCL_AGGS(EW_, IT_)                                                                                              \
   hipLaunchKernelGGL((agg_kernel<LPR, true, true, EW_, IT_, false, true>), grid, block, 0, st, ga.rowptr, ga.col, ga.w,  \
                      ga.ecol, ga.ew, h, ldh, bsh, bias, y, ldy, bsy, n, B, F, nRB, xcd_map, nt, order16,                \
                      (const int32_t*)nullptr, ga.h2, ga.ldh2, ga.bsh2, ga.head)
   if (ga.h2) {  // two-part source: the per-graph default of the plain kernel, 16-byte rows only
+    if (hv) {
+      if constexpr (EL >= 8) {
+        if (ewidth == 8) GCL_AGGHS(8, 1);
+      }
+      if (ewidth == 4) GCL_AGGHS(4, 1);
+      else if (ewidth == 2) GCL_AGGHS(2, 2);
+      else if (ewidth == 1) GCL_AGGHS(1, 2);
+      GCL_CHECK_LAUNCH();
+      return GCL_OK;
+    }
     if constexpr (EL >= 8) {
       if (ewidth == 8) GCL_AGGS(8, 1);
     }
@@ -744,6 +804,29 @@ int launch_agg(const AggArgs& ga, const float* h, int64_t ldh, int64_t bsh, cons
     else if (ewidth == 2) GCL_AGG3(VL_, VS_, 2);                  \
     else GCL_AGG3(VL_, VS_, 1);                                   \
   } while (0)
+  if (hv) {  // (vl && vs, the default ITER of the prefix width)
+    bool done = false;
+    if constexpr (EL >= 8) {
+      if (ewidth == 8) {
+        if (present) GCL_AGGHP(8, 1);
+        else GCL_AGGH(8, 1);
+        done = true;
+      }
+    }
+    if (done) {
+    } else if (ewidth >= 4) {
+      if (present) GCL_AGGHP(4, 1);
+      else GCL_AGGH(4, 1);
+    } else if (ewidth == 2) {
+      if (present) GCL_AGGHP(2, 2);
+      else GCL_AGGH(2, 2);
+    } else {
+      if (present) GCL_AGGHP(1, 2);
+      else GCL_AGGH(1, 2);
+    }
+    GCL_CHECK_LAUNCH();
+    return GCL_OK;
+  }
   if (vl && vs) GCL_AGG2(true, true);
   else if (vl) GCL_AGG2(true, false);
   else if (vs) GCL_AGG2(false, true);
@@ -753,6 +836,9 @@ int launch_agg(const AggArgs& ga, const float* h, int64_t ldh, int64_t bsh, cons
 #undef GCL_AGG4
 #undef GCL_AGGP
 #undef GCL_AGGS
+#undef GCL_AGGH
+#undef GCL_AGGHP
+#undef GCL_AGGHS
   GCL_CHECK_LAUNCH();
   if (ga.n_heavy > 0) return launch_agg_heavy<LPR>(ga, h, ldh, bsh, bias, y, ldy, bsy, B, F, vl, vs, st, present);
   return GCL_OK;
@@ -772,6 +858,8 @@ static int aggregate_impl(const gcl_graph_t* g, int32_t transpose, const float* 
   GCL_CHECK_ARG(dry || h != y, "aggregate: in-place aggregation is not supported");
   AggArgs ga;
   if (compact) ga = *compact;
+  ga.heavy_inside = (transpose & GCL_AGG_HEAVY_INSIDE) != 0;  // `transpose` carries flags (gcl.h)
+  transpose &= 1;
   ga.rowptr = transpose ? g->trowptr : g->rowptr;
   ga.col = transpose ? g->tcol : g->col;
   ga.w = transpose ? g->tw : g->w;
@@ -796,6 +884,8 @@ static int aggregate_impl(const gcl_graph_t* g, int32_t transpose, const float* 
   if (lanes <= 32) return launch_agg<32>(ga, h, ldh, bsh, bias, y, ldy, bsy, g->n, B, F, st, present);
   return launch_agg<64>(ga, h, ldh, bsh, bias, y, ldy, bsy, g->n, B, F, st, present);
 }
+
+extern "C" int64_t gcl_aggregate_heavy_launches(void) { return (int64_t)g_heavy_launches.load(std::memory_order_relaxed); }
 
 extern "C" int gcl_aggregate(const gcl_graph_t* g, int32_t transpose, const float* h, int64_t ldh, int64_t bsh,
                              const float* bias, float* y, int64_t ldy, int64_t bsy, int32_t B, int32_t F,

@@ -476,13 +476,15 @@ __host__ __device__ constexpr int wave_region_f(int tile_f) { return tile_f + kS
 
 // X3: the dense part runs on the bf16 matrix pipe with exact 3-way operand splitting (fp32 accuracy, 0.375x the matrix
 // time, and - unlike the fp32-operand MFMA - it leaves the SIMD's issue port to the other waves' gathers meanwhile).
-template <int NS, int ACT, int EW, int NW, bool SAFE, bool X3>
+// SPLIT: the output has two destinations (gcl_gcn_layer_fwd_split): rows < head go to Y, the others to Yb with their
+// own strides.  head % 32 == 0, so a wave's 32-row tile lies in one part and only its store base differs.
+template <int NS, int ACT, int EW, int NW, bool SAFE, bool X3, bool SPLIT = false>
 __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void gcn_fwd_kernel(
     const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col, const float* __restrict__ w,
     const int32_t* __restrict__ ecol, const float* __restrict__ ew, const float* __restrict__ X, int64_t ldx,
     int64_t bsx, const float* __restrict__ slope_p, const float* __restrict__ W, const float* __restrict__ bias,
     float* __restrict__ Y, int64_t ldy, int64_t bsy, int32_t n, int32_t B, int32_t K, int32_t N, int32_t Nst,
-    int32_t nRT, int32_t n_out) {
+    int32_t nRT, int32_t n_out, float* __restrict__ Yb, int64_t ldb, int64_t bsb, int32_t head) {
   extern __shared__ __align__(16) float smem[];
   const int KP = K + 2;  // K % 4 == 0: even stride with KP/2 odd -> conflict-free 8-byte fragment reads
   float* Wl = smem;      // fp32: [NS*32][KP]; X3: three bf16 piece images [NS*32][kWRowB bytes]
@@ -556,7 +558,10 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void gcn_fwd_kernel(
     asm volatile("" ::"v"(acc[0][0]));
 #endif
     GCL_STAMP(3);
-    store_tile<NS>(acc, At, Y + (int64_t)b * bsy + (int64_t)r0 * ldy, ldy, n_out - r0 < 32 ? n_out - r0 : 32, Nst, bq);
+    float* yt = Y + (int64_t)b * bsy + (int64_t)r0 * ldy;
+    int64_t ldt = ldy;
+    if (SPLIT && r0 >= head) yt = Yb + (int64_t)b * bsb + (int64_t)(r0 - head) * ldb, ldt = ldb;  // (the whole tile: head % 32 == 0)
+    store_tile<NS>(acc, At, yt, ldt, n_out - r0 < 32 ? n_out - r0 : 32, Nst, bq);
     GCL_STAMP(4);
     b = bn;
     r0 = rn;
@@ -965,7 +970,8 @@ extern "C" int gcl_debug_read_stamps(unsigned long long* host_out, int count) {
 static int halo_layer_launch(const gcl_graph_t* g, const float* x, int64_t ldx, int64_t bsx, const int32_t* tab,
                              int64_t x_rows, int32_t act, const float* slope, const float* W, const float* bias, float* y,
                              int64_t ldy, int64_t bsy, int32_t B, int32_t Fin, int32_t Fout, int32_t Fout_store,
-                             int32_t rows_out, hipStream_t st, bool* launched, const int32_t* present = nullptr) {
+                             int32_t rows_out, hipStream_t st, bool* launched, const int32_t* present = nullptr,
+                             bool dry_run = false) {  // dry_run: only tell whether this form would take the layer
   *launched = false;
   const int32_t n = g->n;
   const int halo_on = gcl::env_int("GCL_GCN_HALO", 1);  // read per call: the parity test compares the two kernels
@@ -986,6 +992,10 @@ static int halo_layer_launch(const gcl_graph_t* g, const float* x, int64_t ldx, 
     return GCL_OK;
   if (tab && hp4 > 4) return GCL_OK;  // the table variant exists for the interleaved-issue form only
   if (present && (tab || hp4 > 4 || !gcl::env_int("GCL_GCN_HALO_FORM", 1))) return GCL_OK;  // so does the row predicate
+  if (dry_run) {
+    *launched = true;
+    return GCL_OK;
+  }
   static const int bpc_env = gcl::env_int("GCL_GCN_HALO_BPC", 0);
   const int per_cu = (int)(gcl::kLdsBytes / ldsh);
   const int Jx = 32 * (bpc_env > 0 ? bpc_env : per_cu);
@@ -1036,10 +1046,17 @@ extern "C" int gcl_gcn_layer_fwd(const gcl_graph_t* g, const float* x, int64_t l
                                 g ? g->n : 0, stream);
 }
 
+// second destination of gcl_gcn_layer_fwd_split: rows >= head of every sample go to yb + b * bsb + (i - head) * ldb
+struct SplitDst {
+  float* yb;
+  int64_t ldb, bsb;
+  int32_t head;
+};
+
 static int layer_fwd_impl(const gcl_graph_t* g, const float* x, int64_t ldx, int64_t bsx, int32_t act,
                           const float* slope, const float* W, const float* bias, float* y, int64_t ldy, int64_t bsy,
                           int32_t B, int32_t Fin, int32_t Fout, int32_t Fout_store, int32_t rows_out,
-                          const int32_t* present, gcl_stream_t stream) {
+                          const int32_t* present, gcl_stream_t stream, const SplitDst* sp = nullptr) {
   GCL_CHECK_ARG(g && x && W && y, "gcn_layer_fwd: null argument");
   GCL_CHECK_ARG(g->kind == GCL_GRAPH_GCN || g->kind == GCL_GRAPH_MEAN, "gcn_layer_fwd: graph carries no edge weights");
   GCL_CHECK_ARG(B > 0 && Fin >= 4 && Fin <= 64 && Fin % 4 == 0 && Fout >= 1 && Fout <= 64,
@@ -1055,13 +1072,16 @@ static int layer_fwd_impl(const gcl_graph_t* g, const float* x, int64_t ldx, int
   const int32_t n = g->n;
   GCL_CHECK_ARG(rows_out >= 1 && rows_out <= n, "gcn_layer_fwd: rows_out=%d outside [1, n=%d]", rows_out, n);
   hipStream_t st = (hipStream_t)stream;
+  float* yb = sp ? sp->yb : nullptr;  // (gcl_gcn_layer_fwd_split has made sure that the source-tile form does not take the layer)
+  const int64_t ldb = sp ? sp->ldb : 0, bsb = sp ? sp->bsb : 0;
+  const int32_t head = sp ? sp->head : 0;
   if (present) {  // the form with the output-row predicate, where it exists; storing every row is always right too
     bool launched = false;
     const int rc = halo_layer_launch(g, x, ldx, bsx, nullptr, 0, act, slope, W, bias, y, ldy, bsy, B, Fin, Fout, Fout_store,
                                      rows_out, st, &launched, present);
     if (rc || launched) return rc;
   }
-  {
+  if (!sp) {
     bool launched = false;
     const int rc = halo_layer_launch(g, x, ldx, bsx, nullptr, 0, act, slope, W, bias, y, ldy, bsy, B, Fin, Fout, Fout_store,
                                      rows_out, st, &launched);
@@ -1075,6 +1095,7 @@ static int layer_fwd_impl(const gcl_graph_t* g, const float* x, int64_t ldx, int
   const size_t wave1_b = (size_t)wave_region_f(32 * (KP > NS * 32 ? KP : NS * 32)) * sizeof(float);
   // the split-operand variant holds its A fragments in registers: 8 waves per block (256 VGPRs each) instead of 12
   const bool x3 = x3_env != 0 && (Fin % 16 == 0);
+  GCL_CHECK_ARG(!sp || (x3 && g->kind == GCL_GRAPH_GCN), "gcn_layer_fwd_split: only the split-operand kernel of a GCN graph stores in two parts");
   const int NWr = x3 ? NW8 : NW12;
   const size_t lds = (x3 ? (size_t)3 * NS * 32 * kWRowB : (size_t)NS * 32 * KP * sizeof(float)) + NWr * wave1_b;
   GCL_CHECK_ARG((int64_t)n * ldx * 4 < (int64_t)1 << 31 && n < (1 << 24) && ldx * 4 < (1 << 24),
@@ -1086,16 +1107,18 @@ static int layer_fwd_impl(const gcl_graph_t* g, const float* x, int64_t ldx, int
   const int ewidth = g->ell_cover;  // smallest prefix width that covers (almost) every row: the fix-up loop is the slow path
 #define GCL_GF4(NS_, ACT_, EW_)                \
   do {                                         \
-    if (x3) GCL_GF5(NS_, ACT_, EW_, true);     \
-    else GCL_GF5(NS_, ACT_, EW_, false);       \
+    if (x3 && sp) GCL_GF6(NS_, ACT_, EW_, true, true); /* (split_ok: the two-part form exists with split operands only) */ \
+    else if (x3) GCL_GF6(NS_, ACT_, EW_, true, false); \
+    else GCL_GF6(NS_, ACT_, EW_, false, false); \
   } while (0)
-#define GCL_GF5(NS_, ACT_, EW_, X3_)                                                                                 \
+#define GCL_GF6(NS_, ACT_, EW_, X3_, SP_)                                                                            \
   do {                                                                                                              \
     constexpr int NW = X3_ ? NW8 : NW12;                                                                            \
-    auto kern = gcn_fwd_kernel<NS_, ACT_, EW_, NW, false, X3_>;                                                              \
+    auto kern = gcn_fwd_kernel<NS_, ACT_, EW_, NW, false, X3_, SP_>;                                                \
     GCL_ENSURE_DYN_LDS(kern, gcl::kLdsBytes);                                                                       \
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(NW * 64), lds, st, g->rowptr, g->col, g->w, g->ecol, g->ew, x, \
-                       ldx, bsx, slope, W, bias, y, ldy, bsy, n, B, Fin, Fout, Fout_store, nRT, rows_out);                     \
+                       ldx, bsx, slope, W, bias, y, ldy, bsy, n, B, Fin, Fout, Fout_store, nRT, rows_out, yb, ldb, bsb, \
+                       head);                                                                                       \
   } while (0)
 #define GCL_GF3(NS_, ACT_)                  \
   do {                                      \
@@ -1122,19 +1145,19 @@ static int layer_fwd_impl(const gcl_graph_t* g, const float* x, int64_t ldx, int
       auto kern = gcn_fwd_kernel<2, gcl::kActNone, 8, NW, true, false>;
       GCL_ENSURE_DYN_LDS(kern, gcl::kLdsBytes);
       hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(NW * 64), lds, st, g->rowptr, g->col, g->w, g->ecol, g->ew, x, ldx,
-                         bsx, slope, W, bias, y, ldy, bsy, n, B, Fin, Fout, Fout_store, nRT, rows_out);
+                         bsx, slope, W, bias, y, ldy, bsy, n, B, Fin, Fout, Fout_store, nRT, rows_out, yb, ldb, bsb, head);
     } else {
       auto kern = gcn_fwd_kernel<1, gcl::kActNone, 8, NW, true, false>;
       GCL_ENSURE_DYN_LDS(kern, gcl::kLdsBytes);
       hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(NW * 64), lds, st, g->rowptr, g->col, g->w, g->ecol, g->ew, x, ldx,
-                         bsx, slope, W, bias, y, ldy, bsy, n, B, Fin, Fout, Fout_store, nRT, rows_out);
+                         bsx, slope, W, bias, y, ldy, bsy, n, B, Fin, Fout, Fout_store, nRT, rows_out, yb, ldb, bsb, head);
     }
   } else if (NS == 2) GCL_GF2(2);
   else GCL_GF2(1);
 #undef GCL_GF2
 #undef GCL_GF3
 #undef GCL_GF4
-#undef GCL_GF5
+#undef GCL_GF6
   GCL_CHECK_LAUNCH();
   return GCL_OK;
 }
@@ -1153,6 +1176,52 @@ extern "C" int gcl_gcn_layer_fwd_present(const gcl_graph_t* g, const float* x, i
   GCL_CHECK_ARG(present, "gcn_layer_fwd_present: null presence table");
   return layer_fwd_impl(g, x, ldx, bsx, act, slope, W, bias, y, ldy, bsy, B, Fin, Fout, Fout_store, g ? g->n : 0, present,
                         stream);
+}
+
+// Would gcl_gcn_layer_fwd_split run?  (0: the caller writes one tensor and copies the parts.)
+static bool split_ok(const gcl_graph_t* g, int64_t ldx, int64_t bsx, int64_t lda, int64_t bsa, int64_t ldb, int64_t bsb,
+                     int32_t head, int32_t B, int32_t Fin, int32_t Fout, int32_t Fout_store) {
+  if (!g || g->kind != GCL_GRAPH_GCN || g->n_heavy) return false;
+  const int32_t n = g->n;
+  if (head <= 0 || head >= n || head % 32 != 0) return false;  // a 32-row wave tile must lie in one part
+  if (!(B > 0 && Fin >= 4 && Fin <= 64 && Fin % 4 == 0 && Fout >= 1 && Fout <= 64 && Fout_store >= Fout && Fout_store % 4 == 0 &&
+        Fout_store <= 64))
+    return false;  // the two-kernel fallback's shapes
+  if (ldx < Fin || ldx % 4 || bsx % 4 || lda < Fout_store || ldb < Fout_store || lda % 4 || bsa % 4 || ldb % 4 || bsb % 4)
+    return false;  // whole 16-byte rows in both parts
+  if (!((int64_t)n * ldx * 4 < (int64_t)1 << 31 && n < (1 << 24) && ldx * 4 < (1 << 24) && (int64_t)head * lda * 4 < (int64_t)1 << 31 &&
+        (int64_t)(n - head) * ldb * 4 < (int64_t)1 << 31))
+    return false;  // 32-bit byte offsets, per part
+  // the 8-wave split-operand instantiations carry the variant (what 16-, 32-, 48- and 64-wide inputs select); the 12-wave
+  // fp32-operand ones sit at their register limit
+  if (!(gcl::env_int("GCL_X3", 1) && gcl::env_int("GCL_X3_GCN", 1)) || Fin % 16 != 0) return false;
+  bool halo = false;  // the source-tile form stores through its own path: it keeps the one-tensor destination
+  if (halo_layer_launch(g, nullptr, ldx, bsx, nullptr, 0, GCL_ACT_NONE, nullptr, nullptr, nullptr, nullptr, lda, bsa, B, Fin, Fout,
+                        Fout_store, n, nullptr, &halo, nullptr, true) != GCL_OK)
+    return false;
+  return !halo;
+}
+
+extern "C" int gcl_gcn_layer_fwd_split_ok(const gcl_graph_t* g, int64_t ldx, int64_t bsx, int64_t lda, int64_t bsa, int64_t ldb,
+                                          int64_t bsb, int32_t head, int32_t B, int32_t Fin, int32_t Fout, int32_t Fout_store) {
+  return split_ok(g, ldx, bsx, lda, bsa, ldb, bsb, head, B, Fin, Fout, Fout_store) ? 1 : 0;
+}
+
+// The layer with a two-part destination (gcn_fwd_kernel<.., SPLIT>): rows < head of sample b go to ya + b * bsa + i * lda,
+// the others to yb + b * bsb + (i - head) * ldb.  The same tiles, arithmetic and stores as gcl_gcn_layer_fwd: only a
+// tile's store base differs.  GCL_EINVAL (nothing written) where gcl_gcn_layer_fwd_split_ok says 0.
+extern "C" int gcl_gcn_layer_fwd_split(const gcl_graph_t* g, const float* x, int64_t ldx, int64_t bsx, int32_t act,
+                                       const float* slope, const float* W, const float* bias, float* ya, int64_t lda,
+                                       int64_t bsa, float* yb, int64_t ldb, int64_t bsb, int32_t head, int32_t B, int32_t Fin,
+                                       int32_t Fout, int32_t Fout_store, gcl_stream_t stream) {
+  GCL_CHECK_ARG(g && x && W && ya && yb, "gcn_layer_fwd_split: null argument");
+  GCL_CHECK_ARG(split_ok(g, ldx, bsx, lda, bsa, ldb, bsb, head, B, Fin, Fout, Fout_store),
+                "gcn_layer_fwd_split: head=%d of n=%d rows, strides %lld / %lld or this graph / shape have no two-part form "
+                "(head %% 32 == 0, 0 < head < n, 16-byte rows, the per-edge one-kernel layer)",
+                head, g->n, (long long)lda, (long long)ldb);
+  GCL_CHECK_ARG(gcl::aligned16(yb) && x != yb, "gcn_layer_fwd_split: yb rows must be 16-B aligned and not the input");
+  const SplitDst sp{yb, ldb, bsb, head};
+  return layer_fwd_impl(g, x, ldx, bsx, act, slope, W, bias, ya, lda, bsa, B, Fin, Fout, Fout_store, g->n, nullptr, stream, &sp);
 }
 
 // The layer with its input rows read through a row table (gcn_halo_fwd_kernel<.., TAB>): row i of sample b is row

@@ -43,8 +43,20 @@ class _Grads:
         return tuple(None if r else d for d, r in zip(self.dst, self.ret_none))
 
 
+_ZERO = {}  # device -> the zero scalar every token expands: written once, when it is made, and never again
+
+
 def _token(like: torch.Tensor, shape):  # a stride-0 zero: stands in autograd's graph for rows that travel through a GradLanding
-    return like.new_zeros(()).expand(shape)
+    """No launch: the zero is made once per device.  Nothing writes through a token - autograd adds gradients out of place
+    when a tensor overlaps itself - so all tokens may share it.  The first use on a device inside a stream capture makes
+    a zero of its own instead (memory of the capture's pool must not outlive it)."""
+    z = _ZERO.get(like.device)
+    if z is None:
+        if like.is_cuda and torch.cuda.is_current_stream_capturing():
+            return like.new_zeros(()).expand(shape)
+        with torch.inference_mode(False):
+            z = _ZERO[like.device] = torch.zeros((), dtype=torch.float32, device=like.device)
+    return z.expand(shape)
 
 
 def _flat3(x: torch.Tensor):
@@ -142,6 +154,12 @@ def _split_grad() -> bool:
     return os.environ.get("GCL_NO_SPLIT_GRAD", "0") in ("0", "")
 
 
+def _split_out() -> bool:
+    """The encoder's last conv stores its output where the two readers take it from (GCL_NO_SPLIT_OUT=1: it writes one
+    tensor and each reader copies its rows).  Read per call."""
+    return os.environ.get("GCL_NO_SPLIT_OUT", "0") in ("0", "")
+
+
 def _compact_store() -> bool:
     """The first processor layer's transposed aggregation stores the batch-dependent rows of its output compact
     (GCL_NO_COMPACT_STORE=1: it writes them in place and a gather launch copies them).  Read per call."""
@@ -203,12 +221,14 @@ class LatSource:
     (sum_b dz[b, i]) W and its dW term (sum_b dz[b, i])^T enc_row, so 81 % of the rows (64x32 grid) cost one batch sum
     instead of B dense rows.  maps = MeshLatFn's (map_a, map_b, inv_a, inv_fold)."""
 
-    def __init__(self, tab, maps, M: int, G: int, Md: int, r: int, landing=None, smap=None):
+    def __init__(self, tab, maps, M: int, G: int, Md: int, r: int, landing=None, smap=None, tab_c=None, tail=None):
         """smap: int32 [M], mesh row -> its row among the Md dependent rows of the compact gradient, or -1 (the inverse of
-        inv_a[G: G + Md]; None when that is no one-to-one map)."""
+        inv_a[G: G + Md]; None when that is no one-to-one map).  tab_c = (ne, table): compact_tab(ne), made by the owner once.
+        tail: the rows enc[:, G:, :] as a tensor [B, Md + r, D] of their own, where the encoder stored them there
+        (GradLanding.split_out) - `enc` itself is then a stride-0 token, and readers take `tail` through compact_tab."""
         self.tab, self.maps, self.M, self.G, self.Md, self.r, self.landing = tab, maps, M, G, Md, r, landing
-        self.smap = smap
-        self._compact = {}
+        self.smap, self.tail = smap, tail
+        self._compact = {} if tab_c is None else {tab_c[0]: tab_c[1]}
 
     def compact_tab(self, ne: int):
         """The table relative to the COMPACT rows enc[:, G:, :] copied to [B, Md + r, D] (a GAT layer transforms those
@@ -234,7 +254,12 @@ class GCNStackFn(torch.autograd.Function):
         src/models.py:870-872); the slice is part of this Function so that its backward receives the gradient of
         the slice and widens it with ONE pass of gcl_pad_rows (no zero-fill + copy by autograd)."""
         squeeze = x.dim() == 2
-        x3 = _flat3(x.detach())
+        ctx.enc_shape = None
+        if lat is not None and lat.tail is not None:
+            # x is the token of an encoder output stored in two parts: the mesh rows are in lat.tail [B, Md + r, D]
+            ctx.enc_shape, x3 = tuple(x.shape), lat.tail
+        else:
+            x3 = _flat3(x.detach())
         B, n, _ = x3.shape
         if lat is not None:
             n = lat.M  # x is the encoder output [B, ne, D]; the stack runs on the M mesh rows it is read into
@@ -249,6 +274,11 @@ class GCNStackFn(torch.autograd.Function):
                 and params[2 * (L - 1)].shape[0] % 4 == 0 and _split_grad()):
             split.expect_split_reader()
             ctx.split = split
+        # the same conditions let the last conv STORE its output in two parts (GradLanding.split_out)
+        out_head = None
+        if (split is not None and not has_ln and not out_rows and not squeeze and lat is None
+                and params[2 * (L - 1)].shape[0] % 4 == 0):
+            out_head = split.split_out(B, n, params[2 * (L - 1)].shape[0])
         slope_p = params[2 * L]
         # activation between the convs: learnable PReLU slope (params[2L]), SiLU, or ReLU as a PReLU
         # with the owner's constant zero slope (src/models.py:154-163, :316)
@@ -277,11 +307,20 @@ class GCNStackFn(torch.autograd.Function):
             ldh = (Fout + 3) // 4 * 4  # padded scratch so the gather can use 16-B loads
             act_k, slope_k = (akind, slope_t) if k > 0 else (hip.ACT_NONE, None)
             if k == 0 and lat is not None:
-                p = hip.gcn_layer_fwd_tab(graph, x3, lat.tab, act_k, slope_k, W, b)
+                tab = lat.tab if ctx.enc_shape is None else lat.compact_tab(ctx.enc_shape[1])
+                p = hip.gcn_layer_fwd_tab(graph, x3, tab, act_k, slope_k, W, b)
                 if ldh != Fout:
                     p = p.contiguous()
                 ps.append(p)
                 cur = p
+                continue
+            if k == L - 1 and out_head is not None and hip.gcn_layer_split_ok(graph, cur, Fout, out_head):
+                # the encoder output: grid rows straight into the decoder's input, mesh rows compact; nobody reads it whole
+                tail = torch.empty(B, n - out_head.shape[1], Fout, dtype=torch.float32, device=cur.device)
+                hip.gcn_layer_fwd_split(graph, cur, act_k, slope_k, W, b, out_head, tail)
+                split.keep_split_out(tail)
+                ps.append(None)  # (the backward of a stack without LayerNorm never reads its last output)
+                cur = _token(cur, (B, n, Fout))
                 continue
             if hip.gcn_layer_fusable(graph, cur, W.shape[1], Fout):
                 # ONE kernel (csrc/gcn_layer.hip): gather-aggregate the activated input rows, then the dense
@@ -410,8 +449,12 @@ class GCNStackFn(torch.autograd.Function):
                 dp = hip.linear_bwd_all(dh2, W, inp, slope_t, dsl, dW, None, G.dst[2 * k - 1], G.acc[wi],
                                         acc_colsum=G.acc[2 * k - 1], act=akind).view(B, n, -1)
             elif ctx.lat is not None:
-                dx = _lat_first_layer_bwd(ctx.lat, ctx.x3, dh2.reshape(B, n, -1), W, dW, G.acc[wi], ctx.needs_input_grad[0],
-                                          dzc=dzc)
+                if ctx.enc_shape is not None:  # the forward read the compact rows themselves (LatSource.tail)
+                    dx = _lat_first_layer_bwd(ctx.lat, None, dh2.reshape(B, n, -1), W, dW, G.acc[wi], ctx.needs_input_grad[0],
+                                              Pc=ctx.x3, enc_shape=ctx.enc_shape, dzc=dzc)
+                else:
+                    dx = _lat_first_layer_bwd(ctx.lat, ctx.x3, dh2.reshape(B, n, -1), W, dW, G.acc[wi],
+                                              ctx.needs_input_grad[0], dzc=dzc)
             elif ctx.needs_input_grad[0]:
                 dx = hip.linear_bwd_all(dh2, W, inp, None, None, dW, None, None, G.acc[wi],
                                         act=hip.ACT_NONE).view(B, n, -1)
@@ -433,7 +476,8 @@ class GATLayerFn(torch.autograd.Function):
     def forward(ctx, x, owner, graph, H: int, want_alpha: bool, act, lat, slope, W, att_src, att_dst, bias):
         """act: kind of the activation applied to x on load (None: PReLU when a slope is given); lat: LatSource or None."""
         squeeze = x.dim() == 2
-        x3 = _flat3(x.detach())
+        tail = lat.tail if lat is not None else None
+        x3 = x.detach() if tail is not None else _flat3(x.detach())  # (with a tail x is a token: only its shape is used)
         B, n, _ = x3.shape
         Cc = W.shape[0] // H
         sl = slope.detach() if slope is not None else None
@@ -442,11 +486,13 @@ class GATLayerFn(torch.autograd.Function):
             # x is the encoder output [B, ne, D] (LatSource): only its compact mesh rows are transformed, the attention
             # kernels read the transformed rows through the table - no [B, M, D] latents, no [B, M, H*C] transform
             assert sl is None, "a LatSource feeds the first layer of a stack (no input activation)"
-            if not x3.is_contiguous():
+            if tail is None and not x3.is_contiguous():
                 x3 = x3.contiguous()
             ne, D = x3.shape[1], x3.shape[2]
             nc = lat.Md + lat.r
-            Pc = hip.copy_rows(x3[:, lat.G:, :], torch.empty(B, nc, D, dtype=torch.float32, device=x3.device))
+            # the compact rows: where the encoder stored them, else copied out of its one output tensor
+            Pc = tail if tail is not None else \
+                hip.copy_rows(x3[:, lat.G:, :], torch.empty(B, nc, D, dtype=torch.float32, device=x3.device))
             h = hip.linear_fwd(Pc.view(B * nc, D), W.detach(), None, None, act=act).view(B, nc, H * Cc)
             ctx.lat, ctx.tab, ctx.enc_shape = lat, lat.compact_tab(ne), x3.shape
             x3 = Pc
@@ -662,13 +708,14 @@ class Gather2Fn(torch.autograd.Function):
     def forward(ctx, a, b, maps, nd: int, B: int, landing=None):
         map_a, map_b, inv_a, inv_b = maps
         a3 = a.detach()
-        if not a3.is_contiguous():
-            a3 = a3.contiguous()
         ctx.maps, ctx.B, ctx.landing = maps, B, landing
         ctx.sa, ctx.sb = a3.shape, (b.shape if b is not None else None)
+        # (asked before a3 is made contiguous: with its head rows already in the buffer, a is a stride-0 token)
         buf = landing.take_decoder_input(a3) if landing is not None else None
         if buf is not None:  # the rows of source b are already in place (b itself is a stride-0 token)
             return buf
+        if not a3.is_contiguous():
+            a3 = a3.contiguous()
         b3 = b.detach() if b is not None else None
         if b3 is not None and not b3.is_contiguous():
             b3 = b3.contiguous()
@@ -735,13 +782,27 @@ class GradLanding:
                  -1) and, optionally, the mesh rows with a reader as a list (lets the producer skip the others)
       LayerNorm  ln_plan() - does the output go through the map, and are the unread rows skipped? - then ln_write()
       Gather2Fn  take_decoder_input(): the filled buffer with the head rows copied in; a buffer nobody filled is dropped
-                 (None: the caller gathers both sources)."""
+                 (None: the caller gathers both sources).
+
+    Encoder output (forward).  Inside forward() the encoder output has two readers: the decoder-input gather takes its
+    first `head` rows in order (`head_identity`), the mesh side (a LatSource) the rest.  Where the producer is a GCN stack
+    whose last conv can store to two destinations (gcl_gcn_layer_fwd_split), each part is written where its reader takes it
+    from and the [B, ne, D] tensor never exists:
+      model          open_decoder_input() BEFORE the encoder runs, then want_split_out() - once it knows that the mesh side
+                     will be a LatSource and that the processor's LayerNorm will fill the decoder's input
+      encoder stack  split_out(): the head rows of the decoder's input, or None; after a launch that stored there and
+                     in a fresh compact [B, ne - head, D] tensor, keep_split_out(tail).  Its output is then a stride-0
+                     token
+      model          split_tail(): the compact rows for the LatSource (None: the stack wrote one tensor, today's path)
+      Gather2Fn      take_decoder_input() skips its copy (a buffer whose other rows nobody filled is an error: the
+                     model asks for the split only when the LayerNorm will fill them)."""
 
     def __init__(self, head: int, head_identity: bool = False):
         self.head, self.buf, self.mesh_pending = head, None, False
         self.head_identity, self.split_ready, self.part_head, self.part_tail = head_identity, False, None, None
         self.proc_ready, self.proc_src, self.proc_map = False, None, None
         self.dec_buf, self.dec_map, self.dec_rows, self.dec_filled = None, None, None, False
+        self.out_wanted, self.out_tail, self.dec_head_placed = False, None, False
 
     # encoder-output gradient (the static methods take the landing as it reaches their caller: it may be None)
     @staticmethod
@@ -846,12 +907,36 @@ class GradLanding:
         return stats
 
     def take_decoder_input(self, a3):
-        buf, filled = self.dec_buf, self.dec_filled
-        self.dec_buf, self.dec_filled = None, False
+        buf, filled, placed = self.dec_buf, self.dec_filled, self.dec_head_placed
+        self.dec_buf, self.dec_filled, self.dec_head_placed = None, False, False
+        if placed:  # the encoder's last conv stored the head rows here (a3 is a token)
+            if not filled:  # (the model asks for the split only when the LayerNorm will fill the rest)
+                raise RuntimeError("the encoder output was stored in two parts, but nothing filled the decoder's mesh rows")
+            return buf
         if not filled:
             return None
         hip.copy_rows(a3[:, : self.head, :], buf[:, : self.head, :])
         return buf
+
+    # encoder output
+    def want_split_out(self):
+        self.out_wanted = True
+
+    def split_out(self, B: int, n: int, F: int):
+        """For the stack whose output [B, n, F] is the encoder output: the head rows of the decoder's input to store its
+        first `head` rows into (the others go to a compact tensor the stack makes once the kernel has said yes), or None."""
+        buf = self.dec_buf
+        if not (self.out_wanted and self.head_identity and buf is not None and buf.shape[0] == B and buf.shape[2] == F
+                and buf.shape[1] >= self.head and 0 < self.head < n and _split_out()):
+            return None
+        return buf[:, : self.head]
+
+    def keep_split_out(self, tail):
+        self.out_tail, self.dec_head_placed = tail, True
+
+    def split_tail(self):
+        tail, self.out_tail = self.out_tail, None
+        return tail
 
 
 class MeshLatFn(torch.autograd.Function):

@@ -56,6 +56,7 @@ _SIGNATURES = {
     "gcl_aggregate_present": (C.c_int, [_vp, _i32, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _vp]),
     "gcl_aggregate_compact_ok": (C.c_int, [_vp, _i32, _i64, _i64, _i64, _i64, _i32, _i32]),
     "gcl_aggregate_compact": (C.c_int, [_vp, _i32, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _i64, _i64, _i32, _i32, _vp]),
+    "gcl_aggregate_heavy_launches": (_i64, []),
     "gcl_aggregate_split": (C.c_int, [_vp, _i32, _vp, _i64, _i64, _vp, _i64, _i64, _i32, _vp, _vp, _i64, _i64, _i32, _i32,
                                       _vp]),
     "gcl_gat_fwd": (C.c_int, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _vp]),
@@ -106,6 +107,9 @@ _SIGNATURES = {
                                    C.c_size_t, _vp]),
     "gcl_gcn_layer_fwd": (C.c_int, [_vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp]),
     "gcl_gcn_layer_fwd_rows": (C.c_int, [_vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "gcl_gcn_layer_fwd_split": (C.c_int, [_vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _i64, _i32, _i32, _i32,
+                                          _i32, _i32, _vp]),
+    "gcl_gcn_layer_fwd_split_ok": (C.c_int, [_vp, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32]),
     "gcl_gcn_layer_fwd_present": (C.c_int, [_vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _i32, _i32, _i32, _i32,
                                             _vp]),
     "gcl_layernorm_fwd_map": (C.c_int, [_vp, _i64, _vp, _vp, _f32, _vp, _i64, _i64, _vp, _i32, _vp, _i64, _i32, _vp]),
@@ -569,6 +573,14 @@ def linear_bwd_all(dy, W, x, in_slope, d_in_slope, dW, db, colsum_dx, acc_dW: bo
     return dx
 
 
+AGG_HEAVY_INSIDE = 2  # gcl.h GCL_AGG_HEAVY_INSIDE
+
+
+def _agg_flags(transpose) -> int:
+    """The flag word of the aggregation entries: direction, and heavy rows inside the main launch (gcl.h)."""
+    return (1 if transpose else 0) | AGG_HEAVY_INSIDE
+
+
 def aggregate(graph: Graph, h3, bias, transpose=False, out=None):
     """h3: [B, n, F] with unit channel stride; returns [B, n, F]."""
     B, n, F = h3.shape
@@ -577,7 +589,7 @@ def aggregate(graph: Graph, h3, bias, transpose=False, out=None):
     if out is None:
         out = torch.empty(B, n, F, dtype=torch.float32, device=h3.device)
     tok = _probe_begin("aggregate", graph=graph, transpose=bool(transpose), B=B, F=F)
-    _check(lib().gcl_aggregate(graph.handle, 1 if transpose else 0, _p(h3), h3.stride(1), h3.stride(0), _p(bias),
+    _check(lib().gcl_aggregate(graph.handle, _agg_flags(transpose), _p(h3), h3.stride(1), h3.stride(0), _p(bias),
                                _p(out), out.stride(1), out.stride(0), B, F, _stream()))
     _probe_end(tok)
     return out
@@ -592,7 +604,7 @@ def aggregate_present(graph: Graph, h3, present, bias=None, transpose=False, out
     if out is None:
         out = torch.empty(B, n, F, dtype=torch.float32, device=h3.device)
     tok = _probe_begin("aggregate_present", graph=graph, transpose=bool(transpose), B=B, F=F)
-    _check(lib().gcl_aggregate_present(graph.handle, 1 if transpose else 0, _p(h3), h3.stride(1), h3.stride(0),
+    _check(lib().gcl_aggregate_present(graph.handle, _agg_flags(transpose), _p(h3), h3.stride(1), h3.stride(0),
                                        _pi(present), _p(bias), _p(out), out.stride(1), out.stride(0), B, F, _stream()))
     _probe_end(tok)
     return out
@@ -620,6 +632,11 @@ def aggregate_compact(graph: Graph, h3, smap, outc, transpose=False, out=None):
     return out
 
 
+def aggregate_heavy_launches() -> int:
+    """Launches of the one-block-per-heavy-row kernel as a launch of its own, so far in this process (see gcl.h)."""
+    return int(lib().gcl_aggregate_heavy_launches())
+
+
 def aggregate_split(graph: Graph, a3, b3, transpose=False, out=None):
     """hip.aggregate over the rows of TWO tensors: a3 [B, head, F] are rows < head of every sample, b3 [B, n - head, F] the
     rest (any row / batch strides that keep rows whole 16-byte units).  Reported to the launch probe under a kind of its
@@ -631,7 +648,7 @@ def aggregate_split(graph: Graph, a3, b3, transpose=False, out=None):
     if out is None:
         out = torch.empty(B, n, F, dtype=torch.float32, device=a3.device)
     tok = _probe_begin("aggregate_split", graph=graph, transpose=bool(transpose), B=B, F=F)
-    _check(lib().gcl_aggregate_split(graph.handle, 1 if transpose else 0, _p(a3), a3.stride(1), a3.stride(0), _p(b3),
+    _check(lib().gcl_aggregate_split(graph.handle, _agg_flags(transpose), _p(a3), a3.stride(1), a3.stride(0), _p(b3),
                                      b3.stride(1), b3.stride(0), head, None, _p(out), out.stride(1), out.stride(0), B, F,
                                      _stream()))
     _probe_end(tok)
@@ -1139,6 +1156,37 @@ def gcn_layer_fwd(graph: Graph, x3, act, slope, W, bias, out=None, rows_out=None
                                         Fst, int(rows_out) if rows_out else n, _stream()))
     _probe_end(tok)
     return out[..., :Fout]
+
+
+def gcn_layer_split_ok(graph: Graph, x3, Fout: int, ya, yb=None) -> bool:
+    """True when gcn_layer_fwd_split would store the layer's rows < ya.shape[1] in ya and the others in yb (None: a
+    contiguous [B, n - head, roundup(Fout, 4)] tensor that the caller has yet to make)."""
+    B, n, Fin = x3.shape
+    head, Fst = ya.shape[1], (int(Fout) + 3) // 4 * 4
+    if not (gcn_layer_fusable(graph, x3, Fin, Fout) and n == graph.n and ya.stride(2) == 1 and ya.data_ptr() % 16 == 0):
+        return False
+    if yb is not None and not (yb.stride(2) == 1 and yb.data_ptr() % 16 == 0 and head + yb.shape[1] == n):
+        return False
+    ldb, bsb = (yb.stride(1), yb.stride(0)) if yb is not None else (Fst, (n - head) * Fst)
+    return bool(lib().gcl_gcn_layer_fwd_split_ok(graph.handle, x3.stride(1), x3.stride(0), ya.stride(1), ya.stride(0), ldb, bsb,
+                                                 head, B, Fin, int(Fout), Fst))
+
+
+def gcn_layer_fwd_split(graph: Graph, x3, act, slope, W, bias, ya, yb):
+    """gcn_layer_fwd with a two-part destination (gcl_gcn_layer_fwd_split): rows < head = ya.shape[1] of every sample go to
+    ya [B, head, >= Fout], the others to yb [B, n - head, >= Fout]; both may be row ranges of larger buffers.  Reported to the
+    launch probe under a kind of its own."""
+    B, n, Fin = x3.shape
+    head = ya.shape[1]
+    assert n == graph.n and head + yb.shape[1] == n and ya.shape[0] == B and yb.shape[0] == B
+    assert ya.stride(2) == 1 and yb.stride(2) == 1
+    Fout = W.shape[0]
+    Fst = (Fout + 3) // 4 * 4
+    tok = _probe_begin("gcn_layer_fwd_split", graph=graph, B=B, Fin=Fin, Fout=Fout)
+    _check(lib().gcl_gcn_layer_fwd_split(graph.handle, _p(x3), x3.stride(1), x3.stride(0), int(act), _p(slope), _p(W.contiguous()),
+                                         _p(bias), _p(ya), ya.stride(1), ya.stride(0), _p(yb), yb.stride(1), yb.stride(0), head, B,
+                                         Fin, Fout, Fst, _stream()))
+    _probe_end(tok)
 
 
 def gcn_layer_tab_ok(graph: Graph, x3, Fout: int) -> bool:

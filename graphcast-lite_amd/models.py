@@ -755,6 +755,8 @@ class WeatherPrediction(nn.Module):
         # the same two maps as ONE row table for consumers that read the mesh latents through it (gcl_gcn_layer_fwd_tab):
         # entry >= 0: row of the sample's own encoder output, entry < 0: ~(flat row of the batch-invariant list)
         f.tab = torch.where(f.maps[0] >= 0, f.maps[0], -f.maps[1] - 1).to(torch.int32).contiguous()
+        # ... and relative to the compact rows enc[:, G:, :] as a tensor of their own (functional.LatSource.compact_tab)
+        f.tab_c = (ne, LatSource(f.tab, f.maps, M, G, Md, r).compact_tab(ne))
         # The encoder's MLP is row-wise and EVERY mesh row enters it as [0 | static] (src/models.py:792-801): the Md
         # batch-dependent mesh rows differ between samples only after the encoder's first GCNConv.  So the MLP runs on
         # [G grid | r folded invariant | rd = ceil(Md / B) folded dependent] rows per sample (2209 instead of 4118 at
@@ -792,7 +794,9 @@ class WeatherPrediction(nn.Module):
     def _forward_compact(self, X: torch.Tensor, attention_threshold=0.0, _landing=False, _latents_discarded=False, **kwargs):
         """_landing: the caller keeps only the prediction, or takes the processor's rows in tile order: the encoder
         output's two gradient consumers may share one buffer (functional.GradLanding).  _latents_discarded: nobody sees the
-        processor's output at all (forward()), so its final LayerNorm may write only the rows the decoder reads."""
+        processor's output at all (forward()), so its final LayerNorm may write only the rows the decoder reads - nor the
+        encoder output, whose last conv may then store its two readers' rows apart (the grid latents returned are then a
+        stride-0 token, like the processor's rows)."""
         G, M = self._num_grid_nodes, self._num_mesh_nodes
         squeeze = X.dim() == 2 or (X.dim() == 3 and X.shape[0] == 1)
         X3 = X if X.dim() == 3 else X.unsqueeze(0)
@@ -808,7 +812,22 @@ class WeatherPrediction(nn.Module):
             # made before the encoder runs: its GCN stack, when it can read a gradient in two parts, announces that to the
             # landing it is given (functional.GCNStackFn `split`).  head_identity: checked on the map in _fold_setup
             land = GradLanding(G, head_identity=f.dec_head_identity) if _landing and self._grad_landing else None
+            lat_pre = None
             ekw = {"_split": land} if (land is not None and self.encoder.graph_layer.layer_type == GraphLayerType.ConvGCN) else {}
+            D_enc = self._encoder_width() if ekw else None
+            if D_enc is not None and self._decoder_input_channel(land, _latents_discarded, squeeze):
+                # In forward() the encoder output has two readers, the decoder-input gather (grid rows) and the mesh side.
+                # The decoder's input is opened before the encoder runs, so that its last conv can store the grid rows there
+                # and the mesh rows compact (functional.GradLanding, "Encoder output"): asked for when the mesh side will
+                # read through a LatSource and the processor's final LayerNorm will fill the rest of the decoder's input.
+                land.open_decoder_input(B, G + c.U, D_enc, X3.device, f.maps_dec[3], f.maps_dec[1][G:])
+                ln = self.processor.graph_layer._final_ln()
+                if ln is not None and ln.mode == "node" and ln.in_channels == D_enc:
+                    # the LatSource of the split path is made HERE, once, from the tail's shape (contiguous [B, Md + r, D]: a
+                    # meta tensor stands for it); the tail itself is attached when the encoder has stored it
+                    lat_pre = self._lat_source(c, f, torch.empty(B, c.Md + f.r, D_enc, device="meta"), land)
+                    if lat_pre is not None:
+                        land.want_split_out()
             if self._mlp_on_folded_rows and self.encoder.mlp is not None and f.rd > 0:
                 x_m = AssembleFn.apply(X3, self.init_grid_features, f.mstat2, f.x_tail2)   # [B, G+r+rd, C]
                 h_m = self.encoder.mlp(X=x_m)                                              # [B, G+r+rd, D']
@@ -817,7 +836,11 @@ class WeatherPrediction(nn.Module):
             else:
                 x_c = AssembleFn.apply(X3, self.init_grid_features, f.mstat, f.x_fold if f.r > 0 else None)  # [B, G+Md+r, C]
                 enc_c = self.encoder.forward(X=x_c, edge_index=c.enc_graph, **ekw)  # [B, G+Md+r, D]
-            lat_src = self._lat_source(c, f, enc_c, land)
+            tail = land.split_tail() if land is not None else None  # the stack took the offer: enc_c is a stride-0 token
+            if tail is not None:
+                lat_src, lat_pre.tail = lat_pre, tail
+            else:
+                lat_src = self._lat_source(c, f, enc_c, land)
             if lat_src is None:
                 mesh_lat = MeshLatFn.apply(enc_c, f.maps, M, G + c.Md, f.r, land)   # [B, M, D]
             maps_dec = f.maps_dec
@@ -829,9 +852,7 @@ class WeatherPrediction(nn.Module):
             enc_c = self.encoder.forward(X=x_c, edge_index=c.enc_graph)                 # [B, G+Md, D]
             inv = self.encoder.forward(X=c.x_inv, edge_index=c.empty_graph) if c.Mi > 0 else None  # [1, Mi, D]
             mesh_lat = Gather2Fn.apply(enc_c, inv, c.maps_mesh, M, B)                   # [B, M, D]
-        gl_type = self.processor.graph_layer.layer_type
-        if (land is not None and self._ln_into_decoder_input and _latents_discarded and not squeeze
-                and gl_type in (GraphLayerType.ConvGCN, GraphLayerType.GATConv, GraphLayerType.SparseGATConv)):
+        if land is not None and land.dec_buf is None and self._decoder_input_channel(land, _latents_discarded, squeeze):
             # the processor's output is only consumed by the decoder-input gather: its final LayerNorm writes the rows the
             # decoder reads straight into the decoder's input.  maps_dec[1][G:]: the U mesh rows the decoder reads (a view
             # of the set-up's device table), for a producer that can skip the others
@@ -870,9 +891,24 @@ class WeatherPrediction(nn.Module):
     _mlp_on_folded_rows = os.environ.get("GCL_NO_MLP_FOLD", "0") in ("0", "")
     _ln_into_decoder_input = os.environ.get("GCL_NO_LN_MAP", "0") in ("0", "")
 
+    def _decoder_input_channel(self, land, latents_discarded: bool, squeeze: bool) -> bool:
+        """Does this call open the decoder-input channel of its landing (functional.GradLanding, "Decoder input")?"""
+        return (land is not None and self._ln_into_decoder_input and latents_discarded and not squeeze
+                and self.processor.graph_layer.layer_type in (GraphLayerType.ConvGCN, GraphLayerType.GATConv,
+                                                              GraphLayerType.SparseGATConv))
+
+    def _encoder_width(self):
+        """Output width of the encoder's GCN stack as its configuration gives it (None: not a plain GCNConv stack)."""
+        gl = self.encoder.graph_layer
+        convs = [m for m in gl.layers if isinstance(m, GCNConv)]
+        if gl.layer_type != GraphLayerType.ConvGCN or not convs or gl._final_ln() is not None:
+            return None
+        return int(convs[-1].lin.weight.shape[0])
+
     def _lat_source(self, c, f, enc_c, land):
         """functional.LatSource when the processor's first layer can read the mesh latents through the row table
-        (a GCNConv stack on a source-tile mesh graph, gcl_gcn_layer_fwd_tab), else None."""
+        (a GCNConv stack on a source-tile mesh graph, gcl_gcn_layer_fwd_tab), else None.  enc_c: the tensor the rows will be
+        read from - the encoder output, or a stand-in for its compact mesh rows (only shape and strides are looked at)."""
         if not self._lat_through_table or c.perm is None or self.processor.mlp is not None:
             return None
         gl = self.processor.graph_layer
@@ -883,7 +919,8 @@ class WeatherPrediction(nn.Module):
             g = _graphs.get(self._processing_graph_tiled(), self._num_mesh_nodes, hip.GRAPH_GAT)
             if not hip.gat_tab_ok(g, 1, first.lin.weight.shape[0]):
                 return None
-            return LatSource(f.tab, f.maps, self._num_mesh_nodes, self._num_grid_nodes, c.Md, f.r, land, smap=f.smap)
+            return LatSource(f.tab, f.maps, self._num_mesh_nodes, self._num_grid_nodes, c.Md, f.r, land, smap=f.smap,
+                             tab_c=f.tab_c)
         if gl.layer_type != GraphLayerType.ConvGCN:
             return None
         convs = [m for m in gl.layers if isinstance(m, GCNConv)]
@@ -892,7 +929,8 @@ class WeatherPrediction(nn.Module):
         g = _graphs.get(self._processing_graph_tiled(), self._num_mesh_nodes, hip.GRAPH_GCN)
         if not hip.gcn_layer_tab_ok(g, enc_c, convs[0].lin.weight.shape[0]):
             return None
-        return LatSource(f.tab, f.maps, self._num_mesh_nodes, self._num_grid_nodes, c.Md, f.r, land, smap=f.smap)
+        return LatSource(f.tab, f.maps, self._num_mesh_nodes, self._num_grid_nodes, c.Md, f.r, land, smap=f.smap,
+                         tab_c=f.tab_c)
 
     def forward_with_latents(self, X: torch.Tensor, attention_threshold=0.0, _landing=False, _latents_discarded=False,
                              **kwargs):

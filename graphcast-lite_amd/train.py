@@ -596,7 +596,7 @@ class TrainStep(Captured):
         if defer:
             hip.defer_begin()
         try:
-            loss.backward()
+            loss.backward(self._loss_root(loss))
         except BaseException:
             if defer:
                 hip.defer_flush(drop=True)  # a failed backward: forget what it queued, launch nothing
@@ -604,6 +604,18 @@ class TrainStep(Captured):
         if defer:
             hip.defer_flush()
         return loss.detach()
+
+    def _loss_root(self, loss):
+        """The gradient of the loss with respect to itself: a one that is made once (in an eager step, never inside a
+        capture) and only ever read, instead of the fill launch autograd would issue in every step.  None: autograd's own."""
+        one = getattr(self, "_one", None)
+        if one is not None and one.device == loss.device and one.dtype == loss.dtype and loss.dim() == 0:
+            return one
+        if loss.dim() != 0 or not loss.is_cuda or torch.cuda.is_current_stream_capturing():
+            return None
+        with torch.inference_mode(False):
+            self._one = torch.ones((), dtype=loss.dtype, device=loss.device)
+        return self._one
 
     def _finish(self):
         scale = allreduce_gradients(self.flat, self.world)

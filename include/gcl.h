@@ -237,6 +237,14 @@ int gcl_dense_bwd_dw(const float* dy, int64_t lddy, const float* x, int64_t ldx,
 int gcl_aggregate(const gcl_graph_t* g, int32_t transpose, const float* h, int64_t ldh, int64_t bsh,
                   const float* bias, float* y, int64_t ldy, int64_t bsy, int32_t B, int32_t F,
                   gcl_stream_t stream);
+/* Rows with more than 64 edges (in the direction of the call) are summed by one block each, in a launch of their own
+ * behind the main one.  `transpose` of gcl_aggregate, gcl_aggregate_present and gcl_aggregate_split is a flag word: bit 0
+ * the direction, GCL_AGG_HEAVY_INSIDE asks for those blocks as the FIRST blocks of the main launch instead, where the
+ * per-edge kernel runs it with 16-byte rows (elsewhere, and with GCL_AGG_HEAVY_SEPARATE=1, read per call, the flag is
+ * ignored) - the same bits either way.  gcl_aggregate_heavy_launches: how many separate launches this process has made
+ * (a counter for tests). */
+#define GCL_AGG_HEAVY_INSIDE 2
+int64_t gcl_aggregate_heavy_launches(void);
 /* The same with ABSENT source rows: present [n] has one entry per node, >= 0 = the row of h exists, < 0 = it counts as a
  * row of zeros and is never read, whatever the memory behind it holds (a stage boundary that drops rows: the producer of
  * h need not store them).  Bit-equal to gcl_aggregate on a copy of h whose absent rows are zero. */
@@ -462,6 +470,21 @@ int gcl_gcn_layer_fwd_rows(const gcl_graph_t* g, const float* x, int64_t ldx, in
                            const float* slope, const float* W /*[Fout,Fin]*/, const float* bias, float* y,
                            int64_t ldy, int64_t bsy, int32_t B, int32_t Fin, int32_t Fout, int32_t Fout_store,
                            int32_t rows_out, gcl_stream_t stream);
+/* The layer with a TWO-PART destination: rows i < head of sample b go to ya + b * bsa + i * lda, the others to
+ * yb + b * bsb + (i - head) * ldb (two readers that each want their rows in a tensor of their own - the encoder output's
+ * grid rows in the decoder's input, its mesh rows compact - get them without a copy).  The per-edge kernel stores one
+ * 32-row tile per wave, so with head % 32 == 0 only a tile's store base differs: every row gets the bits
+ * gcl_gcn_layer_fwd gives it.  gcl_gcn_layer_fwd_split_ok returns 1 when the call would run; it returns 0, and the call
+ * GCL_EINVAL without writing anything, when head % 32 != 0, head <= 0 or head >= n, when a stride is no multiple of 4
+ * floats, when a part exceeds 32-bit byte offsets, when Fin % 16 != 0 (the fp32-operand instantiations have no two-part
+ * form), or when the source-tile form or the two-kernel fallback would take the layer (the caller then writes one
+ * tensor and copies). */
+int gcl_gcn_layer_fwd_split(const gcl_graph_t* g, const float* x, int64_t ldx, int64_t bsx, int32_t act,
+                            const float* slope, const float* W /*[Fout,Fin]*/, const float* bias, float* ya, int64_t lda,
+                            int64_t bsa, float* yb, int64_t ldb, int64_t bsb, int32_t head, int32_t B, int32_t Fin,
+                            int32_t Fout, int32_t Fout_store, gcl_stream_t stream);
+int gcl_gcn_layer_fwd_split_ok(const gcl_graph_t* g, int64_t ldx, int64_t bsx, int64_t lda, int64_t bsa, int64_t ldb,
+                               int64_t bsb, int32_t head, int32_t B, int32_t Fin, int32_t Fout, int32_t Fout_store);
 /* The layer with an OUTPUT-ROW predicate: rows i with present[i] < 0 may be left unwritten (a stage boundary behind the
  * layer drops them); rows with present[i] >= 0 get the bits gcl_gcn_layer_fwd gives them.  The source-tile form of the
  * layer folds the table into its stores; every other form stores all rows, which honours the same contract. */
