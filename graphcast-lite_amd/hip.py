@@ -1228,6 +1228,8 @@ def nudge(f3, o3, out3, c0: float, c1: float, form: int, chan_mask=None):
     assert f3.stride(2) == 1 and o3.stride(2) == 1 and out3.stride(2) == 1
     if chan_mask is not None:
         assert chan_mask.is_cuda and chan_mask.dtype == torch.uint8 and chan_mask.numel() == Cc
+    if f3.numel() == 0:  # no element to nudge (an empty view has a null data_ptr(), which the C entry point refuses)
+        return out3
     _check(lib().gcl_nudge(_p(f3), f3.stride(1), f3.stride(0), _p(o3), o3.stride(1), o3.stride(0),
                            chan_mask.data_ptr() if chan_mask is not None else None, float(c0), float(c1), int(form),
                            _p(out3), out3.stride(1), out3.stride(0), B, G, Cc, _stream()))
@@ -1246,6 +1248,8 @@ def nudge_rows(f3, o3, out3, station_mask, net_of_row, alpha, chan_mask=None):
     assert net_of_row.dtype == torch.int32 and net_of_row.numel() == B and alpha.numel() == B
     if chan_mask is not None:
         assert chan_mask.is_cuda and chan_mask.dtype == torch.uint8 and chan_mask.numel() == Cc
+    if f3.numel() == 0:  # as in `nudge`
+        return out3
     _check(lib().gcl_nudge_rows(_p(f3), f3.stride(1), f3.stride(0), _p(o3), o3.stride(1),
                                 o3.stride(0) if o3.shape[0] == B and B > 1 else 0, station_mask.data_ptr(),
                                 station_mask.shape[0], _pi(net_of_row), _p(alpha),
@@ -1373,6 +1377,9 @@ def regrid_blend(src3, nlat: int, cell, w, K: int, g3=None, mask=None, r3=None, 
         assert t is None or (t.shape[0] == B and t.shape[1] == nt and t.shape[2] >= K and t.stride(2) == 1)
     if out3 is not None:
         assert mask is not None and r3 is not None and mask.numel() == nt and mask.is_contiguous()
+    assert g3 is not None or out3 is not None
+    if nt == 0:  # no target row: the empty views have null data_ptr()s, which the C entry point takes for absent
+        return
 
     def lb(t):
         return (t.stride(1), t.stride(0)) if t is not None else (0, 0)
@@ -1386,6 +1393,8 @@ def taper_blend(mask, r3, g3, out3):
     B, nt, K = out3.shape
     assert r3.shape == out3.shape and g3.shape == out3.shape and mask.numel() == nt and mask.is_contiguous()
     assert r3.stride(2) == 1 and g3.stride(2) == 1 and out3.stride(2) == 1
+    if out3.numel() == 0:  # as in `regrid_blend`
+        return out3
     _check(lib().gcl_taper_blend(_p(mask), _p(r3), r3.stride(1), r3.stride(0), _p(g3), g3.stride(1), g3.stride(0),
                                  _p(out3), out3.stride(1), out3.stride(0), nt, K, B, _stream()))
     return out3

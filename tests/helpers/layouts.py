@@ -1,4 +1,5 @@
-"""Row layouts for the kernel contract tests (test_norm_glue, test_dense_layouts, test_sparse_layouts): operands as
+"""Row layouts for the kernel contract tests (test_norm_glue, test_dense_layouts, test_sparse_layouts, test_assim_kernels,
+test_scoring_kernels, test_map_kernels): operands as
 views inside buffers the test owns, whose other elements hold a known value - NaN around an input (a kernel that
 reads its padding poisons the result), a sentinel around an output (a kernel that writes outside its view changes
 it) - plus the element-wise bound check and the launched-kernel queries the tests share."""
@@ -36,7 +37,9 @@ def within(got, ref, tol, what):
 
 def same_bits(a, b):
     """Bit-equal, NaN payloads included (torch.equal calls NaN != NaN)."""
-    return a.shape == b.shape and bool((a.contiguous().view(torch.int32) == b.contiguous().view(torch.int32)).all())
+    bits = {1: torch.uint8, 4: torch.int32, 8: torch.int64}
+    ia, ib = a.contiguous().view(bits[a.element_size()]), b.contiguous().view(bits[b.element_size()])
+    return a.shape == b.shape and ia.dtype == ib.dtype and bool((ia == ib).all())
 
 
 COLBLOCK_LEAD = 8  # the column block starts at column 4 * 2 of its wider row
@@ -83,15 +86,16 @@ class Rows:
       offset    16-byte row stride, base one float past a 16-byte boundary (the scalar path), padding NaN
       mixed     inputs as pad_nan, outputs as offset (vector loads, scalar stores)
     `ld` overrides the row stride of the padded layouts.  With B the samples are bs = rows * ld + gap apart, gap > 0
-    (8 where rows are 16-byte ones, else 5), and the gap holds `fill`."""
+    (8 where rows are 16-byte ones, else 5), and the gap holds `fill`.  `dtype` (float32 unless given) is the element
+    type of the buffer; strides and offsets stay in elements."""
 
-    def __init__(self, rows, F, layout, fill, role="in", ld=None, B=None):
+    def __init__(self, rows, F, layout, fill, role="in", ld=None, B=None, dtype=torch.float32):
         ld, off, lead = geometry(F, layout, role, ld)
         self.ld = ld
         nb = 1 if B is None else B
         self.bs = rows * ld + (0 if B is None else 8 if ld % 4 == 0 else 5)
-        self.buf = torch.full((off + nb * self.bs + 3,), fill, device=DEV)
-        self.ptr = self.buf.data_ptr() + 4 * (off + lead)  # (an empty view's data_ptr() is 0)
+        self.buf = torch.full((off + nb * self.bs + 3,), fill, dtype=dtype, device=DEV)
+        self.ptr = self.buf.data_ptr() + self.buf.element_size() * (off + lead)  # (an empty view's data_ptr() is 0)
         self.inside = torch.zeros(self.buf.shape, dtype=torch.bool, device=DEV)
         if B is None:
             self.view = self.buf[off:off + rows * ld].view(rows, ld)[:, lead:lead + F]
@@ -101,10 +105,10 @@ class Rows:
             torch.as_strided(self.inside, (B, rows, F), (self.bs, ld, 1), off + lead).fill_(True)
 
     @classmethod
-    def of(cls, src, layout, fill, role="in", ld=None):
+    def of(cls, src, layout, fill, role="in", ld=None, dtype=torch.float32):
         """The layout holding a copy of src ([rows, F] or [B, rows, F])."""
         B = src.shape[0] if src.dim() == 3 else None
-        r = cls(src.shape[-2], src.shape[-1], layout, fill, role, ld, B)
+        r = cls(src.shape[-2], src.shape[-1], layout, fill, role, ld, B, dtype)
         r.view.copy_(src)
         return r
 
@@ -114,6 +118,44 @@ class Rows:
     def aligned(self):
         """16-byte rows: what the vector paths of the kernels ask for."""
         return self.ld % 4 == 0 and self.bs % 4 == 0 and self.ptr % 16 == 0
+
+
+class Guarded:
+    """A contiguous tensor of `shape` (for the operands a kernel takes without strides) with eight elements of `fill`
+    on either side of it in the same buffer; `init` is copied into it."""
+
+    def __init__(self, shape, dtype=torch.float32, fill=SENT, init=None):
+        n = math.prod(shape)
+        self.fill = fill
+        self.buf = torch.full((n + 16,), fill, dtype=dtype, device=DEV)
+        self.view = self.buf[8:8 + n].view(shape)
+        if init is not None:
+            self.view.copy_(init)
+
+    def untouched(self):
+        return bool((self.buf[:8] == self.fill).all()) and bool((self.buf[-8:] == self.fill).all())
+
+
+class Worst:
+    """The worst error / bound ratio per group of checks, for the figures DESIGN.md quotes."""
+
+    def __init__(self, title):
+        self.title, self.worst = title, {}
+
+    def within(self, group, got, ref, tol, what):
+        """`within`, and remember the largest |got - ref| / tol of the group (0 / 0 counts as 0)."""
+        within(got, ref, tol, what)
+        got, ref = got.double(), ref.double()
+        tol = torch.as_tensor(tol, dtype=torch.float64, device=ref.device)
+        ratio = ((got - ref).abs() / tol).nan_to_num(nan=0.0)
+        self.worst[group] = max(self.worst.get(group, 0.0), float(ratio.max()) if ratio.numel() else 0.0)
+
+    def exact(self, group):
+        self.worst.setdefault(group, 0.0)
+
+    def report(self, *groups):
+        for g in groups:
+            print(f"[{self.title}] {g}: worst error / bound = {self.worst.get(g, 0.0):.3e}")
 
 
 def input_fill(layout):
