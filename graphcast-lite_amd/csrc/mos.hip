@@ -80,8 +80,9 @@ struct NpSum {
     ++i;
   }
   __device__ double sum() const {
-    if (n >= 8 && body == n) return ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-    return 0.0 + res;  // numpy starts the reduction from the identity
+    // numpy starts the reduction from the identity: an all -0.0 input sums to +0.0 on every path
+    if (n >= 8 && body == n) return 0.0 + (((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7])));
+    return 0.0 + res;
   }
 };
 
@@ -554,7 +555,10 @@ extern "C" int gcl_mos_forest_predict(const void* nodes, const int32_t* roots, i
   GCL_CHECK_ARG(ngroups > 0 && ngroups <= kMaxPoints && nst >= ngroups, "mos_forest_predict: %d groups of %d "
                 "stations (at most %d groups)", ngroups, nst, kMaxPoints);
   GCL_CHECK_ARG(c_t2m >= 0, "mos_forest_predict: no t2m channel");
-  const int pass_max = max(1, min(kMaxPoints, kLeafBudget / (8 * ntrees)));
+  // stations per pass: the leaf budget, and the pass's features and leaves next to sbias within 64 KiB of LDS (128
+  // stations of 44 to 48 trees are within the budget and past 64 KiB)
+  const int fit = (64 * 1024 / 8 - kMaxPoints) / (kNumFeat + ntrees);
+  const int pass_max = max(1, min(kMaxPoints, min(kLeafBudget / (8 * ntrees), fit)));
   const size_t lds = ((size_t)pass_max * kNumFeat + (size_t)pass_max * ntrees + kMaxPoints) * sizeof(double);
   GCL_CHECK_ARG(lds <= 64 * 1024, "mos_forest_predict: %d trees exceed the LDS leaf table", ntrees);
   const Chans ch{c_t2m, c_u, c_v, c_sp, c_tp};

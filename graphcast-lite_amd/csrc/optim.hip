@@ -59,15 +59,14 @@ extern "C" int gcl_adam_step_groups(float* p, const float* g, float* m, float* v
   GCL_CHECK_ARG(gcl::aligned16(p) && gcl::aligned16(g) && gcl::aligned16(m) && gcl::aligned16(v) &&
                     (reinterpret_cast<uintptr_t>(bc) & 7) == 0,
                 "adam_groups: p, g, m, v must be 16-B aligned and bc 8-B aligned");
-  if (num_params == 0) return GCL_OK;
+  if (num_params == 0 || count == 0) return GCL_OK;  // nothing to update: no step is counted either
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(adam_groups_tick_kernel, dim3((unsigned)gcl::cdiv(num_params, 256)), dim3(256), 0, st, active,
                      step, (float2*)bc, num_params, beta1, beta2);
-  const int64_t n4 = count / 4;
-  if (n4 > 0)  // one lane per float4 up to 2048 blocks, grid-stride beyond
-    hipLaunchKernelGGL(adam_groups_kernel, dim3(gcl::grid_for(n4, 2048)), dim3(256), 0, st, (float4*)p, (const float4*)g,
-                       (float4*)m, (float4*)v, n4, chunk_param, active, lr, (const float2*)bc, beta1, beta2, eps,
-                       weight_decay, grad_scale);
+  const int64_t n4 = count / 4;  // one lane per float4 up to 2048 blocks, grid-stride beyond
+  hipLaunchKernelGGL(adam_groups_kernel, dim3(gcl::grid_for(n4, 2048)), dim3(256), 0, st, (float4*)p, (const float4*)g,
+                     (float4*)m, (float4*)v, n4, chunk_param, active, lr, (const float2*)bc, beta1, beta2, eps,
+                     weight_decay, grad_scale);
   GCL_CHECK_LAUNCH();
   return GCL_OK;
 }

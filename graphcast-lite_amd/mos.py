@@ -305,7 +305,7 @@ def apply_mos_t2m(prediction_phys: torch.Tensor, var_order: list, mos_table: dic
     if any(len(t) != n for t in times) or n > S:
         raise IndexError(f"{n} valid times for {S} forecast steps")
     out = torch.empty(p4.shape, dtype=p4.dtype, device=p4.device)
-    if n == 0:
+    if n == 0 or p4.numel() == 0:  # (an empty view has a null data_ptr(), which the C entry point refuses)
         out.copy_(p4)
         return out if prediction_phys.dim() == 4 else out[0]
     t2m = list(var_order).index("t2m")

@@ -442,7 +442,8 @@ int gcl_adam_step_dev(float* p, const float* g, float* m, float* v, int64_t coun
  * (num_params entries): active (0 = frozen: its p, m, v and step are neither read nor written), lr, step (int32,
  * incremented by the call for active parameters) and bc (2 floats of scratch: the bias corrections of its step,
  * computed in double).  beta1, beta2, eps, weight_decay are shared by all groups; grad_scale multiplies the gradient
- * first.  With every parameter active at one step the result is bit-equal to gcl_adam_step.  Two launches. */
+ * first.  With every parameter active at one step the result is bit-equal to gcl_adam_step.  Two launches; none, and
+ * no step counted, when count or num_params is 0. */
 int gcl_adam_step_groups(float* p, const float* g, float* m, float* v, int64_t count, const int32_t* chunk_param,
                          int32_t num_params, const int32_t* active, const float* lr, int32_t* step, float* bc,
                          float beta1, float beta2, float eps, float weight_decay, float grad_scale,

@@ -1,5 +1,5 @@
 """Row layouts for the kernel contract tests (test_norm_glue, test_dense_layouts, test_sparse_layouts, test_assim_kernels,
-test_scoring_kernels, test_map_kernels): operands as
+test_scoring_kernels, test_map_kernels, test_mos_kernels, test_region_glue_kernels): operands as
 views inside buffers the test owns, whose other elements hold a known value - NaN around an input (a kernel that
 reads its padding poisons the result), a sentinel around an output (a kernel that writes outside its view changes
 it) - plus the element-wise bound check and the launched-kernel queries the tests share."""
@@ -37,7 +37,7 @@ def within(got, ref, tol, what):
 
 def same_bits(a, b):
     """Bit-equal, NaN payloads included (torch.equal calls NaN != NaN)."""
-    bits = {1: torch.uint8, 4: torch.int32, 8: torch.int64}
+    bits = {1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}
     ia, ib = a.contiguous().view(bits[a.element_size()]), b.contiguous().view(bits[b.element_size()])
     return a.shape == b.shape and ia.dtype == ib.dtype and bool((ia == ib).all())
 
@@ -134,6 +134,34 @@ class Guarded:
 
     def untouched(self):
         return bool((self.buf[:8] == self.fill).all()) and bool((self.buf[-8:] == self.fill).all())
+
+
+class Field4:
+    """A [B, G, steps, C] forecast view (unit channel stride) inside a flat buffer holding `fill`: with `pad` the steps
+    are C + 2 apart, the rows steps * (C + 2) + 3 and the samples G * that + 5, otherwise the view is dense.  `strides`
+    is (bs, gs, ss) in elements, `ptr` the address of element 0 (an empty view's data_ptr() is 0)."""
+
+    def __init__(self, B, G, steps, C, dtype=torch.float32, pad=True, fill=NAN):
+        ss = C + 2 if pad else C
+        gs = steps * ss + (3 if pad else 0)
+        bs = G * gs + (5 if pad else 0)
+        lead = 7 if pad else 0
+        self.strides, self.fill = (bs, gs, ss), fill
+        self.buf = torch.full((lead + B * bs + 3,), fill, dtype=dtype, device=DEV)
+        self.ptr = self.buf.data_ptr() + self.buf.element_size() * lead
+        self.view = torch.as_strided(self.buf, (B, G, steps, C), (bs, gs, ss, 1), lead)
+        self.inside = torch.zeros(self.buf.shape, dtype=torch.bool, device=DEV)
+        torch.as_strided(self.inside, (B, G, steps, C), (bs, gs, ss, 1), lead).fill_(True)
+
+    @classmethod
+    def of(cls, src, pad=True, fill=NAN):
+        r = cls(*src.shape, dtype=src.dtype, pad=pad, fill=fill)
+        r.view.copy_(src)
+        return r
+
+    def untouched(self):
+        rest = self.buf[~self.inside]
+        return bool(rest.isnan().all()) if math.isnan(self.fill) else bool((rest == self.fill).all())
 
 
 class Worst:
