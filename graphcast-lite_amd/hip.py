@@ -177,6 +177,9 @@ _SIGNATURES = {
                                       _i32, _vp, _vp, _vp]),
     "gcl_maps_finalize": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i64, _i32, _vp, _vp, _i32, _i32, _vp, _vp]),
     "gcl_maps_convert": (C.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _vp]),
+    "gcl_live_max_dest": (C.c_int, []),
+    "gcl_live_frame_pack": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _vp]),
+    "gcl_live_region_stats": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _i32, _vp]),
 }
 
 
@@ -1586,4 +1589,66 @@ def maps_convert(x, conv, flags):
     x = x.contiguous()
     out = torch.empty_like(x)
     _check(lib().gcl_maps_convert(_p(x), _p(out), x.numel(), K, _p(conv), _pi(flags), _stream()))
+    return out
+
+
+def _room(t: torch.Tensor) -> int:
+    """Elements of t's storage from its first element on."""
+    return t.untyped_storage().nbytes() // t.element_size() - t.storage_offset()
+
+
+def live_max_dest() -> int:
+    """The most window slots one gcl_live_frame_pack call fills."""
+    return int(lib().gcl_live_max_dest())
+
+
+def live_frame_pack(arena, statics, chan, chan_div, pos, w, mean, std, out, dests, ldo: int, G: int, C: int):
+    """One analysis cycle into the window slots `out + dests[d] + g * ldo + c` (see gcl_live_frame_pack).  arena float32
+    [n] or None; statics float32 [n_static, G] or None; chan int64 [C, 3]; chan_div float32 [C]; pos int32 / w float64
+    [n_tab, G, 4] or None; mean / std float32 [>= C]; dests: element offsets from out's first element (host ints).
+    Every destination is checked against out's storage here; the positions are the table builder's to validate."""
+    assert chan.is_cuda and chan.dtype == torch.int64 and chan.shape == (C, 3) and chan.is_contiguous()
+    assert chan_div.shape == (C,) and chan_div.is_contiguous() and mean.numel() >= C and std.numel() >= C
+    assert out.is_cuda and out.dtype == torch.float32
+    if pos is not None:
+        assert arena is not None and arena.is_contiguous() and arena.dim() == 1
+        assert pos.dim() == 3 and pos.shape[1:] == (G, 4) and w.shape == pos.shape and pos.is_contiguous() and w.is_contiguous()
+    if statics is not None:
+        assert statics.dim() == 2 and statics.shape[1] == G and statics.is_contiguous()
+    dests = [int(d) for d in dests]
+    if not 1 <= len(dests) <= live_max_dest():
+        raise ValueError(f"live_frame_pack: {len(dests)} destinations (1 .. {live_max_dest()})")
+    if ldo < C or min(dests) < 0 or max(dests) + (G - 1) * int(ldo) + C > _room(out):
+        raise ValueError(f"live_frame_pack: destinations {dests} with row stride {ldo} leave the output buffer")
+    offs = (_i64 * len(dests))(*dests)
+    _check(lib().gcl_live_frame_pack(_p(arena), _p(statics), chan.data_ptr(), _p(chan_div), _pi(pos),
+                                     _pd(w) if w is not None else None, _p(mean), _p(std), out.data_ptr(), offs,
+                                     len(dests), int(ldo), int(G), int(C), _stream()))
+    return out
+
+
+def live_region_stats(pred4, rows, chans, offs, out=None, validated: bool = False):
+    """float64 [B, S, nc, 3] = mean, min, max over the rows `rows` (int32, device) of pred4[b, rows, s, chans[k]]
+    (+ offs[k]) (see gcl_live_region_stats).  pred4 float32 [B, G, S, C], unit channel stride; chans int32 [nc], offs
+    float32 [nc] on the device.  An empty row list raises.  rows and chans are checked against G and C here, which
+    reads them back (one synchronise); a caller that built them from host data it has checked passes validated=True."""
+    assert pred4.dim() == 4 and pred4.stride(3) == 1
+    B, G, S, Cc = pred4.shape
+    n, nc = rows.numel(), chans.numel()
+    if n == 0:
+        raise ValueError("live_region_stats: empty row list (the reference writes no city block then)")
+    if nc == 0:
+        raise ValueError("live_region_stats: no channels listed")
+    if not validated:
+        r, c = rows.cpu(), chans.cpu()
+        if int(r.min()) < 0 or int(r.max()) >= G:
+            raise ValueError(f"live_region_stats: a row index lies outside the {G} nodes")
+        if int(c.min()) < 0 or int(c.max()) >= Cc:
+            raise ValueError(f"live_region_stats: a channel index lies outside the {Cc} channels")
+    assert offs.numel() == nc and rows.is_contiguous() and chans.is_contiguous() and offs.is_contiguous()
+    if out is None:
+        out = torch.empty(B, S, nc, 3, dtype=torch.float64, device=pred4.device)
+    assert out.shape == (B, S, nc, 3) and out.dtype == torch.float64 and out.is_contiguous() and out.is_cuda
+    _check(lib().gcl_live_region_stats(_p(pred4), pred4.stride(0), pred4.stride(1), pred4.stride(2), _pi(rows), n,
+                                       _pi(chans), _p(offs), nc, S, out.data_ptr(), B, _stream()))
     return out

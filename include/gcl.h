@@ -897,6 +897,35 @@ int gcl_maps_finalize(const double* state, const int64_t* count, int32_t plane, 
 int gcl_maps_convert(const float* x, float* out, int64_t total, int32_t K, const float* conv,
                      const int32_t* flags, gcl_stream_t stream);
 
+/* ---- Live forecast glue (csrc/live.hip; scripts/live_gdas_forecast.py) ----
+ * One analysis cycle into window slots (:378-407 build_interpolator / interp_to_nodes, :460-483
+ * extract_live_channels, :486-487 normalize_frame, :617-620): all C channels of all G nodes in one launch, the
+ * channel the fastest index of a thread's work.  chan [C, 3] (device): kind 0 = zero fill, 1 = source field at arena
+ * + chan[c, 1] using point table chan[c, 2], 2 = static template row chan[c, 1] of statics [n_static, G].  pos / w
+ * [n_tab, G, 4]: per node the four positions into the field as the source stores it (unsorted, without the wrap
+ * column) and their float64 weights, corners (lat, lon), (lat, lon+1), (lat+1, lon), (lat+1, lon+1).  A field value is
+ * the four products, each rounded on its own, added in that order onto 0.0 in float64 (what scipy's
+ * RegularGridInterpolator does on float32 values), rounded to float32 and divided by chan_div[c] in float32 (:480-481,
+ * 100 for msl / sp).  Every channel is then z-scored, (x - mean[c]) / std[c] in float32 with the subtraction and the
+ * division rounded separately, and stored at out + dest_off[d] + g * ldo + c for every d < nd.  dest_off is a HOST
+ * array of nd <= gcl_live_max_dest() element offsets (it travels in the kernel arguments); the caller guarantees that
+ * every position lies inside its field and every destination inside out.  No atomics; arena / pos / w may be NULL
+ * together when no channel is a field. */
+int gcl_live_max_dest(void);
+int gcl_live_frame_pack(const float* arena, const float* statics, const int64_t* chan, const float* chan_div,
+                        const int32_t* pos, const double* w, const float* mean, const float* stdv, float* out,
+                        const int64_t* dest_off, int32_t nd, int64_t ldo, int32_t G, int32_t C,
+                        gcl_stream_t stream);
+/* The city-box summary (:543-559 summarize_city): out [B, S, nc, 3] float64 = mean, min, max over the n rows `rows`
+ * of v = pred[b, rows[i], s, chans[k]] (+ offs[k] in float32 when offs[k] != 0: -273.15 for t2m, :552-553).  pred is
+ * float32 with unit channel stride and element strides bs, gs, ss.  One block per (b, s, k), rows reduced in a fixed
+ * order: the mean is a float64 sum of the float32 values over n, min / max the float32 values (NaN propagates).
+ * n == 0 is an argument error (the reference writes no city block then).  The caller guarantees 0 <= rows[i] < G and
+ * 0 <= chans[k] < C: both are device arrays the entry point cannot read. */
+int gcl_live_region_stats(const float* pred, int64_t bs, int64_t gs, int64_t ss, const int32_t* rows, int32_t n,
+                          const int32_t* chans, const float* offs, int32_t nc, int32_t S, double* out, int32_t B,
+                          gcl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
