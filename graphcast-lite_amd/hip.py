@@ -161,6 +161,16 @@ _SIGNATURES = {
                                     _i32, _vp, _i32, _vp, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _sz, _i32, _vp]),
     "gcl_mos_table_apply": (C.c_int, [_vp, _i32, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _vp,
                                       _i32, _i32, _vp]),
+    "gcl_mos_fit_ws_bytes": (_sz, [_i32, _i32, _i32, _i32, _i32]),
+    "gcl_mos_fit_bin": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _i64, _vp]),
+    "gcl_mos_fit_gradients": (C.c_int, [_vp, _vp, _vp, _i32, _vp]),
+    "gcl_mos_fit_histogram": (C.c_int, [_vp, _i64, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "gcl_mos_fit_hist_subtract": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
+    "gcl_mos_fit_split": (C.c_int, [_vp, _vp, _i32, _vp, _i32, C.c_double, _i32, C.c_double, _vp, _vp, _vp, _sz, _vp]),
+    "gcl_mos_fit_partition": (C.c_int, [_vp, _i64, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _sz, _vp]),
+    "gcl_mos_fit_score": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _sz, _vp]),
+    "gcl_mos_fit_tree": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _i32, _i32, _i32,
+                                   C.c_double, C.c_double, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "gcl_multires_window_pack": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, _i64, _i32, _i32, _i32, _vp, _i32, _i32, _vp,
                                            _vp, _vp, _i64, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32,
                                            _vp]),

@@ -3,7 +3,8 @@
 
 * `load_mos_table`, `get_t2m_bias`, `apply_mos_t2m` (`:18-69`): the per-(month, hour) bias table.  The lookup is on the
   host; the add runs on the device (`gcl_mos_table_apply`).
-* `load_learned_mos` (`:93-95`): joblib, as in the reference (sklearn is needed only to unpickle the bundle).
+* `load_learned_mos` (`:93-95`): joblib, as in the reference (sklearn is needed only to unpickle the bundle); an
+  `.npz` written by `save_learned_mos` loads without sklearn.
 * `MOSForest`: the bundle's `HistGradientBoostingRegressor` flattened for the device; `save` / `load` keep it in an npz
   so a machine without sklearn can run it.
 * `apply_learned_mos_t2m` (`:244-340`) with the reference's signature and return convention: `(corrected,
@@ -16,18 +17,22 @@ Kelvin).  Coordinates are host arrays.  The host-side features (valid time and s
 `math` exactly as the reference computes them and uploaded as one small float64 tensor, so new valid times need no
 re-capture.
 
-Kernels: csrc/mos.hip.
+Fitting (scripts/build_learned_mos.py:203-266, :313-315, :332, :340-467): `training_table`, `fit_mos_table`,
+`MOSFitter` / `fit_learned_mos` (the histogram gradient boosting of `HistGradientBoostingRegressor.fit` on the device,
+sklearn-free), `evaluate_learned_mos`, `save_learned_mos`.
+
+Kernels: csrc/mos.hip, csrc/mos_fit.hip.
 """
 import json
 import math
 from datetime import datetime
-from typing import Optional, Sequence
+from typing import NamedTuple, Optional, Sequence
 
 import numpy as np
 import torch
 
 from . import hip
-from .capture import Captured
+from .capture import Captured, graph_enabled
 
 NUM_FEATURES = 20  # FEATURE_COLUMNS of the reference's build_learned_mos.py
 NUM_TIME_FEATURES = 8  # hour sin/cos, doy sin/cos, solar elevation, station lat/lon/elev
@@ -61,7 +66,13 @@ def get_t2m_bias(mos_table: dict, valid_time: datetime) -> float:
 # Learned MOS: the forest
 # ======================================================================================================================
 def load_learned_mos(path) -> dict:
-    """The learned-MOS bundle (a dict with the fitted model under "model"), unpickled with joblib."""
+    """The learned-MOS bundle (a dict with the fitted model under "model"): an `.npz` of `save_learned_mos` (the model
+    is a `MOSForest`, no sklearn needed), anything else unpickled with joblib as in the reference."""
+    if str(path).endswith(".npz"):
+        z = np.load(path)
+        bundle = json.loads(str(z["bundle_json"]))
+        bundle["model"] = MOSForest(*(z[k] for k in MOSForest._FIELDS), float(z["baseline"]), int(z["n_features"]))
+        return bundle
     import joblib
 
     return joblib.load(path)
@@ -211,6 +222,8 @@ def _forest_of(forest_or_bundle) -> MOSForest:
     if isinstance(forest_or_bundle, MOSForest):
         return forest_or_bundle
     model = forest_or_bundle["model"] if isinstance(forest_or_bundle, dict) else forest_or_bundle
+    if isinstance(model, MOSForest):  # a device-fitted bundle (save_learned_mos / MOSFit.bundle)
+        return model
     hit = _FORESTS.get(id(model))
     if hit is None or hit[0] is not model:
         hit = _FORESTS[id(model)] = (model, MOSForest.from_sklearn(model))
@@ -578,3 +591,341 @@ def apply_learned_mos_t2m(prediction_phys: torch.Tensor, var_order: list, model_
     corrected, n = mos.apply(p, tfeat, out=out)
     counts = n.cpu().tolist()
     return corrected, (counts if p.dim() == 4 else counts[0])
+
+
+# ======================================================================================================================
+# Fitting the learned MOS (scripts/build_learned_mos.py)
+# ======================================================================================================================
+# The model's input columns in order (build_learned_mos.py:245-266); the "feature_columns" of a saved bundle.
+FEATURE_COLUMNS = (
+    "era5_temperature_2m", "era5_dewpoint_2m", "era5_windspeed_10m", "wind_dir_sin", "wind_dir_cos",
+    "era5_surface_pressure", "era5_cloudcover", "era5_shortwave_radiation", "era5_precipitation", "hour_sin",
+    "hour_cos", "doy_sin", "doy_cos", "solar_elevation", "dewpoint_depression", "era5_t2m_lag6h", "delta_t2m_6h",
+    "station_lat", "station_lon", "station_elev")
+_ERA5_COLUMNS = ("era5_temperature_2m", "era5_dewpoint_2m", "era5_windspeed_10m", "era5_winddirection_10m",
+                 "era5_surface_pressure", "era5_cloudcover", "era5_shortwave_radiation", "era5_precipitation")
+SEASONS = {"DJF": (12, 1, 2), "MAM": (3, 4, 5), "JJA": (6, 7, 8), "SON": (9, 10, 11)}
+_BIN_SUBSAMPLE = 200000  # sklearn's _BinMapper(subsample=...)
+
+
+def training_table(times, era5: dict, station_t2m_C, station: dict):
+    """One station's fitting table (build_learned_mos.py:313-315, build_features :203-242, :332).
+
+    times: n datetimes in time order; era5: {column: float array [n]} with the eight hourly columns
+    era5_temperature_2m, era5_dewpoint_2m, era5_windspeed_10m, era5_winddirection_10m (degrees), era5_surface_pressure,
+    era5_cloudcover, era5_shortwave_radiation, era5_precipitation; station_t2m_C [n] the observation (NaN where
+    missing); station {"lat", "lon", "elev"}.  Rows without t2m or observation and rows with |bias| >= 20 go first, the
+    6-hour lag is then the sixth row before (as the reference's `shift(6)`), and rows with a NaN feature or bias go last.
+    Returns (X float64 [m, 20] in FEATURE_COLUMNS order, bias float64 [m], the m kept times).  Tables of several
+    stations are concatenated and sorted by time by the caller (:330-331)."""
+    times = list(times)
+    cols = {k: np.asarray(era5[k], dtype=np.float64) for k in _ERA5_COLUMNS}
+    obs = np.asarray(station_t2m_C, dtype=np.float64)
+    n = len(times)
+    if obs.shape != (n,) or any(v.shape != (n,) for v in cols.values()):
+        raise ValueError(f"training_table: every column must have one entry per time ({n})")
+    t2m = cols["era5_temperature_2m"]
+    with np.errstate(invalid="ignore"):
+        bias = obs - t2m
+        keep = ~np.isnan(t2m) & ~np.isnan(obs) & (np.abs(bias) < 20.0)
+    idx = np.nonzero(keep)[0]
+    times = [times[i] for i in idx]
+    cols = {k: v[idx] for k, v in cols.items()}
+    bias, t2m = bias[idx], t2m[idx]
+    hour = np.array([t.hour for t in times], dtype=np.int64)
+    doy = np.array([t.timetuple().tm_yday for t in times], dtype=np.int64)
+    lag = np.full(t2m.shape, np.nan)
+    lag[6:] = t2m[:-6]
+    wd = np.deg2rad(cols["era5_winddirection_10m"])
+    lat, lon, elev = station["lat"], station["lon"], station["elev"]
+    feats = {
+        "wind_dir_sin": np.sin(wd), "wind_dir_cos": np.cos(wd),
+        "hour_sin": np.sin(2 * np.pi * hour / 24), "hour_cos": np.cos(2 * np.pi * hour / 24),
+        "doy_sin": np.sin(2 * np.pi * doy / 365.25), "doy_cos": np.cos(2 * np.pi * doy / 365.25),
+        "solar_elevation": np.array([solar_elevation(lat, lon, t) for t in times], dtype=np.float64),
+        "dewpoint_depression": t2m - cols["era5_dewpoint_2m"], "era5_t2m_lag6h": lag, "delta_t2m_6h": t2m - lag,
+        "station_lat": np.full(t2m.shape, lat, dtype=np.float64),
+        "station_lon": np.full(t2m.shape, lon, dtype=np.float64),
+        "station_elev": np.full(t2m.shape, elev, dtype=np.float64)}
+    X = np.column_stack([feats[c] if c in feats else cols[c] for c in FEATURE_COLUMNS]).reshape(len(times), 20)
+    ok = ~(np.isnan(X).any(axis=1) | np.isnan(bias))
+    return np.ascontiguousarray(X[ok]), bias[ok], [t for t, k in zip(times, ok) if k]
+
+
+def fit_mos_table(times, bias) -> dict:
+    """The static baseline of build_learned_mos.py:381-385: the mean bias per (month, hour), in the
+    `{"bias_table": {str(month): {str(hour): float}}}` form of `load_mos_table` / `get_t2m_bias` / `apply_mos_t2m`."""
+    bias = np.asarray(bias, dtype=np.float64)
+    groups = {}
+    for i, t in enumerate(times):
+        groups.setdefault((t.month, t.hour), []).append(i)
+    table = {}
+    for (m, h) in sorted(groups):
+        table.setdefault(str(m), {})[str(h)] = float(np.mean(bias[groups[(m, h)]]))
+    return {"bias_table": table}
+
+
+def bin_thresholds(X: np.ndarray, max_bins: int = 255, seed=None) -> list:
+    """sklearn's `_BinMapper.fit` for rows without NaN: per feature the float64 thresholds between bins.  With at most
+    `max_bins` distinct values they are the midpoints of consecutive distinct values ((a + b) * 0.5), else the
+    `max_bins - 1` inner percentiles of the sorted column (method "midpoint"); a one-valued feature has none.  Above
+    200 000 rows they come from the rows `RandomState(seed).choice(n, 200000, replace=False)`."""
+    X = np.asarray(X, dtype=np.float64)
+    if X.shape[0] > _BIN_SUBSAMPLE:
+        X = X.take(np.random.RandomState(seed).choice(X.shape[0], _BIN_SUBSAMPLE, replace=False), axis=0)
+    out = []
+    for f in range(X.shape[1]):
+        col = np.sort(X[:, f])
+        distinct = np.unique(col)
+        if len(distinct) <= max_bins:
+            mid = distinct[:-1] + distinct[1:]
+            mid *= 0.5
+        else:
+            mid = np.percentile(col, np.linspace(0, 100, num=max_bins + 1)[1:-1], method="midpoint").astype(np.float64)
+        np.clip(mid, None, 1e300, out=mid)  # sklearn's ALMOST_INF
+        out.append(mid)
+    return out
+
+
+def early_stopping_split(n: int, validation_fraction: float = 0.1, random_state=42):
+    """(seed, train_rows, val_rows) as sklearn's fit draws them: seed = RandomState(random_state).randint(2^32 - 1),
+    perm = RandomState(seed).permutation(n), validation = the first ceil(fraction n) of perm, training = the next
+    floor((1 - fraction) n)."""
+    seed = int(np.random.RandomState(random_state).randint(np.iinfo(np.uint32).max, dtype="u8"))
+    perm = np.random.RandomState(seed).permutation(n)
+    n_val = int(math.ceil(validation_fraction * n))
+    n_train = int(math.floor((1.0 - validation_fraction) * n))
+    return seed, perm[n_val:n_val + n_train], perm[:n_val]
+
+
+def should_stop(scores, n_iter_no_change: int = 15, tol: float = 1e-7) -> bool:
+    """sklearn's `_should_stop`: with p = n_iter_no_change + 1, True once there are p scores and none of the last p - 1
+    exceeds scores[-p] + tol."""
+    p = n_iter_no_change + 1
+    if len(scores) < p:
+        return False
+    ref = scores[-p] + (0.0 if tol is None else tol)
+    return not any(s > ref for s in scores[-p + 1:])
+
+
+class MOSFit(NamedTuple):
+    """What `MOSFitter.fit` returns: the forest, sklearn's `n_iter_` and `validation_score_` (index 0: the baseline;
+    empty without early stopping), the bin thresholds per feature and the rows of X used for training / validation."""
+    forest: MOSForest
+    n_iter_: int
+    validation_score_: np.ndarray
+    bin_thresholds: list
+    train_rows: np.ndarray
+    val_rows: np.ndarray
+
+    def bundle(self, **metadata) -> dict:
+        """The reference's bundle dict (build_learned_mos.py:453-464) with the forest as "model"."""
+        return {"model": self.forest, "feature_columns": list(FEATURE_COLUMNS), **metadata}
+
+
+class _TreeStep(Captured):
+    """One boosting iteration (gcl_mos_fit_tree): the same launch sequence every time, replayed from a hipGraph."""
+
+    def __init__(self, call, use_graph):
+        super().__init__(graph_enabled(use_graph), required=use_graph is True)
+        self._call = call
+
+    def _work(self):
+        hip._check(self._call(hip._stream()))
+
+    def __call__(self):
+        return self._run()
+
+
+class MOSFitter:
+    """`HistGradientBoostingRegressor(loss="squared_error").fit` on the device (build_learned_mos.py:357-369), for rows
+    without missing values.  Hyper-parameters carry sklearn's names; the defaults are the reference's.  The fit
+    reproduces sklearn's trees (features, thresholds, structure) wherever float64 sums decide a split unambiguously,
+    and repeats its own bytes from run to run."""
+
+    def __init__(self, max_iter: int = 500, max_depth: int = 8, learning_rate: float = 0.05, min_samples_leaf: int = 20,
+                 l2_regularization: float = 0.1, max_leaf_nodes: int = 31, max_bins: int = 255,
+                 early_stopping: bool = True, validation_fraction: float = 0.1, n_iter_no_change: int = 15,
+                 tol: float = 1e-7, random_state=42):
+        if not 2 <= max_bins <= 255:
+            raise ValueError(f"max_bins={max_bins} (2 .. 255)")
+        if not 2 <= max_leaf_nodes <= 256:
+            raise ValueError(f"max_leaf_nodes={max_leaf_nodes} (2 .. 256)")
+        if max_iter < 1 or max_depth is None or max_depth < 1 or min_samples_leaf < 1:
+            raise ValueError("max_iter, max_depth and min_samples_leaf must be at least 1")
+        self.max_iter, self.max_depth, self.learning_rate = int(max_iter), int(max_depth), float(learning_rate)
+        self.min_samples_leaf, self.l2_regularization = int(min_samples_leaf), float(l2_regularization)
+        self.max_leaf_nodes, self.max_bins, self.early_stopping = int(max_leaf_nodes), int(max_bins), bool(early_stopping)
+        self.validation_fraction, self.n_iter_no_change, self.tol = validation_fraction, int(n_iter_no_change), tol
+        self.random_state = random_state
+
+    @staticmethod
+    def _host(a, what, ndim):
+        if isinstance(a, torch.Tensor):
+            a = a.detach().cpu().numpy()
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if a.ndim != ndim:
+            raise ValueError(f"MOSFitter.fit: {what} must have {ndim} dimension(s), got shape {a.shape}")
+        if not np.isfinite(a).all():
+            raise ValueError(f"MOSFitter.fit: NaN or inf in {what} (the reference drops such rows before fitting)")
+        return a
+
+    def fit(self, X, y, validation=None, check_every: int = 16, use_graph=None, device=None) -> MOSFit:
+        """Fit on X float64 [n, F <= 32] (host array or device tensor) and y [n].  `validation=(X_val, y_val)` replaces
+        the random split of early stopping.  The device runs whole iterations without the host; every `check_every`
+        iterations the host reads the scores, applies sklearn's stopping rule to each prefix and, when it fires, drops
+        the trees grown past that iteration.  `use_graph`: replay an iteration from a hipGraph (None: unless
+        GCL_NO_GRAPH is set)."""
+        X, y = self._host(X, "X", 2), self._host(y, "y", 1)
+        n_all, F = X.shape
+        if F < 1 or F > 32:
+            raise ValueError(f"MOSFitter.fit: {F} features (1 .. 32, MOSForest's limit)")
+        if y.shape[0] != n_all:
+            raise ValueError(f"MOSFitter.fit: {n_all} rows of X, {y.shape[0]} of y")
+        if check_every < 1:
+            raise ValueError("MOSFitter.fit: check_every must be at least 1")
+        seed = int(np.random.RandomState(self.random_state).randint(np.iinfo(np.uint32).max, dtype="u8"))
+        train_rows, val_rows = np.arange(n_all), np.arange(0)
+        Xv = yv = None
+        if validation is not None:
+            Xv, yv = self._host(validation[0], "X_val", 2), self._host(validation[1], "y_val", 1)
+            if Xv.shape[1] != F or Xv.shape[0] != yv.shape[0]:
+                raise ValueError("MOSFitter.fit: validation rows do not match X / y_val")
+        elif self.early_stopping:
+            _, train_rows, val_rows = early_stopping_split(n_all, self.validation_fraction, self.random_state)
+            Xv, yv = X[val_rows], y[val_rows]
+        if not self.early_stopping:
+            Xv = yv = None
+        n_val = 0 if Xv is None else Xv.shape[0]
+        if self.early_stopping and n_val == 0:
+            raise ValueError("MOSFitter.fit: early stopping needs at least one validation row")
+        Xt, yt = (X, y) if train_rows.size == n_all else (X[train_rows], y[train_rows])
+        n = Xt.shape[0]
+        if n < 1:
+            raise ValueError("MOSFitter.fit: no training rows")
+        if not torch.cuda.is_available():
+            raise RuntimeError("MOSFitter.fit needs a GPU (there is no CPU fallback)")
+        dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        L = hip.lib()
+        thresholds = bin_thresholds(Xt, self.max_bins, seed)
+        baseline = float(np.mean(yt))
+        with torch.cuda.device(dev):
+            thr = np.zeros((F, 256), dtype=np.float64)
+            for f, t in enumerate(thresholds):
+                thr[f, :len(t)] = t
+            d_thr = torch.from_numpy(thr).to(dev)
+            d_nthr = torch.tensor([len(t) for t in thresholds], dtype=torch.int32).to(dev)
+
+            def binned(A):
+                ld = (A.shape[0] + 255) // 256 * 256
+                b = torch.zeros(F, ld, dtype=torch.uint8, device=dev)
+                dA = torch.from_numpy(A).to(dev)
+                hip._check(L.gcl_mos_fit_bin(dA.data_ptr(), A.shape[0], F, d_thr.data_ptr(), d_nthr.data_ptr(),
+                                             b.data_ptr(), ld, hip._stream()))
+                return b, ld
+
+            bins, ld = binned(np.ascontiguousarray(Xt))
+            d_y = torch.from_numpy(np.ascontiguousarray(yt)).to(dev)
+            raw = torch.full((n,), baseline, dtype=torch.float64, device=dev)
+            need = int(L.gcl_mos_fit_ws_bytes(n, n_val, F, self.max_leaf_nodes, self.max_iter))
+            if need == 0:
+                raise ValueError("MOSFitter.fit: the table is outside what gcl_mos_fit_tree takes")
+            ws = torch.empty(need, dtype=torch.uint8, device=dev)
+            nodes = torch.zeros(self.max_iter * (2 * self.max_leaf_nodes - 1) * 16, dtype=torch.uint8, device=dev)
+            roots = torch.zeros(self.max_iter + 1, dtype=torch.int32, device=dev)
+            scores = torch.zeros(self.max_iter + 1, dtype=torch.float64, device=dev)
+            state = torch.zeros(2, dtype=torch.int32, device=dev)
+            if n_val:
+                bins_v, ld_v = binned(np.ascontiguousarray(Xv))
+                d_yv = torch.from_numpy(np.ascontiguousarray(yv)).to(dev)
+                raw_v = torch.full((n_val,), baseline, dtype=torch.float64, device=dev)
+                hip._check(L.gcl_mos_fit_score(raw_v.data_ptr(), d_yv.data_ptr(), n_val, scores.data_ptr(),
+                                               ws.data_ptr(), need, hip._stream()))
+                val_args = (bins_v.data_ptr(), ld_v, n_val, d_yv.data_ptr(), raw_v.data_ptr())
+            else:
+                val_args = (None, 0, 0, None, None)
+
+            def call(stream):
+                return L.gcl_mos_fit_tree(
+                    bins.data_ptr(), ld, n, F, d_nthr.data_ptr(), d_thr.data_ptr(), d_y.data_ptr(), raw.data_ptr(),
+                    *val_args, self.max_leaf_nodes, self.max_depth, self.min_samples_leaf, self.l2_regularization,
+                    self.learning_rate, self.max_iter, nodes.data_ptr(), roots.data_ptr(), scores.data_ptr(),
+                    state.data_ptr(), ws.data_ptr(), need, stream)
+
+            step = _TreeStep(call, use_graph)
+            n_iter, checked = self.max_iter, 0  # scores[:checked + 1] have been through the stopping rule
+            for it in range(1, self.max_iter + 1):
+                step()
+                if self.early_stopping and (it % check_every == 0 or it == self.max_iter):
+                    sc = scores[:it + 1].cpu().numpy()
+                    stop = next((k for k in range(checked + 1, it + 1)
+                                 if should_stop(sc[:k + 1], self.n_iter_no_change, self.tol)), None)
+                    checked = it
+                    if stop is not None:
+                        n_iter = stop
+                        break
+            torch.cuda.synchronize(dev)
+            self.launch_mode = step.launch_mode
+            grown, n_nodes = (int(v) for v in state.cpu().tolist())
+            h_roots = roots.cpu().numpy()
+            if grown < n_iter:
+                raise RuntimeError(f"MOSFitter.fit: {grown} trees on the device, {n_iter} expected")
+            total = n_nodes if n_iter == grown else int(h_roots[n_iter])
+            packed = nodes[:total * 16].cpu().numpy().view([("v", "<f8"), ("a", "<u4"), ("b", "<u4")])
+            val_scores = scores[:n_iter + 1].cpu().numpy() if self.early_stopping else np.zeros(0)
+        b = packed["b"]
+        forest = MOSForest((b >> 24) & 31, packed["v"], packed["a"], b & 0xFFFFFF, (b >> 29) & 1, (b >> 30) & 1,
+                           h_roots[:n_iter], baseline, n_features=F)
+        return MOSFit(forest, n_iter, val_scores, thresholds, train_rows, val_rows)
+
+
+def fit_learned_mos(X, y, validation=None, check_every: int = 16, use_graph=None, device=None, **kw) -> MOSFit:
+    """`MOSFitter(**kw).fit(X, y, ...)`: the reference's model fit (build_learned_mos.py:357-369) on the device."""
+    return MOSFitter(**kw).fit(X, y, validation=validation, check_every=check_every, use_graph=use_graph, device=device)
+
+
+def evaluate_learned_mos(forest, X, y, times, table: Optional[dict] = None) -> dict:
+    """(`forest`: a `MOSFit`, a `MOSForest` or a bundle.)  Step 4 of build_learned_mos.py (:374-433) on a test table: MAE / RMSE of the raw forecast (zero correction), the
+    static (month, hour) table (`fit_mos_table`; None: left out) and the learned forest, overall, per season and per
+    hour (every third, as the reference prints them).  The forest runs on the device (`MOSForest.predict`); the
+    reductions are float64 on the host."""
+    forest = forest.forest if isinstance(forest, MOSFit) else _forest_of(forest)
+    y = np.asarray(y, dtype=np.float64)
+    times = list(times)
+    Xd = X if isinstance(X, torch.Tensor) and X.is_cuda else torch.from_numpy(
+        np.ascontiguousarray(X, dtype=np.float64)).to(torch.device("cuda", torch.cuda.current_device()))
+    pred = forest.predict(Xd).cpu().numpy()
+    month = np.array([t.month for t in times])
+    hour = np.array([t.hour for t in times])
+    methods = {"raw": np.zeros_like(y), "learned": pred}
+    if table is not None:
+        methods["static"] = np.array([get_t2m_bias(table, t) for t in times], dtype=np.float64)
+
+    def mae(mask, p):
+        return float(np.mean(np.abs(y[mask] - p[mask])))
+
+    every = np.ones(y.shape, dtype=bool)
+    out = {"n": int(y.size), "per_season": {}, "per_hour": {}}
+    for name, p in methods.items():
+        out[name] = {"mae": mae(every, p), "rmse": float(np.sqrt(np.mean((y - p) ** 2)))}
+    for name, months in SEASONS.items():
+        mask = np.isin(month, months)
+        if mask.any():
+            out["per_season"][name] = {"n": int(mask.sum()), **{k: mae(mask, p) for k, p in methods.items()}}
+    for h in range(0, 24, 3):
+        mask = hour == h
+        if mask.any():
+            out["per_hour"][h] = {"n": int(mask.sum()), **{k: mae(mask, p) for k, p in methods.items()}}
+    return out
+
+
+def save_learned_mos(path, fit, **metadata) -> None:
+    """Store a fitted forest (a `MOSFit` or `MOSForest`) with the bundle's metadata keys (build_learned_mos.py:453-464:
+    stations_trained, period, split, test_mae, ...; "feature_columns" is added) as an `.npz` that `load_learned_mos`
+    reads back without sklearn."""
+    forest = fit.forest if isinstance(fit, MOSFit) else _forest_of(fit)
+    if not str(path).endswith(".npz"):
+        raise ValueError("save_learned_mos writes an .npz (a .joblib bundle is the reference's, written by joblib)")
+    meta = {"feature_columns": list(FEATURE_COLUMNS), **metadata}
+    np.savez_compressed(path, baseline=np.float64(forest.baseline), n_features=np.int32(forest.n_features),
+                        bundle_json=np.array(json.dumps(meta)), **{k: getattr(forest, k) for k in forest._FIELDS})

@@ -801,6 +801,65 @@ int gcl_mos_table_apply(const void* in, int32_t f64, int64_t bs, int64_t gs, int
                         int64_t ogs, int64_t oss, int32_t G, int32_t steps, int32_t C, int32_t t2m,
                         const double* step_bias, int32_t nvalid, int32_t B, gcl_stream_t stream);
 
+/* ---- Fitting the learned-MOS forest (csrc/mos_fit.hip; scripts/build_learned_mos.py:357-369) ----
+ * The reference's `HistGradientBoostingRegressor(...).fit(X_train, y_train)` for squared error on rows without missing
+ * values: histogram gradient boosting with a constant hessian of 1.  Features are binned into uint8 bins[F, ld]
+ * (feature-major), histograms are two planes hist_sum float64 [F, 256] and hist_cnt uint32 [F, 256] (sum of hessians =
+ * count), rows of a node are a segment [start, start + count) of the int32 partition array.  thr is float64 [F, 256]
+ * (nthr[f] <= 255 used per feature).  No floating-point atomics: a repeated call repeats its bits.  Every workspace
+ * holds gcl_mos_fit_ws_bytes(n, n_val, F, max_leaf_nodes, max_iter) bytes (n >= start + count for the segment calls;
+ * max_leaf_nodes 2 .. 256, F <= 32; 0 for arguments outside that). */
+size_t gcl_mos_fit_ws_bytes(int32_t n, int32_t n_val, int32_t F, int32_t max_leaf_nodes, int32_t max_iter);
+/* build_learned_mos.py:357-369, sklearn's _BinMapper.transform: bins[f, i] = #{k < nthr[f] : thr[f, k] < X[i, f]}, so a
+ * value equal to a threshold goes left.  X float64 [n, F] without NaN. */
+int gcl_mos_fit_bin(const double* X, int32_t n, int32_t F, const double* thr, const int32_t* nthr, void* bins,
+                    int64_t ld, gcl_stream_t stream);
+/* build_learned_mos.py:357-369, the half squared error's gradient: g[i] = float32(raw[i] - y[i]), the difference in
+ * float64. */
+int gcl_mos_fit_gradients(const double* raw, const double* y, float* g, int32_t n, gcl_stream_t stream);
+/* build_learned_mos.py:357-369, sklearn's compute_histograms_brute: hist[f, b] = {sum of g[row], number of rows} over
+ * the rows part[start .. start + count) with bins[f, row] == b.  The rows of at most 256 row ranges are added one
+ * after the other, then the ranges in order. */
+int gcl_mos_fit_histogram(const void* bins, int64_t ld, int32_t F, const int32_t* part, const float* g, int32_t start,
+                          int32_t count, double* hist_sum, void* hist_cnt, void* ws, size_t ws_bytes,
+                          gcl_stream_t stream);
+/* build_learned_mos.py:357-369, sklearn's compute_histograms_subtraction: large = parent - small, element-wise. */
+int gcl_mos_fit_hist_subtract(const double* parent_sum, const void* parent_cnt, const double* small_sum,
+                              const void* small_cnt, double* large_sum, void* large_cnt, int32_t F,
+                              gcl_stream_t stream);
+/* build_learned_mos.py:357-369, sklearn's find_node_split (left-to-right scan): the best split of a node of n rows and
+ * gradient sum sum_g.  A candidate "bins <= b go left" needs both sides >= min_samples_leaf; value(g, h) = -g / (h + l2
+ * + 1e-15), gain = g_P v_P - g_L v_L - g_R v_R in that order; only a strictly larger gain replaces the best (lowest bin,
+ * then lowest feature).  out = {gain (-1: no split), sum_g_left}, iout = {feature, bin, n_left, missing_go_to_left =
+ * n_left > n_right}, both on the device. */
+int gcl_mos_fit_split(const double* hist_sum, const void* hist_cnt, int32_t F, const int32_t* nthr, int32_t n,
+                      double sum_g, int32_t min_samples_leaf, double l2, double* out, int32_t* iout, void* ws,
+                      size_t ws_bytes, gcl_stream_t stream);
+/* build_learned_mos.py:357-369, sklearn's split_indices: the stable partition of part[start .. start + count) by
+ * bins[feat, row] <= bin (left rows first, both sides in their old order).  *n_left (device, optional) receives the
+ * left side's length. */
+int gcl_mos_fit_partition(const void* bins, int64_t ld, int32_t* part, int32_t start, int32_t count, int32_t feat,
+                          int32_t bin, int32_t* n_left, void* ws, size_t ws_bytes, gcl_stream_t stream);
+/* build_learned_mos.py:357-369, the early-stopping score of the squared error: *score = -0.5 mean((raw - y)^2) in
+ * float64, summed in a fixed order.  ws as for n_val = n. */
+int gcl_mos_fit_score(const double* raw, const double* y, int32_t n, double* score, void* ws, size_t ws_bytes,
+                      gcl_stream_t stream);
+/* build_learned_mos.py:357-369, one boosting iteration (sklearn's TreeGrower.grow with the histogram, split and
+ * partition rules above): gradients from raw and y, a tree grown best-first (the splittable leaf with the largest gain
+ * next; max_leaf_nodes; children at max_depth and nodes of fewer than 2 min_samples_leaf rows are leaves; only the
+ * smaller child's histogram is built, the right one on a tie, the other is parent - smaller), leaf values times
+ * learning_rate.  The tree is appended to `nodes` (16-byte MOSForest nodes with numeric thresholds, children after
+ * their parent) at node state[1], roots[state[0]] = state[1]; raw[row] += leaf value for every training row; the n_val
+ * validation rows (bins_val, may be 0 rows) walk the tree into raw_val and scores[state[0] + 1] = the score of
+ * gcl_mos_fit_score; then state[0] += 1, state[1] += the tree's nodes.  state is int32 [2] on the device, zeroed by the
+ * caller before the first tree; a call with state[0] >= max_iter changes nothing.  The launch sequence depends on the
+ * arguments only, never on the data (it can be captured); nothing is read back. */
+int gcl_mos_fit_tree(const void* bins, int64_t ld, int32_t n, int32_t F, const int32_t* nthr, const double* thr,
+                     const double* y, double* raw, const void* bins_val, int64_t ld_val, int32_t n_val,
+                     const double* y_val, double* raw_val, int32_t max_leaf_nodes, int32_t max_depth,
+                     int32_t min_samples_leaf, double l2, double learning_rate, int32_t max_iter, void* nodes,
+                     int32_t* roots, double* scores, int32_t* state, void* ws, size_t ws_bytes, gcl_stream_t stream);
+
 /* ---- Multi-resolution input (csrc/multires.hip) ----
  * Windows of the flat multires node set - the n_kept global points outside the box in (lat, lon)-major order, then
  * n_reg regional points - packed from the device-resident fp16 series without the flat series ever existing.  Replaces
