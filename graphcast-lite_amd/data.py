@@ -75,6 +75,33 @@ class TimeseriesChunkDataset:
         print(f"[ChunkDataset] {split}: {len(self._sample_indices)} samples, {where}, feat={self.n_feat}, "
               f"obs={obs_window}, pred={pred_steps}")
 
+    @classmethod
+    def from_series(cls, series: torch.Tensor, mean, std, obs_window: int = 2, pred_steps: int = 1, split: str = "train",
+                    n_features: Optional[int] = None, test_fraction: float = 0.2) -> "TimeseriesChunkDataset":
+        """The dataset over an fp16 series that is already on the GPU, (T, lon, lat, C) or flat (T, N, C), with its
+        scalers (numpy or tensors): what `dataset.DatasetBuilder`, `repair_channels` or `add_time_features` leave in
+        HBM trains without a disk round trip.  The series is used as it is, not copied."""
+        if not (series.is_cuda and series.dtype == torch.float16 and series.is_contiguous() and series.dim() in (3, 4)):
+            raise TypeError("from_series needs a contiguous float16 GPU series (T, lon, lat, C) or (T, N, C)")
+        self = cls.__new__(cls)
+        self.data_dir, self.obs_window, self.pred_steps = None, obs_window, pred_steps
+        self.split, self.test_fraction, self.device = split, test_fraction, series.device
+        self.flat_grid = series.dim() == 3
+        self.chunk_lengths, self.total_time = [int(series.shape[0])], int(series.shape[0])
+        if self.flat_grid:
+            self.n_nodes, self.n_lon, self.n_lat, self.n_feat_total = int(series.shape[1]), None, None, int(series.shape[2])
+        else:
+            self.n_nodes, self.n_lon, self.n_lat = None, int(series.shape[1]), int(series.shape[2])
+            self.n_feat_total = int(series.shape[3])
+        self.n_feat = n_features if n_features else self.n_feat_total
+        as_np = lambda a: (a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)).astype(np.float32)  # noqa: E731
+        self.mean_np, self.std_np = as_np(mean)[:self.n_feat], as_np(std)[:self.n_feat]
+        self.mean = torch.from_numpy(self.mean_np.copy()).to(self.device)
+        self.std = torch.from_numpy(self.std_np.copy()).to(self.device)
+        self.chunks = [series]
+        self._sample_indices = sample_indices(self.chunk_lengths, obs_window, pred_steps, split, test_fraction)
+        return self
+
     def __len__(self):
         return len(self._sample_indices)
 

@@ -190,6 +190,14 @@ _SIGNATURES = {
     "gcl_live_max_dest": (C.c_int, []),
     "gcl_live_frame_pack": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _vp]),
     "gcl_live_region_stats": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _i32, _vp]),
+    "gcl_dataset_ws_bytes": (_sz, [_i32]),
+    "gcl_dataset_max_sources": (C.c_int, []),
+    "gcl_dataset_pack": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _i64, _i32, _i64, _vp, _vp, _vp, _sz,
+                                   _vp]),
+    "gcl_dataset_stats": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
+                                    _vp]),
+    "gcl_dataset_welford": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp]),
+    "gcl_dataset_widen": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, _i32, _vp, _vp]),
 }
 
 
@@ -1661,4 +1669,96 @@ def live_region_stats(pred4, rows, chans, offs, out=None, validated: bool = Fals
     assert out.shape == (B, S, nc, 3) and out.dtype == torch.float64 and out.is_contiguous() and out.is_cuda
     _check(lib().gcl_live_region_stats(_p(pred4), pred4.stride(0), pred4.stride(1), pred4.stride(2), _pi(rows), n,
                                        _pi(chans), _p(offs), nc, S, out.data_ptr(), B, _stream()))
+    return out
+
+
+DATASET_NAN_TO_ZERO, DATASET_INF_TO_ZERO = 1, 2  # flag bits of gcl_dataset_stats
+
+
+def dataset_max_sources() -> int:
+    """The most source planes one gcl_dataset_pack call takes."""
+    return int(lib().gcl_dataset_max_sources())
+
+
+def _series_shape(series):
+    """(T, n_lon, n_lat, Ct) of a contiguous fp16 series [T, lon, lat, Ct] or flat [T, N, Ct] on the GPU."""
+    assert series.is_cuda and series.dtype == torch.float16 and series.is_contiguous() and series.dim() in (3, 4)
+    if series.dim() == 3:
+        return series.shape[0], series.shape[1], 1, series.shape[2]
+    return tuple(series.shape)
+
+
+def _dataset_ws(C: int, device):
+    ws = workspace(lib().gcl_dataset_ws_bytes(int(C)), device)
+    return ws.data_ptr(), ws.numel()
+
+
+def dataset_pack(sources, chans, scales, nt: int, series, t0: int, sums, sumsq, grid=None):
+    """One time block of float32 planes into rows [t0, t0 + nt) of `series`, with the block's sums (see
+    gcl_dataset_pack).  sources: contiguous float32 GPU tensors, [nt, lon, lat] / [nt, P] or, time-invariant, [lon, lat]
+    / [P]; chans / scales: their destination channels and float32 factors (host).  sums / sumsq: float64 [Ct] on the
+    GPU, written at the listed channels.  series None: the sums alone, on the grid = (n_lon, n_lat, Ct) given."""
+    if series is not None:
+        T, n_lon, n_lat, Ct = _series_shape(series)
+    else:
+        (n_lon, n_lat, Ct), T, t0 = grid, int(nt), 0
+    P, n = n_lon * n_lat, len(sources)
+    if not (1 <= n <= dataset_max_sources() and len(chans) == n and len(scales) == n):
+        raise ValueError(f"dataset_pack: {n} sources (1 .. {dataset_max_sources()}), {len(chans)} channels, "
+                         f"{len(scales)} factors")
+    strides = []
+    for x in sources:
+        assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous(), "dataset_pack: float32 contiguous GPU planes"
+        if x.numel() == nt * P:
+            strides.append(P)
+        elif x.numel() == P:
+            strides.append(0)
+        else:
+            raise ValueError(f"dataset_pack: a source of {tuple(x.shape)} is neither [{nt}, {P}] nor [{P}]")
+    for t in (sums, sumsq):
+        assert t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and t.numel() == Ct
+    dev = sources[0].device
+    ws, ws_bytes = _dataset_ws(Ct, dev)
+    _check(lib().gcl_dataset_pack((_vp * n)(*[x.data_ptr() for x in sources]), (_i64 * n)(*strides),
+                                  (_i32 * n)(*[int(c) for c in chans]), (_f32 * n)(*[float(s) for s in scales]), n,
+                                  int(nt), n_lon, n_lat, series.data_ptr() if series is not None else None, T, Ct,
+                                  int(t0), sums.data_ptr(), sumsq.data_ptr(), ws, ws_bytes, _stream()))
+
+
+def dataset_stats(series, t_s: int, t_e: int, flags: int = 0, out=None):
+    """(sum f64, sumsq f64, min f32, max f32, n_nan i64, n_inf i64), each [Ct] on the GPU, of rows [t_s, t_e) of the
+    fp16 series (see gcl_dataset_stats).  out: such a tuple to fill."""
+    T, n_lon, n_lat, Ct = _series_shape(series)
+    if out is None:
+        mk = lambda dt: torch.empty(Ct, dtype=dt, device=series.device)  # noqa: E731
+        out = (mk(torch.float64), mk(torch.float64), mk(torch.float32), mk(torch.float32), mk(torch.int64),
+               mk(torch.int64))
+    for t, dt in zip(out, (torch.float64, torch.float64, torch.float32, torch.float32, torch.int64, torch.int64)):
+        assert t.is_cuda and t.dtype == dt and t.is_contiguous() and t.numel() == Ct
+    ws, ws_bytes = _dataset_ws(Ct, series.device)
+    _check(lib().gcl_dataset_stats(series.data_ptr(), T, n_lon, n_lat, Ct, int(t_s), int(t_e), int(flags),
+                                   *[t.data_ptr() for t in out], ws, ws_bytes, _stream()))
+    return out
+
+
+def dataset_welford(mean, m2, n, block_sum, block_sumsq, block_n: int):
+    """The reference's welford_update on device state: mean / m2 float64 [C], n int64 [1] (see gcl_dataset_welford)."""
+    Cn = mean.numel()
+    for t in (mean, m2, block_sum, block_sumsq):
+        assert t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and t.numel() == Cn
+    assert n.is_cuda and n.dtype == torch.int64 and n.numel() == 1
+    _check(lib().gcl_dataset_welford(mean.data_ptr(), m2.data_ptr(), n.data_ptr(), block_sum.data_ptr(),
+                                     block_sumsq.data_ptr(), int(block_n), Cn, _stream()))
+
+
+def dataset_widen(src, extra, out=None):
+    """[T, ..., Ct + K] fp16 from src [T, ..., Ct] and extra [T, K] fp16 (see gcl_dataset_widen)."""
+    T, n_lon, n_lat, Ct = _series_shape(src)
+    assert extra.is_cuda and extra.dtype == torch.float16 and extra.is_contiguous() and extra.dim() == 2
+    assert extra.shape[0] == T and extra.shape[1] >= 1
+    Cn = Ct + extra.shape[1]
+    if out is None:
+        out = torch.empty(*src.shape[:-1], Cn, dtype=torch.float16, device=src.device)
+    assert out.is_cuda and out.dtype == torch.float16 and out.is_contiguous() and out.shape == (*src.shape[:-1], Cn)
+    _check(lib().gcl_dataset_widen(src.data_ptr(), T, n_lon, n_lat, Ct, extra.data_ptr(), Cn, out.data_ptr(), _stream()))
     return out

@@ -985,6 +985,49 @@ int gcl_live_region_stats(const float* pred, int64_t bs, int64_t gs, int64_t ss,
                           const int32_t* chans, const float* offs, int32_t nc, int32_t S, double* out, int32_t B,
                           gcl_stream_t stream);
 
+/* ---- Building, repairing and extending datasets (csrc/dataset.hip) ----
+ * The arithmetic core of scripts/build_dataset_512x256.py, recompute_wb2_scalers.py, repair_dataset.py,
+ * add_time_features.py and check_23f_data.py on the fp16 series (T, n_lon, n_lat, Ct) in device memory; n_lat = 1 is
+ * the flat (T, N, Ct) layout.  No entry point allocates or synchronises; offsets are int64; no floating-point atomics;
+ * every reduction has two stages with a fixed order (a block's share of the data and the order of the partial records
+ * follow from the shapes alone), so a result depends only on the data and the shapes.  `ws` is a device scratch buffer
+ * of at least gcl_dataset_ws_bytes(Ct) bytes, the caller's until the call has run. */
+size_t gcl_dataset_ws_bytes(int32_t C);
+/* The most sources one gcl_dataset_pack call takes (they travel in the kernel arguments). */
+int gcl_dataset_max_sources(void);
+/* One time block into the series, with the block's sums (scripts/build_dataset_512x256.py:288-324, the repair of
+ * scripts/repair_dataset.py:163-184, and with series == NULL the statistics alone of
+ * scripts/recompute_wb2_scalers.py:71-79).  src / tstride / chan / scale are HOST arrays of nsrc entries: src[j] a
+ * device float32 plane [nt, P], P = n_lon * n_lat in (time, lon, lat) order, whose time steps are tstride[j] elements
+ * apart (0: a time-invariant field, the expand_dims of :159-166 without the copy).  v = x * scale[j] rounded to float32
+ * on its own (numpy's `arr *= 0.01`; 1.0f leaves the bits), series[t0 + t, p, chan[j]] = fp16(v) round to nearest even
+ * (overflow to +-inf, subnormals kept: ndarray.astype(np.float16)), sum[chan[j]] = sum of (double)v and sumsq[chan[j]]
+ * = sum of (double)(float)(v * v) - the square rounded to float32 first, as (arr * arr).sum(dtype=np.float64) has it.
+ * NaN and inf reach the sums as in numpy.  Channels are distinct.  With all Ct channels listed the block is one
+ * contiguous span, staged through LDS and written with 16-byte stores; with fewer, the bytes of the other channels and
+ * their entries of sum / sumsq are not touched. */
+int gcl_dataset_pack(const float* const* src, const int64_t* tstride, const int32_t* chan, const float* scale,
+                     int32_t nsrc, int32_t nt, int32_t n_lon, int32_t n_lat, uint16_t* series, int64_t T, int32_t Ct,
+                     int64_t t0, double* sum, double* sumsq, void* ws, size_t ws_bytes, gcl_stream_t stream);
+/* Per-channel statistics of rows [t_s, t_e) of a series (the resume pass scripts/build_dataset_512x256.py:238-253,
+ * the good channels of scripts/repair_dataset.py:142-147, the scaler pass of scripts/add_time_features.py:111-121, the
+ * printouts of scripts/check_23f_data.py): sum and sumsq of v = (float)h by the rounding rule of gcl_dataset_pack,
+ * vmin / vmax over the finite values (+inf / -inf when there is none), and the counts of NaN and of +-inf.  flags
+ * bit 0: NaN counts as 0 in the sums, bit 1: +-inf does (repair_dataset.py:144 sets both); the counts and min / max do
+ * not depend on the flags. */
+int gcl_dataset_stats(const uint16_t* series, int64_t T, int32_t n_lon, int32_t n_lat, int32_t Ct, int64_t t_s,
+                      int64_t t_e, int32_t flags, double* sum, double* sumsq, float* vmin, float* vmax,
+                      int64_t* n_nan, int64_t* n_inf, void* ws, size_t ws_bytes, gcl_stream_t stream);
+/* welford_update (scripts/build_dataset_512x256.py:126-136) for C channels, state mean[C], m2[C] and *n on the
+ * device, block_sum / block_sumsq device arrays (what the two entry points above leave): the operations of the numpy
+ * expression in its order, each rounded alone in float64.  One thread per channel. */
+int gcl_dataset_welford(double* mean, double* m2, int64_t* n, const double* block_sum, const double* block_sumsq,
+                        int64_t block_n, int32_t C, gcl_stream_t stream);
+/* dst (T, P, Ct_new) from src (T, P, Ct_old): the old channels bit for bit, channel Ct_old + k of every point of
+ * time step t = extra[t, k] (fp16 bits, [T, Ct_new - Ct_old]) - scripts/add_time_features.py:94-101. */
+int gcl_dataset_widen(const uint16_t* src, int64_t T, int32_t n_lon, int32_t n_lat, int32_t Ct_old,
+                      const uint16_t* extra, int32_t Ct_new, uint16_t* dst, gcl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
