@@ -198,6 +198,11 @@ _SIGNATURES = {
                                     _vp]),
     "gcl_dataset_welford": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp]),
     "gcl_dataset_widen": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, _i32, _vp, _vp]),
+    "gcl_wrf_sample": (C.c_int, [_vp, _i32, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp]),
+    "gcl_wrf_scores_ws_bytes": (_sz, [_i32, _i32]),
+    "gcl_wrf_scores": (C.c_int, [_vp, _i32, _i64, _vp, _vp, _vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32,
+                                 _vp, _i64, _vp, _i32, _vp, _vp, _sz, _vp]),
+    "gcl_wrf_box_means": (C.c_int, [_vp, _i64, _i64, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _i64, _vp, _i64, _vp]),
 }
 
 
@@ -1761,4 +1766,165 @@ def dataset_widen(src, extra, out=None):
         out = torch.empty(*src.shape[:-1], Cn, dtype=torch.float16, device=src.device)
     assert out.is_cuda and out.dtype == torch.float16 and out.is_contiguous() and out.shape == (*src.shape[:-1], Cn)
     _check(lib().gcl_dataset_widen(src.data_ptr(), T, n_lon, n_lat, Ct, extra.data_ptr(), Cn, out.data_ptr(), _stream()))
+    return out
+
+
+WRF_POINT, WRF_SRC0, WRF_SRC1, WRF_POINT64, WRF_CONVERT = 0, 1, 2, 3, 4  # side kinds of a gcl_wrf_scores job
+
+
+class WrfSource:
+    """A source of grid fields for gcl_wrf_sample / gcl_wrf_scores: `values` a float32 or fp16 GPU tensor read in place,
+    `node_stride` the elements between two nodes of a field, `n_nodes` the nodes of a field, pos int32 / w float64
+    [P, 4] its point table on the GPU (from wrf.wrf_point_tables: every position below n_nodes, negative = outside)."""
+
+    def __init__(self, values, node_stride: int, n_nodes: int, pos, w):
+        if not values.is_cuda or values.dtype not in (torch.float32, torch.float16):
+            raise RuntimeError("libgcl_hip needs float32 or fp16 GPU tensors as WRF sources (there is no CPU fallback)")
+        if pos.dim() != 2 or pos.shape[1] != 4 or w.shape != pos.shape:
+            raise ValueError(f"WrfSource: point table of shapes {tuple(pos.shape)} / {tuple(w.shape)}, expected [P, 4]")
+        if node_stride < 1 or n_nodes < 1:
+            raise ValueError(f"WrfSource: node stride {node_stride}, {n_nodes} nodes")
+        self.values, self.node_stride, self.n_nodes, self.pos, self.w = values, int(node_stride), int(n_nodes), pos, w
+        self.half = int(values.dtype == torch.float16)
+        self.P = int(pos.shape[0])
+
+    def check_offsets(self, offs, what: str):
+        """Every field at the element offsets `offs` (host ints) lies inside the storage of `values`."""
+        if len(offs) and (min(offs) < 0 or max(offs) + (self.n_nodes - 1) * self.node_stride >= _room(self.values)):
+            raise ValueError(f"{what}: a field offset in [{min(offs)}, {max(offs)}] with node stride {self.node_stride} "
+                             f"and {self.n_nodes} nodes leaves the source buffer")
+
+    def args(self):
+        return (self.values.data_ptr(), self.half, self.node_stride, _pi(self.pos), _pd(self.w))
+
+
+def wrf_sample(source: WrfSource, field_off, field_off_dev=None, mul=None, add=None, out=None):
+    """float64 [nf, P]: the fields of `source` at the element offsets field_off (host ints) on its point table, NaN
+    outside the source axes (see gcl_wrf_sample).  mul / add: float32 [nf] GPU tensors (both or neither), the
+    conversion applied to every source value first.  field_off_dev: the same offsets as an int64 GPU tensor, for a
+    caller that keeps them there."""
+    offs = [int(o) for o in field_off]
+    nf = len(offs)
+    if nf == 0:
+        raise ValueError("wrf_sample: no fields listed")
+    source.check_offsets(offs, "wrf_sample")
+    if (mul is None) != (add is None):
+        raise ValueError("wrf_sample: mul and add go together")
+    dev = source.values.device
+    if field_off_dev is None:
+        field_off_dev = torch.tensor(offs, dtype=torch.int64, device=dev)
+    assert field_off_dev.is_cuda and field_off_dev.dtype == torch.int64 and field_off_dev.numel() == nf
+    if mul is not None:
+        assert mul.numel() == nf and add.numel() == nf and mul.is_contiguous() and add.is_contiguous()
+    if out is None:
+        out = torch.empty(nf, source.P, dtype=torch.float64, device=dev)
+    assert out.shape == (nf, source.P) and out.is_contiguous()
+    _check(lib().gcl_wrf_sample(*source.args()[:3], field_off_dev.data_ptr(), _p(mul), _p(add), nf, *source.args()[3:],
+                                source.P, _pd(out), _stream()))
+    return out
+
+
+def wrf_scores(P: int, jobs, conv, jobs_dev=None, conv_dev=None, src0=None, src1=None, pts=None, pts64=None, slots=None,
+               offsets=None, target: int = 0, filled=None, accumulate: bool = False, out=None, validated: bool = False):
+    """float64 [S, 6] = n, sum d, sum d^2, sum |d|, sum a, sum b of the NaN-masked pairs of every job (see
+    gcl_wrf_scores).  pts float32 / pts64 float64: the arenas of the point fields.  jobs: host rows (kind a, offset a,
+    kind b, offset b, gated, delta), conv: host rows (mul a, add a, mul b, add b); every offset is checked here against the side's buffer.  jobs_dev / conv_dev: the same tables on the
+    GPU (int64 [J, 6] / float32 [J, 4]) for a caller that keeps them there.  slots: S (default J: one slot per job);
+    offsets int64 [J / S] and filled int32 [S] on the GPU serve the gated jobs.  validated: the caller has checked this
+    job table against these buffers already (a table it reuses every step)."""
+    J = len(jobs)
+    if J == 0 or len(conv) != J:
+        raise ValueError(f"wrf_scores: {J} jobs, {len(conv)} conversion rows")
+    S = J if slots is None else int(slots)
+    if S < 1 or J % S:
+        raise ValueError(f"wrf_scores: {J} jobs do not fill {S} slots evenly")
+    srcs = (src0, src1)
+    by_side = {0: [], 1: [], 2: [], 3: []}
+    gated = validated and offsets is not None
+    for row in ([] if validated else jobs):
+        if len(row) != 6:
+            raise ValueError("wrf_scores: a job is (kind a, offset a, kind b, offset b, gated, delta)")
+        for kind, off in ((row[0], row[1]), (row[2], row[3])):
+            if not 0 <= int(kind) < 8:
+                raise ValueError(f"wrf_scores: unknown side kind {kind}")
+            by_side[int(kind) & 3].append(int(off))
+        gated = gated or bool(row[4])
+    for k in (1, 2):
+        if by_side[k]:
+            if srcs[k - 1] is None:
+                raise ValueError(f"wrf_scores: a job reads source {k - 1}, which is not given")
+            if srcs[k - 1].P != P:
+                raise ValueError(f"wrf_scores: source {k - 1} has a table of {srcs[k - 1].P} points, the jobs {P}")
+            srcs[k - 1].check_offsets(by_side[k], f"wrf_scores source {k - 1}")
+    if by_side[0]:
+        if pts is None:
+            raise ValueError("wrf_scores: a job reads a point field, and pts is not given")
+        assert pts.is_contiguous()
+        if min(by_side[0]) < 0 or max(by_side[0]) + P > pts.numel():
+            raise ValueError(f"wrf_scores: a point field of {P} values leaves pts ({pts.numel()} values)")
+    if by_side[3]:
+        if pts64 is None:
+            raise ValueError("wrf_scores: a job reads a float64 point field, and pts64 is not given")
+        if min(by_side[3]) < 0 or max(by_side[3]) + P > pts64.numel():
+            raise ValueError(f"wrf_scores: a point field of {P} values leaves pts64 ({pts64.numel()} values)")
+    if gated:
+        if offsets is None or filled is None:
+            raise ValueError("wrf_scores: gated jobs need offsets and filled")
+        assert offsets.is_cuda and offsets.dtype == torch.int64 and offsets.is_contiguous() and offsets.numel() == J // S
+        assert filled.is_cuda and filled.dtype == torch.int32 and filled.is_contiguous() and filled.numel() == S
+    dev = next(t for t in (pts, pts64, src0 and src0.values, src1 and src1.values) if t is not None).device
+    if jobs_dev is None:
+        jobs_dev = torch.tensor([[int(v) for v in r] for r in jobs], dtype=torch.int64, device=dev)
+        conv_dev = torch.tensor([[float(v) for v in r] for r in conv], dtype=torch.float32, device=dev)
+    assert jobs_dev.is_cuda and jobs_dev.dtype == torch.int64 and jobs_dev.shape == (J, 6) and jobs_dev.is_contiguous()
+    assert conv_dev.is_cuda and conv_dev.dtype == torch.float32 and conv_dev.shape == (J, 4) and conv_dev.is_contiguous()
+    if out is None:
+        if accumulate:
+            raise ValueError("wrf_scores: accumulate needs the state to add to")
+        out = torch.empty(S, 6, dtype=torch.float64, device=dev)
+    assert out.numel() == S * 6 and out.is_contiguous()
+    nbytes = int(lib().gcl_wrf_scores_ws_bytes(J, int(P)))
+    ws = workspace(nbytes, dev)
+    none = (None, 0, 0, None, None)
+    _check(lib().gcl_wrf_scores(*(src0.args() if src0 is not None else none),
+                                *(src1.args() if src1 is not None else none), _p(pts),
+                                _pd(pts64) if pts64 is not None else None, jobs_dev.data_ptr(),
+                                _p(conv_dev), J, S, int(P), offsets.data_ptr() if gated else None, int(target),
+                                _pi(filled) if gated else None, int(bool(accumulate)), _pd(out), ws.data_ptr(),
+                                ws.numel(), _stream()))
+    return out
+
+
+def wrf_box_means(x3, rows, n_rows_total: int, std, mean, out=None, count=None, validated: bool = False):
+    """float32 [B, K]: the mean over the listed rows of x3[s, rows[r], k] * std[k % C] + mean[k % C] in numpy's float32
+    order (see gcl_wrf_box_means).  x3 float32 [B, G, K] with unit column stride; rows int32 on the GPU; std / mean
+    float32 [C] on the GPU, K a multiple of C.  With `count` (int64 [1] on the GPU) the rows go to out[count + s] of an
+    out [cap, K]; rows past cap are dropped.  rows are checked against G here, which reads them back (one
+    synchronise); a caller that built them from host data it has checked passes validated=True."""
+    assert x3.dim() == 3 and x3.stride(2) == 1
+    B, G, K = x3.shape
+    R, Cc = rows.numel(), std.numel()
+    if R == 0:
+        raise ValueError("wrf_box_means: empty row list (the mean of no rows is undefined)")
+    if Cc == 0 or K % Cc or mean.numel() != Cc:
+        raise ValueError(f"wrf_box_means: {K} columns and scalers of {Cc} / {mean.numel()} channels")
+    if G != n_rows_total:
+        raise ValueError(f"wrf_box_means: the batch has {G} rows, the row list was made for {n_rows_total}")
+    if not validated:
+        r = rows.cpu()
+        if int(r.min()) < 0 or int(r.max()) >= G:
+            raise ValueError(f"wrf_box_means: a row index lies outside the {G} nodes")
+    assert std.is_contiguous() and mean.is_contiguous()
+    if out is None:
+        if count is not None:
+            raise ValueError("wrf_box_means: count needs the state to write to")
+        out = torch.empty(B, K, dtype=torch.float32, device=x3.device)
+    assert out.dim() == 2 and out.shape[1] == K and out.stride(1) == 1 and out.dtype == torch.float32 and out.is_cuda
+    if count is None and out.shape[0] < B:
+        raise ValueError(f"wrf_box_means: out has {out.shape[0]} rows for {B} samples")
+    if count is not None:
+        assert count.is_cuda and count.dtype == torch.int64 and count.numel() == 1
+    _check(lib().gcl_wrf_box_means(_p(x3), x3.stride(0), x3.stride(1), _pi(rows), R, _p(std), _p(mean), Cc, K, B,
+                                   out.data_ptr(), out.stride(0), count.data_ptr() if count is not None else None,
+                                   out.shape[0], _stream()))
     return out

@@ -92,3 +92,33 @@ class CapturedRollout(Captured):
     @torch.no_grad()
     def __call__(self, X: torch.Tensor, y: Optional[torch.Tensor] = None) -> torch.Tensor:
         return self._forecast(X, y)
+
+
+PREDICTION_KEYS = ("predictions", "ground_truth", "n_features", "ar_steps", "obs_window", "n_lon", "n_lat",
+                   "sample_offsets", "data_dir")
+
+
+def save_predictions(path, preds: torch.Tensor, truth: torch.Tensor, n_features: int, ar_steps: int, obs_window: int,
+                     n_lon: int, n_lat: int, sample_offsets=None, data_dir="") -> dict:
+    """Write the `predictions.pt` bundle of scripts/predict.py:617-631: normalised forecasts and truth [N, G, C * P] as
+    host tensors plus the integers and strings the comparison scripts read back.  sample_offsets: the temporal offset
+    of every sample (default 0 .. N-1).  Returns the dictionary written."""
+    if preds.dim() != 3 or preds.shape != truth.shape:
+        raise ValueError(f"save_predictions: predictions {tuple(preds.shape)} and truth {tuple(truth.shape)}, expected "
+                         "two [N, G, C * P]")
+    if preds.shape[2] != int(n_features) * int(ar_steps):
+        raise ValueError(f"save_predictions: {preds.shape[2]} columns are not {n_features} features x {ar_steps} steps")
+    offsets = list(range(preds.shape[0])) if sample_offsets is None else [int(o) for o in sample_offsets]
+    if len(offsets) != preds.shape[0]:
+        raise ValueError(f"save_predictions: {len(offsets)} offsets for {preds.shape[0]} samples")
+    bundle = {"predictions": preds.detach().cpu(), "ground_truth": truth.detach().cpu(), "n_features": int(n_features),
+              "ar_steps": int(ar_steps), "obs_window": int(obs_window), "n_lon": int(n_lon), "n_lat": int(n_lat),
+              "sample_offsets": offsets, "data_dir": str(data_dir)}
+    torch.save(bundle, str(path))
+    return bundle
+
+
+def load_predictions(path):
+    """What `save_predictions` (or the reference's predict.py) wrote, on the host: the dictionary, or the bare tensor
+    of the legacy form."""
+    return torch.load(str(path), map_location="cpu", weights_only=True)

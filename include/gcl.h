@@ -1028,6 +1028,51 @@ int gcl_dataset_welford(double* mean, double* m2, int64_t* n, const double* bloc
 int gcl_dataset_widen(const uint16_t* src, int64_t T, int32_t n_lon, int32_t n_lat, int32_t Ct_old,
                       const uint16_t* extra, int32_t Ct_new, uint16_t* dst, gcl_stream_t stream);
 
+/* ---- The WRF benchmark (csrc/wrf.hip; scripts/compare_wrf_era5.py, scripts/compare_wrf.py) ----
+ * No entry point allocates or synchronises; no floating-point atomics; every reduction has a fixed order, so a result
+ * has the same bits on every run.  A point table is pos int32 [P, 4] / w float64 [P, 4]: per WRF point the node numbers
+ * of the corners (lon, lat), (lon, lat+1), (lon+1, lat), (lon+1, lat+1) of its source cell and their weights
+ * (1 * w_lon) * w_lat; pos[4 i] < 0 marks a point outside the source axes.  A source is float32 (half = 0) or fp16
+ * (half = 1, widened exactly); node p of the field at element offset `off` is read at off + p * node_stride, so a
+ * channel of a (T, n_lon, n_lat, C) series and a column of an [n, G, P * C] forecast are read in place.  The caller
+ * guarantees that every position lies inside its field.
+ *
+ * interpolate_era5_to_wrf (compare_wrf_era5.py:127-152) for nf fields: out [nf, P] float64, out[f, i] = the four
+ * products (double)v_k * w_k, each rounded on its own, added in corner order onto 0.0 - scipy's
+ * RegularGridInterpolator on float32 values - or NaN outside (bounds_error=False, fill_value=nan).  With mul / add
+ * (device float32 [nf], both or neither) v = x * mul[f], then v + add[f], each rounded in float32 first: the
+ * denormalisation of compare_wrf.py:162.  field_off: device int64 [nf]. */
+int gcl_wrf_sample(const void* src, int32_t half, int64_t node_stride, const int64_t* field_off, const float* mul,
+                   const float* add, int32_t nf, const int32_t* pos, const double* w, int32_t P, double* out,
+                   gcl_stream_t stream);
+/* compute_metrics (compare_wrf_era5.py:155-164) for J jobs over the same P points, nothing sampled being stored.
+ * jobs: device int64 [J, 6] = kind a, offset a, kind b, offset b, gated, delta; conv: device float32 [J, 4] = mul a,
+ * add a, mul b, add b.  kind & 3: 0 = a point field pts[offset + i] (float32; with kind & 4 times mul, rounded in
+ * float32: WRF psfc_Pa * 0.01, :247), 1 / 2 = a field of source 0 / 1 at that element offset, sampled as
+ * gcl_wrf_sample samples it (kind & 4: with the conversion), 3 = a float64 point field pts64[offset + i] as it is
+ * (a field gcl_wrf_sample left).  d = a - b in float64 over the points where neither side
+ * is NaN (infinities stay, as in the reference); a job yields {n, sum d, sum d^2, sum |d|, sum a, sum b}: 256 points
+ * per block combined in a fixed order, the blocks of a job added in order.  The J jobs fill S slots, job j slot j % S
+ * (J = S * samples): stats [S, 6] float64 = (accumulate ? stats : 0) + the slot's jobs in job order.  A gated job
+ * counts only when offsets[j / S] (device int64, one per sample) == target + delta and filled[slot] (device int32 [S])
+ * is still 0, which it then sets: the first sample at that offset (compare_wrf.py:670-681).  offsets / filled may be
+ * NULL when no job is gated.  ws: at least gcl_wrf_scores_ws_bytes(J, P) bytes of device scratch. */
+size_t gcl_wrf_scores_ws_bytes(int32_t J, int32_t P);
+int gcl_wrf_scores(const void* src0, int32_t half0, int64_t stride0, const int32_t* pos0, const double* w0,
+                   const void* src1, int32_t half1, int64_t stride1, const int32_t* pos1, const double* w1,
+                   const float* pts, const double* pts64, const int64_t* jobs, const float* conv, int32_t J,
+                   int32_t S, int32_t P, const int64_t* offsets, int64_t target, int32_t* filled, int32_t accumulate,
+                   double* stats, void* ws, size_t ws_bytes, gcl_stream_t stream);
+/* pred_region.mean(axis=1) of compare_wrf.py:160-170, :202-203, :385-386: out[first + s, k], k < K = P * C, = the
+ * float32 sum over the R listed rows in their listed order of x[s, rows[r], k] * stdv[k % C] + mean[k % C] (product
+ * and sum rounded separately, no FMA), divided by (float)R - the order of numpy's float32 reduction over a non-last
+ * axis.  x float32 with unit column stride and element strides bs, gs; out rows ldo apart; first = *count (device
+ * int64) or 0 when count is NULL; rows at or past `cap` are not written.  One thread per (s, k).  R == 0 is an
+ * argument error.  The caller guarantees 0 <= rows[r] < G. */
+int gcl_wrf_box_means(const float* x, int64_t bs, int64_t gs, const int32_t* rows, int32_t R, const float* stdv,
+                      const float* mean, int32_t C, int32_t K, int32_t B, float* out, int64_t ldo,
+                      const int64_t* count, int64_t cap, gcl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
