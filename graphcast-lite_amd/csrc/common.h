@@ -117,6 +117,51 @@ __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast
 __device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
 __device__ __forceinline__ float4 add4(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
 
+// Contiguous spans of fp16 values that start off a 16-byte boundary (the dataset and downscaler kernels stage a tile in
+// LDS and move it with these).  kThreads is the block size of the calling kernel, which every thread of the block
+// enters: the body is dealt over kThreads threads, the head goes to threads 0 .. 6 and the tail to threads 64 .. 70
+// (another wave than the head's), so a block needs two waves.
+// n halves from get(k) to dst, which may start anywhere: the 16-byte aligned body as 16-byte stores, the at most seven
+// halves either side of it one by one.
+template <int kThreads, class Get>
+__device__ __forceinline__ void store_span(uint16_t* dst, int n, Get get) {
+  static_assert(kThreads >= 128 && kThreads % 64 == 0, "store_span: whole waves, and the tail goes to the second");
+  const int tid = threadIdx.x;
+  int head = (int)(((16 - (reinterpret_cast<uintptr_t>(dst) & 15)) & 15) >> 1);
+  head = head < n ? head : n;
+  const int nvec = (n - head) >> 3;
+  for (int i = tid; i < nvec; i += kThreads) {
+    const int k = head + 8 * i;
+    union { uint4 q; uint16_t h[8]; } u;
+#pragma unroll
+    for (int m = 0; m < 8; ++m) u.h[m] = get(k + m);
+    *reinterpret_cast<uint4*>(dst + k) = u.q;
+  }
+  const int done = head + 8 * nvec;
+  if (tid < head) dst[tid] = get(tid);
+  if (tid >= 64 && tid - 64 < n - done) dst[done + tid - 64] = get(done + tid - 64);
+}
+
+// n halves from src (any alignment) into lds[0 .. n), 16-byte loads over the aligned body
+template <int kThreads>
+__device__ __forceinline__ void load_span(const uint16_t* __restrict__ src, int n, uint16_t* lds) {
+  static_assert(kThreads >= 128 && kThreads % 64 == 0, "load_span: whole waves, and the tail goes to the second");
+  const int tid = threadIdx.x;
+  int head = (int)(((16 - (reinterpret_cast<uintptr_t>(src) & 15)) & 15) >> 1);
+  head = head < n ? head : n;
+  const int nvec = (n - head) >> 3;
+  for (int i = tid; i < nvec; i += kThreads) {
+    const int k = head + 8 * i;
+    union { uint4 q; uint16_t h[8]; } u;
+    u.q = *reinterpret_cast<const uint4*>(src + k);
+#pragma unroll
+    for (int m = 0; m < 8; ++m) lds[k + m] = u.h[m];
+  }
+  const int done = head + 8 * nvec;
+  if (tid < head) lds[tid] = src[tid];
+  if (tid >= 64 && tid - 64 < n - done) lds[done + tid - 64] = src[done + tid - 64];
+}
+
 // One element of torch.optim.Adam (no amsgrad, no maximize), src/main.py:212: the update of gcl_adam_step and
 // gcl_adam_step_groups, written once so that both round identically.  hipcc may contract a product into the add that
 // follows it, and does so differently in a scalar and a float4 loop; `rounded` pins every product so that no

@@ -5,7 +5,9 @@
 // depends only on the data and the shapes.
 #include "common.h"
 
+using gcl::load_span;
 using gcl::rounded;
+using gcl::store_span;
 using gcl::wave_sum;
 
 namespace {
@@ -14,44 +16,6 @@ constexpr int kMaxSrc = 32;    // sources of one pack call (they travel in the k
 constexpr int kTile = 512;     // points of one pack tile: 512 * Ct halves are staged in LDS
 constexpr int kBlocks = 2048;  // most blocks of a reducing kernel = partial records of its second stage
 constexpr int kStatQ = 6;      // sum, sumsq, min, max, #NaN, #inf
-
-// n halves from get(k) to dst, which may start anywhere: the 16-byte aligned body as 16-byte stores, the at most seven
-// halves either side of it one by one.
-template <class Get>
-__device__ __forceinline__ void store_span(uint16_t* dst, int n, Get get) {
-  const int tid = threadIdx.x;
-  int head = (int)(((16 - (reinterpret_cast<uintptr_t>(dst) & 15)) & 15) >> 1);
-  head = head < n ? head : n;
-  const int nvec = (n - head) >> 3;
-  for (int i = tid; i < nvec; i += 256) {
-    const int k = head + 8 * i;
-    union { uint4 q; uint16_t h[8]; } u;
-#pragma unroll
-    for (int m = 0; m < 8; ++m) u.h[m] = get(k + m);
-    *reinterpret_cast<uint4*>(dst + k) = u.q;
-  }
-  const int done = head + 8 * nvec;
-  if (tid < head) dst[tid] = get(tid);
-  if (tid >= 64 && tid - 64 < n - done) dst[done + tid - 64] = get(done + tid - 64);
-}
-
-// n halves from src (any alignment) into lds[0 .. n), 16-byte loads over the aligned body
-__device__ __forceinline__ void load_span(const uint16_t* __restrict__ src, int n, uint16_t* lds) {
-  const int tid = threadIdx.x;
-  int head = (int)(((16 - (reinterpret_cast<uintptr_t>(src) & 15)) & 15) >> 1);
-  head = head < n ? head : n;
-  const int nvec = (n - head) >> 3;
-  for (int i = tid; i < nvec; i += 256) {
-    const int k = head + 8 * i;
-    union { uint4 q; uint16_t h[8]; } u;
-    u.q = *reinterpret_cast<const uint4*>(src + k);
-#pragma unroll
-    for (int m = 0; m < 8; ++m) lds[k + m] = u.h[m];
-  }
-  const int done = head + 8 * nvec;
-  if (tid < head) lds[tid] = src[tid];
-  if (tid >= 64 && tid - 64 < n - done) lds[done + tid - 64] = src[done + tid - 64];
-}
 
 // ---- pack ------------------------------------------------------------------------------------------------------------
 struct PackArgs {
@@ -148,7 +112,7 @@ __global__ __launch_bounds__(256) void dataset_pack_kernel(PackArgs a) {
     }
     if (a.series && a.full) {
       __syncthreads();
-      store_span(a.series + row0, np * a.Ct, [&](int k) { return stage[k]; });
+      store_span<256>(a.series + row0, np * a.Ct, [&](int k) { return stage[k]; });
       __syncthreads();
     }
   }
@@ -313,10 +277,10 @@ __global__ __launch_bounds__(256) void dataset_widen_kernel(const uint16_t* __re
     const int64_t t = tl / tiles_per_t;
     const int64_t p0 = (tl - t * tiles_per_t) * tile;
     const int np = (int)((P - p0) < tile ? (P - p0) : tile);
-    load_span(src + (t * P + p0) * Co, np * Co, stage);
+    load_span<256>(src + (t * P + p0) * Co, np * Co, stage);
     __syncthreads();
     const uint16_t* ex = extra + t * (Cn - Co);
-    store_span(dst + (t * P + p0) * Cn, np * Cn, [&](int k) {
+    store_span<256>(dst + (t * P + p0) * Cn, np * Cn, [&](int k) {
       const int p = k / Cn, c = k - p * Cn;
       return c < Co ? stage[p * Co + c] : ex[c - Co];
     });

@@ -203,6 +203,13 @@ _SIGNATURES = {
     "gcl_wrf_scores": (C.c_int, [_vp, _i32, _i64, _vp, _vp, _vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32,
                                  _vp, _i64, _vp, _i32, _vp, _vp, _sz, _vp]),
     "gcl_wrf_box_means": (C.c_int, [_vp, _i64, _i64, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _i64, _vp, _i64, _vp]),
+    "gcl_downscale_coarse": (C.c_int, [_vp, _i64, _i64, _i32, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _vp]),
+    "gcl_downscale_pred": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp,
+                                     _i64, _vp]),
+    "gcl_downscale_batch": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp,
+                                      _vp, _f32, _vp, _vp, _vp]),
+    "gcl_downscale_ws_bytes": (_sz, [_i32]),
+    "gcl_downscale_pair_mse": (C.c_int, [_vp, _vp, _i64, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 
@@ -1927,4 +1934,116 @@ def wrf_box_means(x3, rows, n_rows_total: int, std, mean, out=None, count=None, 
     _check(lib().gcl_wrf_box_means(_p(x3), x3.stride(0), x3.stride(1), _pi(rows), R, _p(std), _p(mean), Cc, K, B,
                                    out.data_ptr(), out.stride(0), count.data_ptr() if count is not None else None,
                                    out.shape[0], _stream()))
+    return out
+
+
+def _ph(t):
+    assert t.is_cuda and t.dtype == torch.float16 and t.is_contiguous()
+    return t.data_ptr()
+
+
+def _pl(t):
+    assert t.is_cuda and t.dtype == torch.int64 and t.is_contiguous()
+    return t.data_ptr()
+
+
+def _point_table(pos, w, who: str):
+    """P of a device point table pos int32 [P, 4] / w float64 [P, 4]."""
+    if pos.dim() != 2 or pos.shape[1] != 4 or tuple(w.shape) != tuple(pos.shape) or pos.shape[0] == 0:
+        raise ValueError(f"{who}: a point table is pos int32 [P, 4] and w float64 [P, 4] with P > 0")
+    _pi(pos), _pd(w)
+    return pos.shape[0]
+
+
+def downscale_coarse(series, pos, w, t0: int, nt: int, out, to0: int):
+    """Frames [t0, t0 + nt) of the fp16 `series` [T, N, C] (or [T, lon, lat, C]) through the point table onto frames
+    [to0, to0 + nt) of the fp16 archive `out` [T_out, P, C] (or [T_out, lon, lat, C]); pos / w None: the frames are
+    copied (see gcl_downscale_coarse).  The table's positions must lie below N (the caller's tables are checked on the
+    host, where they are built)."""
+    _ph(series), _ph(out)
+    T, Cc = series.shape[0], series.shape[-1]
+    N = series.numel() // (T * Cc) if T * Cc else 0
+    T_out = out.shape[0]
+    P = out.numel() // (T_out * Cc) if T_out * Cc else 0
+    if out.shape[-1] != Cc:
+        raise ValueError(f"downscale_coarse: {Cc} channels in, {out.shape[-1]} out")
+    if (pos is None) != (w is None):
+        raise ValueError("downscale_coarse: the positions and the weights of a point table go together")
+    if pos is not None and _point_table(pos, w, "downscale_coarse") != P:
+        raise ValueError(f"downscale_coarse: a table of {pos.shape[0]} points for frames of {P}")
+    _check(lib().gcl_downscale_coarse(series.data_ptr(), T, N, Cc, None if pos is None else pos.data_ptr(),
+                                      None if w is None else w.data_ptr(), P, int(t0), int(nt), out.data_ptr(), T_out,
+                                      int(to0), _stream()))
+    return out
+
+
+def downscale_pred(pred3, pos, w, std, mean, dest, out, last3=None):
+    """The float32 predictions pred3 [B, G, >= C] (unit channel stride; last3 alike: the residual base) through the
+    point table, denormalised, into the frames dest (int64 [B] on the GPU) of the fp16 archive out [T_out, P, C] (see
+    gcl_downscale_pred).  The table's positions must lie below G."""
+    _ph(out)
+    B, G, Cc = pred3.shape[0], pred3.shape[1], out.shape[-1]
+    T_out = out.shape[0]
+    P = _point_table(pos, w, "downscale_pred")
+    if out.numel() != T_out * P * Cc:
+        raise ValueError(f"downscale_pred: an archive of shape {tuple(out.shape)} for a table of {P} points")
+    for x in (pred3,) + ((last3,) if last3 is not None else ()):
+        if x.dim() != 3 or x.stride(2) != 1 or x.shape[2] < Cc or x.shape[:2] != (B, G):
+            raise ValueError(f"downscale_pred: a [B, G, >= {Cc}] tensor with unit channel stride, got {tuple(x.shape)}")
+    if std.numel() != Cc or mean.numel() != Cc or dest.numel() != B:
+        raise ValueError(f"downscale_pred: scalers of {std.numel()} / {mean.numel()} channels for {Cc}, {dest.numel()} "
+                         f"destinations for {B} samples")
+    _check(lib().gcl_downscale_pred(_p(pred3), pred3.stride(0), pred3.stride(1), _p(last3),
+                                    last3.stride(0) if last3 is not None else 0,
+                                    last3.stride(1) if last3 is not None else 0, pos.data_ptr(), w.data_ptr(), P, Cc, B,
+                                    _p(std), _p(mean), _pl(dest), out.data_ptr(), T_out, _stream()))
+    return out
+
+
+def downscale_batch(coarse, fine, t, obs: int, mean, std, static=None, flip=None, neg=None, noise=None,
+                    sigma: float = 0.0, out=None):
+    """(X [B, obs * C + Ns, H, W], Y [B, C, H, W]) float32 of the samples t (int64 [B] on the GPU) from the fp16
+    archives coarse / fine [T, W, H, C] (see gcl_downscale_batch).  static float32 [W, H, Ns]; flip int32 [B]; neg int32
+    [C]; noise float32 [B, obs * C, H, W] with its factor sigma.  out: (X, Y) to fill."""
+    _ph(coarse), _ph(fine)
+    if coarse.dim() != 4 or coarse.shape != fine.shape:
+        raise ValueError(f"downscale_batch: archives of {tuple(coarse.shape)} and {tuple(fine.shape)}")
+    T, W, Hh, Cc = coarse.shape
+    B, Ns = t.numel(), 0 if static is None else static.shape[-1]
+    if static is not None and (tuple(static.shape[:2]) != (W, Hh) or not static.is_contiguous()):
+        raise ValueError(f"downscale_batch: static fields of {tuple(static.shape)} on a grid of {W} x {Hh}")
+    if mean.numel() != Cc or std.numel() != Cc:
+        raise ValueError(f"downscale_batch: scalers of {mean.numel()} / {std.numel()} channels for {Cc}")
+    if flip is not None and flip.numel() != B or neg is not None and neg.numel() != Cc:
+        raise ValueError("downscale_batch: flip is one int32 per sample, neg one per channel")
+    if noise is not None and (tuple(noise.shape) != (B, obs * Cc, Hh, W) or not noise.is_contiguous()):
+        raise ValueError(f"downscale_batch: noise of {tuple(noise.shape)} for {(B, obs * Cc, Hh, W)}")
+    if out is None:
+        out = (torch.empty(B, obs * Cc + Ns, Hh, W, dtype=torch.float32, device=coarse.device),
+               torch.empty(B, Cc, Hh, W, dtype=torch.float32, device=coarse.device))
+    X, Y = out
+    assert X.is_contiguous() and Y.is_contiguous() and tuple(X.shape) == (B, obs * Cc + Ns, Hh, W)
+    assert tuple(Y.shape) == (B, Cc, Hh, W)
+    _check(lib().gcl_downscale_batch(coarse.data_ptr(), fine.data_ptr(), T, W, Hh, Cc, _pl(t), B, int(obs), _p(mean),
+                                     _p(std), _p(static), Ns, _pi(flip), _pi(neg), _p(noise), float(sigma), _p(X), _p(Y),
+                                     _stream()))
+    return X, Y
+
+
+def downscale_pair_mse(a, b, t, mean, std, out=None):
+    """float64 [C, 2] = per channel {elements, sum of d^2} of the normalised difference of the fp16 archives a and b
+    [T, ..., C] over the frames t (int64 on the GPU; see gcl_downscale_pair_mse)."""
+    _ph(a), _ph(b)
+    if a.shape != b.shape or a.dim() < 2:
+        raise ValueError(f"downscale_pair_mse: archives of {tuple(a.shape)} and {tuple(b.shape)}")
+    T, Cc = a.shape[0], a.shape[-1]
+    P = a.numel() // (T * Cc) if T * Cc else 0
+    if mean.numel() != Cc or std.numel() != Cc or t.numel() == 0:
+        raise ValueError(f"downscale_pair_mse: scalers of {mean.numel()} / {std.numel()} channels for {Cc}, "
+                         f"{t.numel()} frames")
+    if out is None:
+        out = torch.empty(Cc, 2, dtype=torch.float64, device=a.device)
+    ws = workspace(lib().gcl_downscale_ws_bytes(Cc), a.device)
+    _check(lib().gcl_downscale_pair_mse(a.data_ptr(), b.data_ptr(), T, P, Cc, _pl(t), t.numel(), _p(mean), _p(std),
+                                        _pd(out), ws.data_ptr(), ws.numel(), _stream()))
     return out

@@ -1073,6 +1073,52 @@ int gcl_wrf_box_means(const float* x, int64_t bs, int64_t gs, const int32_t* row
                       const float* mean, int32_t C, int32_t K, int32_t B, float* out, int64_t ldo,
                       const int64_t* count, int64_t cap, gcl_stream_t stream);
 
+/* ---- The downscaler data layer (csrc/downscale.hip; scripts/build_downscaler_dataset.py,
+ * scripts/generate_gnn_predictions.py, DownscalerDataset and compute_metrics of scripts/train_downscaler.py) ----
+ * No entry point allocates or synchronises; no floating-point atomics; every reduction has a fixed order.  A point
+ * table is pos int32 [P, 4] / w float64 [P, 4] in OUTPUT order (p = j * n_lat_f + i, the lon-first storage): the node
+ * rows of the four corners of a point's source cell and their weights, in the corner order of the interpolator that
+ * is reproduced.  The caller guarantees that every position lies inside its source.  An archive is fp16
+ * (T, n_lon, n_lat, C); a frame is one contiguous span of P * C halves, which may start off a 16-byte boundary.
+ *
+ * build_downscaler_dataset.py:137-157 for frames t0 .. t0 + nt - 1 of `series` (fp16, T frames of N nodes, node
+ * lon * n_lat + lat): out[to0 + t, p, c] = the four corner values widened exactly to float64, each times its weight
+ * (every product rounded on its own, a zero weight included: 0 * inf = NaN), added in corner order onto 0.0, and that
+ * float64 rounded to binary16 ONCE (nearest even, overflow to +-inf, subnormals kept), as
+ * ndarray.astype(np.float16) does.  pos == w == NULL (then P == N): the frames are copied bit for bit (:125-127).
+ * A frame holds fewer than 2^32 halves (N * C), N fewer than 2^31 nodes. */
+int gcl_downscale_coarse(const uint16_t* series, int64_t T, int64_t N, int32_t C, const int32_t* pos, const double* w,
+                         int64_t P, int64_t t0, int64_t nt, uint16_t* out, int64_t T_out, int64_t to0,
+                         gcl_stream_t stream);
+/* generate_gnn_predictions.py:226-254 for B samples: v = pred[b, g, c] (float32, element strides bs / gs, unit
+ * channel stride), with `last` (its own strides lbs / lgs) v = last + pred rounded in float32; the float64 corner
+ * sum of gcl_downscale_coarse over the node rows of the table, rounded to float32; times stdv[c], plus mean[c], each
+ * rounded in float32 (no FMA); rounded to fp16 into out[dest[b], p, c].  dest: device int64 [B]; a sample whose dest is
+ * below 0 or at or past T_out is skipped and its frame keeps its bytes (the t_pred < T rule of :249). */
+int gcl_downscale_pred(const float* pred, int64_t bs, int64_t gs, const float* last, int64_t lbs, int64_t lgs,
+                       const int32_t* pos, const double* w, int64_t P, int32_t C, int32_t B, const float* stdv,
+                       const float* mean, const int64_t* dest, uint16_t* out, int64_t T_out, gcl_stream_t stream);
+/* DownscalerDataset.__getitem__ (train_downscaler.py:137-183) for B samples, t: device int64 [B].  coarse / fine:
+ * archives (T, W = n_lon, H = n_lat, C), C <= 64.  X float32 [B, obs * C + Ns, H, W]: frames t - obs + 1 .. t of
+ * coarse in order, every value (x - mean[c]) / (std[c] + 1e-8f) with the sum, the difference and the quotient each
+ * rounded in float32, then X[b, obs * C + s, h, w] = stat[w, h, s] (float32 [W, H, Ns], as it is; stat NULL when
+ * Ns == 0).  Y float32 [B, C, H, W]: frame t of fine, normalised alike.  flip (device int32 [B] or NULL) != 0 mirrors
+ * X and Y in w, and the channels c with neg[c] != 0 (device int32 [C] or NULL) are negated in every obs frame of X and
+ * in Y; statics are mirrored, not negated.  noise (float32 [B, obs * C, H, W] or NULL): X += noise * sigma, product
+ * and sum rounded in float32.  A sample whose frames do not all lie in [0, T) is left untouched. */
+int gcl_downscale_batch(const uint16_t* coarse, const uint16_t* fine, int64_t T, int32_t W, int32_t H, int32_t C,
+                        const int64_t* t, int32_t B, int32_t obs, const float* mean, const float* stdv, const float* stat,
+                        int32_t Ns, const int32_t* flip, const int32_t* neg, const float* noise, float sigma, float* X,
+                        float* Y, gcl_stream_t stream);
+/* The coarse baseline of compute_metrics (train_downscaler.py:288-305) over the n frames t[i] (device int64; a frame
+ * outside [0, T) is skipped): stats float64 [C, 2] = {number of elements, sum of d^2}, d = xa - xb in float32 on the
+ * normalised values as gcl_downscale_batch forms them, d^2 and the sum in float64.  Two stages in a fixed order: the
+ * bits depend only on the data and the shapes.  ws: at least gcl_downscale_ws_bytes(C) bytes of device scratch. */
+size_t gcl_downscale_ws_bytes(int32_t C);
+int gcl_downscale_pair_mse(const uint16_t* xa, const uint16_t* xb, int64_t T, int64_t P, int32_t C, const int64_t* t,
+                           int32_t n, const float* mean, const float* stdv, double* stats, void* ws, size_t ws_bytes,
+                           gcl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
