@@ -6,7 +6,8 @@ GNN one sample at a time with 19 interpolators per sample, and `DownscalerDatase
 `scripts/train_downscaler.py` pack batches and score the coarse baseline from memmaps.  Here the point tables are
 built once on the host (`verify.find_cells` / `verify.regrid_tables`, the same corner order and weights as scipy's)
 and the arithmetic runs in `csrc/downscale.hip`: `gcl_downscale_coarse`, `gcl_downscale_pred`, `gcl_downscale_batch`
-and `gcl_downscale_pair_mse`.  The U-Net itself is not part of this module.
+and `gcl_downscale_pair_mse`.  The objective, the scores and the training loop (`downscale_train.py`, kernels in
+`csrc/downscale_loss.hip`) are re-exported from here.  The U-Net itself is not part of this module.
 """
 import json
 import os
@@ -19,6 +20,9 @@ import torch
 from . import hip
 from .capture import Captured
 from .data import _upload_fp16
+from .downscale_train import (DownscalerMetrics, compute_metrics, downscaler_loss, downscaler_results,  # noqa: F401
+                              fit_downscaler, gradient_loss, iter_batches, masked_mse_loss, metrics_table,
+                              spectral_loss, train_epoch, validate)
 from .verify import regrid_tables, regrid_tables_latlon
 
 # ======================================================================================================================

@@ -210,6 +210,13 @@ _SIGNATURES = {
                                       _vp, _f32, _vp, _vp, _vp]),
     "gcl_downscale_ws_bytes": (_sz, [_i32]),
     "gcl_downscale_pair_mse": (C.c_int, [_vp, _vp, _i64, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "gcl_downscale_loss_ws_bytes": (_sz, [_i32, _i32, _i32, _i32]),
+    "gcl_downscale_loss_fwd_bwd": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _f32, _vp, _vp, _vp,
+                                             _sz, _vp]),
+    "gcl_downscale_spectral_fwd_bwd": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _i32,
+                                                 _vp, _vp, _vp, _sz, _vp]),
+    "gcl_downscale_metrics": (C.c_int, [_vp, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "gcl_downscale_loss_scale": (C.c_int, [_vp, _vp, _i64, _vp, _vp]),
 }
 
 
@@ -2046,4 +2053,104 @@ def downscale_pair_mse(a, b, t, mean, std, out=None):
     ws = workspace(lib().gcl_downscale_ws_bytes(Cc), a.device)
     _check(lib().gcl_downscale_pair_mse(a.data_ptr(), b.data_ptr(), T, P, Cc, _pl(t), t.numel(), _p(mean), _p(std),
                                         _pd(out), ws.data_ptr(), ws.numel(), _stream()))
+    return out
+
+
+# ---- the downscaler's objective and scores (csrc/downscale_loss.hip) ---------------------------------------------------
+DOWNSCALE_LOSS_MAX_DIM, DOWNSCALE_LOSS_MAX_C = 256, 64
+_twiddles = {}
+
+
+def _twiddle_tables(H: int, W: int, device):
+    """(tw_h float64 [H, 2], tw_w float64 [W, 2]) = (cos, sin)(2 pi k / n) on the device, built once in double."""
+    import numpy as np
+
+    out = []
+    for n in (H, W):
+        key = (n, str(torch.device(device)))
+        t = _twiddles.get(key)
+        if t is None:
+            a = 2.0 * np.pi * np.arange(n, dtype=np.float64) / n
+            t = torch.from_numpy(np.stack([np.cos(a), np.sin(a)], axis=1)).to(device)
+            _twiddles[key] = t
+        out.append(t)
+    return out
+
+
+def downscale_loss_check(out, Y, x_last=None, mask=None, who: str = "downscale_loss"):
+    """(B, C, H, W) of the operands of the downscaler losses, or an error: everything here is decided from shapes,
+    dtypes and devices, before any GPU work."""
+    if out.dim() != 4 or out.shape != Y.shape:
+        raise ValueError(f"{who}: out and target are [B, C, H, W] of one shape, got {tuple(out.shape)} and {tuple(Y.shape)}")
+    B, Cc, Hh, W = (int(v) for v in out.shape)
+    if B < 1 or not (2 <= Hh <= DOWNSCALE_LOSS_MAX_DIM and 2 <= W <= DOWNSCALE_LOSS_MAX_DIM):
+        raise ValueError(f"{who}: a grid of {Hh} x {W} for {B} samples; H and W lie in 2 .. {DOWNSCALE_LOSS_MAX_DIM}")
+    if not 1 <= Cc <= DOWNSCALE_LOSS_MAX_C:
+        raise ValueError(f"{who}: {Cc} channels; at most {DOWNSCALE_LOSS_MAX_C} (the limit of gcl_downscale_batch)")
+    if mask is not None and (mask.dim() != 1 or mask.numel() != Cc):
+        raise ValueError(f"{who}: a channel mask of shape {tuple(mask.shape)} for {Cc} channels")
+    if x_last is not None and (tuple(x_last.shape) != (B, Cc, Hh, W)
+                               or x_last.stride()[1:] != (Hh * W, W, 1) or x_last.stride(0) < Cc * Hh * W):
+        raise ValueError(f"{who}: x_last is a channel slice [B, {Cc}, {Hh}, {W}] of a contiguous X, got shape "
+                         f"{tuple(x_last.shape)} with strides {x_last.stride()}")
+    for t in (out, Y, x_last, mask):
+        _p(t)
+    if not (out.is_contiguous() and Y.is_contiguous()):
+        raise ValueError(f"{who}: out and target must be contiguous")
+    return B, Cc, Hh, W
+
+
+def downscale_loss_fwd_bwd(out, Y, rec, x_last=None, mask=None, mse_weight: float = 1.0, gradient_weight: float = 0.0,
+                           dout=None):
+    """rec[0] = mse and rec[1] = grad (float64 [3] on the GPU; a term whose weight is not > 0 is skipped), and
+    d(mse_weight * mse + gradient_weight * grad) / d out into dout (see gcl_downscale_loss_fwd_bwd)."""
+    B, Cc, Hh, W = downscale_loss_check(out, Y, x_last, mask, "downscale_loss_fwd_bwd")
+    assert dout is None or (dout.is_contiguous() and dout.shape == out.shape)
+    ws = workspace(lib().gcl_downscale_loss_ws_bytes(0, 0, 0, 0), out.device)
+    _check(lib().gcl_downscale_loss_fwd_bwd(_p(out), _p(x_last), x_last.stride(0) if x_last is not None else 0, _p(Y),
+                                            _p(mask), B, Cc, Hh, W, float(mse_weight), float(gradient_weight), _pd(rec),
+                                            _p(dout), ws.data_ptr(), ws.numel(), _stream()))
+    return rec
+
+
+def downscale_spectral_fwd_bwd(out, Y, rec, x_last=None, mask=None, spectral_weight: float = 1.0, dout=None,
+                               accumulate: bool = False):
+    """rec[2] = spec, and spectral_weight * d spec / d out added to (accumulate) or stored in dout (see
+    gcl_downscale_spectral_fwd_bwd)."""
+    B, Cc, Hh, W = downscale_loss_check(out, Y, x_last, mask, "downscale_spectral_fwd_bwd")
+    assert dout is None or (dout.is_contiguous() and dout.shape == out.shape)
+    tw_h, tw_w = _twiddle_tables(Hh, W, out.device)
+    ws = workspace(lib().gcl_downscale_loss_ws_bytes(B, Cc, Hh, W), out.device)
+    _check(lib().gcl_downscale_spectral_fwd_bwd(_p(out), _p(x_last), x_last.stride(0) if x_last is not None else 0, _p(Y),
+                                                _p(mask), _pd(tw_h), _pd(tw_w), B, Cc, Hh, W, float(spectral_weight),
+                                                1 if accumulate else 0, _pd(rec), _p(dout), ws.data_ptr(), ws.numel(),
+                                                _stream()))
+    return rec
+
+
+def downscale_metrics(out, x_last, Y, residual: bool, state, count):
+    """One batch of compute_metrics: state float64 [C, 2] += the per-batch means of (o - Y)^2 and (x_last - Y)^2, count
+    (int64 [1] on the GPU) += 1 (see gcl_downscale_metrics)."""
+    if out.dim() != 4 or out.shape != Y.shape or x_last.shape != out.shape:
+        raise ValueError(f"downscale_metrics: out, x_last and Y are [B, C, H, W] of one shape, got {tuple(out.shape)}, "
+                         f"{tuple(x_last.shape)} and {tuple(Y.shape)}")
+    B, Cc, Hh, W = (int(v) for v in out.shape)
+    if not 1 <= Cc <= DOWNSCALE_LOSS_MAX_C or B < 1:
+        raise ValueError(f"downscale_metrics: {Cc} channels for {B} samples; at most {DOWNSCALE_LOSS_MAX_C} channels")
+    if x_last.stride()[1:] != (Hh * W, W, 1) or x_last.stride(0) < Cc * Hh * W:
+        raise ValueError(f"downscale_metrics: x_last is a channel slice of a contiguous X, got strides {x_last.stride()}")
+    if tuple(state.shape) != (Cc, 2) or count.numel() != 1 or not (out.is_contiguous() and Y.is_contiguous()):
+        raise ValueError("downscale_metrics: state is float64 [C, 2], count int64 [1], out and Y contiguous")
+    ws = workspace(lib().gcl_downscale_loss_ws_bytes(0, 0, 0, 0), out.device)
+    _check(lib().gcl_downscale_metrics(_p(out), _p(x_last), x_last.stride(0), _p(Y), 1 if residual else 0, B, Cc, Hh, W,
+                                       _pd(state), _pl(count), ws.data_ptr(), ws.numel(), _stream()))
+    return state
+
+
+def downscale_loss_scale(dout, g, out=None):
+    """dout * g[0] with g a float32 scalar on the GPU (see gcl_downscale_loss_scale)."""
+    assert dout.is_contiguous() and g.numel() == 1
+    if out is None:
+        out = torch.empty_like(dout)
+    _check(lib().gcl_downscale_loss_scale(_p(dout), _p(g), dout.numel(), _p(out), _stream()))
     return out

@@ -1119,6 +1119,45 @@ int gcl_downscale_pair_mse(const uint16_t* xa, const uint16_t* xb, int64_t T, in
                            int32_t n, const float* mean, const float* stdv, double* stats, void* ws, size_t ws_bytes,
                            gcl_stream_t stream);
 
+/* ---- The downscaler's objective and scores (csrc/downscale_loss.hip; the losses, train_epoch and compute_metrics of
+ * scripts/train_downscaler.py) ----
+ * No entry point allocates or synchronises; offsets are int64; no floating-point atomics; every reduction has a fixed
+ * order (bit-equal from run to run).  out, Y, dOut: contiguous float32 [B, C, H, W].  x_last: the channel slice
+ * X[:, (obs - 1) * C : obs * C] of the input as a pointer to its first element and the batch stride xbs of X in
+ * elements (channel stride H * W, rows contiguous), or NULL: o = out, or o = x_last + out rounded once in float32
+ * (train_downscaler.py:236-240).  mask: float32 [C] or NULL (all ones).  rec: float64 [3] on the device = {mse, grad,
+ * spec}; an entry point writes only the terms it computes.  ws: at least gcl_downscale_loss_ws_bytes(B, C, H, W) bytes
+ * of 16-byte aligned device scratch.  2 <= H, W <= 256 and C <= 64, else GCL_EINVAL. */
+size_t gcl_downscale_loss_ws_bytes(int32_t B, int32_t C, int32_t H, int32_t W);
+/* masked_mse_loss (train_downscaler.py:189-193) and gradient_loss (:207-220) in one pass: with e = o - Y in float32 and
+ * float64 sums, rec[0] = sum m_c e^2 / (B C H W) (masked channels stay in the denominator) and rec[1] =
+ * sum m_c (e[h+1,w] - e[h,w])^2 / (B C (H-1) W) + sum m_c (e[h,w+1] - e[h,w])^2 / (B C H (W-1)).  A term whose weight
+ * is not > 0 is skipped and its record untouched (:243-246); at least one must run.  dOut (or NULL) takes
+ * d(mse_weight * mse + gradient_weight * grad) / d out, every element written exactly once: a tile of rows is staged
+ * with one halo row either side. */
+int gcl_downscale_loss_fwd_bwd(const float* out, const float* x_last, int64_t xbs, const float* Y, const float* mask,
+                               int32_t B, int32_t C, int32_t H, int32_t W, float mse_weight, float gradient_weight,
+                               double* rec, float* dOut, void* ws, size_t ws_bytes, gcl_stream_t stream);
+/* spectral_loss (train_downscaler.py:196-204): rec[2] = sum | |P| - |T| | / (B C H (W/2+1)), P = rfft2(m_c o,
+ * norm="ortho") and T the same of Y, every half-spectrum bin once; a separable direct DFT in float64, rows then
+ * columns.  tw_h / tw_w: float64 [H, 2] / [W, 2] = (cos, sin)(2 pi k / n), built in double by the caller.  dOut (or
+ * NULL) takes spectral_weight times the gradient, the adjoint of the real transform applied to sign(|P| - |T|) P / |P|
+ * / count (0 where |P| = 0 or |P| = |T|): added to what dOut holds when accumulate != 0, stored otherwise. */
+int gcl_downscale_spectral_fwd_bwd(const float* out, const float* x_last, int64_t xbs, const float* Y, const float* mask,
+                                   const double* tw_h, const double* tw_w, int32_t B, int32_t C, int32_t H, int32_t W,
+                                   float spectral_weight, int32_t accumulate, double* rec, float* dOut, void* ws,
+                                   size_t ws_bytes, gcl_stream_t stream);
+/* One batch of compute_metrics (train_downscaler.py:280-298): state float64 [C, 2] += the means over (B, H, W) of
+ * (o - Y)^2 and of (x_last - Y)^2 (differences in float32, squares and sums in float64), o with x_last added when
+ * residual != 0; count (device int64) += 1.  Per-batch means are averaged, as the reference does: a short last batch
+ * weighs as much as a full one.  Everything stays on the device, so a captured graph can replay it. */
+int gcl_downscale_metrics(const float* out, const float* x_last, int64_t xbs, const float* Y, int32_t residual, int32_t B,
+                          int32_t C, int32_t H, int32_t W, double* state, int64_t* count, void* ws, size_t ws_bytes,
+                          gcl_stream_t stream);
+/* loss.backward() of train_downscaler.py:248 through the saved dOut: out[i] = dOut[i] * g[0], g the incoming gradient
+ * on the device (no host sync).  In place is fine. */
+int gcl_downscale_loss_scale(const float* dOut, const float* g, int64_t n, float* out, gcl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
