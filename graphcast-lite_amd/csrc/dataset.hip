@@ -407,3 +407,59 @@ extern "C" int gcl_dataset_widen(const uint16_t* src, int64_t T, int32_t n_lon, 
   GCL_CHECK_LAUNCH();
   return GCL_OK;
 }
+
+// ---- legacy tensor datasets --------------------------------------------------------------------------------------------
+// Batches from the stored tensors of src/data/dataloader.py:25-153 ([N, G, W, F] float32: X_train.pt etc. as saved, the
+// grid flattened): the last Wu of the W stored steps, the first Fu of the F stored features (:129-132), sample idx[b]:
+//   outX[b, g, w * Fu + f] = X[idx[b], g, Wx - Wxu + w, f],   outY[b, g, w * Fu + f] = Y[idx[b], g, Wy - Wyu + w, f]
+// One thread per output element, X and Y rows in one launch; plain copies, so bit-exact.  A sample outside [0, N)
+// comes back as NaN, as a window that leaves the series does in gcl_window_pack.
+namespace {
+
+__global__ __launch_bounds__(256) void tensor_batch_pack_kernel(const float* __restrict__ X, int32_t Wx, int32_t Wxu,
+                                                                const float* __restrict__ Y, int32_t Wy, int32_t Wyu,
+                                                                int64_t N, int32_t G, int32_t F, int32_t Fu,
+                                                                const int64_t* __restrict__ idx, int32_t B,
+                                                                float* __restrict__ outX, int64_t ldx, int64_t bsx,
+                                                                float* __restrict__ outY, int64_t ldy, int64_t bsy) {
+  const int rowx = Wxu * Fu, row = rowx + (Y ? Wyu * Fu : 0);
+  const int64_t total = (int64_t)B * G * row;
+  for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (int64_t)gridDim.x * 256) {
+    int k = (int)(t % row);
+    const int64_t bg = t / row;
+    const int64_t g = bg % G;
+    const int64_t b = bg / G;
+    const bool is_y = k >= rowx;
+    if (is_y) k -= rowx;
+    const int w = k / Fu, f = k - w * Fu;
+    const int64_t n = idx[b];
+    float v = __builtin_nanf("");
+    if (n >= 0 && n < N) {
+      const int W = is_y ? Wy : Wx, w0 = is_y ? Wy - Wyu : Wx - Wxu;
+      v = (is_y ? Y : X)[((n * G + g) * W + w0 + w) * F + f];
+    }
+    if (is_y) outY[b * bsy + g * ldy + k] = v;
+    else outX[b * bsx + g * ldx + k] = v;
+  }
+}
+
+}  // namespace
+
+extern "C" int gcl_tensor_batch_pack(const float* X, int32_t Wx, int32_t Wxu, const float* Y, int32_t Wy, int32_t Wyu,
+                                     int64_t N, int32_t G, int32_t F, int32_t Fu, const int64_t* idx, int32_t B,
+                                     float* outX, int64_t ldx, int64_t bsx, float* outY, int64_t ldy, int64_t bsy,
+                                     gcl_stream_t stream) {
+  GCL_CHECK_ARG(X && idx && outX, "tensor_batch_pack: null argument");
+  GCL_CHECK_ARG(!Y == !outY, "tensor_batch_pack: Y and outY go together");
+  GCL_CHECK_ARG(N > 0 && G > 0 && F > 0 && B > 0, "tensor_batch_pack: bad shape (N=%lld, G=%d, F=%d, B=%d)", (long long)N,
+                G, F, B);
+  GCL_CHECK_ARG(Fu >= 1 && Fu <= F, "tensor_batch_pack: %d of %d features", Fu, F);
+  GCL_CHECK_ARG(Wxu >= 1 && Wxu <= Wx, "tensor_batch_pack: %d of %d stored steps (X)", Wxu, Wx);
+  GCL_CHECK_ARG(!Y || (Wyu >= 1 && Wyu <= Wy), "tensor_batch_pack: %d of %d stored steps (Y)", Wyu, Wy);
+  GCL_CHECK_ARG(ldx >= (int64_t)Wxu * Fu && (!Y || ldy >= (int64_t)Wyu * Fu), "tensor_batch_pack: output row too short");
+  const int64_t total = (int64_t)B * G * ((int64_t)Wxu * Fu + (Y ? (int64_t)Wyu * Fu : 0));
+  hipLaunchKernelGGL(tensor_batch_pack_kernel, dim3(gcl::grid_for(total, 16384)), dim3(256), 0, (hipStream_t)stream, X, Wx,
+                     Wxu, Y, Wy, Wyu, N, G, F, Fu, idx, B, outX, ldx, bsx, outY, ldy, bsy);
+  GCL_CHECK_LAUNCH();
+  return GCL_OK;
+}

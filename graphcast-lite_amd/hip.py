@@ -217,6 +217,12 @@ _SIGNATURES = {
                                                  _vp, _vp, _vp, _sz, _vp]),
     "gcl_downscale_metrics": (C.c_int, [_vp, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
     "gcl_downscale_loss_scale": (C.c_int, [_vp, _vp, _i64, _vp, _vp]),
+    "gcl_eval_colstats_ws_bytes": (_sz, [_i32, _i32, _i32]),
+    "gcl_eval_colstats": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _i32, _vp, _i64, _i64,
+                                    _vp, _i32, _i32, _i32, _vp, _sz, _vp]),
+    "gcl_eval_accumulate": (C.c_int, [_vp, _vp, _vp, C.c_double, _i32, _i32, _i32, _vp, _vp]),
+    "gcl_tensor_batch_pack": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i32, _i64, _i32, _i32, _i32, _vp, _i32, _vp, _i64,
+                                        _i64, _vp, _i64, _i64, _vp]),
 }
 
 
@@ -2154,3 +2160,79 @@ def downscale_loss_scale(dout, g, out=None):
         out = torch.empty_like(dout)
     _check(lib().gcl_downscale_loss_scale(_p(dout), _p(g), dout.numel(), _p(out), _stream()))
     return out
+
+
+EVAL_NS = 7  # sums per (sample, channel) of gcl_eval_colstats
+
+
+def _bgc(t, who: str):
+    if t.dim() != 3 or t.stride(2) != 1:
+        raise ValueError(f"{who}: expected a [B, G, C] view with unit channel stride, got {tuple(t.shape)} / {t.stride()}")
+    return t.stride(1), t.stride(0)
+
+
+def eval_colstats(delta3, x_last3, y3, node_w, chan_kind, residual: bool, stats, out3=None):
+    """The seven float64 sums per (sample, channel) behind the scores of one validation batch, into stats [B, C, 7]
+    (see gcl_eval_colstats).  delta3 / x_last3 / y3 / out3: [B, G, C] views with unit channel stride (x_last3 the last
+    slot of the window, y3 step 0 of the targets); node_w float32 [G] or None; chan_kind int32 [C] or None.  With out3
+    the one-step prediction is stored as well, bit-equal to `ar_advance`'s."""
+    B, G, Cc = delta3.shape
+    if tuple(x_last3.shape) != (B, G, Cc) or tuple(y3.shape) != (B, G, Cc) or (out3 is not None and tuple(out3.shape) != (B, G, Cc)):
+        raise ValueError(f"eval_colstats: delta {tuple(delta3.shape)}, x_last {tuple(x_last3.shape)}, y {tuple(y3.shape)}"
+                         + (f", out {tuple(out3.shape)}" if out3 is not None else "") + " must be one [B, G, C]")
+    if tuple(stats.shape) != (B, Cc, EVAL_NS):
+        raise ValueError(f"eval_colstats: stats is float64 [{B}, {Cc}, {EVAL_NS}], got {tuple(stats.shape)}")
+    if node_w is not None and (node_w.numel() != G or not node_w.is_contiguous()):
+        raise ValueError(f"eval_colstats: node_w holds {node_w.numel()} weights for {G} nodes")
+    if chan_kind is not None and chan_kind.numel() != Cc:
+        raise ValueError(f"eval_colstats: chan_kind holds {chan_kind.numel()} entries for {Cc} channels")
+    ldd, bsd = _bgc(delta3, "eval_colstats")
+    ldx, bsx = _bgc(x_last3, "eval_colstats")
+    ldy, bsy = _bgc(y3, "eval_colstats")
+    ldo, bso = _bgc(out3, "eval_colstats") if out3 is not None else (0, 0)
+    ws = workspace(lib().gcl_eval_colstats_ws_bytes(B, G, Cc), delta3.device)
+    _check(lib().gcl_eval_colstats(_p(delta3), ldd, bsd, _p(x_last3), ldx, bsx, _p(y3), ldy, bsy, _p(node_w), _pi(chan_kind),
+                                   1 if residual else 0, _p(out3), ldo, bso, _pd(stats), B, G, Cc, ws.data_ptr(),
+                                   ws.numel(), _stream()))
+    return stats
+
+
+def eval_accumulate(stats, chan_w, chan_kind, inv_wsum: float, G: int, state):
+    """state (float64 [4] on the GPU) += {loss, acc, raw_mse, 1} of the batch whose sums stats [B, C, 7] holds (see
+    gcl_eval_accumulate)."""
+    B, Cc, ns = stats.shape
+    if ns != EVAL_NS or state.numel() != 4:
+        raise ValueError(f"eval_accumulate: stats is [B, C, {EVAL_NS}] and state float64 [4], got {tuple(stats.shape)} and "
+                         f"{tuple(state.shape)}")
+    if chan_w is not None and (chan_w.numel() != Cc or not chan_w.is_contiguous()):
+        raise ValueError(f"eval_accumulate: chan_w holds {chan_w.numel()} weights for {Cc} channels")
+    _check(lib().gcl_eval_accumulate(_pd(stats), _p(chan_w), _pi(chan_kind), float(inv_wsum), B, int(G), Cc, _pd(state),
+                                     _stream()))
+    return state
+
+
+def tensor_batch_pack(X4, Y4, idx, Wxu: int, Wyu: int, Fu: int, out=None):
+    """Batches from the stored legacy tensors X4 [N, G, Wx, F] / Y4 [N, G, Wy, F] (float32, contiguous, on the GPU; Y4
+    may be None): samples idx (int64 [B] on the GPU), the last Wxu / Wyu steps, the first Fu features -> (X [B, G,
+    Wxu * Fu], Y [B, G, Wyu * Fu] or None), one launch (see gcl_tensor_batch_pack).  out = (X, Y): [B, G, .] views with
+    unit channel stride to fill in place."""
+    if X4.dim() != 4 or not X4.is_contiguous() or (Y4 is not None and (Y4.dim() != 4 or not Y4.is_contiguous()
+                                                                       or Y4.shape[:2] != X4.shape[:2] or Y4.shape[3] != X4.shape[3])):
+        raise ValueError("tensor_batch_pack: X4 and Y4 are contiguous [N, G, W, F] tensors over the same samples, nodes and "
+                         "features")
+    N, G, Wx, F = (int(v) for v in X4.shape)
+    Wy = int(Y4.shape[2]) if Y4 is not None else 0
+    B = idx.numel()
+    X, Y = out if out is not None else (None, None)
+    if X is None:
+        X = torch.empty(B, G, Wxu * Fu, dtype=torch.float32, device=X4.device)
+    if Y is None and Y4 is not None:
+        Y = torch.empty(B, G, Wyu * Fu, dtype=torch.float32, device=X4.device)
+    if tuple(X.shape) != (B, G, Wxu * Fu) or (Y4 is not None and tuple(Y.shape) != (B, G, Wyu * Fu)):
+        raise ValueError(f"tensor_batch_pack: out buffers {tuple(X.shape)} / {tuple(Y.shape) if Y is not None else None} do "
+                         f"not hold [{B}, {G}, {Wxu * Fu}] / [{B}, {G}, {Wyu * Fu}]")
+    ldx, bsx = _bgc(X, "tensor_batch_pack")
+    ldy, bsy = _bgc(Y, "tensor_batch_pack") if Y4 is not None else (0, 0)
+    _check(lib().gcl_tensor_batch_pack(_p(X4), Wx, int(Wxu), _p(Y4), Wy, int(Wyu), N, G, F, int(Fu), _pl(idx), B, _p(X), ldx,
+                                       bsx, _p(Y) if Y4 is not None else None, ldy, bsy, _stream()))
+    return X, (Y if Y4 is not None else None)

@@ -6,7 +6,8 @@
 Adam-state buffer, gradients accumulated in place by the backward kernels, ONE RCCL all-reduce of
 the flat gradient bucket per optimiser step, one grouped Adam update (per-parameter lr, active
 flag and step on the device).  `build_optimizer` and `train` restate the reference's fine-tuning optimiser and
-training driver (src/main.py:190-211, src/train.py:311-524) on `TrainStep`.
+training driver (src/main.py:190-211, src/train.py:311-524) on `TrainStep`.  `Evaluator` is `test` as one captured
+step per batch (csrc/eval_step.hip), with its scores kept on the device until the end of a pass.
 """
 import os
 
@@ -236,6 +237,94 @@ def test(model, test_dataloader, loss_fn, device, lat_weights=None, spatial_mask
             accs.append(spatial_corr(outs, y0, exclude_channels=skip if skip else None))
     n = max(len(raw), 1)
     return total / max(len(test_dataloader), 1), sum(accs) / n, (sum(raw) / n) ** 0.5
+
+
+class Evaluator(Captured):
+    """`test` (src/train.py:241-309) as a fused, captured step: per batch the model forward, `gcl_eval_colstats` (the
+    one-step prediction with its static / forcing carry-forward formed on the fly, never stored, and the sums behind
+    the three scores in one pass) and `gcl_eval_accumulate` (the batch's scores added to a float64 state on the
+    device).  `update` synchronises nothing and reads nothing back; `results` is the one host read of a pass.
+
+    The first `warmup` full batches run eagerly (the first of a shape also builds the cached weight vectors, which
+    reads their sums back once), the next is captured into a hipGraph and later ones replay it: `use_graph` as for
+    `TrainStep`.  A batch smaller than the largest seen so far (the last of a pass) and a sparse-GAT model run eagerly."""
+
+    def __init__(self, model, lat_weights=None, channel_mask=None, spatial_mask=None, static_channels=None,
+                 forcing_channels=None, use_residual=True, use_graph=None):
+        self.model = model
+        self.lat_weights, self.channel_mask, self.spatial_mask = lat_weights, channel_mask, spatial_mask
+        self.static_channels, self.forcing_channels = static_channels, forcing_channels
+        self.use_residual = bool(use_residual)
+        self._state, self._stats, self._full = None, {}, None
+        super().__init__(graph_enabled(use_graph), required=use_graph is True)
+
+    def _buffers(self, B, C, device):
+        """The state and the [B, C, 7] sums: made on the first eager call for a shape, never inside a capture."""
+        if self._state is None or self._state.device != device:
+            self._state = torch.zeros(4, dtype=torch.float64, device=device)
+            self._stats = {}
+        stats = self._stats.get((B, C))
+        if stats is None:
+            stats = self._stats[(B, C)] = torch.empty(B, C, hip.EVAL_NS, dtype=torch.float64, device=device)
+        return self._state, stats
+
+    def _work(self, X, y):
+        B, G, _ = X.shape
+        obs = self.model.obs_window
+        C = X.shape[-1] // obs
+        delta = self.model(X=X, attention_threshold=0.0)
+        if delta.dim() == 2:
+            delta = delta.unsqueeze(0)
+        node_w, chan_w, wsum1 = _loss_weights(G, C, self.lat_weights, self.channel_mask, self.spatial_mask, X.device)
+        kinds = _channel_kinds(C, self.static_channels, self.forcing_channels, X.device)
+        state, stats = self._buffers(B, C, X.device)
+        x_last = X.view(B, G, obs, C)[:, :, obs - 1, :]
+        hip.eval_colstats(delta, x_last, y[:, :, :C], node_w, kinds, self.use_residual, stats)
+        hip.eval_accumulate(stats, chan_w, kinds, 1.0 / max(wsum1 * B, 1e-12), G, state)
+
+    @torch.no_grad()
+    def update(self, X, y):
+        """Add one batch (X [B, G, obs*C], y [B, G, P*C] on the GPU; step 0 of y is scored) to the running scores."""
+        self.model.eval()
+        if X.dim() == 2:
+            X, y = X.unsqueeze(0), y.unsqueeze(0)
+        if not X.is_contiguous():
+            X = X.contiguous()
+        shape = (tuple(X.shape), tuple(y.shape))
+        if self._full is None or X.shape[0] > self._full[0][0] or (X.shape[0] == self._full[0][0] and shape != self._full):
+            self._full = shape
+            self.reset_graph()
+        if shape != self._full or getattr(self.model, "using_sparse_gat", False):
+            self._work(X, y)
+        else:
+            self._run(X, y)
+
+    def input_buffers(self):
+        """(X, y) the captured graph reads a full batch from, or None before the capture / on the eager path: a batch
+        written into them (`DeviceLoader(buffers=evaluator.input_buffers)`) is scored without a copy."""
+        return tuple(self._static) if self.graph_active else None
+
+    def results(self, num_batches=None):
+        """`test`'s triple (mean loss, mean ACC, sqrt(mean raw MSE)) over the batches since the last call - the one
+        host read - and a reset.  num_batches: the reference's `len(test_dataloader)` for the loss mean (default:
+        the batches seen)."""
+        if self._state is None:
+            return 0.0, 0.0, 0.0
+        loss, acc, raw, n = self._state.cpu().tolist()
+        self._state.zero_()
+        n = max(n, 1.0)
+        return loss / max(num_batches if num_batches is not None else n, 1), acc / n, (raw / n) ** 0.5
+
+    def evaluate(self, batches, device=None):
+        """`update` over an iterable of (X, y), then `results`; `device`: where to move host batches."""
+        count = 0
+        for X, y in batches:
+            y = y.squeeze(0) if y.dim() == 4 else y
+            if device is not None:
+                X, y = X.to(device), y.to(device)
+            self.update(X, y)
+            count += 1
+        return self.results(len(batches) if hasattr(batches, "__len__") else count)
 
 
 _ADAM_DEFAULTS = dict(lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0)
@@ -672,42 +761,17 @@ def build_optimizer(model, config, pretrained: bool):
     return torch.optim.Adam(params=model.parameters(), lr=base_lr)
 
 
-def train(model, train_dataloader, val_dataloader, test_dataloader, optimiser, num_epochs, device, config,
-          results_save_dir, dataset_metadata=None, print_losses=True, wandb_log=False, resume_checkpoint=None, *,
-          world_size=1, use_graph=None):
-    """src/train.py:311-524 on the fused step: the same masks, AR curriculum, attention-threshold schedule, processor
-    unfreeze, early stopping, `training_log.txt`, best model, `checkpoint.pth` and results JSON, with every batch one
-    `TrainStep` call (captured and replayed; dropped and captured again at an unfreeze or an AR change).
-
-    `optimiser` is the reference's torch.optim.Adam (e.g. from `build_optimizer`): its `param_groups` become the fused
-    step's groups and its state, if any, is carried over; the fused state is written back into it at the end.
-    Checkpoints hold the optimiser state in torch's layout, so the reference's `train()` resumes them and this one
-    resumes the reference's.  `dataset_metadata` and `config` are duck-typed (the attributes the reference reads);
-    batches are `(X, y)` pairs of CPU or device tensors from any iterable.  `test_dataloader` is unused, as in the
-    reference.  With `world_size > 1` each rank passes its own shard of the batches and rank 0 writes the files."""
-    import json
-    from datetime import datetime
-
-    if wandb_log:
-        raise NotImplementedError("wandb logging is not provided by this package (see README, 'What is not provided')")
-    if not isinstance(optimiser, torch.optim.Adam) or any(g.get("amsgrad") or g.get("maximize")
-                                                          for g in optimiser.param_groups):
-        raise ValueError("train() runs torch.optim.Adam (no amsgrad, no maximize) on the fused step; "
-                         f"got {type(optimiser).__name__}")
+def loss_masks(config, dataset_metadata, device):
+    """The loss weights and channel roles `train()` derives from the configuration and the dataset's metadata
+    (src/train.py:333-377), as the keyword arguments `TrainStep`, `test` and `Evaluator` share: latitude weights,
+    the channel mask that takes static / forcing channels out of the loss, the boundary and ROI node masks."""
     device = torch.device(device)
-    main = world_size == 1 or dist.get_rank() == 0
-    say = print if (print_losses and main) else (lambda *a, **k: None)
-
     lat_weights = None
     if getattr(config, "use_latitude_weighting", False) and dataset_metadata:
         if getattr(dataset_metadata, "flat_grid", False) and hasattr(dataset_metadata, "cordinates"):
             lat_weights = get_lat_weights(0, 0, device, flat_lats=dataset_metadata.cordinates[0])
         else:
             lat_weights = get_lat_weights(dataset_metadata.num_latitudes, dataset_metadata.num_longitudes, device)
-
-    ar_steps = 1
-    max_ar = config.max_ar_steps
-    epochs_per_stage = num_epochs // max_ar if max_ar > 0 else num_epochs
 
     static_ch = getattr(config, "static_channels", [])
     forcing_ch = getattr(config, "forcing_channels", [])
@@ -733,7 +797,46 @@ def train(model, train_dataloader, val_dataloader, test_dataloader, optimiser, n
         if roi is not None:
             roi_spatial_mask = torch.as_tensor(roi, dtype=torch.float32, device=device).view(1, -1, 1)
     spatial_mask = combine_spatial_masks(spatial_mask, roi_spatial_mask)
-    use_residual = getattr(config, "use_residual", True)
+    return dict(lat_weights=lat_weights, channel_mask=channel_mask, spatial_mask=spatial_mask,
+                static_channels=static_ch, forcing_channels=forcing_ch,
+                use_residual=getattr(config, "use_residual", True))
+
+
+def train(model, train_dataloader, val_dataloader, test_dataloader, optimiser, num_epochs, device, config,
+          results_save_dir, dataset_metadata=None, print_losses=True, wandb_log=False, resume_checkpoint=None, *,
+          world_size=1, use_graph=None, evaluator=None):
+    """src/train.py:311-524 on the fused step: the same masks, AR curriculum, attention-threshold schedule, processor
+    unfreeze, early stopping, `training_log.txt`, best model, `checkpoint.pth` and results JSON, with every batch one
+    `TrainStep` call (captured and replayed; dropped and captured again at an unfreeze or an AR change).
+
+    `optimiser` is the reference's torch.optim.Adam (e.g. from `build_optimizer`): its `param_groups` become the fused
+    step's groups and its state, if any, is carried over; the fused state is written back into it at the end.
+    Checkpoints hold the optimiser state in torch's layout, so the reference's `train()` resumes them and this one
+    resumes the reference's.  `dataset_metadata` and `config` are duck-typed (the attributes the reference reads);
+    batches are `(X, y)` pairs of CPU or device tensors from any iterable.  `test_dataloader` is unused, as in the
+    reference.  With `world_size > 1` each rank passes its own shard of the batches and rank 0 writes the files.
+    `evaluator`: an `Evaluator` built from `loss_masks(config, dataset_metadata, device)`; validation then runs on the
+    fused, captured step instead of `test` (one host read per pass)."""
+    import json
+    from datetime import datetime
+
+    if wandb_log:
+        raise NotImplementedError("wandb logging is not provided by this package (see README, 'What is not provided')")
+    if not isinstance(optimiser, torch.optim.Adam) or any(g.get("amsgrad") or g.get("maximize")
+                                                          for g in optimiser.param_groups):
+        raise ValueError("train() runs torch.optim.Adam (no amsgrad, no maximize) on the fused step; "
+                         f"got {type(optimiser).__name__}")
+    device = torch.device(device)
+    main = world_size == 1 or dist.get_rank() == 0
+    say = print if (print_losses and main) else (lambda *a, **k: None)
+
+    masks = loss_masks(config, dataset_metadata, device)
+    lat_weights, channel_mask, spatial_mask = masks["lat_weights"], masks["channel_mask"], masks["spatial_mask"]
+    static_ch, forcing_ch, use_residual = masks["static_channels"], masks["forcing_channels"], masks["use_residual"]
+
+    ar_steps = 1
+    max_ar = config.max_ar_steps
+    epochs_per_stage = num_epochs // max_ar if max_ar > 0 else num_epochs
 
     step = TrainStep(model, lr=optimiser.defaults["lr"], lat_weights=lat_weights, channel_mask=channel_mask,
                      spatial_mask=spatial_mask, use_residual=use_residual, ar_steps=ar_steps, world_size=world_size,
@@ -769,6 +872,8 @@ def train(model, train_dataloader, val_dataloader, test_dataloader, optimiser, n
     _log("-" * 90)
 
     def _validate():
+        if evaluator is not None:
+            return evaluator.evaluate(val_dataloader, device=device)
         return test(model, val_dataloader, None, device, lat_weights, spatial_mask=spatial_mask,
                     channel_mask=channel_mask, static_channels=static_ch, forcing_channels=forcing_ch,
                     use_residual=use_residual)

@@ -1158,6 +1158,39 @@ int gcl_downscale_metrics(const float* out, const float* x_last, int64_t xbs, co
  * on the device (no host sync).  In place is fine. */
 int gcl_downscale_loss_scale(const float* dOut, const float* g, int64_t n, float* out, gcl_stream_t stream);
 
+/* ---- Fused validation step (csrc/eval_step.hip; test() of src/train.py:241-309 for one batch) ----
+ * No entry point allocates, synchronises or reads back; no atomics; every reduction has a fixed order, so results are
+ * bit-equal from run to run.  The one-step prediction is formed as gcl_ar_advance forms step_out (src/train.py:273-292):
+ * o = residual ? x_last + delta : delta in float32, static channels (chan_kind 1) take x_last, forcing channels
+ * (chan_kind 2) take y; chan_kind NULL: all predicted.  delta / x_last / y / out are addressed with (ld, bs): x_last is
+ * the last slot of the [B,G,obs*C] window (ldx = obs*C), y step 0 of [B,G,P*C] (ldy = P*C). */
+size_t gcl_eval_colstats_ws_bytes(int32_t B, int32_t G, int32_t C);
+/* stats[b,c,0..6] (float64) = sums over the G nodes of (o-y)^2, node_w[g] (o-y)^2 (node_w NULL = 1; the weights of
+ * src/train.py:85-100), o', o'^2, y', y'^2, o' y' with o' = o - o[b,0,c], y' = y - y[b,0,c] (the sums behind
+ * src/train.py:123-125; the shift removes the cancellation of one-pass variances).  o is stored to out [B,G,C] when
+ * out is given, with the bits of gcl_ar_advance's step_out.  G >= 2 (torch's unbiased std is NaN below), B, C <= 65535;
+ * ws: at least gcl_eval_colstats_ws_bytes(B, G, C) bytes of 8-byte aligned device scratch. */
+int gcl_eval_colstats(const float* delta, int64_t ldd, int64_t bsd, const float* x_last, int64_t ldx, int64_t bsx,
+                      const float* y, int64_t ldy, int64_t bsy, const float* node_w, const int32_t* chan_kind,
+                      int32_t residual, float* out, int64_t ldo, int64_t bso, double* stats, int32_t B, int32_t G,
+                      int32_t C, void* ws, size_t ws_bytes, gcl_stream_t stream);
+/* Folds stats [B,C,7] into state (float64 [4] on the device) += {loss, acc, raw_mse, 1} of the batch
+ * (src/train.py:295-303): loss = inv_wsum sum_b sum_c chan_w[c] stats[b,c,1] (chan_w NULL = 1), raw_mse =
+ * sum stats[b,c,0] / (B G C), acc = the mean over b of the mean over the kept channels of cov / ((std_o + 1e-8)
+ * (std_y + 1e-8)), cov = (S_o'y' - S_o' S_y' / G) / G, std = sqrt(max(S_x'x' - S_x'^2 / G, 0) / (G - 1)); kept channels
+ * are those of chan_kind 0, or all of them when that leaves none (src/train.py:126-130). */
+int gcl_eval_accumulate(const double* stats, const float* chan_w, const int32_t* chan_kind, double inv_wsum, int32_t B,
+                        int32_t G, int32_t C, double* state, gcl_stream_t stream);
+
+/* Batches from the stored legacy tensors (csrc/dataset.hip; src/data/dataloader.py:116-139, WeatherDataset.__getitem__
+ * :22-23 under a DataLoader): X [N,G,Wx,F] and Y [N,G,Wy,F] contiguous float32 as the files hold them, idx device int64
+ * [B].  outX[b,g,w*Fu+f] = X[idx[b], g, Wx-Wxu+w, f] for w < Wxu, f < Fu, and outY the same from Y with (Wy, Wyu); Y and
+ * outY may both be NULL.  outX / outY are addressed with (ld, bs).  Copies are bit-exact; an idx[b] outside [0, N) gives
+ * NaN rows for that sample.  One launch. */
+int gcl_tensor_batch_pack(const float* X, int32_t Wx, int32_t Wxu, const float* Y, int32_t Wy, int32_t Wyu, int64_t N,
+                          int32_t G, int32_t F, int32_t Fu, const int64_t* idx, int32_t B, float* outX, int64_t ldx,
+                          int64_t bsx, float* outY, int64_t ldy, int64_t bsy, gcl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
