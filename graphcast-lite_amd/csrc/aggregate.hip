@@ -26,6 +26,10 @@
 
 namespace {
 
+// gcl_aggregate_head: a two-part source whose second part is one row of zeros (H2 == nullptr: every row j >= head, read with
+// row and batch stride 0).  As wide as the widest row the aggregation takes.
+__device__ __attribute__((aligned(16))) float agg_zero_row[256];
+
 // One block per (heavy row, sample): the 256/LPR lane groups stride over the row's edges (4 loads
 // in flight each) and are combined through LDS in a fixed order.  Only rows with more than kHeavy
 // edges take this path (polar mesh nodes of E_G2M / E_M2G at 512x256: up to 943 edges), so a
@@ -46,7 +50,7 @@ __device__ __forceinline__ void agg_heavy_row(const int row, const int b, const 
   const bool cactive = c0 < F;
   const int cc = cactive ? c0 : 0;
   const float* __restrict__ Hb = H + (int64_t)b * bsh;
-  const float* __restrict__ H2b = SPLIT ? H2 + (int64_t)b * bsh2 : nullptr;
+  const float* __restrict__ H2b = SPLIT ? (H2 ? H2 + (int64_t)b * bsh2 : agg_zero_row) : nullptr;
   const int start = rowptr[row], end = rowptr[row + 1];
   float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
   auto ld4 = [&](int j, float& x0, float& x1, float& x2, float& x3) {
@@ -179,7 +183,7 @@ __global__ __launch_bounds__(256) void agg_kernel(const int32_t* __restrict__ ro
   const bool cactive = c0 < F;
   const int cc = cactive ? c0 : 0;  // inactive channel lanes re-read channel 0 (never stored)
   const float* __restrict__ Hb = H + (int64_t)b * bsh;
-  const float* __restrict__ H2b = SPLIT ? H2 + (int64_t)b * bsh2 : nullptr;
+  const float* __restrict__ H2b = SPLIT ? (H2 ? H2 + (int64_t)b * bsh2 : agg_zero_row) : nullptr;
   float* __restrict__ Yb = Y + (int64_t)b * bsy;
 
   float bz0 = 0.f, bz1 = 0.f, bz2 = 0.f, bz3 = 0.f;
@@ -589,6 +593,8 @@ struct AggArgs {
   const float* h2 = nullptr;
   int64_t ldh2 = 0, bsh2 = 0;
   int32_t head = 0;
+  bool zero_tail = false;  // gcl_aggregate_head: two parts with h2 == nullptr, the kernels then read the zero row
+  bool two_part() const { return h2 != nullptr || zero_tail; }
   // gcl_aggregate_compact: rows with smap[row] >= 0 are stored to yc instead (source-tile kernel only); dry: only say
   // whether the source-tile kernel would take the call
   const int32_t* smap = nullptr;
@@ -669,7 +675,7 @@ int launch_agg_heavy(const AggArgs& ga, const float* h, int64_t ldh, int64_t bsh
                      const int32_t* present = nullptr) {
   g_heavy_launches.fetch_add(1, std::memory_order_relaxed);
   dim3 hgrid((unsigned)ga.n_heavy, (unsigned)B), block(256);
-  if (ga.h2) {  // (only 16-byte rows reach here: gcl_aggregate_split refuses others)
+  if (ga.two_part()) {  // (only 16-byte rows reach here: gcl_aggregate_split refuses others)
     hipLaunchKernelGGL((agg_heavy_kernel<LPR, true, true, false, true>), hgrid, block, 0, st, ga.heavy, ga.rowptr, ga.col,
                        ga.w, h, ldh, bsh, bias, y, ldy, bsy, F, (const int32_t*)nullptr, ga.h2, ga.ldh2, ga.bsh2, ga.head);
     GCL_CHECK_LAUNCH();
@@ -709,7 +715,7 @@ int launch_agg(const AggArgs& ga, const float* h, int64_t ldh, int64_t bsh, cons
   const bool vl = (ldh % 4 == 0) && (bsh % 4 == 0) && gcl::aligned16(h) && ldh >= ((F + 3) / 4) * 4;
   const bool vs = (ldy % 4 == 0) && (bsy % 4 == 0) && gcl::aligned16(y) && (F % 4 == 0);
   if constexpr (LPR >= 16) {
-    if (!ga.h2 && vl && vs && (!bias || gcl::aligned16(bias))) {  // (the source tiles stage ONE tensor's rows)
+    if (!ga.two_part() && vl && vs && (!bias || gcl::aligned16(bias))) {  // (the source tiles stage ONE tensor's rows)
       const int hr = launch_agg_halo<LPR>(ga, h, ldh, bsh, bias, y, ldy, bsy, n, B, F, st, present);
       if (hr >= 0) {
         if (hr != GCL_OK || ga.n_heavy == 0 || ga.dry) return hr;
@@ -727,7 +733,7 @@ int launch_agg(const AggArgs& ga, const float* h, int64_t ldh, int64_t bsh, cons
   // measured on MI355X (profiles/r01_c_*): dense prefixes (mesh) run best with one batch per wave,
   // near-diagonal bipartite graphs with two (next batch's metadata prefetched)
   // (the variant with absent sources exists for the per-graph default only)
-  const int iter = (!present && !ga.h2 && (iter_env == 1 || iter_env == 2 || iter_env == 4 || iter_env == 8)) ? iter_env
+  const int iter = (!present && !ga.two_part() && (iter_env == 1 || iter_env == 2 || iter_env == 4 || iter_env == 8)) ? iter_env
                                                                                                      : (ewidth >= 4 ? 1 : 2);
   int32_t nRB = (int32_t)gcl::cdiv(n, RPW * 4 * iter);
   if (ga.order16 && RPW * 4 * iter <= 16) nRB = ga.n_order16 * (16 / (RPW * 4 * iter));  // whole 16-row groups (rows >= n are masked)
@@ -765,7 +771,7 @@ int launch_agg(const AggArgs& ga, const float* h, int64_t ldh, int64_t bsh, cons
   hipLaunchKernelGGL((agg_kernel<LPR, true, true, EW_, IT_, false, true>), grid, block, 0, st, ga.rowptr, ga.col, ga.w,  \
                      ga.ecol, ga.ew, h, ldh, bsh, bias, y, ldy, bsy, n, B, F, nRB, xcd_map, nt, order16,                \
                      (const int32_t*)nullptr, ga.h2, ga.ldh2, ga.bsh2, ga.head)
-  if (ga.h2) {  // two-part source: the per-graph default of the plain kernel, 16-byte rows only
+  if (ga.two_part()) {  // two-part source: the per-graph default of the plain kernel, 16-byte rows only
     if (hv) {
       if constexpr (EL >= 8) {
         if (ewidth == 8) GCL_AGGHS(8, 1);
@@ -913,6 +919,19 @@ extern "C" int gcl_aggregate_split(const gcl_graph_t* g, int32_t transpose, cons
                 "aggregate_split: both source parts and y need 16-byte rows (F %% 4 == 0, aligned bases and strides)");
   GCL_CHECK_ARG(h2 != y, "aggregate: in-place aggregation is not supported");
   return aggregate_impl(g, transpose, h, ldh, bsh, nullptr, bias, y, ldy, bsy, B, F, stream, h2, ldh2, bsh2, head);
+}
+
+extern "C" int gcl_aggregate_head(const gcl_graph_t* g, int32_t transpose, const float* h, int64_t ldh, int64_t bsh,
+                                  int32_t head, const float* bias, float* y, int64_t ldy, int64_t bsy, int32_t B, int32_t F,
+                                  gcl_stream_t stream) {
+  GCL_CHECK_ARG(g && h && y, "aggregate_head: null argument");
+  GCL_CHECK_ARG(head > 0 && head <= g->n, "aggregate_head: head=%d outside (0, n=%d]", head, g->n);
+  GCL_CHECK_ARG(F > 0 && F % 4 == 0 && ldh >= F && ldh % 4 == 0 && bsh % 4 == 0 && ldy % 4 == 0 && bsy % 4 == 0 &&
+                    gcl::aligned16(h) && gcl::aligned16(y),
+                "aggregate_head: the source and y need 16-byte rows (F %% 4 == 0, aligned bases and strides)");
+  AggArgs za;
+  za.zero_tail = true;
+  return aggregate_impl(g, transpose, h, ldh, bsh, nullptr, bias, y, ldy, bsy, B, F, stream, nullptr, 0, 0, head, &za);
 }
 
 // 1 when gcl_aggregate_compact can take a call with these strides (the source-tile kernel runs it: GCL_AGG_HALO, a graph

@@ -282,8 +282,15 @@ __device__ __forceinline__ bf16x8 tr_frag(const unsigned char* base, int o0, int
   return __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
 }
 
-template <int NO>
-__global__ __launch_bounds__(256, 2) void linear_x3_bwd_kernel(
+// One body for the two kernels below (as agg_heavy_row in aggregate.hip).  A flag that is off removes the code of what the
+// caller did not ask for instead of testing a pointer where the result would be stored:
+//   ACT   - an input activation (in_slope may be given): act(P), act', the slope gradient and the copy of P kept for them;
+//           off: a = P, dX = dY W
+//   DB    - the running column sums of dY (part_db)          CS - the running column sums of dX (part_cs)
+//   YMASK - the element masks of dY's last partial float4 (needed when Fout % 4 != 0)
+// With all four on this is the text of linear_x3_bwd_kernel as it was, run-time tests included.
+template <int NO, bool ACT, bool DB, bool CS, bool YMASK>
+__device__ __forceinline__ void linear_x3_bwd_body(
     const float* __restrict__ dY, int64_t lddy, const float* __restrict__ W, const float* __restrict__ P,
     int64_t ldp, const float* __restrict__ in_slope, float* __restrict__ dX, int64_t lddx, int64_t rows, int32_t Fin,
     int32_t Fout, float* __restrict__ part_dw, float* __restrict__ part_db, float* __restrict__ part_cs,
@@ -329,7 +336,7 @@ __global__ __launch_bounds__(256, 2) void linear_x3_bwd_kernel(
     __syncthreads();
   }
 
-  const bool act = in_slope != nullptr;
+  const bool act = ACT && in_slope != nullptr;
   const float slope = act ? *in_slope : 1.f;
   const int64_t ntiles = (rows + 63) / 64;
 
@@ -387,13 +394,15 @@ __global__ __launch_bounds__(256, 2) void linear_x3_bwd_kernel(
 #pragma unroll
     for (int it = 0; it < 4; ++it) {
       float4 y = pre_y[it];
-      y.x = __uint_as_float(__float_as_uint(y.x) & ym0); y.y = __uint_as_float(__float_as_uint(y.y) & ym1);
-      y.z = __uint_as_float(__float_as_uint(y.z) & ym2); y.w = __uint_as_float(__float_as_uint(y.w) & ym3);
-      db4.x += y.x; db4.y += y.y; db4.z += y.z; db4.w += y.w;
+      if (YMASK) {
+        y.x = __uint_as_float(__float_as_uint(y.x) & ym0); y.y = __uint_as_float(__float_as_uint(y.y) & ym1);
+        y.z = __uint_as_float(__float_as_uint(y.z) & ym2); y.w = __uint_as_float(__float_as_uint(y.w) & ym3);
+      }
+      if (DB) { db4.x += y.x; db4.y += y.y; db4.z += y.z; db4.w += y.w; }
       const float4 z = pre_p[it];
-      cur_p[it] = z;
-      float4 a;
-      {
+      float4 a = z;
+      if (ACT) {
+        cur_p[it] = z;
         const float mx = z.x * slope, my = z.y * slope, mz = z.z * slope, mw = z.w * slope;
         a.x = z.x > 0.f ? z.x : mx; a.y = z.y > 0.f ? z.y : my; a.z = z.z > 0.f ? z.z : mz; a.w = z.w > 0.f ? z.w : mw;
       }
@@ -468,12 +477,14 @@ __global__ __launch_bounds__(256, 2) void linear_x3_bwd_kernel(
       for (int it = 0; it < 4; ++it) {
         const int row = wave * 16 + it * 4 + rsub;
         float4 v = *reinterpret_cast<const float4*>(Stg + row * 64 + csub * 4);
-        const float4 z = cur_p[it];
-        const bool nx = act && z.x <= 0.f, ny = act && z.y <= 0.f, nz = act && z.z <= 0.f, nw = act && z.w <= 0.f;
-        // fp64 across float4s: the slope gradient is a long signed sum with heavy cancellation
-        slope_acc += (double)(((nx ? v.x * z.x : 0.f) + (ny ? v.y * z.y : 0.f)) + ((nz ? v.z * z.z : 0.f) + (nw ? v.w * z.w : 0.f)));
-        v.x = nx ? v.x * slope : v.x; v.y = ny ? v.y * slope : v.y; v.z = nz ? v.z * slope : v.z; v.w = nw ? v.w * slope : v.w;
-        cs4.x += v.x; cs4.y += v.y; cs4.z += v.z; cs4.w += v.w;
+        if (ACT) {
+          const float4 z = cur_p[it];
+          const bool nx = act && z.x <= 0.f, ny = act && z.y <= 0.f, nz = act && z.z <= 0.f, nw = act && z.w <= 0.f;
+          // fp64 across float4s: the slope gradient is a long signed sum with heavy cancellation
+          slope_acc += (double)(((nx ? v.x * z.x : 0.f) + (ny ? v.y * z.y : 0.f)) + ((nz ? v.z * z.z : 0.f) + (nw ? v.w * z.w : 0.f)));
+          v.x = nx ? v.x * slope : v.x; v.y = ny ? v.y * slope : v.y; v.z = nz ? v.z * slope : v.z; v.w = nw ? v.w * slope : v.w;
+        }
+        if (CS) { cs4.x += v.x; cs4.y += v.y; cs4.z += v.z; cs4.w += v.w; }
         buf_st4<GCL_X3_ST_AUX>(rx, pok ? (unsigned)((row * lddx + csub * 4) * 4) : kOOB, v);
       }
     }
@@ -491,29 +502,57 @@ __global__ __launch_bounds__(256, 2) void linear_x3_bwd_kernel(
 #pragma unroll
     for (int r = 0; r < 16; ++r) out[(size_t)(so * 32 + d_row(r, lane)) * FiP + sc * 32 + li] = dw_hi[r] + dw_lo[r];
   }
+  if (!(ACT || DB || CS)) return;  // the dW block is all this launch was asked for besides dX
   __syncthreads();
   float* red = reinterpret_cast<float*>(smem8);  // [2][16][64]: db and colsum partials of the 16 row groups
   {
     float* rdb = red + (wave * 4 + rsub) * 64 + csub * 4;
-    *reinterpret_cast<float4*>(rdb) = db4;
-    *reinterpret_cast<float4*>(rdb + 16 * 64) = cs4;
+    if (DB) *reinterpret_cast<float4*>(rdb) = db4;
+    if (CS) *reinterpret_cast<float4*>(rdb + 16 * 64) = cs4;
   }
-  for (int off = 32; off > 0; off >>= 1) slope_acc += __shfl_down(slope_acc, off, 64);
   double* dred = reinterpret_cast<double*>(red + 2 * 16 * 64);
-  if (lane == 0) dred[wave] = slope_acc;
+  if (ACT) {
+    for (int off = 32; off > 0; off >>= 1) slope_acc += __shfl_down(slope_acc, off, 64);
+    if (lane == 0) dred[wave] = slope_acc;
+  }
   __syncthreads();
   if (tid < 128) {
-    const int which = tid >> 6, c = tid & 63;
-    float s = 0.f;
+    const int which = tid >> 6, c = tid & 63;  // (wave-uniform)
+    if (which == 0 ? DB : CS) {
+      float s = 0.f;
 #pragma unroll
-    for (int q = 0; q < 16; ++q) s += red[(which * 16 + q) * 64 + c];
-    if (which == 0) {
-      if (part_db && c < FoP) part_db[(size_t)blockIdx.x * REC + c] = s;
-    } else {
-      if (part_cs) part_cs[(size_t)blockIdx.x * REC + c] = s;
+      for (int q = 0; q < 16; ++q) s += red[(which * 16 + q) * 64 + c];
+      if (which == 0) {
+        if (part_db && c < FoP) part_db[(size_t)blockIdx.x * REC + c] = s;
+      } else {
+        if (part_cs) part_cs[(size_t)blockIdx.x * REC + c] = s;
+      }
     }
   }
-  if (part_slope && tid == 0) part_slope[blockIdx.x] = (dred[0] + dred[1]) + (dred[2] + dred[3]);
+  if (ACT && part_slope && tid == 0) part_slope[blockIdx.x] = (dred[0] + dred[1]) + (dred[2] + dred[3]);
+}
+
+// The call that wants both column sums (db and those of dX; with an activation that is everything) and, with
+// GCL_X3_BWD_LEAN=0, every call: all of the body, each request tested at run time.
+template <int NO>
+__global__ __launch_bounds__(256, 2) void linear_x3_bwd_kernel(
+    const float* __restrict__ dY, int64_t lddy, const float* __restrict__ W, const float* __restrict__ P,
+    int64_t ldp, const float* __restrict__ in_slope, float* __restrict__ dX, int64_t lddx, int64_t rows, int32_t Fin,
+    int32_t Fout, float* __restrict__ part_dw, float* __restrict__ part_db, float* __restrict__ part_cs,
+    double* __restrict__ part_slope) {
+  linear_x3_bwd_body<NO, true, true, true, true>(dY, lddy, W, P, ldp, in_slope, dX, lddx, rows, Fin, Fout, part_dw, part_db,
+                                                 part_cs, part_slope);
+}
+
+// Every other combination of requests: the body without the code of what was not asked for (same grid, LDS and records).
+template <int NO, bool ACT, bool DB, bool CS, bool YMASK>
+__global__ __launch_bounds__(256, 2) void linear_x3_bwd_lean_kernel(
+    const float* __restrict__ dY, int64_t lddy, const float* __restrict__ W, const float* __restrict__ P,
+    int64_t ldp, const float* __restrict__ in_slope, float* __restrict__ dX, int64_t lddx, int64_t rows, int32_t Fin,
+    int32_t Fout, float* __restrict__ part_dw, float* __restrict__ part_db, float* __restrict__ part_cs,
+    double* __restrict__ part_slope) {
+  linear_x3_bwd_body<NO, ACT, DB, CS, YMASK>(dY, lddy, W, P, ldp, in_slope, dX, lddx, rows, Fin, Fout, part_dw, part_db,
+                                             part_cs, part_slope);
 }
 
 int x3_ablate() {  // GCL_ABLATE: timing-only experiments (tools/ablate.sh) - honoured by the diagnostic build only
@@ -591,16 +630,49 @@ int x3_linear_bwd(const float* dy, int64_t lddy, const float* W, const float* x,
                   float* part_cs, double* part_slope, hipStream_t st) {
   const int grid = x3_linear_bwd_blocks(rows);
   const size_t lds = 6 * (size_t)kImg64B + 64 * 64 * sizeof(float);
-#define GCL_X3B(NO_)                                                                                              \
+#define GCL_X3B_GO(KERN_)                                                                                         \
   do {                                                                                                            \
-    auto kern = linear_x3_bwd_kernel<NO_>;                                                                        \
+    auto kern = KERN_;                                                                                            \
     GCL_ENSURE_DYN_LDS(kern, gcl::kLdsBytes);                                                                     \
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, dy, lddy, W, x, ldx, in_slope, dx, lddx, rows, Fin, Fout, \
                        part_dw, part_db, part_cs, part_slope);                                                    \
   } while (0)
-  if (Fout > 32) GCL_X3B(2);
-  else GCL_X3B(1);
+#define GCL_X3B(NO_) GCL_X3B_GO((linear_x3_bwd_kernel<NO_>))
+  // what the caller asked for (the slope gradient comes with the activation).  A call that wants both column sums, db and
+  // those of dX, keeps the full kernel whether or not it has an activation: no layer of the models makes such a call (an
+  // MLP layer wants db, a GCNConv the column sums of dX), and linear_x3_bwd_kernel stays the kernel of the complete
+  // contract.  GCL_X3_BWD_LEAN=0 (read per call: the tests compare the two kernels): every call
+  const bool act = in_slope != nullptr, wdb = part_db != nullptr, wcs = part_cs != nullptr, ymask = (Fout & 3) != 0;
+  if ((wdb && wcs) || !env_int("GCL_X3_BWD_LEAN", 1)) {
+    if (Fout > 32) GCL_X3B(2);
+    else GCL_X3B(1);
+  } else {
+#define GCL_X3L(NO_, A_, D_, C_, M_) GCL_X3B_GO((linear_x3_bwd_lean_kernel<NO_, A_, D_, C_, M_>))
+#define GCL_X3L_M(NO_, A_, D_, C_)          \
+  do {                                      \
+    if (ymask) GCL_X3L(NO_, A_, D_, C_, true); \
+    else GCL_X3L(NO_, A_, D_, C_, false);   \
+  } while (0)
+#define GCL_X3L_A(NO_, A_)                          \
+  do {                                              \
+    if (wdb) GCL_X3L_M(NO_, A_, true, false);       \
+    else if (wcs) GCL_X3L_M(NO_, A_, false, true);  \
+    else GCL_X3L_M(NO_, A_, false, false);          \
+  } while (0)
+#define GCL_X3L_NO(NO_)           \
+  do {                            \
+    if (act) GCL_X3L_A(NO_, true); \
+    else GCL_X3L_A(NO_, false);   \
+  } while (0)
+    if (Fout > 32) GCL_X3L_NO(2);
+    else GCL_X3L_NO(1);
+#undef GCL_X3L_NO
+#undef GCL_X3L_A
+#undef GCL_X3L_M
+#undef GCL_X3L
+  }
 #undef GCL_X3B
+#undef GCL_X3B_GO
   GCL_CHECK_LAUNCH();
   return GCL_OK;
 }

@@ -80,14 +80,18 @@ __global__ __launch_bounds__(256) void assemble4_kernel(const float* __restrict_
   }
 }
 
-// loss partials + gradient (src/train.py:203-213,85-102)
+// loss partials + gradient (src/train.py:203-213,85-102).  OUTLD: dd[b, g, c] goes to dd + b * bso + g * ldo + c and the
+// columns C <= c < ldo of every row are written as zeros (gcl_wmse_fwd_bwd_ld: the gradient born in the padded layout of
+// the tensor it is the gradient of); the thread that owns an element, the sums and their order are those of the dense
+// form, so the loss is the same bit for bit.
+template <bool OUTLD>
 __global__ __launch_bounds__(256) void wmse_kernel(const float* __restrict__ delta, int64_t ldd, int64_t bsd,
                                                    const float* __restrict__ xl, int64_t ldx, int64_t bsx,
                                                    const float* __restrict__ y, int64_t ldy, int64_t bsy,
                                                    const float* __restrict__ node_w, const float* __restrict__ chan_w,
                                                    float inv_wsum, float grad_scale, float* __restrict__ dd,
                                                    float* __restrict__ out_state, float* __restrict__ part,
-                                                   int32_t B, int32_t G, int32_t C) {
+                                                   int32_t B, int32_t G, int32_t C, int64_t ldo, int64_t bso) {
   __shared__ float red[4];
   const int64_t total = (int64_t)B * G * C;
   float acc = 0.f;
@@ -104,7 +108,16 @@ __global__ __launch_bounds__(256) void wmse_kernel(const float* __restrict__ del
     if (node_w) w *= node_w[g];
     const float d = o - t;
     acc += (d * d) * w;
-    if (dd) dd[idx] = 2.f * w * d * inv_wsum * grad_scale;
+    if (OUTLD) {
+      if (dd) {
+        float* row = dd + b * bso + (int64_t)g * ldo;
+        row[c] = 2.f * w * d * inv_wsum * grad_scale;
+        if (c == C - 1)
+          for (int q = C; q < ldo; ++q) row[q] = 0.f;
+      }
+    } else {
+      if (dd) dd[idx] = 2.f * w * d * inv_wsum * grad_scale;
+    }
     if (out_state) out_state[idx] = o;
   }
   for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
@@ -372,6 +385,43 @@ __global__ __launch_bounds__(256) void ar_step_bwd_kernel(const float* __restric
   }
 }
 
+// The same with row / batch strides on dd and d_delta (gcl_ar_step_bwd_ld): columns C <= c < ldo of every d_delta row are
+// written as zeros.  STATE == false (no d_state): only the last window slot is visited, B * G * C elements instead of
+// B * G * obs * C.  The arithmetic of every element is that of ar_step_bwd_kernel.
+template <bool STATE>
+__global__ __launch_bounds__(256) void ar_step_bwd_ld_kernel(const float* __restrict__ dd, int64_t ldd, int64_t bsd,
+                                                             const float* __restrict__ g_loss,
+                                                             const float* __restrict__ g_new,
+                                                             const int32_t* __restrict__ chan_kind, int32_t has_y,
+                                                             int32_t residual, float* __restrict__ d_delta, int64_t ldo,
+                                                             int64_t bso, float* __restrict__ d_state, int32_t B,
+                                                             int32_t G, int32_t obs, int32_t C) {
+  const float gl = g_loss ? *g_loss : 1.f;
+  const int64_t total = (int64_t)B * G * (STATE ? obs : 1) * C;
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  // with the state: (b * G + g, slot, c) as in ar_step_bwd_kernel; without: (b, g, c) of the last slot
+  for (Walk3 w(idx, stride, STATE ? obs : G, C); idx < total; idx += stride, w.next()) {
+    const int c = w.c, k = STATE ? w.i : obs - 1;
+    const int64_t bb = STATE ? (int64_t)((uint64_t)w.b / (uint32_t)G) : w.b;
+    const int64_t gg = STATE ? w.b - bb * G : (int64_t)w.i;
+    const int64_t sidx = STATE ? idx : ((bb * G + gg) * obs + (obs - 1)) * C + c;  // this element in [B, G, obs, C]
+    float ds = (STATE && g_new && k >= 1) ? g_new[sidx - C] : 0.f;
+    if (k == obs - 1) {
+      int kind = chan_kind ? chan_kind[c] : 0;
+      if (kind == 2 && !has_y) kind = 0;
+      const float gd = gl * dd[bb * bsd + gg * ldd + c];
+      const float gn = g_new ? g_new[sidx] : 0.f;
+      float* row = d_delta + bb * bso + gg * ldo;
+      row[c] = gd + (kind == 0 ? gn : 0.f);
+      if (c == C - 1)
+        for (int q = C; q < ldo; ++q) row[q] = 0.f;
+      ds += (residual ? gd : 0.f) + ((kind == 1 || (kind == 0 && residual)) ? gn : 0.f);
+    }
+    if (STATE) d_state[sidx] = ds;
+  }
+}
+
 // dst[b, i, c] = (i < rows_src && c < F_src) ? src[b, i, c] : 0   for i < rows_dst, c < F_dst: widens a gradient to the
 // zero-padded layout of a layer whose output was returned as a row / column slice (the decoder returns the grid rows
 // and the first 33 / 19 columns of its last, 36- / 20-wide conv: src/models.py:870-872).
@@ -422,23 +472,47 @@ extern "C" size_t gcl_wmse_ws_bytes(int32_t B, int32_t G, int32_t C) {
   return (size_t)kLossBlocks * sizeof(float);
 }
 
-extern "C" int gcl_wmse_fwd_bwd(const float* delta, int64_t ldd, int64_t bsd, const float* x_last, int64_t ldx,
-                                int64_t bsx, const float* y, int64_t ldy, int64_t bsy, const float* node_w,
-                                const float* chan_w, float inv_wsum, float grad_scale, float* d_delta,
-                                float* out_state, const float* loss_prev, float* loss_out, int32_t B, int32_t G,
-                                int32_t C, void* ws, size_t ws_bytes, gcl_stream_t stream) {
+static int wmse_impl(const float* delta, int64_t ldd, int64_t bsd, const float* x_last, int64_t ldx, int64_t bsx,
+                     const float* y, int64_t ldy, int64_t bsy, const float* node_w, const float* chan_w, float inv_wsum,
+                     float grad_scale, float* d_delta, bool outld, int64_t ldd_out, int64_t bsd_out, float* out_state,
+                     const float* loss_prev, float* loss_out, int32_t B, int32_t G, int32_t C, void* ws, size_t ws_bytes,
+                     gcl_stream_t stream) {
   GCL_CHECK_ARG(delta && y && loss_out, "wmse: null argument");
   GCL_CHECK_ARG(B > 0 && G > 0 && C > 0 && ldd >= C && ldy >= C && (!x_last || ldx >= C), "wmse: bad shape");
   GCL_CHECK_ARG(ws && ws_bytes >= gcl_wmse_ws_bytes(B, G, C), "wmse: workspace too small");
   hipStream_t st = (hipStream_t)stream;
   const int64_t total = (int64_t)B * G * C;
   const unsigned nb = grid_for(total, kLossBlocks);
-  hipLaunchKernelGGL(wmse_kernel, dim3(nb), dim3(256), 0, st, delta, ldd, bsd, x_last, ldx, bsx, y, ldy, bsy, node_w,
-                     chan_w, inv_wsum, grad_scale, d_delta, out_state, (float*)ws, B, G, C);
+  if (outld)
+    hipLaunchKernelGGL(wmse_kernel<true>, dim3(nb), dim3(256), 0, st, delta, ldd, bsd, x_last, ldx, bsx, y, ldy, bsy, node_w,
+                       chan_w, inv_wsum, grad_scale, d_delta, out_state, (float*)ws, B, G, C, ldd_out, bsd_out);
+  else
+    hipLaunchKernelGGL(wmse_kernel<false>, dim3(nb), dim3(256), 0, st, delta, ldd, bsd, x_last, ldx, bsx, y, ldy, bsy, node_w,
+                       chan_w, inv_wsum, grad_scale, d_delta, out_state, (float*)ws, B, G, C, (int64_t)0, (int64_t)0);
   hipLaunchKernelGGL(wmse_final_kernel, dim3(1), dim3(256), 0, st, (const float*)ws, (int)nb, inv_wsum, loss_prev,
                      loss_out);
   GCL_CHECK_LAUNCH();
   return GCL_OK;
+}
+
+extern "C" int gcl_wmse_fwd_bwd(const float* delta, int64_t ldd, int64_t bsd, const float* x_last, int64_t ldx,
+                                int64_t bsx, const float* y, int64_t ldy, int64_t bsy, const float* node_w,
+                                const float* chan_w, float inv_wsum, float grad_scale, float* d_delta,
+                                float* out_state, const float* loss_prev, float* loss_out, int32_t B, int32_t G,
+                                int32_t C, void* ws, size_t ws_bytes, gcl_stream_t stream) {
+  return wmse_impl(delta, ldd, bsd, x_last, ldx, bsx, y, ldy, bsy, node_w, chan_w, inv_wsum, grad_scale, d_delta, false, 0, 0,
+                   out_state, loss_prev, loss_out, B, G, C, ws, ws_bytes, stream);
+}
+
+extern "C" int gcl_wmse_fwd_bwd_ld(const float* delta, int64_t ldd, int64_t bsd, const float* x_last, int64_t ldx,
+                                   int64_t bsx, const float* y, int64_t ldy, int64_t bsy, const float* node_w,
+                                   const float* chan_w, float inv_wsum, float grad_scale, float* d_delta, int64_t ldd_out,
+                                   int64_t bsd_out, float* out_state, const float* loss_prev, float* loss_out, int32_t B,
+                                   int32_t G, int32_t C, void* ws, size_t ws_bytes, gcl_stream_t stream) {
+  GCL_CHECK_ARG(!d_delta || (ldd_out >= C && bsd_out >= (int64_t)(G - 1) * ldd_out + ldd_out),
+                "wmse: output rows overlap (ldd_out=%lld, bsd_out=%lld)", (long long)ldd_out, (long long)bsd_out);
+  return wmse_impl(delta, ldd, bsd, x_last, ldx, bsx, y, ldy, bsy, node_w, chan_w, inv_wsum, grad_scale, d_delta, true, ldd_out,
+                   bsd_out, out_state, loss_prev, loss_out, B, G, C, ws, ws_bytes, stream);
 }
 
 extern "C" int gcl_adam_step(float* p, const float* g, float* m, float* v, int64_t count, float lr, float beta1,
@@ -517,6 +591,27 @@ extern "C" int gcl_ar_step_bwd(const float* dd, const float* g_loss, const float
   const int64_t total = (int64_t)B * G * obs * C;
   hipLaunchKernelGGL(ar_step_bwd_kernel, dim3(grid_for(total, 8192)), dim3(256), 0, (hipStream_t)stream, dd, g_loss,
                      g_new, chan_kind, has_y, residual, d_delta, d_state, B, G, obs, C);
+  GCL_CHECK_LAUNCH();
+  return GCL_OK;
+}
+
+extern "C" int gcl_ar_step_bwd_ld(const float* dd, int64_t ldd, int64_t bsd, const float* g_loss, const float* g_new,
+                                  const int32_t* chan_kind, int32_t has_y, int32_t residual, float* d_delta, int64_t ldd_out,
+                                  int64_t bsd_out, float* d_state, int32_t B, int32_t G, int32_t obs, int32_t C,
+                                  gcl_stream_t stream) {
+  GCL_CHECK_ARG(dd && d_delta, "ar_step_bwd: null argument");
+  GCL_CHECK_ARG(B > 0 && G > 0 && obs >= 1 && C > 0 && ldd >= C, "ar_step_bwd: bad shape");
+  GCL_CHECK_ARG(ldd_out >= C && bsd_out >= (int64_t)G * ldd_out, "ar_step_bwd: output rows overlap (ldd_out=%lld, bsd_out=%lld)",
+                (long long)ldd_out, (long long)bsd_out);
+  if (d_state) {
+    const int64_t total = (int64_t)B * G * obs * C;
+    hipLaunchKernelGGL(ar_step_bwd_ld_kernel<true>, dim3(grid_for(total, 8192)), dim3(256), 0, (hipStream_t)stream, dd, ldd,
+                       bsd, g_loss, g_new, chan_kind, has_y, residual, d_delta, ldd_out, bsd_out, d_state, B, G, obs, C);
+  } else {
+    const int64_t total = (int64_t)B * G * C;
+    hipLaunchKernelGGL(ar_step_bwd_ld_kernel<false>, dim3(grid_for(total, 8192)), dim3(256), 0, (hipStream_t)stream, dd, ldd,
+                       bsd, g_loss, g_new, chan_kind, has_y, residual, d_delta, ldd_out, bsd_out, d_state, B, G, obs, C);
+  }
   GCL_CHECK_LAUNCH();
   return GCL_OK;
 }

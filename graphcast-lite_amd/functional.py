@@ -59,6 +59,44 @@ def _token(like: torch.Tensor, shape):  # a stride-0 zero: stands in autograd's 
     return z.expand(shape)
 
 
+_ONE = {}  # device -> the constant one that stands for d loss / d loss (const_one): never written after it is made
+
+
+def const_one(like: torch.Tensor):
+    """The upstream gradient of a scalar loss as ONE tensor per device, made outside any capture and only ever read (like
+    the zero of _token).  ARStepLossFn.backward recognises it by its address and then has nothing to multiply.  None when
+    the first use on a device falls inside a stream capture (the caller then lets autograd make its own)."""
+    one = _ONE.get(like.device)
+    if one is None:
+        if like.is_cuda and torch.cuda.is_current_stream_capturing():
+            return None
+        with torch.inference_mode(False):
+            one = _ONE[like.device] = torch.ones((), dtype=torch.float32, device=like.device)
+    return one
+
+
+def _loss_grad_inplace() -> bool:
+    """GCL_NO_LOSS_GRAD_INPLACE=1 (read per call): the loss gradient is born dense, scaled by gcl_ar_step_bwd and widened
+    by gcl_pad_rows again."""
+    return os.environ.get("GCL_NO_LOSS_GRAD_INPLACE", "0") != "1"
+
+
+def _wide_in_place(dy: torch.Tensor, Fp: int):
+    """dy [B, rows, Fo] (Fo <= Fp) as the [B, rows, Fp] tensor it is a column slice of, when it can be read so where it
+    lies: unit channel stride, rows Fp apart, samples rows * Fp apart, a 16-byte aligned base and a storage that holds all
+    B * rows * Fp floats behind it (a foreign view may end inside the last row's padding).  None otherwise.  The columns
+    Fo.. must hold finite values, as gcl_linear_bwd_all asks of padded rows; the library's own producers write zeros."""
+    if dy.dim() != 3 or dy.dtype != torch.float32 or not dy.is_cuda:
+        return None
+    B, rows, Fo = dy.shape
+    if Fo > Fp or rows == 0 or dy.stride(2) != 1 or dy.stride(1) != Fp or dy.stride(0) != rows * Fp or dy.data_ptr() % 16:
+        return None
+    off = dy.storage_offset()
+    if (off + B * rows * Fp) * 4 > dy.untyped_storage().nbytes():
+        return None
+    return torch.as_strided(dy, (B, rows, Fp), (rows * Fp, Fp, 1), off)
+
+
 def _flat3(x: torch.Tensor):
     """[B,n,F] (or [n,F]) -> contiguous [B,n,F]."""
     if x.dim() == 2:
@@ -377,11 +415,16 @@ class GCNStackFn(torch.autograd.Function):
         G = _Grads(list(params), needs)
         dy, parts = GradLanding.claim_parts(ctx.split, dy)  # parts: (head rows [B, head, F], tail rows [B, n - head, F])
         dy, dy_map = GradLanding.claim(ctx.land, dy)
+        pad = ctx.pad_last
+        # a gradient that already lies in the padded layout of the last conv (the loss writes it so) is read where it is:
+        # no widened copy, the rows that were not returned are the zero tail of gcl_aggregate_head
+        wide = None
+        if pad is not None and dy_map is None and parts is None and _loss_grad_inplace():
+            wide = _wide_in_place(dy, pad[0])
         # (with a map or with parts `dy` is the token: only its shape is used)
-        dy3 = dy if (dy_map is not None or parts is not None) else _flat3(dy)
+        dy3 = dy if (dy_map is not None or parts is not None or wide is not None) else _flat3(dy)
         B, n = dy3.shape[0], ctx.n_rows
         ps = ctx.ps
-        pad = ctx.pad_last
         dy_rows = dy3  # gradient of the rows that were returned (bias gradient of the last conv sums these)
         if ctx.out_rows and (ctx.has_ln or pad is None):
             dy3 = hip.pad_rows(dy3, n, dy3.shape[2])  # rows that were not returned carry a zero gradient
@@ -414,11 +457,14 @@ class GCNStackFn(torch.autograd.Function):
             # layout (extra rows / columns 0) in one pass; the dense backward then reads it Fout wide with row stride Fp
             # - the padding columns only ever meet zero weights - so dW / dX need no padded weight copy.
             Fp = pad[0]
-            dp = hip.pad_rows(dy_rows if not ctx.has_ln else dp, n, Fp)
+            dp = hip.pad_rows(dy_rows if not ctx.has_ln else dp, n, Fp) if wide is None else None
         if G.dst[bi_last] is not None and not cs_done:  # bias of the last conv: its dp comes from outside this stack
             src = dy_rows if not ctx.has_ln else dp[..., :Fo]
             if parts is not None:
                 hip.colsum_split(parts[0], parts[1], G.dst[bi_last], G.acc[bi_last])
+            elif wide is not None:  # the same rows, Fp apart (a reshape would copy them)
+                hip.colsum(torch.as_strided(dy, (B * dy.shape[1], Fo), (Fp, 1), dy.storage_offset()), G.dst[bi_last],
+                           G.acc[bi_last])
             else:
                 hip.colsum(src.reshape(-1, Fo), G.dst[bi_last], G.acc[bi_last])
         dzc = None
@@ -432,6 +478,8 @@ class GCNStackFn(torch.autograd.Function):
                 dh2 = hip.aggregate_present(graph, dp, ctx.present, transpose=True).view(B * n, -1)
             elif k == L - 1 and parts is not None:
                 dh2 = hip.aggregate_split(graph, parts[0], parts[1], transpose=True).view(B * n, -1)
+            elif k == L - 1 and wide is not None:
+                dh2 = hip.aggregate_head(graph, wide, transpose=True).view(B * n, -1)
             elif (k == 0 and ctx.lat is not None and ctx.lat.smap is not None and ctx.lat.Md > 0 and _compact_store()
                   and dp.is_contiguous() and hip.aggregate_compact_ok(graph, dp, transpose=True)):
                 # the Md batch-dependent rows go straight into the compact gradient of _lat_first_layer_bwd, the others
@@ -682,8 +730,13 @@ class ARStepLossFn(torch.autograd.Function):
         if d3.stride(2) != 1:
             d3 = d3.contiguous()
         x_last = st[:, :, obs - 1, :] if residual else None
+        # delta with rows padded to whole 16 bytes (the decoder's last conv stores 33 / 19 columns 36 / 20 wide): its
+        # gradient is born in the same row layout, zero padding columns included, where the decoder's backward reads it
+        ctx.inplace = _loss_grad_inplace()
+        ldp = (Cc + 3) // 4 * 4
+        ctx.ldo = ldp if (ctx.inplace and ldp != Cc and d3.stride(1) == ldp) else None
         loss, dd, _ = hip.wmse_fwd_bwd(d3, x_last, y3, node_w, chan_w, inv_wsum, 1.0, want_grad=True,
-                                       loss_prev=loss_prev.detach() if loss_prev is not None else None)
+                                       loss_prev=loss_prev.detach() if loss_prev is not None else None, ldd_out=ctx.ldo)
         new_state = hip.ar_advance(st, d3, y3, kinds, None, 0, residual) if advance else st.new_empty(0)
         ctx.dd, ctx.kinds, ctx.residual, ctx.advance, ctx.obs, ctx.has_y = dd, kinds, residual, advance, obs, y3 is not None
         if not advance:
@@ -693,8 +746,14 @@ class ARStepLossFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_loss, g_new):
         g_new = g_new if (ctx.advance and g_new is not None and g_new.numel()) else None
+        one = _ONE.get(g_loss.device)
+        if (ctx.inplace and g_new is None and not ctx.needs_input_grad[0] and one is not None
+                and g_loss.data_ptr() == one.data_ptr()):
+            # the upstream gradient is the constant one: dd IS d_delta, no launch (a view, so that nothing adds into dd)
+            return None, ctx.dd[..., :ctx.dd.shape[2]], None, (g_loss if ctx.needs_input_grad[3] else None), None, None, None, \
+                None, None, None
         d_delta, d_state = hip.ar_step_bwd(ctx.dd, g_loss, g_new, ctx.kinds, ctx.has_y, ctx.residual, ctx.obs,
-                                           want_state=ctx.needs_input_grad[0])
+                                           want_state=ctx.needs_input_grad[0], ldd_out=ctx.ldo)
         return d_state, d_delta, None, (g_loss if ctx.needs_input_grad[3] else None), None, None, None, None, None, None
 
 

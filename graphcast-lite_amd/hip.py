@@ -59,6 +59,7 @@ _SIGNATURES = {
     "gcl_aggregate_heavy_launches": (_i64, []),
     "gcl_aggregate_split": (C.c_int, [_vp, _i32, _vp, _i64, _i64, _vp, _i64, _i64, _i32, _vp, _vp, _i64, _i64, _i32, _i32,
                                       _vp]),
+    "gcl_aggregate_head": (C.c_int, [_vp, _i32, _vp, _i64, _i64, _i32, _vp, _vp, _i64, _i64, _i32, _i32, _vp]),
     "gcl_gat_fwd": (C.c_int, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _vp]),
     "gcl_gat_bwd": (C.c_int, [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64,
                               _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _sz, _vp]),
@@ -91,7 +92,11 @@ _SIGNATURES = {
     "gcl_assemble_input_tail": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp]),
     "gcl_wmse_fwd_bwd": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _f32, _f32, _vp,
                                    _vp, _vp, _vp, _i32, _i32, _i32, _vp, _sz, _vp]),
+    "gcl_wmse_fwd_bwd_ld": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _f32, _f32, _vp, _i64, _i64,
+                                      _vp, _vp, _vp, _i32, _i32, _i32, _vp, _sz, _vp]),
     "gcl_ar_step_bwd": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
+    "gcl_ar_step_bwd_ld": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _i32, _i32, _vp, _i64, _i64, _vp, _i32, _i32, _i32, _i32,
+                                     _vp]),
     "gcl_pad_rows": (C.c_int, [_vp, _i64, _i64, _i32, _i32, _vp, _i64, _i64, _i32, _i32, _i32, _vp]),
     "gcl_zero": (C.c_int, [_vp, _sz, _vp]),
     "gcl_wmse_ws_bytes": (_sz, [_i32, _i32, _i32]),
@@ -701,6 +706,21 @@ def aggregate_split(graph: Graph, a3, b3, transpose=False, out=None):
     return out
 
 
+def aggregate_head(graph: Graph, a3, transpose=False, out=None):
+    """hip.aggregate over a source whose rows >= head are zeros that are stored nowhere: a3 [B, head, F] are rows < head of
+    every sample (rows whole 16-byte units, as for aggregate_split).  Reported to the launch probe under a kind of its own."""
+    B, head, F = a3.shape
+    n = graph.n
+    assert 0 < head <= n and a3.stride(2) == 1
+    if out is None:
+        out = torch.empty(B, n, F, dtype=torch.float32, device=a3.device)
+    tok = _probe_begin("aggregate_head", graph=graph, transpose=bool(transpose), B=B, F=F)
+    _check(lib().gcl_aggregate_head(graph.handle, _agg_flags(transpose), _p(a3), a3.stride(1), a3.stride(0), head, None,
+                                    _p(out), out.stride(1), out.stride(0), B, F, _stream()))
+    _probe_end(tok)
+    return out
+
+
 def layernorm_fwd(x, gamma, beta, eps=1e-5):
     rows, F = x.shape
     y = torch.empty(rows, F, dtype=torch.float32, device=x.device)
@@ -907,22 +927,31 @@ def assemble_input(x3, grid_static, mesh_static, tail3=None):
 
 
 def wmse_fwd_bwd(delta3, x_last3, y3, node_w, chan_w, inv_wsum, grad_scale, want_grad=True, want_state=False,
-                 loss_prev=None):
-    """delta3 [B,G,C] contiguous; x_last3 / y3 may be strided views (unit channel stride)."""
+                 loss_prev=None, ldd_out=None):
+    """delta3 [B,G,C] contiguous; x_last3 / y3 may be strided views (unit channel stride).  ldd_out (>= C): the gradient
+    is the [..., :C] view of a contiguous [B, G, ldd_out] tensor whose other columns are written as zeros
+    (gcl_wmse_fwd_bwd_ld); the loss and the values are the same."""
     B, G, Cc = delta3.shape
     dev = delta3.device
     if delta3.stride(2) != 1:
         delta3 = delta3.contiguous()  # (a row-strided view - e.g. the grid rows of a padded output - is read in place)
-    dd = torch.empty(B, G, Cc, dtype=torch.float32, device=dev) if want_grad else None
+    dd = None
+    if want_grad:
+        dd = torch.empty(B, G, ldd_out if ldd_out else Cc, dtype=torch.float32, device=dev)
     st = torch.empty(B, G, Cc, dtype=torch.float32, device=dev) if want_state else None
     loss = torch.empty((), dtype=torch.float32, device=dev)
     nb = lib().gcl_wmse_ws_bytes(B, G, Cc)
     ws = workspace(nb, dev)
     xl = x_last3
-    _check(lib().gcl_wmse_fwd_bwd(
-        _p(delta3), delta3.stride(1), delta3.stride(0), _p(xl), xl.stride(1) if xl is not None else 0, xl.stride(0) if xl is not None else 0,
-        _p(y3), y3.stride(1), y3.stride(0), _p(node_w), _p(chan_w), float(inv_wsum), float(grad_scale), _p(dd), _p(st),
-        _p(loss_prev), _p(loss), B, G, Cc, ws.data_ptr(), ws.numel(), _stream()))
+    head = (_p(delta3), delta3.stride(1), delta3.stride(0), _p(xl), xl.stride(1) if xl is not None else 0,
+            xl.stride(0) if xl is not None else 0, _p(y3), y3.stride(1), y3.stride(0), _p(node_w), _p(chan_w), float(inv_wsum),
+            float(grad_scale), _p(dd))
+    tail = (_p(st), _p(loss_prev), _p(loss), B, G, Cc, ws.data_ptr(), ws.numel(), _stream())
+    if ldd_out:
+        assert ldd_out >= Cc
+        _check(lib().gcl_wmse_fwd_bwd_ld(*head, int(ldd_out), G * int(ldd_out), *tail))
+        return loss, (dd[..., :Cc] if dd is not None else None), st
+    _check(lib().gcl_wmse_fwd_bwd(*head, *tail))
     return loss, dd, st
 
 
@@ -1065,13 +1094,23 @@ def ar_advance(state4, delta3, y_step3, chan_kind, out3, out_off: int, residual:
     return new_state
 
 
-def ar_step_bwd(dd3, g_loss, g_new4, chan_kind, has_y: bool, residual: bool, obs: int, want_state: bool):
-    """Backward of one autoregressive training step (see gcl_ar_step_bwd): (d_delta [B,G,C], d_state [B,G,obs,C] | None)."""
+def ar_step_bwd(dd3, g_loss, g_new4, chan_kind, has_y: bool, residual: bool, obs: int, want_state: bool, ldd_out=None):
+    """Backward of one autoregressive training step (see gcl_ar_step_bwd): (d_delta [B,G,C], d_state [B,G,obs,C] | None).
+    ldd_out: d_delta is the [..., :C] view of a contiguous [B, G, ldd_out] tensor with zero padding columns, and dd3 may be
+    such a view itself (gcl_ar_step_bwd_ld)."""
     B, G, Cc = dd3.shape
-    d_delta = torch.empty_like(dd3)
     d_state = torch.empty(B, G, obs, Cc, dtype=torch.float32, device=dd3.device) if want_state else None
     if g_new4 is not None and not g_new4.is_contiguous():
         g_new4 = g_new4.contiguous()
+    if ldd_out or not dd3.is_contiguous():
+        assert dd3.stride(2) == 1
+        ldo = int(ldd_out) if ldd_out else Cc
+        d_delta = torch.empty(B, G, ldo, dtype=torch.float32, device=dd3.device)
+        _check(lib().gcl_ar_step_bwd_ld(_p(dd3), dd3.stride(1), dd3.stride(0), _p(g_loss), _p(g_new4), _pi(chan_kind),
+                                        1 if has_y else 0, 1 if residual else 0, _p(d_delta), ldo, G * ldo, _p(d_state), B, G,
+                                        obs, Cc, _stream()))
+        return d_delta[..., :Cc], d_state
+    d_delta = torch.empty_like(dd3)
     _check(lib().gcl_ar_step_bwd(_p(dd3), _p(g_loss), _p(g_new4), _pi(chan_kind), 1 if has_y else 0, 1 if residual else 0,
                                  _p(d_delta), _p(d_state), B, G, obs, Cc, _stream()))
     return d_delta, d_state

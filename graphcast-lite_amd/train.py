@@ -16,7 +16,7 @@ import torch.distributed as dist
 
 from . import hip
 from .capture import Captured, graph_enabled
-from .functional import ARStepLossFn, WeightedMSEFn
+from .functional import ARStepLossFn, WeightedMSEFn, const_one
 
 
 class FileNames:
@@ -695,16 +695,12 @@ class TrainStep(Captured):
         return loss.detach()
 
     def _loss_root(self, loss):
-        """The gradient of the loss with respect to itself: a one that is made once (in an eager step, never inside a
-        capture) and only ever read, instead of the fill launch autograd would issue in every step.  None: autograd's own."""
-        one = getattr(self, "_one", None)
-        if one is not None and one.device == loss.device and one.dtype == loss.dtype and loss.dim() == 0:
-            return one
-        if loss.dim() != 0 or not loss.is_cuda or torch.cuda.is_current_stream_capturing():
+        """The gradient of the loss with respect to itself: the constant one of functional.const_one (made once per device,
+        never inside a capture, only ever read) instead of the fill launch autograd would issue in every step - and the
+        loss's backward, which knows that tensor, multiplies nothing by it.  None: autograd's own."""
+        if loss.dim() != 0 or not loss.is_cuda or loss.dtype != torch.float32:
             return None
-        with torch.inference_mode(False):
-            self._one = torch.ones((), dtype=loss.dtype, device=loss.device)
-        return self._one
+        return const_one(loss)
 
     def _finish(self):
         scale = allreduce_gradients(self.flat, self.world)

@@ -258,6 +258,12 @@ int gcl_aggregate_present(const gcl_graph_t* g, int32_t transpose, const float* 
 int gcl_aggregate_split(const gcl_graph_t* g, int32_t transpose, const float* h, int64_t ldh, int64_t bsh,
                         const float* h2, int64_t ldh2, int64_t bsh2, int32_t head, const float* bias, float* y,
                         int64_t ldy, int64_t bsy, int32_t B, int32_t F, gcl_stream_t stream);
+/* The two-part form whose second part is all zeros: rows j < head of every sample are h + b * bsh + j * ldh, rows
+ * j >= head count as rows of zeros that the library supplies itself (the gradient of a layer that returned only its
+ * first `head` rows, read where its producer left it instead of from a zero-filled copy).  Same conditions on h and y as
+ * gcl_aggregate_split; 0 < head <= n.  Bit-equal to gcl_aggregate on h widened with zero rows. */
+int gcl_aggregate_head(const gcl_graph_t* g, int32_t transpose, const float* h, int64_t ldh, int64_t bsh, int32_t head,
+                       const float* bias, float* y, int64_t ldy, int64_t bsy, int32_t B, int32_t F, gcl_stream_t stream);
 /* gcl_aggregate with a STORE map: smap [n] has one entry per row, >= 0 = that row of every sample is stored to row
  * smap[i] of the compact destination yc [B, *, F] INSTEAD of y, < 0 = stored to y as always.  Each row is written once,
  * to one place, with gcl_aggregate's bits; the rows of y with an entry >= 0 are not touched.  Only the source-tile kernel
@@ -421,6 +427,14 @@ int gcl_wmse_fwd_bwd(const float* delta, int64_t ldd, int64_t bsd, const float* 
                      const float* chan_w, float inv_wsum, float grad_scale, float* d_delta,
                      float* out_state, const float* loss_prev, float* loss_out, int32_t B, int32_t G,
                      int32_t C, void* ws, size_t ws_bytes, gcl_stream_t stream);
+/* The same with the gradient written in a caller-given layout: d_delta[b, g, c] goes to d_delta + b * bsd_out +
+ * g * ldd_out + c, and the columns C <= c < ldd_out of every row are written as zeros (ldd_out >= C, bsd_out >=
+ * G * ldd_out).  Loss, gradient values, partial sums and their order are those of gcl_wmse_fwd_bwd. */
+int gcl_wmse_fwd_bwd_ld(const float* delta, int64_t ldd, int64_t bsd, const float* x_last, int64_t ldx,
+                        int64_t bsx, const float* y, int64_t ldy_, int64_t bsy, const float* node_w,
+                        const float* chan_w, float inv_wsum, float grad_scale, float* d_delta, int64_t ldd_out,
+                        int64_t bsd_out, float* out_state, const float* loss_prev, float* loss_out, int32_t B,
+                        int32_t G, int32_t C, void* ws, size_t ws_bytes, gcl_stream_t stream);
 size_t gcl_wmse_ws_bytes(int32_t B, int32_t G, int32_t C);
 
 /* torch.optim.Adam step (src/main.py:212, src/train.py:233) over one flat parameter buffer:
@@ -560,6 +574,13 @@ int gcl_ar_advance(const float* state, const float* delta, int64_t ldd, int64_t 
 int gcl_ar_step_bwd(const float* dd, const float* g_loss, const float* g_new, const int32_t* chan_kind,
                     int32_t has_y, int32_t residual, float* d_delta, float* d_state, int32_t B, int32_t G,
                     int32_t obs, int32_t C, gcl_stream_t stream);
+/* The same with dd read as dd + b * bsd + g * ldd + c and d_delta written as d_delta + b * bsd_out + g * ldd_out + c, the
+ * columns C <= c < ldd_out of every row as zeros (g_new and d_state stay contiguous).  Without d_state only the last
+ * window slot is visited.  Element for element the values of gcl_ar_step_bwd. */
+int gcl_ar_step_bwd_ld(const float* dd, int64_t ldd, int64_t bsd, const float* g_loss, const float* g_new,
+                       const int32_t* chan_kind, int32_t has_y, int32_t residual, float* d_delta, int64_t ldd_out,
+                       int64_t bsd_out, float* d_state, int32_t B, int32_t G, int32_t obs, int32_t C,
+                       gcl_stream_t stream);
 
 /* dst[b, i, c] = (i < rows_src && c < F_src) ? src[b, i, c] : 0 for i < rows_dst, c < F_dst: the gradient of a row /
  * column slice (decoder output: grid rows, first 33 / 19 columns - src/models.py:870-872) widened to the sliced
