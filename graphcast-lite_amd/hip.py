@@ -228,6 +228,13 @@ _SIGNATURES = {
     "gcl_eval_accumulate": (C.c_int, [_vp, _vp, _vp, C.c_double, _i32, _i32, _i32, _vp, _vp]),
     "gcl_tensor_batch_pack": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i32, _i64, _i32, _i32, _i32, _vp, _i32, _vp, _i64,
                                         _i64, _vp, _i64, _i64, _vp]),
+    "gcl_region_cache_record_bytes": (_sz, [_i32] * 7),
+    "gcl_region_cache_store": (C.c_int, [_vp, _i64, _i64] * 5 + [_vp, _vp, _vp, _vp, _i64] + [_i32] * 10 + [_vp]),
+    "gcl_region_cache_fetch": (C.c_int, [_vp, _i64, _vp] + [_i32] * 8 + [_vp, _i64] * 4 + [_vp]),
+    "gcl_region_eval_pair_ws_bytes": (_sz, [_i32] * 4),
+    "gcl_region_eval_pair": (C.c_int, [_i32] + [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _i64, _i64] * 2
+                             + [_vp, _i64, _i64, _vp, _i32, _vp, _i32, C.c_double, _vp, _i32, _i32, _i32, _i32, _vp, _sz,
+                                _vp]),
 }
 
 
@@ -2275,3 +2282,123 @@ def tensor_batch_pack(X4, Y4, idx, Wxu: int, Wyu: int, Fu: int, out=None):
     _check(lib().gcl_tensor_batch_pack(_p(X4), Wx, int(Wxu), _p(Y4), Wy, int(Wyu), N, G, F, int(Fu), _pl(idx), B, _p(X), ldx,
                                        bsx, _p(Y) if Y4 is not None else None, ldy, bsy, _stream()))
     return X, (Y if Y4 is not None else None)
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# Training and scoring the regional heads (csrc/region_train.hip)
+# ------------------------------------------------------------------------------------------------------------------
+class RegionRecord:
+    """Shape of one cache record (see gcl_region_cache_record_bytes): the used widths, the padded row widths and the
+    float offsets of the four parts.  Pure arithmetic (`nbytes` asks the library, which refuses unsupported shapes)."""
+
+    def __init__(self, n_roi: int, half_E: int, XF: int, D: int, Dm: int, C: int, P: int = 1):
+        self.n_roi, self.half_E, self.XF, self.D, self.Dm, self.C, self.P = (int(v) for v in (n_roi, half_E, XF, D, Dm, C, P))
+        up4 = lambda v: (v + 3) // 4 * 4
+        self.Sp, self.Dgp, self.Cp, self.Yp = up4(self.XF + self.D), up4(self.Dm), up4(self.C), up4(self.P * self.C)
+        self.sizes = (self.n_roi * self.Sp, self.half_E * self.Dgp, self.n_roi * self.Cp, self.n_roi * self.Yp)
+        self.offsets = (0, self.sizes[0], self.sizes[0] + self.sizes[1], self.sizes[0] + self.sizes[1] + self.sizes[2])
+        self.floats = sum(self.sizes)
+
+    @property
+    def dims(self):
+        return self.n_roi, self.half_E, self.XF, self.D, self.Dm, self.C, self.P
+
+    @property
+    def nbytes(self) -> int:
+        nb = lib().gcl_region_cache_record_bytes(*self.dims)
+        if nb != 4 * self.floats:
+            raise ValueError(f"region cache record {self.dims}: the library reports {nb} bytes, the layout {4 * self.floats}")
+        return nb
+
+    def parts(self, B: int, device):
+        """Fresh contiguous (roi3 [B, n_roi, Sp], send [B, half_E, Dgp], pred [B, n_roi, Cp], y [B, n_roi, Yp])."""
+        e = lambda r, w: torch.empty(B, r, w, dtype=torch.float32, device=device)
+        return e(self.n_roi, self.Sp), e(self.half_E, self.Dgp), e(self.n_roi, self.Cp), e(self.n_roi, self.Yp)
+
+
+def _cache_of(rec: RegionRecord, cache, who: str) -> int:
+    if cache.dim() != 2 or cache.shape[1] != rec.floats or not cache.is_contiguous() or cache.shape[0] == 0:
+        raise ValueError(f"{who}: the cache is a contiguous float32 [n_slots, {rec.floats}] tensor, got {tuple(cache.shape)}")
+    return cache.shape[0]
+
+
+def region_cache_store(rec: RegionRecord, cache, slots, pred3, lat3, mesh3, X3, y3, rows, snd):
+    """Records slots[b] (device int64 [B], distinct) of cache [n_slots, rec.floats] from one batch of global outputs (see
+    gcl_region_cache_store).  pred3 [B,G,C], lat3 [B,G,D], mesh3 [B,M,Dm], X3 [B,G,XF], y3 [B,G,P*C]: unit channel stride,
+    any row / batch stride.  rows int32 [n_roi], snd int32 [half_E]."""
+    n_slots = _cache_of(rec, cache, "region_cache_store")
+    B, G = X3.shape[0], X3.shape[1]
+    M = mesh3.shape[1]
+    want = {"pred": (pred3, (B, G, rec.C)), "lat": (lat3, (B, G, rec.D)), "mesh": (mesh3, (B, M, rec.Dm)),
+            "X": (X3, (B, G, rec.XF)), "y": (y3, (B, G, rec.P * rec.C))}
+    args = []
+    for name, (t, shape) in want.items():
+        if tuple(t.shape) != shape or t.stride(2) != 1:
+            raise ValueError(f"region_cache_store: {name} is a {shape} view with unit channel stride, got {tuple(t.shape)} / "
+                             f"{t.stride()}")
+        args += [_p(t), t.stride(1), t.stride(0)]
+    if rows.numel() != rec.n_roi or snd.numel() != rec.half_E or slots.numel() != B:
+        raise ValueError(f"region_cache_store: {rows.numel()} rows / {snd.numel()} senders / {slots.numel()} slots for a "
+                         f"record of {rec.n_roi} / {rec.half_E} and a batch of {B}")
+    _check(lib().gcl_region_cache_store(*args, _pi(rows), _pi(snd), _pl(slots), _p(cache), n_slots, B, G, M, *rec.dims,
+                                        _stream()))
+    return cache
+
+
+def region_cache_fetch(rec: RegionRecord, cache, slots, out=None):
+    """(roi3, send, pred, y) of the records slots (device int64 [B]; repeats allowed, a slot outside the cache gives zero
+    rows), one launch (see gcl_region_cache_fetch).  out: the four destination buffers (`rec.parts`), any of them None."""
+    n_slots = _cache_of(rec, cache, "region_cache_fetch")
+    B = slots.numel()
+    if out is None:
+        out = rec.parts(B, cache.device)
+    rows = (rec.n_roi, rec.half_E, rec.n_roi, rec.n_roi)
+    widths = (rec.Sp, rec.Dgp, rec.Cp, rec.Yp)
+    args = []
+    for t, r, w in zip(out, rows, widths):
+        if t is None:
+            args += [None, 0]
+            continue
+        if tuple(t.shape) != (B, r, w) or t.stride(2) != 1 or (r > 1 and t.stride(1) != w):
+            raise ValueError(f"region_cache_fetch: a destination is a [{B}, {r}, {w}] buffer with dense rows, got "
+                             f"{tuple(t.shape)} / {t.stride()}")
+        args += [_p(t), t.stride(0)]
+    _check(lib().gcl_region_cache_fetch(_p(cache), n_slots, _pl(slots), B, *rec.dims, *args, _stream()))
+    return tuple(out)
+
+
+def region_eval_pair(preds, y_step3, chan_kind, residual: bool, rows, weight: float, acc, obs: int, n=None):
+    """One lock-step AR step of one or two predictions and their ROI losses (see gcl_region_eval_pair).  preds: a list of
+    one or two (delta3 [B,G,C], win3 [B,G,obs*C], new_win4 [B,G,obs,C] contiguous | None, out3 [B,G,C] | None); y_step3
+    [B,G,C]; views with unit channel stride.  rows: int32 device rows the loss runs over (None: the first `n` rows, all G
+    by default).  acc: device float64 [len(preds)], acc[q] += weight * mean((step_out_q - y)^2 over the rows)."""
+    nq = len(preds)
+    B, G, Cc = preds[0][0].shape
+    n = rows.numel() if rows is not None else (G if n is None else int(n))
+    if nq not in (1, 2) or acc.numel() != nq:
+        raise ValueError(f"region_eval_pair: one or two predictions and a float64 [{nq}] accumulator, got {nq} and "
+                         f"{tuple(acc.shape)}")
+    if tuple(y_step3.shape) != (B, G, Cc):
+        raise ValueError(f"region_eval_pair: y_step {tuple(y_step3.shape)} is not [{B}, {G}, {Cc}]")
+    ldy, bsy = _bgc(y_step3, "region_eval_pair")
+    args = []
+    for delta3, win3, new4, out3 in preds:
+        if tuple(delta3.shape) != (B, G, Cc) or tuple(win3.shape[:2]) != (B, G) or win3.shape[2] < obs * Cc:
+            raise ValueError(f"region_eval_pair: delta {tuple(delta3.shape)} / window {tuple(win3.shape)} do not hold "
+                             f"[{B}, {G}, {Cc}] / [{B}, {G}, {obs * Cc}]")
+        if new4 is not None and (tuple(new4.shape) != (B, G, obs, Cc) or not new4.is_contiguous()):
+            raise ValueError(f"region_eval_pair: the new window is a contiguous [{B}, {G}, {obs}, {Cc}] tensor")
+        if out3 is not None and tuple(out3.shape) != (B, G, Cc):
+            raise ValueError(f"region_eval_pair: out {tuple(out3.shape)} is not [{B}, {G}, {Cc}]")
+        ldd, bsd = _bgc(delta3, "region_eval_pair")
+        ldw, bsw = _bgc(win3, "region_eval_pair")
+        ldo, bso = _bgc(out3, "region_eval_pair") if out3 is not None else (0, 0)
+        args += [_p(delta3), ldd, bsd, _p(win3), ldw, bsw, _p(new4), _p(out3), ldo, bso]
+    if nq == 1:
+        args += [None, 0, 0, None, 0, 0, None, None, 0, 0]
+    if chan_kind is not None and chan_kind.numel() != Cc:
+        raise ValueError(f"region_eval_pair: chan_kind holds {chan_kind.numel()} entries for {Cc} channels")
+    ws = workspace(lib().gcl_region_eval_pair_ws_bytes(nq, B, n, Cc), y_step3.device)
+    _check(lib().gcl_region_eval_pair(nq, *args, _p(y_step3), ldy, bsy, _pi(chan_kind), 1 if residual else 0, _pi(rows), n,
+                                      float(weight), _pd(acc), B, G, int(obs), Cc, ws.data_ptr(), ws.numel(), _stream()))
+    return acc

@@ -1212,6 +1212,60 @@ int gcl_tensor_batch_pack(const float* X, int32_t Wx, int32_t Wxu, const float* 
                           int32_t G, int32_t F, int32_t Fu, const int64_t* idx, int32_t B, float* outX, int64_t ldx,
                           int64_t bsx, float* outY, int64_t ldy, int64_t bsy, gcl_stream_t stream);
 
+/* ---- Training and scoring the regional heads (csrc/region_train.hip; scripts/train_dual_mesh.py) ----
+ * No entry point allocates, synchronises or reads back; no atomics; every reduction has a fixed order, so results are
+ * bit-equal from run to run.
+ *
+ * The cache of the frozen global model's outputs (`--precompute`, scripts/train_dual_mesh.py:548-580) on the device.  One
+ * record per sample, float32, four parts whose rows are zero-padded to a multiple of 4 floats (so every part is 16-byte
+ * aligned in a 16-byte aligned cache), with XF = obs * C:
+ *   roi3 [n_roi, roundup(XF + D, 4)] = [X[rows[i]] | latent[rows[i]] | 0]    (the roi_input of src/dual_mesh.py:683-686)
+ *   send [half_E, roundup(Dm, 4)]    = [mesh[snd[k]] | 0]                    (the cross senders' rows, :774-777)
+ *   pred [n_roi, roundup(C, 4)]      = [pred[rows[i]] | 0]
+ *   y    [n_roi, roundup(P * C, 4)]  = [y[rows[i]] | 0]
+ * gcl_region_cache_record_bytes: the size of one record (a multiple of 16), 0 for a shape that is not supported. */
+size_t gcl_region_cache_record_bytes(int32_t n_roi, int32_t half_E, int32_t XF, int32_t D, int32_t Dm, int32_t C,
+                                     int32_t P);
+/* precompute_global (src/dual_mesh.py:731-752) for a batch of B samples in one launch: record slots[b] (device int64,
+ * distinct within a call) of `cache` (n_slots records) is written from the dense global prediction pred [B,G,C], the
+ * grid latents lat [B,G,D], the processed mesh latents mesh [B,M,Dm], the input window X [B,G,XF] and the target y
+ * [B,G,P*C], each addressed with (ld, bs) as in gcl_roi_gather_rows.  rows: int32 [n_roi] grid rows; snd: int32 [half_E]
+ * mesh rows in the order the regional module takes them.  A row index outside its source gives a zero row; a slot
+ * outside [0, n_slots) is skipped.  Copies are bit-exact and pad columns are zero. */
+int gcl_region_cache_store(const float* pred, int64_t ldp, int64_t bsp, const float* lat, int64_t ldl, int64_t bsl,
+                           const float* mesh, int64_t ldm, int64_t bsm, const float* X, int64_t ldx, int64_t bsx,
+                           const float* y, int64_t ldy, int64_t bsy, const int32_t* rows, const int32_t* snd,
+                           const int64_t* slots, float* cache, int64_t n_slots, int32_t B, int32_t G, int32_t M,
+                           int32_t n_roi, int32_t half_E, int32_t XF, int32_t D, int32_t Dm, int32_t C, int32_t P,
+                           gcl_stream_t stream);
+/* `cache[batch_idx]` and its `.to(device)` calls (scripts/train_dual_mesh.py:180-185) in one launch: the four parts of
+ * the records slots[0..B) (device int64; a slot may repeat) go to roi3 / send / pred / y, each a [B, rows, padded width]
+ * buffer with a sample stride bs (floats, a multiple of 4) and 16-byte alignment; a NULL destination is left out.  A
+ * slot outside [0, n_slots) reads nothing and gives zero rows. */
+int gcl_region_cache_fetch(const float* cache, int64_t n_slots, const int64_t* slots, int32_t B, int32_t n_roi,
+                           int32_t half_E, int32_t XF, int32_t D, int32_t Dm, int32_t C, int32_t P, float* roi3,
+                           int64_t bs_roi, float* send, int64_t bs_send, float* pred, int64_t bs_pred, float* y,
+                           int64_t bs_y, gcl_stream_t stream);
+/* One autoregressive step of eval_dual (scripts/train_dual_mesh.py:318-356; cached mode :289-308) for nq = 1 or 2
+ * predictions - the corrected one and the global-only one - that advance in lock-step.  Per prediction q: delta_q
+ * [B,G,C] and its input window win_q [B,G,obs*C], both with (ld, bs); step_out is formed as gcl_ar_advance forms it,
+ * with the same bits (residual add of the window's last slot, static channels carried, forcing channels from y_step
+ * [B,G,C]; chan_kind NULL: all predicted); new_win_q (contiguous [B,G,obs,C], or NULL: no window traffic) takes the
+ * shifted window and out_q (with (ld, bs), or NULL; never delta_q or win_q themselves: the loss pass forms step_out
+ * from them again) the step_out.  acc[q] (device float64) += weight * mean over
+ * B * n * C of (step_out - y_step)^2 on the rows rows[0..n) (int32; NULL: rows 0..n), which is
+ * weighted_mse_loss(out_roi, y_roi, None); weight = 1 / steps adds the mean over the AR steps.  A row index outside
+ * [0, G) adds nothing.  Two-stage sum in float64: fixed chunks of 2048 elements, then the chunks in ascending order.
+ * ws: at least gcl_region_eval_pair_ws_bytes(nq, B, n, C) bytes of 8-byte aligned device scratch. */
+size_t gcl_region_eval_pair_ws_bytes(int32_t nq, int32_t B, int32_t n, int32_t C);
+int gcl_region_eval_pair(int32_t nq, const float* delta0, int64_t ldd0, int64_t bsd0, const float* win0, int64_t ldw0,
+                         int64_t bsw0, float* new_win0, float* out0, int64_t ldo0, int64_t bso0, const float* delta1,
+                         int64_t ldd1, int64_t bsd1, const float* win1, int64_t ldw1, int64_t bsw1, float* new_win1,
+                         float* out1, int64_t ldo1, int64_t bso1, const float* y_step, int64_t ldy, int64_t bsy,
+                         const int32_t* chan_kind, int32_t residual, const int32_t* rows, int32_t n, double weight,
+                         double* acc, int32_t B, int32_t G, int32_t obs, int32_t C, void* ws, size_t ws_bytes,
+                         gcl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
