@@ -6,6 +6,7 @@
 // Operand maps of v_mfma_f32_32x32x16_bf16 (cdna_hip_programming.md §3), lane l: r = l & 31, h = l >> 5:
 //   A: A[row r][k = 8h + j], j = 0..7      B: B[k = 8h + j][col r]      D: reg q -> D[(q&3) + 8(q>>2) + 4h][col r]
 // so both fragments are 16 contiguous bytes of a [row | col][k] bf16 image: one ds_read_b128 each.
+#include "ln_row.h"
 #include "mfma_io.h"
 #include "x3.h"
 
@@ -16,6 +17,10 @@ typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 #ifndef GCL_X3_ST_AUX
 #define GCL_X3_ST_AUX 2  // cache-policy bits of the streamed-out stores: 2 = non-temporal (measured +1.1 % end to end: the outputs are
                          // consumed by a LATER kernel, keeping them out of the producer XCD's L2 leaves it to the inputs); 0 = default
+#endif
+#ifndef GCL_X3_LN_ST_AUX
+#define GCL_X3_LN_ST_AUX 0  // the LayerNorm output of the chained MLP forward keeps the plain stores ln_fwd_kernel gives it: its
+                           // reader is the NEXT kernel (the gather into the encoder's input, 19.3 -> 17.6 us a launch against 2)
 #endif
 // rows that this kernel reads exactly once: non-temporal loads (measured +0.7 % end to end; -DGCL_X3_LD_PLAIN: plain)
 __device__ __forceinline__ float4 ld_stream(const float4* p) {
@@ -52,6 +57,226 @@ __device__ unsigned long long x3_stamps[8 * 4096];  // diagnostic builds only (m
 #endif
 
 // ---------------------------------------------------------------------------------------------
+// The tile body of the forward as functions: ONE text for linear_x3_fwd_kernel and for the chained kernel of a whole
+// MLP (mlp_x3_chain_kernel), so a layer computes the same bits in either.
+// ---------------------------------------------------------------------------------------------
+struct X3Stamp {  // diagnostic builds only (X3_STAMP): unused, and so removed, in the product
+  unsigned long long acc[8], last;
+};
+
+// what a lane knows about its place: its wave's LDS region, its fragment offset, its place in the staging map
+// (16 lanes x float4 = one 64-float row, 4 rows per wave-instruction, 8 instructions per tile)
+struct X3Lane {
+  int tid, lane, wave, fo, rsub, csub;
+  unsigned char* Aw;
+};
+__device__ __forceinline__ X3Lane x3_lane(unsigned char* smem8) {
+  X3Lane l;
+  l.tid = threadIdx.x;
+  l.lane = l.tid & 63;
+  l.wave = __builtin_amdgcn_readfirstlane(l.tid >> 6);
+  l.Aw = smem8 + l.wave * kTileB;
+  l.fo = (l.lane & 31) * kRowB + (l.lane >> 5) * 16;  // this lane's fragment inside a row-block, k-step 0
+  l.rsub = l.lane >> 4;
+  l.csub = l.lane & 15;
+  return l;
+}
+
+// weight fragments: the block splits W once into piece images laid over the (still unused) tile regions, every wave
+// then lifts its NS * NKS * 3 fragments into registers.  Two block barriers; the regions are free again afterwards.
+template <int NS, int NKS>
+__device__ __forceinline__ void x3_fwd_weights(unsigned char* smem8, const X3Lane& l, const float* __restrict__ W, int K,
+                                               int N, bf16x8 (&wf)[NS][NKS][3]) {
+  constexpr int kWimgB = NS * 32 * kRowB;  // one piece of the whole panel
+  const int tid = l.tid;
+  float2 wv[NS * 4];
+#pragma unroll
+  for (int i = 0; i < NS * 4; ++i) {  // NS*32 rows x 32 k-pairs over 256 threads, all loads in flight at once
+    const int idx = i * 256 + tid;
+    const int j = idx >> 5, k = (idx & 31) * 2;
+    const bool okj = j < N;
+    wv[i].x = (okj && k < K) ? W[(int64_t)j * K + k] : 0.f;
+    wv[i].y = (okj && k + 1 < K) ? W[(int64_t)j * K + k + 1] : 0.f;
+  }
+#pragma unroll
+  for (int i = 0; i < NS * 4; ++i) {
+    const int idx = i * 256 + tid;
+    const int j = idx >> 5, k = (idx & 31) * 2;
+    const Pk3 p = split2(wv[i].x, wv[i].y);
+    unsigned char* d = smem8 + j * kRowB + k * 2;
+    *reinterpret_cast<unsigned*>(d) = p.h;
+    *reinterpret_cast<unsigned*>(d + kWimgB) = p.m;
+    *reinterpret_cast<unsigned*>(d + 2 * kWimgB) = p.l;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int t = 0; t < NS; ++t)
+#pragma unroll
+    for (int s = 0; s < NKS; ++s)
+#pragma unroll
+      for (int p = 0; p < 3; ++p)
+        wf[t][s][p] = *reinterpret_cast<const bf16x8*>(smem8 + p * kWimgB + t * 32 * kRowB + l.fo + s * 32);
+  __syncthreads();  // the last block barrier of a layer's set-up: afterwards every wave only touches its own region
+}
+
+// bias of the four columns this lane stores (added after the transpose: one rounding on the finished sum)
+template <int NS>
+__device__ __forceinline__ float4 x3_fwd_bias(const float* __restrict__ bias, int lane, int N) {
+  float4 bq;
+  const int oc = (lane % (NS * 8)) * 4;
+  bq.x = (bias && oc < N) ? bias[oc] : 0.f;
+  bq.y = (bias && oc + 1 < N) ? bias[oc + 1] : 0.f;
+  bq.z = (bias && oc + 2 < N) ? bias[oc + 2] : 0.f;
+  bq.w = (bias && oc + 3 < N) ? bias[oc + 3] : 0.f;
+  return bq;
+}
+
+// the loads of this wave's 32 rows of `tile`; rows past `rows_ld` and columns past K read the zero page
+__device__ __forceinline__ void x3_fwd_issue(const X3Lane& l, const float* __restrict__ X, int64_t ldx, int64_t rows_ld,
+                                             int K, int64_t tile, float4 (&pre)[8]) {
+  const bool cok = l.csub * 4 < K;
+  const int64_t r0 = tile * 128 + l.wave * 32;
+#pragma unroll
+  for (int it = 0; it < 8; ++it) {
+    const int64_t row = r0 + it * 4 + l.rsub;
+    const float4* p = (cok && row < rows_ld) ? reinterpret_cast<const float4*>(X + row * ldx + l.csub * 4) : zero4;
+    pre[it] = ld_stream(p);
+  }
+}
+
+// activation and 3-way split of the rows in `pre` into the wave's hi / mid / lo images
+template <bool SILU>
+__device__ __forceinline__ void x3_fwd_commit(const X3Lane& l, const float4 (&pre)[8], int K, float pa) {
+  // K % 4 != 0: the 16 bytes of the last loading lane end in the row's padding (columns K.. of a 16-byte row), which
+  // is not data: it is cleared before the split, whatever it holds (a NaN there would meet the zero weight and still
+  // poison the row).  Block-uniform test: nothing changes for K % 4 == 0.
+  const int kleft = K - l.csub * 4;  // data columns in this lane's float4
+#pragma unroll
+  for (int it = 0; it < 8; ++it) {
+    float4 v = pre[it];
+    if (K & 3) {
+      v.y = kleft > 1 ? v.y : 0.f; v.z = kleft > 2 ? v.z : 0.f; v.w = kleft > 3 ? v.w : 0.f;
+    }
+    if (SILU) {
+      v.x = gcl::silu_f(v.x); v.y = gcl::silu_f(v.y); v.z = gcl::silu_f(v.z); v.w = gcl::silu_f(v.w);
+    } else {  // PReLU and "none" (pa = 1) share one branch-free form
+      const float mx = v.x * pa, my = v.y * pa, mz = v.z * pa, mw = v.w * pa;
+      v.x = v.x > 0.f ? v.x : mx; v.y = v.y > 0.f ? v.y : my;
+      v.z = v.z > 0.f ? v.z : mz; v.w = v.w > 0.f ? v.w : mw;
+    }
+    const Pk3 p01 = split2(v.x, v.y), p23 = split2(v.z, v.w);
+    unsigned char* d = l.Aw + (it * 4 + l.rsub) * kRowB + l.csub * 8;
+    *reinterpret_cast<u32x2*>(d) = u32x2{p01.h, p23.h};
+    *reinterpret_cast<u32x2*>(d + kImgB) = u32x2{p01.m, p23.m};
+    *reinterpret_cast<u32x2*>(d + 2 * kImgB) = u32x2{p01.l, p23.l};
+  }
+}
+
+// the NS * NKS * 6 MFMAs of a tile, smallest piece products first.  The row fragments are re-read from LDS in every
+// pass (6 * NKS ds_read_b128 per tile) rather than held
+template <int NS, int NKS>
+__device__ __forceinline__ void x3_fwd_mfma(const X3Lane& l, const bf16x8 (&wf)[NS][NKS][3], f32x16 (&acc)[NS]) {
+  const unsigned char* Aw = l.Aw;
+  const int fo = l.fo;
+#pragma unroll
+  for (int s = 0; s < NKS; ++s) {
+    const unsigned char* ap = Aw + fo + s * 32;
+    const bf16x8 ah = *reinterpret_cast<const bf16x8*>(ap);
+    const bf16x8 am = *reinterpret_cast<const bf16x8*>(ap + kImgB);
+    const bf16x8 al = *reinterpret_cast<const bf16x8*>(ap + 2 * kImgB);
+#pragma unroll
+    for (int c = 0; c < NS; ++c) acc[c] = mfma_lo(acc[c], ah, am, al, wf[c][s][0], wf[c][s][1], wf[c][s][2]);
+  }
+#pragma unroll
+  for (int s = 0; s < NKS; ++s) {
+    const unsigned char* ap = Aw + fo + s * 32;
+    const bf16x8 ah = *reinterpret_cast<const bf16x8*>(ap);
+    const bf16x8 am = *reinterpret_cast<const bf16x8*>(ap + kImgB);
+#pragma unroll
+    for (int c = 0; c < NS; ++c) acc[c] = mfma_mid(acc[c], ah, am, wf[c][s][0], wf[c][s][1]);
+  }
+#pragma unroll
+  for (int s = 0; s < NKS; ++s) {
+    const bf16x8 ah = *reinterpret_cast<const bf16x8*>(Aw + fo + s * 32);
+#pragma unroll
+    for (int c = 0; c < NS; ++c) acc[c] = mfma_hi(acc[c], ah, wf[c][s][0]);
+  }
+}
+
+// rows a lane holds after the transpose: float4 number p is row p * RPP + lane / LPO, columns (lane % LPO) * 4 ..
+template <int NS>
+struct X3Out {
+  static constexpr int OS = NS * 32, LPO = OS / 4, RPP = 64 / LPO, NP = 32 / RPP;
+};
+
+// transpose of the accumulators through the wave's region ([32][NS*32] fp32 <= 8 KiB of its 13.5), the bias, and the
+// store of whole 16-byte row segments of this wave's rows of `tile`; `out` keeps what was stored.  For NS = 2 a lane
+// then holds row p * 4 + (lane >> 4), columns (lane & 15) * 4 ..: the element x3_fwd_commit expects in pre[p], and the
+// 16-lanes-per-row layout of ln_fwd_kernel<16>.
+template <int NS>
+__device__ __forceinline__ void x3_fwd_finish(const X3Lane& l, const f32x16 (&acc)[NS], float4 bq, float* __restrict__ Y,
+                                              int64_t ldy, int64_t rows, int N, int64_t tile, bool drop,
+                                              float4 (&out)[X3Out<NS>::NP]) {
+  const int lane = l.lane;
+  const int64_t r0 = tile * 128 + l.wave * 32;
+  const int64_t nr64 = rows - r0;
+  const int nr = nr64 < 0 ? 0 : (nr64 < 32 ? (int)nr64 : 32);
+  constexpr int OS = X3Out<NS>::OS, LPO = X3Out<NS>::LPO, RPP = X3Out<NS>::RPP;
+  float* Ot = reinterpret_cast<float*>(l.Aw);
+#pragma unroll
+  for (int s = 0; s < NS; ++s)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) Ot[d_row(r, lane) * OS + s * 32 + (lane & 31)] = acc[s][r];
+  const __amdgpu_buffer_rsrc_t ry = make_rsrc(Y + r0 * ldy, (nr > 0 && !drop) ? ((int64_t)(nr - 1) * ldy + N) * 4 : 0);
+  const int orow = lane / LPO, ocol = (lane % LPO) * 4;
+#pragma unroll
+  for (int p = 0; p < 32 / RPP; ++p) {
+    const int i = p * RPP + orow;
+    float4 v = *reinterpret_cast<const float4*>(Ot + i * OS + ocol);
+    v.x += bq.x; v.y += bq.y; v.z += bq.z; v.w += bq.w;
+    buf_st4<GCL_X3_ST_AUX>(ry, (ocol < N) ? (unsigned)((i * ldy + ocol) * 4) : kOOB, v);
+    out[p] = v;
+  }
+}
+
+// One layer on one tile: commit `in`, (NEXT: issue the loads of `next_tile` into `in`), MFMA passes, transpose, bias,
+// store; `out` = the biased rows.  abl: see linear_x3_fwd_kernel (0 in the product).
+template <int NS, bool SILU, int NKS, bool NEXT>
+__device__ __forceinline__ void x3_fwd_tile_layer(const X3Lane& l, X3Stamp& stamps, float4 (&in)[8],
+                                                  const float* __restrict__ X, int64_t ldx, int64_t rows_ld,
+                                                  int64_t next_tile, int K, float pa, const bf16x8 (&wf)[NS][NKS][3],
+                                                  float4 bq, float* __restrict__ Y, int64_t ldy, int64_t rows, int N,
+                                                  int64_t tile, int abl, float4 (&out)[X3Out<NS>::NP]) {
+#ifdef GCL_STAMPS
+  unsigned long long(&stamp_acc)[8] = stamps.acc;
+  unsigned long long& stamp_last = stamps.last;
+#endif
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // LDS operations of one wave complete in order
+  X3_STAMP(0);
+#ifdef GCL_STAMPS
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // split "waiting for the prefetched rows" from the commit work
+#endif
+  X3_STAMP(1);
+  x3_fwd_commit<SILU>(l, in, K, pa);
+  X3_STAMP(2);
+  if (NEXT) x3_fwd_issue(l, X, ldx, rows_ld, K, next_tile, in);  // rows past the end read the zero page
+  X3_STAMP(3);
+
+  f32x16 acc[NS];
+#pragma unroll
+  for (int s = 0; s < NS; ++s)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[s][r] = 0.f;
+  if (!(abl & 2)) x3_fwd_mfma<NS, NKS>(l, wf, acc);  // uniform
+#ifdef GCL_STAMPS
+  asm volatile("" ::"v"(acc[0][0]));
+#endif
+  X3_STAMP(4);
+  x3_fwd_finish<NS>(l, acc, bq, Y, ldy, rows, N, tile, (abl & 1) != 0, out);
+  X3_STAMP(5);
+}
+
+// ---------------------------------------------------------------------------------------------
 // Forward:  Y[r, j] = sum_k act(X[r, k]) W[j, k] + bias[j].   4 waves per block, each wave owns 32 rows of the
 // block's 128-row tile and ITS OWN LDS region: no block barrier after the set-up.  The weight fragments of
 // all six piece combinations live in registers for the whole launch (NS * 4 * 3 fragments).  Per tile a wave
@@ -72,178 +297,123 @@ __global__ __launch_bounds__(256, 2) void linear_x3_fwd_kernel(const float* __re
 #ifdef GCL_STAMPS
   const unsigned long long stamp_t0 = __builtin_amdgcn_s_memtime();
 #endif
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  unsigned char* Aw = smem8 + wave * kTileB;
-  const int fo = (lane & 31) * kRowB + (lane >> 5) * 16;  // this lane's fragment inside a row-block, k-step 0
-  const bool no_mfma = (abl & 2) != 0;
+  const X3Lane l = x3_lane(smem8);
   const int64_t rows_ld = (abl & 4) ? 0 : rows;
-
-  // ---- weight fragments: the block splits W once into piece images laid over the (still unused) tile
-  // regions, every wave then lifts its NS * NKS * 3 fragments into registers ----
   bf16x8 wf[NS][NKS][3];
-  {
-    constexpr int kWimgB = NS * 32 * kRowB;  // one piece of the whole panel
-    float2 wv[NS * 4];
-#pragma unroll
-    for (int i = 0; i < NS * 4; ++i) {  // NS*32 rows x 32 k-pairs over 256 threads, all loads in flight at once
-      const int idx = i * 256 + tid;
-      const int j = idx >> 5, k = (idx & 31) * 2;
-      const bool okj = j < N;
-      wv[i].x = (okj && k < K) ? W[(int64_t)j * K + k] : 0.f;
-      wv[i].y = (okj && k + 1 < K) ? W[(int64_t)j * K + k + 1] : 0.f;
-    }
-#pragma unroll
-    for (int i = 0; i < NS * 4; ++i) {
-      const int idx = i * 256 + tid;
-      const int j = idx >> 5, k = (idx & 31) * 2;
-      const Pk3 p = split2(wv[i].x, wv[i].y);
-      unsigned char* d = smem8 + j * kRowB + k * 2;
-      *reinterpret_cast<unsigned*>(d) = p.h;
-      *reinterpret_cast<unsigned*>(d + kWimgB) = p.m;
-      *reinterpret_cast<unsigned*>(d + 2 * kWimgB) = p.l;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int t = 0; t < NS; ++t)
-#pragma unroll
-      for (int s = 0; s < NKS; ++s)
-#pragma unroll
-        for (int p = 0; p < 3; ++p)
-          wf[t][s][p] = *reinterpret_cast<const bf16x8*>(smem8 + p * kWimgB + t * 32 * kRowB + fo + s * 32);
-    __syncthreads();  // the last block barrier: from here on every wave only touches its own region
-  }
-
+  x3_fwd_weights<NS, NKS>(smem8, l, W, K, N, wf);
   const float pa = (akind == gcl::kActPrelu) ? *slope_p : 1.f;  // x > 0 ? x : x * pa ("none": pa = 1, exact)
-  // bias of the four columns this lane stores (added after the transpose: one rounding on the finished sum)
-  float4 bq;
-  {
-    const int oc = (lane % (NS * 8)) * 4;
-    bq.x = (bias && oc < N) ? bias[oc] : 0.f;
-    bq.y = (bias && oc + 1 < N) ? bias[oc + 1] : 0.f;
-    bq.z = (bias && oc + 2 < N) ? bias[oc + 2] : 0.f;
-    bq.w = (bias && oc + 3 < N) ? bias[oc + 3] : 0.f;
-  }
-
-  // staging map: 16 lanes x float4 = one 64-float row, 4 rows per wave-instruction, 8 instructions per tile
-  const int rsub = lane >> 4, csub = lane & 15;
-  const bool cok = csub * 4 < K;
-  // K % 4 != 0: the 16 bytes of the last loading lane end in the row's padding (columns K.. of a 16-byte row), which
-  // is not data: it is cleared before the split, whatever it holds (a NaN there would meet the zero weight and still
-  // poison the row).  Block-uniform test: nothing changes for K % 4 == 0.
-  const int kleft = K - csub * 4;  // data columns in this lane's float4
-  float4 pre[8];
-  auto issue = [&](int64_t tile) {
-    const int64_t r0 = tile * 128 + wave * 32;
-#pragma unroll
-    for (int it = 0; it < 8; ++it) {
-      const int64_t row = r0 + it * 4 + rsub;
-      const float4* p = (cok && row < rows_ld) ? reinterpret_cast<const float4*>(X + row * ldx + csub * 4) : zero4;
-      pre[it] = ld_stream(p);
-    }
-  };
-  auto commit = [&]() {
-#pragma unroll
-    for (int it = 0; it < 8; ++it) {
-      float4 v = pre[it];
-      if (K & 3) {
-        v.y = kleft > 1 ? v.y : 0.f; v.z = kleft > 2 ? v.z : 0.f; v.w = kleft > 3 ? v.w : 0.f;
-      }
-      if (SILU) {
-        v.x = gcl::silu_f(v.x); v.y = gcl::silu_f(v.y); v.z = gcl::silu_f(v.z); v.w = gcl::silu_f(v.w);
-      } else {  // PReLU and "none" (pa = 1) share one branch-free form
-        const float mx = v.x * pa, my = v.y * pa, mz = v.z * pa, mw = v.w * pa;
-        v.x = v.x > 0.f ? v.x : mx; v.y = v.y > 0.f ? v.y : my;
-        v.z = v.z > 0.f ? v.z : mz; v.w = v.w > 0.f ? v.w : mw;
-      }
-      const Pk3 p01 = split2(v.x, v.y), p23 = split2(v.z, v.w);
-      unsigned char* d = Aw + (it * 4 + rsub) * kRowB + csub * 8;
-      *reinterpret_cast<u32x2*>(d) = u32x2{p01.h, p23.h};
-      *reinterpret_cast<u32x2*>(d + kImgB) = u32x2{p01.m, p23.m};
-      *reinterpret_cast<u32x2*>(d + 2 * kImgB) = u32x2{p01.l, p23.l};
-    }
-  };
+  const float4 bq = x3_fwd_bias<NS>(bias, l.lane, N);
 
   const int64_t ntiles = (rows + 127) / 128;
-  issue(blockIdx.x);
+  float4 pre[8];
+  x3_fwd_issue(l, X, ldx, rows_ld, K, blockIdx.x, pre);
+  X3Stamp stamps;
 #ifdef GCL_STAMPS
-  unsigned long long stamp_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, stamp_last = __builtin_amdgcn_s_memtime();
+  unsigned long long(&stamp_acc)[8] = stamps.acc;
+  unsigned long long& stamp_last = stamps.last;
+  for (int i = 0; i < 8; ++i) stamp_acc[i] = 0;
+  stamp_last = __builtin_amdgcn_s_memtime();
   stamp_acc[6] = stamp_last - stamp_t0;  // set-up (weight fragments)
   stamp_acc[7] = stamp_t0;               // absolute start: are all blocks resident at once?
 #endif
   for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // LDS operations of one wave complete in order
-    X3_STAMP(0);
-#ifdef GCL_STAMPS
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // split "waiting for the prefetched rows" from the commit work
-#endif
-    X3_STAMP(1);
-    commit();
-    X3_STAMP(2);
-    issue(t + gridDim.x);  // rows past the end read the zero page
-    X3_STAMP(3);
-
-    f32x16 acc[NS];
-#pragma unroll
-    for (int s = 0; s < NS; ++s)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[s][r] = 0.f;
-    // fragments are re-read from LDS in every pass (6 * NKS ds_read_b128 per tile) rather than held: registers
-    // are what limits this kernel to two waves per SIMD
-    if (!no_mfma) {  // uniform
-#pragma unroll
-      for (int s = 0; s < NKS; ++s) {
-        const unsigned char* ap = Aw + fo + s * 32;
-        const bf16x8 ah = *reinterpret_cast<const bf16x8*>(ap);
-        const bf16x8 am = *reinterpret_cast<const bf16x8*>(ap + kImgB);
-        const bf16x8 al = *reinterpret_cast<const bf16x8*>(ap + 2 * kImgB);
-#pragma unroll
-        for (int c = 0; c < NS; ++c) acc[c] = mfma_lo(acc[c], ah, am, al, wf[c][s][0], wf[c][s][1], wf[c][s][2]);
-      }
-#pragma unroll
-      for (int s = 0; s < NKS; ++s) {
-        const unsigned char* ap = Aw + fo + s * 32;
-        const bf16x8 ah = *reinterpret_cast<const bf16x8*>(ap);
-        const bf16x8 am = *reinterpret_cast<const bf16x8*>(ap + kImgB);
-#pragma unroll
-        for (int c = 0; c < NS; ++c) acc[c] = mfma_mid(acc[c], ah, am, wf[c][s][0], wf[c][s][1]);
-      }
-#pragma unroll
-      for (int s = 0; s < NKS; ++s) {
-        const bf16x8 ah = *reinterpret_cast<const bf16x8*>(Aw + fo + s * 32);
-#pragma unroll
-        for (int c = 0; c < NS; ++c) acc[c] = mfma_hi(acc[c], ah, wf[c][s][0]);
-      }
-    }
-
-#ifdef GCL_STAMPS
-    asm volatile("" ::"v"(acc[0][0]));
-#endif
-    X3_STAMP(4);
-    // transpose through the wave's region ([32][NS*32] fp32 <= 8 KiB of its 13.5) and store 16-byte row segments
-    const int64_t r0 = t * 128 + wave * 32;
-    const int64_t nr64 = rows - r0;
-    const int nr = nr64 < 0 ? 0 : (nr64 < 32 ? (int)nr64 : 32);
-    constexpr int OS = NS * 32, LPO = OS / 4, RPP = 64 / LPO;
-    float* Ot = reinterpret_cast<float*>(Aw);
-#pragma unroll
-    for (int s = 0; s < NS; ++s)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) Ot[d_row(r, lane) * OS + s * 32 + (lane & 31)] = acc[s][r];
-    const __amdgpu_buffer_rsrc_t ry = make_rsrc(Y + r0 * ldy, (nr > 0 && !(abl & 1)) ? ((int64_t)(nr - 1) * ldy + N) * 4 : 0);
-    const int orow = lane / LPO, ocol = (lane % LPO) * 4;
-#pragma unroll
-    for (int p = 0; p < 32 / RPP; ++p) {
-      const int i = p * RPP + orow;
-      float4 v = *reinterpret_cast<const float4*>(Ot + i * OS + ocol);
-      v.x += bq.x; v.y += bq.y; v.z += bq.z; v.w += bq.w;
-      buf_st4<GCL_X3_ST_AUX>(ry, (ocol < N) ? (unsigned)((i * ldy + ocol) * 4) : kOOB, v);
-    }
-    X3_STAMP(5);
+    float4 out[X3Out<NS>::NP];
+    x3_fwd_tile_layer<NS, SILU, NKS, true>(l, stamps, pre, X, ldx, rows_ld, t + gridDim.x, K, pa, wf, bq, Y, ldy, rows, N,
+                                           t, abl, out);
   }
 #ifdef GCL_STAMPS
-  if (lane == 0 && blockIdx.x < 1024)
-    for (int i = 0; i < 8; ++i) x3_stamps[(blockIdx.x * 4 + wave) * 8 + i] = stamp_acc[i];
+  if (l.lane == 0 && blockIdx.x < 1024)
+    for (int i = 0; i < 8; ++i) x3_stamps[(blockIdx.x * 4 + l.wave) * 8 + i] = stamp_acc[i];
 #endif
+}
+
+// ---------------------------------------------------------------------------------------------
+// A run of L = 2 or 3 Linear layers of an MLP in one launch: y_k = act_k(y_{k-1}) W_k^T + b_k, every y_k stored for the
+// backward, each layer the text of linear_x3_fwd_kernel<2, false, 4> (all widths 33..64).  A wave keeps the biased
+// float4s of its 32 rows after a layer's store and commits them as the next layer's input: the rows never come back
+// from memory, and since a wave only touches its own LDS region there is no barrier between layers either.  Only layer 0
+// loads from global memory, one tile ahead.
+// Every layer's 24 weight fragments stay in registers (96 VGPRs a layer): one 4-wave block per CU, one wave per SIMD
+// with the whole 512-register file.  (Two waves per SIMD would have to keep the layers' piece images in LDS and re-read
+// the fragments per tile: 27 KiB a layer next to 8 x 13.5 KiB of tile regions is more than the 160 KiB of a CU for two
+// layers already.)
+// LN: the run ends at the MLP's last Linear and a node LayerNorm follows: the 16 lanes that hold a row apply the row
+// arithmetic of ln_fwd_kernel<16, true> (ln_row.h) to it and store y and (mean, rstd) besides the pre-norm row.
+// ---------------------------------------------------------------------------------------------
+struct X3Chain {
+  const float* W[3];
+  const float* bias[3];
+  const float* slope[3];  // PReLU slope in front of layer k, or null: no activation
+  float* Z[3];            // pre-activation output of layer k [rows, N[k]], row stride ldz[k]
+  int64_t ldz[3];
+  int32_t K[3], N[3];
+  const float* gamma;  // LN only
+  const float* beta;
+  float* Y;  // [rows, N[L-1]], row stride ldy
+  int64_t ldy;
+  float* stats;  // [rows][2]
+  float eps;
+};
+
+template <int L, bool LN>
+__global__ __launch_bounds__(256, 1) void mlp_x3_chain_kernel(const float* __restrict__ X, int64_t ldx, int64_t rows,
+                                                             const X3Chain a) {
+  extern __shared__ __align__(16) unsigned char smem8[];
+  const X3Lane l = x3_lane(smem8);
+  bf16x8 wf[L][2][4][3];
+  float pa[L];
+  float4 bq[L];
+#pragma unroll
+  for (int k = 0; k < L; ++k) {
+    x3_fwd_weights<2, 4>(smem8, l, a.W[k], a.K[k], a.N[k], wf[k]);
+    pa[k] = a.slope[k] ? *a.slope[k] : 1.f;
+    bq[k] = x3_fwd_bias<2>(a.bias[k], l.lane, a.N[k]);
+  }
+  // LayerNorm: this lane's four columns of gamma and beta (F % 4 == 0)
+  const int c0 = l.csub * 4, F = a.N[L - 1];
+  const bool cin = c0 < F;
+  float g0 = 0, g1 = 0, g2 = 0, g3 = 0, b0 = 0, b1 = 0, b2 = 0, b3 = 0;
+  if (LN && cin) {
+    g0 = a.gamma[c0]; g1 = a.gamma[c0 + 1]; g2 = a.gamma[c0 + 2]; g3 = a.gamma[c0 + 3];
+    b0 = a.beta[c0]; b1 = a.beta[c0 + 1]; b2 = a.beta[c0 + 2]; b3 = a.beta[c0 + 3];
+  }
+  const float invF = 1.f / (float)F;
+  const int64_t ntiles = (rows + 127) / 128;
+  float4 pre[8];
+  x3_fwd_issue(l, X, ldx, rows, a.K[0], blockIdx.x, pre);
+  X3Stamp stamps;
+  for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    float4 cur[8];
+    x3_fwd_tile_layer<2, false, 4, true>(l, stamps, pre, X, ldx, rows, t + gridDim.x, a.K[0], pa[0], wf[0], bq[0], a.Z[0],
+                                         a.ldz[0], rows, a.N[0], t, 0, cur);
+#pragma unroll
+    for (int k = 1; k < L; ++k) {
+      // the columns K.. of a row are zeros where the layer loads them (zero page): the same here, whatever the
+      // accumulators of the unused columns hold (NaN x 0 for a row with a NaN in it)
+      const bool cok = l.csub * 4 < a.K[k];
+#pragma unroll
+      for (int p = 0; p < 8; ++p) cur[p] = cok ? cur[p] : make_float4(0.f, 0.f, 0.f, 0.f);
+      x3_fwd_tile_layer<2, false, 4, false>(l, stamps, cur, nullptr, 0, 0, 0, a.K[k], pa[k], wf[k], bq[k], a.Z[k],
+                                            a.ldz[k], rows, a.N[k], t, 0, cur);
+    }
+    if (LN) {
+      const int64_t r0 = t * 128 + l.wave * 32;
+      const int64_t nr64 = rows - r0;
+      const int nr = nr64 < 0 ? 0 : (nr64 < 32 ? (int)nr64 : 32);
+      const __amdgpu_buffer_rsrc_t ry = make_rsrc(a.Y + r0 * a.ldy, nr > 0 ? ((int64_t)(nr - 1) * a.ldy + F) * 4 : 0);
+      const __amdgpu_buffer_rsrc_t rs = make_rsrc(a.stats + r0 * 2, (int64_t)nr * 8);
+#pragma unroll
+      for (int p = 0; p < 8; ++p) {
+        const int i = p * 4 + l.rsub;
+        float mean, rstd;
+        float4 y;  // the columns past F are zeros where ln_fwd_kernel does not load them
+        gcl::ln::fwd_row<16>(cin ? cur[p].x : 0.f, cin ? cur[p].y : 0.f, cin ? cur[p].z : 0.f, cin ? cur[p].w : 0.f, c0, F,
+                             invF, a.eps, g0, g1, g2, g3, b0, b1, b2, b3, mean, rstd, y.x, y.y, y.z, y.w);
+        buf_st4<GCL_X3_LN_ST_AUX>(ry, cin ? (unsigned)((i * a.ldy + c0) * 4) : kOOB, y);
+        buf_st2<0>(rs, l.csub == 0 ? (unsigned)(i * 8) : kOOB, make_float2(mean, rstd));
+      }
+    }
+  }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -611,6 +781,61 @@ int x3_linear_fwd(const float* x, int64_t ldx, int akind, const float* slope, co
   return GCL_OK;
 }
 
+// ---- the chained forward of an MLP (mlp_x3_chain_kernel) ----
+struct X3ChainCall {  // the arguments of gcl_mlp_fwd_chain(_ok) per layer
+  const float* x;
+  int64_t ldx, rows;
+  int K, act0, L;
+  const float* z[3];
+  int64_t ldz[3];
+  int N[3];
+  const float *gamma, *y, *stats;  // the LayerNorm epilogue (gamma null: none)
+  int64_t ldy;
+};
+
+static bool x3_chain_ok(const X3ChainCall& c) {
+  if (!env_int("GCL_MLP_CHAIN", 1)) return false;  // read per call: the tests compare the chain with the per-layer launches
+  static const bool valu = env_is("GCL_LINEAR_IMPL", "valu");  // (gcl_dense_fwd then takes no matrix-pipe kernel)
+  if (valu || c.L < 2 || c.L > 3 || c.rows < 0 || !c.x) return false;
+  if (c.act0 != kActNone && c.act0 != kActPrelu) return false;
+  const float* in = c.x;
+  int64_t ldin = c.ldx;
+  int K = c.K;
+  for (int k = 0; k < c.L; ++k) {
+    // the layer as gcl_dense_fwd would launch it, and on linear_x3_fwd_kernel<2, false, 4>
+    if (!c.z[k] || !x3_linear_fwd_applicable(in, ldin, c.z[k], c.ldz[k], K, c.N[k], k ? kActPrelu : c.act0)) return false;
+    if (K < 33 || c.N[k] < 33 || ldin < K || c.ldz[k] < c.N[k]) return false;
+    if (k + 1 < c.L && c.ldz[k] != c.N[k]) return false;  // handed over: contiguous
+    in = c.z[k];
+    ldin = c.ldz[k];
+    K = c.N[k];
+  }
+  if (c.gamma) {  // the epilogue: two-layer runs (with three the kernel would not fit the register file), 16-byte rows
+    if (c.L != 2 || !c.y || !c.stats || (c.ldy & 3) || c.ldy < K || !aligned16(c.y) || ((uintptr_t)c.stats & 7)) return false;
+    if (c.ldy * 4 * 35 >= ((int64_t)1 << 31)) return false;  // 32-bit offsets inside a tile
+  }
+  return true;
+}
+
+static int x3_chain_launch(const float* x, int64_t ldx, int64_t rows, int L, bool ln, const X3Chain& a, hipStream_t st) {
+  if (rows == 0) return GCL_OK;
+  const int64_t ntiles = cdiv(rows, 128);
+  const int grid = (int)(ntiles < kNumCU ? ntiles : kNumCU);  // one block a CU: the register file holds one wave a SIMD
+  const size_t lds = 4 * (size_t)kTileB;
+#define GCL_X3C(L_, LN_)                                                       \
+  do {                                                                         \
+    auto kern = mlp_x3_chain_kernel<L_, LN_>;                                  \
+    GCL_ENSURE_DYN_LDS(kern, lds);                                             \
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, x, ldx, rows, a); \
+  } while (0)
+  if (L == 2 && ln) GCL_X3C(2, true);
+  else if (L == 2) GCL_X3C(2, false);
+  else GCL_X3C(3, false);
+#undef GCL_X3C
+  GCL_CHECK_LAUNCH();
+  return GCL_OK;
+}
+
 bool x3_linear_bwd_applicable(const float* dy, int64_t lddy, const float* x, int64_t ldx, const float* dx, int64_t lddx,
                               int Fin, int Fout) {
   if (!env_int("GCL_X3", 1)) return false;  // read per call: the dispatch tests compare GCL_X3=0 with the default
@@ -678,3 +903,55 @@ int x3_linear_bwd(const float* dy, int64_t lddy, const float* W, const float* x,
 }
 
 }  // namespace gcl
+
+static gcl::X3ChainCall chain_call(const float* x, int64_t ldx, int64_t rows, int32_t K, int32_t act0, int32_t nlayers,
+                                   const float* z0, int64_t ldz0, int32_t N0, const float* z1, int64_t ldz1, int32_t N1,
+                                   const float* z2, int64_t ldz2, int32_t N2, const float* gamma, const float* y,
+                                   int64_t ldy, const float* stats) {
+  gcl::X3ChainCall c;
+  c.x = x; c.ldx = ldx; c.rows = rows; c.K = K; c.act0 = act0; c.L = nlayers;
+  c.z[0] = z0; c.ldz[0] = ldz0; c.N[0] = N0;
+  c.z[1] = z1; c.ldz[1] = ldz1; c.N[1] = N1;
+  c.z[2] = z2; c.ldz[2] = ldz2; c.N[2] = N2;
+  c.gamma = gamma; c.y = y; c.ldy = ldy; c.stats = stats;
+  return c;
+}
+
+extern "C" int gcl_mlp_fwd_chain_ok(const float* x, int64_t ldx, int64_t rows, int32_t K, int32_t act0, int32_t nlayers,
+                                    const float* z0, int64_t ldz0, int32_t N0, const float* z1, int64_t ldz1, int32_t N1,
+                                    const float* z2, int64_t ldz2, int32_t N2, const float* gamma, const float* y,
+                                    int64_t ldy, const float* stats) {
+  return gcl::x3_chain_ok(chain_call(x, ldx, rows, K, act0, nlayers, z0, ldz0, N0, z1, ldz1, N1, z2, ldz2, N2, gamma, y, ldy,
+                                     stats))
+             ? 1
+             : 0;
+}
+
+extern "C" int gcl_mlp_fwd_chain(const float* x, int64_t ldx, int64_t rows, int32_t K, int32_t act0, const float* slope0,
+                                 int32_t nlayers, const float* W0, const float* b0, float* z0, int64_t ldz0, int32_t N0,
+                                 const float* W1, const float* b1, const float* slope1, float* z1, int64_t ldz1, int32_t N1,
+                                 const float* W2, const float* b2, const float* slope2, float* z2, int64_t ldz2, int32_t N2,
+                                 const float* gamma, const float* beta, float eps, float* y, int64_t ldy, float* stats,
+                                 gcl_stream_t stream) {
+  GCL_CHECK_ARG(x && W0 && z0 && W1 && z1 && (nlayers == 2 || (W2 && z2)), "mlp_fwd_chain: null argument");
+  GCL_CHECK_ARG(!gamma || (beta && y && stats), "mlp_fwd_chain: the LayerNorm needs beta, y and stats");
+  GCL_CHECK_ARG(act0 != GCL_ACT_PRELU || slope0, "mlp_fwd_chain: GCL_ACT_PRELU needs the slope pointer");
+  GCL_CHECK_ARG(gcl::x3_chain_ok(chain_call(x, ldx, rows, K, act0, nlayers, z0, ldz0, N0, z1, ldz1, N1, z2, ldz2, N2, gamma, y,
+                                            ldy, stats)),
+                "mlp_fwd_chain: not a run this kernel takes (gcl_mlp_fwd_chain_ok): launch it per layer");
+  X3Chain a = {};
+  const float* Ws[3] = {W0, W1, W2};
+  const float* bs[3] = {b0, b1, b2};
+  const float* sl[3] = {act0 == GCL_ACT_PRELU ? slope0 : nullptr, slope1, slope2};
+  float* zs[3] = {z0, z1, z2};
+  const int64_t ldz[3] = {ldz0, ldz1, ldz2};
+  const int32_t Ns[3] = {N0, N1, N2};
+  int32_t Kk = K;
+  for (int k = 0; k < nlayers; ++k) {
+    a.W[k] = Ws[k]; a.bias[k] = bs[k]; a.slope[k] = sl[k]; a.Z[k] = zs[k]; a.ldz[k] = ldz[k];
+    a.K[k] = Kk; a.N[k] = Ns[k];
+    Kk = Ns[k];
+  }
+  a.gamma = gamma; a.beta = beta; a.Y = y; a.ldy = ldy; a.stats = stats; a.eps = eps;
+  return gcl::x3_chain_launch(x, ldx, rows, nlayers, gamma != nullptr, a, (hipStream_t)stream);
+}

@@ -42,6 +42,12 @@ __device__ __forceinline__ void buf_st1(__amdgpu_buffer_rsrc_t r, unsigned off, 
   __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, off, 0, AUX);
 }
 template <int AUX>
+__device__ __forceinline__ void buf_st2(__amdgpu_buffer_rsrc_t r, unsigned off, float2 v) {
+  typedef unsigned int u32x2_t __attribute__((ext_vector_type(2)));
+  const u32x2_t u = {__builtin_bit_cast(unsigned, v.x), __builtin_bit_cast(unsigned, v.y)};
+  __builtin_amdgcn_raw_buffer_store_b64(u, r, off, 0, AUX);
+}
+template <int AUX>
 __device__ __forceinline__ void buf_st4(__amdgpu_buffer_rsrc_t r, unsigned off, float4 v) {
   u32x4 u = {__builtin_bit_cast(unsigned, v.x), __builtin_bit_cast(unsigned, v.y), __builtin_bit_cast(unsigned, v.z),
              __builtin_bit_cast(unsigned, v.w)};

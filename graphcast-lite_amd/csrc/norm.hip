@@ -3,15 +3,11 @@
 // SURVEY.md Appendix A.4.  Row-wise kernels use the same row->lane-group mapping as the
 // aggregation kernel (LPR lanes x 4 channels, 16-B accesses, shuffle reductions inside the group).
 #include "common.h"
+#include "ln_row.h"
 
 namespace {
 
-template <int LPR>
-__device__ __forceinline__ float group_sum(float v) {
-#pragma unroll
-  for (int off = LPR / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
+using gcl::ln::group_sum;  // (ln_row.h)
 
 __device__ __forceinline__ void load4(const float* p, int c0, int F, bool vec, float& a, float& b, float& c, float& d) {
   if (vec) {
@@ -108,6 +104,18 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ X
     }
     float x0 = 0, x1 = 0, x2 = 0, x3 = 0;
     if (c0 < F) load4_row<V>(X + row * ldx + c0, c0, F, vx, x0, x1, x2, x3);
+    if (V && !MAP) {
+      // the plain 16-byte-row kernel: the row arithmetic it shares with the chained MLP forward (ln_row.h), which spells
+      // out the operations this instantiation has always been compiled to
+      float mean, rstd, y0, y1, y2, y3;
+      gcl::ln::fwd_row<LPR>(x0, x1, x2, x3, c0, F, invF, eps, g0, g1, g2, g3, b0, b1, b2, b3, mean, rstd, y0, y1, y2, y3);
+      if (c0 < F) store4(Y + row * ldy + c0, c0, F, vy, y0, y1, y2, y3);
+      if (l == 0 && stats) {
+        stats[2 * row] = mean;
+        stats[2 * row + 1] = rstd;
+      }
+      continue;
+    }
     const float mean = group_sum<LPR>(x0 + x1 + x2 + x3) * invF;
     const float d0 = (c0 < F) ? x0 - mean : 0.f, d1 = (c0 + 1 < F) ? x1 - mean : 0.f;
     const float d2 = (c0 + 2 < F) ? x2 - mean : 0.f, d3 = (c0 + 3 < F) ? x3 - mean : 0.f;

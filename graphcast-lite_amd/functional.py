@@ -118,16 +118,29 @@ class MLPFn(torch.autograd.Function):
         x2 = hip.rows2d(x.detach())
         zs = []
         cur, slope = x2, None
+        out = stats = None
         for k in range(L):
+            # the last two or three Linear layers, and the LayerNorm where it fits, in one launch when the chained kernel
+            # takes them (hip.mlp_fwd_chain: the same z_k, output and statistics, bit for bit); the layers in front of
+            # such a run, and every other MLP, layer by layer
+            if 2 <= L - k <= 3:
+                tail = hip.mlp_fwd_chain(cur, [params[3 * j].detach() for j in range(k, L)],
+                                         [params[3 * j + 1].detach() for j in range(k, L)],
+                                         [params[3 * j + 2].detach() for j in range(k, L - 1)], slope,
+                                         ln=(params[-2].detach(), params[-1].detach(), eps) if has_ln else None)
+                if tail is not None:
+                    zs.extend(tail[0])
+                    cur, out, stats = tail[0][-1], tail[1], tail[2]
+                    break
             W, b = params[3 * k], params[3 * k + 1]
             z = hip.linear_fwd(cur, W.detach(), b.detach(), slope)
             zs.append(z)
             cur = z
             slope = params[3 * k + 2].detach() if k < L - 1 else None
-        stats = None
-        out = cur
-        if has_ln:
-            out, stats = hip.layernorm_fwd(cur, params[-2].detach(), params[-1].detach(), eps)
+        if out is None:
+            out = cur
+            if has_ln:
+                out, stats = hip.layernorm_fwd(cur, params[-2].detach(), params[-1].detach(), eps)
         ctx.owner, ctx.has_ln, ctx.L = owner, has_ln, L
         ctx.x2, ctx.zs, ctx.stats = x2, zs, stats
         ctx.params = params

@@ -106,6 +106,9 @@ _SIGNATURES = {
                                        _f32, _vp]),
     "gcl_copy_rows": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _vp]),
     "gcl_dense_fwd": (C.c_int, [_vp, _i64, _i32, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _vp]),
+    "gcl_mlp_fwd_chain_ok": (C.c_int, [_vp, _i64, _i64, _i32, _i32, _i32] + [_vp, _i64, _i32] * 3 + [_vp, _vp, _i64, _vp]),
+    "gcl_mlp_fwd_chain": (C.c_int, [_vp, _i64, _i64, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _i64, _i32]
+                          + [_vp, _vp, _vp, _vp, _i64, _i32] * 2 + [_vp, _vp, _f32, _vp, _i64, _vp, _vp]),
     "gcl_dense_bwd_dx": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i32, _i32,
                                    _vp, C.c_size_t, _vp]),
     "gcl_dense_bwd_dw": (C.c_int, [_vp, _i64, _vp, _i64, _i32, _vp, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _vp,
@@ -408,6 +411,46 @@ def linear_fwd(x, W, bias, in_slope, out=None, ld_out=None, act=None):
     _check(lib().gcl_dense_fwd(_p(x), _ld(x), _act_of(act, in_slope), _p(in_slope), _p(W), W.stride(0), _p(bias), None, 0,
                                _p(out), _ld(out), rows, Fin, Fout, _stream()))
     return out
+
+
+def mlp_fwd_chain(x, Ws, bs, slopes, in_slope=None, ln=None):
+    """2 or 3 consecutive Linear layers in one launch: z_0 = act(x) W_0^T + b_0 (PReLU when in_slope is given, else
+    identity), z_k = prelu(z_{k-1}; slopes[k-1]) W_k^T + b_k.  ln = (gamma, beta, eps): the node LayerNorm behind the last
+    layer.  Returns ([z_0, ..], y, stats) - the tensors, bit for bit, that linear_fwd gives layer by layer and
+    layernorm_fwd gives for the last of them; y and stats are None when no LayerNorm was asked for or the kernel does
+    not take it with this run (the caller then launches it) - or None when the run is not one the chained kernel takes
+    (gcl_mlp_fwd_chain_ok; GCL_MLP_CHAIN=0 turns it off): the caller then launches the layers one by one."""
+    n = len(Ws)
+    rows, Fin = x.shape
+    if n < 2 or n > 3 or rows == 0 or len(slopes) != n - 1 or any(W.stride(0) != W.shape[1] or W.stride(1) != 1 for W in Ws):
+        return None
+    if Fin > 64 or any(W.shape[0] > 64 for W in Ws):  # no output tensors for a wide MLP, which the kernel never takes
+        return None
+    zs = [torch.empty(rows, W.shape[0], dtype=torch.float32, device=x.device) for W in Ws]
+    act0 = ACT_PRELU if in_slope is not None else ACT_NONE
+    zargs = []
+    for z in zs + [None] * (3 - n):
+        zargs += [_p(z), z.shape[1] if z is not None else 0, z.shape[1] if z is not None else 0]
+    y = stats = None
+    if ln is not None:
+        y = torch.empty(rows, Ws[-1].shape[0], dtype=torch.float32, device=x.device)
+        stats = torch.empty(rows, 2, dtype=torch.float32, device=x.device)
+        if not lib().gcl_mlp_fwd_chain_ok(_p(x), _ld(x), rows, Fin, act0, n, *zargs, _p(ln[0]), _p(y), y.shape[1], _p(stats)):
+            ln = y = stats = None
+    if ln is None and not lib().gcl_mlp_fwd_chain_ok(_p(x), _ld(x), rows, Fin, act0, n, *zargs, None, None, 0, None):
+        return None
+    largs = [_p(Ws[0]), _p(bs[0])] + zargs[0:3]
+    for k in (1, 2):
+        if k < n:
+            largs += [_p(Ws[k]), _p(bs[k]), _p(slopes[k - 1])] + zargs[3 * k: 3 * k + 3]
+        else:
+            largs += [None, None, None, None, 0, 0]
+    if ln is not None:
+        largs += [_p(ln[0]), _p(ln[1]), float(ln[2]), _p(y), y.shape[1], _p(stats)]
+    else:
+        largs += [None, None, 0.0, None, 0, None]
+    _check(lib().gcl_mlp_fwd_chain(_p(x), _ld(x), rows, Fin, act0, _p(in_slope), n, *largs, _stream()))
+    return zs, y, stats
 
 
 def linear_bwd_dx(dy, W, x, in_slope, d_in_slope, act=None):

@@ -217,6 +217,30 @@ int gcl_dense_bwd_dw(const float* dy, int64_t lddy, const float* x, int64_t ldx,
                      int32_t Fin, int32_t Fout, int32_t accumulate, void* ws, size_t ws_bytes,
                      gcl_stream_t stream);
 
+/* A run of nlayers = 2 or 3 consecutive Linear layers of an MLP in ONE launch (src/models.py:106-109):
+ *   z0 = act0(x) W0^T + b0,   z1 = prelu(z0; slope1) W1^T + b1,   z2 = prelu(z1; slope2) W2^T + b2
+ * with every z_k [rows, N_k] stored (row stride ldz_k) as the per-layer calls store it, bit for bit: a layer runs the same
+ * code as in gcl_dense_fwd, its input rows are handed over inside the kernel instead of being read back.  act0 is
+ * GCL_ACT_NONE or GCL_ACT_PRELU (slope0); a null slope1 / slope2 means no activation in front of that layer; the
+ * arguments of layer 2 are ignored when nlayers == 2.  gamma != NULL: the node LayerNorm that follows the last layer is
+ * applied in the same launch (the arithmetic of gcl_layernorm_fwd on 16-byte rows, bit for bit): y [rows, N_last] (row
+ * stride ldy) and stats [rows][2] = (mean, rstd) are stored besides the pre-norm z.
+ * gcl_mlp_fwd_chain_ok answers 1 when the run can be chained: GCL_MLP_CHAIN is not 0 (read per call), every layer is
+ * one that gcl_dense_fwd runs on the 3-way-split bf16 kernel for 33..64 wide layers (33 <= K, N_k <= 64, N_k % 4 == 0,
+ * GCL_X3 on, 16-byte rows), z_k of every layer but the last is contiguous (ldz_k == N_k) and, with gamma, nlayers == 2,
+ * y has 16-byte rows and stats is 8-byte aligned (a run refused with gamma may pass without: the LayerNorm is then a
+ * launch of its own).  gcl_mlp_fwd_chain refuses other runs with GCL_EINVAL: the caller launches them per layer. */
+int gcl_mlp_fwd_chain_ok(const float* x, int64_t ldx, int64_t rows, int32_t K, int32_t act0, int32_t nlayers,
+                         const float* z0, int64_t ldz0, int32_t N0, const float* z1, int64_t ldz1, int32_t N1,
+                         const float* z2, int64_t ldz2, int32_t N2, const float* gamma, const float* y, int64_t ldy,
+                         const float* stats);
+int gcl_mlp_fwd_chain(const float* x, int64_t ldx, int64_t rows, int32_t K, int32_t act0, const float* slope0,
+                      int32_t nlayers, const float* W0, const float* b0, float* z0, int64_t ldz0, int32_t N0,
+                      const float* W1, const float* b1, const float* slope1, float* z1, int64_t ldz1, int32_t N1,
+                      const float* W2, const float* b2, const float* slope2, float* z2, int64_t ldz2, int32_t N2,
+                      const float* gamma, const float* beta, float eps, float* y, int64_t ldy, float* stats,
+                      gcl_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Sparse aggregation over the CSR  y[b,i,:] = sum_{e in row i} w_e * h[b, col_e, :] (+ bias)
  * Replaces the index_select -> multiply -> scatter_add_ of PyG propagate for GCNConv
