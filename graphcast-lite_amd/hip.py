@@ -238,6 +238,10 @@ _SIGNATURES = {
     "gcl_region_eval_pair": (C.c_int, [_i32] + [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _i64, _i64] * 2
                              + [_vp, _i64, _i64, _vp, _i32, _vp, _i32, C.c_double, _vp, _i32, _i32, _i32, _i32, _vp, _sz,
                                 _vp]),
+    "gcl_obs_pack": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _i64, _i64, _vp]),
+    "gcl_region_interp_scores_ws_bytes": (_sz, [_i32] * 4),
+    "gcl_region_interp_scores": (C.c_int, [_vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp,
+                                           _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 
@@ -2445,3 +2449,60 @@ def region_eval_pair(preds, y_step3, chan_kind, residual: bool, rows, weight: fl
     _check(lib().gcl_region_eval_pair(nq, *args, _p(y_step3), ldy, bsy, _pi(chan_kind), 1 if residual else 0, _pi(rows), n,
                                       float(weight), _pd(acc), B, G, int(obs), Cc, ws.data_ptr(), ws.numel(), _stream()))
     return acc
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# Station observations and regional scoring of a saved forecast (csrc/predict.hip)
+# ------------------------------------------------------------------------------------------------------------------
+def _pu8(t, n: int, who: str):
+    if not (t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and t.numel() == n):
+        raise ValueError(f"{who}: expected a contiguous uint8 device tensor of {n} entries")
+    return t.data_ptr()
+
+
+def obs_pack(y3, keep_row, keep_chan, out3=None):
+    """out3[b, g, k] = y3[b, g, k] where keep_row[g] and keep_chan[k % C] (uint8 device masks [G] / [C]), NaN elsewhere;
+    one launch (see gcl_obs_pack).  y3 / out3: [B, G, K] views with unit channel stride; out3 may be y3."""
+    B, G, K = y3.shape
+    if out3 is None:
+        out3 = torch.empty(B, G, K, dtype=torch.float32, device=y3.device)
+    if tuple(out3.shape) != (B, G, K):
+        raise ValueError(f"obs_pack: out {tuple(out3.shape)} is not [{B}, {G}, {K}]")
+    Cc = keep_chan.numel()
+    if Cc == 0 or K % Cc:
+        raise ValueError(f"obs_pack: {K} columns are not whole steps of {Cc} channels")
+    ldy, bsy = _bgc(y3, "obs_pack")
+    ldo, bso = _bgc(out3, "obs_pack")
+    if B * G == 0:
+        return out3
+    _check(lib().gcl_obs_pack(_p(y3), ldy, bsy, _pu8(keep_row, G, "obs_pack"), _pu8(keep_chan, Cc, "obs_pack"), B, G, K, Cc,
+                              _p(out3), ldo, bso, _stream()))
+    return out3
+
+
+REGION_NS = 11  # per (horizon, channel): se, ae, base se, count, St, Stt, Sv, Svv, Stv, pivot t, pivot v
+
+
+def region_interp_scores(pred3, nlat: int, cell, w, series, t0, first: int, mean, std, P: int, Cc: int, sums, vout=None,
+                         tout=None):
+    """The float64 sums [P, C, REGION_NS] behind the regional scores of a saved global forecast (see
+    gcl_region_interp_scores).  pred3 [N, Gg, >= P * C] float32 with unit column stride; cell int32 [nr, 2] / w float64
+    [nr, 4]; series fp16 [n_time, nr, n_feat] contiguous; t0 int32 [N] on the device (-1: skip); first: the first sample
+    that is not skipped; mean / std float64 [C].  vout / tout: contiguous float32 [N, P, nr, C] or None."""
+    N, Gg = pred3.shape[0], pred3.shape[1]
+    nr = cell.shape[0]
+    if pred3.dim() != 3 or pred3.stride(2) != 1 or pred3.shape[2] < P * Cc:
+        raise ValueError(f"region_interp_scores: the forecast is a [N, G, >= {P * Cc}] view with unit column stride")
+    if series.dim() != 3 or series.shape[1] != nr or series.shape[2] < Cc or tuple(w.shape) != (nr, 4):
+        raise ValueError(f"region_interp_scores: series {tuple(series.shape)} / weights {tuple(w.shape)} for {nr} nodes")
+    if t0.numel() != N or mean.numel() != Cc or std.numel() != Cc or tuple(sums.shape) != (P, Cc, REGION_NS):
+        raise ValueError("region_interp_scores: t0 [N], mean / std [C] and sums [P, C, 11] expected")
+    for t in (vout, tout):
+        if t is not None and (tuple(t.shape) != (N, P, nr, Cc) or not t.is_contiguous()):
+            raise ValueError(f"region_interp_scores: a stored field is a contiguous [{N}, {P}, {nr}, {Cc}] tensor")
+    ws = workspace(int(lib().gcl_region_interp_scores_ws_bytes(N, P, nr, Cc)), pred3.device)
+    _check(lib().gcl_region_interp_scores(_p(pred3), pred3.stride(1), pred3.stride(0), Gg, int(nlat), _pi(cell), _pd(w),
+                                          _ph(series), series.shape[2], series.shape[0], _pi(t0), int(first), _pd(mean),
+                                          _pd(std), N, int(P), nr, int(Cc), _pd(sums), _p(vout), _p(tout), ws.data_ptr(),
+                                          ws.numel(), _stream()))
+    return sums

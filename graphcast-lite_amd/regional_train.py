@@ -672,16 +672,18 @@ KEY_VARS = ["t2m", "10u", "10v", "msl", "z@500", "t@850", "u@850", "v@850", "z@8
 
 
 class RegionScores:
-    """A host snapshot of one `StreamingMetrics` object: what the tables of predict_dual_mesh.py read from it."""
+    """A host snapshot of one `StreamingMetrics` object: what the tables of predict_dual_mesh.py (and, with `mse`, of
+    predict.py) read from it."""
 
-    def __init__(self, n, rmse, mae, acc, rmse_per_channel, acc_per_channel):
+    def __init__(self, n, rmse, mae, acc, rmse_per_channel, acc_per_channel, mse=None):
         self.n, self.rmse, self.mae, self.acc = int(n), float(rmse), float(mae), float(acc)
+        self.mse = float(rmse) ** 2 if mse is None else float(mse)
         self.rmse_per_channel = np.asarray(rmse_per_channel, dtype=np.float64)
         self.acc_per_channel = np.asarray(acc_per_channel, dtype=np.float64)
 
     @classmethod
     def of(cls, sm):
-        return cls(sm.n, sm.rmse, sm.mae, sm.acc, sm.rmse_per_channel, sm.acc_per_channel)
+        return cls(sm.n, sm.rmse, sm.mae, sm.acc, sm.rmse_per_channel, sm.acc_per_channel, mse=sm.mse)
 
 
 class PredictResults(dict):

@@ -903,3 +903,233 @@ def metric_maps(model, dataset, indices=None, ar_steps: int = 1, batch_size: int
             if base is not None:
                 base.update(truth, Persistence(X, C))
     return (mm, base) if persistence else mm
+
+
+# ======================================================================================================================
+# Regional scoring of a saved global forecast (scripts/interpolate_to_region.py)
+# ======================================================================================================================
+class _Moments:
+    """Count, means, centred second moments and co-moment of (t, v) over a set of values; `+` pools two sets with the
+    pairwise update of Chan et al., so that the pooled moments are centred on the pooled means (what `compute_acc` of
+    interpolate_to_region.py:76-81 does) without ever forming an uncentred sum."""
+
+    def __init__(self, n=0.0, mt=0.0, mv=0.0, m2t=0.0, m2v=0.0, ctv=0.0):
+        self.n, self.mt, self.mv, self.m2t, self.m2v, self.ctv = n, mt, mv, m2t, m2v, ctv
+
+    @classmethod
+    def of_sums(cls, s):
+        """From one (horizon, channel) row of gcl_region_interp_scores: sums of t' = t - tp and v' = v - vp."""
+        n, St, Stt, Sv, Svv, Stv, tp, vp = s[3], s[4], s[5], s[6], s[7], s[8], s[9], s[10]
+        if n == 0:
+            return cls()
+        return cls(n, tp + St / n, vp + Sv / n, max(Stt - St * (St / n), 0.0), max(Svv - Sv * (Sv / n), 0.0),
+                   Stv - St * (Sv / n))
+
+    def __add__(self, o):
+        if self.n == 0:
+            return o
+        if o.n == 0:
+            return self
+        n = self.n + o.n
+        dt, dv = o.mt - self.mt, o.mv - self.mv
+        f = self.n * o.n / n
+        return _Moments(n, self.mt + dt * (o.n / n), self.mv + dv * (o.n / n), self.m2t + o.m2t + dt * dt * f,
+                        self.m2v + o.m2v + dv * dv * f, self.ctv + o.ctv + dt * dv * f)
+
+    @property
+    def acc(self) -> float:
+        return float(self.ctv / (np.sqrt(self.m2t) * np.sqrt(self.m2v) + 1e-8))
+
+
+class RegionBundleScores:
+    """The scores of scripts/interpolate_to_region.py:204-249 from the float64 sums [P, C, 11] of
+    `gcl_region_interp_scores`: `horizon(p)`, `channel(p, c)` and `overall` return dictionaries with rmse, base (the
+    persistence RMSE), skill, acc (and mae per horizon).  `n_matched` of `n_samples` samples were inside the regional
+    series; `n_nodes` regional nodes."""
+
+    def __init__(self, sums, n_matched: int, n_samples: int, n_nodes: int):
+        self.sums = np.asarray(sums, dtype=np.float64)
+        self.P, self.C = self.sums.shape[:2]
+        self.n_matched, self.n_samples, self.n_nodes = int(n_matched), int(n_samples), int(n_nodes)
+        self.interpolated = self.truth = None  # float32 [n_matched, P, n_lon_r, n_lat_r, C] when they were kept
+
+    def _pool(self, cells):
+        s = np.stack([self.sums[p, c] for p, c in cells])
+        n = s[:, 3].sum()
+        rmse, base = float(np.sqrt(s[:, 0].sum() / n)), float(np.sqrt(s[:, 2].sum() / n))
+        mom = _Moments()
+        for row in s:
+            mom = mom + _Moments.of_sums(row)
+        return {"rmse": rmse, "base": base, "mae": float(s[:, 1].sum() / n), "skill": 1.0 - rmse / (base + 1e-12),
+                "acc": mom.acc, "n": int(n)}
+
+    def horizon(self, p: int) -> dict:
+        return self._pool([(p, c) for c in range(self.C)])
+
+    def channel(self, p: int, c: int) -> dict:
+        return self._pool([(p, c)])
+
+    @property
+    def overall(self) -> dict:
+        return self._pool([(p, c) for p in range(self.P) for c in range(self.C)])
+
+    def report(self, variables, per_channel: bool = False, say=print):
+        """The script's per-horizon lines, its `--per-channel` rows and its overall block."""
+        for p in range(self.P):
+            h = self.horizon(p)
+            say(f"\n  +{(p + 1) * 6:02d}h: RMSE={h['rmse']:.6f} | base={h['base']:.6f} | skill={h['skill'] * 100:.2f}% | "
+                f"MAE={h['mae']:.6f} | ACC={h['acc']:.4f}")
+            if per_channel:
+                for c in range(self.C):
+                    k = self.channel(p, c)
+                    say(f"    {c:2d}: {variables[c]:>8s}  RMSE={k['rmse']:.4f} base={k['base']:.4f} "
+                        f"skill={k['skill'] * 100:+.1f}% ACC={k['acc']:.4f}")
+        o = self.overall
+        say(f"\n{'=' * 70}")
+        say(f"Overall ({self.n_matched}×{self.P} horizons × {self.n_nodes} nodes × {self.C} ch):")
+        say(f"  RMSE={o['rmse']:.6f} | base={o['base']:.6f} | skill={o['skill'] * 100:.2f}% | ACC={o['acc']:.4f}")
+        say(f"{'=' * 70}")
+
+
+def match_regional_steps(sample_offsets, obs_window: int, time_offset: int, P: int, n_time: int) -> np.ndarray:
+    """int32 [N]: the regional step of horizon 0 of every sample (local_t + obs_window + time_offset), or -1 where the
+    forecast or its persistence step falls outside the regional series (interpolate_to_region.py:169-176)."""
+    t0 = np.full(len(sample_offsets), -1, dtype=np.int32)
+    for s, local_t in enumerate(sample_offsets):
+        start = int(local_t) + obs_window + time_offset
+        if start < 0 or start + P > n_time or start - 1 < 0:
+            continue
+        t0[s] = start
+    return t0
+
+
+def interpolate_to_region(predictions, global_data, region_data, per_channel: bool = False, out=None, device=None,
+                          say=print) -> RegionBundleScores:
+    """`scripts/interpolate_to_region.py`: the forecasts of a `predictions.pt` bundle (`predict.save_predictions`, or
+    the bare tensor of the legacy form) interpolated from the global grid of `global_data` onto the regional grid of
+    `region_data` and scored against the regional fp16 series, with persistence (the regional step before the
+    forecast) as the baseline.  Samples are matched to regional steps on the host; the regional series is uploaded
+    once; every matched sample, horizon, node and channel is interpolated and scored in one launch pair
+    (`gcl_region_interp_scores`), with one host read of [P, C, 11] sums.  Prints the script's lines; with `out` writes
+    its bundle (interpolated forecasts and regional truth as float32 [n, P, n_lon, n_lat, C])."""
+    import json
+    import os
+    from datetime import datetime
+
+    from .data import _upload_fp16
+    from .predict import load_predictions
+
+    if device is None:
+        if not torch.cuda.is_available():
+            raise RuntimeError("interpolate_to_region needs a GPU (the HIP path has no CPU fallback)")
+        device = "cuda:0"
+    device = torch.device(device)
+    global_dir, region_dir = str(global_data), str(region_data)
+    read_json = lambda d, f: json.load(open(os.path.join(d, f)))  # noqa: E731
+
+    def coords(d):
+        z = np.load(os.path.join(d, "coords.npz"))
+        return z["latitude"].astype(np.float64), z["longitude"].astype(np.float64)
+
+    g_lats, g_lons = coords(global_dir)
+    var_file = os.path.join(global_dir, "variables.json")
+    sav = load_predictions(predictions)
+    if isinstance(sav, dict):
+        preds = sav["predictions"]
+        C, P = int(sav["n_features"]), int(sav["ar_steps"])
+        n_lon_g, n_lat_g = int(sav["n_lon"]), int(sav["n_lat"])
+        OBS = int(sav.get("obs_window", 2))
+        offsets = list(sav.get("sample_offsets", range(len(preds))))
+    else:  # the bare tensor: the grid and the channel count come from the global data set
+        preds = sav
+        n_lon_g, n_lat_g = len(g_lons), len(g_lats)
+        if not os.path.exists(var_file):
+            raise ValueError("a bare prediction tensor needs the global data set's variables.json for its channel count")
+        C = len(read_json(global_dir, "variables.json"))
+        P, OBS, offsets = preds.shape[-1] // C, 2, list(range(len(preds)))
+    N = preds.shape[0]
+    if preds.dim() != 3 or preds.shape[1] != n_lon_g * n_lat_g or preds.shape[2] != P * C:
+        raise ValueError(f"predictions {tuple(preds.shape)} are not [N, {n_lon_g * n_lat_g}, {P * C}]")
+    say(f"Loaded {N} predictions: grid={n_lon_g}×{n_lat_g}, C={C}, P={P}")
+    g_info = read_json(global_dir, "dataset_info.json")
+    g_start = datetime.strptime(g_info["time_start"], "%Y-%m-%d")
+    say(f"Global: {g_info['time_start']}–{g_info['time_end']}  lon=[{g_lons[0]:.2f}..{g_lons[-1]:.2f}]  "
+        f"lat=[{g_lats[0]:.2f}..{g_lats[-1]:.2f}]")
+    r_lats, r_lons = coords(region_dir)
+    scl = np.load(os.path.join(region_dir, "scalers.npz"))
+    r_mean, r_std = scl["mean"].astype(np.float64), scl["std"].astype(np.float64)
+    r_info = read_json(region_dir, "dataset_info.json")
+    r_start = datetime.strptime(r_info["time_start"], "%Y-%m-%d")
+    n_lon_r, n_lat_r = int(r_info["n_lon"]), int(r_info["n_lat"])
+    n_feat_r = int(r_info.get("n_features", r_info.get("n_feat", C)))
+    n_time_r = int(r_info["n_time"])
+    G_region = n_lon_r * n_lat_r
+    say(f"Region: {r_info['time_start']}–{r_info['time_end']}  lon=[{r_lons[0]:.2f}..{r_lons[-1]:.2f}]  "
+        f"lat=[{r_lats[0]:.2f}..{r_lats[-1]:.2f}]  grid={n_lon_r}×{n_lat_r}={G_region}")
+    if (len(r_lons), len(r_lats)) != (n_lon_r, n_lat_r) or n_feat_r < C:
+        raise ValueError(f"regional data set: axes of {len(r_lons)} x {len(r_lats)} and {n_feat_r} features for a grid of "
+                         f"{n_lon_r} x {n_lat_r} and {C} channels")
+    time_offset = int((g_start - r_start).total_seconds() / (6 * 3600))
+    say(f"Temporal offset: global starts {time_offset} steps after regional")
+    raw = np.memmap(os.path.join(region_dir, "data.npy"), dtype=np.float16, mode="r")
+    series = _upload_fp16(raw.reshape(n_time_r, G_region, n_feat_r), device)
+    say(f"Regional data loaded: {(n_time_r, n_lon_r, n_lat_r, n_feat_r)}")
+    variables = read_json(global_dir, "variables.json") if os.path.exists(var_file) else [f"ch{i}" for i in range(C)]
+    say(f"\n{'=' * 70}")
+    say(f"Interpolating {N} global samples → {n_lon_r}×{n_lat_r} regional grid")
+    say(f"{'=' * 70}")
+    t0 = match_regional_steps(offsets, OBS, time_offset, P, n_time_r)
+    matched = np.nonzero(t0 >= 0)[0]
+    say(f"\nMatched samples: {len(matched)}/{N}")
+    if len(matched) == 0:
+        say("ERROR: no temporal overlap. Check dataset dates.")
+        raise SystemExit(1)
+    cell, w = _device_tables(g_lats, g_lons, r_lats, r_lons, device)
+    pred3 = hip._rows_view(preds.to(device))
+    sums = torch.empty(P, C, hip.REGION_NS, dtype=torch.float64, device=device)
+    vout = tout = None
+    if out:
+        vout = torch.empty(N, P, G_region, C, dtype=torch.float32, device=device)
+        tout = torch.empty_like(vout)
+    hip.region_interp_scores(pred3, n_lat_g, cell, w, series, torch.from_numpy(t0).to(device), int(matched[0]),
+                             torch.from_numpy(r_mean[:C].copy()).to(device), torch.from_numpy(r_std[:C].copy()).to(device),
+                             P, C, sums, vout, tout)
+    res = RegionBundleScores(sums.cpu().numpy(), len(matched), N, G_region)
+    res.report(variables, per_channel=per_channel, say=say)
+    if out:
+        keep = torch.from_numpy(matched).to(device)
+        shape = (len(matched), P, n_lon_r, n_lat_r, C)
+        res.interpolated = vout.index_select(0, keep).cpu().view(shape)
+        res.truth = tout.index_select(0, keep).cpu().view(shape)
+        torch.save({"interpolated_predictions": res.interpolated, "regional_ground_truth": res.truth,
+                    "variables": variables[:C], "region_lats": r_lats, "region_lons": r_lons, "n_matched": len(matched),
+                    "scalers_mean": r_mean[:C], "scalers_std": r_std[:C]}, str(out))
+        say(f"Saved interpolated: {out}")
+    return res
+
+
+def build_parser():
+    import argparse
+
+    ap = argparse.ArgumentParser(prog="python -m graphcast_lite_amd.verify",
+                                 description="Interpolate global predictions to regional grid")
+    ap.add_argument("--predictions", required=True, help="predictions .pt saved by graphcast_lite_amd.predict --save")
+    ap.add_argument("--global-data", required=True, help="global dataset directory")
+    ap.add_argument("--region-data", required=True, help="regional dataset directory")
+    ap.add_argument("--per-channel", action="store_true")
+    ap.add_argument("--out", default=None, help="save the interpolated predictions as .pt")
+    return ap
+
+
+def main(argv=None, device=None):
+    """`python -m graphcast_lite_amd.verify --predictions p.pt --global-data g --region-data r [--per-channel] [--out o.pt]`
+    with the options of scripts/interpolate_to_region.py."""
+    import sys
+
+    a = build_parser().parse_args(sys.argv[1:] if argv is None else argv)
+    return interpolate_to_region(a.predictions, a.global_data, a.region_data, per_channel=a.per_channel, out=a.out,
+                                 device=device)
+
+
+if __name__ == "__main__":
+    main()

@@ -1290,6 +1290,38 @@ int gcl_region_eval_pair(int32_t nq, const float* delta0, int64_t ldd0, int64_t 
                          double* acc, int32_t B, int32_t G, int32_t obs, int32_t C, void* ws, size_t ws_bytes,
                          gcl_stream_t stream);
 
+/* ---- Station observations and regional scoring of a saved forecast (csrc/predict.hip) ----
+ * No entry point allocates, synchronises or reads back; no atomics; every reduction has a fixed order, so results are
+ * bit-equal from run to run.
+ *
+ * The sparse observation tensor of scripts/create_obs.py:79-144 (and the inline draw of scripts/predict.py:394-421,
+ * :471-483) in one launch: obs[b,g,k] = keep_row[g] && keep_chan[k % C] ? y[b,g,k] : NaN for k < K, NaN the quiet NaN
+ * that float('nan') gives (bits 0x7fc00000).  y / obs [B,G,K] are addressed with (ld, bs); keep_row uint8 [G], keep_chan
+ * uint8 [C].  Rows move as 16-byte accesses when K, the strides and both bases allow it, element by element otherwise;
+ * kept values are copied bit for bit and a row that is not kept is never read.  obs may be y itself. */
+int gcl_obs_pack(const float* y, int64_t ldy, int64_t bsy, const uint8_t* keep_row, const uint8_t* keep_chan, int32_t B,
+                 int32_t G, int32_t K, int32_t C, float* obs, int64_t ldo, int64_t bso, gcl_stream_t stream);
+/* The interpolation loop and the sums behind every score of scripts/interpolate_to_region.py:168-249.  pred [N,Gg,>=P*C]
+ * float32 with (ld, bs), longitude-major with nlat latitudes; cell int32 [nr,2] / w float64 [nr,4]: the tables of the
+ * regional nodes (longitude-major) as gcl_regrid_blend takes them; series fp16 [n_time,nr,n_feat], n_feat >= C; t0 device
+ * int32 [N]: the regional step of horizon 0 of every sample, a sample with t0 < 1 or t0 + P > n_time (-1 by convention)
+ * is skipped; first: the index of the first sample that is not skipped; mean / std float64 [C].  Per sample s, horizon p,
+ * node i, channel c:
+ *   v = the bilinear value of pred[s, :, p*C + c] in float64, four products rounded one by one and added in the order of
+ *       gcl_regrid_blend (scipy's);  t = ((double)series[t0 + p, i, c] - mean[c]) / std[c];  b the same at t0 - 1.
+ * sums float64 [P,C,11] = sum (v-t)^2, sum |v-t|, sum (b-t)^2, the count, sum t', sum t'^2, sum v', sum v'^2, sum t'v'
+ * with t' = t - tp, v' = v - vp, and the pivots tp, vp: t and v at node 0 of sample `first` for that (p, c) (0 when
+ * that sample is skipped).  vout / tout (both or neither; float32 [N,P,nr,C]) take (float)v and (float)t of the samples
+ * that are not skipped; the other samples' rows are left as they are.  A cell outside the Gg source rows gives NaN.
+ * C <= 256; N, P <= 65535.  Two stages: fixed node chunks per (sample, horizon), then the partials of a (p, c) in a fixed
+ * tree.  ws: at least gcl_region_interp_scores_ws_bytes(N, P, nr, C) bytes of 8-byte aligned device scratch. */
+size_t gcl_region_interp_scores_ws_bytes(int32_t N, int32_t P, int32_t nr, int32_t C);
+int gcl_region_interp_scores(const float* pred, int64_t ldp, int64_t bsp, int32_t Gg, int32_t nlat, const int32_t* cell,
+                             const double* w, const void* series, int32_t n_feat, int32_t n_time, const int32_t* t0,
+                             int32_t first, const double* mean, const double* std, int32_t N, int32_t P, int32_t nr,
+                             int32_t C, double* sums, float* vout, float* tout, void* ws, size_t ws_bytes,
+                             gcl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
