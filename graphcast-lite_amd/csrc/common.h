@@ -101,6 +101,19 @@ __device__ __forceinline__ double rounded(double x) {
   return x;
 }
 
+// The float64 bilinear value of a cell: src[n00], src[n00 + 1], src[n00 + nlat], src[n00 + nlat + 1] (rows of ld
+// elements) times w[0 .. 3], every product rounded on its own and added left to right - scipy's order of the four
+// corners.  The FIRST PRODUCT STARTS THE SUM, so four -0.0 corners give -0.0.  The position-form kernels (live, wrf,
+// multires, downscale) start from acc = 0.0 instead, where 0.0 + (-0.0) is +0.0: the two forms are not interchangeable.
+template <typename T>
+__device__ __forceinline__ double cell_corner_sum(const T* src, int64_t ld, int64_t n00, int32_t nlat, const double* w) {
+  double acc = rounded((double)src[n00 * ld] * w[0]);
+  acc = acc + rounded((double)src[(n00 + 1) * ld] * w[1]);
+  acc = acc + rounded((double)src[(n00 + nlat) * ld] * w[2]);
+  acc = acc + rounded((double)src[(n00 + nlat + 1) * ld] * w[3]);
+  return acc;
+}
+
 // sum over the 64 lanes of a wave, in a fixed butterfly order (every lane gets the sum)
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

@@ -8,28 +8,23 @@
 //   [2] sum o'   [3] sum o'^2   [4] sum y'   [5] sum y'^2   [6] sum o' y'      o' = o - o[b,0,c],  y' = y - y[b,0,c]
 // The shift by the column's first node takes the cancellation out of the one-pass variances, and a column that is
 // constant over the nodes has exactly zero centred sums.  Two launches with a fixed order, as in csrc/verify.hip: the
-// partial kernel sums fixed chunks of rows (the chunking depends on G only), the combine kernel sums a column's
-// chunks in a fixed order.  No atomics: a (b, c) result depends on its own data and G only, and repeats bit for bit.
+// partial kernel sums fixed chunks of rows, the combine kernel sums a column's chunks in a fixed order
+// (csrc/colsum.h, which also says why a (b, c) result depends on its own data and G only).
 //
 // Accumulate.  One launch folds the [B,C,7] sums into the float64 state [sum loss, sum acc, sum raw_mse, batches]
 // of an evaluation pass: the weighted MSE (src/train.py:85-102), the spatial anomaly correlation (:114-130, per
 // sample, unbiased std + 1e-8, static / forcing channels left out unless that leaves none) and the unweighted MSE.
+#include "colsum.h"
 #include "common.h"
 
 namespace {
 
-constexpr int kNS = 7;           // sums per (b, c)
-constexpr int kColTile = 32;     // columns per block of the partial kernel
-constexpr int kRowLanes = 8;     // row lanes per block: 256 threads = 32 columns x 8 row lanes
-constexpr int kMaxChunks = 512;  // chunks of rows per column
-constexpr int kMinChunkRows = 64;
+using gcl::chunk_rows;
+using gcl::kColTile;
+using gcl::kRowLanes;
+using gcl::num_chunks;
 
-// Chunking of G rows: a function of G only (see the file comment).
-__host__ __device__ inline int chunk_rows(int n) {
-  const int r = (n + kMaxChunks - 1) / kMaxChunks;
-  return r < kMinChunkRows ? kMinChunkRows : r;
-}
-__host__ __device__ inline int num_chunks(int n) { return n <= 0 ? 0 : (n + chunk_rows(n) - 1) / chunk_rows(n); }
+constexpr int kNS = 7;  // sums per (b, c)
 
 struct EvalIn {
   const float *delta, *x_last, *y, *node_w;
@@ -88,18 +83,8 @@ __global__ __launch_bounds__(256) void eval_partial_kernel(EvalIn a, int32_t G, 
       acc[6] = fma(op, yp, acc[6]);
     }
   }
-#pragma unroll
-  for (int s = 0; s < kNS; ++s) red[s][tid] = acc[s];
-  __syncthreads();
-  if (lane_r == 0 && live) {
-    double* dst = part + (b * C + c) * kNS * nchunk + ch;
-    for (int s = 0; s < kNS; ++s) {
-      double v = red[s][cl];
-#pragma unroll
-      for (int l = 1; l < kRowLanes; ++l) v += red[s][cl + l * kColTile];
-      dst[(int64_t)s * nchunk] = v;
-    }
-  }
+  gcl::lanes_to_part(red, acc, tid, kRowLanes, kColTile, lane_r == 0 && live, part + (b * C + c) * kNS * nchunk + ch,
+                     nchunk);
 }
 
 // One wave per (column blockIdx.x, sample blockIdx.y): lane l sums chunks l, l + 64, .. in ascending order, then the
@@ -111,12 +96,7 @@ __global__ __launch_bounds__(64) void eval_combine_kernel(const double* __restri
   const int nchunk = num_chunks(G);
   const double* src = part + (b * C + c) * kNS * nchunk;
   double v[kNS];
-#pragma unroll
-  for (int s = 0; s < kNS; ++s) {
-    double t = 0.0;
-    for (int j = lane; j < nchunk; j += 64) t += src[(int64_t)s * nchunk + j];
-    v[s] = gcl::wave_sum(t);
-  }
+  gcl::wave_strided_sum(src, nchunk, lane, v);
   if (lane < kNS) {
     double pick = v[0];
 #pragma unroll
@@ -154,14 +134,7 @@ __global__ __launch_bounds__(256) void eval_accumulate_kernel(const double* __re
     }
   }
   red[0][tid] = loss, red[1][tid] = acc, red[2][tid] = raw;
-  __syncthreads();
-  for (int w = 128; w >= 1; w >>= 1) {
-    if (tid < w) {
-#pragma unroll
-      for (int s = 0; s < 3; ++s) red[s][tid] += red[s][tid + w];
-    }
-    __syncthreads();
-  }
+  gcl::block_tree_sum(red, tid);
   if (tid == 0) {
     state[0] += inv_wsum * red[0][0];
     state[1] += red[1][0] / ((double)B * (double)nkept);

@@ -11,19 +11,23 @@
 // Column statistics (for ACC, compute_stat :84-89): per sample b and column k the mean and the unbiased standard
 // deviation over the scored rows of the converted prediction and truth, in float64.  Sums are shifted by the column's
 // first scored row, so a column 1e4 sigma from zero keeps its precision and a constant column has exactly zero
-// variance.  Two launches with a fixed order: chunks of rows (a function of n only) summed by 8 row
-// lanes, then a column's chunks summed in a fixed tree; a column's result depends on its own data and n, never on K
-// or the launch.
+// variance.  Two launches with a fixed order: chunks of rows summed by 8 row lanes, then a column's chunks summed
+// by one wave (csrc/colsum.h, which also says why a column's result depends on its own data and n only).
 //
 // Accumulate.  One thread owns its state elements and adds the B samples of the batch in sample order, so the state
 // is read and written once per update and there are no atomics.  State: float64 [lead][sum][row * C + c], sums in the
 // order of their bits (kSumE, kSumSq, kSumAbs, kSumPT), only the requested ones present.  The flat kernel reads four
 // consecutive values per 16-byte load; the generic one (row list, column map, padded rows) reads one element per
 // thread.  Both call add_sample, so they produce the same bits.
+#include "colsum.h"
 #include "common.h"
 
 namespace {
 
+using gcl::chunk_rows;
+using gcl::kColTile;  // at most this many columns per block
+using gcl::kRowLanes;
+using gcl::num_chunks;
 using gcl::rounded;
 
 constexpr int kSumE = 1, kSumSq = 2, kSumAbs = 4, kSumPT = 8;  // sum e, sum e^2, sum |e|, sum p^ t^
@@ -31,18 +35,8 @@ constexpr int kDenorm = 1, kZDiv = 2;
 constexpr float kG0 = 9.80665f;
 constexpr int kKindRmse = 0, kKindSkill = 4;  // 1 mae, 2 bias, 3 acc: the sum over n
 
-constexpr int kRowLanes = 8;     // row lanes of a chunk: fixes the summation order
 constexpr int kColBlock = 512;   // threads of a partial block: as many whole chunks as fit (3 x 152 lanes at K = 19)
-constexpr int kColTile = 32;     // at most this many columns per block
-constexpr int kMaxChunks = 512;  // chunks of rows per column
-constexpr int kMinChunkRows = 64;
 constexpr int kPartSums = 4;     // Sp, Spp, St, Stt
-
-__host__ __device__ inline int chunk_rows(int n) {
-  const int r = (n + kMaxChunks - 1) / kMaxChunks;
-  return r < kMinChunkRows ? kMinChunkRows : r;
-}
-__host__ __device__ inline int num_chunks(int n) { return n <= 0 ? 0 : (n + chunk_rows(n) - 1) / chunk_rows(n); }
 
 struct Conv {
   float scale, mean, factor, offset;
@@ -132,19 +126,8 @@ __global__ __launch_bounds__(kColBlock) void maps_colstats_partial_kernel(
       }
     }
   }
-#pragma unroll
-  for (int s = 0; s < kPartSums; ++s) red[s][tid] = acc[s];
-  __syncthreads();
-  if (live && rl == 0) {
-    double* out = part + ((int64_t)b * K + k) * kPartSums * nchunk + ch;
-#pragma unroll
-    for (int s = 0; s < kPartSums; ++s) {
-      double v = red[s][tid];
-#pragma unroll
-      for (int l = 1; l < kRowLanes; ++l) v += red[s][tid + l * CT];
-      out[(int64_t)s * nchunk] = v;
-    }
-  }
+  gcl::lanes_to_part(red, acc, tid, kRowLanes, CT, live && rl == 0,
+                     part + ((int64_t)b * K + k) * kPartSums * nchunk + ch, nchunk);
 }
 
 // One wave per (column blockIdx.x, sample blockIdx.y): cs[(b * K + k) * 4 + {mean_p, std_p, mean_t, std_t}].
@@ -160,15 +143,8 @@ __global__ __launch_bounds__(64) void maps_colstats_combine_kernel(
   const int64_t r0 = rows ? rows[0] : 0;
   const float tf = T[(int64_t)b * bst + r0 * ldt + k];
   const float pf = P[(int64_t)b * bsp + r0 * ldp + (pmap ? pmap[k] : k)];
-  // a lane adds its chunks in ascending order; the four sums advance together so that their loads overlap
-  double S[kPartSums] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll 4
-  for (int j = tid; j < nchunk; j += 64) {
-#pragma unroll
-    for (int s = 0; s < kPartSums; ++s) S[s] += src[(int64_t)s * nchunk + j];
-  }
-#pragma unroll
-  for (int s = 0; s < kPartSums; ++s) S[s] = gcl::wave_sum(S[s]);
+  double S[kPartSums];
+  gcl::wave_strided_sum(src, nchunk, tid, S);
   if (tid == 0) {
     const double t0 = (double)to_units(tf, cv);
     const double p0 = (double)to_units(pf, cv);

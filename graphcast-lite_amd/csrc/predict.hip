@@ -16,11 +16,10 @@
 // kernel adds the partials of a (p, c) in a fixed tree.
 #include <hip/hip_fp16.h>
 
+#include "colsum.h"
 #include "common.h"
 
 namespace {
-
-using gcl::rounded;
 
 constexpr uint32_t kQuietNaN = 0x7fc00000u;
 
@@ -88,13 +87,7 @@ __device__ __forceinline__ double interp(const RegionIn& a, int s, int i, int co
   const int64_t n00 = (int64_t)a.cell[2 * i] * a.nlat + a.cell[2 * i + 1];
   if (a.cell[2 * i] < 0 || a.cell[2 * i + 1] < 0 || a.cell[2 * i + 1] + 1 >= a.nlat || n00 + a.nlat + 1 >= a.Gg)
     return __longlong_as_double(0x7ff8000000000000ll);
-  const float* src = a.pred + (int64_t)s * a.bsp + col;
-  const double* wi = a.w + 4 * (int64_t)i;
-  double acc = rounded((double)src[n00 * a.ldp] * wi[0]);
-  acc = acc + rounded((double)src[(n00 + 1) * a.ldp] * wi[1]);
-  acc = acc + rounded((double)src[(n00 + a.nlat) * a.ldp] * wi[2]);
-  acc = acc + rounded((double)src[(n00 + a.nlat + 1) * a.ldp] * wi[3]);
-  return acc;
+  return gcl::cell_corner_sum(a.pred + (int64_t)s * a.bsp + col, a.ldp, n00, a.nlat, a.w + 4 * (int64_t)i);
 }
 
 __device__ __forceinline__ double truth(const RegionIn& a, int t, int i, int c, double m, double sd) {
@@ -152,18 +145,9 @@ __global__ __launch_bounds__(256) void region_partial_kernel(RegionIn a, double*
       }
     }
   }
-#pragma unroll
-  for (int q = 0; q < kNS; ++q) red[q][tid] = acc[q];
-  __syncthreads();
-  if (tid < C) {
-    const int64_t nparts = (int64_t)a.N * nchunk;
-    double* out = part + (int64_t)(p * C + tid) * kNS * nparts + (int64_t)s * nchunk + chunk;
-    for (int q = 0; q < kNS; ++q) {
-      double v = red[q][tid];
-      for (int l = 1; l < R; ++l) v += red[q][tid + l * C];
-      out[(int64_t)q * nparts] = v;
-    }
-  }
+  const int64_t nparts = (int64_t)a.N * nchunk;
+  gcl::lanes_to_part(red, acc, tid, R, C, tid < C,
+                     part + (int64_t)(p * C + tid) * kNS * nparts + (int64_t)s * nchunk + chunk, nparts);
 }
 
 // One block per (p, c): the partials of each sum in a fixed tree; sums[(p * C + c) * kNOut + {0..8: the sums, 9: tp, 10: vp}]
@@ -172,19 +156,8 @@ __global__ __launch_bounds__(256) void region_combine_kernel(RegionIn a, const d
   __shared__ double red[kNS][256];
   const int pc = blockIdx.x, tid = threadIdx.x;
   const double* src = part + (int64_t)pc * kNS * nparts;
-  for (int q = 0; q < kNS; ++q) {
-    double v = 0.0;
-    for (int64_t j = tid; j < nparts; j += 256) v += src[(int64_t)q * nparts + j];
-    red[q][tid] = v;
-  }
-  __syncthreads();
-  for (int wd = 128; wd >= 1; wd >>= 1) {
-    if (tid < wd) {
-#pragma unroll
-      for (int q = 0; q < kNS; ++q) red[q][tid] += red[q][tid + wd];
-    }
-    __syncthreads();
-  }
+  for (int q = 0; q < kNS; ++q) red[q][tid] = gcl::strided_sum(src + (int64_t)q * nparts, nparts, tid);
+  gcl::block_tree_sum(red, tid);
   double* o = sums + (int64_t)pc * kNOut;
   if (tid < kNS) o[tid] = red[tid][0];
   if (tid == 0) {

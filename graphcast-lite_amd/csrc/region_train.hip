@@ -12,6 +12,7 @@
 //   pred [n_roi, Cp]   = [pred[rows[i]] | 0],                 Cp  = roundup(C, 4)
 //   y    [n_roi, Yp]   = [y[rows[i]] | 0],                    Yp  = roundup(P * C, 4)
 // No kernel here allocates, synchronises or uses atomics; the reductions have a fixed order.
+#include "colsum.h"
 #include "common.h"
 
 namespace {
@@ -227,11 +228,7 @@ __global__ __launch_bounds__(256) void pair_partial_kernel(PairIn a, const int32
     }
   }
   red[0][tid] = acc[0], red[1][tid] = acc[1];
-  __syncthreads();
-  for (int w = 128; w >= 1; w >>= 1) {
-    if (tid < w) red[0][tid] += red[0][tid + w], red[1][tid] += red[1][tid + w];
-    __syncthreads();
-  }
+  gcl::block_tree_sum(red, tid);
   if (tid < NQ) part[(int64_t)tid * nchunk + blockIdx.x] = red[tid][0];
 }
 
@@ -241,15 +238,8 @@ __global__ __launch_bounds__(256) void pair_combine_kernel(const double* __restr
                                                            double scale, double* __restrict__ acc) {
   __shared__ double red[2][256];
   const int tid = threadIdx.x;
-  double v[2] = {0.0, 0.0};
-  for (int q = 0; q < nq; ++q)
-    for (int64_t j = tid; j < nchunk; j += 256) v[q] += part[(int64_t)q * nchunk + j];
-  red[0][tid] = v[0], red[1][tid] = v[1];
-  __syncthreads();
-  for (int w = 128; w >= 1; w >>= 1) {
-    if (tid < w) red[0][tid] += red[0][tid + w], red[1][tid] += red[1][tid + w];
-    __syncthreads();
-  }
+  for (int q = 0; q < 2; ++q) red[q][tid] = q < nq ? gcl::strided_sum(part + (int64_t)q * nchunk, nchunk, tid) : 0.0;
+  gcl::block_tree_sum(red, tid);
   if (tid < nq) acc[tid] += scale * red[tid][0];
 }
 

@@ -7,26 +7,26 @@
 // The centred sums come from one pass over values shifted by the column's first row (t' = t - t[row 0],
 // p' = p - p[row 0]), so a column whose mean is 1e4 standard deviations from 0 loses nothing to cancellation and a
 // constant column has exactly zero centred sums (corr = 0 / 1e-8 = 0).  Two launches with a fixed order: the
-// partial kernel sums fixed chunks of rows (the chunking depends on n only), the combine kernel sums the chunks of a
-// column in a fixed tree.  A column's result therefore depends on its own data and n, never on K, on the other
-// columns or on the launch: a per-horizon slice scored alone gives the same bits as inside the full forecast.
+// partial kernel sums fixed chunks of rows, the combine kernel sums the chunks of a column in a fixed tree
+// (csrc/colsum.h, which also says why a column's result depends on its own data and n only).
 //
 // Accumulate.  Adds the column results of one or more samples into the float64 state of StreamingMetrics objects
 // (one job per object), in the reference's order.
 //
 // Regrid + blend.  Bilinear interpolation with host-built tables (cell, four float64 weights), summed in float64 in
 // scipy's order and rounded once to float32; optionally the taper blend m r + (1 - m) g in float32.
+#include "colsum.h"
 #include "common.h"
 
 namespace {
 
+using gcl::chunk_rows;
+using gcl::kColTile;
+using gcl::kRowLanes;
+using gcl::num_chunks;
 using gcl::rounded;  // products rounded on their own, never contracted (common.h)
 
 constexpr int kMaxPred = 4;
-constexpr int kColTile = 32;     // columns per block of the partial kernel
-constexpr int kRowLanes = 8;     // row lanes per block: 256 threads = 32 columns x 8 row lanes
-constexpr int kMaxChunks = 512;  // chunks of rows per column
-constexpr int kMinChunkRows = 64;
 
 struct Preds {
   const float* p[kMaxPred];
@@ -34,13 +34,6 @@ struct Preds {
   int64_t bs[kMaxPred];
   const int32_t* map[kMaxPred];
 };
-
-// Chunking of n rows: a function of n only (see the file comment).
-__host__ __device__ inline int chunk_rows(int n) {
-  const int r = (n + kMaxChunks - 1) / kMaxChunks;
-  return r < kMinChunkRows ? kMinChunkRows : r;
-}
-__host__ __device__ inline int num_chunks(int n) { return n <= 0 ? 0 : (n + chunk_rows(n) - 1) / chunk_rows(n); }
 
 // Sums per column, in this order: St, Stt, then per prediction Sp, Spp, Stp, Sse, Sae.
 template <int NP>
@@ -112,18 +105,8 @@ __global__ __launch_bounds__(256) void colstats_partial_kernel(const float* __re
       }
     }
   }
-#pragma unroll
-  for (int s = 0; s < NS; ++s) red[s][tid] = acc[s];
-  __syncthreads();
-  if (lane_r == 0 && live) {
-    double* out = part + ((int64_t)b * K + c) * NS * nchunk + ch;
-    for (int s = 0; s < NS; ++s) {
-      double v = red[s][cl];
-#pragma unroll
-      for (int l = 1; l < kRowLanes; ++l) v += red[s][cl + l * kColTile];
-      out[(int64_t)s * nchunk] = v;
-    }
-  }
+  gcl::lanes_to_part(red, acc, tid, kRowLanes, kColTile, lane_r == 0 && live,
+                     part + ((int64_t)b * K + c) * NS * nchunk + ch, nchunk);
 }
 
 // One block per (column blockIdx.x, sample blockIdx.y): the column's chunks in a fixed tree, then the three results
@@ -136,19 +119,8 @@ __global__ __launch_bounds__(256) void colstats_combine_kernel(const double* __r
   const int k = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
   const int nchunk = num_chunks(n);
   const double* src = part + ((int64_t)b * K + k) * NS * nchunk;
-  for (int s = 0; s < NS; ++s) {
-    double v = 0.0;
-    for (int j = tid; j < nchunk; j += 256) v += src[(int64_t)s * nchunk + j];
-    red[s][tid] = v;
-  }
-  __syncthreads();
-  for (int w = 128; w >= 1; w >>= 1) {
-    if (tid < w) {
-#pragma unroll
-      for (int s = 0; s < NS; ++s) red[s][tid] += red[s][tid + w];
-    }
-    __syncthreads();
-  }
+  for (int s = 0; s < NS; ++s) red[s][tid] = gcl::strided_sum(src + (int64_t)s * nchunk, nchunk, tid);
+  gcl::block_tree_sum(red, tid);
   if (tid < NP) {
     const int q = tid;
     const double N = (double)n;
@@ -234,12 +206,7 @@ __global__ __launch_bounds__(256) void regrid_kernel(const TS* __restrict__ src,
     const int64_t b = rem / nt;
     const int64_t n00 = (int64_t)cell[2 * i] * nlat + cell[2 * i + 1];
     const TS* s = src + b * bss + k;
-    const double* wi = w + 4 * (int64_t)i;
-    double acc = rounded((double)s[n00 * lds] * wi[0]);
-    acc = acc + rounded((double)s[(n00 + 1) * lds] * wi[1]);
-    acc = acc + rounded((double)s[(n00 + nlat) * lds] * wi[2]);
-    acc = acc + rounded((double)s[(n00 + nlat + 1) * lds] * wi[3]);
-    const float gv = (float)acc;
+    const float gv = (float)gcl::cell_corner_sum(s, lds, n00, nlat, w + 4 * (int64_t)i);
     if (g) g[b * bsg + (int64_t)i * ldg + k] = gv;
     if (out) {
       const float m = mask[i];

@@ -11,7 +11,6 @@ and `gcl_downscale_pair_mse`.  The objective, the scores and the training loop (
 """
 import json
 import os
-from collections import OrderedDict
 from typing import Optional, Sequence
 
 import numpy as np
@@ -23,37 +22,13 @@ from .data import _upload_fp16
 from .downscale_train import (DownscalerMetrics, compute_metrics, downscaler_loss, downscaler_results,  # noqa: F401
                               fit_downscaler, gradient_loss, iter_batches, masked_mse_loss, metrics_table,
                               spectral_loss, train_epoch, validate)
+from .interp_tables import TableCache, device_tables
 from .verify import regrid_tables, regrid_tables_latlon
 
 # ======================================================================================================================
 # Host tables (once per geometry)
 # ======================================================================================================================
-_TABLES = OrderedDict()  # least recently used first
-MAX_CACHED_TABLES = 16
-
-
-def _key(a):
-    a = np.ascontiguousarray(a)
-    return (a.dtype.str, a.shape, a.tobytes())
-
-
-def _cached(key, make):
-    hit = _TABLES.get(key)
-    if hit is not None:
-        _TABLES.move_to_end(key)
-        return hit
-    val = make()
-    for a in val:
-        a.setflags(write=False)
-    _TABLES[key] = val
-    while len(_TABLES) > MAX_CACHED_TABLES:
-        _TABLES.popitem(last=False)
-    return val
-
-
-def _device_tables(pos, w, device):
-    # (the cached tables are read-only: upload copies)
-    return torch.from_numpy(np.array(pos)).to(device), torch.from_numpy(np.array(w)).to(device)
+_TABLES = TableCache()
 
 
 def roi_crop(g_lats, g_lons, roi, buffer: float = 1.0):
@@ -87,7 +62,8 @@ def coarse_tables(g_lats, g_lons, r_lats, r_lons, roi, buffer: float = 1.0):
         assert pos.min() >= 0 and pos.max() < n_lat * len(g_lons) < 2 ** 31
         return np.ascontiguousarray(pos.astype(np.int32)), np.ascontiguousarray(w)
 
-    return _cached(("coarse", _key(g_lats), _key(g_lons), _key(r_lats), _key(r_lons), roi, float(buffer)), make)
+    key = TableCache.array_key
+    return _TABLES.get(("coarse", key(g_lats), key(g_lons), key(r_lats), key(r_lons), roi, float(buffer)), make)
 
 
 def prediction_tables(grid_lats, grid_lons, roi, target_lats, target_lons, flat_grid: bool = True):
@@ -136,7 +112,8 @@ def prediction_tables(grid_lats, grid_lons, roi, target_lats, target_lons, flat_
         assert pos.min() >= 0 and pos.max() < len(grid_lats) < 2 ** 31
         return np.ascontiguousarray(pos.astype(np.int32)), np.ascontiguousarray(w)
 
-    return _cached(("pred", _key(grid_lats), _key(grid_lons), roi, _key(t_lats), _key(t_lons), bool(flat_grid)), make)
+    key = TableCache.array_key
+    return _TABLES.get(("pred", key(grid_lats), key(grid_lons), roi, key(t_lats), key(t_lons), bool(flat_grid)), make)
 
 
 def _lon_first(pos, w, n_lat: int, n_lon: int):
@@ -243,7 +220,7 @@ def build_downscaler_dataset(global_src, region_src, roi, static_channels: Seque
     if T < 1 or frames_per_launch < 1:
         raise ValueError(f"build_downscaler_dataset: {T} common frames, {frames_per_launch} frames per launch")
     n_lon_f, n_lat_f = len(r_lons), len(r_lats)
-    pos, w = _device_tables(*coarse_tables(g_lats, g_lons, r_lats, r_lons, roi), g_series.device)
+    pos, w = device_tables(*coarse_tables(g_lats, g_lons, r_lats, r_lons, roi), g_series.device)
     coarse = torch.empty(T, n_lon_f, n_lat_f, C, dtype=torch.float16, device=g_series.device)
     fine = torch.empty_like(coarse)
     for t0 in range(0, T, frames_per_launch):
@@ -276,7 +253,7 @@ def crop_and_upsample_roi(pred_flat, grid_lats, grid_lons, roi, target_lats, tar
     if pred_flat.stride(1) != 1:
         pred_flat = pred_flat.contiguous()
     G, C = pred_flat.shape
-    pos, w = _device_tables(*tables, pred_flat.device)
+    pos, w = device_tables(*tables, pred_flat.device)
     src = hip.WrfSource(pred_flat, pred_flat.stride(0), G, pos, w)
     out64 = hip.wrf_sample(src, list(range(C)))  # [C, P], P latitude-major
     return out64.to(torch.float32).t().reshape(len(target_lats), len(target_lons), C).contiguous()
@@ -298,7 +275,7 @@ class GnnPredictionArchive:
         # (the targets are the axes as coords.npz holds them: float32, widened - what the reference's script reads)
         t_lats, t_lons = (np.asarray(a).astype(np.float32).astype(np.float64) for a in (pairs.lats, pairs.lons))
         pos, w = prediction_tables(grid_lats, grid_lons, roi, t_lats, t_lons, flat_grid)
-        self.pos, self.w = _device_tables(*_lon_first(pos, w, n_lat, n_lon), dev)
+        self.pos, self.w = device_tables(*_lon_first(pos, w, n_lat, n_lon), dev)
         f32 = lambda a: torch.from_numpy(np.asarray(a, dtype=np.float32)[:self.C].copy()).to(dev)  # noqa: E731
         self.mean, self.std = f32(mean), f32(std)
         if pairs.gnn_pred is None:

@@ -18,7 +18,6 @@ numpy arrays or device tensors in the source's own orientation, and different va
 Kernels: csrc/live.hip.
 """
 import json
-from collections import OrderedDict
 from datetime import datetime, timedelta
 from pathlib import Path
 from typing import Dict, List, Optional, Sequence, Tuple
@@ -27,7 +26,7 @@ import numpy as np
 import torch
 
 from . import hip, mos, pipeline, predict
-from .verify import find_cells
+from .interp_tables import CORNERS, TableCache, bilinear_corners
 
 CITY_BBOX = (55.5, 56.5, 92.0, 94.0)
 
@@ -249,13 +248,8 @@ def summarize_city(out_path, prediction_phys: np.ndarray, latitudes: np.ndarray,
 # ======================================================================================================================
 # Point tables (:378-407)
 # ======================================================================================================================
-_TABLES = OrderedDict()  # least recently used first
 MAX_CACHED_TABLES = 16  # a key holds copies of its axes and node lists, a value 48 bytes per node
-
-
-def _key(a: np.ndarray):
-    a = np.ascontiguousarray(a)
-    return (a.dtype.str, a.shape, a.tobytes())
+_TABLES = TableCache(MAX_CACHED_TABLES)
 
 
 def point_tables(src_lats, src_lons, node_lats, node_lons):
@@ -271,41 +265,27 @@ def point_tables(src_lats, src_lons, node_lats, node_lons):
     node_lats, node_lons = np.asarray(node_lats), np.asarray(node_lons)
     if src_lats.ndim != 1 or src_lons.ndim != 1 or node_lats.ndim != 1 or node_lats.shape != node_lons.shape:
         raise ValueError("point_tables: the source axes and the node coordinates must be 1-d (nodes of equal length)")
-    key = (_key(src_lats), _key(src_lons), _key(node_lats), _key(node_lons))
-    hit = _TABLES.get(key)
-    if hit is not None:
-        _TABLES.move_to_end(key)
-        return hit
-    lats = np.asarray(src_lats, dtype=np.float32)
-    lons = np.asarray(src_lons, dtype=np.float32) % 360.0
-    lat_order, lon_order = np.argsort(lats), np.argsort(lons)
-    lats_sorted, lons_sorted = lats[lat_order], lons[lon_order]
-    ext_lons = np.concatenate([lons_sorted, [lons_sorted[0] + 360.0]])
-    col_of = np.concatenate([lon_order, lon_order[:1]])  # the wrap column is the first sorted column again
-    q_lat = node_lats.astype(np.float32)
-    q_lon = np.mod(node_lons, 360.0).astype(np.float32)
-    if not (np.all(np.isfinite(q_lat)) and np.all(np.isfinite(q_lon))):
-        raise ValueError("point_tables: node coordinates must be finite")
-    ilat, ylat = find_cells(lats_sorted, q_lat)
-    ilon, ylon = find_cells(ext_lons, q_lon)
-    nlon = lons.size
-    one = np.float64(1.0)
-    lat_w = (one * (1 - ylat), one * ylat)
-    lon_w = (1 - ylon, ylon)
-    pos = np.empty((q_lat.size, 4), dtype=np.int64)
-    w = np.empty((q_lat.size, 4), dtype=np.float64)
-    for k, (da, do) in enumerate(((0, 0), (0, 1), (1, 0), (1, 1))):
-        pos[:, k] = lat_order[ilat + da].astype(np.int64) * nlon + col_of[ilon + do]
-        w[:, k] = lat_w[da] * lon_w[do]
-    if pos.size and (pos.min() < 0 or pos.max() >= lats.size * nlon or lats.size * nlon >= 2 ** 31):
-        raise ValueError("point_tables: a corner position lies outside the source field")
-    pos = pos.astype(np.int32)
-    pos.setflags(write=False)
-    w.setflags(write=False)
-    _TABLES[key] = (pos, w)
-    while len(_TABLES) > MAX_CACHED_TABLES:
-        _TABLES.popitem(last=False)
-    return pos, w
+    key = tuple(TableCache.array_key(a) for a in (src_lats, src_lons, node_lats, node_lons))
+
+    def make():
+        lats = np.asarray(src_lats, dtype=np.float32)
+        lons = np.asarray(src_lons, dtype=np.float32) % 360.0
+        lat_order, lon_order = np.argsort(lats), np.argsort(lons)
+        lats_sorted, lons_sorted = lats[lat_order], lons[lon_order]
+        ext_lons = np.concatenate([lons_sorted, [lons_sorted[0] + 360.0]])
+        col_of = np.concatenate([lon_order, lon_order[:1]])  # the wrap column is the first sorted column again
+        q_lat = node_lats.astype(np.float32)
+        q_lon = np.mod(node_lons, 360.0).astype(np.float32)
+        if not (np.all(np.isfinite(q_lat)) and np.all(np.isfinite(q_lon))):
+            raise ValueError("point_tables: node coordinates must be finite")
+        ilat, ilon, w = bilinear_corners(lats_sorted, ext_lons, q_lat, q_lon)
+        nlon = lons.size
+        pos = np.stack([lat_order[ilat + da].astype(np.int64) * nlon + col_of[ilon + do] for da, do in CORNERS], axis=1)
+        if pos.size and (pos.min() < 0 or pos.max() >= lats.size * nlon or lats.size * nlon >= 2 ** 31):
+            raise ValueError("point_tables: a corner position lies outside the source field")
+        return pos.astype(np.int32), w
+
+    return _TABLES.get(key, make)
 
 
 # ======================================================================================================================
@@ -370,7 +350,7 @@ class LiveFramePacker:
             lats, lons = np.asarray(lats), np.asarray(lons)
             if tuple(values.shape) != (lats.size, lons.size):
                 raise ValueError(f"{name}: values {tuple(values.shape)} do not match the axes ({lats.size}, {lons.size})")
-            layout.append((name, _key(lats), _key(lons)))
+            layout.append((name, TableCache.array_key(lats), TableCache.array_key(lons)))
             axes.append((lats, lons))
         key = tuple(layout)
         hit = self._plans.get(key)

@@ -31,6 +31,7 @@ import torch
 
 from . import hip
 from .capture import Captured
+from .interp_tables import TableCache, bilinear_corners, device_tables, find_cells  # noqa: F401
 
 _STATE_FIXED = 4  # [sum_se, sum_ae, n, total_elem] ahead of the four per-channel vectors
 
@@ -326,38 +327,13 @@ class ForecastVerifier:
 # ======================================================================================================================
 # Regridding (scripts/predict_pipeline.py:95-132, scripts/interpolate_to_region.py:64-73)
 # ======================================================================================================================
-def find_cells(grid, x):
-    """(cell index, normalised distance) of every x on an ascending axis, as scipy's RegularGridInterpolator finds
-    them: the cell [grid[i], grid[i+1]) holding x, clipped to [0, n-2] (x below the first node: cell 0, x on or past
-    the last node: cell n-2), distance (x - grid[i]) / (grid[i+1] - grid[i]) in float64 (outside [0, 1] when
-    extrapolating)."""
-    grid = np.asarray(grid, dtype=np.float64)
-    x = np.asarray(x, dtype=np.float64)
-    if grid.ndim != 1 or grid.size < 2 or not np.all(np.diff(grid) > 0):
-        raise ValueError("the source axes must be strictly ascending with at least 2 points")
-    i = np.clip(np.searchsorted(grid, x, side="right") - 1, 0, grid.size - 2)
-    return i.astype(np.int64), (x - grid[i]) / (grid[i + 1] - grid[i])
-
-
 def regrid_tables(src_lats, src_lons, dst_lats, dst_lons):
     """Host tables of the bilinear regrid from the (src_lons, src_lats) grid onto the targets (dst_lons[j],
     dst_lats[i]), numbered longitude-major (j * len(dst_lats) + i): int32 [nt, 2] cells (lon, lat) and float64 [nt, 4]
     weights of the corners (lon, lat), (lon, lat+1), (lon+1, lat), (lon+1, lat+1), each formed as 1 * w_lon * w_lat."""
-    ilon, ylon = find_cells(src_lons, dst_lons)
-    ilat, ylat = find_cells(src_lats, dst_lats)
-    nj, ni = len(ilon), len(ilat)
-    cell = np.empty((nj, ni, 2), dtype=np.int32)
-    cell[..., 0] = ilon[:, None]
-    cell[..., 1] = ilat[None, :]
-    one = np.float64(1.0)
-    lon_w = ((one * (1 - ylon))[:, None], (one * ylon)[:, None])
-    lat_w = ((1 - ylat)[None, :], ylat[None, :])
-    w = np.empty((nj, ni, 4), dtype=np.float64)
-    w[..., 0] = lon_w[0] * lat_w[0]
-    w[..., 1] = lon_w[0] * lat_w[1]
-    w[..., 2] = lon_w[1] * lat_w[0]
-    w[..., 3] = lon_w[1] * lat_w[1]
-    return cell.reshape(-1, 2), w.reshape(-1, 4)
+    q_lons, q_lats = np.asarray(dst_lons, dtype=np.float64), np.asarray(dst_lats, dtype=np.float64)
+    ilon, ilat, w = bilinear_corners(src_lons, src_lats, q_lons[:, None], q_lats[None, :])
+    return np.stack([ilon, ilat], axis=1).astype(np.int32), w
 
 
 def regrid_tables_latlon(src_lats, src_lons, dst_lats, dst_lons):
@@ -366,35 +342,19 @@ def regrid_tables_latlon(src_lats, src_lons, dst_lats, dst_lons):
     and float64 [nt, 4] weights of the corners (lat, lon), (lat, lon+1), (lat+1, lon), (lat+1, lon+1), each formed as
     (1 * w_lat) * w_lon.  The products equal those of `regrid_tables`; the ORDER of the corners is what differs, and
     with it the float64 sum."""
-    ilat, ylat = find_cells(src_lats, dst_lats)
-    ilon, ylon = find_cells(src_lons, dst_lons)
-    ni, nj = len(ilat), len(ilon)
-    cell = np.empty((ni, nj, 2), dtype=np.int32)
-    cell[..., 0] = ilat[:, None]
-    cell[..., 1] = ilon[None, :]
-    one = np.float64(1.0)
-    lat_w = ((one * (1 - ylat))[:, None], (one * ylat)[:, None])
-    lon_w = ((1 - ylon)[None, :], ylon[None, :])
-    w = np.empty((ni, nj, 4), dtype=np.float64)
-    w[..., 0] = lat_w[0] * lon_w[0]
-    w[..., 1] = lat_w[0] * lon_w[1]
-    w[..., 2] = lat_w[1] * lon_w[0]
-    w[..., 3] = lat_w[1] * lon_w[1]
-    return cell.reshape(-1, 2), w.reshape(-1, 4)
+    q_lats, q_lons = np.asarray(dst_lats, dtype=np.float64), np.asarray(dst_lons, dtype=np.float64)
+    ilat, ilon, w = bilinear_corners(src_lats, src_lons, q_lats[:, None], q_lons[None, :])
+    return np.stack([ilat, ilon], axis=1).astype(np.int32), w
 
 
-_TABLES = {}
+_TABLES = TableCache()
 
 
 def _device_tables(src_lats, src_lons, dst_lats, dst_lons, device):
+    """The `regrid_tables` of the axes on the device: built and uploaded once, then the same (shared) tensors."""
     axes = [np.ascontiguousarray(np.asarray(a, dtype=np.float64)) for a in (src_lats, src_lons, dst_lats, dst_lons)]
-    key = tuple((a.tobytes(), a.size) for a in axes) + (str(device),)
-    t = _TABLES.get(key)
-    if t is None:
-        cell, w = regrid_tables(*axes)
-        t = (torch.from_numpy(cell).to(device), torch.from_numpy(w).to(device))
-        _TABLES[key] = t
-    return t
+    key = tuple(TableCache.array_key(a) for a in axes)
+    return device_tables(*_TABLES.get(key, lambda: regrid_tables(*axes)), device)
 
 
 def interpolate_global_to_region(global_pred, global_lats, global_lons, region_lats, region_lons):

@@ -15,7 +15,6 @@ Reading netCDF WRF output (xarray, netCDF4) and plotting are not provided: WRF c
 Kernels: csrc/wrf.hip.
 """
 import json
-from collections import OrderedDict
 from datetime import datetime, timedelta
 from pathlib import Path
 from typing import Dict, Optional, Sequence
@@ -25,7 +24,7 @@ import torch
 
 from . import hip
 from .capture import Captured
-from .verify import find_cells
+from .interp_tables import CORNERS, TableCache, bilinear_corners, device_tables
 
 # WRF d03 (Krasnoyarsk), compare_wrf.py:36-37
 WRF_LAT_MIN, WRF_LAT_MAX = 55.5, 56.5
@@ -196,13 +195,7 @@ def find_wrf_matching_sample(data_dir, wrf_path, sample_offsets, obs_window, P=N
     return idx
 
 
-_TABLES = OrderedDict()  # least recently used first
-MAX_CACHED_TABLES = 16
-
-
-def _key(a):
-    a = np.ascontiguousarray(a)
-    return (a.dtype.str, a.shape, a.tobytes())
+_TABLES = TableCache()
 
 
 def wrf_point_tables(src_lons, src_lats, wrf_lon, wrf_lat, node_of=None):
@@ -214,7 +207,7 @@ def wrf_point_tables(src_lons, src_lats, wrf_lon, wrf_lat, node_of=None):
     strictly above the last node of either axis is outside: its positions are -1 and its weights 0 (the kernels give
     NaN); a point exactly on the last node is inside, cell n-2 with weight 1.  node_of (int [n_lon * n_lat]): the
     storage row of every regular node, for a flat grid that holds the same nodes in another order.  Cached per distinct
-    arguments (the MAX_CACHED_TABLES most recently used); the arrays are shared and read-only."""
+    arguments (the 16 most recently used); the arrays are shared and read-only."""
     src_lons, src_lats = np.asarray(src_lons, dtype=np.float64), np.asarray(src_lats, dtype=np.float64)
     q_lon = np.asarray(wrf_lon).reshape(-1).astype(np.float64)
     q_lat = np.asarray(wrf_lat).reshape(-1).astype(np.float64)
@@ -229,43 +222,24 @@ def wrf_point_tables(src_lons, src_lats, wrf_lon, wrf_lat, node_of=None):
         node_of = np.asarray(node_of, dtype=np.int64)
         if node_of.shape != (n_lon * n_lat,) or node_of.min() < 0 or node_of.max() >= 2 ** 31:
             raise ValueError("wrf_point_tables: node_of must hold one row per regular node")
-    key = (_key(src_lons), _key(src_lats), _key(q_lon), _key(q_lat), None if node_of is None else _key(node_of))
-    hit = _TABLES.get(key)
-    if hit is not None:
-        _TABLES.move_to_end(key)
-        return hit
-    ilon, ylon = find_cells(src_lons, q_lon)
-    ilat, ylat = find_cells(src_lats, q_lat)
-    outside = (q_lon < src_lons[0]) | (q_lon > src_lons[-1]) | (q_lat < src_lats[0]) | (q_lat > src_lats[-1])
-    one = np.float64(1.0)
-    lon_w = (one * (1 - ylon), one * ylon)
-    lat_w = (1 - ylat, ylat)
-    pos = np.empty((q_lon.size, 4), dtype=np.int64)
-    w = np.empty((q_lon.size, 4), dtype=np.float64)
-    for k, (da, do) in enumerate(((0, 0), (0, 1), (1, 0), (1, 1))):
-        pos[:, k] = (ilon + da) * n_lat + (ilat + do)
-        w[:, k] = lon_w[da] * lat_w[do]
-    if node_of is not None:
-        pos = node_of[pos]
-    pos[outside] = -1
-    w[outside] = 0.0
-    pos = pos.astype(np.int32)
-    pos.setflags(write=False)
-    w.setflags(write=False)
-    _TABLES[key] = (pos, w)
-    while len(_TABLES) > MAX_CACHED_TABLES:
-        _TABLES.popitem(last=False)
-    return pos, w
+    key = tuple(None if a is None else TableCache.array_key(a) for a in (src_lons, src_lats, q_lon, q_lat, node_of))
+
+    def make():
+        ilon, ilat, w = bilinear_corners(src_lons, src_lats, q_lon, q_lat)
+        outside = (q_lon < src_lons[0]) | (q_lon > src_lons[-1]) | (q_lat < src_lats[0]) | (q_lat > src_lats[-1])
+        pos = np.stack([(ilon + da) * n_lat + (ilat + do) for da, do in CORNERS], axis=1)
+        if node_of is not None:
+            pos = node_of[pos]
+        pos[outside] = -1
+        w[outside] = 0.0
+        return pos.astype(np.int32), w
+
+    return _TABLES.get(key, make)
 
 
 # ======================================================================================================================
 # Device functions
 # ======================================================================================================================
-def _device_tables(pos, w, device):
-    # (the cached tables are read-only: upload copies)
-    return torch.from_numpy(np.array(pos)).to(device), torch.from_numpy(np.array(w)).to(device)
-
-
 def _field_source(field, era5_lons, era5_lats, wrf_lat, wrf_lon):
     """(WrfSource, element offset) of one [n_lon, n_lat] field tensor read in place."""
     n_lon, n_lat = len(era5_lons), len(era5_lats)
@@ -274,7 +248,7 @@ def _field_source(field, era5_lons, era5_lats, wrf_lat, wrf_lon):
     if field.stride(1) < 1 or field.stride(0) != n_lat * field.stride(1):
         field = field.contiguous()
     pos, w = wrf_point_tables(era5_lons, era5_lats, wrf_lon, wrf_lat)
-    pos_d, w_d = _device_tables(pos, w, field.device)
+    pos_d, w_d = device_tables(pos, w, field.device)
     return hip.WrfSource(field, field.stride(1), n_lon * n_lat, pos_d, w_d), 0
 
 
@@ -370,7 +344,7 @@ def compare_wrf_era5(wrf, era5_series, era5_lons, era5_lats, var_names, time_sta
     stats = None
     if present and steps:
         pos, w = wrf_point_tables(era5_lons, era5_lats, wrf_lon, wrf_lat)
-        src = hip.WrfSource(era5_series, C, n_lon * n_lat, *_device_tables(pos, w, dev))
+        src = hip.WrfSource(era5_series, C, n_lon * n_lat, *device_tables(pos, w, dev))
         arena = np.stack([fields[k][wi].reshape(-1) for k, _ in present for _, wi, _ in steps]).astype(np.float32)
         jobs, conv = [], []
         for a, (k, v) in enumerate(present):
@@ -630,7 +604,7 @@ class WrfBenchmark:
         fields, wrf_lat, wrf_lon = wrf_fields[0], wrf_fields[1], wrf_fields[2]
         ax_lon, ax_lat, node_of = _regular_axes(lats32, lons32, self.flat_grid)
         pos, w = wrf_point_tables(ax_lon, ax_lat, wrf_lon, wrf_lat, node_of=node_of)
-        self._pos, self._w = _device_tables(pos, w, self.device)
+        self._pos, self._w = device_tables(pos, w, self.device)
         self.Pw = int(pos.shape[0])
         self.grid_vars = [(key, v["era5"], float(v["era5_to_wrf"])) for key, v in VAR_MAP.items()
                           if v["era5"] in self.var_names]

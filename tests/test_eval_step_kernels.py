@@ -13,7 +13,9 @@ import torch
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-SHAPES = [(1, 2, 1), (2, 48, 5), (3, 203, 33), (2, 2051, 19)]  # G below, across and well beyond one 64-row chunk
+# G below, across and well beyond one 64-row chunk; 197: a last chunk of 5 rows, fewer than the 8 row lanes; 32835: 506
+# chunks of 65 rows, more than one pass of the 64-lane combine
+SHAPES = [(1, 2, 1), (2, 48, 5), (3, 203, 33), (2, 2051, 19), (2, 197, 19), (2, 32835, 3)]
 LD = np.longdouble
 
 

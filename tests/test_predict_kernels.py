@@ -119,20 +119,24 @@ def test_sparse_observations_is_what_the_reference_loop_builds(lib_built):
 # ----------------------------------------------------------------------------------------------------------------------
 # gcl_region_interp_scores
 # ----------------------------------------------------------------------------------------------------------------------
-def _region_case(one_node: bool, seed=11):
+def _region_case(one_node: bool, seed=11, wide: bool = False):
     """The 16 x 8 -> 7 x 5 grids of the fixture (descending regional latitudes, regional longitudes past the last global
     one) or a 1-node region; N = 5 with a first sample whose base step would be -1 and an unmatched one in the middle;
-    P = 2; C = 3 of n_feat = 4; channel 1 sits 10^4 standard deviations from 0."""
+    P = 2; C = 3 of n_feat = 4; channel 1 sits 10^4 standard deviations from 0.  wide: C = 19 of n_feat = 20 on 23 x 21
+    regional nodes inside the global axes (the three channels' scalers repeated)."""
     from graphcast_lite_amd.verify import regrid_tables
 
     f = pc.interp_inputs(pc.fixture())
     r_lats, r_lons = (f["r_lats"][2:3], f["r_lons"][6:7]) if one_node else (f["r_lats"], f["r_lons"])
+    if wide:
+        r_lats = np.linspace(f["g_lats"][-2], f["g_lats"][1], 23)
+        r_lons = np.linspace(f["g_lons"][1], f["g_lons"][-2], 21)
     cell, w = regrid_tables(f["g_lats"], f["g_lons"], r_lats, r_lons)
     rng = np.random.default_rng(seed)
-    N, P, C, NF, NT, Gg = 5, 2, 3, 4, 12, f["nlg"] * f["ntg"]
+    N, P, C, NF, NT, Gg = 5, 2, 19 if wide else 3, 20 if wide else 4, 12, f["nlg"] * f["ntg"]
     nr = cell.shape[0]
-    mean, std = np.asarray([280.0, -1e4, 1.5]), np.asarray([11.0, 1.0, 4.0])
-    raw = rng.standard_normal((NT, nr, NF)) * np.asarray([11.0, 1.0, 4.0, 1.0]) + np.asarray([280.0, 0.0, 1.5, 7.0])
+    mean, std = np.resize([280.0, -1e4, 1.5], C), np.resize([11.0, 1.0, 4.0], C)
+    raw = rng.standard_normal((NT, nr, NF)) * np.append(std, 1.0) + np.append(np.resize([280.0, 0.0, 1.5], C), 7.0)
     series = raw.astype(np.float16)
     pred = rng.standard_normal((N, Gg, P * C)).astype(np.float32)
     pred[:, :, 1::C] += np.float32(1e4)
@@ -199,6 +203,34 @@ def test_region_sums_scores_and_fields_match_the_restatement(one_node, lib_built
         direct = float((ta * va).sum() / (np.linalg.norm(ta) * np.linalg.norm(va) + 1e-8))
         assert abs(a.channel(0, 1)["acc"] - direct) <= 1e-10
     # two runs, with and without the stored fields: the same bits
+    again, _, _ = _launch(c, pred3, store=False)
+    assert torch.equal(again, sums)
+
+
+def test_region_sums_with_19_channels_and_a_partial_last_chunk(lib_built):
+    """C = 19: a block is 13 node lanes x 19 channels (9 threads idle) and a chunk 13 x 32 = 416 nodes; 483 nodes leave a
+    last chunk of 67, whose lanes 2 .. 12 hold 5 nodes and lanes 0, 1 hold 6.  Same restatement and same 1e-12 as above:
+    a float64 sum of 3 x 483 terms in any order lies within 1449 x 2^-53 = 1.6e-13 of its sum of absolute values, and
+    the sums about the pivot are no random walks (their mean term is the column mean minus the pivot)."""
+    c = _region_case(False, wide=True)
+    assert (c["C"], c["nr"]) == (19, 483) and c["nr"] % ((256 // 19) * 32) != 0
+    v, t, b = pc.region_fields(c["pred"], c["nlat"], c["cell"], c["w"], c["series"], c["t0"], c["mean"], c["std"], c["P"],
+                               c["C"])
+    want = pc.region_sums(v, t, b, c["t0"], c["NT"])
+    pred3 = torch.from_numpy(c["pred"]).to(DEV)
+    sums, vout, tout = _launch(c, pred3, store=True)
+    got = sums.cpu().numpy()
+    assert np.array_equal(got[..., 3], want[..., 3]) and got[0, 0, 3] == 3 * c["nr"]
+    assert np.array_equal(got[..., 9:], want[..., 9:]), "the pivots are values of the data"
+    err = np.abs(got - want) / np.maximum(np.abs(want), 1e-300)
+    err[want == 0] = np.abs(got[want == 0])
+    print(f"C=19, nr=483: worst relative error of a sum {err.max():.2e} (sum {int(err.argmax()) % 11})")
+    assert err.max() <= 1e-12, (err.max(), got, want)
+    ok = (c["t0"] >= 1) & (c["t0"] + c["P"] <= c["NT"])
+    gv, gt = vout.cpu().numpy(), tout.cpu().numpy()
+    assert np.array_equal(gv[ok].view(np.int32), v[ok].astype(np.float32).view(np.int32))
+    assert np.array_equal(gt[ok].view(np.int32), t[ok].astype(np.float32).view(np.int32))
+    assert (gv[~ok] == SENTINEL).all() and (gt[~ok] == SENTINEL).all(), "skipped samples are left as they are"
     again, _, _ = _launch(c, pred3, store=False)
     assert torch.equal(again, sums)
 

@@ -329,6 +329,27 @@ def test_regrid_blend(hip, f64, mode, B, nt, K):
 
 
 @gpu
+@pytest.mark.parametrize("f64", [False, True])
+def test_regrid_keeps_the_sign_of_zero(hip, f64):
+    """A target whose four corners hold -0.0: the first product starts the sum, so the value is -0.0, as numpy's and
+    scipy's; a sum started from 0.0 would give +0.0 (0.0 + -0.0)."""
+    B, nt, K, i = 2, 53, 5, 7
+    cell, w, src, _, _ = regrid_case(B, nt, K, seed=3)
+    n00 = int(cell[i, 0]) * 6 + int(cell[i, 1])
+    src[:, [n00, n00 + 1, n00 + 6, n00 + 7]] = -0.0
+    src = src if f64 else src.astype(np.float32)
+    g_ref = regrid_ref(src, 6, cell, w, K)
+    assert (g_ref[:, i].view(np.uint32) == 0x80000000).all(), "the restatement itself gives -0.0"
+    S = Rows.of(torch.from_numpy(src), "pad_nan", NAN, dtype=torch.float64 if f64 else torch.float32)
+    Gg = Rows(nt, K, "odd_ld", SENT, "out", B=B)
+    hip.regrid_blend(S.view, 6, i32(cell).view(nt, 2), torch.from_numpy(w).to(DEV), K, g3=Gg.view)
+    torch.cuda.synchronize()
+    assert Gg.untouched(SENT)
+    assert same_bits(Gg.view, torch.from_numpy(g_ref).to(DEV)), "regrid differs from numpy float64 rounded once"
+    assert (Gg.view[:, i].contiguous().cpu().numpy().view(np.uint32) == 0x80000000).all()
+
+
+@gpu
 @pytest.mark.parametrize("B,nt,K", [(1, 53, 19), (2, 300, 5), (3, 0, 4)])
 def test_taper_blend(hip, B, nt, K):
     _, _, _, mask, r = regrid_case(B, nt, K, seed=7)

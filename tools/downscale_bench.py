@@ -140,7 +140,7 @@ def main():
     P = len(r_lats) * len(r_lons)
     gen = torch.Generator(device=dev).manual_seed(0)
     series = torch.randn(T, N_LON, N_LAT, C, generator=gen, device=dev).half()
-    pos, w = D._device_tables(*D.coarse_tables(g_lats, g_lons, r_lats, r_lons, ROI), dev)
+    pos, w = D.device_tables(*D.coarse_tables(g_lats, g_lons, r_lats, r_lons, ROI), dev)
     arch = [torch.empty(T, len(r_lons), len(r_lats), C, dtype=torch.float16, device=dev) for _ in range(2)]
     fine = torch.randn(T, len(r_lons), len(r_lats), C, generator=gen, device=dev).half()
     nt = min(FPL, T)
@@ -149,7 +149,7 @@ def main():
     ppos, pw = D.prediction_tables(lat_g.ravel().astype(np.float32), lon_g.ravel().astype(np.float32), ROI, r_lats, r_lons,
                                    flat_grid=False)
     roi_nodes = len(np.unique(ppos))
-    ppos, pw = D._device_tables(*D._lon_first(ppos, pw, len(r_lats), len(r_lons)), dev)
+    ppos, pw = D.device_tables(*D._lon_first(ppos, pw, len(r_lats), len(r_lons)), dev)
     pred = torch.randn(B_PRED, N_LON * N_LAT, C, generator=gen, device=dev)
     last = torch.randn(B_PRED, N_LON * N_LAT, OBS * C, generator=gen, device=dev)[:, :, C:]
     mean, std = torch.zeros(C, device=dev), torch.ones(C, device=dev)
