@@ -218,7 +218,7 @@ __global__ __launch_bounds__(256, (MI == 1 ? 3 : 2)) void gemm_tile_kernel(
             if (silu) {  // block-uniform
               v *= has_z ? gcl::dsilu_f(zv[r]) : 1.f;
             } else {
-              const bool neg = has_z && (zv[r] <= 0.f);
+              const bool neg = has_z && !(zv[r] > 0.f);
               slope_acc += neg ? (double)(v * zv[r]) : 0.0;
               v = neg ? v * slope : v;
             }
@@ -402,7 +402,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tile_x3_kernel(
             if (silu) {  // block-uniform
               v *= has_z ? gcl::dsilu_f(zv[r]) : 1.f;
             } else {
-              const bool neg = has_z && (zv[r] <= 0.f);
+              const bool neg = has_z && !(zv[r] > 0.f);
               slope_acc += neg ? (double)(v * zv[r]) : 0.0;
               v = neg ? v * slope : v;
             }

@@ -109,10 +109,10 @@ __global__ __launch_bounds__(256) void act_bwd_kernel(const float* __restrict__ 
     if (kind == gcl::kActSilu) {
       g.x *= gcl::dsilu_f(z.x); g.y *= gcl::dsilu_f(z.y); g.z *= gcl::dsilu_f(z.z); g.w *= gcl::dsilu_f(z.w);
     } else {
-      acc += (z.x <= 0.f ? (double)(g.x * z.x) : 0.0) + (z.y <= 0.f ? (double)(g.y * z.y) : 0.0) +
-             (z.z <= 0.f ? (double)(g.z * z.z) : 0.0) + (z.w <= 0.f ? (double)(g.w * z.w) : 0.0);
-      g.x = z.x <= 0.f ? g.x * a : g.x; g.y = z.y <= 0.f ? g.y * a : g.y;
-      g.z = z.z <= 0.f ? g.z * a : g.z; g.w = z.w <= 0.f ? g.w * a : g.w;
+      acc += (!(z.x > 0.f) ? (double)(g.x * z.x) : 0.0) + (!(z.y > 0.f) ? (double)(g.y * z.y) : 0.0) +
+             (!(z.z > 0.f) ? (double)(g.z * z.z) : 0.0) + (!(z.w > 0.f) ? (double)(g.w * z.w) : 0.0);
+      g.x = !(z.x > 0.f) ? g.x * a : g.x; g.y = !(z.y > 0.f) ? g.y * a : g.y;
+      g.z = !(z.z > 0.f) ? g.z * a : g.z; g.w = !(z.w > 0.f) ? g.w * a : g.w;
     }
     st4(dx + 4 * i, g);
   }

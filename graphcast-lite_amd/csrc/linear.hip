@@ -239,7 +239,7 @@ __global__ __launch_bounds__(256, lin_min_waves(NS, KT)) void linear_mfma_kernel
           if (silu) {  // block-uniform
             v *= has_z ? gcl::dsilu_f(zv[r]) : 1.f;
           } else {
-            const bool neg = has_z && (zv[r] <= 0.f);
+            const bool neg = has_z && !(zv[r] > 0.f);
             slope_acc += neg ? (double)(v * zv[r]) : 0.0;
             v = neg ? v * zs : v;
           }
@@ -301,7 +301,7 @@ __global__ __launch_bounds__(256) void linear_valu_kernel(const float* __restric
       const float z = Z[r * ldz + j];
       if (akind == gcl::kActSilu) {
         acc *= gcl::dsilu_f(z);
-      } else if (z <= 0.f) {
+      } else if (!(z > 0.f)) {  // (NaN takes the slope branch, as in the forward and in torch)
         slope_acc += (double)(acc * z);
         acc *= zs;
       }
@@ -632,7 +632,7 @@ __global__ __launch_bounds__(256, 1) void linear_bwd_fused_kernel(
       for (int r = 0; r < 16; ++r) {
         const int rr = wave * 32 + d_row(r, lane);
         float v = acc[s2][r];
-        const bool neg = act && (zv[r] <= 0.f);
+        const bool neg = act && !(zv[r] > 0.f);
         slope_acc += neg ? (double)(v * zv[r]) : 0.0;
         v = neg ? v * slope : v;
         cs[s2] += v;
@@ -833,7 +833,7 @@ __global__ __launch_bounds__(256, 3) void linear_bwd_fused64_kernel(
       for (int r = 0; r < 16; ++r) {
         const int rr = rg * 32 + d_row(r, lane);
         float v = acc[r];
-        const bool neg = act && (zv[r] <= 0.f);
+        const bool neg = act && !(zv[r] > 0.f);
         slope_acc += neg ? (double)(v * zv[r]) : 0.0;
         v = neg ? v * slope : v;
         cs += v;

@@ -649,7 +649,7 @@ __device__ __forceinline__ void linear_x3_bwd_body(
         float4 v = *reinterpret_cast<const float4*>(Stg + row * 64 + csub * 4);
         if (ACT) {
           const float4 z = cur_p[it];
-          const bool nx = act && z.x <= 0.f, ny = act && z.y <= 0.f, nz = act && z.z <= 0.f, nw = act && z.w <= 0.f;
+          const bool nx = act && !(z.x > 0.f), ny = act && !(z.y > 0.f), nz = act && !(z.z > 0.f), nw = act && !(z.w > 0.f);
           // fp64 across float4s: the slope gradient is a long signed sum with heavy cancellation
           slope_acc += (double)(((nx ? v.x * z.x : 0.f) + (ny ? v.y * z.y : 0.f)) + ((nz ? v.z * z.z : 0.f) + (nw ? v.w * z.w : 0.f)));
           v.x = nx ? v.x * slope : v.x; v.y = ny ? v.y * slope : v.y; v.z = nz ? v.z * slope : v.z; v.w = nw ? v.w * slope : v.w;

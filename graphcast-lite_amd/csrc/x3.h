@@ -8,6 +8,22 @@
 // 32 cycles per 32x32x16 block against 8 of 64 cycles with v_mfma_f32_32x32x2_f32 - 0.375x the matrix
 // time - and, unlike the fp32 instruction, the bf16 one leaves the SIMD's issue port free for the
 // wave's own vector instructions while it runs (tools/probes/mfma_valu_probe.hip).
+//
+// THE BAND in which "fp32-equivalent" holds (tests/test_value_contract.py; measured table in DESIGN.md 3.1):
+//   operands: every element v of both operands is 0 or 2^-110 <= |v| < 2^127;
+//   products: for every output, sum_k |a_k| |b_k| < 2^127.
+// Why.  bf16 has fp32's exponent range and a subnormal grid of 2^-133.  hi = bf16(v) rounds everything from
+// 2^128 (1 - 2^-9) on - FLT_MAX included - to inf, after which mid = -inf and lo = NaN: a FINITE v then gives NaN.  The
+// band stops a binade short of that, at 2^127, where the product bound ends as well.  The residues v - hi and v - hi - mid are exact in fp32 (its
+// subnormals are kept), but lo = bf16(v - hi - mid) must hold bit 2^(e - 23) of v = m 2^e: exact iff e - 23 >= -133,
+// i.e. |v| >= 2^-110.  Below, the lost bits are an ABSOLUTE error of at most 2^-134 per element (half the grid):
+// accuracy degrades by a factor 2 per binade (measured: x16 per four), not at once, and nothing becomes non-finite.
+// The matrix pipe keeps subnormal bf16 operands and subnormal fp32 products and sums (measured: no loss down to
+// 2^-110, where lo pieces and piece products are far below 2^-126), so the split alone sets the lower edge.  The
+// product bound keeps the hi x hi partial sums finite: a hi piece exceeds its operand by at most 2^-8 relative, and
+// the sums of one sign run ahead of the result like those of any fp32 GEMM.  Inside the band, scaling an operand by a
+// power of two scales every piece, piece product and partial sum by it: the result follows bit for bit.
+// Inf and NaN operands give non-finite results in the rows / columns that read them (inf becomes NaN: inf - inf).
 #pragma once
 #include "common.h"
 

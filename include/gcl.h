@@ -107,6 +107,20 @@ int gcl_graph_halo_info(const gcl_graph_t* g, int32_t transpose, int32_t T, int3
  * the LDS, or a contraction longer than 128 on rows that are not 16-byte ones) whose contraction length is no multiple
  * of 4 or whose input rows or weight rows are not 16-byte ones; gcl_dense_bwd_dx on that kernel also needs Fin % 4 == 0
  * unless it can transpose W into the workspace first (Fout % 4 == 0 and rows >= 4096).
+ * Values (tests/test_value_contract.py).  A NaN or Inf in one element reaches only the outputs the arithmetic carries it
+ * to (a row of y or dx, a row / column of dW, an element of db); every other output keeps, bit for bit, what it has
+ * without it.  PReLU takes its slope branch for NaN in the forward AND in the backward (x > 0 ? 1 : slope, as torch does),
+ * so a NaN in x reaches the slope gradient.  The kernels are linear in each operand: while nothing leaves fp32's normal
+ * range, scaling an operand (and the additive terms) by 2^k scales the result by exactly 2^k.
+ * The band of the split-operand kernels.  gcl_dense_fwd (Fin <= 64, Fout <= 64 on 16-byte rows; the tile
+ * kernel once it has 1536 tiles), gcl_linear_bwd_all (Fin 33..64), gcl_mlp_fwd_chain and the staged gcl_gcn_layer_fwd run on the bf16 matrix
+ * pipe with every fp32 operand split into three bf16 pieces (csrc/x3.h; GCL_X3=0: the fp32-operand kernels).  Their
+ * result is as close to the exact one as an fp32 GEMM's when
+ *   - every element v of both operands is 0 or 2^-110 <= |v| < 2^127, and
+ *   - for every output the sum of |products| is below 2^127.
+ * Below 2^-110 an element loses the bits under 2^-133 (accuracy halves per binade; nothing becomes non-finite); from
+ * 2^128 (1 - 2^-9) on - the largest finite fp32 included - a FINITE element gives NaN, because its first piece rounds
+ * to inf.  Measured table and derivation: csrc/x3.h, DESIGN.md 3.1.
  * ------------------------------------------------------------------------------------------- */
 int gcl_linear_fwd(const float* x, int64_t ldx, const float* in_slope, const float* W /*[Fout,Fin]*/,
                    const float* bias /*[Fout] or NULL*/, float* y, int64_t ldy, int64_t rows,
