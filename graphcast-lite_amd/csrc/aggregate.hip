@@ -23,6 +23,7 @@
 #include "common.h"
 #include "halo.h"
 #include "mfma_io.h"
+#include "tile_plan.h"
 
 namespace {
 
@@ -586,7 +587,6 @@ struct AggArgs {
   const int32_t *rowptr, *col, *ecol, *heavy;
   const float *w, *ew;
   int ell_width, n_heavy;
-  const gcl_halo* halo;  // [2]: T = 64, T = 32 (T == 0: not built)
   const int32_t* order16 = nullptr;  // processing order of 16-row groups (common.h), or nullptr
   int32_t n_order16 = 0;
   // gcl_aggregate_split: rows >= head of the source come from h2 (h2 == nullptr: one source)
@@ -595,73 +595,38 @@ struct AggArgs {
   int32_t head = 0;
   bool zero_tail = false;  // gcl_aggregate_head: two parts with h2 == nullptr, the kernels then read the zero row
   bool two_part() const { return h2 != nullptr || zero_tail; }
-  // gcl_aggregate_compact: rows with smap[row] >= 0 are stored to yc instead (source-tile kernel only); dry: only say
-  // whether the source-tile kernel would take the call
+  // gcl_aggregate_compact: rows with smap[row] >= 0 are stored to yc instead (source-tile kernel only)
   const int32_t* smap = nullptr;
   float* yc = nullptr;
   int64_t ldc = 0, bsc = 0;
-  bool dry = false;
   bool heavy_inside = false;  // GCL_AGG_HEAVY_INSIDE: heavy rows as the first blocks of agg_kernel's launch
 };
 
-// Source-tile path: returns GCL_OK after launching, or -1 when this call is not eligible (agg_kernel runs instead).
+// Source-tile path of a call that plan_aggregate gave to it (tile_plan.h).
 template <int LPR>
-int launch_agg_halo(const AggArgs& ga, const float* h, int64_t ldh, int64_t bsh, const float* bias, float* y,
-                    int64_t ldy, int64_t bsy, int32_t n, int32_t B, int32_t F, hipStream_t st,
-                    const int32_t* present = nullptr) {
-  const int enabled = gcl::env_int("GCL_AGG_HALO", 1);  // read per call: the parity tests switch it to compare the two kernels
-  static const int force_t = gcl::env_int("GCL_AGG_HALO_T", 0);    // tuning: tile height
-  static const int bpc_env = gcl::env_int("GCL_AGG_HALO_BPC", 0);  // tuning: blocks per CU
+int launch_agg_halo(const AggArgs& ga, const gcl::plan::AggPlan& p, const float* h, int64_t ldh, int64_t bsh,
+                    const float* bias, float* y, int64_t ldy, int64_t bsy, int32_t n, int32_t B, int32_t F, hipStream_t st,
+                    const int32_t* present) {
   static const int nt = gcl::env_int("GCL_AGG_NT", 1);
-  if (!enabled || ga.ell_width != 8) return -1;  // the arithmetic below is that of agg_kernel<.., EW = 8>
-  if ((int64_t)n * ldh * 4 >= (int64_t)1 << 31 || ldh * 4 >= (int64_t)1 << 24 || n >= 1 << 24) return -1;  // 32-bit row offsets
-  constexpr int RPW = 64 / LPR;
-  const gcl_halo* hl = nullptr;
-  for (int t = 0; t < 2; ++t) {
-    const gcl_halo& c = ga.halo[t];
-    if (c.T == 0 || (force_t && c.T != force_t)) continue;
-    const int64_t bytes = (int64_t)(c.smax + 1) * LPR * 16;
-    if (bytes > 80 * 1024 || gcl::cdiv((c.smax - c.T) / RPW, 4) > 32) continue;  // at least two blocks per CU
-    hl = &c;
-    break;
-  }
-  if (!hl) return -1;
-  if (ga.dry) return GCL_OK;
-  const int64_t lds = (int64_t)(hl->smax + 1) * LPR * 16;
+  const gcl_halo* hl = p.hl;
   // (wide rows, F = 128: 66 KB images, two blocks per CU.  Launched back to back at B = 8 the per-edge kernel on the same
   // tile-ordered graph is as fast, 79 vs 82 us - the whole batch sits in the Infinity Cache then; inside the training
   // step it is not, and the staged form wins, 88 vs 102 us per launch, so there is no batch-size switch here.)
-  // persistent blocks, as many per CU as LDS allows; every block walks its share of the (tile, sample) items of its XCD group
-  const int per_cu = (int)std::min<int64_t>(8, gcl::kLdsBytes / lds);
-  const int J = 32 * (bpc_env > 0 ? bpc_env : per_cu);  // blocks per XCD
-  const int mpw = (int)gcl::cdiv((hl->smax - hl->T) / RPW, 4);  // halo pieces per wave of the fullest tile
-  dim3 grid((unsigned)(gcl::kNumXCD * J)), block(256);
-  auto go = [&](auto kern) -> int {
-    GCL_ENSURE_DYN_LDS(kern, (size_t)lds);
-    hipLaunchKernelGGL(kern, grid, block, (size_t)lds, st, hl->list, hl->cnt, reinterpret_cast<const int2*>(hl->rec),
-                       ga.rowptr, hl->opos, ga.w, hl->smax, h, ldh, bsh, bias, y, ldy, bsy, n, B, F, hl->ntiles, nt, present,
-                       ga.smap, ga.yc, ga.ldc, ga.bsc);
-    return GCL_OK;
-  };
-  int rc;
-  if (ga.smap && hl->T == 64)
-    rc = mpw <= 4 ? go(&agg_halo_loop_kernel<LPR, 64, 4, false, true>) : mpw <= 8 ? go(&agg_halo_loop_kernel<LPR, 64, 8, false, true>)
-       : mpw <= 16 ? go(&agg_halo_loop_kernel<LPR, 64, 16, false, true>) : go(&agg_halo_loop_kernel<LPR, 64, 32, false, true>);
-  else if (ga.smap)
-    rc = mpw <= 4 ? go(&agg_halo_loop_kernel<LPR, 32, 4, false, true>) : mpw <= 8 ? go(&agg_halo_loop_kernel<LPR, 32, 8, false, true>)
-       : mpw <= 16 ? go(&agg_halo_loop_kernel<LPR, 32, 16, false, true>) : go(&agg_halo_loop_kernel<LPR, 32, 32, false, true>);
-  else if (present && hl->T == 64)
-    rc = mpw <= 4 ? go(&agg_halo_loop_kernel<LPR, 64, 4, true>) : mpw <= 8 ? go(&agg_halo_loop_kernel<LPR, 64, 8, true>)
-       : mpw <= 16 ? go(&agg_halo_loop_kernel<LPR, 64, 16, true>) : go(&agg_halo_loop_kernel<LPR, 64, 32, true>);
-  else if (present)
-    rc = mpw <= 4 ? go(&agg_halo_loop_kernel<LPR, 32, 4, true>) : mpw <= 8 ? go(&agg_halo_loop_kernel<LPR, 32, 8, true>)
-       : mpw <= 16 ? go(&agg_halo_loop_kernel<LPR, 32, 16, true>) : go(&agg_halo_loop_kernel<LPR, 32, 32, true>);
-  else if (hl->T == 64)
-    rc = mpw <= 4 ? go(&agg_halo_loop_kernel<LPR, 64, 4>) : mpw <= 8 ? go(&agg_halo_loop_kernel<LPR, 64, 8>)
-       : mpw <= 16 ? go(&agg_halo_loop_kernel<LPR, 64, 16>) : go(&agg_halo_loop_kernel<LPR, 64, 32>);
-  else
-    rc = mpw <= 4 ? go(&agg_halo_loop_kernel<LPR, 32, 4>) : mpw <= 8 ? go(&agg_halo_loop_kernel<LPR, 32, 8>)
-       : mpw <= 16 ? go(&agg_halo_loop_kernel<LPR, 32, 16>) : go(&agg_halo_loop_kernel<LPR, 32, 32>);
+  // every persistent block walks its share of the (tile, sample) items of its XCD group
+  const int variant = ga.smap ? 2 : present ? 1 : 0;  // plain / absent source rows / store map
+  const int rc = gcl::plan::pick<0, 1, 2>(variant, [&](auto V) {
+    return gcl::plan::pick<64, 32>(hl->T, [&](auto T) {
+      return gcl::plan::pick<4, 8, 16, 32>(p.geo.bucket(), [&](auto MPW) {
+        constexpr int v = decltype(V)::value;
+        auto kern = &agg_halo_loop_kernel<LPR, decltype(T)::value, decltype(MPW)::value, v == 1, v == 2>;
+        GCL_ENSURE_DYN_LDS(kern, (size_t)p.geo.lds);
+        hipLaunchKernelGGL(kern, dim3(p.geo.grid), dim3(256), (size_t)p.geo.lds, st, hl->list, hl->cnt,
+                           reinterpret_cast<const int2*>(hl->rec), ga.rowptr, hl->opos, ga.w, hl->smax, h, ldh, bsh, bias, y, ldy,
+                           bsy, n, B, F, hl->ntiles, nt, present, ga.smap, ga.yc, ga.ldc, ga.bsc);
+        return (int)GCL_OK;
+      });
+    });
+  });
   if (rc) return rc;
   GCL_CHECK_LAUNCH();
   return GCL_OK;
@@ -681,49 +646,34 @@ int launch_agg_heavy(const AggArgs& ga, const float* h, int64_t ldh, int64_t bsh
     GCL_CHECK_LAUNCH();
     return GCL_OK;
   }
-  if (present) {
-#define GCL_AGGH(VL_, VS_)                                                                                       \
-  hipLaunchKernelGGL((agg_heavy_kernel<LPR, VL_, VS_, true>), hgrid, block, 0, st, ga.heavy, ga.rowptr, ga.col, ga.w, \
-                     h, ldh, bsh, bias, y, ldy, bsy, F, present)
-    if (vl && vs) GCL_AGGH(true, true);
-    else if (vl) GCL_AGGH(true, false);
-    else if (vs) GCL_AGGH(false, true);
-    else GCL_AGGH(false, false);
-#undef GCL_AGGH
-    GCL_CHECK_LAUNCH();
-    return GCL_OK;
-  }
-#define GCL_AGGH(VL_, VS_)                                                                                       \
-  hipLaunchKernelGGL((agg_heavy_kernel<LPR, VL_, VS_>), hgrid, block, 0, st, ga.heavy, ga.rowptr, ga.col, ga.w, h, \
-                     ldh, bsh, bias, y, ldy, bsy, F, (const int32_t*)nullptr)
-  if (vl && vs) GCL_AGGH(true, true);
-  else if (vl) GCL_AGGH(true, false);
-  else if (vs) GCL_AGGH(false, true);
-  else GCL_AGGH(false, false);
-#undef GCL_AGGH
+  using gcl::plan::pick;
+  pick<0, 1>(vl, [&](auto VL) {
+    return pick<0, 1>(vs, [&](auto VS) {
+      return pick<0, 1>(present != nullptr, [&](auto PRES) {
+        hipLaunchKernelGGL((agg_heavy_kernel<LPR, decltype(VL)::value != 0, decltype(VS)::value != 0, decltype(PRES)::value != 0>), hgrid,
+                           block, 0, st, ga.heavy, ga.rowptr, ga.col, ga.w, h, ldh, bsh, bias, y, ldy, bsy, F, present);
+        return (int)GCL_OK;
+      });
+    });
+  });
   GCL_CHECK_LAUNCH();
   return GCL_OK;
 }
 
 template <int LPR>
-int launch_agg(const AggArgs& ga, const float* h, int64_t ldh, int64_t bsh, const float* bias, float* y, int64_t ldy,
-               int64_t bsy, int32_t n, int32_t B, int32_t F, hipStream_t st, const int32_t* present = nullptr) {
+int launch_agg(const AggArgs& ga, const gcl::plan::AggPlan& p, const float* h, int64_t ldh, int64_t bsh, const float* bias,
+               float* y, int64_t ldy, int64_t bsy, int32_t n, int32_t B, int32_t F, hipStream_t st, const int32_t* present) {
   constexpr int RPW = 64 / LPR;
   constexpr int EL = LPR < gcl::kEll ? LPR : gcl::kEll;
-  if ((ga.smap || ga.dry) && ga.n_heavy > 0) return -1;  // (the one-block-per-row kernel has no store map)
-  // vector loads need 16-B aligned rows and a padded tail (ldh >= roundup(F,4))
-  const bool vl = (ldh % 4 == 0) && (bsh % 4 == 0) && gcl::aligned16(h) && ldh >= ((F + 3) / 4) * 4;
-  const bool vs = (ldy % 4 == 0) && (bsy % 4 == 0) && gcl::aligned16(y) && (F % 4 == 0);
+  const bool vl = p.vl && gcl::aligned16(h), vs = p.vs && gcl::aligned16(y);
   if constexpr (LPR >= 16) {
-    if (!ga.two_part() && vl && vs && (!bias || gcl::aligned16(bias))) {  // (the source tiles stage ONE tensor's rows)
-      const int hr = launch_agg_halo<LPR>(ga, h, ldh, bsh, bias, y, ldy, bsy, n, B, F, st, present);
-      if (hr >= 0) {
-        if (hr != GCL_OK || ga.n_heavy == 0 || ga.dry) return hr;
-        return launch_agg_heavy<LPR>(ga, h, ldh, bsh, bias, y, ldy, bsy, B, F, true, true, st, present);
-      }
+    if (p.form == gcl::plan::AggForm::kTile && vl && vs && (!bias || gcl::aligned16(bias))) {
+      const int hr = launch_agg_halo<LPR>(ga, p, h, ldh, bsh, bias, y, ldy, bsy, n, B, F, st, present);
+      if (hr != GCL_OK || ga.n_heavy == 0) return hr;
+      return launch_agg_heavy<LPR>(ga, h, ldh, bsh, bias, y, ldy, bsy, B, F, true, true, st, present);
     }
   }
-  if (ga.smap || ga.dry) return -1;  // the store map lives in the source-tile kernel only: the caller asked first
+  GCL_CHECK_ARG(!ga.smap, "aggregate_compact: the source-tile kernel cannot take this call");
   static const int iter_env = gcl::env_int("GCL_AGG_ITER", 0);  // tuning overrides (0 = per-graph default)
   static const int ew_env = gcl::env_int("GCL_AGG_EW", 0);
   static const int nt = gcl::env_int("GCL_AGG_NT", 1);  // non-temporal output stores (measured: -7..-12 %)
@@ -852,16 +802,22 @@ int launch_agg(const AggArgs& ga, const float* h, int64_t ldh, int64_t bsh, cons
 
 }  // namespace
 
+// The switches of plan_aggregate: GCL_AGG_HALO per call (the parity tests switch it to compare the two kernels).
+static gcl::plan::AggSwitches agg_switches() {
+  static const int force_t = gcl::env_int("GCL_AGG_HALO_T", 0);    // tuning: tile height
+  static const int bpc_env = gcl::env_int("GCL_AGG_HALO_BPC", 0);  // tuning: blocks per CU
+  return {gcl::env_int("GCL_AGG_HALO", 1) != 0, force_t, bpc_env};
+}
+
 static int aggregate_impl(const gcl_graph_t* g, int32_t transpose, const float* h, int64_t ldh, int64_t bsh,
                           const int32_t* present, const float* bias, float* y, int64_t ldy, int64_t bsy, int32_t B,
                           int32_t F, gcl_stream_t stream, const float* h2 = nullptr, int64_t ldh2 = 0, int64_t bsh2 = 0,
                           int32_t head = 0, const AggArgs* compact = nullptr) {
-  const bool dry = compact && compact->dry;
-  GCL_CHECK_ARG(g && (dry || (h && y)), "aggregate: null argument");
+  GCL_CHECK_ARG(g && h && y, "aggregate: null argument");
   GCL_CHECK_ARG(B > 0 && F > 0 && F <= 256, "aggregate: unsupported B=%d F=%d (F must be in 1..256)", B, F);
   GCL_CHECK_ARG(ldh >= F && ldy >= F, "aggregate: leading dimension smaller than F");
   GCL_CHECK_ARG(g->kind != GCL_GRAPH_GAT, "aggregate: GAT graphs carry no edge weights; use gcl_gat_fwd");
-  GCL_CHECK_ARG(dry || h != y, "aggregate: in-place aggregation is not supported");
+  GCL_CHECK_ARG(h != y, "aggregate: in-place aggregation is not supported");
   AggArgs ga;
   if (compact) ga = *compact;
   ga.heavy_inside = (transpose & GCL_AGG_HEAVY_INSIDE) != 0;  // `transpose` carries flags (gcl.h)
@@ -876,19 +832,17 @@ static int aggregate_impl(const gcl_graph_t* g, int32_t transpose, const float* 
   ga.n_order16 = g->n_order16;
   ga.heavy = transpose ? g->theavy : g->heavy;
   ga.n_heavy = transpose ? g->n_theavy : g->n_heavy;
-  ga.halo = g->halo[transpose ? 1 : 0];
   ga.h2 = h2;
   ga.ldh2 = ldh2;
   ga.bsh2 = bsh2;
   ga.head = head;
   GCL_CHECK_ARG(B <= 65535 || ga.n_heavy == 0, "aggregate: batch too large for the heavy-row launch");
   hipStream_t st = (hipStream_t)stream;
-  const int lanes = (F + 3) / 4;
-  if (lanes <= 4) return launch_agg<4>(ga, h, ldh, bsh, bias, y, ldy, bsy, g->n, B, F, st, present);
-  if (lanes <= 8) return launch_agg<8>(ga, h, ldh, bsh, bias, y, ldy, bsy, g->n, B, F, st, present);
-  if (lanes <= 16) return launch_agg<16>(ga, h, ldh, bsh, bias, y, ldy, bsy, g->n, B, F, st, present);
-  if (lanes <= 32) return launch_agg<32>(ga, h, ldh, bsh, bias, y, ldy, bsy, g->n, B, F, st, present);
-  return launch_agg<64>(ga, h, ldh, bsh, bias, y, ldy, bsy, g->n, B, F, st, present);
+  const gcl::plan::AggPlan p =
+      gcl::plan::plan_aggregate(*g, {transpose, ldh, bsh, ldy, bsy, F, ga.two_part(), ga.smap != nullptr}, agg_switches());
+  return gcl::plan::pick<4, 8, 16, 32, 64>(p.lpr, [&](auto L) {
+    return launch_agg<decltype(L)::value>(ga, p, h, ldh, bsh, bias, y, ldy, bsy, g->n, B, F, st, present);
+  });
 }
 
 extern "C" int64_t gcl_aggregate_heavy_launches(void) { return (int64_t)g_heavy_launches.load(std::memory_order_relaxed); }
@@ -938,11 +892,8 @@ extern "C" int gcl_aggregate_head(const gcl_graph_t* g, int32_t transpose, const
 // with source tiles in that direction and no heavy rows, 16-byte rows of more than 32 columns), else 0.
 extern "C" int gcl_aggregate_compact_ok(const gcl_graph_t* g, int32_t transpose, int64_t ldh, int64_t bsh, int64_t ldy,
                                         int64_t bsy, int32_t B, int32_t F) {
-  if (!g || g->kind == GCL_GRAPH_GAT || B <= 0 || F <= 32 || F > 256 || F % 4 != 0 || ldh < F || ldy < F) return 0;
-  AggArgs ca;
-  ca.dry = true;
-  return aggregate_impl(g, transpose, nullptr, ldh, bsh, nullptr, nullptr, nullptr, ldy, bsy, B, F, nullptr, nullptr, 0, 0, 0,
-                        &ca) == GCL_OK ? 1 : 0;
+  if (!g || g->kind == GCL_GRAPH_GAT || B <= 0 || F > 256 || ldh < F || ldy < F) return 0;  // aggregate_impl's argument checks
+  return gcl::plan::plan_aggregate(*g, {transpose, ldh, bsh, ldy, bsy, F, false, true}, agg_switches()).form == gcl::plan::AggForm::kTile;
 }
 
 extern "C" int gcl_aggregate_compact(const gcl_graph_t* g, int32_t transpose, const float* h, int64_t ldh, int64_t bsh,
@@ -958,7 +909,5 @@ extern "C" int gcl_aggregate_compact(const gcl_graph_t* g, int32_t transpose, co
   ca.yc = yc;
   ca.ldc = ldc;
   ca.bsc = bsc;
-  const int rc = aggregate_impl(g, transpose, h, ldh, bsh, nullptr, nullptr, y, ldy, bsy, B, F, stream, nullptr, 0, 0, 0, &ca);
-  GCL_CHECK_ARG(rc != -1, "aggregate_compact: the source-tile kernel cannot take this call");
-  return rc;
+  return aggregate_impl(g, transpose, h, ldh, bsh, nullptr, nullptr, y, ldy, bsy, B, F, stream, nullptr, 0, 0, 0, &ca);
 }

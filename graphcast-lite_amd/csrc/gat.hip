@@ -17,6 +17,7 @@
 
 #include "common.h"
 #include "halo.h"
+#include "tile_plan.h"
 
 namespace {
 
@@ -1189,16 +1190,22 @@ inline int chunk_heads(int H, int h0, int maxc) {
   return hc;
 }
 
+// The template constants of a one-head source-tile kernel: f(lanes per row 16 | 32, MAXPW 4 | 8 | 16, TAB 0 | 1)
+template <class F>
+int tile_kernel_pick(int C, const gcl::plan::TileGeo& geo, const void* tab, F&& f) {
+  using gcl::plan::pick;
+  return pick<16, 32>(C / 4, [&](auto LPR) {
+    return pick<4, 8, 16>(geo.bucket(), [&](auto MPW) { return pick<0, 1>(tab != nullptr, [&](auto TAB) { return f(LPR, MPW, TAB); }); });
+  });
+}
+
 }  // namespace
 
-#define GCL_DISPATCH_LPR(lpr, CALL) \
-  switch (lpr) {                    \
-    case 4: CALL(4); break;         \
-    case 8: CALL(8); break;         \
-    case 16: CALL(16); break;       \
-    case 32: CALL(32); break;       \
-    default: CALL(64); break;       \
-  }
+// f(lanes per row as a template constant: std::integral_constant<int, 4 | 8 | 16 | 32 | 64>)
+template <class F>
+static void for_lpr(int lpr, F&& f) {
+  gcl::plan::pick<4, 8, 16, 32, 64>(lpr, [&](auto L) { return f(L), 0; });
+}
 
 static int gat_fwd_impl(const gcl_graph_t* g, const float* h, int64_t ldh, int64_t bsh, const int32_t* tab,
                         const float* att_src, const float* att_dst, const float* bias, float* a_src, float* a_dst,
@@ -1213,38 +1220,22 @@ static int gat_fwd_impl(const gcl_graph_t* g, const float* h, int64_t ldh, int64
   GCL_CHECK_ARG((ldy % 4) == 0 && (bsy % 4) == 0 && gcl::aligned16(y), "gat_fwd: y must be 16-B aligned with ld %% 4 == 0");
   GCL_CHECK_ARG(g->kind == GCL_GRAPH_GAT, "gat_fwd: graph was not created with GCL_GRAPH_GAT");
   hipStream_t st = (hipStream_t)stream;
-  {
-    // one head on a graph with a tile layout: everything of the layer from one LDS image per tile (gat_halo_fwd_kernel)
-    const int halo_on = gcl::env_int("GCL_GAT_HALO", 1);  // read per call: the parity test compares the two forms
+  // one head on a graph with a tile layout: everything of the layer from one LDS image per tile (gat_halo_fwd_kernel);
+  // GCL_GAT_HALO is read per call: the parity test compares the two forms
+  const gcl::plan::GatPlan p = gcl::plan::plan_gat_fwd(*g, ldh, H, C, gcl::env_int("GCL_GAT_HALO", 1) != 0);
+  if (p.form == gcl::plan::GatForm::kTile && gcl::aligned16(att_src) && gcl::aligned16(att_dst) && (!bias || gcl::aligned16(bias))) {
     const gcl_halo& hl = g->halo[0][0];
-    const int lprh = C / 4;
-    const int64_t ldsb = (int64_t)(hl.smax + 1) * lprh * 16 + (int64_t)(hl.smax + 1 + 64) * 4;
-    if (halo_on && H == 1 && (C == 64 || C == 128) && hl.T == 64 && g->n_heavy == 0 && ldsb <= 80 * 1024 &&
-        (int64_t)g->n * ldh * 4 < ((int64_t)1 << 31) && ldh * 4 < (1 << 24) && g->n < (1 << 24) && gcl::aligned16(att_src) &&
-        gcl::aligned16(att_dst) && (!bias || gcl::aligned16(bias))) {
-      const int rpw = 64 / lprh;
-      const int mpw = (int)gcl::cdiv((hl.smax - 64) / rpw, 4);
-      if (mpw <= 16) {
-        const int per_cu = (int)std::min<int64_t>(8, gcl::kLdsBytes / ldsb);
-        dim3 grid((unsigned)(gcl::kNumXCD * 32 * per_cu));
-        auto go = [&](auto kern) -> int {
-          GCL_ENSURE_DYN_LDS(kern, (size_t)ldsb);
-          hipLaunchKernelGGL(kern, grid, dim3(256), (size_t)ldsb, st, hl.list, hl.cnt, reinterpret_cast<const int2*>(hl.rec),
-                             g->rowptr, hl.opos, hl.smax, h, ldh, bsh, att_src, att_dst, bias, a_src, a_dst, alpha, y, ldy,
-                             bsy, g->n, g->e, B, C, hl.ntiles, tab);
-          return GCL_OK;
-        };
-        int rc2;
-        if (tab) {
-          if (lprh == 16) rc2 = mpw <= 4 ? go(&gat_halo_fwd_kernel<16, 4, true>) : mpw <= 8 ? go(&gat_halo_fwd_kernel<16, 8, true>) : go(&gat_halo_fwd_kernel<16, 16, true>);
-          else rc2 = mpw <= 4 ? go(&gat_halo_fwd_kernel<32, 4, true>) : mpw <= 8 ? go(&gat_halo_fwd_kernel<32, 8, true>) : go(&gat_halo_fwd_kernel<32, 16, true>);
-        } else if (lprh == 16) rc2 = mpw <= 4 ? go(&gat_halo_fwd_kernel<16, 4>) : mpw <= 8 ? go(&gat_halo_fwd_kernel<16, 8>) : go(&gat_halo_fwd_kernel<16, 16>);
-        else rc2 = mpw <= 4 ? go(&gat_halo_fwd_kernel<32, 4>) : mpw <= 8 ? go(&gat_halo_fwd_kernel<32, 8>) : go(&gat_halo_fwd_kernel<32, 16>);
-        if (rc2) return rc2;
-        GCL_CHECK_LAUNCH();
-        return GCL_OK;
-      }
-    }
+    rc = tile_kernel_pick(C, p.geo, tab, [&](auto LPR, auto MPW, auto TAB) {
+      auto kern = &gat_halo_fwd_kernel<decltype(LPR)::value, decltype(MPW)::value, decltype(TAB)::value != 0>;
+      GCL_ENSURE_DYN_LDS(kern, (size_t)p.geo.lds);
+      hipLaunchKernelGGL(kern, dim3(p.geo.grid), dim3(256), (size_t)p.geo.lds, st, hl.list, hl.cnt, reinterpret_cast<const int2*>(hl.rec),
+                         g->rowptr, hl.opos, hl.smax, h, ldh, bsh, att_src, att_dst, bias, a_src, a_dst, alpha, y, ldy, bsy, g->n,
+                         g->e, B, C, hl.ntiles, tab);
+      return (int)GCL_OK;
+    });
+    if (rc) return rc;
+    GCL_CHECK_LAUNCH();
+    return GCL_OK;
   }
   if (tab) {
     gcl::set_error("gat_fwd_tab: this graph / shape has no source-tile form (H=%d C=%d)", H, C);
@@ -1258,21 +1249,19 @@ static int gat_fwd_impl(const gcl_graph_t* g, const float* h, int64_t ldh, int64
     const int64_t rows = (int64_t)B * g->n;
     int64_t nbs = gcl::cdiv(rows, rpb);
     if (nbs > 4096) nbs = 4096;
-#define CALL(L)                                                                                                     \
-  hipLaunchKernelGGL((gat_scores_kernel<L>), dim3((unsigned)nbs), dim3(256), 0, st, hh, ldh, bsh, att_src + h0 * C, \
-                     att_dst + h0 * C, a_src, a_dst, g->n, B, hc, C, padded_width(C), H, h0)
-    GCL_DISPATCH_LPR(lpr, CALL)
-#undef CALL
+    for_lpr(lpr, [&](auto L) {
+      hipLaunchKernelGGL((gat_scores_kernel<decltype(L)::value>), dim3((unsigned)nbs), dim3(256), 0, st, hh, ldh, bsh, att_src + h0 * C,
+                         att_dst + h0 * C, a_src, a_dst, g->n, B, hc, C, padded_width(C), H, h0);
+    });
     GCL_CHECK_LAUNCH();
     const int32_t nRB = (int32_t)gcl::cdiv(g->n, rpb);
     const int xcd_map = B >= 8 ? 1 : 0;
     const int64_t nb = xcd_map ? (int64_t)8 * gcl::cdiv(B, 8) * nRB : (int64_t)B * nRB;
-#define CALL(L)                                                                                                       \
-  hipLaunchKernelGGL((gat_fwd_kernel<L>), dim3((unsigned)nb), dim3(256), 0, st, g->rowptr, g->col, g->ecol, hh, ldh,  \
-                     bsh, a_src, a_dst, h0 == 0 ? bias : nullptr, alpha, y, ldy, bsy, g->n, g->e, B, hc, C,           \
-                     padded_width(C), nRB, xcd_map, H, h0, H, h0 > 0 ? 1 : 0)
-    GCL_DISPATCH_LPR(lpr, CALL)
-#undef CALL
+    for_lpr(lpr, [&](auto L) {
+      hipLaunchKernelGGL((gat_fwd_kernel<decltype(L)::value>), dim3((unsigned)nb), dim3(256), 0, st, g->rowptr, g->col, g->ecol, hh, ldh,
+                         bsh, a_src, a_dst, h0 == 0 ? bias : nullptr, alpha, y, ldy, bsy, g->n, g->e, B, hc, C,
+                         padded_width(C), nRB, xcd_map, H, h0, H, h0 > 0 ? 1 : 0);
+    });
     GCL_CHECK_LAUNCH();
     h0 += hc;
   }
@@ -1298,20 +1287,11 @@ extern "C" int gcl_gat_fwd_tab(const gcl_graph_t* g, const float* h, int64_t ldh
 }
 
 extern "C" int gcl_gat_tab_ok(const gcl_graph_t* g, int64_t ldh, int32_t H, int32_t C) {
-  if (!g || g->kind != GCL_GRAPH_GAT || H != 1 || !(C == 64 || C == 128) || g->n_heavy || g->n_theavy) return 0;
-  if (!gcl::env_int("GCL_GAT_HALO", 1)) return 0;
-  const gcl_halo& hf = g->halo[0][0];
-  const gcl_halo& ht = g->halo[1][0];
-  if (hf.T != 64 || ht.T != 64) return 0;
-  const int lprh = C / 4, rpw = 64 / lprh;
-  const int64_t ldsf = (int64_t)(hf.smax + 1) * lprh * 16 + (int64_t)(hf.smax + 1 + 64) * 4;
-  const int64_t ldsd = (int64_t)(hf.smax + 1) * lprh * 16 + (int64_t)(64 + 128 + 8) * 4;
-  const int64_t ldss = (int64_t)(ht.smax + 1) * lprh * 16;
-  const int mpd = (int)gcl::cdiv((hf.smax - 64) / rpw, 4), mps = (int)gcl::cdiv((ht.smax - 64) / rpw, 4);
-  return ldsf <= 80 * 1024 && ldsd <= 80 * 1024 && ldss <= 80 * 1024 && hf.smax - 64 <= 128 && mpd <= 16 && mps <= 16 &&
-                 ldh * 4 < (1 << 24) && g->n < (1 << 24)
-             ? 1
-             : 0;
+  // both launchers' plans say source-tile, for the contiguous dy [B, n, C] of hip.gat_bwd (and their checks of ldh pass)
+  if (!g || ldh < (int64_t)H * C || ldh % 4 != 0) return 0;
+  const bool on = gcl::env_int("GCL_GAT_HALO", 1) != 0;
+  return gcl::plan::plan_gat_fwd(*g, ldh, H, C, on).form == gcl::plan::GatForm::kTile &&
+         gcl::plan::plan_gat_bwd(*g, ldh, C, (int64_t)g->n * C, H, C, on).form == gcl::plan::GatForm::kTile;
 }
 
 extern "C" size_t gcl_gat_bwd_ws_bytes(int64_t e_prime, int32_t n, int32_t B, int32_t H, int32_t C) {
@@ -1352,54 +1332,34 @@ static int gat_bwd_impl(const gcl_graph_t* g, const float* dy, int64_t lddy, int
   bool halo_done = false;
   int halo_parts = 0;  // partial records of the attention-vector gradients written by the staged dst-side kernel
   int halo_bparts = 0;  // partial records of d_bias (column sums of dy) written by the staged src-side kernel
-  {
-    // one head on a graph with tile layouts in both directions: both edge passes from LDS images (gat_halo_bwd_*_kernel)
-    const int halo_on = gcl::env_int("GCL_GAT_HALO", 1);
+  // one head on a graph with tile layouts in both directions: both edge passes from LDS images (gat_halo_bwd_*_kernel)
+  const gcl::plan::GatPlan p = gcl::plan::plan_gat_bwd(*g, ldh, lddy, bsdy, H, C, gcl::env_int("GCL_GAT_HALO", 1) != 0);
+  if (p.form == gcl::plan::GatForm::kTile && gcl::aligned16(dy) && gcl::aligned16(att_src) && gcl::aligned16(att_dst)) {
     const gcl_halo& hf = g->halo[0][0];
     const gcl_halo& ht = g->halo[1][0];
-    const int lprh = C / 4;
-    const int64_t ldsd = (int64_t)(hf.smax + 1) * lprh * 16 + (int64_t)(64 + 128 + 8) * 4;  // image + a_s of up to 64 + 128 staged rows
-    const int64_t ldss = (int64_t)(ht.smax + 1) * lprh * 16;
-    if (halo_on && H == 1 && (C == 64 || C == 128) && hf.T == 64 && ht.T == 64 && g->n_heavy == 0 &&
-        g->n_theavy == 0 && hf.smax - 64 <= 128 && ldsd <= 80 * 1024 && ldss <= 80 * 1024 && vdy &&
-        (int64_t)g->n * ldh * 4 < ((int64_t)1 << 31) && ldh * 4 < (1 << 24) && (int64_t)g->n * lddy * 4 < ((int64_t)1 << 31) &&
-        lddy * 4 < (1 << 24) && g->n < (1 << 24) && gcl::aligned16(att_src) && gcl::aligned16(att_dst)) {
-      const int rpw = 64 / lprh;
-      const int mpd = (int)gcl::cdiv((hf.smax - 64) / rpw, 4), mps = (int)gcl::cdiv((ht.smax - 64) / rpw, 4);
-      if (mpd <= 16 && mps <= 16) {
-        auto god = [&](auto kern) -> int {
-          GCL_ENSURE_DYN_LDS(kern, (size_t)ldsd);
-          const int per_cu = (int)std::min<int64_t>(8, gcl::kLdsBytes / ldsd);
-          hipLaunchKernelGGL(kern, dim3((unsigned)(gcl::kNumXCD * 32 * per_cu)), dim3(256), (size_t)ldsd, st, hf.list, hf.cnt,
-                             reinterpret_cast<const int2*>(hf.rec), g->rowptr, hf.opos, hf.smax, dy, lddy, bsdy, h, ldh, bsh,
-                             a_src, a_dst, alpha, de, dad, part, g->n, g->e, B, C, hf.ntiles, tab);
-          halo_parts = (int)(gcl::kNumXCD * 32 * per_cu);
-          return GCL_OK;
-        };
-        auto gos = [&](auto kern) -> int {
-          GCL_ENSURE_DYN_LDS(kern, (size_t)ldss);
-          const int per_cu = (int)std::min<int64_t>(8, gcl::kLdsBytes / ldss);
-          hipLaunchKernelGGL(kern, dim3((unsigned)(gcl::kNumXCD * 32 * per_cu)), dim3(256), (size_t)ldss, st, ht.list, ht.cnt,
-                             reinterpret_cast<const int2*>(ht.rec), g->trowptr, ht.opos, g->tslot, ht.smax, dy, lddy, bsdy, alpha,
-                             de, dad, att_src, att_dst, das, dh, lddh, bsdh, d_bias ? cs_ws : nullptr, g->n, g->e, B, C, ht.ntiles);
-          halo_bparts = d_bias ? (int)(gcl::kNumXCD * 32 * per_cu) : 0;
-          return GCL_OK;
-        };
-        int rc2;
-        if (tab) {
-          if (lprh == 16) rc2 = mpd <= 4 ? god(&gat_halo_bwd_dst_kernel<16, 4, true>) : mpd <= 8 ? god(&gat_halo_bwd_dst_kernel<16, 8, true>) : god(&gat_halo_bwd_dst_kernel<16, 16, true>);
-          else rc2 = mpd <= 4 ? god(&gat_halo_bwd_dst_kernel<32, 4, true>) : mpd <= 8 ? god(&gat_halo_bwd_dst_kernel<32, 8, true>) : god(&gat_halo_bwd_dst_kernel<32, 16, true>);
-        } else if (lprh == 16) rc2 = mpd <= 4 ? god(&gat_halo_bwd_dst_kernel<16, 4>) : mpd <= 8 ? god(&gat_halo_bwd_dst_kernel<16, 8>) : god(&gat_halo_bwd_dst_kernel<16, 16>);
-        else rc2 = mpd <= 4 ? god(&gat_halo_bwd_dst_kernel<32, 4>) : mpd <= 8 ? god(&gat_halo_bwd_dst_kernel<32, 8>) : god(&gat_halo_bwd_dst_kernel<32, 16>);
-        if (rc2) return rc2;
-        GCL_CHECK_LAUNCH();
-        if (lprh == 16) rc2 = mps <= 4 ? gos(&gat_halo_bwd_src_kernel<16, 4>) : mps <= 8 ? gos(&gat_halo_bwd_src_kernel<16, 8>) : gos(&gat_halo_bwd_src_kernel<16, 16>);
-        else rc2 = mps <= 4 ? gos(&gat_halo_bwd_src_kernel<32, 4>) : mps <= 8 ? gos(&gat_halo_bwd_src_kernel<32, 8>) : gos(&gat_halo_bwd_src_kernel<32, 16>);
-        if (rc2) return rc2;
-        GCL_CHECK_LAUNCH();
-        halo_done = true;
-      }
-    }
+    rc = tile_kernel_pick(C, p.geo, tab, [&](auto LPR, auto MPW, auto TAB) {
+      auto kern = &gat_halo_bwd_dst_kernel<decltype(LPR)::value, decltype(MPW)::value, decltype(TAB)::value != 0>;
+      GCL_ENSURE_DYN_LDS(kern, (size_t)p.geo.lds);
+      hipLaunchKernelGGL(kern, dim3(p.geo.grid), dim3(256), (size_t)p.geo.lds, st, hf.list, hf.cnt, reinterpret_cast<const int2*>(hf.rec),
+                         g->rowptr, hf.opos, hf.smax, dy, lddy, bsdy, h, ldh, bsh, a_src, a_dst, alpha, de, dad, part, g->n, g->e, B,
+                         C, hf.ntiles, tab);
+      return (int)GCL_OK;
+    });
+    if (rc) return rc;
+    GCL_CHECK_LAUNCH();
+    rc = tile_kernel_pick(C, p.geo_src, nullptr, [&](auto LPR, auto MPW, auto) {
+      auto kern = &gat_halo_bwd_src_kernel<decltype(LPR)::value, decltype(MPW)::value>;
+      GCL_ENSURE_DYN_LDS(kern, (size_t)p.geo_src.lds);
+      hipLaunchKernelGGL(kern, dim3(p.geo_src.grid), dim3(256), (size_t)p.geo_src.lds, st, ht.list, ht.cnt,
+                         reinterpret_cast<const int2*>(ht.rec), g->trowptr, ht.opos, g->tslot, ht.smax, dy, lddy, bsdy, alpha, de, dad,
+                         att_src, att_dst, das, dh, lddh, bsdh, d_bias ? cs_ws : nullptr, g->n, g->e, B, C, ht.ntiles);
+      return (int)GCL_OK;
+    });
+    if (rc) return rc;
+    GCL_CHECK_LAUNCH();
+    halo_done = true;
+    halo_parts = (int)p.geo.grid;  // one record per block
+    halo_bparts = d_bias ? (int)p.geo_src.grid : 0;
   }
   if (tab && !halo_done) {
     gcl::set_error("gat_bwd_tab: this graph / shape has no source-tile form (H=%d C=%d)", H, C);
@@ -1413,20 +1373,18 @@ static int gat_bwd_impl(const gcl_graph_t* g, const float* dy, int64_t lddy, int
     const unsigned nb = (unsigned)(xcd_map ? (int64_t)8 * gcl::cdiv(B, 8) * nRB : (int64_t)B * nRB);
     const float* hh = h + (int64_t)h0 * C;
     if (!halo_done) {
-#define CALL(L)                                                                                                    \
-  hipLaunchKernelGGL((gat_bwd_dst_kernel<L>), dim3(nb), dim3(256), 0, st, g->rowptr, g->col, g->ecol, dy, lddy,     \
-                     bsdy, hh, ldh, bsh, a_src, a_dst, alpha, de, dad, g->n, g->e, B, hc, C, padded_width(C), nRB,  \
-                     xcd_map, H, h0, H)
-      GCL_DISPATCH_LPR(lpr, CALL)
-#undef CALL
+      for_lpr(lpr, [&](auto L) {
+        hipLaunchKernelGGL((gat_bwd_dst_kernel<decltype(L)::value>), dim3(nb), dim3(256), 0, st, g->rowptr, g->col, g->ecol, dy, lddy,
+                           bsdy, hh, ldh, bsh, a_src, a_dst, alpha, de, dad, g->n, g->e, B, hc, C, padded_width(C), nRB,
+                           xcd_map, H, h0, H);
+      });
       GCL_CHECK_LAUNCH();
-#define CALL(L)                                                                                                       \
-  hipLaunchKernelGGL((gat_bwd_src_kernel<L>), dim3(nb), dim3(256), 0, st, g->trowptr, g->tcol, g->tslot, g->tecol,    \
-                     g->teslot, dy, lddy, bsdy, alpha, de, dad, att_src + h0 * C, att_dst + h0 * C, das,              \
-                     dh + (int64_t)h0 * C, lddh, bsdh, g->n, g->e, B, hc, C, padded_width(C), nRB, vdy, xcd_map, H,   \
-                     h0, H)
-      GCL_DISPATCH_LPR(lpr, CALL)
-#undef CALL
+      for_lpr(lpr, [&](auto L) {
+        hipLaunchKernelGGL((gat_bwd_src_kernel<decltype(L)::value>), dim3(nb), dim3(256), 0, st, g->trowptr, g->tcol, g->tslot, g->tecol,
+                           g->teslot, dy, lddy, bsdy, alpha, de, dad, att_src + h0 * C, att_dst + h0 * C, das,
+                           dh + (int64_t)h0 * C, lddh, bsdh, g->n, g->e, B, hc, C, padded_width(C), nRB, vdy, xcd_map, H,
+                           h0, H);
+      });
       GCL_CHECK_LAUNCH();
     }
     int64_t nbd = gcl::cdiv(rows, rpb);
@@ -1434,11 +1392,10 @@ static int gat_bwd_impl(const gcl_graph_t* g, const float* dy, int64_t lddy, int
     if (halo_done) {
       nbd = halo_parts;  // the staged dst-side kernel already left one record per block (H = 1: [2][C])
     } else {
-#define CALL(L)                                                                                                    \
-  hipLaunchKernelGGL((gat_datt_kernel<L>), dim3((unsigned)nbd), dim3(256), 0, st, hh, ldh, bsh, das, dad, part, g->n, \
-                     B, hc, C, padded_width(C), H, h0)
-      GCL_DISPATCH_LPR(lpr, CALL)
-#undef CALL
+      for_lpr(lpr, [&](auto L) {
+        hipLaunchKernelGGL((gat_datt_kernel<decltype(L)::value>), dim3((unsigned)nbd), dim3(256), 0, st, hh, ldh, bsh, das, dad, part, g->n,
+                           B, hc, C, padded_width(C), H, h0);
+      });
       GCL_CHECK_LAUNCH();
     }
     const int HC = hc * C;

@@ -25,6 +25,7 @@
 #include "common.h"
 #include "halo.h"
 #include "mfma_io.h"
+#include "tile_plan.h"
 #include "x3.h"
 
 namespace {
@@ -964,77 +965,43 @@ extern "C" int gcl_debug_read_stamps(unsigned long long* host_out, int count) {
 }
 #endif
 
-// Source-tile form of the layer (gcn_halo_fwd_kernel): graphs with a tile layout (mesh rows in tile order), 64-wide rows,
-// split-operand dense part.  Returns GCL_OK with *launched = false when the shape / graph is outside its range.
-// tab != nullptr: the input rows are read through the row table (see the kernel), x_rows = rows of X as one flat list.
-static int halo_layer_launch(const gcl_graph_t* g, const float* x, int64_t ldx, int64_t bsx, const int32_t* tab,
-                             int64_t x_rows, int32_t act, const float* slope, const float* W, const float* bias, float* y,
-                             int64_t ldy, int64_t bsy, int32_t B, int32_t Fin, int32_t Fout, int32_t Fout_store,
-                             int32_t rows_out, hipStream_t st, bool* launched, const int32_t* present = nullptr,
-                             bool dry_run = false) {  // dry_run: only tell whether this form would take the layer
-  *launched = false;
-  const int32_t n = g->n;
-  const int halo_on = gcl::env_int("GCL_GCN_HALO", 1);  // read per call: the parity test compares the two kernels
-  const int x3_on = gcl::env_int("GCL_X3", 1) && gcl::env_int("GCL_X3_GCN", 1);  // per call, as in gcl_gcn_layer_fwd_tab_ok
-  const gcl_halo& hl = g->halo[0][0];
-  const int hp4 = hl.T == 64 ? (int)gcl::cdiv((hl.smax - 64) / 4, 4) : 99;
-  const int KPh = Fin + 2;
-  const size_t ldsh = (size_t)2 * (32 * KPh > 2048 ? 32 * KPh : 2048) * 4 + (size_t)(hl.smax + 1) * 256 + (present ? 512 : 0);
-  // 32-bit byte offsets: inside one sample without a table, inside the whole of X with one
-  const bool offs_ok = tab ? (x_rows * ldx * 4 < ((int64_t)1 << 32) && (int64_t)B * bsx * 4 < ((int64_t)1 << 32) && x_rows < (1 << 24))
-                           : ((int64_t)n * ldx * 4 < ((int64_t)1 << 31));
-  // only where the gather is the bulk of the layer (>= 6 edges per row: the mesh graph has 7.4): on the decoder graph
-  // of the 512x256 configs (3.3 edges per row) the per-edge kernel's twelve wave-independent pipelines run 1.6x faster
-  // heavy rows (> kHeavy in-edges) have no records in the tile layout (build_halo_host): never this kernel
-  if (!(halo_on && x3_on && g->kind == GCL_GRAPH_GCN && g->n_heavy == 0 && hl.T == 64 && hp4 <= 8 && Fin % 16 == 0 && Fin > 32 && rows_out == n &&
-        g->e >= 6 * (int64_t)n && ldsh <= 80 * 1024 && offs_ok && n < (1 << 24) && ldx * 4 < (1 << 24) &&
-        (int64_t)n * ldy * 4 < ((int64_t)1 << 31)))
-    return GCL_OK;
-  if (tab && hp4 > 4) return GCL_OK;  // the table variant exists for the interleaved-issue form only
-  if (present && (tab || hp4 > 4 || !gcl::env_int("GCL_GCN_HALO_FORM", 1))) return GCL_OK;  // so does the row predicate
-  if (dry_run) {
-    *launched = true;
-    return GCL_OK;
-  }
+using gcl::plan::GcnForm;
+
+// The switches of plan_gcn_layer (tile_plan.h), read per call: the parity tests compare the kernels and the forms.
+static gcl::plan::GcnSwitches gcn_switches() {
   static const int bpc_env = gcl::env_int("GCL_GCN_HALO_BPC", 0);
-  const int per_cu = (int)(gcl::kLdsBytes / ldsh);
-  const int Jx = 32 * (bpc_env > 0 ? bpc_env : per_cu);
-  dim3 grid((unsigned)(gcl::kNumXCD * Jx));
-  auto go = [&](auto kern) -> int {
-    GCL_ENSURE_DYN_LDS(kern, ldsh);
-    hipLaunchKernelGGL(kern, grid, dim3(256), ldsh, st, hl.list, hl.cnt, reinterpret_cast<const int2*>(hl.rec), g->rowptr,
-                       hl.opos, g->w, hl.smax, x, ldx, bsx, slope, W, bias, y, ldy, bsy, n, B, Fin, Fout, Fout_store,
-                       hl.ntiles, tab, present);
-    return GCL_OK;
-  };
-  int rc;
-  // hp4 <= 4 (the icosphere meshes: <= 64 halo rows per tile): non-temporal stores straight from the accumulator and
-  // the next item's DMA pieces issued between the k-steps of the dense part (in the step 111.5 -> 102.6 us per mesh
+  return {gcl::env_int("GCL_GCN_HALO", 1) != 0, gcl::env_int("GCL_X3", 1) && gcl::env_int("GCL_X3_GCN", 1),
+          gcl::env_int("GCL_GCN_HALO_FORM", 1) != 0, bpc_env};
+}
+
+// Source-tile forms of the layer (gcn_halo_fwd_kernel): graphs with a tile layout (mesh rows in tile order), 64-wide rows,
+// split-operand dense part.  p: a plan with is_tile(p.form).  tab != nullptr (kTileTab): the input rows are read through
+// the row table (see the kernel); present != nullptr (kTilePred): the output-row predicate.
+static int launch_gcn_tile(const gcl_graph_t* g, const gcl::plan::GcnPlan& p, const float* x, int64_t ldx, int64_t bsx,
+                           const int32_t* tab, int32_t act, const float* slope, const float* W, const float* bias, float* y,
+                           int64_t ldy, int64_t bsy, int32_t B, int32_t Fin, int32_t Fout, int32_t Fout_store, hipStream_t st,
+                           const int32_t* present) {
+  static_assert(GCL_ACT_NONE == gcl::kActNone && GCL_ACT_PRELU == gcl::kActPrelu && GCL_ACT_SILU == gcl::kActSilu, "act codes");
+  const gcl_halo& hl = g->halo[0][0];
+  // kTileInterleaved (the icosphere meshes: <= 64 halo rows per tile): non-temporal stores straight from the accumulator
+  // and the next item's DMA pieces issued between the k-steps of the dense part (in the step 111.5 -> 102.6 us per mesh
   // layer; GCL_GCN_HALO_FORM=0 selects the first form - DMA issue up front, staged 16-byte stores - for comparison)
-  const int form_env = gcl::env_int("GCL_GCN_HALO_FORM", 1);
-  if (present)
-    rc = act == GCL_ACT_PRELU  ? go(&gcn_halo_fwd_kernel<gcl::kActPrelu, 4, 2, true, true, false, true>)
-         : act == GCL_ACT_SILU ? go(&gcn_halo_fwd_kernel<gcl::kActSilu, 4, 2, true, true, false, true>)
-                               : go(&gcn_halo_fwd_kernel<gcl::kActNone, 4, 2, true, true, false, true>);
-  else if (tab)
-    rc = act == GCL_ACT_PRELU  ? go(&gcn_halo_fwd_kernel<gcl::kActPrelu, 4, 2, true, true, true>)
-         : act == GCL_ACT_SILU ? go(&gcn_halo_fwd_kernel<gcl::kActSilu, 4, 2, true, true, true>)
-                               : go(&gcn_halo_fwd_kernel<gcl::kActNone, 4, 2, true, true, true>);
-  else if (hp4 <= 4 && form_env)
-    rc = act == GCL_ACT_PRELU  ? go(&gcn_halo_fwd_kernel<gcl::kActPrelu, 4, 2, true, true>)
-         : act == GCL_ACT_SILU ? go(&gcn_halo_fwd_kernel<gcl::kActSilu, 4, 2, true, true>)
-                               : go(&gcn_halo_fwd_kernel<gcl::kActNone, 4, 2, true, true>);
-  else if (hp4 <= 4)
-    rc = act == GCL_ACT_PRELU  ? go(&gcn_halo_fwd_kernel<gcl::kActPrelu, 4>)
-         : act == GCL_ACT_SILU ? go(&gcn_halo_fwd_kernel<gcl::kActSilu, 4>)
-                               : go(&gcn_halo_fwd_kernel<gcl::kActNone, 4>);
-  else
-    rc = act == GCL_ACT_PRELU  ? go(&gcn_halo_fwd_kernel<gcl::kActPrelu, 8, 2, true>)
-         : act == GCL_ACT_SILU ? go(&gcn_halo_fwd_kernel<gcl::kActSilu, 8, 2, true>)
-                               : go(&gcn_halo_fwd_kernel<gcl::kActNone, 8, 2, true>);
+  const int rc = gcl::plan::pick<(int)GcnForm::kTileFirst, (int)GcnForm::kTileInterleaved, (int)GcnForm::kTileTab,
+                                 (int)GcnForm::kTilePred, (int)GcnForm::kTileEight>((int)p.form, [&](auto FORM) {
+    return gcl::plan::pick<gcl::kActNone, gcl::kActPrelu, gcl::kActSilu>(act, [&](auto ACT) {
+      constexpr GcnForm f = (GcnForm) decltype(FORM)::value;
+      constexpr bool first = f == GcnForm::kTileFirst, eight = f == GcnForm::kTileEight;
+      auto kern = &gcn_halo_fwd_kernel<decltype(ACT)::value, eight ? 8 : 4, first ? 0 : 2, !first, !first && !eight,
+                                       f == GcnForm::kTileTab, f == GcnForm::kTilePred>;
+      GCL_ENSURE_DYN_LDS(kern, (size_t)p.geo.lds);
+      hipLaunchKernelGGL(kern, dim3(p.geo.grid), dim3(256), (size_t)p.geo.lds, st, hl.list, hl.cnt,
+                         reinterpret_cast<const int2*>(hl.rec), g->rowptr, hl.opos, g->w, hl.smax, x, ldx, bsx, slope, W, bias, y,
+                         ldy, bsy, g->n, B, Fin, Fout, Fout_store, hl.ntiles, tab, present);
+      return (int)GCL_OK;
+    });
+  });
   if (rc) return rc;
   GCL_CHECK_LAUNCH();
-  *launched = true;
   return GCL_OK;
 }
 
@@ -1053,111 +1020,83 @@ struct SplitDst {
   int32_t head;
 };
 
+// The scalar part of the argument checks (all that the `_ok` queries see): shapes, whole 16-byte rows of x and y.
+static bool layer_shapes_ok(int32_t B, int32_t Fin, int32_t Fout, int32_t Fout_store, int64_t ldx, int64_t bsx, int64_t ldy, int64_t bsy) {
+  return B > 0 && Fin >= 4 && Fin <= 64 && Fin % 4 == 0 && Fout >= 1 && Fout <= 64 && Fout_store >= Fout && Fout_store % 4 == 0 &&
+         Fout_store <= 64 && ldx >= Fin && ldx % 4 == 0 && bsx % 4 == 0 && ldy >= Fout_store && ldy % 4 == 0 && bsy % 4 == 0;
+}
+
+// The argument checks of every entry of the layer (fn: the entry's name).  tab: gcl_gcn_layer_fwd_tab - GCN graphs only,
+// whose heavy rows are the plan's refusal, and x is never y's [B, n, ..] tensor.
+static int check_layer_args(const char* fn, bool tab, const gcl_graph_t* g, const float* x, int64_t ldx, int64_t bsx, int32_t act,
+                            const float* slope, const float* W, const float* y, int64_t ldy, int64_t bsy, int32_t B, int32_t Fin,
+                            int32_t Fout, int32_t Fout_store) {
+  GCL_CHECK_ARG(g && x && W && y, "%s: null argument", fn);
+  GCL_CHECK_ARG(g->kind == GCL_GRAPH_GCN || (!tab && g->kind == GCL_GRAPH_MEAN), "%s: graph carries no edge weights", fn);
+  GCL_CHECK_ARG(layer_shapes_ok(B, Fin, Fout, Fout_store, ldx, bsx, ldy, bsy) && gcl::aligned16(x) && gcl::aligned16(y),
+                "%s: unsupported B=%d Fin=%d Fout=%d Fout_store=%d (Fin %% 4 == 0, Fout_store a multiple of 4 in [Fout, ldy], all <= 64) "
+                "or rows of x / y that are not whole 16-B aligned units", fn, B, Fin, Fout, Fout_store);
+  GCL_CHECK_ARG(tab || g->n_heavy == 0, "%s: the graph has rows with more than %d in-edges", fn, gcl::kHeavy);
+  GCL_CHECK_ARG(act == GCL_ACT_NONE || act == GCL_ACT_SILU || (act == GCL_ACT_PRELU && slope), "%s: bad activation %d", fn, act);
+  GCL_CHECK_ARG(act == GCL_ACT_NONE || g->kind != GCL_GRAPH_MEAN, "%s: mean-aggregation graphs take no activation", fn);
+  GCL_CHECK_ARG(tab || x != y, "%s: in-place is not supported", fn);
+  return GCL_OK;
+}
+
 static int layer_fwd_impl(const gcl_graph_t* g, const float* x, int64_t ldx, int64_t bsx, int32_t act,
                           const float* slope, const float* W, const float* bias, float* y, int64_t ldy, int64_t bsy,
                           int32_t B, int32_t Fin, int32_t Fout, int32_t Fout_store, int32_t rows_out,
                           const int32_t* present, gcl_stream_t stream, const SplitDst* sp = nullptr) {
-  GCL_CHECK_ARG(g && x && W && y, "gcn_layer_fwd: null argument");
-  GCL_CHECK_ARG(g->kind == GCL_GRAPH_GCN || g->kind == GCL_GRAPH_MEAN, "gcn_layer_fwd: graph carries no edge weights");
-  GCL_CHECK_ARG(B > 0 && Fin >= 4 && Fin <= 64 && Fin % 4 == 0 && Fout >= 1 && Fout <= 64,
-                "gcn_layer_fwd: unsupported Fin=%d Fout=%d (Fin %% 4 == 0, both <= 64)", Fin, Fout);
-  GCL_CHECK_ARG(Fout_store >= Fout && Fout_store % 4 == 0 && Fout_store <= 64 && ldy >= Fout_store,
-                "gcn_layer_fwd: Fout_store=%d must be a multiple of 4 in [Fout, min(64, ldy)]", Fout_store);
-  GCL_CHECK_ARG(ldx >= Fin && ldx % 4 == 0 && bsx % 4 == 0 && gcl::aligned16(x), "gcn_layer_fwd: x rows must be 16-B aligned");
-  GCL_CHECK_ARG(ldy % 4 == 0 && bsy % 4 == 0 && gcl::aligned16(y), "gcn_layer_fwd: y rows must be 16-B aligned");
-  GCL_CHECK_ARG(g->n_heavy == 0, "gcn_layer_fwd: the graph has rows with more than %d in-edges", gcl::kHeavy);
-  GCL_CHECK_ARG(act == GCL_ACT_NONE || act == GCL_ACT_SILU || (act == GCL_ACT_PRELU && slope),
-                "gcn_layer_fwd: bad activation %d", act);
-  GCL_CHECK_ARG(x != y, "gcn_layer_fwd: in-place is not supported");
+  if (const int rc = check_layer_args("gcn_layer_fwd", false, g, x, ldx, bsx, act, slope, W, y, ldy, bsy, B, Fin, Fout, Fout_store)) return rc;
   const int32_t n = g->n;
   GCL_CHECK_ARG(rows_out >= 1 && rows_out <= n, "gcn_layer_fwd: rows_out=%d outside [1, n=%d]", rows_out, n);
   hipStream_t st = (hipStream_t)stream;
-  float* yb = sp ? sp->yb : nullptr;  // (gcl_gcn_layer_fwd_split has made sure that the source-tile form does not take the layer)
+  float* yb = sp ? sp->yb : nullptr;
   const int64_t ldb = sp ? sp->ldb : 0, bsb = sp ? sp->bsb : 0;
   const int32_t head = sp ? sp->head : 0;
-  if (present) {  // the form with the output-row predicate, where it exists; storing every row is always right too
-    bool launched = false;
-    const int rc = halo_layer_launch(g, x, ldx, bsx, nullptr, 0, act, slope, W, bias, y, ldy, bsy, B, Fin, Fout, Fout_store,
-                                     rows_out, st, &launched, present);
-    if (rc || launched) return rc;
-  }
-  if (!sp) {
-    bool launched = false;
-    const int rc = halo_layer_launch(g, x, ldx, bsx, nullptr, 0, act, slope, W, bias, y, ldy, bsy, B, Fin, Fout, Fout_store,
-                                     rows_out, st, &launched);
-    if (rc || launched) return rc;
-  }
+  // present: the form with the output-row predicate, where it exists; storing every row is always right too
+  const gcl::plan::GcnPlan p = gcl::plan::plan_gcn_layer(
+      *g, {ldx, bsx, ldy, B, Fin, rows_out, 0, false, present != nullptr, sp != nullptr}, gcn_switches());
+  GCL_CHECK_ARG(p.form != GcnForm::kRefused, "%s", p.why);
+  if (gcl::plan::is_tile(p.form))
+    return launch_gcn_tile(g, p, x, ldx, bsx, nullptr, act, slope, W, bias, y, ldy, bsy, B, Fin, Fout, Fout_store, st,
+                           p.form == GcnForm::kTilePred ? present : nullptr);
   const int32_t nRT = (int32_t)gcl::cdiv(rows_out, 32);  // only the tiles that hold requested rows are computed
   const int NS = Fout_store > 32 ? 2 : 1;
   constexpr int NW12 = 12, NW8 = 8;
   const int KP = Fin + 2;
-  const int x3_env = gcl::env_int("GCL_X3", 1) && gcl::env_int("GCL_X3_GCN", 1);
   const size_t wave1_b = (size_t)wave_region_f(32 * (KP > NS * 32 ? KP : NS * 32)) * sizeof(float);
   // the split-operand variant holds its A fragments in registers: 8 waves per block (256 VGPRs each) instead of 12
-  const bool x3 = x3_env != 0 && (Fin % 16 == 0);
-  GCL_CHECK_ARG(!sp || (x3 && g->kind == GCL_GRAPH_GCN), "gcn_layer_fwd_split: only the split-operand kernel of a GCN graph stores in two parts");
+  const bool x3 = p.form == GcnForm::kEdgeX3;
   const int NWr = x3 ? NW8 : NW12;
   const size_t lds = (x3 ? (size_t)3 * NS * 32 * kWRowB : (size_t)NS * 32 * KP * sizeof(float)) + NWr * wave1_b;
-  GCL_CHECK_ARG((int64_t)n * ldx * 4 < (int64_t)1 << 31 && n < (1 << 24) && ldx * 4 < (1 << 24),
-                "gcn_layer_fwd: one sample of x must stay below 2 GiB (n, row bytes < 2^24)");
   const int64_t tiles = (int64_t)B * nRT;
   int64_t grid = gcl::kNumCU;
   if (tiles < grid * NWr) grid = gcl::cdiv(tiles, NWr);
   if (B >= gcl::kNumXCD) grid = gcl::cdiv(grid, gcl::kNumXCD) * gcl::kNumXCD;  // XCD-aware schedule needs a multiple of 8
   const int ewidth = g->ell_cover;  // smallest prefix width that covers (almost) every row: the fix-up loop is the slow path
-#define GCL_GF4(NS_, ACT_, EW_)                \
-  do {                                         \
-    if (x3 && sp) GCL_GF6(NS_, ACT_, EW_, true, true); /* (split_ok: the two-part form exists with split operands only) */ \
-    else if (x3) GCL_GF6(NS_, ACT_, EW_, true, false); \
-    else GCL_GF6(NS_, ACT_, EW_, false, false); \
-  } while (0)
-#define GCL_GF6(NS_, ACT_, EW_, X3_, SP_)                                                                            \
-  do {                                                                                                              \
-    constexpr int NW = X3_ ? NW8 : NW12;                                                                            \
-    auto kern = gcn_fwd_kernel<NS_, ACT_, EW_, NW, false, X3_, SP_>;                                                \
-    GCL_ENSURE_DYN_LDS(kern, gcl::kLdsBytes);                                                                       \
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(NW * 64), lds, st, g->rowptr, g->col, g->w, g->ecol, g->ew, x, \
-                       ldx, bsx, slope, W, bias, y, ldy, bsy, n, B, Fin, Fout, Fout_store, nRT, rows_out, yb, ldb, bsb, \
-                       head);                                                                                       \
-  } while (0)
-#define GCL_GF3(NS_, ACT_)                  \
-  do {                                      \
-    switch (ewidth) {                       \
-      case 8: GCL_GF4(NS_, ACT_, 8); break; \
-      case 4: GCL_GF4(NS_, ACT_, 4); break; \
-      default: GCL_GF4(NS_, ACT_, 2); break; \
-    }                                       \
-  } while (0)
-#define GCL_GF2(NS_)                                         \
-  do {                                                       \
-    if (act == GCL_ACT_PRELU) GCL_GF3(NS_, gcl::kActPrelu);  \
-    else if (act == GCL_ACT_SILU) GCL_GF3(NS_, gcl::kActSilu); \
-    else GCL_GF3(NS_, gcl::kActNone);                        \
-  } while (0)
-  if (g->kind == GCL_GRAPH_MEAN) {  // no self-loops: masked (SAFE) variant, activation-free, widest prefix
-    GCL_CHECK_ARG(act == GCL_ACT_NONE, "gcn_layer_fwd: mean-aggregation graphs take no activation");
-    constexpr int NW = NW12;
-    const size_t lds = (size_t)NS * 32 * KP * sizeof(float) + NW * wave1_b;
-    int64_t grid = gcl::kNumCU;
-    if (tiles < grid * NW) grid = gcl::cdiv(tiles, NW);
-    if (B >= gcl::kNumXCD) grid = gcl::cdiv(grid, gcl::kNumXCD) * gcl::kNumXCD;
-    if (NS == 2) {
-      auto kern = gcn_fwd_kernel<2, gcl::kActNone, 8, NW, true, false>;
-      GCL_ENSURE_DYN_LDS(kern, gcl::kLdsBytes);
-      hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(NW * 64), lds, st, g->rowptr, g->col, g->w, g->ecol, g->ew, x, ldx,
-                         bsx, slope, W, bias, y, ldy, bsy, n, B, Fin, Fout, Fout_store, nRT, rows_out, yb, ldb, bsb, head);
-    } else {
-      auto kern = gcn_fwd_kernel<1, gcl::kActNone, 8, NW, true, false>;
-      GCL_ENSURE_DYN_LDS(kern, gcl::kLdsBytes);
-      hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(NW * 64), lds, st, g->rowptr, g->col, g->w, g->ecol, g->ew, x, ldx,
-                         bsx, slope, W, bias, y, ldy, bsy, n, B, Fin, Fout, Fout_store, nRT, rows_out, yb, ldb, bsb, head);
-    }
-  } else if (NS == 2) GCL_GF2(2);
-  else GCL_GF2(1);
-#undef GCL_GF2
-#undef GCL_GF3
-#undef GCL_GF4
-#undef GCL_GF6
+  auto launch = [&](auto kern, int nw) {
+    GCL_ENSURE_DYN_LDS(kern, gcl::kLdsBytes);
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(nw * 64), lds, st, g->rowptr, g->col, g->w, g->ecol, g->ew, x, ldx, bsx,
+                       slope, W, bias, y, ldy, bsy, n, B, Fin, Fout, Fout_store, nRT, rows_out, yb, ldb, bsb, head);
+    return (int)GCL_OK;
+  };
+  using gcl::plan::pick;
+  const int rc = pick<1, 2>(NS, [&](auto NS_) {
+    constexpr int ns = decltype(NS_)::value;
+    if (p.form == GcnForm::kEdgeMean)  // no self-loops: masked (SAFE) variant, activation-free, widest prefix
+      return launch(gcn_fwd_kernel<ns, gcl::kActNone, 8, NW12, true, false>, NW12);
+    return pick<gcl::kActNone, gcl::kActPrelu, gcl::kActSilu>(act, [&](auto ACT) {
+      return pick<8, 4, 2>(ewidth == 8 || ewidth == 4 ? ewidth : 2, [&](auto EW) {
+        // fp32 operands / split operands / split operands and a two-part destination (which exists with them only)
+        return pick<0, 1, 2>(!x3 ? 0 : !sp ? 1 : 2, [&](auto V) {
+          constexpr int v = decltype(V)::value, NW = v ? NW8 : NW12;
+          return launch(gcn_fwd_kernel<ns, decltype(ACT)::value, decltype(EW)::value, NW, false, v != 0, v == 2>, NW);
+        });
+      });
+    });
+  });
+  if (rc) return rc;
   GCL_CHECK_LAUNCH();
   return GCL_OK;
 }
@@ -1179,32 +1118,18 @@ extern "C" int gcl_gcn_layer_fwd_present(const gcl_graph_t* g, const float* x, i
 }
 
 // Would gcl_gcn_layer_fwd_split run?  (0: the caller writes one tensor and copies the parts.)
-static bool split_ok(const gcl_graph_t* g, int64_t ldx, int64_t bsx, int64_t lda, int64_t bsa, int64_t ldb, int64_t bsb,
-                     int32_t head, int32_t B, int32_t Fin, int32_t Fout, int32_t Fout_store) {
-  if (!g || g->kind != GCL_GRAPH_GCN || g->n_heavy) return false;
-  const int32_t n = g->n;
-  if (head <= 0 || head >= n || head % 32 != 0) return false;  // a 32-row wave tile must lie in one part
-  if (!(B > 0 && Fin >= 4 && Fin <= 64 && Fin % 4 == 0 && Fout >= 1 && Fout <= 64 && Fout_store >= Fout && Fout_store % 4 == 0 &&
-        Fout_store <= 64))
-    return false;  // the two-kernel fallback's shapes
-  if (ldx < Fin || ldx % 4 || bsx % 4 || lda < Fout_store || ldb < Fout_store || lda % 4 || bsa % 4 || ldb % 4 || bsb % 4)
-    return false;  // whole 16-byte rows in both parts
-  if (!((int64_t)n * ldx * 4 < (int64_t)1 << 31 && n < (1 << 24) && ldx * 4 < (1 << 24) && (int64_t)head * lda * 4 < (int64_t)1 << 31 &&
-        (int64_t)(n - head) * ldb * 4 < (int64_t)1 << 31))
-    return false;  // 32-bit byte offsets, per part
-  // the 8-wave split-operand instantiations carry the variant (what 16-, 32-, 48- and 64-wide inputs select); the 12-wave
-  // fp32-operand ones sit at their register limit
-  if (!(gcl::env_int("GCL_X3", 1) && gcl::env_int("GCL_X3_GCN", 1)) || Fin % 16 != 0) return false;
-  bool halo = false;  // the source-tile form stores through its own path: it keeps the one-tensor destination
-  if (halo_layer_launch(g, nullptr, ldx, bsx, nullptr, 0, GCL_ACT_NONE, nullptr, nullptr, nullptr, nullptr, lda, bsa, B, Fin, Fout,
-                        Fout_store, n, nullptr, &halo, nullptr, true) != GCL_OK)
-    return false;
-  return !halo;
-}
-
 extern "C" int gcl_gcn_layer_fwd_split_ok(const gcl_graph_t* g, int64_t ldx, int64_t bsx, int64_t lda, int64_t bsa, int64_t ldb,
                                           int64_t bsb, int32_t head, int32_t B, int32_t Fin, int32_t Fout, int32_t Fout_store) {
-  return split_ok(g, ldx, bsx, lda, bsa, ldb, bsb, head, B, Fin, Fout, Fout_store) ? 1 : 0;
+  if (!g || g->n_heavy) return false;
+  const int32_t n = g->n;
+  if (head <= 0 || head >= n || head % 32 != 0) return false;  // a 32-row wave tile must lie in one part
+  if (!layer_shapes_ok(B, Fin, Fout, Fout_store, ldx, bsx, lda, bsa) || ldb < Fout_store || ldb % 4 || bsb % 4)
+    return false;  // the layer's shapes, whole 16-byte rows in both parts
+  if (!gcl::plan::bytes31_ok(head, lda) || !gcl::plan::bytes31_ok(n - head, ldb)) return false;  // 32-bit byte offsets, per part
+  // The per-edge split-operand kernel of a GCN graph carries the variant (what 16-, 32-, 48- and 64-wide inputs select;
+  // the 12-wave fp32-operand instantiations sit at their register limit).  A source-tile form stores through its own
+  // path and keeps the one-tensor destination: the plan refuses that too.
+  return gcl::plan::plan_gcn_layer(*g, {ldx, bsx, lda, B, Fin, n, 0, false, false, true}, gcn_switches()).form == GcnForm::kEdgeX3;
 }
 
 // The layer with a two-part destination (gcn_fwd_kernel<.., SPLIT>): rows < head of sample b go to ya + b * bsa + i * lda,
@@ -1215,7 +1140,7 @@ extern "C" int gcl_gcn_layer_fwd_split(const gcl_graph_t* g, const float* x, int
                                        int64_t bsa, float* yb, int64_t ldb, int64_t bsb, int32_t head, int32_t B, int32_t Fin,
                                        int32_t Fout, int32_t Fout_store, gcl_stream_t stream) {
   GCL_CHECK_ARG(g && x && W && ya && yb, "gcn_layer_fwd_split: null argument");
-  GCL_CHECK_ARG(split_ok(g, ldx, bsx, lda, bsa, ldb, bsb, head, B, Fin, Fout, Fout_store),
+  GCL_CHECK_ARG(gcl_gcn_layer_fwd_split_ok(g, ldx, bsx, lda, bsa, ldb, bsb, head, B, Fin, Fout, Fout_store),
                 "gcn_layer_fwd_split: head=%d of n=%d rows, strides %lld / %lld or this graph / shape have no two-part form "
                 "(head %% 32 == 0, 0 < head < n, 16-byte rows, the per-edge one-kernel layer)",
                 head, g->n, (long long)lda, (long long)ldb);
@@ -1224,7 +1149,7 @@ extern "C" int gcl_gcn_layer_fwd_split(const gcl_graph_t* g, const float* x, int
   return layer_fwd_impl(g, x, ldx, bsx, act, slope, W, bias, ya, lda, bsa, B, Fin, Fout, Fout_store, g->n, nullptr, stream, &sp);
 }
 
-// The layer with its input rows read through a row table (gcn_halo_fwd_kernel<.., TAB>): row i of sample b is row
+// The layer with its input rows read through a row table (GcnForm::kTileTab): row i of sample b is row
 // tab[i] of sample b of x when tab[i] >= 0, the batch-invariant flat row ~tab[i] of x otherwise.  Only the source-tile
 // form supports it: GCL_EUNSUPPORTED elsewhere (gcl_gcn_layer_fwd_tab_ok tells beforehand), and the caller
 // materialises the rows (gcl_gather2_rows) and calls gcl_gcn_layer_fwd instead.
@@ -1232,44 +1157,20 @@ extern "C" int gcl_gcn_layer_fwd_tab(const gcl_graph_t* g, const float* x, int64
                                      const int32_t* tab, int32_t act, const float* slope, const float* W,
                                      const float* bias, float* y, int64_t ldy, int64_t bsy, int32_t B, int32_t Fin,
                                      int32_t Fout, int32_t Fout_store, gcl_stream_t stream) {
-  GCL_CHECK_ARG(g && x && W && y && tab, "gcn_layer_fwd_tab: null argument");
-  GCL_CHECK_ARG(g->kind == GCL_GRAPH_GCN, "gcn_layer_fwd_tab: graph carries no GCN edge weights");
-  GCL_CHECK_ARG(B > 0 && Fin >= 4 && Fin <= 64 && Fin % 4 == 0 && Fout >= 1 && Fout <= 64,
-                "gcn_layer_fwd_tab: unsupported Fin=%d Fout=%d (Fin %% 4 == 0, both <= 64)", Fin, Fout);
-  GCL_CHECK_ARG(Fout_store >= Fout && Fout_store % 4 == 0 && Fout_store <= 64 && ldy >= Fout_store,
-                "gcn_layer_fwd_tab: Fout_store=%d must be a multiple of 4 in [Fout, min(64, ldy)]", Fout_store);
-  GCL_CHECK_ARG(ldx >= Fin && ldx % 4 == 0 && bsx % 4 == 0 && gcl::aligned16(x) && x_rows >= 1,
-                "gcn_layer_fwd_tab: x rows must be 16-B aligned");
-  GCL_CHECK_ARG(ldy % 4 == 0 && bsy % 4 == 0 && gcl::aligned16(y), "gcn_layer_fwd_tab: y rows must be 16-B aligned");
-  GCL_CHECK_ARG(act == GCL_ACT_NONE || act == GCL_ACT_SILU || (act == GCL_ACT_PRELU && slope),
-                "gcn_layer_fwd_tab: bad activation %d", act);
-  bool launched = false;
-  const int rc = halo_layer_launch(g, x, ldx, bsx, tab, x_rows, act, slope, W, bias, y, ldy, bsy, B, Fin, Fout, Fout_store,
-                                   g->n, (hipStream_t)stream, &launched);
-  if (rc) return rc;
-  if (!launched && g->n_heavy) {
-    gcl::set_error("gcn_layer_fwd_tab: the graph has %d heavy rows (more than %d in-edges), which the source-tile form "
-                   "does not compute", g->n_heavy, gcl::kHeavy);
+  if (const int rc = check_layer_args("gcn_layer_fwd_tab", true, g, x, ldx, bsx, act, slope, W, y, ldy, bsy, B, Fin, Fout, Fout_store)) return rc;
+  GCL_CHECK_ARG(tab && x_rows >= 1, "gcn_layer_fwd_tab: null row table or no rows of x");
+  const gcl::plan::GcnPlan p = gcl::plan::plan_gcn_layer(*g, {ldx, bsx, ldy, B, Fin, g->n, x_rows, true}, gcn_switches());
+  if (p.form == GcnForm::kRefused) {
+    gcl::set_error("%s (Fin=%d Fout=%d)", p.why, Fin, Fout);
     return GCL_EUNSUPPORTED;
   }
-  if (!launched) {
-    gcl::set_error("gcn_layer_fwd_tab: this graph / shape has no source-tile form (Fin=%d Fout=%d)", Fin, Fout);
-    return GCL_EUNSUPPORTED;
-  }
-  return GCL_OK;
+  return launch_gcn_tile(g, p, x, ldx, bsx, tab, act, slope, W, bias, y, ldy, bsy, B, Fin, Fout, Fout_store, (hipStream_t)stream, nullptr);
 }
 
 extern "C" int gcl_gcn_layer_fwd_tab_ok(const gcl_graph_t* g, int64_t ldx, int64_t bsx, int64_t x_rows, int32_t B,
                                         int32_t Fin, int32_t Fout) {
-  if (!g || g->kind != GCL_GRAPH_GCN || g->n_heavy) return 0;
-  const int x3_on = gcl::env_int("GCL_X3", 1) && gcl::env_int("GCL_X3_GCN", 1);
-  const gcl_halo& hl = g->halo[0][0];
-  if (!gcl::env_int("GCL_GCN_HALO", 1) || !x3_on || hl.T != 64) return 0;
-  const int hp4 = (int)gcl::cdiv((hl.smax - 64) / 4, 4);
-  const size_t ldsh = (size_t)2 * (32 * (Fin + 2) > 2048 ? 32 * (Fin + 2) : 2048) * 4 + (size_t)(hl.smax + 1) * 256;
-  return hp4 <= 4 && Fin % 16 == 0 && Fin > 32 && Fin <= 64 && Fout >= 1 && Fout <= 64 && g->e >= 6 * (int64_t)g->n &&
-                 ldsh <= 80 * 1024 && x_rows * ldx * 4 < ((int64_t)1 << 32) && (int64_t)B * bsx * 4 < ((int64_t)1 << 32) &&
-                 x_rows < (1 << 24) && g->n < (1 << 24) && ldx * 4 < (1 << 24)
-             ? 1
-             : 0;
+  // the launcher's scalar checks and plan, for the contiguous [B, n, Fst] output that hip.gcn_layer_fwd_tab allocates
+  const int32_t Fst = (Fout + 3) / 4 * 4;
+  if (!g || g->kind != GCL_GRAPH_GCN || !layer_shapes_ok(B, Fin, Fout, Fst, ldx, bsx, Fst, 0) || x_rows < 1) return 0;
+  return gcl::plan::plan_gcn_layer(*g, {ldx, bsx, Fst, B, Fin, g->n, x_rows, true}, gcn_switches()).form == GcnForm::kTileTab;
 }

@@ -306,7 +306,8 @@ int gcl_aggregate_head(const gcl_graph_t* g, int32_t transpose, const float* h, 
  * smap[i] of the compact destination yc [B, *, F] INSTEAD of y, < 0 = stored to y as always.  Each row is written once,
  * to one place, with gcl_aggregate's bits; the rows of y with an entry >= 0 are not touched.  Only the source-tile kernel
  * has the map: gcl_aggregate_compact_ok says (1 / 0) whether a call with these strides is taken, otherwise
- * gcl_aggregate_compact returns GCL_EINVAL and writes nothing. */
+ * gcl_aggregate_compact returns GCL_EINVAL and writes nothing.  The query reads the plan the launcher reads
+ * (csrc/tile_plan.h, plan_aggregate): it is 1 exactly when the call runs, given 16-byte aligned h, y and yc. */
 int gcl_aggregate_compact_ok(const gcl_graph_t* g, int32_t transpose, int64_t ldh, int64_t bsh, int64_t ldy, int64_t bsy,
                              int32_t B, int32_t F);
 int gcl_aggregate_compact(const gcl_graph_t* g, int32_t transpose, const float* h, int64_t ldh, int64_t bsh,
@@ -340,7 +341,10 @@ size_t gcl_gat_bwd_ws_bytes(int64_t e_prime, int32_t n, int32_t B, int32_t H, in
  * into the first processor layer: only the compact rows are transformed, functional.LatSource): row i of sample b is
  * row tab[i] of sample b of h when tab[i] >= 0, the batch-invariant flat row ~tab[i] of h otherwise; a_src / a_dst /
  * alpha / y / dh stay dense [B, n, ..].  One head on a source-tile graph (gcl_gat_tab_ok returns 1), else
- * GCL_EUNSUPPORTED.  gcl_gat_bwd_tab's dh is the gradient of the table-read rows; the caller folds it back. */
+ * GCL_EUNSUPPORTED.  gcl_gat_bwd_tab's dh is the gradient of the table-read rows; the caller folds it back.
+ * gcl_gat_tab_ok is 1 when the plans of BOTH launchers (csrc/tile_plan.h, plan_gat_fwd and plan_gat_bwd) choose the
+ * source-tile kernels for this ldh, taking dy as a contiguous [B, n, C] tensor.  It sees neither pointers nor B and bsh:
+ * 16-byte aligned att_src / att_dst / bias / dy and B * bsh * 4 < 2^32 are the caller's to keep. */
 int gcl_gat_fwd_tab(const gcl_graph_t* g, const float* h, int64_t ldh, int64_t bsh, const int32_t* tab /*[n]*/,
                     const float* att_src, const float* att_dst, const float* bias, float* a_src, float* a_dst,
                     float* alpha, float* y, int64_t ldy, int64_t bsy, int32_t B, int32_t H, int32_t C,
@@ -531,7 +535,7 @@ int gcl_gcn_layer_fwd_rows(const gcl_graph_t* g, const float* x, int64_t ldx, in
  * GCL_EINVAL without writing anything, when head % 32 != 0, head <= 0 or head >= n, when a stride is no multiple of 4
  * floats, when a part exceeds 32-bit byte offsets, when Fin % 16 != 0 (the fp32-operand instantiations have no two-part
  * form), or when the source-tile form or the two-kernel fallback would take the layer (the caller then writes one
- * tensor and copies). */
+ * tensor and copies).  Query and call read one plan (csrc/tile_plan.h, plan_gcn_layer). */
 int gcl_gcn_layer_fwd_split(const gcl_graph_t* g, const float* x, int64_t ldx, int64_t bsx, int32_t act,
                             const float* slope, const float* W /*[Fout,Fin]*/, const float* bias, float* ya, int64_t lda,
                             int64_t bsa, float* yb, int64_t ldb, int64_t bsb, int32_t head, int32_t B, int32_t Fin,
@@ -549,7 +553,10 @@ int gcl_gcn_layer_fwd_present(const gcl_graph_t* g, const float* x, int64_t ldx,
  * stage split of src/models.py:837-838 - `mesh_node_features = encoded[..., G:, :]` - folded into the first processor
  * layer's loads): input row i of sample b is row tab[i] of sample b of x when tab[i] >= 0, and row ~tab[i] of x viewed
  * as ONE flat list of x_rows rows (a batch-invariant row, shared by all samples) when tab[i] < 0.  Source-tile graphs
- * only (gcn_halo_fwd_kernel): GCL_EUNSUPPORTED otherwise; gcl_gcn_layer_fwd_tab_ok returns 1 when the call would run. */
+ * only (gcn_halo_fwd_kernel): GCL_EUNSUPPORTED otherwise; gcl_gcn_layer_fwd_tab_ok returns 1 when the call would run.
+ * The query reads the launcher's plan (csrc/tile_plan.h, plan_gcn_layer) and its scalar argument checks.  It has no
+ * ldy: for the n * ldy * 4 < 2^31 limit of the output it assumes the contiguous [B, n, roundup(Fout, 4)] tensor
+ * (ldy = Fout_store = roundup(Fout, 4)); a caller with a wider ldy keeps that limit itself. */
 int gcl_gcn_layer_fwd_tab(const gcl_graph_t* g, const float* x, int64_t ldx, int64_t bsx, int64_t x_rows,
                           const int32_t* tab /*[n]*/, int32_t act, const float* slope, const float* W /*[Fout,Fin]*/,
                           const float* bias, float* y, int64_t ldy, int64_t bsy, int32_t B, int32_t Fin, int32_t Fout,

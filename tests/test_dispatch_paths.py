@@ -1,8 +1,8 @@
 """The kernels the launchers pick when a gate or a switch moves them off the default path: the fp32-operand fallbacks
 (GCL_X3=0, GCL_X3_GCN=0, GCL_X3_TILE=0), the first form of the staged GCN layer (GCL_GCN_HALO_FORM=0), the separate
 and 128-row backward (GCL_NO_FUSED_BWD, GCL_NO_FUSED64), the dense kernel choice (GCL_DENSE_IMPL), the row-group order
-of agg_kernel (GCL_AGG_ORDER), the Python-side switches of the model, heavy rows on the staged kernels and the
-SparseGAT pruning on the compact pipeline.
+of agg_kernel (GCL_AGG_ORDER), the Python-side switches of the model, heavy rows on the staged kernels, the `_ok`
+queries against the launches they speak for, and the SparseGAT pruning on the compact pipeline.
 
 Every test proves that the path it names ran: kernel names from torch.profiler (HIP kernel names on ROCm) or a query
 of the library.  Small-integer inputs on constant-degree graphs make every path BIT-equal to float64; random inputs
@@ -395,6 +395,96 @@ def test_heavy_row_gat_on_tile_graph(hip, mesh35):
     assert rel(dx[:, heavy_row], x.grad[:, heavy_row]) < 5e-5
     assert rel(d_as.cpu(), a_s.grad.reshape(-1)) < 5e-5 and rel(d_ad.cpu(), a_d.grad.reshape(-1)) < 5e-5
     assert rel(d_b, b.grad) < TOL
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# The `_ok` queries and the launchers read one dispatch plan (csrc/tile_plan.h): a query says 1 exactly when the call runs
+# ------------------------------------------------------------------------------------------------------------------
+def _plan_graph(which, mesh35):
+    """(edge list, n, pieces per wave of its tiles or None with a heavy row) of the ring with n = 64 * 9 + 5 rows, or of
+    the [3, 5] mesh in tile order (at most 64 halo rows per tile)."""
+    if which == "mesh35":
+        return mesh35["ei"], mesh35["n"], 4
+    n = 64 * 9 + 5
+    near = ring(n, [d for d in range(-7, 9) if d != 0])  # sixteen in-edges per row: 16 halo rows per tile, 1 piece
+    if which == "ring16":
+        return near, n, 4
+    if which == "ring40":  # offsets out to +-40: 80 halo rows per tile = 5 pieces per wave (the 8-piece kernels)
+        return ring(n, [-40, -30, -20, -10, -1, 1, 10, 20, 30, 40]), n, 8
+    rng = np.random.default_rng(5)  # the graph of test_heavy_row_gcn_layer_through_row_table_is_refused
+    far = torch.from_numpy(rng.choice(np.setdiff1d(np.arange(n), np.arange(300 - 8, 300 + 9)), 64, replace=False))
+    return torch.cat([near, torch.stack([far, torch.full_like(far, 300)])], 1), n, None
+
+
+def _attempt(fn):
+    """fn(), or None for a refused call: a RuntimeError from a return code, nothing launched."""
+    try:
+        return fn()
+    except RuntimeError as exc:
+        assert "libgcl_hip error" in str(exc), exc
+        return None
+
+
+@pytest.mark.parametrize("width", [32, 48, 64])
+@pytest.mark.parametrize("which", ["ring16", "ring40", "heavy", "mesh35"])
+def test_queries_agree_with_launches(hip, env, mesh35, which, width):
+    """gcn_layer_tab_ok, gcn_layer_split_ok, aggregate_compact_ok and gat_tab_ok against the calls they speak for, with
+    the source-tile switches on and off, and the kernel and template arguments of the form the plan implies.  (The
+    source-tile aggregation needs the 8-wide edge prefix; on a ring every prefix width costs the same and the graph
+    takes the narrowest, so only the mesh has a store map.)"""
+    ei, n, pieces = _plan_graph(which, mesh35)
+    B, Fout, head = 2, 48, 256
+    gh, G = hip.Graph(ei, n, hip.GRAPH_GCN), hip.Graph(ei, n, hip.GRAPH_GAT)
+    assert gh.halo_info(False, 64) is not None and G.halo_info(True, 64) is not None
+    x, dy = rnd(B, n, width, seed=1).to(DEV), rnd(B, n, width, seed=6).to(DEV)
+    W, b, att = rnd(Fout, width, seed=2, scale=0.2).to(DEV), rnd(Fout, seed=3).to(DEV), rnd(width, seed=4, scale=0.3).to(DEV)
+    tab = torch.arange(n, dtype=torch.int32, device=DEV)
+    ya, yb = torch.empty(B, head, Fout, device=DEV), torch.empty(B, n - head, Fout, device=DEV)
+    outc = torch.empty(B, 8, width, device=DEV)
+    smap = torch.full((n,), -1, dtype=torch.int32, device=DEV)
+    smap[:8] = torch.arange(8, dtype=torch.int32)
+    dpar = [torch.empty(width, device=DEV) for _ in range(3)]
+    nodes, edges = torch.empty(B, n, 1, device=DEV), torch.empty(B, G.e, 1, device=DEV)  # stand-ins for a refused gat_fwd
+
+    def every():
+        """Which of the calls ran; the plain layer (no query: it always has a kernel without heavy rows) runs last."""
+        ran = dict(tab=_attempt(lambda: hip.gcn_layer_fwd_tab(gh, x, tab, hip.ACT_NONE, None, W, b)) is not None,
+                   split=_attempt(lambda: hip.gcn_layer_fwd_split(gh, x, hip.ACT_NONE, None, W, b, ya, yb) or True) is not None,
+                   compact=_attempt(lambda: hip.aggregate_compact(gh, x, smap, outc)) is not None)
+        fwd = _attempt(lambda: hip.gat_fwd(G, x, att, att, None, 1, width, tab=tab))
+        _, a_s, a_d, alpha = fwd or (None, nodes, nodes, edges)
+        bwd = _attempt(lambda: hip.gat_bwd(G, dy, x, att, att, a_s, a_d, alpha, *dpar, False, 1, width, tab=tab))
+        ran["gat"] = fwd is not None
+        assert (bwd is not None) == ran["gat"]
+        if pieces is not None:
+            hip.gcn_layer_fwd(gh, x, hip.ACT_NONE, None, W, b)
+        return ran
+
+    for on in (True, False):
+        env(GCL_GCN_HALO=None if on else 0, GCL_GAT_HALO=None if on else 0, GCL_AGG_HALO=None if on else 0)
+        tiles = on and pieces is not None  # heavy rows have no records in the tile layout
+        gcn_tile = tiles and width > 32    # 48- and 64-wide inputs
+        want = dict(tab=gcn_tile and pieces == 4, split=pieces is not None and not gcn_tile,
+                    compact=tiles and width > 32 and which == "mesh35", gat=tiles and width == 64)
+        assert hip.gcn_layer_tab_ok(gh, x, Fout) == want["tab"]
+        assert hip.gcn_layer_split_ok(gh, x, Fout, ya, yb) == want["split"]
+        assert hip.aggregate_compact_ok(gh, x) == want["compact"]
+        assert hip.gat_tab_ok(G, 1, width) == want["gat"]
+        if pieces is None:  # every call is refused: no kernel for the profiler to record
+            assert every() == want
+            continue
+        ran, names = launched(every)
+        assert ran == want
+        form = ["4", "2", "true", "true"] if pieces == 4 else ["8", "2", "true", "false"]  # MAXPW, STAUX, DIRECT, INTER
+        halo = ([form + ["false", "false"]] if gcn_tile else []) + ([form + ["true", "false"]] if want["tab"] else [])  # TAB, PRED
+        assert sorted(t[1:] for t in targs(names, "gcn_halo_fwd_kernel")) == sorted(halo), names
+        x3 = "true" if width % 16 == 0 else "false"  # gcn_fwd_kernel<NS, ACT, EW, NW, SAFE, X3, SPLIT>
+        edge = ([] if gcn_tile else [[x3, "false"]]) + ([["true", "true"]] if want["split"] else [])
+        assert sorted(t[5:] for t in targs(names, "gcn_fwd_kernel")) == sorted(edge), names
+        assert targs(names, "agg_halo_loop_kernel") == ([["16", "64", str(pieces), "false", "true"]] if want["compact"] else []), names
+        for kern, args in (("gat_halo_fwd_kernel", ["16", str(pieces), "true"]), ("gat_halo_bwd_dst_kernel", ["16", str(pieces), "true"]),
+                           ("gat_halo_bwd_src_kernel", ["16", str(pieces)])):
+            assert targs(names, kern) == ([args] if want["gat"] else []), names
 
 
 # ------------------------------------------------------------------------------------------------------------------
