@@ -7,7 +7,9 @@ GNN one sample at a time with 19 interpolators per sample, and `DownscalerDatase
 built once on the host (`verify.find_cells` / `verify.regrid_tables`, the same corner order and weights as scipy's)
 and the arithmetic runs in `csrc/downscale.hip`: `gcl_downscale_coarse`, `gcl_downscale_pred`, `gcl_downscale_batch`
 and `gcl_downscale_pair_mse`.  The objective, the scores and the training loop (`downscale_train.py`, kernels in
-`csrc/downscale_loss.hip`) are re-exported from here.  The U-Net itself is not part of this module.
+`csrc/downscale_loss.hip`) are re-exported from here.  The U-Net's inference is `unet.py`; the loop around it that
+`scripts/predict_cascade.py` runs - GNN, crop and upsample, U-Net, scores against the fine truth - is `CascadeRefiner`
+and `predict_cascade` at the end of this module (`gcl_cascade_pack`, `gcl_cascade_scores` of `csrc/unet.hip`).
 """
 import json
 import os
@@ -431,3 +433,136 @@ def coarse_baseline(ds: DownscalerDataset, channel_names: Optional[Sequence[str]
     if len(channel_names) != len(rmse):
         raise ValueError(f"coarse_baseline: {len(channel_names)} names for {len(rmse)} channels")
     return {name: float(v) for name, v in zip(channel_names, rmse)}
+
+
+# ======================================================================================================================
+# The cascade: GNN -> crop and upsample -> U-Net, scored against the fine truth (scripts/predict_cascade.py)
+# ======================================================================================================================
+class CascadeRefiner:
+    """The per-step refinement and scores of `predict_cascade.py:338-372` for B samples at a time.
+
+    `refine(coarse)`: coarse float32 [B, H, W, C] in the GNN's normalised space (the ROI output on the fine grid) ->
+    (cascade_out [B, C, H, W], coarse_phys [B, H, W, C]): `gcl_cascade_pack`, then the network (`unet.WeatherUNet`, with
+    the x_last add fused when `residual`).  `score(step, cascade_out, coarse_phys, t_fine, t_persist)` adds the step's
+    per-channel mean squared errors of GNN, cascade and persistence into the float64 device state (`gcl_cascade_scores`);
+    `results()` is the one host read."""
+
+    def __init__(self, unet, pairs_or_dir, gnn_mean, gnn_std, obs_window: int = 2, residual: bool = False,
+                 ar_steps: int = 4, device="cuda:0"):
+        pairs = pairs_or_dir if isinstance(pairs_or_dir, DownscalerPairs) else DownscalerPairs.load(pairs_or_dir, device)
+        self.unet, self.pairs, self.obs_window, self.residual = unet, pairs, int(obs_window), bool(residual)
+        self.T, self.W, self.H, self.C = (int(v) for v in pairs.fine.shape)
+        dev = pairs.device
+        f32 = lambda a: torch.from_numpy(np.asarray(a, dtype=np.float32)[:self.C].copy()).to(dev)  # noqa: E731
+        self.gnn_mean, self.gnn_std, self.ds_mean, self.ds_std = f32(gnn_mean), f32(gnn_std), f32(pairs.mean), f32(pairs.std)
+        for v in (self.gnn_mean, self.gnn_std, self.ds_mean, self.ds_std):
+            if v.numel() != self.C:
+                raise ValueError(f"CascadeRefiner: scalers of {v.numel()} channels for {self.C}")
+        self.static_fine = pairs.static_fine.float().contiguous() if pairs.static_fine is not None else None
+        ns = 0 if self.static_fine is None else int(self.static_fine.shape[2])
+        want = self.obs_window * self.C + ns
+        if getattr(unet, "in_channels", want) != want or getattr(unet, "out_channels", self.C) != self.C:
+            raise ValueError(f"CascadeRefiner: the network maps {unet.in_channels} to {unet.out_channels} channels, the "
+                             f"cascade feeds {want} and scores {self.C}")
+        self.reset(ar_steps)
+
+    def reset(self, ar_steps: int):
+        dev = self.pairs.device
+        self.state = torch.zeros(int(ar_steps), self.C, 3, dtype=torch.float64, device=dev)
+        self.count = torch.zeros(int(ar_steps), dtype=torch.int64, device=dev)
+
+    def refine(self, coarse):
+        if coarse.dim() != 4 or tuple(coarse.shape[1:]) != (self.H, self.W, self.C):
+            raise ValueError(f"CascadeRefiner: coarse [B, {self.H}, {self.W}, {self.C}] expected, got {tuple(coarse.shape)}")
+        coarse_phys, X = hip.cascade_pack(coarse.contiguous(), self.gnn_mean, self.gnn_std, self.ds_mean, self.ds_std,
+                                          self.static_fine, self.obs_window)
+        rf = ((self.obs_window - 1) * self.C, self.obs_window * self.C) if self.residual else None
+        return self.unet(X, residual_from=rf), coarse_phys
+
+    def score(self, step: int, cascade_out, coarse_phys, t_fine, t_persist):
+        """t_fine / t_persist: int64 [B] (device tensors or host ints); a frame outside the archive skips its sample."""
+        dev = self.pairs.device
+        as_dev = lambda t: (t if isinstance(t, torch.Tensor) else torch.tensor([int(v) for v in t], dtype=torch.int64)).to(dev)  # noqa: E731
+        hip.cascade_scores(cascade_out, coarse_phys, self.pairs.fine, as_dev(t_fine), as_dev(t_persist), self.ds_mean,
+                           self.ds_std, self.state, self.count, step)
+
+    def results(self):
+        """The dictionary `predict_cascade.py:481-494` writes: per horizon n_samples and, per dynamic channel,
+        rmse_persist / rmse_gnn / rmse_cascade."""
+        state, count = self.state.cpu().numpy(), self.count.cpu().numpy()
+        static = set(self.pairs.info.get("static_channels", []))
+        names = self.pairs.variables if self.pairs.variables else [f"ch{i}" for i in range(self.C)]
+        out = {}
+        for s in range(state.shape[0]):
+            rmse = np.sqrt(state[s] / count[s]) if count[s] > 0 else np.zeros_like(state[s])
+            out[f"+{(s + 1) * 6}h"] = {
+                "n_samples": int(count[s]),
+                "per_channel": {names[c]: {"rmse_persist": float(rmse[c, 2]), "rmse_gnn": float(rmse[c, 0]),
+                                           "rmse_cascade": float(rmse[c, 1])}
+                                for c in range(self.C) if c not in static}}
+        return out
+
+
+def predict_cascade(gnn_model, unet, test_dataset, pairs_or_dir, grid_lats, grid_lons, roi, gnn_mean, gnn_std,
+                    ar_steps: int = 4, max_samples: int = 50, batch_size: int = 8, use_residual: bool = False,
+                    unet_residual: bool = False, flat_grid: bool = True, obs_window: int = 2, refiner=None):
+    """The loop of `predict_cascade.py:292-372` over a `batch(indices)`-style data set, `batch_size` samples at a time.
+
+    Sample i sits at local_t = its `_sample_indices` entry's (else i); persistence is the fine frame t_persist =
+    local_t + obs - 1 (a sample whose t_persist is outside the archive is left out altogether), the target of step s the
+    frame t_fine = local_t + obs + s (a sample whose t_fine runs past the archive is skipped from that step on).  Each
+    step runs the GNN, puts its ROI output on the fine grid through `prediction_tables` (all samples and channels in one
+    launch), refines it (`CascadeRefiner.refine`) and scores it on the device; there is one host read, at the end.  The
+    result does not depend on batch_size.  Returns the dictionary of `cascade_results.json`."""
+    if refiner is None:
+        refiner = CascadeRefiner(unet, pairs_or_dir, gnn_mean, gnn_std, obs_window, unet_residual, ar_steps)
+    else:
+        refiner.reset(ar_steps)
+    pairs, C, T = refiner.pairs, refiner.C, refiner.T
+    dev = pairs.device
+    t_lats, t_lons = (np.asarray(a).astype(np.float32).astype(np.float64) for a in (pairs.lats, pairs.lons))
+    pos, w = device_tables(*prediction_tables(grid_lats, grid_lons, roi, t_lats, t_lons, flat_grid), dev)
+    n = min(int(max_samples), len(test_dataset))
+    si = getattr(test_dataset, "_sample_indices", None)
+    local_t = [int(si[i][1]) if si is not None and i < len(si) else i for i in range(n)]
+    obs = None
+    for a in range(0, n, max(1, int(batch_size))):
+        idx = list(range(a, min(n, a + batch_size)))
+        X, _ = test_dataset.batch(idx)
+        B, G, F = X.shape
+        obs = F // C
+        keep = [k for k, i in enumerate(idx) if local_t[i] + obs - 1 < T]  # :308-310
+        if not keep:
+            continue
+        if len(keep) < B:
+            X = X[torch.tensor(keep, device=X.device)]
+        lt = [local_t[idx[k]] for k in keep]
+        B = len(keep)
+        t_persist = torch.tensor([t + obs - 1 for t in lt], dtype=torch.int64).to(dev)
+        curr = X.view(B, G, obs, C)
+        offs = [b * G * C + c for b in range(B) for c in range(C)]
+        offs_dev = torch.tensor(offs, dtype=torch.int64).to(dev)
+        for step in range(int(ar_steps)):
+            tf = [t + obs + step if t + obs + step < T else -1 for t in lt]  # :330-333: the sample ends here
+            if all(t < 0 for t in tf):
+                break
+            with torch.no_grad():
+                pred = gnn_model(X=curr.reshape(B, G, obs * C), attention_threshold=0.0)
+            if pred.dim() == 2:
+                pred = pred.unsqueeze(0)
+            out = (curr[:, :, -1, :] + pred if use_residual else pred).detach().contiguous()
+            curr = torch.cat([curr[:, :, 1:, :], out.unsqueeze(2)], dim=2)
+            # the ROI nodes on the fine grid, float64 interpolation rounded once: [B * C, P], P latitude-major
+            fine64 = hip.wrf_sample(hip.WrfSource(out, C, G, pos, w), offs, field_off_dev=offs_dev)
+            coarse = fine64.to(torch.float32).view(B, C, refiner.H, refiner.W).permute(0, 2, 3, 1).contiguous()
+            cascade_out, coarse_phys = refiner.refine(coarse)
+            refiner.score(step, cascade_out, coarse_phys, torch.tensor(tf, dtype=torch.int64).to(dev), t_persist)
+    return refiner.results()
+
+
+def save_cascade_results(results, ds_dir: str) -> str:
+    """`cascade_results.json` in the downscaler's experiment directory (predict_cascade.py:495-497)."""
+    path = os.path.join(ds_dir, "cascade_results.json")
+    with open(path, "w") as fh:
+        json.dump(results, fh, indent=2)
+    return path

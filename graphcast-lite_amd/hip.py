@@ -242,6 +242,14 @@ _SIGNATURES = {
     "gcl_region_interp_scores_ws_bytes": (_sz, [_i32] * 4),
     "gcl_region_interp_scores": (C.c_int, [_vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp,
                                            _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "gcl_unet_packed_floats": (_i64, [_i32, _i32]),
+    "gcl_unet_pack_weights": (C.c_int, [_vp, _i32, _i32, _vp, _vp]),
+    "gcl_unet_conv3x3": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "gcl_unet_conv1x1_out": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "gcl_unet_launches": (_i64, []),
+    "gcl_cascade_pack": (C.c_int, [_vp] * 8 + [_i32] * 6 + [_vp]),
+    "gcl_cascade_scores_ws_bytes": (_sz, [_i32] * 4),
+    "gcl_cascade_scores": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp] + [_i32] * 6 + [_vp, _sz, _vp]),
 }
 
 
@@ -2506,3 +2514,110 @@ def region_interp_scores(pred3, nlat: int, cell, w, series, t0, first: int, mean
                                           _pd(std), N, int(P), nr, int(Cc), _pd(sums), _p(vout), _p(tout), ws.data_ptr(),
                                           ws.numel(), _stream()))
     return sums
+
+
+# ======================================================================================================================
+# WeatherUNet inference and the cascade scores (csrc/unet.hip)
+# ======================================================================================================================
+UNET_PLANAR, UNET_ROWS, UNET_POOL, UNET_UPCAT = 0, 1, 2, 3
+
+
+class UnetSrc(C.Structure):
+    """gcl_unet_src_t: how a 3x3 convolution reads its input (see include/gcl.h)."""
+    _fields_ = [("a", _vp), ("b", _vp), ("kind", _i32), ("C1", _i32), ("C2", _i32), ("Hs", _i32), ("Ws", _i32)]
+
+
+def unet_src(kind: int, a, b=None):
+    """The source descriptor of `a` (and, for UNET_UPCAT, the low tensor `b`): contiguous float32 device tensors, planar
+    [B, C, H, W] for UNET_PLANAR and channels-last [B, H, W, C] otherwise."""
+    for t in (a, b):
+        if t is not None and not t.is_contiguous():
+            raise ValueError("unet_src: contiguous tensors expected")
+    s = UnetSrc(_p(a), _p(b), int(kind), 0, 0, 0, 0)
+    if kind == UNET_POOL:
+        s.Hs, s.Ws = a.shape[1], a.shape[2]
+    elif kind == UNET_UPCAT:
+        s.C1, s.C2, s.Hs, s.Ws = a.shape[3], b.shape[3], b.shape[1], b.shape[2]
+    return s
+
+
+def unet_launches() -> int:
+    """Kernels launched by the entry points of csrc/unet.hip in this process."""
+    return int(lib().gcl_unet_launches())
+
+
+def unet_pack_weights(w, out=None):
+    """torch's [Cout, Cin, 3, 3] convolution weight in the order gcl_unet_conv3x3 streams."""
+    if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3) or not w.is_contiguous():
+        raise ValueError(f"unet_pack_weights: a contiguous [Cout, Cin, 3, 3] weight expected, got {tuple(w.shape)}")
+    Cout, Cin = w.shape[0], w.shape[1]
+    n = int(lib().gcl_unet_packed_floats(Cin, Cout))
+    if out is None:
+        out = torch.empty(n, dtype=torch.float32, device=w.device)
+    elif out.numel() != n or not out.is_contiguous():
+        raise ValueError(f"unet_pack_weights: out holds {out.numel()} floats, {n} expected")
+    _check(lib().gcl_unet_pack_weights(_p(w), Cin, Cout, _p(out), _stream()))
+    return out
+
+
+def unet_conv3x3(src: UnetSrc, packed, norm, eps: float, y, Cin: int):
+    """y [B, H, W, Cout] = the 3x3 convolution of the source with BatchNorm (norm = (gamma, beta, mean, var)) and GELU
+    behind it; norm None: the bare convolution (see gcl_unet_conv3x3)."""
+    if y.dim() != 4 or not y.is_contiguous():
+        raise ValueError("unet_conv3x3: y is a contiguous [B, H, W, Cout] tensor")
+    B, H, W, Cout = y.shape
+    g, bt, m, v = norm if norm is not None else (None, None, None, None)
+    _check(lib().gcl_unet_conv3x3(C.byref(src), _p(packed), _p(g), _p(bt), _p(m), _p(v), float(eps), _p(y), B, H, W,
+                                  int(Cin), Cout, _stream()))
+    return y
+
+
+def unet_conv1x1_out(x, w, bias, y, residual=None, res_bs: int = 0):
+    """y [B, Cout, H, W] (planar) = x [B, H, W, F] times w [Cout, F] plus bias, plus channel co of the planar `residual`
+    view (sample stride res_bs floats) when given (see gcl_unet_conv1x1_out)."""
+    B, H, W, F = x.shape
+    Cout = w.shape[0]
+    if tuple(y.shape) != (B, Cout, H, W) or not (x.is_contiguous() and y.is_contiguous() and w.is_contiguous()):
+        raise ValueError(f"unet_conv1x1_out: contiguous x [B, H, W, F], w [Cout, F] and y [{B}, {Cout}, {H}, {W}] expected")
+    _check(lib().gcl_unet_conv1x1_out(_p(x), _p(w), _p(bias), _p(residual), int(res_bs), _p(y), B, H, W, F, Cout,
+                                      _stream()))
+    return y
+
+
+def cascade_pack(coarse, gnn_mean, gnn_std, ds_mean, ds_std, static_fine, obs: int, coarse_phys=None, X=None):
+    """(coarse_phys [B, H, W, C], X [B, obs * C + Ns, H, W]) of coarse [B, H, W, C] (see gcl_cascade_pack).  The four
+    vectors: float32 [C]; static_fine: float32 [W, H, Ns] or None."""
+    B, H, W, Cc = coarse.shape
+    Ns = 0 if static_fine is None else static_fine.shape[2]
+    if static_fine is not None and (tuple(static_fine.shape[:2]) != (W, H) or not static_fine.is_contiguous()):
+        raise ValueError(f"cascade_pack: static_fine is a contiguous [{W}, {H}, Ns] tensor")
+    if not coarse.is_contiguous() or any(v.numel() != Cc for v in (gnn_mean, gnn_std, ds_mean, ds_std)):
+        raise ValueError("cascade_pack: a contiguous coarse [B, H, W, C] and four vectors of C values expected")
+    if coarse_phys is None:
+        coarse_phys = torch.empty_like(coarse)
+    if X is None:
+        X = torch.empty(B, obs * Cc + Ns, H, W, dtype=torch.float32, device=coarse.device)
+    if tuple(X.shape) != (B, obs * Cc + Ns, H, W) or not X.is_contiguous() or not coarse_phys.is_contiguous():
+        raise ValueError(f"cascade_pack: X is a contiguous [{B}, {obs * Cc + Ns}, {H}, {W}] tensor")
+    _check(lib().gcl_cascade_pack(_p(coarse), _p(gnn_mean), _p(gnn_std), _p(ds_mean), _p(ds_std), _p(static_fine),
+                                  _p(coarse_phys), _p(X), B, H, W, Cc, int(obs), Ns, _stream()))
+    return coarse_phys, X
+
+
+def cascade_scores(out, coarse_phys, fine, t_fine, t_persist, ds_mean, ds_std, state, count, step: int, ws=None):
+    """state [AR, C, 3] float64 / count [AR] int64 += the scores of one step (see gcl_cascade_scores).  out [B, C, H, W];
+    coarse_phys [B, H, W, C]; fine fp16 [T, W, H, n_feat]; t_fine / t_persist int64 [B] on the device."""
+    B, Cc, H, W = out.shape
+    if tuple(coarse_phys.shape) != (B, H, W, Cc) or fine.dim() != 4 or tuple(fine.shape[1:3]) != (W, H):
+        raise ValueError(f"cascade_scores: coarse_phys [{B}, {H}, {W}, {Cc}] and fine [T, {W}, {H}, >= {Cc}] expected")
+    if not (out.is_contiguous() and coarse_phys.is_contiguous()) or t_fine.numel() != B or t_persist.numel() != B:
+        raise ValueError("cascade_scores: contiguous fields and t_fine / t_persist of B values expected")
+    if state.dim() != 3 or tuple(state.shape[1:]) != (Cc, 3) or count.numel() != state.shape[0]:
+        raise ValueError(f"cascade_scores: state [AR, {Cc}, 3] and count [AR] expected")
+    need = int(lib().gcl_cascade_scores_ws_bytes(B, H, W, Cc))
+    if ws is None:
+        ws = workspace(need, out.device)
+    _check(lib().gcl_cascade_scores(_p(out), _p(coarse_phys), _ph(fine), fine.shape[0], fine.shape[3], _pl(t_fine),
+                                    _pl(t_persist), _p(ds_mean), _p(ds_std), _pd(state), _pl(count), int(step),
+                                    state.shape[0], B, H, W, Cc, ws.data_ptr(), ws.numel() * ws.element_size(), _stream()))
+    return state

@@ -1343,6 +1343,78 @@ int gcl_region_interp_scores(const float* pred, int64_t ldp, int64_t bsp, int32_
                              int32_t C, double* sums, float* vout, float* tout, void* ws, size_t ws_bytes,
                              gcl_stream_t stream);
 
+/* ---- WeatherUNet inference and the cascade scores (csrc/unet.hip) ----
+ * The eval-mode forward of src/unet/model.py:11-98 as one launch per convolution, and the per-step refinement and scores
+ * of scripts/predict_cascade.py:338-372.  No entry point allocates, synchronises or reads back; no floating-point
+ * atomics; every sum has an order fixed by the layer's shape, never by B or a sample's place in the batch.
+ *
+ * Activations between layers are channels-last [B,H,W,C] float32.  MaxPool2d(2), Upsample(bilinear, align_corners),
+ * the pad to the skip's size and the concatenation (model.py:32-56) are not launches or tensors: they are ways the next
+ * convolution reads its input, described by gcl_unet_src_t:
+ *   PLANAR  a = the caller's [B,Cin,H,W] tensor (the first layer).
+ *   ROWS    a = [B,H,W,Cin].
+ *   POOL    a = [B,Hs,Ws,Cin]; the input is its 2x2 maximum, H = Hs / 2, W = Ws / 2 (a last odd row / column is dropped,
+ *           a NaN in a window gives NaN: torch's max_pool2d).
+ *   UPCAT   channels 0 .. C1-1 are a = the skip [B,H,W,C1]; channels C1 .. C1+C2-1 are the bilinear interpolation of
+ *           b = [B,Hs,Ws,C2] to 2 Hs x 2 Ws (align_corners=True: s = dst * (in-1)/(out-1) in float32, i0 = floor(s),
+ *           i1 = min(i0+1, in-1), l = s - i0), zero at rows >= 2 Hs or columns >= 2 Ws.  C1 + C2 = Cin. */
+#define GCL_UNET_SRC_PLANAR 0
+#define GCL_UNET_SRC_ROWS 1
+#define GCL_UNET_SRC_POOL 2
+#define GCL_UNET_SRC_UPCAT 3
+typedef struct gcl_unet_src {
+  const float* a;
+  const float* b;
+  int32_t kind;
+  int32_t C1, C2; /* UPCAT */
+  int32_t Hs, Ws; /* POOL: the source's size; UPCAT: the low tensor's */
+} gcl_unet_src_t;
+/* torch's Conv2d weight [Cout,Cin,3,3] (model.py:16,19) into the order gcl_unet_conv3x3 streams: per 32 output channels,
+ * tap and 8 input channels one 1 KiB record holding each lane's four B operands of v_mfma_f32_32x32x2_f32, zero where
+ * Cin or Cout is padded.  packed: gcl_unet_packed_floats(Cin, Cout) floats, 16-byte aligned.  One launch. */
+int64_t gcl_unet_packed_floats(int32_t Cin, int32_t Cout);
+int gcl_unet_pack_weights(const float* w, int32_t Cin, int32_t Cout, float* packed, gcl_stream_t stream);
+/* One 3x3 convolution (padding 1, no bias) with BatchNorm2d in eval mode and the exact (erf) GELU behind it
+ * (model.py:15-22), one launch: y[b,y,x,co] = gelu((acc - mean[co]) * (gamma[co] / sqrt(var[co] + eps)) + beta[co]) from
+ * the four vectors as they are at the call (no folded copy); gamma == NULL (then all four are ignored): y = acc.
+ * An implicit GEMM on the fp32-operand matrix instruction: a block owns 4 x 8 output pixels of one sample and 32 output
+ * channels; the input tile with its one-pixel halo is staged in LDS 32 channels at a time and all nine taps are read
+ * from there; the block's four waves take 8 channels of a chunk each and their partial sums are added in LDS as
+ * (w0 + w1) + (w2 + w3) (from Cin = 256 on: eight waves, chunks of 64 channels, + ((w4 + w5) + (w6 + w7))).  Cin >= 1, Cout % 4 == 0, H, W >= 1, B <= 65535; y [B,H,W,Cout] and packed 16-byte aligned.
+ * A NaN or Inf reaches only the outputs of its own sample. */
+int gcl_unet_conv3x3(const gcl_unet_src_t* src, const float* packed, const float* gamma, const float* beta,
+                     const float* mean, const float* var, float eps, float* y, int32_t B, int32_t H, int32_t W,
+                     int32_t Cin, int32_t Cout, gcl_stream_t stream);
+/* The 1x1 output convolution (model.py:85,98): x [B,H,W,F] times w [Cout,F] plus bias [Cout], written as the planar
+ * y [B,Cout,H,W]; the products are added in ascending f.  residual (may be NULL): a planar tensor whose sample stride is
+ * res_bs floats and whose channel co is added, y = (conv + bias) + residual, each sum rounded in float32: the x_last of
+ * predict_cascade.py:357-359 read from the network's own input.  F % 4 == 0, x and w 16-byte aligned, Cout any. */
+int gcl_unet_conv1x1_out(const float* x, const float* w, const float* bias, const float* residual, int64_t res_bs,
+                         float* y, int32_t B, int32_t H, int32_t W, int32_t F, int32_t Cout, gcl_stream_t stream);
+/* How many kernels the entry points of this section have launched in this process (a counter for tests). */
+int64_t gcl_unet_launches(void);
+/* predict_cascade.py:346-354 for B samples in one launch.  coarse [B,H,W,C] in GNN-normalised space;
+ * coarse_phys [B,H,W,C] = coarse * gnn_std + gnn_mean, product and sum rounded one by one; X [B,obs*C+Ns,H,W]: channel
+ * o*C + c = (coarse_phys - ds_mean[c]) / ds_std[c] (each operation rounded, no epsilon) for o < obs, channel obs*C + s =
+ * static_fine[x,y,s] (static_fine [W,H,Ns], NULL when Ns == 0).  The four vectors are float32 [C]. */
+int gcl_cascade_pack(const float* coarse, const float* gnn_mean, const float* gnn_std, const float* ds_mean,
+                     const float* ds_std, const float* static_fine, float* coarse_phys, float* X, int32_t B, int32_t H,
+                     int32_t W, int32_t C, int32_t obs, int32_t Ns, gcl_stream_t stream);
+/* predict_cascade.py:360-372.  out [B,C,H,W]: the network's planar output (residual applied); coarse_phys [B,H,W,C];
+ * fine: fp16 [T,W,H,n_feat], n_feat >= C; t_fine / t_persist: device int64 [B].  cascade_phys = out * ds_std + ds_mean
+ * (float32, rounded one by one).  Per (sample, channel): the mean over H*W of (coarse_phys - f)^2, (cascade_phys - f)^2
+ * and (p - f)^2, f = (float)fine[t_fine], p = (float)fine[t_persist]; differences and squares in float32, the sum over
+ * the pixels in float64 (fixed chunks of pixels, then the chunks in a fixed order), divided by H*W.  state float64
+ * [AR,C,3] (gnn, cascade, persistence): state[step] += the samples' means one after the other in batch order, so that
+ * the batch size does not reach the bits; count int64 [AR]: count[step] += the samples scored.  A sample whose t_fine or
+ * t_persist is outside [0, T) is skipped.  ws: gcl_cascade_scores_ws_bytes(B, H, W, C) bytes, 8-byte aligned.
+ * Two launches. */
+size_t gcl_cascade_scores_ws_bytes(int32_t B, int32_t H, int32_t W, int32_t C);
+int gcl_cascade_scores(const float* out, const float* coarse_phys, const void* fine, int32_t T, int32_t n_feat,
+                       const int64_t* t_fine, const int64_t* t_persist, const float* ds_mean, const float* ds_std,
+                       double* state, int64_t* count, int32_t step, int32_t AR, int32_t B, int32_t H, int32_t W,
+                       int32_t C, void* ws, size_t ws_bytes, gcl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
