@@ -7,6 +7,8 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <type_traits>
+
 #include "../../include/gcl.h"
 
 namespace gcl {
@@ -64,6 +66,16 @@ inline bool env_is(const char* name, const char* value) {
   const char* e = getenv(name);
   return e && strcmp(e, value) == 0;
 }
+
+namespace plan {
+// Run-time value -> template constant: calls f(std::integral_constant<int, V>) for the V of Vs... equal to v.
+template <int... Vs, class F>
+int pick(int v, F&& f) {
+  int rc = GCL_EINVAL;
+  if (!((v == Vs && ((rc = f(std::integral_constant<int, Vs>{})), true)) || ...)) set_error("dispatch: no kernel for %d", v);
+  return rc;
+}
+}  // namespace plan
 
 constexpr int kWave = 64;     // CDNA wavefront
 constexpr int kNumXCD = 8;    // MI355X: 8 XCDs, blocks are dealt round-robin over them

@@ -17,6 +17,7 @@
 // Included by linear.hip (same translation unit: shares its launch plumbing).
 #pragma once
 #include "common.h"
+#include "dense_plan.h"
 #include "mfma_io.h"
 #include "x3.h"
 
@@ -26,10 +27,7 @@ enum { EPI_BIAS = 0, EPI_DX = 1 };
 #define GCL_ST_AUX 0  // cache-policy bits of the streamed-out stores (2 = nt)
 #endif
 
-constexpr int kGtTN = 128, kGtKC = 32, kGtKP = kGtKC + 2;
-// MI = 32-row MFMA tiles per wave: the block tile is (64*MI) x 128.  MI = 1 (64-row tiles) is used when
-// 128-row tiles would leave the persistent grid a short, badly balanced queue (a few hundred tiles).
-constexpr size_t gt_lds(int MI) { return (size_t)2 * (64 * MI + kGtTN) * kGtKP * sizeof(float); }
+// kGtTN / kGtKC / kGtKP, kX3KC / kX3RowB and the LDS sizes: dense_plan.h, with the launch geometry (plan_tile)
 
 // EPI_BIAS: akind/in_slope describe the activation applied to X on load.
 // EPI_DX  : X is dY (no activation), Wl = W^T (TRANS), akind/in_slope describe the activation whose
@@ -254,8 +252,6 @@ __global__ __launch_bounds__(256, (MI == 1 ? 3 : 2)) void gemm_tile_kernel(
 // and the five correction products are kept in two accumulators (see x3.h) and added in the epilogue.
 // EPI / activation / addend / Z semantics are those of gemm_tile_kernel; non-transposed weights only.
 // ---------------------------------------------------------------------------------------------
-constexpr int kX3KC = 16, kX3RowB = 48;
-constexpr size_t gtx3_lds() { return (size_t)2 * 3 * 256 * kX3RowB; }
 
 template <int EPI>
 __global__ __launch_bounds__(256, 2) void gemm_tile_x3_kernel(
@@ -427,30 +423,4 @@ __global__ __launch_bounds__(256, 2) void gemm_tile_x3_kernel(
     __syncthreads();
     if (tid == 0) slope_part[blockIdx.x] = (dred[0] + dred[1]) + (dred[2] + dred[3]);
   }
-}
-
-struct GtGeom {
-  int mi;
-  int nt;
-  int64_t total;
-  int per_xcd;
-  unsigned grid;
-};
-static inline GtGeom gt_geom(int64_t rows, int N) {
-  GtGeom g;
-  g.nt = (N + kGtTN - 1) / kGtTN;
-  // 128-row tiles unless they would give the 512 persistent blocks fewer than ~3 tiles each
-  g.mi = (gcl::cdiv(rows, 128) * g.nt < 3 * 2 * gcl::kNumCU) ? 1 : 2;  // env GCL_GT_MI overrides (experiments)
-  static const int force = gcl::env_int("GCL_GT_MI", 0);
-  if (force == 1 || force == 2) g.mi = force;
-  const int TM = 64 * g.mi;
-  g.total = gcl::cdiv(rows, TM) * g.nt;
-  // whole row tiles per XCD so that the column tiles of a row tile share an L2
-  const int64_t row_tiles_per_xcd = gcl::cdiv(gcl::cdiv(rows, TM), gcl::kNumXCD);
-  g.per_xcd = (int)(row_tiles_per_xcd * g.nt);
-  // persistent: the resident blocks per CU (LDS-limited: 2 at 128-row tiles, 3 at 64-row tiles)
-  const int cap = (g.mi == 1 ? 3 : 2) * gcl::kNumCU / gcl::kNumXCD;
-  const int slots = g.per_xcd < cap ? g.per_xcd : cap;
-  g.grid = (unsigned)(slots * gcl::kNumXCD);
-  return g;
 }

@@ -18,6 +18,7 @@
 namespace {
 
 using namespace gcl::mfma_io;  // f32x16, d_row, buffer loads / stores, zero4 (mfma_io.h)
+using namespace gcl::plan;     // the dispatch plans and the constants they share with the kernels (dense_plan.h)
 
 #include "gemm_tile.h"  // also EPI_BIAS / EPI_DX and GCL_ST_AUX
 
@@ -35,9 +36,7 @@ using namespace gcl::mfma_io;  // f32x16, d_row, buffer loads / stores, zero4 (m
 // activation applied) after it, so HBM latency hides under the matrix work instead of being paid
 // once per tile.  KT = compile-time bound on K (size of the prefetch register array).
 // ---------------------------------------------------------------------------------------------
-// waves per SIMD the register allocator must leave room for (LDS admits ~3 blocks of 4 waves at
-// K,N <= 64; wide panels are LDS-limited to 1-2 blocks anyway)
-constexpr int lin_min_waves(int NS, int KT) { return (NS <= 2 && KT <= 64) ? 3 : (NS <= 2 && KT <= 128) ? 2 : 1; }
+// (lin_min_waves, the waves per SIMD the register allocator must leave room for: dense_plan.h)
 // wide panels (NS >= 4) fill the LDS with one block per CU, i.e. one wave per SIMD: give those
 // instantiations the whole register file and fetch Z before the MFMA loop instead of after it
 constexpr bool lin_zpre(int NS, int EPI) { return EPI == 1 && NS >= 4; }
@@ -326,8 +325,7 @@ __global__ __launch_bounds__(256) void linear_valu_kernel(const float* __restric
 // (wo,wc) owns o-slabs {wo, wo+WO, ..} x c-slabs {wc, wc+WC, ..} (TO x TC accumulators), so no
 // cross-wave reduction is needed.  One partial tile set per block, reduced by reduce_parts_kernel.
 // ---------------------------------------------------------------------------------------------
-constexpr int kDwRT = 64;  // rows per step
-
+// (kDwRT = 64 rows per step: dense_plan.h)
 template <int NO, int NC>
 struct DwCfg {
   static constexpr int WO = NO >= 4 ? 4 : NO;         // waves along the output-channel slabs
@@ -916,11 +914,7 @@ __global__ void reduce_scalar_kernel(const double* __restrict__ part, int32_t np
 // every partial record starting at offset `poff[g]`; element e of it goes to out[g][(e / pld) * ldo
 // + e % pld] when (e % pld) < cols (partial tiles are padded to pld columns).  16 threads split
 // the partial records of one element, combined through LDS in a fixed order.
-struct RedSeg {
-  float* out;
-  int32_t poff, count, pld, cols, ldo;
-  int32_t acc;  // add into out (1) or overwrite it (0): every destination has its own flag
-};
+using RedSeg = gcl_reduce_seg;  // (acc: add into out (1) or overwrite it (0): every destination has its own flag)
 __global__ __launch_bounds__(256) void reduce_multi_kernel(const float* __restrict__ part, int32_t nparts,
                                                            int64_t pstride, RedSeg s0, RedSeg s1, RedSeg s2,
                                                            const double* __restrict__ spart, int32_t ns,
@@ -1087,6 +1081,7 @@ struct RedJobsK {
   int32_t n, sblk;  // sblk: 1 when block 0 is the scalar block (the body blocks follow it), else 0
 };
 static_assert(sizeof(RedJobsK) <= 4096, "the job table is passed by value: kernel arguments are limited to 4 KB");
+static_assert(sizeof(RedSeg) == 32, "gcl_reduce_seg (gcl.h) is the kernels' segment: three of them in the 144 bytes of a job");
 __global__ __launch_bounds__(256) void reduce_jobs_kernel(RedJobsK J) {
   const int blk = (int)blockIdx.x - J.sblk;
   if (blk < 0) {  // the extra block: scalar partials
@@ -1165,153 +1160,68 @@ int gcl_ablate() {  // GCL_ABLATE: timing-only experiments (tools/ablate.sh) - h
   return v;
 }
 
-bool use_valu() {
-  static const bool v = gcl::env_is("GCL_LINEAR_IMPL", "valu");
-  return v;
+// this translation unit's reader of the switches (dense_plan.h): the cached ones here, the per-call ones on first use
+DenseSwitches switches() {
+  static const bool valu = gcl::env_is("GCL_LINEAR_IMPL", "valu");
+  static const int gt_mi = gcl::env_int("GCL_GT_MI", 0);
+  DenseSwitches sw;
+  sw.valu = valu; sw.gt_mi = gt_mi;
+  return sw;
 }
 
-constexpr int kDwBlocks = 512;
-
-struct LinGeom {
-  int NS;
-  int waves;
-  int KT;
-  size_t lds;
-  int grid;
-};
-
-int lin_geom(int64_t rows, int K, int N, bool vec_x, LinGeom* g) {
-  GCL_CHECK_ARG(K >= 1 && K <= 256 && N >= 1 && N <= 256, "linear: unsupported K=%d N=%d (K<=256, N<=256)", K, N);
-  GCL_CHECK_ARG(vec_x || K <= 128, "linear: K=%d > 128 needs 16-B aligned rows (ld %% 4 == 0)", K);
-  g->NS = (N + 31) / 32;
-  if (g->NS == 3) g->NS = 4;
-  if (g->NS > 4) g->NS = 8;  // instantiated: 1,2,4,8
-  g->KT = K <= 64 ? 64 : K <= 128 ? 128 : 256;
-  const int KP = ((K + 3) & ~3) + 2;
-  g->waves = 4;
-  g->lds = ((size_t)g->NS * 32 + 128) * KP * sizeof(float) + 64;
-  if (g->lds > gcl::kLdsBytes) {  // wide panels: 64-row tiles (2 waves) keep the weight panel resident
-    g->waves = 2;
-    g->lds = ((size_t)g->NS * 32 + 64) * KP * sizeof(float) + 64;
-  }
-  GCL_CHECK_ARG(g->lds <= gcl::kLdsBytes, "linear: K=%d N=%d needs %zu B of LDS (>160 KiB)", K, N, g->lds);
-  // persistent grid = what is resident at once (LDS- and register-limited), so no partial last wave
-  int bpc = (int)(gcl::kLdsBytes / g->lds);
-  const int by_regs = lin_min_waves(g->NS, g->KT) * 4 / g->waves;
-  if (bpc > by_regs) bpc = by_regs;
-  if (bpc < 1) bpc = 1;
-  const int64_t ntiles = gcl::cdiv(rows, 32 * g->waves);
-  const int64_t cap = (int64_t)gcl::kNumCU * bpc;
-  g->grid = (int)(ntiles < cap ? ntiles : cap);
+template <int EPI>
+int launch_valu(const float* X, int64_t ldx, const float* in_slope, const float* W, int ldw, int trans, const float* bias,
+                float* Y, int64_t ldy, int64_t rows, int K, int N, const float* Z, int64_t ldz, const float* z_slope,
+                double* slope_part, int* nparts, hipStream_t st, int akind) {
+  const int grid = (int)gcl::grid_for(rows * N, kValuGridCap);
+  hipLaunchKernelGGL((linear_valu_kernel<EPI>), dim3(grid), dim3(256), 0, st, X, ldx, in_slope, W, ldw, trans, bias, Y,
+                     ldy, rows, K, N, Z, ldz, z_slope, slope_part, akind);
+  GCL_CHECK_LAUNCH();
+  if (nparts) *nparts = grid;
   return GCL_OK;
 }
 
 template <int EPI>
-int launch_linear(const float* X, int64_t ldx, const float* in_slope, const float* W, int ldw, int trans,
-                  const float* bias, float* Y, int64_t ldy, int64_t rows, int K, int N, const float* Z, int64_t ldz,
-                  const float* z_slope, double* slope_part, int* nparts, hipStream_t st, int akind) {
-  if (rows == 0) {
-    if (nparts) *nparts = 0;
-    return GCL_OK;
-  }
-  if (use_valu()) {
-    const int64_t total = rows * N;
-    int grid = (int)(gcl::cdiv(total, 256) < 4096 ? gcl::cdiv(total, 256) : 4096);
-    hipLaunchKernelGGL((linear_valu_kernel<EPI>), dim3(grid), dim3(256), 0, st, X, ldx, in_slope, W, ldw, trans,
-                       bias, Y, ldy, rows, K, N, Z, ldz, z_slope, slope_part, akind);
-    GCL_CHECK_LAUNCH();
-    if (nparts) *nparts = grid;
-    return GCL_OK;
-  }
-  const int vec_x = (K % 4 == 0) && (ldx % 4 == 0) && gcl::aligned16(X);
-  LinGeom g;
-  int rc = lin_geom(rows, K, N, vec_x != 0, &g);
+int launch_linear(const PanelPlan& g, const float* X, int64_t ldx, const float* in_slope, const float* W, int ldw,
+                  int trans, const float* bias, float* Y, int64_t ldy, int64_t rows, int K, int N, const float* Z,
+                  int64_t ldz, const float* z_slope, double* slope_part, int* nparts, hipStream_t st, int akind) {
+  GCL_CHECK_ARG(g.range_ok, "linear: unsupported K=%d N=%d (K<=256, N<=256)", K, N);
+  GCL_CHECK_ARG(g.vec_ok, "linear: K=%d > 128 needs 16-B aligned rows (ld %% 4 == 0)", K);
+  GCL_CHECK_ARG(g.valid(), "linear: K=%d N=%d needs %zu B of LDS (>160 KiB)", K, N, g.lds);
+  // <KT, VEC>: (64, t) (64, f) (128, t) (128, f) (256, t) - K > 128 has 16-byte rows (vec_ok)
+  const int rc = pick<1, 2, 4, 8>(g.NS, [&](auto NS) {
+    return pick<0, 1, 2, 3, 4>(g.KT == 256 ? 4 : (g.KT == 128 ? 2 : 0) + (g.vec ? 0 : 1), [&](auto KV) {
+      constexpr int kv = decltype(KV)::value;
+      auto kern = linear_mfma_kernel<decltype(NS)::value, EPI, kv == 4 ? 256 : kv >= 2 ? 128 : 64, kv == 4 || !(kv & 1)>;
+      GCL_ENSURE_DYN_LDS(kern, gcl::kLdsBytes);
+      hipLaunchKernelGGL(kern, dim3(g.grid), dim3(g.waves * 64), g.lds, st, X, ldx, in_slope, W, ldw, trans, bias, Y, ldy,
+                         rows, K, N, Z, ldz, z_slope, slope_part, akind, gcl_ablate());
+      return (int)GCL_OK;
+    });
+  });
   if (rc) return rc;
-#define GCL_LIN3(NS_, KT_, V_)                                                                                    \
-  do {                                                                                                            \
-    auto kern = linear_mfma_kernel<NS_, EPI, KT_, V_>;                                                            \
-    GCL_ENSURE_DYN_LDS(kern, gcl::kLdsBytes);                                                                     \
-    hipLaunchKernelGGL(kern, dim3(g.grid), dim3(g.waves * 64), g.lds, st, X, ldx, in_slope, W, ldw, trans, bias,  \
-                       Y, ldy, rows, K, N, Z, ldz, z_slope, slope_part, akind, gcl_ablate());                     \
-  } while (0)
-#define GCL_LIN2(NS_, KT_)                 \
-  do {                                     \
-    if (vec_x) GCL_LIN3(NS_, KT_, true);   \
-    else GCL_LIN3(NS_, KT_, false);        \
-  } while (0)
-#define GCL_LIN(NS_)                                \
-  do {                                              \
-    if (g.KT == 64) GCL_LIN2(NS_, 64);              \
-    else if (g.KT == 128) GCL_LIN2(NS_, 128);       \
-    else GCL_LIN3(NS_, 256, true);                  \
-  } while (0)
-  switch (g.NS) {
-    case 1: GCL_LIN(1); break;
-    case 2: GCL_LIN(2); break;
-    case 4: GCL_LIN(4); break;
-    default: GCL_LIN(8); break;
-  }
-#undef GCL_LIN3
-#undef GCL_LIN
-#undef GCL_LIN2
   GCL_CHECK_LAUNCH();
   if (nparts) *nparts = g.grid;
   return GCL_OK;
 }
 
-// does the resident-panel kernel take this shape?
-// K: contraction length, N: output width.  Measured on MI355X (tools/gemm_bench.py): the 128x128
-// tile kernel wins once the contraction is long or the output fills its 128 columns.
-bool panel_fits(int K, int N, bool vec_x, bool trans, bool w_ok) {
-  // read per call (the dispatch tests switch it)
-  const int impl = gcl::env_is("GCL_DENSE_IMPL", "tile") ? 1 : gcl::env_is("GCL_DENSE_IMPL", "panel") ? 2 : 0;
-  const bool tile_ok = vec_x && w_ok && K % 4 == 0 && N % 4 == 0;
-  if (impl == 1 && tile_ok) return false;
-  if (impl == 0 && tile_ok && (K > 128 || (N >= 128 && (K >= 128 || trans)))) return false;
-  if (K < 1 || K > 256 || N < 1 || N > 256) return false;
-  if (!vec_x && K > 128) return false;
-  int NS = (N + 31) / 32;
-  if (NS == 3) NS = 4;
-  if (NS > 4) NS = 8;
-  const int KP = ((K + 3) & ~3) + 2;
-  return ((size_t)NS * 32 + 64) * KP * sizeof(float) + 64 <= gcl::kLdsBytes;
-}
-
 template <int EPI>
-int launch_gemm(const float* X, int64_t ldx, int akind, const float* slope, const float* W, int64_t ldw, int trans,
+int launch_gemm(const DensePlan& p, const float* X, int64_t ldx, int akind, const float* slope, const float* W, int64_t ldw,
                 const float* bias, float* Y, int64_t ldy, int64_t rows, int K, int N, const float* Z, int64_t ldz,
                 const float* add, int64_t ldadd, double* slope_part, int* nparts, hipStream_t st) {
-  if (nparts) *nparts = 0;
-  if (rows == 0) return GCL_OK;
+  const TilePlan& g = p.tile;
   GCL_CHECK_ARG((K % 4 == 0) && (ldx % 4 == 0) && gcl::aligned16(X), "dense: wide shapes need K %% 4 == 0 and 16-B aligned rows (K=%d ldx=%lld)", K, (long long)ldx);
-  GCL_CHECK_ARG((ldw % 4 == 0) && gcl::aligned16(W) && (!trans || N % 4 == 0), "dense: wide shapes need a 16-B aligned weight block (ldw=%lld N=%d)", (long long)ldw, N);
-  GtGeom g = gt_geom(rows, N);
-  // split-operand bf16 variant (gemm_tile_x3_kernel): non-transposed weights, 128-row tiles
-  const int x3_tile = gcl::env_int("GCL_X3", 1) != 0 && gcl::env_int("GCL_X3_TILE", 1) != 0;  // read per call
-  if (x3_tile && !trans && g.mi == 2) {
-    auto kern = gemm_tile_x3_kernel<EPI>;
+  GCL_CHECK_ARG((ldw % 4 == 0) && gcl::aligned16(W) && (!p.trans || N % 4 == 0), "dense: wide shapes need a 16-B aligned weight block (ldw=%lld N=%d)", (long long)ldw, N);
+  auto go = [&](auto kern) {
     GCL_ENSURE_DYN_LDS(kern, gcl::kLdsBytes);
-    hipLaunchKernelGGL(kern, dim3(g.grid), dim3(256), gtx3_lds(), st, X, ldx, akind, slope, W, ldw, bias, Y, ldy, rows, K, N,
+    hipLaunchKernelGGL(kern, dim3(g.grid), dim3(256), p.tile_lds, st, X, ldx, akind, slope, W, ldw, bias, Y, ldy, rows, K, N,
                        Z, ldz, add, ldadd, slope_part, g.nt, g.total, g.per_xcd);
-    GCL_CHECK_LAUNCH();
-    if (nparts) *nparts = (int)g.grid;
-    return GCL_OK;
-  }
-#define GCL_GT(T_, MI_)                                                                                           \
-  do {                                                                                                            \
-    auto kern = gemm_tile_kernel<EPI, T_, MI_>;                                                                   \
-    GCL_ENSURE_DYN_LDS(kern, gcl::kLdsBytes);                                                                     \
-    hipLaunchKernelGGL(kern, dim3(g.grid), dim3(256), gt_lds(MI_), st, X, ldx, akind, slope, W, ldw, bias, Y, ldy, \
-                       rows, K, N, Z, ldz, add, ldadd, slope_part, g.nt, g.total, g.per_xcd);                     \
-  } while (0)
-  if (trans) {
-    if (g.mi == 1) GCL_GT(true, 1);
-    else GCL_GT(true, 2);
-  } else {
-    if (g.mi == 1) GCL_GT(false, 1);
-    else GCL_GT(false, 2);
-  }
-#undef GCL_GT
+    return (int)GCL_OK;
+  };
+  const int rc = p.form == DenseForm::kTileX3 ? go(gemm_tile_x3_kernel<EPI>) : pick<0, 1>(p.trans, [&](auto T) {
+    return pick<1, 2>(g.mi, [&](auto MI) { return go(gemm_tile_kernel<EPI, decltype(T)::value != 0, decltype(MI)::value>); });
+  });
+  if (rc) return rc;
   GCL_CHECK_LAUNCH();
   if (nparts) *nparts = (int)g.grid;
   return GCL_OK;
@@ -1336,15 +1246,23 @@ extern "C" int gcl_dense_fwd(const float* x, int64_t ldx, int32_t act, const flo
                 "dense_fwd: bad shape rows=%lld ldx=%lld ldy=%lld ldw=%lld", (long long)rows, (long long)ldx,
                 (long long)ldy, (long long)ldw);
   if (int rc = check_act("dense_fwd", act, slope)) return rc;
-  const bool vec_x = (Fin % 4 == 0) && (ldx % 4 == 0) && gcl::aligned16(x);
-  if (!addend && ldw == Fin && !use_valu() && gcl::x3_linear_fwd_applicable(x, ldx, y, ldy, Fin, Fout, act))
-    return gcl::x3_linear_fwd(x, ldx, act, act == GCL_ACT_PRELU ? slope : nullptr, W, bias, y, ldy, rows, Fin, Fout,
-                              (hipStream_t)stream);
-  if (!addend && ldw == Fin && (use_valu() || panel_fits(Fin, Fout, vec_x, false, (ldw % 4 == 0) && gcl::aligned16(W))))
-    return launch_linear<EPI_BIAS>(x, ldx, act == GCL_ACT_PRELU ? slope : nullptr, W, Fin, 0, bias, y, ldy, rows, Fin,
-                                   Fout, nullptr, 0, nullptr, nullptr, nullptr, (hipStream_t)stream, act);
-  return launch_gemm<EPI_BIAS>(x, ldx, act, act == GCL_ACT_PRELU ? slope : nullptr, W, ldw, 0, bias, y, ldy, rows, Fin,
-                               Fout, nullptr, 0, addend, ldadd, nullptr, nullptr, (hipStream_t)stream);
+  const DenseCall c{rows, Fin, Fout, !addend && ldw == Fin, (Fin % 4 == 0) && (ldx % 4 == 0) && gcl::aligned16(x),
+                    (ldw % 4 == 0) && gcl::aligned16(W)};
+  const DensePlan p = plan_dense_fwd(c, ldx, ldy, gcl::aligned16(x), gcl::aligned16(y), act, switches());
+  hipStream_t st = (hipStream_t)stream;
+  const float* sl = act == GCL_ACT_PRELU ? slope : nullptr;
+  if (rows == 0) return GCL_OK;
+  switch (p.form) {
+    case DenseForm::kX3: return gcl::x3_linear_fwd(p.x3, x, ldx, act, sl, W, bias, y, ldy, rows, Fin, Fout, st);
+    case DenseForm::kValu:
+      return launch_valu<EPI_BIAS>(x, ldx, sl, W, Fin, 0, bias, y, ldy, rows, Fin, Fout, nullptr, 0, nullptr, nullptr, nullptr, st, act);
+    case DenseForm::kPanel:
+      return launch_linear<EPI_BIAS>(p.panel, x, ldx, sl, W, Fin, 0, bias, y, ldy, rows, Fin, Fout, nullptr, 0, nullptr, nullptr,
+                                     nullptr, st, act);
+    default:
+      return launch_gemm<EPI_BIAS>(p, x, ldx, act, sl, W, ldw, bias, y, ldy, rows, Fin, Fout, nullptr, 0, addend, ldadd, nullptr,
+                                   nullptr, st);
+  }
 }
 
 extern "C" int gcl_linear_fwd(const float* x, int64_t ldx, const float* in_slope, const float* W, const float* bias,
@@ -1353,22 +1271,8 @@ extern "C" int gcl_linear_fwd(const float* x, int64_t ldx, const float* in_slope
                        Fin, Fout, stream);
 }
 
-// slope partials: one double per block of the dx kernel (the tiled kernel launches a block per tile)
-static size_t slope_parts_cap(int64_t rows, int32_t Fin) {
-  const int64_t g = (int64_t)gt_geom(rows, Fin).grid;
-  return (size_t)(g > 4096 ? g : 4096);
-}
-
 extern "C" size_t gcl_linear_bwd_ws_bytes(int64_t rows, int32_t Fin, int32_t Fout) {
-  size_t nc = (size_t)(Fin + 31) / 32;
-  if (nc > 4) nc = 4;  // wider inputs are walked in 128-column chunks
-  const size_t FinP = nc * 32;
-  size_t no = (size_t)(Fout + 31) / 32;
-  no = no <= 2 ? no : no <= 4 ? 4 : 8;
-  const size_t FoutP = no * 32;
-  const size_t dw = (size_t)kDwBlocks * FoutP * (FinP + 1) * sizeof(float);
-  const size_t sl = slope_parts_cap(rows, Fin) * sizeof(double);
-  return dw + sl;
+  return dense_bwd_ws_bytes(rows, Fin, Fout, switches());
 }
 
 extern "C" int gcl_dense_bwd_dx(const float* dy, int64_t lddy, const float* W, int64_t ldw, const float* z, int64_t ldz,
@@ -1381,33 +1285,31 @@ extern "C" int gcl_dense_bwd_dx(const float* dy, int64_t lddy, const float* W, i
   GCL_CHECK_ARG(act == GCL_ACT_NONE || (z && ldz >= Fin), "dense_bwd_dx: activation given without its pre-activation z");
   hipStream_t st = (hipStream_t)stream;
   const float* sl = act == GCL_ACT_PRELU ? slope : nullptr;
+  const DenseCall c{rows, Fout, Fin, !addend && ldw == Fin, (Fout % 4 == 0) && (lddy % 4 == 0) && gcl::aligned16(dy),
+                    (ldw % 4 == 0) && gcl::aligned16(W)};
+  const DensePlan p = plan_dense_bwd_dx(c, ws ? ws_bytes : 0, gcl::aligned16(ws), switches());
   double* slope_part = nullptr;
   if (sl && d_slope) {
-    GCL_CHECK_ARG(ws && ws_bytes >= slope_parts_cap(rows, Fin) * sizeof(double) && gcl::aligned16(ws), "dense_bwd_dx: workspace too small");
+    GCL_CHECK_ARG(ws && ws_bytes >= p.slope_cap * sizeof(double) && gcl::aligned16(ws), "dense_bwd_dx: workspace too small");
     slope_part = (double*)ws;
   }
+  if (rows == 0) return GCL_OK;
   int nparts = 0, rc;
   const float* zz = act == GCL_ACT_NONE ? nullptr : z;
-  const bool vec_x = (Fout % 4 == 0) && (lddy % 4 == 0) && gcl::aligned16(dy);
-  // contraction over Fout: "weights" are W^T, i.e. Wl[j=c][k=o] = W[o*ldw + c]
-  if (!addend && ldw == Fin && (use_valu() || panel_fits(Fout, Fin, vec_x, true, (ldw % 4 == 0) && gcl::aligned16(W))))
-    rc = launch_linear<EPI_DX>(dy, lddy, nullptr, W, Fin, 1, nullptr, dx, lddx, rows, Fout, Fin, zz, ldz, sl, slope_part,
+  if (p.form == DenseForm::kValu) {
+    rc = launch_valu<EPI_DX>(dy, lddy, nullptr, W, Fin, 1, nullptr, dx, lddx, rows, Fout, Fin, zz, ldz, sl, slope_part, &nparts, st, act);
+  } else if (p.form == DenseForm::kPanel) {
+    rc = launch_linear<EPI_DX>(p.panel, dy, lddy, nullptr, W, Fin, 1, nullptr, dx, lddx, rows, Fout, Fin, zz, ldz, sl, slope_part,
                                &nparts, st, act);
-  else {
-    // the tile kernel stages k-contiguous weight rows twice as cheaply as strided ones: transpose W
-    // (a few hundred KB) into the workspace first when there is room
-    const size_t off = (slope_parts_cap(rows, Fin) * sizeof(double) + 255) & ~(size_t)255;
-    const size_t need = off + (size_t)Fin * Fout * sizeof(float);
-    if (ws && ws_bytes >= need && gcl::aligned16(ws) && Fout % 4 == 0 && rows >= 4096) {
-      float* Wt = reinterpret_cast<float*>(static_cast<char*>(ws) + off);
-      hipLaunchKernelGGL(transpose_kernel, dim3((unsigned)gcl::cdiv(Fin, 32), (unsigned)gcl::cdiv(Fout, 32)), dim3(256), 0,
-                         st, W, ldw, Wt, Fout, Fin);
-      rc = launch_gemm<EPI_DX>(dy, lddy, act, sl, Wt, Fout, 0, nullptr, dx, lddx, rows, Fout, Fin, zz, ldz, addend,
-                               ldadd, slope_part, &nparts, st);
-    } else {
-      rc = launch_gemm<EPI_DX>(dy, lddy, act, sl, W, ldw, 1, nullptr, dx, lddx, rows, Fout, Fin, zz, ldz, addend, ldadd,
-                               slope_part, &nparts, st);
-    }
+  } else if (p.transpose_first) {
+    float* Wt = reinterpret_cast<float*>(static_cast<char*>(ws) + p.wt_off_bytes);
+    hipLaunchKernelGGL(transpose_kernel, dim3((unsigned)gcl::cdiv(Fin, 32), (unsigned)gcl::cdiv(Fout, 32)), dim3(256), 0, st,
+                       W, ldw, Wt, Fout, Fin);
+    rc = launch_gemm<EPI_DX>(p, dy, lddy, act, sl, Wt, Fout, nullptr, dx, lddx, rows, Fout, Fin, zz, ldz, addend, ldadd,
+                             slope_part, &nparts, st);
+  } else {
+    rc = launch_gemm<EPI_DX>(p, dy, lddy, act, sl, W, ldw, nullptr, dx, lddx, rows, Fout, Fin, zz, ldz, addend, ldadd,
+                             slope_part, &nparts, st);
   }
   if (rc) return rc;
   if (slope_part && nparts > 0) {
@@ -1430,103 +1332,55 @@ extern "C" int gcl_linear_bwd_dx(const float* dy, int64_t lddy, const float* W, 
 static int dw_block(const float* dy, int64_t lddy, const float* x, int64_t ldx, int akind, const float* in_slope,
                     float* dW, int64_t lddw, float* db, int64_t rows, int32_t Fin, int32_t Fout, int32_t accumulate,
                     void* ws, hipStream_t st, gcl_reduce_job* job = nullptr) {
-  const int nct = (Fin + 127) / 128;                      // input chunks
-  const int NC = nct > 1 ? 4 : (Fin + 31) / 32;           // slabs of the (widest) chunk
-  int NO = (Fout + 31) / 32;
-  NO = NO <= 2 ? NO : NO <= 4 ? 4 : 8;  // instantiated: 1, 2, 4, 8 (extra slabs are zero)
-  const int FinP = NC * 32, FoutP = NO * 32;
-  const size_t lds = (size_t)kDwRT * (FoutP + FinP) * sizeof(float);
-  // one partial tile per block: no more blocks than are resident at once (wide tiles fill the LDS
-  // with one block per CU, and their partials are what the reduction then has to read back), and
-  // at least four 64-row steps per block so the load pipeline has something to hide under
-  const int64_t cap = (lds > 80 * 1024 ? gcl::kNumCU : kDwBlocks) / nct;
-  int64_t nblk = gcl::cdiv(rows, (nct > 1 ? 4 : 2) * kDwRT);
-  if (nblk > cap) nblk = cap;
-  if (nblk < 1) nblk = 1;
-  int64_t rpb = gcl::cdiv(rows, nblk);
-  rpb = gcl::cdiv(rpb, kDwRT) * kDwRT;
-  nblk = rows > 0 ? gcl::cdiv(rows, rpb) : 1;
-  float* part = (float*)ws;
-  float* dbpart = part + (size_t)kDwBlocks * FoutP * FinP;
-  const int64_t tile_stride = (int64_t)nblk * FoutP * FinP;
-  const bool vec = (lddy % 4 == 0) && (ldx % 4 == 0) && gcl::aligned16(dy) && gcl::aligned16(x);
-#define GCL_DW3(NO_, NC_, V_)                                                                                     \
-  do {                                                                                                            \
-    auto kern = dw_mfma_kernel<NO_, NC_, V_>;                                                                     \
-    GCL_ENSURE_DYN_LDS(kern, gcl::kLdsBytes);                                                                     \
-    hipLaunchKernelGGL(kern, dim3((unsigned)nblk, (unsigned)nct), dim3(256), lds, st, dy, lddy, x, ldx, in_slope, part, \
-                       db ? dbpart : nullptr, rows, Fin, Fout, rpb, akind, tile_stride);                          \
-  } while (0)
-#define GCL_DW2(NO_, NC_)              \
-  do {                                 \
-    if (vec) GCL_DW3(NO_, NC_, true);  \
-    else GCL_DW3(NO_, NC_, false);     \
-  } while (0)
-#define GCL_DW(NO_)                    \
-  do {                                 \
-    switch (NC) {                      \
-      case 1: GCL_DW2(NO_, 1); break;  \
-      case 2: GCL_DW2(NO_, 2); break;  \
-      case 3: GCL_DW2(NO_, 3); break;  \
-      default: GCL_DW2(NO_, 4); break; \
-    }                                  \
-  } while (0)
-  switch (NO) {
-    case 1: GCL_DW(1); break;
-    case 2: GCL_DW(2); break;
-    case 4: GCL_DW(4); break;
-    default: GCL_DW(8); break;
-  }
-#undef GCL_DW
-#undef GCL_DW2
-#undef GCL_DW3
+  const DwPlan p = plan_dw(rows, Fin, Fout, (lddy % 4 == 0) && (ldx % 4 == 0) && gcl::aligned16(dy) && gcl::aligned16(x));
+  float* part = (float*)ws + p.part_off;
+  float* dbpart = (float*)ws + p.dbpart_off;
+  int rc = pick<1, 2, 4, 8>(p.NO, [&](auto NO) {
+    return pick<1, 2, 3, 4>(p.NC, [&](auto NC) {
+      return pick<0, 1>(p.vec, [&](auto V) {
+        auto kern = dw_mfma_kernel<decltype(NO)::value, decltype(NC)::value, decltype(V)::value != 0>;
+        GCL_ENSURE_DYN_LDS(kern, gcl::kLdsBytes);
+        hipLaunchKernelGGL(kern, dim3((unsigned)p.nblk, (unsigned)p.nct), dim3(256), p.lds, st, dy, lddy, x, ldx, in_slope, part,
+                           db ? dbpart : nullptr, rows, Fin, Fout, p.rpb, akind, p.tile_stride);
+        return (int)GCL_OK;
+      });
+    });
+  });
+  if (rc) return rc;
   GCL_CHECK_LAUNCH();
+  // input chunk c: its records start c * tile_stride floats into `part`
+  auto chunk = [&](int c) {
+    return RedSeg{dW + c * 128, (int32_t)(c * p.tile_stride), Fout * p.FinP, p.FinP, std::min(Fin - c * 128, 128), (int32_t)lddw,
+                  accumulate ? 1 : 0};
+  };
   // deferred (job[0]: the dW tiles, job[1]: db - they are two partial buffers): only when the immediate passes below
   // are ONE launch for dW and both take the 16-byte reducer, which is the only one the queue has
-  const bool defer = job && nct <= 3 && nblk >= 64 && gcl::aligned16(part) && gcl::aligned16(dbpart) &&
-                     tile_stride % 4 == 0 && 2 * tile_stride < ((int64_t)1 << 31);
-  if (defer) {
+  if (job && p.may_defer && gcl::aligned16(part) && gcl::aligned16(dbpart)) {
     job[0].part = part;
-    job[0].pstride = (int64_t)FoutP * FinP;
-    job[0].nparts = (int32_t)nblk;
-    for (int c = 0; c < nct; ++c) {
-      const int fi = Fin - c * 128 < 128 ? Fin - c * 128 : 128;
-      job[0].seg[c].out = dW + c * 128;
-      job[0].seg[c].poff = (int32_t)(c * tile_stride);
-      job[0].seg[c].count = Fout * FinP;
-      job[0].seg[c].pld = FinP;
-      job[0].seg[c].cols = fi;
-      job[0].seg[c].ldo = (int32_t)lddw;
-      job[0].seg[c].acc = accumulate ? 1 : 0;
-    }
+    job[0].pstride = p.rec;
+    job[0].nparts = (int32_t)p.nblk;
+    for (int c = 0; c < p.nct; ++c) job[0].seg[c] = chunk(c);
     if (db) {
       job[1].part = dbpart;
-      job[1].pstride = FoutP;
-      job[1].nparts = (int32_t)nblk;
-      job[1].seg[0].out = db;
-      job[1].seg[0].poff = 0;
-      job[1].seg[0].count = FoutP;
-      job[1].seg[0].pld = FoutP;
-      job[1].seg[0].cols = Fout;
-      job[1].seg[0].ldo = Fout;
-      job[1].seg[0].acc = accumulate ? 1 : 0;
+      job[1].pstride = p.FoutP;
+      job[1].nparts = (int32_t)p.nblk;
+      job[1].seg[0] = RedSeg{db, 0, p.FoutP, p.FoutP, Fout, Fout, accumulate ? 1 : 0};
     }
     return GCL_OK;
   }
-  // final pass: the input chunks of a wide layer three to a launch (one segment each: chunk ct's records start
-  // ct * tile_stride floats into the workspace) - a 256-wide layer used to end in two of these launches per call
-  for (int ct = 0; ct < nct; ct += 3) {
-    RedSeg seg[3] = {{nullptr, 0, 0, 1, 0, 0, 0}, {nullptr, 0, 0, 1, 0, 0, 0}, {nullptr, 0, 0, 1, 0, 0, 0}};
-    for (int q = 0; q < 3 && ct + q < nct; ++q) {
-      const int c = ct + q;
-      const int fi = Fin - c * 128 < 128 ? Fin - c * 128 : 128;
-      GCL_CHECK_ARG((int64_t)c * tile_stride < ((int64_t)1 << 31), "dense_bwd_dw: partial workspace offset overflows");
-      seg[q] = RedSeg{dW + c * 128, (int32_t)(c * tile_stride), Fout * FinP, FinP, fi, (int32_t)lddw, accumulate};
+  // final pass: the input chunks of a wide layer three to a launch (one segment each) - a 256-wide layer used to end
+  // in two of these launches per call
+  const RedSeg none{nullptr, 0, 0, 1, 0, 0, 0};
+  for (int ct = 0; ct < p.nct; ct += 3) {
+    RedSeg seg[3] = {none, none, none};
+    for (int q = 0; q < 3 && ct + q < p.nct; ++q) {
+      GCL_CHECK_ARG(below_2_31((ct + q) * p.tile_stride), "dense_bwd_dw: partial workspace offset overflows");
+      seg[q] = chunk(ct + q);
     }
-    launch_reduce_multi(part, (int)nblk, (int64_t)FoutP * FinP, seg[0], seg[1], seg[2], st);
+    launch_reduce_multi(part, (int)p.nblk, p.rec, seg[0], seg[1], seg[2], st);
     GCL_CHECK_LAUNCH();
   }
-  if (db) return gcl::launch_reduce_parts(dbpart, (int)nblk, (int64_t)FoutP, FoutP, db, Fout, 1, Fout, accumulate, st);
+  if (db) return gcl::launch_reduce_parts(dbpart, (int)p.nblk, (int64_t)p.FoutP, p.FoutP, db, Fout, 1, Fout, accumulate, st);
   return GCL_OK;
 }
 
@@ -1585,24 +1439,9 @@ extern "C" int gcl_linear_bwd_dw(const float* dy, int64_t lddy, const float* x, 
                           Fout, accumulate, ws, ws_bytes, stream);
 }
 
-// Fused path geometry / workspace (see linear_bwd_fused_kernel)
-static bool fused_ok(const float* dy, int64_t lddy, const float* x, int64_t ldx, const float* dx, int64_t lddx,
-                     int32_t Fin, int32_t Fout) {
-  const int off = gcl::env_int("GCL_NO_FUSED_BWD", 0) != 0;  // read per call (the dispatch tests switch it)
-  if (off || use_valu()) return false;
-  // Fout need not be a multiple of 4 when the rows of dy are padded to one (lddy >= roundup(Fout, 4)): the 16-byte
-  // loads then also fetch the padding columns, which meet zero weight rows (they must hold finite values)
-  return Fout <= 64 && Fin <= 96 && (lddy >= ((Fout + 3) & ~3)) && (Fin % 4 == 0) && (lddy % 4 == 0) && (ldx % 4 == 0) &&
-         (lddx >= Fin) && gcl::aligned16(dy) && gcl::aligned16(x) && dx != nullptr;
-}
-
+// the fused form's records, or what the separate kernels (dW + dx, then the column sums) need of the same buffer
 extern "C" size_t gcl_linear_bwd_all_ws_bytes(int64_t rows, int32_t Fin, int32_t Fout) {
-  const size_t FiP = (size_t)((Fin + 31) / 32) * 32, FoP = (size_t)((Fout + 31) / 32) * 32;
-  const size_t fused = (size_t)3 * gcl::kNumCU * (FoP * FiP + FoP + FiP) * sizeof(float) + (size_t)3 * gcl::kNumCU * 8 + 64;
-  size_t sep = gcl_linear_bwd_ws_bytes(rows, Fin, Fout);
-  const size_t cs = gcl_colsum_ws_bytes(rows, Fin);
-  if (cs > sep) sep = cs;
-  return fused > sep ? fused : sep;
+  return std::max({fused_layout(Fin, Fout).bytes, gcl_linear_bwd_ws_bytes(rows, Fin, Fout), gcl_colsum_ws_bytes(rows, Fin)});
 }
 
 static int bwd_all_impl(const float* dy, int64_t lddy, const float* W, const float* x, int64_t ldx,
@@ -1617,7 +1456,10 @@ static int bwd_all_impl(const float* dy, int64_t lddy, const float* W, const flo
   // parameters (colsum_dx is the bias gradient of the layer below) with different .grad states
   const int acc_dw = (accumulate & GCL_ACC_DW) ? 1 : 0, acc_db = (accumulate & GCL_ACC_DB) ? 1 : 0,
             acc_cs = (accumulate & GCL_ACC_COLSUM) ? 1 : 0;
-  if (!fused_ok(dy, lddy, x, ldx, dx, lddx, Fin, Fout) || rows == 0) {
+  const BwdAllCall c{rows, lddy, ldx, lddx, Fin, Fout, gcl::aligned16(dy), gcl::aligned16(x), gcl::aligned16(dx), dx != nullptr,
+                     in_slope != nullptr, db != nullptr, colsum_dx != nullptr};
+  const BwdAllPlan p = plan_bwd_all(c, switches());
+  if (p.form == BwdAllForm::kSeparate) {
     int rc;
     if (db && acc_db != acc_dw) {  // separate kernels share one flag between dW and db: split the call
       rc = gcl_linear_bwd_dw(dy, lddy, x, ldx, in_slope, dW, nullptr, rows, Fin, Fout, acc_dw, ws, ws_bytes, stream);
@@ -1633,89 +1475,49 @@ static int bwd_all_impl(const float* dy, int64_t lddy, const float* W, const flo
     if (colsum_dx) rc = gcl_colsum(dx, lddx, rows, Fin, colsum_dx, acc_cs, ws, ws_bytes, stream);
     return rc;  // (nothing deferred: job stays empty)
   }
-  const int NO = (Fout + 31) / 32, NC = (Fin + 31) / 32;
-  const int FoP = NO * 32, FiP = NC * 32;
-  const int no64 = gcl::env_int("GCL_NO_FUSED64", 0) != 0;  // read per call
-  const bool use64 = (NC == 2) && !no64;  // 64-row tiles, 3 blocks per CU
-  // split-operand bf16 kernel (x3.h): same partial records, two blocks per CU
-  const bool use_x3 = use64 && gcl::x3_linear_bwd_applicable(dy, lddy, x, ldx, dx, lddx, Fin, Fout);
-  const int64_t ntiles = gcl::cdiv(rows, use64 ? 64 : 128);
-  const int64_t cap = use64 ? 3 * gcl::kNumCU : gcl::kNumCU;
-  const int nblk = use_x3 ? gcl::x3_linear_bwd_blocks(rows) : (int)(ntiles < cap ? ntiles : cap);
-  const size_t rec_f = (size_t)FoP * FiP + FoP + FiP;  // floats per block record
   float* part_dw = (float*)ws;
-  float* part_db = part_dw + (size_t)FoP * FiP;
-  float* part_cs = part_db + FoP;
-  double* part_sl = (double*)(((uintptr_t)(part_dw + (size_t)3 * gcl::kNumCU * rec_f) + 15) & ~(uintptr_t)15);
+  float* part_db = db ? part_dw + p.db_off : nullptr;
+  float* part_cs = colsum_dx ? part_dw + p.cs_off : nullptr;
   const bool want_slope = in_slope && d_in_slope;
-  if (use_x3) {
-    if (int rc = gcl::x3_linear_bwd(dy, lddy, W, x, ldx, in_slope, dx, lddx, rows, Fin, Fout, part_dw, db ? part_db : nullptr,
-                                    colsum_dx ? part_cs : nullptr, want_slope ? part_sl : nullptr, st))
-      return rc;
-  } else if (use64) {
-    const size_t lds64 = ((size_t)FiP * (FoP + 2) + 64 * (size_t)(FoP + 2) + 64 * (size_t)FiP) * sizeof(float);
-#define GCL_FB64(NO_)                                                                                             \
-  do {                                                                                                            \
-    auto kern = linear_bwd_fused64_kernel<NO_>;                                                                   \
-    hipLaunchKernelGGL(kern, dim3(nblk), dim3(256), lds64, st, dy, lddy, W, x, ldx, in_slope, dx, lddx, rows, Fin, \
-                       Fout, part_dw, db ? part_db : nullptr, colsum_dx ? part_cs : nullptr,                      \
-                       want_slope ? part_sl : nullptr);                                                           \
-  } while (0)
-    if (NO == 1) GCL_FB64(1);
-    else GCL_FB64(2);
-#undef GCL_FB64
-  } else {
-  const size_t lds = ((size_t)FiP * (FoP + 2) + 128 * (size_t)(FoP + 2) + 128 * (size_t)FiP) * sizeof(float);
-#define GCL_FB(NO_, NC_)                                                                                          \
-  do {                                                                                                            \
-    auto kern = linear_bwd_fused_kernel<NO_, NC_>;                                                                \
-    GCL_ENSURE_DYN_LDS(kern, gcl::kLdsBytes);                                                                     \
-    hipLaunchKernelGGL(kern, dim3(nblk), dim3(256), lds, st, dy, lddy, W, x, ldx, in_slope, dx, lddx, rows, Fin,  \
-                       Fout, part_dw, db ? part_db : nullptr, colsum_dx ? part_cs : nullptr,                      \
-                       want_slope ? part_sl : nullptr);                                                           \
-  } while (0)
-  if (NO == 1 && NC == 1) GCL_FB(1, 1);
-  else if (NO == 1 && NC == 2) GCL_FB(1, 2);
-  else if (NO == 1 && NC == 3) GCL_FB(1, 3);
-  else if (NO == 2 && NC == 1) GCL_FB(2, 1);
-  else if (NO == 2 && NC == 2) GCL_FB(2, 2);
-  else GCL_FB(2, 3);
-#undef GCL_FB
-  }
+  double* part_sl = want_slope ? (double*)(((uintptr_t)ws + p.slope_off_bytes + 15) & ~(uintptr_t)15) : nullptr;
+  auto go = [&](auto kern, bool raise_lds) {
+    if (raise_lds) GCL_ENSURE_DYN_LDS(kern, gcl::kLdsBytes);
+    hipLaunchKernelGGL(kern, dim3(p.nblk), dim3(256), p.lds, st, dy, lddy, W, x, ldx, in_slope, dx, lddx, rows, Fin, Fout, part_dw,
+                       part_db, part_cs, part_sl);
+    return (int)GCL_OK;
+  };
+  int rc;
+  if (p.form == BwdAllForm::kFused128)
+    rc = pick<1, 2>(p.NO, [&](auto NO) {
+      return pick<1, 2, 3>(p.NC, [&](auto NC) { return go(linear_bwd_fused_kernel<decltype(NO)::value, decltype(NC)::value>, true); });
+    });
+  else if (p.form == BwdAllForm::kFused64)
+    rc = pick<1, 2>(p.NO, [&](auto NO) { return go(linear_bwd_fused64_kernel<decltype(NO)::value>, false); });  // 50 KB: below the default limit
+  else
+    rc = gcl::x3_linear_bwd(p, dy, lddy, W, x, ldx, in_slope, dx, lddx, rows, Fin, Fout, part_dw, part_db, part_cs, part_sl, st);
+  if (rc) return rc;
   GCL_CHECK_LAUNCH();
-  {
-    // per-block record: [dW tile FoP*FiP | db FoP | colsum FiP]; one launch reduces all three
-    const int64_t rec = (int64_t)FoP * FiP + FoP + FiP;
-    RedSeg s0{dW, 0, Fout * FiP, FiP, Fin, Fin, acc_dw};
-    RedSeg s1{db, FoP * FiP, db ? Fout : 0, FoP, Fout, 0, acc_db};
-    RedSeg s2{colsum_dx, FoP * FiP + FoP, colsum_dx ? Fin : 0, FiP, Fin, 0, acc_cs};
-    if (job) {
-      // deferred: describe the final pass instead of launching it.  db / colsum segments are widened to their padded
-      // lengths (cols still limits what is written) so that every job takes the 16-byte reducer.
-      s1.count = db ? FoP : 0;
-      s2.count = colsum_dx ? FiP : 0;
-      job->part = part_dw;
-      job->nparts = nblk;
-      job->pstride = rec;
-      const RedSeg* ss[3] = {&s0, &s1, &s2};
-      for (int q = 0; q < 3; ++q) {
-        job->seg[q].out = ss[q]->out;
-        job->seg[q].poff = ss[q]->poff;
-        job->seg[q].count = ss[q]->count;
-        job->seg[q].pld = ss[q]->pld;
-        job->seg[q].cols = ss[q]->cols;
-        job->seg[q].ldo = ss[q]->ldo;
-        job->seg[q].acc = ss[q]->acc;
-      }
-      job->spart = want_slope ? part_sl : nullptr;
-      job->ns = want_slope ? nblk : 0;
-      job->sout = want_slope ? d_in_slope : nullptr;
-      return GCL_OK;
-    }
-    // + the slope partials (one extra block of the same launch)
-    launch_reduce_multi(part_dw, nblk, rec, s0, s1, s2, st, want_slope ? part_sl : nullptr, nblk, d_in_slope);
-    GCL_CHECK_LAUNCH();
+  // one launch reduces the three parts of the records
+  RedSeg s0{dW, 0, Fout * p.FiP, p.FiP, Fin, Fin, acc_dw};
+  RedSeg s1{db, p.db_off, db ? Fout : 0, p.FoP, Fout, 0, acc_db};
+  RedSeg s2{colsum_dx, p.cs_off, colsum_dx ? Fin : 0, p.FiP, Fin, 0, acc_cs};
+  if (job) {
+    // deferred: describe the final pass instead of launching it.  db / colsum segments are widened to their padded
+    // lengths (cols still limits what is written) so that every job takes the 16-byte reducer.
+    s1.count = db ? p.FoP : 0;
+    s2.count = colsum_dx ? p.FiP : 0;
+    job->part = part_dw;
+    job->nparts = p.nblk;
+    job->pstride = p.rec;
+    job->seg[0] = s0; job->seg[1] = s1; job->seg[2] = s2;
+    job->spart = part_sl;
+    job->ns = want_slope ? p.nblk : 0;
+    job->sout = want_slope ? d_in_slope : nullptr;
+    return GCL_OK;
   }
+  // + the slope partials (one extra block of the same launch)
+  launch_reduce_multi(part_dw, p.nblk, p.rec, s0, s1, s2, st, part_sl, p.nblk, d_in_slope);
+  GCL_CHECK_LAUNCH();
   return GCL_OK;
 }
 
@@ -1758,8 +1560,9 @@ extern "C" int gcl_reduce_jobs(const gcl_reduce_job* jobs, int32_t n, gcl_stream
       int total = 0;
       for (int t = 0; t < 3; ++t) {
         GCL_CHECK_ARG((g.seg[t].poff | g.seg[t].count) % 4 == 0, "reduce_jobs: segment not 16-byte granular");
-        *ss[t] = RedSeg{g.seg[t].out, g.seg[t].poff, g.seg[t].out ? g.seg[t].count : 0, g.seg[t].pld > 0 ? g.seg[t].pld : 1,
-                        g.seg[t].cols, g.seg[t].ldo, g.seg[t].acc};
+        *ss[t] = g.seg[t];
+        if (!ss[t]->out) ss[t]->count = 0;   // unused segment
+        if (ss[t]->pld <= 0) ss[t]->pld = 1;  // (a zeroed job: the kernel divides by it)
         total += ss[t]->count;
       }
       k.spart = g.spart;

@@ -746,183 +746,92 @@ extern "C" int gcl_debug_read_stamps_x3(unsigned long long* host_out, int count)
 
 namespace gcl {
 
-bool x3_linear_fwd_applicable(const float* x, int64_t ldx, const float* y, int64_t ldy, int K, int N, int akind) {
-  if (!env_int("GCL_X3", 1)) return false;  // read per call: the dispatch tests compare GCL_X3=0 with the default
-  if (K < 1 || K > 64 || N < 4 || N > 64 || (N & 3)) return false;
-  if ((ldx & 3) || (ldy & 3) || !aligned16(x) || !aligned16(y)) return false;
-  if (ldx * 4 * 35 >= ((int64_t)1 << 31) || ldy * 4 * 35 >= ((int64_t)1 << 31)) return false;  // 32-bit offsets inside a tile
-  return akind == kActNone || akind == kActPrelu || akind == kActSilu;
+using namespace plan;
+static_assert(kX3FwdLds == 4 * (size_t)kTileB && kX3BwdLds == 6 * (size_t)kImg64B + 64 * 64 * sizeof(float),
+              "dense_plan.h states the LDS of these kernels");
+
+// this translation unit's reader of the switches (dense_plan.h): the cached one here, the per-call ones on first use
+static DenseSwitches switches() {
+  static const bool valu = env_is("GCL_LINEAR_IMPL", "valu");
+  DenseSwitches sw;
+  sw.valu = valu;
+  return sw;
 }
 
-int x3_linear_fwd(const float* x, int64_t ldx, int akind, const float* slope, const float* W, const float* bias,
-                  float* y, int64_t ldy, int64_t rows, int K, int N, hipStream_t st) {
+int x3_linear_fwd(const X3FwdPlan& p, const float* x, int64_t ldx, int akind, const float* slope, const float* W,
+                  const float* bias, float* y, int64_t ldy, int64_t rows, int K, int N, hipStream_t st) {
   if (rows == 0) return GCL_OK;
-  const int64_t ntiles = cdiv(rows, 128);
-  const int grid = (int)(ntiles < 2 * kNumCU ? ntiles : 2 * kNumCU);
-  const size_t lds = 4 * (size_t)kTileB;
-#define GCL_X3F3(NS_, SILU_, NKS_)                                                                                \
-  hipLaunchKernelGGL((linear_x3_fwd_kernel<NS_, SILU_, NKS_>), dim3(grid), dim3(256), lds, st, x, ldx, slope, akind, \
-                     W, bias, y, ldy, rows, K, N, x3_ablate())
-#define GCL_X3F(NS_, SILU_)           \
-  do {                                \
-    if (K <= 32) GCL_X3F3(NS_, SILU_, 2); \
-    else GCL_X3F3(NS_, SILU_, 4);     \
-  } while (0)
-  if (akind == kActSilu) {
-    if (N > 32) GCL_X3F(2, true);
-    else GCL_X3F(1, true);
-  } else {
-    if (N > 32) GCL_X3F(2, false);
-    else GCL_X3F(1, false);
-  }
-#undef GCL_X3F3
-#undef GCL_X3F
+  const int rc = pick<1, 2>(p.NS, [&](auto NS) {
+    return pick<0, 1>(p.SILU, [&](auto SILU) {
+      return pick<2, 4>(p.NKS, [&](auto NKS) {
+        hipLaunchKernelGGL((linear_x3_fwd_kernel<decltype(NS)::value, decltype(SILU)::value != 0, decltype(NKS)::value>),
+                           dim3(p.grid), dim3(256), p.lds, st, x, ldx, slope, akind, W, bias, y, ldy, rows, K, N, x3_ablate());
+        return (int)GCL_OK;
+      });
+    });
+  });
+  if (rc) return rc;
   GCL_CHECK_LAUNCH();
   return GCL_OK;
 }
 
 // ---- the chained forward of an MLP (mlp_x3_chain_kernel) ----
-struct X3ChainCall {  // the arguments of gcl_mlp_fwd_chain(_ok) per layer
-  const float* x;
-  int64_t ldx, rows;
-  int K, act0, L;
-  const float* z[3];
-  int64_t ldz[3];
-  int N[3];
-  const float *gamma, *y, *stats;  // the LayerNorm epilogue (gamma null: none)
-  int64_t ldy;
-};
-
-static bool x3_chain_ok(const X3ChainCall& c) {
-  if (!env_int("GCL_MLP_CHAIN", 1)) return false;  // read per call: the tests compare the chain with the per-layer launches
-  static const bool valu = env_is("GCL_LINEAR_IMPL", "valu");  // (gcl_dense_fwd then takes no matrix-pipe kernel)
-  if (valu || c.L < 2 || c.L > 3 || c.rows < 0 || !c.x) return false;
-  if (c.act0 != kActNone && c.act0 != kActPrelu) return false;
-  const float* in = c.x;
-  int64_t ldin = c.ldx;
-  int K = c.K;
-  for (int k = 0; k < c.L; ++k) {
-    // the layer as gcl_dense_fwd would launch it, and on linear_x3_fwd_kernel<2, false, 4>
-    if (!c.z[k] || !x3_linear_fwd_applicable(in, ldin, c.z[k], c.ldz[k], K, c.N[k], k ? kActPrelu : c.act0)) return false;
-    if (K < 33 || c.N[k] < 33 || ldin < K || c.ldz[k] < c.N[k]) return false;
-    if (k + 1 < c.L && c.ldz[k] != c.N[k]) return false;  // handed over: contiguous
-    in = c.z[k];
-    ldin = c.ldz[k];
-    K = c.N[k];
-  }
-  if (c.gamma) {  // the epilogue: two-layer runs (with three the kernel would not fit the register file), 16-byte rows
-    if (c.L != 2 || !c.y || !c.stats || (c.ldy & 3) || c.ldy < K || !aligned16(c.y) || ((uintptr_t)c.stats & 7)) return false;
-    if (c.ldy * 4 * 35 >= ((int64_t)1 << 31)) return false;  // 32-bit offsets inside a tile
-  }
-  return true;
-}
-
-static int x3_chain_launch(const float* x, int64_t ldx, int64_t rows, int L, bool ln, const X3Chain& a, hipStream_t st) {
+static int x3_chain_launch(const ChainPlan& p, const float* x, int64_t ldx, int64_t rows, const X3Chain& a, hipStream_t st) {
   if (rows == 0) return GCL_OK;
-  const int64_t ntiles = cdiv(rows, 128);
-  const int grid = (int)(ntiles < kNumCU ? ntiles : kNumCU);  // one block a CU: the register file holds one wave a SIMD
-  const size_t lds = 4 * (size_t)kTileB;
-#define GCL_X3C(L_, LN_)                                                       \
-  do {                                                                         \
-    auto kern = mlp_x3_chain_kernel<L_, LN_>;                                  \
-    GCL_ENSURE_DYN_LDS(kern, lds);                                             \
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, x, ldx, rows, a); \
-  } while (0)
-  if (L == 2 && ln) GCL_X3C(2, true);
-  else if (L == 2) GCL_X3C(2, false);
-  else GCL_X3C(3, false);
-#undef GCL_X3C
+  const int rc = pick<0, 1, 2>(p.L == 3 ? 2 : p.LN, [&](auto V) {  // <L, LN>: (2, false) (2, true) (3, false)
+    auto kern = mlp_x3_chain_kernel<decltype(V)::value == 2 ? 3 : 2, decltype(V)::value == 1>;
+    GCL_ENSURE_DYN_LDS(kern, p.lds);
+    hipLaunchKernelGGL(kern, dim3(p.grid), dim3(256), p.lds, st, x, ldx, rows, a);
+    return (int)GCL_OK;
+  });
+  if (rc) return rc;
   GCL_CHECK_LAUNCH();
   return GCL_OK;
 }
 
-bool x3_linear_bwd_applicable(const float* dy, int64_t lddy, const float* x, int64_t ldx, const float* dx, int64_t lddx,
-                              int Fin, int Fout) {
-  if (!env_int("GCL_X3", 1)) return false;  // read per call: the dispatch tests compare GCL_X3=0 with the default
-  if (Fin < 33 || Fin > 64 || (Fin & 3) || Fout < 1 || Fout > 64) return false;
-  if (lddy < ((Fout + 3) & ~3) || (lddy & 3) || (ldx & 3) || (lddx & 3) || lddx < Fin) return false;
-  if (!aligned16(dy) || !aligned16(x) || !aligned16(dx)) return false;
-  return lddx * 4 * 70 < ((int64_t)1 << 31);  // 32-bit store offsets inside a tile
-}
-
-int x3_linear_bwd_blocks(int64_t rows) {
-  const int64_t ntiles = cdiv(rows, 64);
-  return (int)(ntiles < 2 * kNumCU ? ntiles : 2 * kNumCU);
-}
-
-int x3_linear_bwd(const float* dy, int64_t lddy, const float* W, const float* x, int64_t ldx, const float* in_slope,
-                  float* dx, int64_t lddx, int64_t rows, int Fin, int Fout, float* part_dw, float* part_db,
-                  float* part_cs, double* part_slope, hipStream_t st) {
-  const int grid = x3_linear_bwd_blocks(rows);
-  const size_t lds = 6 * (size_t)kImg64B + 64 * 64 * sizeof(float);
-#define GCL_X3B_GO(KERN_)                                                                                         \
-  do {                                                                                                            \
-    auto kern = KERN_;                                                                                            \
-    GCL_ENSURE_DYN_LDS(kern, gcl::kLdsBytes);                                                                     \
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, dy, lddy, W, x, ldx, in_slope, dx, lddx, rows, Fin, Fout, \
-                       part_dw, part_db, part_cs, part_slope);                                                    \
-  } while (0)
-#define GCL_X3B(NO_) GCL_X3B_GO((linear_x3_bwd_kernel<NO_>))
-  // what the caller asked for (the slope gradient comes with the activation).  A call that wants both column sums, db and
-  // those of dX, keeps the full kernel whether or not it has an activation: no layer of the models makes such a call (an
-  // MLP layer wants db, a GCNConv the column sums of dX), and linear_x3_bwd_kernel stays the kernel of the complete
-  // contract.  GCL_X3_BWD_LEAN=0 (read per call: the tests compare the two kernels): every call
-  const bool act = in_slope != nullptr, wdb = part_db != nullptr, wcs = part_cs != nullptr, ymask = (Fout & 3) != 0;
-  if ((wdb && wcs) || !env_int("GCL_X3_BWD_LEAN", 1)) {
-    if (Fout > 32) GCL_X3B(2);
-    else GCL_X3B(1);
-  } else {
-#define GCL_X3L(NO_, A_, D_, C_, M_) GCL_X3B_GO((linear_x3_bwd_lean_kernel<NO_, A_, D_, C_, M_>))
-#define GCL_X3L_M(NO_, A_, D_, C_)          \
-  do {                                      \
-    if (ymask) GCL_X3L(NO_, A_, D_, C_, true); \
-    else GCL_X3L(NO_, A_, D_, C_, false);   \
-  } while (0)
-#define GCL_X3L_A(NO_, A_)                          \
-  do {                                              \
-    if (wdb) GCL_X3L_M(NO_, A_, true, false);       \
-    else if (wcs) GCL_X3L_M(NO_, A_, false, true);  \
-    else GCL_X3L_M(NO_, A_, false, false);          \
-  } while (0)
-#define GCL_X3L_NO(NO_)           \
-  do {                            \
-    if (act) GCL_X3L_A(NO_, true); \
-    else GCL_X3L_A(NO_, false);   \
-  } while (0)
-    if (Fout > 32) GCL_X3L_NO(2);
-    else GCL_X3L_NO(1);
-#undef GCL_X3L_NO
-#undef GCL_X3L_A
-#undef GCL_X3L_M
-#undef GCL_X3L
-  }
-#undef GCL_X3B
-#undef GCL_X3B_GO
+int x3_linear_bwd(const BwdAllPlan& p, const float* dy, int64_t lddy, const float* W, const float* x, int64_t ldx,
+                  const float* in_slope, float* dx, int64_t lddx, int64_t rows, int Fin, int Fout, float* part_dw,
+                  float* part_db, float* part_cs, double* part_slope, hipStream_t st) {
+  auto go = [&](auto kern) {
+    GCL_ENSURE_DYN_LDS(kern, gcl::kLdsBytes);
+    hipLaunchKernelGGL(kern, dim3(p.nblk), dim3(256), p.lds, st, dy, lddy, W, x, ldx, in_slope, dx, lddx, rows, Fin, Fout,
+                       part_dw, part_db, part_cs, part_slope);
+    return (int)GCL_OK;
+  };
+  // kX3Lean: <NO, ACT, DB, CS, YMASK> with at most one of DB / CS (both: the full kernel), as one code
+  const int want = p.DB ? 1 : p.CS ? 2 : 0;
+  const int rc = p.form == BwdAllForm::kX3Full
+                     ? pick<1, 2>(p.NO, [&](auto NO) { return go(linear_x3_bwd_kernel<decltype(NO)::value>); })
+                     : pick<1, 2>(p.NO, [&](auto NO) {
+                         return pick<0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11>(want * 4 + p.ACT * 2 + p.YMASK, [&](auto C) {
+                           constexpr int c = decltype(C)::value;
+                           return go(linear_x3_bwd_lean_kernel<decltype(NO)::value, (c & 2) != 0, c / 4 == 1, c / 4 == 2, (c & 1) != 0>);
+                         });
+                       });
+  if (rc) return rc;
   GCL_CHECK_LAUNCH();
   return GCL_OK;
 }
 
 }  // namespace gcl
 
-static gcl::X3ChainCall chain_call(const float* x, int64_t ldx, int64_t rows, int32_t K, int32_t act0, int32_t nlayers,
-                                   const float* z0, int64_t ldz0, int32_t N0, const float* z1, int64_t ldz1, int32_t N1,
-                                   const float* z2, int64_t ldz2, int32_t N2, const float* gamma, const float* y,
-                                   int64_t ldy, const float* stats) {
-  gcl::X3ChainCall c;
-  c.x = x; c.ldx = ldx; c.rows = rows; c.K = K; c.act0 = act0; c.L = nlayers;
-  c.z[0] = z0; c.ldz[0] = ldz0; c.N[0] = N0;
-  c.z[1] = z1; c.ldz[1] = ldz1; c.N[1] = N1;
-  c.z[2] = z2; c.ldz[2] = ldz2; c.N[2] = N2;
-  c.gamma = gamma; c.y = y; c.ldy = ldy; c.stats = stats;
-  return c;
+static gcl::plan::ChainCall chain_call(const float* x, int64_t ldx, int64_t rows, int32_t K, int32_t act0, int32_t nlayers,
+                                       const float* z0, int64_t ldz0, int32_t N0, const float* z1, int64_t ldz1, int32_t N1,
+                                       const float* z2, int64_t ldz2, int32_t N2, const float* gamma, const float* y,
+                                       int64_t ldy, const float* stats) {
+  using gcl::aligned16;
+  return {ldx, rows, K, act0, nlayers, x != nullptr, aligned16(x),
+          {z0 != nullptr, z1 != nullptr, z2 != nullptr}, {aligned16(z0), aligned16(z1), aligned16(z2)},
+          {ldz0, ldz1, ldz2}, {N0, N1, N2},
+          gamma != nullptr, y != nullptr, aligned16(y), stats != nullptr, ((uintptr_t)stats & 7) == 0, ldy};
 }
 
 extern "C" int gcl_mlp_fwd_chain_ok(const float* x, int64_t ldx, int64_t rows, int32_t K, int32_t act0, int32_t nlayers,
                                     const float* z0, int64_t ldz0, int32_t N0, const float* z1, int64_t ldz1, int32_t N1,
                                     const float* z2, int64_t ldz2, int32_t N2, const float* gamma, const float* y,
                                     int64_t ldy, const float* stats) {
-  return gcl::x3_chain_ok(chain_call(x, ldx, rows, K, act0, nlayers, z0, ldz0, N0, z1, ldz1, N1, z2, ldz2, N2, gamma, y, ldy,
-                                     stats))
+  return gcl::plan_mlp_chain(chain_call(x, ldx, rows, K, act0, nlayers, z0, ldz0, N0, z1, ldz1, N1, z2, ldz2, N2, gamma, y, ldy,
+                                        stats), gcl::switches()).ok
              ? 1
              : 0;
 }
@@ -936,9 +845,9 @@ extern "C" int gcl_mlp_fwd_chain(const float* x, int64_t ldx, int64_t rows, int3
   GCL_CHECK_ARG(x && W0 && z0 && W1 && z1 && (nlayers == 2 || (W2 && z2)), "mlp_fwd_chain: null argument");
   GCL_CHECK_ARG(!gamma || (beta && y && stats), "mlp_fwd_chain: the LayerNorm needs beta, y and stats");
   GCL_CHECK_ARG(act0 != GCL_ACT_PRELU || slope0, "mlp_fwd_chain: GCL_ACT_PRELU needs the slope pointer");
-  GCL_CHECK_ARG(gcl::x3_chain_ok(chain_call(x, ldx, rows, K, act0, nlayers, z0, ldz0, N0, z1, ldz1, N1, z2, ldz2, N2, gamma, y,
-                                            ldy, stats)),
-                "mlp_fwd_chain: not a run this kernel takes (gcl_mlp_fwd_chain_ok): launch it per layer");
+  const gcl::plan::ChainPlan p = gcl::plan_mlp_chain(
+      chain_call(x, ldx, rows, K, act0, nlayers, z0, ldz0, N0, z1, ldz1, N1, z2, ldz2, N2, gamma, y, ldy, stats), gcl::switches());
+  GCL_CHECK_ARG(p.ok, "mlp_fwd_chain: not a run this kernel takes (gcl_mlp_fwd_chain_ok): launch it per layer");
   X3Chain a = {};
   const float* Ws[3] = {W0, W1, W2};
   const float* bs[3] = {b0, b1, b2};
@@ -953,5 +862,5 @@ extern "C" int gcl_mlp_fwd_chain(const float* x, int64_t ldx, int64_t rows, int3
     Kk = Ns[k];
   }
   a.gamma = gamma; a.beta = beta; a.Y = y; a.ldy = ldy; a.stats = stats; a.eps = eps;
-  return gcl::x3_chain_launch(x, ldx, rows, nlayers, gamma != nullptr, a, (hipStream_t)stream);
+  return gcl::x3_chain_launch(p, x, ldx, rows, a, (hipStream_t)stream);
 }

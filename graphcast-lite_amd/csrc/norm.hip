@@ -419,13 +419,7 @@ inline bool vec_store_ok(const float* p, int64_t ld, int F) { return (ld % 4 == 
 inline bool reduce_job_ok(const float* part, int nparts) { return nparts >= 64 && gcl::aligned16(part); }
 // one vector of `pld` (padded) floats per record, `cols` of them valid
 inline void set_seg(gcl_reduce_job* job, int q, float* out, int poff, int pld, int cols, int acc) {
-  job->seg[q].out = out;
-  job->seg[q].poff = poff;
-  job->seg[q].count = pld;
-  job->seg[q].pld = pld;
-  job->seg[q].cols = cols;
-  job->seg[q].ldo = cols;
-  job->seg[q].acc = acc;
+  job->seg[q] = gcl_reduce_seg{out, poff, pld, pld, cols, cols, acc};
 }
 
 }  // namespace

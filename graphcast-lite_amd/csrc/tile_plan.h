@@ -4,7 +4,6 @@
 // pins every comparison on a CPU.  What depends on a pointer (16-byte alignment) is checked where the launch is made.
 #pragma once
 #include <algorithm>
-#include <type_traits>
 
 #include "common.h"
 
@@ -39,14 +38,6 @@ inline TileGeo tile_geo(const gcl_halo& hl, int lpr, int64_t extra, int bpc = 0)
   t.per_cu = (int)std::min<int64_t>(8, kLdsBytes / t.lds);
   t.grid = (unsigned)(kNumXCD * 32 * (bpc > 0 ? bpc : t.per_cu));
   return t;
-}
-
-// Run-time value -> template constant: calls f(std::integral_constant<int, V>) for the V of Vs... equal to v.
-template <int... Vs, class F>
-int pick(int v, F&& f) {
-  int rc = GCL_EINVAL;
-  if (!((v == Vs && ((rc = f(std::integral_constant<int, Vs>{})), true)) || ...)) set_error("dispatch: no kernel for %d", v);
-  return rc;
 }
 
 // ---- aggregation ------------------------------------------------------------------------------------------------

@@ -26,23 +26,20 @@
 // Inf and NaN operands give non-finite results in the rows / columns that read them (inf becomes NaN: inf - inf).
 #pragma once
 #include "common.h"
+#include "dense_plan.h"
 
 namespace gcl {
 
-// y = act(x) W^T + b for K <= 64, N <= 64 (N % 4 == 0), 16-B aligned rows.  `applicable` is the host-side
-// shape test; the launch returns GCL_OK / GCL_EHIP.
-bool x3_linear_fwd_applicable(const float* x, int64_t ldx, const float* y, int64_t ldy, int K, int N, int akind);
-int x3_linear_fwd(const float* x, int64_t ldx, int akind, const float* slope, const float* W, const float* bias,
-                  float* y, int64_t ldy, int64_t rows, int K, int N, hipStream_t st);
+// y = act(x) W^T + b for K <= 64, N <= 64 (N % 4 == 0), 16-B aligned rows, as plan_x3_fwd (dense_plan.h) laid it out;
+// the launch returns GCL_OK / GCL_EHIP.
+int x3_linear_fwd(const plan::X3FwdPlan& p, const float* x, int64_t ldx, int akind, const float* slope, const float* W,
+                  const float* bias, float* y, int64_t ldy, int64_t rows, int K, int N, hipStream_t st);
 
-// Fused backward (dX, dW, db, colsum(dX), d_slope partials) for Fin in 33..64 (Fin % 4 == 0), Fout <= 64: same
-// per-block partial records as linear_bwd_fused64_kernel (linear.hip), x3_linear_bwd_blocks(rows) of them.
-bool x3_linear_bwd_applicable(const float* dy, int64_t lddy, const float* x, int64_t ldx, const float* dx, int64_t lddx,
-                              int Fin, int Fout);
-int x3_linear_bwd_blocks(int64_t rows);
-int x3_linear_bwd(const float* dy, int64_t lddy, const float* W, const float* x, int64_t ldx, const float* in_slope,
-                  float* dx, int64_t lddx, int64_t rows, int Fin, int Fout, float* part_dw, float* part_db,
-                  float* part_cs, double* part_slope, hipStream_t st);
+// Fused backward (dX, dW, db, colsum(dX), d_slope partials) for Fin in 33..64 (Fin % 4 == 0), Fout <= 64: the kX3Full /
+// kX3Lean forms of plan_bwd_all, same per-block partial records as linear_bwd_fused64_kernel (linear.hip).
+int x3_linear_bwd(const plan::BwdAllPlan& p, const float* dy, int64_t lddy, const float* W, const float* x, int64_t ldx,
+                  const float* in_slope, float* dx, int64_t lddx, int64_t rows, int Fin, int Fout, float* part_dw,
+                  float* part_db, float* part_cs, double* part_slope, hipStream_t st);
 
 }  // namespace gcl
 

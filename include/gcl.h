@@ -163,13 +163,16 @@ size_t gcl_linear_bwd_all_ws_bytes(int64_t rows, int32_t Fin, int32_t Fout);
  * Rules: every deferred call needs its OWN workspace, alive until gcl_reduce_jobs has run; two pending jobs must not
  * write the same dW / db / colsum_dx (flush first; a shared slope gradient is fine: slopes are summed job after job);
  * job->nparts == 0 means the call took the non-fused path and has already reduced on the spot. */
+/* One output of a final pass: `count` consecutive floats of every partial record from offset `poff`; element e goes to
+ * out[(e / pld) * ldo + e % pld] when e % pld < cols, added to what is there (acc 1) or replacing it (acc 0). */
+typedef struct gcl_reduce_seg {
+  float* out; /* NULL: unused segment */
+  int32_t poff, count, pld, cols, ldo, acc;
+} gcl_reduce_seg;
 typedef struct gcl_reduce_job {
   const float* part; /* per-block partial records */
   int64_t pstride;   /* floats between records */
-  struct {
-    float* out; /* NULL: unused segment */
-    int32_t poff, count, pld, cols, ldo, acc;
-  } seg[3];           /* dW | db | colsum_dx */
+  gcl_reduce_seg seg[3]; /* dW | db | colsum_dx */
   const double* spart; /* slope partials (one per block) or NULL */
   float* sout;
   int32_t nparts, ns;

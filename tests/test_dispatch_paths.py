@@ -265,6 +265,59 @@ def test_linear_bwd_all_fallbacks(hip, env, rows, Fin, Fout, switch):
 
 
 # ------------------------------------------------------------------------------------------------------------------
+# boundaries of the dense plans (csrc/dense_plan.h) the cases above do not reach
+# ------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("rows,queued", [(8064, 0), (8065, 1)])
+def test_dw_deferral_boundary(hip, env, rows, queued):
+    """gcl_dense_bwd_dw_deferred hands its final pass to the queue from 64 partial records on (plan_dw: 128 rows a block
+    at these widths, so 8064 rows reduce on the spot and 8065 are queued); deferred + gcl_reduce_jobs is bit-equal to
+    the immediate call either way, and both are within 1e-5 of float64."""
+    x, dy = rnd(rows, 64, seed=1).to(DEV), rnd(rows, 64, seed=2).to(DEV)
+    dW0, db0 = torch.empty(64, 64, device=DEV), torch.empty(64, device=DEV)
+    hip.dense_bwd_dw(dy, x, dW0, db0, False)
+    dW1, db1 = torch.full((64, 64), 9.0, device=DEV), torch.full((64,), 9.0, device=DEV)
+    hip.defer_begin()
+    try:
+        hip.dense_bwd_dw(dy, x, dW1, db1, False)
+        assert (len(hip._deferred.jobs) > 0) == bool(queued), len(hip._deferred.jobs)
+    finally:
+        hip.defer_flush()
+    assert torch.equal(dW0, dW1) and torch.equal(db0, db1)
+    assert rel(dW0, dy.double().t() @ x.double()) < TOL and rel(db0, dy.double().sum(0)) < TOL
+
+
+@pytest.mark.parametrize("Fin", [128, 132])
+def test_dw_chunk_boundary(hip, env, Fin):
+    """gcl_dense_bwd_dw at one and at two 128-column input chunks (Fin 128 / 132), PReLU on the input: 1e-5 of float64."""
+    rows, Fout = 1000, 48
+    x, dy, a = rnd(rows, Fin, seed=1), rnd(rows, Fout, seed=2), torch.tensor([0.25])
+    dW, db = torch.empty(Fout, Fin, device=DEV), torch.empty(Fout, device=DEV)
+    hip.dense_bwd_dw(dy.to(DEV), x.to(DEV), dW, db, False, 1, a.to(DEV))
+    assert rel(dW, dy.double().t() @ _act64(x.double(), 1, a.double())) < TOL and rel(db, dy.double().sum(0)) < TOL
+
+
+@pytest.mark.parametrize("Fout,fused", [(64, True), (68, False)])
+def test_linear_bwd_all_fout_boundary(hip, env, Fout, fused):
+    """gcl_linear_bwd_all at the widest fused output (64) and just past it (68: the separate kernels): the path ran, and
+    dx / dW / db / column sums / slope gradient are within the bars of test_linear_bwd_all_fallbacks of float64."""
+    rows, Fin = 1000, 64
+    x, W, dy, a = rnd(rows, Fin, seed=1), rnd(Fout, Fin, seed=2, scale=0.2), rnd(rows, Fout, seed=4), torch.tensor([0.25])
+    x64, W64, a64 = x.double().requires_grad_(), W.double().requires_grad_(), a.double().requires_grad_()
+    b64 = torch.zeros(Fout, dtype=torch.float64, requires_grad=True)
+    (torch.where(x64 > 0, x64, a64 * x64) @ W64.t() + b64).backward(dy.double())
+
+    def run():
+        dW, db, cs, da = (torch.empty(Fout, Fin, device=DEV), torch.empty(Fout, device=DEV), torch.empty(Fin, device=DEV),
+                          torch.zeros(1, device=DEV))
+        dx = hip.linear_bwd_all(dy.to(DEV), W.to(DEV), x.to(DEV), a.to(DEV), da, dW, db, cs, False)
+        return dx, dW, db, cs, da
+    (dx, dW, db, cs, da), names = launched(run)
+    assert has(names, "linear_x3_bwd") == fused and has(names, "dw_mfma_kernel") == (not fused), names
+    assert rel(dx, x64.grad) < TOL and rel(dW, W64.grad) < 2e-5 and rel(db, b64.grad) < 2e-5
+    assert rel(cs, x64.grad.sum(0)) < 1e-4 and rel(da, a64.grad) < 1e-4
+
+
+# ------------------------------------------------------------------------------------------------------------------
 # GCL_X3_GCN=0, GCL_X3=0, GCL_GCN_HALO_FORM=0: the one-kernel GCN layer
 # ------------------------------------------------------------------------------------------------------------------
 GCN_MODES = ((None, None), ("GCL_GCN_HALO_FORM", "0"), ("GCL_X3_GCN", "0"), ("GCL_X3", "0"))
