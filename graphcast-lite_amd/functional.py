@@ -10,13 +10,14 @@ in place on the device and returns None for that input (fused accumulation - no 
 per parameter, and gradients land directly in the flat bucket that the data-parallel all-reduce
 uses); otherwise it returns a fresh gradient tensor and autograd stores it as usual.
 """
-from typing import List, Optional
+from typing import List, NamedTuple, Optional
 
 import os
 
 import torch
 
 from . import hip
+from .stack_plan import Layout, StackPlan, Switches, plan_gcn_stack
 
 
 def _grad_slot(p: Optional[torch.Tensor], needs: bool):
@@ -295,6 +296,116 @@ class LatSource:
         return t
 
 
+def stack_switches() -> Switches:
+    """What plan_gcn_stack obeys, read here and nowhere else in GCNStackFn.forward: the two module attributes as the import
+    (or a test) left them, the environment per call."""
+    return Switches(ln_colsum=_LN_COLSUM, rows_out=_ROWS_OUT, row_skip=_row_skip(), split_grad=_split_grad())
+
+
+def _expect_dense(t, B: int, n: int, F: int, aligned: bool = True):
+    """The plan took `t` for a fresh contiguous [B, n, F] tensor when it asked the kernels' gates: anything else is an error,
+    never another path.  aligned=False: the gate asked looks at strides alone."""
+    if tuple(t.shape) != (B, n, F) or not t.is_contiguous() or (aligned and t.data_ptr() % 16):
+        raise RuntimeError(f"GCN stack: a layer received {tuple(t.shape)} with strides {t.stride()} where its plan assumed a "
+                           f"dense 16-byte aligned [{B}, {n}, {F}]")
+
+
+def _stack_act(owner, slope_p):
+    """Activation between the convs: learnable PReLU slope (params[2L]), SiLU, or ReLU as a PReLU with the owner's constant
+    zero slope (src/models.py:154-163, :316)."""
+    return getattr(owner, "act_kind", hip.ACT_PRELU), (slope_p.detach() if slope_p is not None
+                                                       else getattr(owner, "const_slope", None))
+
+
+class _StackIO(NamedTuple):
+    """What the steps of one forward call reach beside their operands."""
+    plan: StackPlan
+    graph: object
+    lat: object
+    split: object
+    out_head: Optional[torch.Tensor]
+    present: Optional[torch.Tensor]
+
+
+# One function per ConvStep.kind: (step, io, input, activation, slope, W, b) -> (what the backward keeps, the next input)
+def _conv_tab(st, io, cur, act, slope, W, b):
+    tab = io.lat.tab if io.plan.enc_shape is None else io.lat.compact_tab(io.plan.enc_shape[1])
+    p = hip.gcn_layer_fwd_tab(io.graph, cur, tab, act, slope, W, b)
+    return p, p
+
+
+def _conv_split(st, io, cur, act, slope, W, b):
+    # the encoder output: grid rows straight into the decoder's input, mesh rows compact; nobody reads it whole
+    B, n = io.plan.B, io.plan.n
+    tail = torch.empty(B, n - io.out_head.shape[1], st.Fout, dtype=torch.float32, device=cur.device)
+    hip.gcn_layer_fwd_split(io.graph, cur, act, slope, W, b, io.out_head, tail)
+    io.split.keep_split_out(tail)
+    return None, _token(cur, (B, n, st.Fout))  # (the backward of a stack without LayerNorm never reads its last output)
+
+
+def _conv_fused(st, io, cur, act, slope, W, b):
+    # ONE kernel (csrc/gcn_layer.hip): gather-aggregate the activated input rows, then the dense transform; an output width
+    # that is not a multiple of 4 (33 / 19 variables) is stored ldh wide with zero padding columns
+    p = hip.gcn_layer_fwd(io.graph, cur, act, slope, W, b, rows_out=st.rows_out, present=io.present if st.present else None)
+    return p, p
+
+
+def _conv_two_kernel_padded(st, io, cur, act, slope, W, b):
+    # two-kernel path of the padded last layer: zero weight rows / bias entries for the extra columns
+    B, n = io.plan.B, io.plan.n
+    Wp = torch.nn.functional.pad(W, (0, 0, 0, st.ldh - st.Fout))
+    bp = torch.nn.functional.pad(b, (0, st.ldh - st.Fout))
+    h = hip.linear_fwd(cur.view(B * n, -1), Wp, None, slope, act=act)
+    p = hip.aggregate(io.graph, h.view(B, n, st.ldh), bp)
+    return p, p[..., :st.Fout]
+
+
+def _conv_two_kernel(st, io, cur, act, slope, W, b):
+    B, n = io.plan.B, io.plan.n
+    h = hip.linear_fwd(cur.view(B * n, -1), W, None, slope, ld_out=st.ldh, act=act)  # padded scratch: 16-B loads in the gather
+    p = hip.aggregate(io.graph, torch.as_strided(h, (B, n, st.Fout), (n * st.ldh, st.ldh, 1)), b)
+    return p, p
+
+
+_CONV = {"tab": _conv_tab, "split": _conv_split, "fused": _conv_fused, "two_kernel_padded": _conv_two_kernel_padded,
+         "two_kernel": _conv_two_kernel}
+
+
+class _Incoming(NamedTuple):
+    """The gradient a stack's backward received (_incoming_grad)."""
+    kind: str  # dense | mapped | parts | wide
+    dy: torch.Tensor  # dense: contiguous [B, rows, F]; wide: as it came; mapped / parts: the token (only its shape is used)
+    dy_map: Optional[tuple]  # mapped: (source, row map) for hip.layernorm_bwd
+    parts: Optional[tuple]  # parts: (head rows [B, head, F], tail rows [B, n - head, F])
+    wide: Optional[torch.Tensor]  # wide: dy as the [B, rows, ldh] tensor it is a column slice of
+    compact: bool  # the first layer's transposed aggregation stores the batch-dependent rows compact
+
+
+def _incoming_grad(plan: StackPlan, split, land, lat, graph, dy) -> _Incoming:
+    """Claims what the landings hold for this stack and says which of the four forms the gradient has; the only reader of
+    GCL_NO_LOSS_GRAD_INPLACE and GCL_NO_COMPACT_STORE in the backward."""
+    dy, parts = GradLanding.claim_parts(split, dy)
+    dy, dy_map = GradLanding.claim(land, dy)
+    kind, wide = "parts" if parts is not None else "mapped" if dy_map is not None else "dense", None
+    if kind == "dense" and plan.padded_last is not None and _loss_grad_inplace():
+        # a gradient that already lies in the padded layout of the last conv (the loss writes it so) is read where it is: no
+        # widened copy, the rows that were not returned are the zero tail of gcl_aggregate_head
+        wide = _wide_in_place(dy, plan.padded_last[0])
+        kind = "dense" if wide is None else "wide"
+    if kind == "dense":
+        dy = _flat3(dy)
+    # The Md batch-dependent rows of a row-table first layer's gradient go straight into the compact gradient of
+    # _lat_first_layer_bwd, the others (their batch sums are taken from there) to their usual place: every row is written
+    # once.  The aggregation's input there is a fresh dense tensor; in a stack of one conv it is the last conv's too, and a
+    # form of its own (present rows, wide) goes first.
+    one = len(plan.convs) == 1
+    F0 = plan.padded_last[0] if one and plan.padded_last is not None else plan.convs[0].Fout
+    compact = (plan.convs[0].kind == "tab" and lat.smap is not None and lat.Md > 0 and _compact_store()
+               and not (one and (plan.ln == "mapped_skip" or kind == "wide"))
+               and hip.aggregate_compact_ok(graph, Layout.dense(plan.B, plan.n, F0), transpose=True))
+    return _Incoming(kind, dy, dy_map, parts, wide, compact)
+
+
 class GCNStackFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, owner, graph, L: int, has_ln: bool, eps: float, out_rows: int, land, lat, split, *params):
@@ -303,225 +414,134 @@ class GCNStackFn(torch.autograd.Function):
         rows from the decoder-input gather, the rest from the mesh side): its backward reads both where they are.
         out_rows > 0: only the first `out_rows` rows are returned (the decoder keeps the grid rows,
         src/models.py:870-872); the slice is part of this Function so that its backward receives the gradient of
-        the slice and widens it with ONE pass of gcl_pad_rows (no zero-fill + copy by autograd)."""
-        squeeze = x.dim() == 2
-        ctx.enc_shape = None
+        the slice and widens it with ONE pass of gcl_pad_rows (no zero-fill + copy by autograd).
+        Everything is decided by plan_gcn_stack before the first launch; the backward reads ctx.plan."""
+        enc_shape = None
         if lat is not None and lat.tail is not None:
             # x is the token of an encoder output stored in two parts: the mesh rows are in lat.tail [B, Md + r, D]
-            ctx.enc_shape, x3 = tuple(x.shape), lat.tail
+            enc_shape, x3 = tuple(x.shape), lat.tail
         else:
             x3 = _flat3(x.detach())
-        B, n, _ = x3.shape
+        if lat is not None and not x3.is_contiguous():
+            x3 = x3.contiguous()  # x is the encoder output [B, ne, D]; the stack runs on the M mesh rows it is read into
+        plan, out_head, present = plan_gcn_stack(Layout.of(x3), enc_shape, x.dim() == 2, [params[2 * k].shape for k in range(L)],
+                                                 graph, has_ln, out_rows, land, lat, split, stack_switches())
+        B, n = plan.B, plan.n
         if lat is not None:
-            n = lat.M  # x is the encoder output [B, ne, D]; the stack runs on the M mesh rows it is read into
-            if not x3.is_contiguous():
-                x3 = x3.contiguous()
             GradLanding.expect_tail(lat.landing)  # this Function's backward fills the shared buffer's tail rows (as MeshLatFn)
-        ctx.lat = lat
-        # what the two-part reader assumes: the gradient goes straight to the last conv (no LayerNorm, no row slice, no
-        # padded width) in whole 16-byte rows
-        ctx.split = None
-        if (split is not None and not has_ln and not out_rows and not squeeze and lat is None
-                and params[2 * (L - 1)].shape[0] % 4 == 0 and _split_grad()):
+        if plan.split_reader:
             split.expect_split_reader()
-            ctx.split = split
-        # the same conditions let the last conv STORE its output in two parts (GradLanding.split_out)
-        out_head = None
-        if (split is not None and not has_ln and not out_rows and not squeeze and lat is None
-                and params[2 * (L - 1)].shape[0] % 4 == 0):
-            out_head = split.split_out(B, n, params[2 * (L - 1)].shape[0])
-        slope_p = params[2 * L]
-        # activation between the convs: learnable PReLU slope (params[2L]), SiLU, or ReLU as a PReLU
-        # with the owner's constant zero slope (src/models.py:154-163, :316)
-        akind = getattr(owner, "act_kind", hip.ACT_PRELU)
-        slope_t = slope_p.detach() if slope_p is not None else getattr(owner, "const_slope", None)
-        ps = []  # pre-activation outputs of every conv
-        cur = x3
-        pad_last = None
-        # The landing serves a stack whose whole LayerNorm output goes to the decoder-input gather.  Where that output goes
-        # is decided here, once, because the last conv needs the answer too: dense, through the row map into the decoder's
-        # input (`mapped`), or mapped with the rows that have no reader neither stored nor loaded (`present`: the last conv
-        # stores only present rows, the LayerNorm pair skips the rest, and the transposed aggregation takes their zero
-        # gradient from the table).  Rows are skipped only when every reader of those tensors honours the table: the
-        # LayerNorm backward emits the bias gradient's column sums itself (_LN_COLSUM) and rows are whole 16-byte units.  (The
-        # LayerNorm's input is contiguous on every branch of the loop below: odd widths are copied dense.)
-        if not (has_ln and not (out_rows and out_rows < n) and not squeeze):
-            land = None
-        F_last = params[2 * (L - 1)].shape[0]
-        mapped, present = False, None
-        if land is not None:
+        if plan.landing:
             land.expect_mapped_reader()
-            mapped, present = land.ln_plan(n, F_last, _LN_COLSUM and F_last % 4 == 0 and _row_skip())
-        for k in range(L):
-            W, b = params[2 * k].detach(), params[2 * k + 1].detach()
-            Fout = W.shape[0]
-            ldh = (Fout + 3) // 4 * 4  # padded scratch so the gather can use 16-B loads
+        io = _StackIO(plan, graph, lat, split, out_head, present)
+        akind, slope_t = _stack_act(owner, params[2 * L])
+        ps, cur = [], x3  # ps: pre-activation outputs of every conv
+        for k, st in enumerate(plan.convs):
+            if k > 0:
+                _expect_dense(cur, B, n, st.Fin)
             act_k, slope_k = (akind, slope_t) if k > 0 else (hip.ACT_NONE, None)
-            if k == 0 and lat is not None:
-                tab = lat.tab if ctx.enc_shape is None else lat.compact_tab(ctx.enc_shape[1])
-                p = hip.gcn_layer_fwd_tab(graph, x3, tab, act_k, slope_k, W, b)
-                if ldh != Fout:
-                    p = p.contiguous()
-                ps.append(p)
-                cur = p
-                continue
-            if k == L - 1 and out_head is not None and hip.gcn_layer_split_ok(graph, cur, Fout, out_head):
-                # the encoder output: grid rows straight into the decoder's input, mesh rows compact; nobody reads it whole
-                tail = torch.empty(B, n - out_head.shape[1], Fout, dtype=torch.float32, device=cur.device)
-                hip.gcn_layer_fwd_split(graph, cur, act_k, slope_k, W, b, out_head, tail)
-                split.keep_split_out(tail)
-                ps.append(None)  # (the backward of a stack without LayerNorm never reads its last output)
-                cur = _token(cur, (B, n, Fout))
-                continue
-            if hip.gcn_layer_fusable(graph, cur, W.shape[1], Fout):
-                # ONE kernel (csrc/gcn_layer.hip): gather-aggregate the activated input rows, then the dense
-                # transform; an output width that is not a multiple of 4 (33 / 19 variables) is stored ldh wide
-                # with zero padding columns, so the layer and its backward stay on 16-byte rows
-                # the last conv of a stack whose caller keeps only the first rows (decoder: grid rows) computes only those
-                last_rows = int(out_rows) if (k == L - 1 and out_rows and out_rows < n and not has_ln and _ROWS_OUT) else None
-                p = hip.gcn_layer_fwd(graph, cur, act_k, slope_k, W, b, rows_out=last_rows,
-                                      present=present if k == L - 1 else None)
-                if k == L - 1 and ldh != Fout and not has_ln:
-                    pad_last = (ldh, Fout, None)
-                elif ldh != Fout:
-                    p = p.contiguous()  # an odd width that feeds another layer / the LayerNorm: dense rows
-                ps.append(p)
-                cur = p
-                continue
-            if k == L - 1 and ldh != Fout and not has_ln:
-                # two-kernel path of the same padded layer: zero weight rows / bias entries for the extra columns
-                Wp = torch.nn.functional.pad(W, (0, 0, 0, ldh - Fout))
-                bp = torch.nn.functional.pad(b, (0, ldh - Fout))
-                h = hip.linear_fwd(cur.reshape(B * n, -1), Wp, None, slope_k, act=act_k)
-                p = hip.aggregate(graph, h.view(B, n, ldh), bp)
-                ps.append(p)
-                cur = p[..., :Fout]
-                pad_last = (ldh, Fout, Wp)
-                continue
-            h = hip.linear_fwd(cur.reshape(B * n, -1) if not cur.is_contiguous() else cur.view(B * n, -1), W, None, slope_k,
-                               ld_out=ldh, act=act_k)
-            h3 = torch.as_strided(h, (B, n, Fout), (n * ldh, ldh, 1))
-            p = hip.aggregate(graph, h3, b)
+            p, cur = _CONV[st.kind](st, io, cur, act_k, slope_k, params[2 * k].detach(), params[2 * k + 1].detach())
+            if st.dense_after:
+                p = cur = p.contiguous()
             ps.append(p)
-            cur = p
-        ctx.akind, ctx.slope_t, ctx.pad_last = akind, slope_t, pad_last
         out, stats = cur, None
-        if mapped:
+        if plan.ln in ("mapped", "mapped_skip"):
             # the rows the decoder-input gather takes go straight into the decoder's input, the others nowhere
-            stats = land.ln_write(cur.view(B * n, -1), params[-2].detach(), params[-1].detach(), eps, present is not None)
+            stats = land.ln_write(cur.view(B * n, -1), params[-2].detach(), params[-1].detach(), eps, plan.ln == "mapped_skip")
             out = _token(cur, (B, n, cur.shape[2]))
-        elif has_ln:
+        elif plan.ln == "dense":
             o2, stats = hip.layernorm_fwd(cur.view(B * n, -1), params[-2].detach(), params[-1].detach(), eps)
             out = o2.view(B, n, -1)
-        ctx.land, ctx.present = land, present
-        ctx.owner, ctx.graph, ctx.L, ctx.has_ln = owner, graph, L, has_ln
-        ctx.x3, ctx.ps, ctx.stats, ctx.params, ctx.squeeze = x3, ps, stats, params, squeeze
-        ctx.n_rows, ctx.out_rows = n, (int(out_rows) if out_rows and out_rows < n else 0)
-        if ctx.out_rows:
-            out = out[:, :ctx.out_rows, :]
-        return out[0] if squeeze else out
+        ctx.plan, ctx.x3, ctx.ps, ctx.stats, ctx.params, ctx.present = plan, x3, ps, stats, params, present
+        ctx.owner, ctx.graph, ctx.lat = owner, graph, lat
+        ctx.land, ctx.split = (land if plan.landing else None), (split if plan.split_reader else None)
+        if plan.out_rows:
+            out = out[:, :plan.out_rows, :]
+        return out[0] if plan.squeeze else out
 
     @staticmethod
     def backward(ctx, dy):
-        params, L, graph = ctx.params, ctx.L, ctx.graph
-        needs = list(ctx.needs_input_grad[10:])
-        G = _Grads(list(params), needs)
-        dy, parts = GradLanding.claim_parts(ctx.split, dy)  # parts: (head rows [B, head, F], tail rows [B, n - head, F])
-        dy, dy_map = GradLanding.claim(ctx.land, dy)
-        pad = ctx.pad_last
-        # a gradient that already lies in the padded layout of the last conv (the loss writes it so) is read where it is:
-        # no widened copy, the rows that were not returned are the zero tail of gcl_aggregate_head
-        wide = None
-        if pad is not None and dy_map is None and parts is None and _loss_grad_inplace():
-            wide = _wide_in_place(dy, pad[0])
-        # (with a map or with parts `dy` is the token: only its shape is used)
-        dy3 = dy if (dy_map is not None or parts is not None or wide is not None) else _flat3(dy)
-        B, n = dy3.shape[0], ctx.n_rows
-        ps = ctx.ps
-        dy_rows = dy3  # gradient of the rows that were returned (bias gradient of the last conv sums these)
-        if ctx.out_rows and (ctx.has_ln or pad is None):
+        plan, params, graph, ps = ctx.plan, ctx.params, ctx.graph, ctx.ps
+        L, B, n, pad = len(plan.convs), plan.B, plan.n, plan.padded_last
+        G = _Grads(list(params), list(ctx.needs_input_grad[10:]))
+        g = _incoming_grad(plan, ctx.split, ctx.land, ctx.lat, graph, dy)
+        b_src = dy3 = g.dy  # b_src: what the last conv's bias gradient sums - without a LayerNorm, the rows that were returned
+        if plan.out_rows and pad is None:
             dy3 = hip.pad_rows(dy3, n, dy3.shape[2])  # rows that were not returned carry a zero gradient
+        Fo = plan.convs[-1].Fout
         bi_last = 2 * L - 1
-        cs_done = False
-        if ctx.has_ln:
+        cs = None
+        if plan.ln is not None:
             gi, bi = len(params) - 2, len(params) - 1
             dgam = G.dst[gi] if G.dst[gi] is not None else torch.zeros_like(params[gi])
             dbet = G.dst[bi] if G.dst[bi] is not None else torch.zeros_like(params[bi])
             # the LayerNorm backward also sums its dx over the rows: that IS the bias gradient of the last conv
-            cs = G.dst[bi_last] if (pad is None and _LN_COLSUM) else None
-            if ctx.present is not None and dy_map is None:
+            cs = G.dst[bi_last] if plan.ln_colsum else None
+            if plan.ln == "mapped_skip" and g.kind != "mapped":
                 raise RuntimeError("the processor's output received a gradient from outside the decoder-input gather, but its "
                                    "dropped rows were not kept (set GCL_NO_ROW_SKIP=1 to keep them)")
-            dp = hip.layernorm_bwd(None if dy_map is not None else dy3.view(B * n, -1), ps[-1].view(B * n, -1),
+            dp = hip.layernorm_bwd(None if g.kind == "mapped" else dy3.view(B * n, -1), ps[-1].view(B * n, -1),
                                    params[gi].detach(), ctx.stats, dgam, dbet, G.acc[gi] and G.acc[bi], colsum_dx=cs,
-                                   acc_colsum=bool(cs is not None and G.acc[bi_last]), dy_map=dy_map,
-                                   skip=ctx.present is not None).view(B, n, -1)
-            cs_done = cs is not None
-        else:
-            dp = dy3
-        si = 2 * L
-        dsl = G.dst[si] if params[si] is not None else None
-        slope_t, akind = ctx.slope_t, ctx.akind
-        dx = None
-        Fo = params[2 * (L - 1)].shape[0]
-        Fp = Fo
-        if pad is not None:
-            # The last conv ran Fp = roundup(Fout, 4) wide (zero padding columns).  Its gradient is widened to that
-            # layout (extra rows / columns 0) in one pass; the dense backward then reads it Fout wide with row stride Fp
+                                   acc_colsum=bool(cs is not None and G.acc[bi_last]), dy_map=g.dy_map,
+                                   skip=plan.ln == "mapped_skip").view(B, n, -1)
+            b_src = dp
+        elif pad is not None:
+            # The last conv ran ldh = roundup(Fout, 4) wide (zero padding columns).  Its gradient is widened to that
+            # layout (extra rows / columns 0) in one pass; the dense backward then reads it Fout wide with row stride ldh
             # - the padding columns only ever meet zero weights - so dW / dX need no padded weight copy.
-            Fp = pad[0]
-            dp = hip.pad_rows(dy_rows if not ctx.has_ln else dp, n, Fp) if wide is None else None
-        if G.dst[bi_last] is not None and not cs_done:  # bias of the last conv: its dp comes from outside this stack
-            src = dy_rows if not ctx.has_ln else dp[..., :Fo]
-            if parts is not None:
-                hip.colsum_split(parts[0], parts[1], G.dst[bi_last], G.acc[bi_last])
-            elif wide is not None:  # the same rows, Fp apart (a reshape would copy them)
-                hip.colsum(torch.as_strided(dy, (B * dy.shape[1], Fo), (Fp, 1), dy.storage_offset()), G.dst[bi_last],
+            dp = hip.pad_rows(g.dy, n, pad[0]) if g.kind != "wide" else None
+        else:
+            dp = dy3  # (with parts: the token - only aggregate_split may read "it", through g.parts)
+        if G.dst[bi_last] is not None and cs is None:  # bias of the last conv: its dp comes from outside this stack
+            if g.kind == "parts":
+                hip.colsum_split(g.parts[0], g.parts[1], G.dst[bi_last], G.acc[bi_last])
+            elif g.kind == "wide":  # the same rows, ldh apart (a reshape would copy them)
+                hip.colsum(torch.as_strided(g.dy, (B * g.dy.shape[1], Fo), (pad[0], 1), g.dy.storage_offset()), G.dst[bi_last],
                            G.acc[bi_last])
             else:
-                hip.colsum(src.reshape(-1, Fo), G.dst[bi_last], G.acc[bi_last])
-        dzc = None
-        assert ctx.present is None or parts is None  # (with parts `dp` is the token: only aggregate_split may read "it")
+                hip.colsum(b_src.reshape(-1, Fo), G.dst[bi_last], G.acc[bi_last])
+        si = 2 * L
+        dsl = G.dst[si] if params[si] is not None else None
+        akind, slope_t = _stack_act(ctx.owner, params[si])
+        dx = dzc = None
         for k in range(L - 1, -1, -1):
-            W = params[2 * k].detach()
-            wi = 2 * k
-            inp = (ctx.x3 if k == 0 else ps[k - 1]).view(-1, (ctx.x3 if k == 0 else ps[k - 1]).shape[-1])
-            if k == L - 1 and ctx.present is not None:
+            st, last = plan.convs[k], k == L - 1
+            W, wi = params[2 * k].detach(), 2 * k
+            inp = ctx.x3 if k == 0 else ps[k - 1]
+            inp = inp.view(-1, inp.shape[-1])
+            if last and plan.ln == "mapped_skip":
                 # the dropped rows of dp were not written: their zeros come from the table
-                dh2 = hip.aggregate_present(graph, dp, ctx.present, transpose=True).view(B * n, -1)
-            elif k == L - 1 and parts is not None:
-                dh2 = hip.aggregate_split(graph, parts[0], parts[1], transpose=True).view(B * n, -1)
-            elif k == L - 1 and wide is not None:
-                dh2 = hip.aggregate_head(graph, wide, transpose=True).view(B * n, -1)
-            elif (k == 0 and ctx.lat is not None and ctx.lat.smap is not None and ctx.lat.Md > 0 and _compact_store()
-                  and dp.is_contiguous() and hip.aggregate_compact_ok(graph, dp, transpose=True)):
-                # the Md batch-dependent rows go straight into the compact gradient of _lat_first_layer_bwd, the others
-                # (their batch sums are taken from there) to their usual place: every row is written once
+                dh3 = hip.aggregate_present(graph, dp, ctx.present, transpose=True)
+            elif last and g.kind == "parts":
+                dh3 = hip.aggregate_split(graph, g.parts[0], g.parts[1], transpose=True)
+            elif last and g.kind == "wide":
+                dh3 = hip.aggregate_head(graph, g.wide, transpose=True)
+            elif k == 0 and g.compact:
+                _expect_dense(dp, B, n, dp.shape[2], aligned=False)
                 dzc = torch.empty(B, ctx.lat.Md + ctx.lat.r, dp.shape[2], dtype=torch.float32, device=dp.device)
-                dh2 = hip.aggregate_compact(graph, dp, ctx.lat.smap, dzc, transpose=True).view(B * n, -1)
+                dh3 = hip.aggregate_compact(graph, dp, ctx.lat.smap, dzc, transpose=True)
             else:
-                dh2 = hip.aggregate(graph, dp, None, transpose=True).view(B * n, -1)
-            if k == L - 1 and Fp != Fo:
-                dh2 = dh2[:, :Fo]  # [rows, Fout] view with row stride Fp
+                dh3 = hip.aggregate(graph, dp, None, transpose=True)
+            dh2 = dh3.view(B * n, -1)
+            if last and pad is not None:
+                dh2 = dh2[:, :Fo]  # [rows, Fout] view with row stride ldh
             dW = G.dst[wi] if G.dst[wi] is not None else torch.zeros_like(params[wi])
             if k > 0:
                 # one fused launch: dp_{k-1} (with PReLU'), dW_k, d(slope) and the bias gradient of
                 # conv k-1 (= column sums of dp_{k-1}), which accumulates by ITS parameter's state
                 dp = hip.linear_bwd_all(dh2, W, inp, slope_t, dsl, dW, None, G.dst[2 * k - 1], G.acc[wi],
                                         acc_colsum=G.acc[2 * k - 1], act=akind).view(B, n, -1)
-            elif ctx.lat is not None:
-                if ctx.enc_shape is not None:  # the forward read the compact rows themselves (LatSource.tail)
-                    dx = _lat_first_layer_bwd(ctx.lat, None, dh2.reshape(B, n, -1), W, dW, G.acc[wi], ctx.needs_input_grad[0],
-                                              Pc=ctx.x3, enc_shape=ctx.enc_shape, dzc=dzc)
-                else:
-                    dx = _lat_first_layer_bwd(ctx.lat, ctx.x3, dh2.reshape(B, n, -1), W, dW, G.acc[wi],
-                                              ctx.needs_input_grad[0], dzc=dzc)
+            elif st.kind == "tab":
+                # with enc_shape the forward read the compact rows themselves (LatSource.tail): x3 IS Pc
+                dx = _lat_first_layer_bwd(ctx.lat, None if plan.enc_shape else ctx.x3, dh2.reshape(B, n, -1), W, dW, G.acc[wi],
+                                          ctx.needs_input_grad[0], Pc=ctx.x3 if plan.enc_shape else None,
+                                          enc_shape=plan.enc_shape, dzc=dzc)
             elif ctx.needs_input_grad[0]:
                 dx = hip.linear_bwd_all(dh2, W, inp, None, None, dW, None, None, G.acc[wi],
                                         act=hip.ACT_NONE).view(B, n, -1)
             else:
                 hip.linear_bwd_dw(dh2, inp, None, dW, None, G.acc[wi])
-        if dx is not None and ctx.squeeze:
+        if dx is not None and plan.squeeze:
             dx = dx[0]
         return (dx,) + (None,) * 9 + G.out()
 
