@@ -24,11 +24,15 @@
 #include "colsum.h"
 #include "common.h"
 #include "mfma_io.h"
+#include "unet_src.h"
 
 namespace {
 
 using gcl::mfma_io::d_row;
 using gcl::mfma_io::f32x16;
+using gcl::unet_src::gelu_erf;
+using gcl::unet_src::src_read;
+using gcl::unet_src::Vec;
 
 std::atomic<int64_t> g_launches{0};
 
@@ -53,70 +57,6 @@ struct ConvArgs {
   float* y;
   int32_t H, W, Cin, Cout, G, NT, TX;
 };
-
-template <int V>
-struct Vec {
-  float v[V];
-};
-template <int V>
-__device__ __forceinline__ Vec<V> ldv(const float* p) {
-  Vec<V> r;
-  if constexpr (V == 4) {
-    const float4 t = *reinterpret_cast<const float4*>(p);
-    r.v[0] = t.x, r.v[1] = t.y, r.v[2] = t.z, r.v[3] = t.w;
-  } else {
-    r.v[0] = *p;
-  }
-  return r;
-}
-
-// torch's max_pool2d update: a NaN replaces the running maximum and then stays
-__device__ __forceinline__ float pool_take(float m, float v) { return (v > m || v != v) ? v : m; }
-
-// V channels c .. c+V-1 (all < Cin, and on one side of C1) of input pixel (y, x) of sample b; 0 <= y < H, 0 <= x < W
-template <int KIND, int V>
-__device__ __forceinline__ Vec<V> src_read(const ConvArgs& s, int64_t b, int y, int x, int c) {
-  if constexpr (KIND == GCL_UNET_SRC_PLANAR) {
-    static_assert(V == 1, "planar sources are read channel by channel");
-    return ldv<1>(s.a + ((b * s.Cin + c) * s.H + y) * s.W + x);
-  } else if constexpr (KIND == GCL_UNET_SRC_ROWS) {
-    return ldv<V>(s.a + ((b * s.H + y) * s.W + x) * s.Cin + c);
-  } else if constexpr (KIND == GCL_UNET_SRC_POOL) {
-    const float* p = s.a + ((b * s.Hs + 2 * y) * s.Ws + 2 * x) * s.Cin + c;
-    const int64_t row = (int64_t)s.Ws * s.Cin;
-    const Vec<V> v00 = ldv<V>(p), v01 = ldv<V>(p + s.Cin), v10 = ldv<V>(p + row), v11 = ldv<V>(p + row + s.Cin);
-    Vec<V> r;
-#pragma unroll
-    for (int i = 0; i < V; ++i) {
-      float m = -INFINITY;
-      m = pool_take(m, v00.v[i]);
-      m = pool_take(m, v01.v[i]);
-      m = pool_take(m, v10.v[i]);
-      m = pool_take(m, v11.v[i]);
-      r.v[i] = m;
-    }
-    return r;
-  } else {
-    if (c < s.C1) return ldv<V>(s.a + ((b * s.H + y) * s.W + x) * s.C1 + c);
-    Vec<V> r;
-#pragma unroll
-    for (int i = 0; i < V; ++i) r.v[i] = 0.f;
-    if (y >= 2 * s.Hs || x >= 2 * s.Ws) return r;  // the pad to the skip's size
-    const float fy = s.sy * (float)y, fx = s.sx * (float)x;
-    const int y0 = (int)fy, x0 = (int)fx;
-    const int y1 = y0 + (y0 < s.Hs - 1 ? 1 : 0), x1 = x0 + (x0 < s.Ws - 1 ? 1 : 0);
-    const float ly = fy - (float)y0, lx = fx - (float)x0, hy = 1.f - ly, hx = 1.f - lx;
-    const float* base = s.b + b * s.Hs * s.Ws * s.C2 + (c - s.C1);
-    const Vec<V> v00 = ldv<V>(base + ((int64_t)y0 * s.Ws + x0) * s.C2), v01 = ldv<V>(base + ((int64_t)y0 * s.Ws + x1) * s.C2),
-                 v10 = ldv<V>(base + ((int64_t)y1 * s.Ws + x0) * s.C2), v11 = ldv<V>(base + ((int64_t)y1 * s.Ws + x1) * s.C2);
-#pragma unroll
-    for (int i = 0; i < V; ++i)
-      r.v[i] = hy * (hx * v00.v[i] + lx * v01.v[i]) + ly * (hx * v10.v[i] + lx * v11.v[i]);
-    return r;
-  }
-}
-
-__device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752440f)); }
 
 template <int KIND, int V, int NW>
 __global__ __launch_bounds__(64 * NW) void unet_conv3x3_kernel(const ConvArgs s) {

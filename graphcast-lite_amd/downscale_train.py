@@ -5,13 +5,16 @@ The reference evaluates `masked_mse_loss`, `spectral_loss` and `gradient_loss` (
 two `rfft2` per step; here the three terms and `d loss / d out` come from `csrc/downscale_loss.hip`
 (`gcl_downscale_loss_fwd_bwd`, `gcl_downscale_spectral_fwd_bwd`) in float64 sums with a fixed order, and
 `compute_metrics` (:271-310) from `gcl_downscale_metrics`.  `train_epoch`, `validate`, `compute_metrics` and
-`fit_downscaler` (the loop of :422-506) take any callable that maps X [B, obs * C + Ns, H, W] to [B, C, H, W]: the
-network itself is not part of this module.  Differences from the reference: sums in float64 (it sums in float32), the
+`fit_downscaler` (the loop of :422-506) take any callable that maps X [B, obs * C + Ns, H, W] to [B, C, H, W]; on the HIP
+path that is `unet.TrainableUNet`, whose forward in training mode and backward run on `csrc/unet_train.hip`.
+`python -m graphcast_lite_amd.downscale_train <experiment_dir> --data-dir D` (`build_parser`, `main`) is the script's
+`main` (:316-420): config defaults, datasets, `TrainableUNet`, AdamW, cosine schedule, `fit_downscaler`.  Differences from the reference: sums in float64 (it sums in float32), the
 random draws come from the caller's `torch.Generator` (`iter_batches`), and the losses accept 2 <= H, W <= 256 and
 C <= 64 only.
 """
 import json
 import os
+import sys
 from datetime import datetime
 from typing import Optional, Sequence
 
@@ -216,8 +219,8 @@ def train_epoch(model, batches, optimizer, channel_mask, residual, spectral_weig
                 obs_window=None, per_batch=None):
     """`train_downscaler.py:226-252` over any iterable of (X, Y) device tensors: the mean of the per-batch losses.  The
     objective and its gradient with respect to the network's output are `downscaler_loss`; the backward pass of the
-    network, gradient clipping (`clip_grad_norm_`, max norm 1.0) and `optimizer.step()` act on the caller's network and
-    stay torch calls.  The losses are added on the device (float64) and read once at the end.  per_batch: a list
+    network is the caller's network's own (`unet.TrainableUNet`: the kernels of csrc/unet_train.hip, through autograd);
+    gradient clipping (`clip_grad_norm_`, max norm 1.0) and `optimizer.step()` stay torch calls.  The losses are added on the device (float64) and read once at the end.  per_batch: a list
     that receives every batch's loss as a 0-dim GPU tensor."""
     _set_mode(model, True)
     total, n = None, 0
@@ -269,7 +272,8 @@ def fit_downscaler(model, optimizer, scheduler, train_ds, val_ds, test_ds, exp_d
                    batch_size: int = 32, channel_mask=None, residual: bool = False, spectral_weight: float = 0.0,
                    gradient_weight: float = 0.0, static_channels=None, var_names=None, generator=None,
                    data_dir: str = "", log=print):
-    """The loop of `train_downscaler.py:422-506` around a caller-supplied network, optimizer and scheduler: epochs of
+    """The loop of `train_downscaler.py:422-506` around a caller-supplied network (`unet.TrainableUNet` on the HIP path;
+    any nn.Module that maps X to the output works), optimizer and scheduler: epochs of
     `train_epoch` (shuffled, last short batch dropped) and `validate`, the best state in exp_dir/best_model.pth, early
     stopping after `patience` epochs without a better validation loss, then the best state reloaded, the test loss and
     the table of `compute_metrics`; everything logged to exp_dir/training_log.txt in the reference's format (the
@@ -339,3 +343,86 @@ def fit_downscaler(model, optimizer, scheduler, train_ds, val_ds, test_ds, exp_d
         json.dump(results, fh, indent=2)
     _log(f"\nResults saved to {exp_dir}")
     return results
+
+
+# ======================================================================================================================
+# The entry point
+# ======================================================================================================================
+CONFIG_DEFAULTS = {  # train_downscaler.py:344-354
+    "num_features": 19, "obs_window": 2, "batch_size": 32, "learning_rate": 1e-3, "num_epochs": 50, "patience": 15,
+    "base_filters": 64, "static_context": True, "residual": False, "static_channels": [7, 8], "random_seed": 42,
+}
+WIND_U_NAMES = ("10u", "u@850", "u@500")  # :366-369: negated on a horizontal flip
+
+
+def build_parser():
+    """The options of scripts/train_downscaler.py:317-330 with the reference's names, types and defaults."""
+    import argparse
+
+    ap = argparse.ArgumentParser(prog="python -m graphcast_lite_amd.downscale_train")
+    ap.add_argument("experiment_dir", help="e.g. experiments/downscaler_krsk")
+    ap.add_argument("--data-dir", required=True, help="Path to downscaler dataset")
+    ap.add_argument("--gnn-input", action="store_true", help="Use GNN predictions (gnn_pred.npy) instead of ERA5 coarse")
+    ap.add_argument("--spectral-weight", type=float, default=0.0, help="Weight for FFT spectral loss (e.g. 0.1)")
+    ap.add_argument("--gradient-weight", type=float, default=0.0, help="Weight for spatial gradient loss (e.g. 0.05)")
+    ap.add_argument("--input-noise", type=float, default=0.0, help="Gaussian noise sigma added to input (e.g. 0.05)")
+    ap.add_argument("--augment-flip", action="store_true", help="Random horizontal flip augmentation")
+    return ap
+
+
+def load_config(exp_dir: str) -> dict:
+    """exp_dir/config.json over `CONFIG_DEFAULTS` (:336-354); a missing file gives the defaults."""
+    cfg = dict(CONFIG_DEFAULTS)
+    path = os.path.join(exp_dir, "config.json")
+    if os.path.exists(path):
+        with open(path) as fh:
+            cfg.update({k: v for k, v in json.load(fh).items() if k in CONFIG_DEFAULTS})
+    return cfg
+
+
+def wind_u_channels(data_dir: str):
+    """:364-369: the indices of the wind-u variables in data_dir/variables.json (none when the file is missing)."""
+    path = os.path.join(data_dir, "variables.json")
+    if not os.path.exists(path):
+        return ()
+    with open(path) as fh:
+        return tuple(i for i, v in enumerate(json.load(fh)) if v in WIND_U_NAMES)
+
+
+def main(argv=None, device="cuda:0", log=print):
+    """`python -m graphcast_lite_amd.downscale_train <experiment_dir> --data-dir D [options]`: `main` of
+    scripts/train_downscaler.py (:316-506) with `unet.TrainableUNet` as the network.  Returns the results dictionary of
+    `fit_downscaler`."""
+    from .downscale import DownscalerDataset
+    from .unet import TrainableUNet
+
+    args = build_parser().parse_args(sys.argv[1:] if argv is None else argv)
+    exp_dir = args.experiment_dir
+    os.makedirs(exp_dir, exist_ok=True)
+    cfg = load_config(exp_dir)
+    C, obs, static_ch = cfg["num_features"], cfg["obs_window"], cfg["static_channels"]
+    torch.manual_seed(cfg["random_seed"])
+    np.random.seed(cfg["random_seed"])
+    wind_u = wind_u_channels(args.data_dir)
+    if args.augment_flip and wind_u and log is not None:
+        log(f"Wind-u channels to negate on flip: {wind_u}")
+    kw = dict(obs_window=obs, static_context=cfg["static_context"], use_gnn_input=args.gnn_input, device=device)
+    train_ds = DownscalerDataset(args.data_dir, split="train", augment_flip=args.augment_flip, input_noise=args.input_noise,
+                                 wind_u_channels=wind_u, **kw)
+    val_ds = DownscalerDataset(train_ds.pairs, split="val", **kw)
+    test_ds = DownscalerDataset(train_ds.pairs, split="test", **kw)
+    n_static = len(static_ch) if cfg["static_context"] else 0
+    in_channels = obs * C + n_static
+    model = TrainableUNet(in_channels=in_channels, out_channels=C, base_filters=cfg["base_filters"]).to(device)
+    if log is not None:
+        log(f"WeatherUNet: {model.num_params:,} params | in={in_channels} out={C} filters={cfg['base_filters']}")
+        log(f"Grid: {train_ds.n_lat}x{train_ds.n_lon} (HxW) | obs={obs}")
+    optimizer = torch.optim.AdamW(model.parameters(), lr=cfg["learning_rate"], weight_decay=1e-5)
+    scheduler = torch.optim.lr_scheduler.CosineAnnealingLR(optimizer, T_max=cfg["num_epochs"])
+    return fit_downscaler(model, optimizer, scheduler, train_ds, val_ds, test_ds, exp_dir, cfg["num_epochs"], cfg["patience"],
+                          batch_size=cfg["batch_size"], residual=cfg["residual"], spectral_weight=args.spectral_weight,
+                          gradient_weight=args.gradient_weight, static_channels=static_ch, data_dir=args.data_dir, log=log)
+
+
+if __name__ == "__main__":
+    main()

@@ -250,6 +250,19 @@ _SIGNATURES = {
     "gcl_cascade_pack": (C.c_int, [_vp] * 8 + [_i32] * 6 + [_vp]),
     "gcl_cascade_scores_ws_bytes": (_sz, [_i32] * 4),
     "gcl_cascade_scores": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp] + [_i32] * 6 + [_vp, _sz, _vp]),
+    "gcl_unet_train_launches": (_i64, []),
+    "gcl_unet_colsum_ws_bytes": (_sz, [_i64, _i64]),
+    "gcl_unet_bn_stats": (C.c_int, [_vp, _i64, _i32, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "gcl_unet_bn_gelu": (C.c_int, [_vp] * 6 + [_i64, _i32, _vp]),
+    "gcl_unet_bn_gelu_bwd": (C.c_int, [_vp] * 9 + [_i64, _i32, _vp, _sz, _vp]),
+    "gcl_unet_wgrad_chunks": (_i32, [_i32] * 5),
+    "gcl_unet_wgrad_ws_bytes": (_sz, [_i32] * 5),
+    "gcl_unet_conv3x3_wgrad": (C.c_int, [_vp, _vp, _vp] + [_i32] * 5 + [_vp, _sz, _vp]),
+    "gcl_unet_pack_weights_dgrad": (C.c_int, [_vp, _i32, _i32, _vp, _vp]),
+    "gcl_unet_pool_bwd": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _vp]),
+    "gcl_unet_upsample_bwd": (C.c_int, [_vp, _i64, _i32, _vp] + [_i32] * 6 + [_vp]),
+    "gcl_unet_conv1x1_out_bwd_ws_bytes": (_sz, [_i32] * 5),
+    "gcl_unet_conv1x1_out_bwd": (C.c_int, [_vp] * 6 + [_i32] * 5 + [_vp, _sz, _vp]),
 }
 
 
@@ -2621,3 +2634,149 @@ def cascade_scores(out, coarse_phys, fine, t_fine, t_persist, ds_mean, ds_std, s
                                     _pl(t_persist), _p(ds_mean), _p(ds_std), _pd(state), _pl(count), int(step),
                                     state.shape[0], B, H, W, Cc, ws.data_ptr(), ws.numel() * ws.element_size(), _stream()))
     return state
+
+
+# ======================================================================================================================
+# WeatherUNet training (csrc/unet_train.hip)
+# ======================================================================================================================
+def unet_train_launches() -> int:
+    """Kernels launched by the entry points of csrc/unet_train.hip in this process."""
+    return int(lib().gcl_unet_train_launches())
+
+
+def _ws_for(need: int, ws, device):
+    """(pointer, bytes) of the caller's scratch tensor, or of the shared workspace when None."""
+    if ws is None:
+        ws = workspace(need, device)
+    return ws.data_ptr(), ws.numel() * ws.element_size()
+
+
+def _rows(t, who):
+    if t.dim() < 2 or not t.is_contiguous():
+        raise ValueError(f"{who}: a contiguous [..., C] tensor expected, got {tuple(t.shape)}")
+    return t.numel() // t.shape[-1], t.shape[-1]
+
+
+def unet_bn_stats(z, eps: float, momentum: float, mean, invstd, running_mean=None, running_var=None,
+                  num_batches=None, ws=None):
+    """(mean, invstd) float32 [C] of the rows of z [..., C]; the running buffers and the int64 counter are updated in
+    place when given (see gcl_unet_bn_stats)."""
+    n, Cc = _rows(z, "unet_bn_stats")
+    if any(t is not None and (t.numel() != Cc or not t.is_contiguous()) for t in (mean, invstd, running_mean, running_var)):
+        raise ValueError(f"unet_bn_stats: vectors of {Cc} values expected")
+    if n < 2:
+        raise ValueError(f"unet_bn_stats: expected more than 1 value per channel when training, got {n}")
+    if num_batches is not None and (num_batches.dtype != torch.int64 or num_batches.numel() != 1 or not num_batches.is_cuda):
+        raise ValueError("unet_bn_stats: num_batches is one int64 on the device")
+    wp, wb = _ws_for(int(lib().gcl_unet_colsum_ws_bytes(n, 2 * Cc)), ws, z.device)
+    _check(lib().gcl_unet_bn_stats(_p(z), n, Cc, float(eps), float(momentum), _p(mean), _p(invstd), _p(running_mean),
+                                   _p(running_var), None if num_batches is None else num_batches.data_ptr(), wp, wb,
+                                   _stream()))
+    return mean, invstd
+
+
+def unet_bn_gelu(z, gamma, beta, mean, invstd, out):
+    """out = gelu(gamma * (z - mean) * invstd + beta) over the rows of z [..., C] (see gcl_unet_bn_gelu)."""
+    n, Cc = _rows(z, "unet_bn_gelu")
+    if out.shape != z.shape or not out.is_contiguous():
+        raise ValueError("unet_bn_gelu: out has z's shape")
+    _check(lib().gcl_unet_bn_gelu(_p(z), _p(gamma), _p(beta), _p(mean), _p(invstd), _p(out), n, Cc, _stream()))
+    return out
+
+
+def unet_bn_gelu_bwd(z, dA, gamma, beta, mean, invstd, dZ, dgamma, dbeta, ws=None):
+    """(dZ, dgamma, dbeta) of gelu(batch_norm(z)) given dA; dZ may be dA (see gcl_unet_bn_gelu_bwd)."""
+    n, Cc = _rows(z, "unet_bn_gelu_bwd")
+    if dA.shape != z.shape or dZ.shape != z.shape or not (dA.is_contiguous() and dZ.is_contiguous()):
+        raise ValueError("unet_bn_gelu_bwd: dA and dZ have z's shape")
+    if dgamma.numel() != Cc or dbeta.numel() != Cc:
+        raise ValueError(f"unet_bn_gelu_bwd: dgamma and dbeta of {Cc} values expected")
+    wp, wb = _ws_for(int(lib().gcl_unet_colsum_ws_bytes(n, 2 * Cc)), ws, z.device)
+    _check(lib().gcl_unet_bn_gelu_bwd(_p(z), _p(dA), _p(gamma), _p(beta), _p(mean), _p(invstd), _p(dZ), _p(dgamma),
+                                      _p(dbeta), n, Cc, wp, wb, _stream()))
+    return dZ, dgamma, dbeta
+
+
+def unet_wgrad_chunks(B: int, H: int, W: int, Cin: int, Cout: int) -> int:
+    """The pixel chunks gcl_unet_conv3x3_wgrad splits this shape into."""
+    return int(lib().gcl_unet_wgrad_chunks(B, H, W, Cin, Cout))
+
+
+def unet_wgrad_ws_bytes(B: int, H: int, W: int, Cin: int, Cout: int) -> int:
+    return int(lib().gcl_unet_wgrad_ws_bytes(B, H, W, Cin, Cout))
+
+
+def unet_conv3x3_wgrad(src: UnetSrc, dZ, Cin: int, dW=None, ws=None):
+    """dW [Cout, Cin, 3, 3] of the 3x3 convolution that read `src`, from dZ [B, H, W, Cout] (see
+    gcl_unet_conv3x3_wgrad)."""
+    if dZ.dim() != 4 or not dZ.is_contiguous():
+        raise ValueError("unet_conv3x3_wgrad: dZ is a contiguous [B, H, W, Cout] tensor")
+    B, H, W, Cout = dZ.shape
+    if dW is None:
+        dW = torch.empty(Cout, int(Cin), 3, 3, dtype=torch.float32, device=dZ.device)
+    elif tuple(dW.shape) != (Cout, int(Cin), 3, 3) or not dW.is_contiguous():
+        raise ValueError(f"unet_conv3x3_wgrad: dW is a contiguous [{Cout}, {Cin}, 3, 3] tensor")
+    wp, wb = _ws_for(unet_wgrad_ws_bytes(B, H, W, int(Cin), Cout), ws, dZ.device)
+    _check(lib().gcl_unet_conv3x3_wgrad(C.byref(src), _p(dZ), _p(dW), B, H, W, int(Cin), Cout, wp, wb, _stream()))
+    return dW
+
+
+def unet_pack_weights_dgrad(w, out=None):
+    """torch's [Cout, Cin, 3, 3] weight transposed and tap-flipped, in the order gcl_unet_conv3x3 streams: the data
+    gradient is unet_conv3x3(unet_src(UNET_ROWS, dZ), packed, None, eps, dX [B, H, W, Cin], Cout)."""
+    if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3) or not w.is_contiguous():
+        raise ValueError(f"unet_pack_weights_dgrad: a contiguous [Cout, Cin, 3, 3] weight expected, got {tuple(w.shape)}")
+    Cout, Cin = w.shape[0], w.shape[1]
+    n = int(lib().gcl_unet_packed_floats(Cout, Cin))
+    if out is None:
+        out = torch.empty(n, dtype=torch.float32, device=w.device)
+    elif out.numel() != n or not out.is_contiguous():
+        raise ValueError(f"unet_pack_weights_dgrad: out holds {out.numel()} floats, {n} expected")
+    _check(lib().gcl_unet_pack_weights_dgrad(_p(w), Cin, Cout, _p(out), _stream()))
+    return out
+
+
+def unet_pool_bwd(act, dpooled, dA, skip=None):
+    """dA [B, Hs, Ws, C] = skip + the max-pool backward of dpooled [B, Hs // 2, Ws // 2, C] through the argmax of act;
+    skip: a [B, Hs, Ws, C] view of wider contiguous rows (a channel slice from 0), or None (see gcl_unet_pool_bwd)."""
+    B, Hs, Ws, Cc = act.shape
+    if tuple(dpooled.shape) != (B, Hs // 2, Ws // 2, Cc) or tuple(dA.shape) != (B, Hs, Ws, Cc) or not (
+            act.is_contiguous() and dpooled.is_contiguous() and dA.is_contiguous()):
+        raise ValueError(f"unet_pool_bwd: contiguous act / dA [{B}, {Hs}, {Ws}, {Cc}] and dpooled at half the size expected")
+    ld = 0
+    if skip is not None:
+        ld = skip.stride(2)
+        if tuple(skip.shape) != (B, Hs, Ws, Cc) or skip.stride(3) != 1 or skip.stride(1) != Ws * ld or skip.stride(0) != Hs * Ws * ld:
+            raise ValueError("unet_pool_bwd: skip is a leading channel slice of contiguous [B, Hs, Ws, ld] rows")
+    _check(lib().gcl_unet_pool_bwd(_p(act), _p(dpooled), _p(skip), int(ld), _p(dA), B, Hs, Ws, Cc, _stream()))
+    return dA
+
+
+def unet_upsample_bwd(d, c_off: int, dlow):
+    """dlow [B, Hs, Ws, C2] = the adjoint of upsample-and-pad applied to channels c_off .. c_off + C2 of the contiguous
+    d [B, H, W, ld] (see gcl_unet_upsample_bwd)."""
+    B, H, W, ld = d.shape
+    if dlow.dim() != 4 or dlow.shape[0] != B or not (d.is_contiguous() and dlow.is_contiguous()):
+        raise ValueError("unet_upsample_bwd: contiguous d [B, H, W, ld] and dlow [B, Hs, Ws, C2] expected")
+    _check(lib().gcl_unet_upsample_bwd(_p(d), ld, int(c_off), _p(dlow), B, H, W, dlow.shape[1], dlow.shape[2],
+                                       dlow.shape[3], _stream()))
+    return dlow
+
+
+def unet_conv1x1_out_bwd(dY, a, w, dA, dW=None, db=None, ws=None):
+    """(dA [B, H, W, F], dW [Cout, F], db [Cout]) of unet_conv1x1_out from the planar dY [B, Cout, H, W] (see
+    gcl_unet_conv1x1_out_bwd)."""
+    B, H, W, F = a.shape
+    Cout = w.shape[0]
+    if tuple(dY.shape) != (B, Cout, H, W) or tuple(dA.shape) != (B, H, W, F) or tuple(w.shape) != (Cout, F) or not (
+            dY.is_contiguous() and a.is_contiguous() and w.is_contiguous() and dA.is_contiguous()):
+        raise ValueError(f"unet_conv1x1_out_bwd: contiguous dY [{B}, {Cout}, {H}, {W}], a / dA [B, H, W, F], w [Cout, F] expected")
+    if dW is None:
+        dW = torch.empty(Cout, F, dtype=torch.float32, device=a.device)
+    if db is None:
+        db = torch.empty(Cout, dtype=torch.float32, device=a.device)
+    if dW.numel() != Cout * F or db.numel() != Cout or not (dW.is_contiguous() and db.is_contiguous()):
+        raise ValueError("unet_conv1x1_out_bwd: dW [Cout, F] and db [Cout] expected")
+    wp, wb = _ws_for(int(lib().gcl_unet_conv1x1_out_bwd_ws_bytes(B, H, W, F, Cout)), ws, a.device)
+    _check(lib().gcl_unet_conv1x1_out_bwd(_p(dY), _p(a), _p(w), _p(dA), _p(dW), _p(db), B, H, W, F, Cout, wp, wb, _stream()))
+    return dA, dW, db

@@ -6,8 +6,9 @@ reference checkpoint works with `strict=True`.  The forward is 15 launches of `c
 bilinear Upsample, the pad to the skip's size and the concatenation are not launches: they are how the next convolution
 reads its input.  Activations are channels-last `[B, H, W, C]` float32 tensors of a per-shape workspace the module holds.
 
-The HIP path is inference-only: there is no backward and no BatchNorm in training mode.  Training runs the reference's
-torch module through `downscale.fit_downscaler`.
+`WeatherUNet` is inference-only: its forward refuses training mode.  `TrainableUNet` is the same module tree with a
+training forward (BatchNorm on batch statistics, running buffers updated) and a backward on `csrc/unet_train.hip`, one
+`torch.autograd.Function` over the 44 parameters: what `downscale_train.fit_downscaler` trains.
 """
 import torch
 import torch.nn as nn
@@ -173,6 +174,236 @@ class WeatherUNet(nn.Module):
         res = x[:, residual_from[0]:residual_from[1]] if residual_from is not None else None
         plan.append(("out_conv", lambda: hip.unet_conv1x1_out(a[13], oc.weight.view(self.out_channels, f), oc.bias, y,
                                                               residual=res, res_bs=x.stride(0))))
+        return plan
+
+
+def _levels(H, W):
+    sizes = [(H, W)]
+    for _ in range(3):
+        sizes.append((sizes[-1][0] // 2, sizes[-1][1] // 2))
+    return sizes
+
+
+class _TrainWorkspace:
+    """What one training step of one shape keeps between forward and backward: per convolution the raw output z, the
+    activation a, the batch mean and invstd and the gradient buffer dA (dZ overwrites it); per pooled or concatenated
+    convolution the data gradient at the convolution's own input size.  `step` counts the forwards that wrote it."""
+
+    def __init__(self, f, cin, B, H, W, device):
+        sizes = _levels(H, W)
+        lv = [0, 0, 1, 1, 2, 2, 3, 3, 2, 2, 1, 1, 0, 0]
+        cout = [f, f, 2 * f, 2 * f, 4 * f, 4 * f, 8 * f, 8 * f, 4 * f, 4 * f, 2 * f, 2 * f, f, f]
+        self.cin = [cin, f, f, 2 * f, 2 * f, 4 * f, 4 * f, 8 * f, 12 * f, 4 * f, 6 * f, 2 * f, 3 * f, f]
+
+        def rows(k, c):
+            return torch.empty(B, sizes[k][0], sizes[k][1], c, dtype=torch.float32, device=device)
+
+        self.z = [rows(k, c) for k, c in zip(lv, cout)]
+        self.a = [rows(k, c) for k, c in zip(lv, cout)]
+        self.dA = [rows(k, c) for k, c in zip(lv, cout)]
+        self.mean = [torch.empty(c, dtype=torch.float32, device=device) for c in cout]
+        self.invstd = [torch.empty(c, dtype=torch.float32, device=device) for c in cout]
+        # the data gradients that are not a dA: POOL layers 2, 4, 6 (at the pooled size), UPCAT layers 8, 10, 12
+        self.dX = {i: rows(lv[i], self.cin[i]) for i in (2, 4, 6, 8, 10, 12)}
+        self.step = 0
+
+
+_UPCAT = {8: (5, 7), 10: (3, 9), 12: (1, 11)}  # convolution -> (skip activation, low activation)
+_POOL = {2: 1, 4: 3, 6: 5}                      # convolution -> pooled activation
+_SKIP_OF = {5: 8, 3: 10, 1: 12}                 # activation -> the UPCAT convolution that also read it
+
+
+class _UNetTrainStep(torch.autograd.Function):
+    """The training forward and the backward of `TrainableUNet` as one node over its parameters."""
+
+    @staticmethod
+    def forward(ctx, model, x, *params):
+        B, _, H, W = x.shape
+        ws = model._train_workspace(B, H, W, x.device)
+        y = torch.empty(B, model.out_channels, H, W, dtype=torch.float32, device=x.device)
+        for _, launch in model.train_launch_plan(x, y, ws):
+            launch()
+        ws.step += 1
+        ctx.model, ctx.ws, ctx.step, ctx.x = model, ws, ws.step, x
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        model, ws = ctx.model, ctx.ws
+        if ws.step != ctx.step:
+            raise RuntimeError("TrainableUNet: another training forward of the same shape has run since this one; its "
+                               "saved activations are gone (run backward before the next forward)")
+        params = list(model.parameters())
+        need = {id(p): ctx.needs_input_grad[2 + k] for k, p in enumerate(params)}
+        grads = {}
+        for _, launch in model.backward_launch_plan(ctx.x, g.to(torch.float32).contiguous(), ws, need, grads):
+            launch()
+        return (None, None) + tuple(grads.get(id(p)) if need[id(p)] else None for p in params)
+
+
+class TrainableUNet(WeatherUNet):
+    """`WeatherUNet` that also trains on the HIP path.  Same module tree, names, state dict and `num_params`.
+
+    Eval mode: the parent's forward, bit for bit.  Training mode: `forward(x)` is the forward of model.py:87-98 with
+    BatchNorm on the batch statistics (running_mean, running_var and num_batches_tracked updated as nn.BatchNorm2d does)
+    and returns y with a grad_fn; `y.backward(g)` leaves `.grad` on the 14 convolution weights, the 28 BatchNorm affine
+    vectors and out_conv's weight and bias.  There is no gradient with respect to x.  Per convolution the forward is
+    three entry points (`gcl_unet_conv3x3` with gamma NULL, `gcl_unet_bn_stats`, `gcl_unet_bn_gelu`) and the backward
+    `gcl_unet_bn_gelu_bwd`, `gcl_unet_conv3x3_wgrad` and, as the data gradient, `gcl_unet_conv3x3` on the transposed
+    tap-flipped weight, routed through `gcl_unet_pool_bwd` / `gcl_unet_upsample_bwd` where the input was pooled or
+    upsampled.  A backward must run before the next training forward of the same shape.  The module keeps the training
+    workspace of the most recent input shape only; `release_workspaces()` drops it."""
+
+    def __init__(self, in_channels: int, out_channels: int, base_filters: int = 64):
+        super().__init__(in_channels, out_channels, base_filters)
+        self._packed_dgrad = {}  # conv index -> ((data_ptr, _version), transposed tap-flipped pack)
+        self._train_ws = {}      # (device, B, H, W) -> _TrainWorkspace; the most recent shape only
+
+    def _ensure_packed_dgrad(self):
+        """The data-gradient packs of convolutions 1 .. 13, rebuilt for every weight that changed since its last pack."""
+        out = {}
+        for i, (conv, _) in enumerate(self._conv_list()):
+            if i == 0:
+                continue
+            w = conv.weight
+            key = (w.data_ptr(), w._version)
+            cur = self._packed_dgrad.get(i)
+            if cur is None or cur[0] != key:
+                buf = cur[1] if cur is not None and cur[1].device == w.device else None
+                cur = (key, hip.unet_pack_weights_dgrad(w.detach().contiguous(), out=buf))
+                self._packed_dgrad[i] = cur
+            out[i] = cur[1]
+        return out
+
+    def _train_workspace(self, B, H, W, device):
+        key = (str(device), B, H, W)
+        ws = self._train_ws.get(key)
+        if ws is None:
+            # one shape at a time (about 0.55 GB at 41 x 61, f = 64, B = 32): a new shape replaces the old one, whose
+            # memory is freed once no pending backward holds it
+            ws = _TrainWorkspace(self.base_filters, self.in_channels, B, H, W, device)
+            self._train_ws = {key: ws}
+        return ws
+
+    def release_workspaces(self):
+        """Drop the training workspace and the inference activations (they are rebuilt on the next forward)."""
+        self._train_ws, self._acts = {}, {}
+
+    def _sources(self, x, a):
+        S = hip.unet_src
+        names = ["inc.0", "inc.3", "down1.0", "down1.3", "down2.0", "down2.3", "down3.0", "down3.3", "up1.0", "up1.3",
+                 "up2.0", "up2.3", "up3.0", "up3.3"]
+        out = []
+        for i, name in enumerate(names):
+            if i == 0:
+                src = S(hip.UNET_PLANAR, x)
+            elif i in _UPCAT:
+                src = S(hip.UNET_UPCAT, a[_UPCAT[i][0]], a[_UPCAT[i][1]])
+            elif i in _POOL:
+                src = S(hip.UNET_POOL, a[_POOL[i]])
+            else:
+                src = S(hip.UNET_ROWS, a[i - 1])
+            out.append((name, src))
+        return out
+
+    def forward(self, x, residual_from=None):
+        """Eval mode: `WeatherUNet.forward`.  Training mode: x float32 [B, in_channels, H, W] on the GPU (not requiring
+        grad) -> y [B, out_channels, H, W] with a grad_fn; residual_from is refused (the loss adds x_last itself:
+        `downscaler_loss(..., X=X, residual=True)`)."""
+        if not self.training:
+            return super().forward(x, residual_from)
+        if residual_from is not None:
+            raise ValueError("TrainableUNet: residual_from is an inference option; in training the loss adds x_last "
+                             "(downscaler_loss(..., X=X, residual=True))")
+        if x.dim() != 4 or x.shape[1] != self.in_channels:
+            raise ValueError(f"TrainableUNet: input [B, {self.in_channels}, H, W] expected, got {tuple(x.shape)}")
+        B, _, H, W = x.shape
+        if H < MIN_GRID or W < MIN_GRID:
+            raise ValueError(f"TrainableUNet: the grid must be at least {MIN_GRID} x {MIN_GRID} (three poolings), got {H} x {W}")
+        if B * (H // 8) * (W // 8) < 2:
+            raise ValueError(f"TrainableUNet: expected more than 1 value per channel when training, got "
+                             f"{B} x {H // 8} x {W // 8} at the deepest level")
+        if x.requires_grad:
+            raise ValueError("TrainableUNet: an input that requires grad is not supported (there is no gradient with "
+                             "respect to x)")
+        if x.dtype != torch.float32:
+            raise RuntimeError(f"TrainableUNet needs float32 tensors, got {x.dtype} (there is no CPU fallback)")
+        if not x.is_cuda:
+            raise RuntimeError("TrainableUNet needs GPU tensors (there is no CPU fallback)")
+        for _, bn in self._conv_list():
+            if bn.momentum is None or not bn.track_running_stats:
+                raise ValueError("TrainableUNet: BatchNorm2d with a momentum and running statistics expected")
+        return _UNetTrainStep.apply(self, x.detach().contiguous(), *self.parameters())
+
+    def train_launch_plan(self, x, y, ws):
+        """The entry-point calls of a training forward of the contiguous x into y, in order: [(name, callable)]."""
+        packed = self._ensure_packed()
+        convs = self._conv_list()
+        plan = []
+        for i, (name, src) in enumerate(self._sources(x, ws.a)):
+            bn = convs[i][1]
+            plan.append((name, lambda src=src, i=i, eps=bn.eps: hip.unet_conv3x3(src, packed[i], None, eps, ws.z[i], ws.cin[i])))
+            plan.append((name + ".bn_stats", lambda i=i, bn=bn: hip.unet_bn_stats(
+                ws.z[i], bn.eps, bn.momentum, ws.mean[i], ws.invstd[i], bn.running_mean, bn.running_var,
+                bn.num_batches_tracked)))
+            plan.append((name + ".bn_gelu", lambda i=i, bn=bn: hip.unet_bn_gelu(
+                ws.z[i], bn.weight.detach(), bn.bias.detach(), ws.mean[i], ws.invstd[i], ws.a[i])))
+        oc, f = self.out_conv, self.base_filters
+        plan.append(("out_conv", lambda: hip.unet_conv1x1_out(ws.a[13], oc.weight.detach().view(self.out_channels, f),
+                                                              oc.bias.detach(), y)))
+        return plan
+
+    def backward_launch_plan(self, x, g, ws, need=None, grads=None):
+        """The entry-point calls of the backward of the last training forward on `ws`, given the planar g = d loss / d y,
+        in order: [(name, callable)].  grads (a dict) receives id(parameter) -> gradient, fresh tensors; need: id ->
+        bool (None: every parameter); only a convolution weight that needs none saves work (its wgrad)."""
+        grads = {} if grads is None else grads
+        wanted = (lambda p: True) if need is None else (lambda p: need[id(p)])
+        convs, f, dev = self._conv_list(), self.base_filters, x.device
+        packed_t = self._ensure_packed_dgrad()
+        sources = self._sources(x, ws.a)
+        oc = self.out_conv
+        plan = []
+
+        def new(*shape):
+            return torch.empty(*shape, dtype=torch.float32, device=dev)
+
+        def out_bwd():
+            dW, db = new(self.out_channels, f, 1, 1), new(self.out_channels)
+            hip.unet_conv1x1_out_bwd(g, ws.a[13], oc.weight.detach().view(self.out_channels, f), ws.dA[13], dW, db)
+            grads[id(oc.weight)], grads[id(oc.bias)] = dW, db
+
+        plan.append(("out_conv.bwd", out_bwd))
+        for i in range(13, -1, -1):
+            name, src = sources[i]
+            conv, bn = convs[i]
+
+            def bn_bwd(i=i, bn=bn):
+                dg, db = new(bn.num_features), new(bn.num_features)
+                hip.unet_bn_gelu_bwd(ws.z[i], ws.dA[i], bn.weight.detach(), bn.bias.detach(), ws.mean[i], ws.invstd[i],
+                                     ws.dA[i], dg, db)
+                grads[id(bn.weight)], grads[id(bn.bias)] = dg, db
+
+            plan.append((name + ".bn_gelu_bwd", bn_bwd))
+            if wanted(conv.weight):
+                def wgrad(i=i, src=src, conv=conv):
+                    grads[id(conv.weight)] = hip.unet_conv3x3_wgrad(src, ws.dA[i], ws.cin[i])
+
+                plan.append((name + ".wgrad", wgrad))
+            if i == 0:
+                break
+            target = ws.dX[i] if i in ws.dX else ws.dA[i - 1]
+            plan.append((name + ".dgrad", lambda i=i, target=target, eps=bn.eps: hip.unet_conv3x3(
+                hip.unet_src(hip.UNET_ROWS, ws.dA[i]), packed_t[i], None, eps, target, ws.dA[i].shape[3])))
+            if i in _UPCAT:
+                skip, low = _UPCAT[i]
+                plan.append((name + ".upsample_bwd", lambda i=i, skip=skip, low=low: hip.unet_upsample_bwd(
+                    ws.dX[i], ws.a[skip].shape[3], ws.dA[low])))
+            elif i in _POOL:
+                act = _POOL[i]
+                up = _SKIP_OF[act]
+                plan.append((name + ".pool_bwd", lambda i=i, act=act, up=up: hip.unet_pool_bwd(
+                    ws.a[act], ws.dX[i], ws.dA[act], skip=ws.dX[up][..., :ws.a[act].shape[3]])))
         return plan
 
 

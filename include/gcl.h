@@ -1418,6 +1418,69 @@ int gcl_cascade_scores(const float* out, const float* coarse_phys, const void* f
                        double* state, int64_t* count, int32_t step, int32_t AR, int32_t B, int32_t H, int32_t W,
                        int32_t C, void* ws, size_t ws_bytes, gcl_stream_t stream);
 
+/* ---- WeatherUNet training (csrc/unet_train.hip) ----
+ * model.py:11-98 in .train(): BatchNorm2d on batch statistics, and the backward pass of every layer.  Activations stay
+ * channels-last [B,H,W,C] float32 (n = B*H*W rows of C values).  No entry point allocates, synchronises or reads back.
+ * No atomics.  Every per-channel sum runs in float64 in two stages: fixed chunks of rows (the chunking of the scorers,
+ * a function of n alone), then a column's chunks in a fixed order; so two calls give equal bits.  The counter below is
+ * this section's own: gcl_unet_launches does not see these launches. */
+int64_t gcl_unet_train_launches(void);
+/* Workspace of a two-stage column sum over n rows and ncols columns (float64 partials), 8-byte aligned:
+ * gcl_unet_bn_stats and gcl_unet_bn_gelu_bwd take ncols = 2 C. */
+size_t gcl_unet_colsum_ws_bytes(int64_t n, int64_t ncols);
+/* The batch statistics of z [n,C] (model.py:17,20 in training): mean[c], and invstd[c] = 1 / sqrt(var + eps) with the
+ * biased variance, from sum z and sum z^2 in float64, stored as float32 [C].  running_mean / running_var (may be NULL)
+ * are updated in place as nn.BatchNorm2d does, r = (1 - momentum) r + momentum * (mean | var * n / (n - 1)), and
+ * *num_batches (device int64, may be NULL) is incremented.  n >= 2 (torch refuses one value per channel too).
+ * Two launches. */
+int gcl_unet_bn_stats(const float* z, int64_t n, int32_t C, float eps, float momentum, float* mean, float* invstd,
+                      float* running_mean, float* running_var, int64_t* num_batches, void* ws, size_t ws_bytes,
+                      gcl_stream_t stream);
+/* a = gelu_erf(gamma * (z - mean) * invstd + beta).  C % 4 == 0, every tensor 16-byte aligned.  One launch. */
+int gcl_unet_bn_gelu(const float* z, const float* gamma, const float* beta, const float* mean, const float* invstd, float* a,
+                     int64_t n, int32_t C, gcl_stream_t stream);
+/* The backward of the two above.  xhat = (z - mean) * invstd, u = gamma * xhat + beta, g = dA * gelu'(u);
+ * dbeta[c] = S1 = sum g, dgamma[c] = S2 = sum g * xhat (float64, two stages: the reduce), then
+ * dZ = gamma * invstd * (g - S1 / n - xhat * S2 / n) (the apply).  dZ may be dA.  Three launches. */
+int gcl_unet_bn_gelu_bwd(const float* z, const float* dA, const float* gamma, const float* beta, const float* mean,
+                         const float* invstd, float* dZ, float* dgamma, float* dbeta, int64_t n, int32_t C, void* ws,
+                         size_t ws_bytes, gcl_stream_t stream);
+/* The weight gradient of gcl_unet_conv3x3: dW[co][ci][ty][tx] = sum over b, y, x of dZ[b,y,x,co] * in(b, y+ty-1, x+tx-1, ci),
+ * `in` read through the same source descriptor as the forward (zero outside the image), dW in torch's [Cout,Cin,3,3]
+ * layout.  An implicit GEMM on the fp32-operand matrix instruction with M = 32 output channels, N = 32 input channels and
+ * K = pixels: a one-wave block owns a (32 co, 32 ci) tile for all nine taps and a chunk of consecutive 4 x 8 pixel tiles
+ * (numbered over the whole batch); the chunks' partial tiles go to ws and a second launch adds them per element in
+ * ascending chunk order in float64.  The chunk count - gcl_unet_wgrad_chunks, at most 256 - is a function of
+ * (B, H, W, Cin, Cout) alone.  Cout % 4 == 0; dZ and ws 16-byte aligned; ws: gcl_unet_wgrad_ws_bytes bytes, every byte of
+ * which that is read is written first.  Two launches. */
+int32_t gcl_unet_wgrad_chunks(int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout);
+size_t gcl_unet_wgrad_ws_bytes(int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout);
+int gcl_unet_conv3x3_wgrad(const gcl_unet_src_t* src, const float* dZ, float* dW, int32_t B, int32_t H, int32_t W,
+                           int32_t Cin, int32_t Cout, void* ws, size_t ws_bytes, gcl_stream_t stream);
+/* w [Cout,Cin,3,3] transposed and tap-flipped, w'[ci][co][t] = w[co][ci][8 - t], in the record order gcl_unet_conv3x3
+ * streams: the data gradient of a convolution is gcl_unet_conv3x3(ROWS(dZ), packed', gamma = NULL) with Cin' = Cout and
+ * Cout' = Cin (a multiple of 4).  packed: gcl_unet_packed_floats(Cout, Cin) floats.  One launch. */
+int gcl_unet_pack_weights_dgrad(const float* w, int32_t Cin, int32_t Cout, float* packed, gcl_stream_t stream);
+/* The data gradient of a POOL source back at the source's size: dA[b,y,x,c] = skip[b,y,x,c] + (pixel is its 2x2 window's
+ * argmax ? dpooled[b,y/2,x/2,c] : 0).  act [B,Hs,Ws,C] is the saved activation; the argmax is recomputed by torch's scan
+ * (row-major; a value replaces the running maximum if v > m or v != v).  skip (may be NULL): rows of skip_ld floats whose
+ * first C are added - the first C1 channels of an UPCAT data gradient, read in place.  A dropped odd last row or column
+ * receives the skip part only.  Every element of dA is written exactly once.  C % 4 == 0.  One launch. */
+int gcl_unet_pool_bwd(const float* act, const float* dpooled, const float* skip, int64_t skip_ld, float* dA, int32_t B,
+                      int32_t Hs, int32_t Ws, int32_t C, gcl_stream_t stream);
+/* The adjoint of the UPCAT source's bilinear read (align_corners=True) and zero pad, in gather form:
+ * dlow [B,Hs,Ws,C2] from channels c_off .. c_off+C2-1 of d [B,H,W,ld]; a low element adds the contributions of the
+ * pixels below (2 Hs, 2 Ws) that read it in ascending (y, x) order, the weights formed by the read's float32 rule.
+ * C2 % 4 == 0, c_off % 4 == 0, ld % 4 == 0.  One launch. */
+int gcl_unet_upsample_bwd(const float* d, int64_t ld, int32_t c_off, float* dlow, int32_t B, int32_t H, int32_t W, int32_t Hs,
+                          int32_t Ws, int32_t C2, gcl_stream_t stream);
+/* The backward of gcl_unet_conv1x1_out from the planar dY [B,Cout,H,W]: dA [B,H,W,F] = sum over c (ascending) of
+ * dY[c] * w[c,f]; dW [Cout,F] = sum over pixels of dY[c] * a[f] and db [Cout] = sum dY[c], as two-stage float64 column
+ * sums.  F % 4 == 0.  Three launches. */
+size_t gcl_unet_conv1x1_out_bwd_ws_bytes(int32_t B, int32_t H, int32_t W, int32_t F, int32_t Cout);
+int gcl_unet_conv1x1_out_bwd(const float* dY, const float* a, const float* w, float* dA, float* dW, float* db, int32_t B,
+                             int32_t H, int32_t W, int32_t F, int32_t Cout, void* ws, size_t ws_bytes, gcl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
