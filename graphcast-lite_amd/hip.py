@@ -263,6 +263,19 @@ _SIGNATURES = {
     "gcl_unet_upsample_bwd": (C.c_int, [_vp, _i64, _i32, _vp] + [_i32] * 6 + [_vp]),
     "gcl_unet_conv1x1_out_bwd_ws_bytes": (_sz, [_i32] * 5),
     "gcl_unet_conv1x1_out_bwd": (C.c_int, [_vp] * 6 + [_i32] * 5 + [_vp, _sz, _vp]),
+    "gcl_unet_v2_launches": (_i64, []),
+    "gcl_unet_v2_gn_stats": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _vp]),
+    "gcl_unet_v2_gn_gelu": (C.c_int, [_vp] * 6 + [_i32] * 4 + [_vp]),
+    "gcl_unet_v2_conv1x1": (C.c_int, [_vp] * 5 + [_i64] + [_i32] * 5 + [_vp]),
+    "gcl_unet_v2_tail_chunks": (_i32, [_i32]),
+    "gcl_unet_v2_tail_ws_bytes": (_sz, [_i32] * 3),
+    "gcl_unet_v2_block_tail": (C.c_int, [_vp] * 11 + [_i32] * 5 + [_vp, _sz, _vp]),
+    "gcl_unet_v2_layernorm": (C.c_int, [_vp, _vp, _vp, _f32, _vp, _i64, _i32, _vp]),
+    "gcl_unet_v2_attention": (C.c_int, [_vp, _vp] + [_i32] * 4 + [_vp]),
+    "gcl_unet_v2_spectral_pack": (C.c_int, [_vp, _vp] + [_i32] * 6 + [_vp, _vp]),
+    "gcl_unet_v2_spectral_fwd": (C.c_int, [_vp, _vp] + [_i32] * 6 + [_vp]),
+    "gcl_unet_v2_spectral_mix": (C.c_int, [_vp] * 3 + [_i32] * 4 + [_vp]),
+    "gcl_unet_v2_spectral_inv": (C.c_int, [_vp, _vp, _i64] + [_i32] * 6 + [_vp]),
 }
 
 
@@ -2780,3 +2793,186 @@ def unet_conv1x1_out_bwd(dY, a, w, dA, dW=None, db=None, ws=None):
     wp, wb = _ws_for(int(lib().gcl_unet_conv1x1_out_bwd_ws_bytes(B, H, W, F, Cout)), ws, a.device)
     _check(lib().gcl_unet_conv1x1_out_bwd(_p(dY), _p(a), _p(w), _p(dA), _p(dW), _p(db), B, H, W, F, Cout, wp, wb, _stream()))
     return dA, dW, db
+
+
+# ======================================================================================================================
+# WeatherUNetV2 inference (csrc/unet_v2.hip)
+# ======================================================================================================================
+def unet_v2_launches() -> int:
+    """Kernels launched by the entry points of csrc/unet_v2.hip in this process."""
+    return int(lib().gcl_unet_v2_launches())
+
+
+def _v2_rows(t, who, name):
+    if t.dim() != 4 or not t.is_contiguous():
+        raise ValueError(f"{who}: {name} is a contiguous [B, H, W, C] tensor, got {tuple(t.shape)}")
+    return t.shape[0], t.shape[1] * t.shape[2], t.shape[3]
+
+
+def _v2_slice(out, shape, who):
+    """ldo of `out`: a [B, H, W, C] channel slice of contiguous [B, H, W, ld] rows."""
+    B, H, W, Cc = shape
+    ld = out.stride(2)
+    if tuple(out.shape) != tuple(shape) or ld < Cc or out.stride() != (H * W * ld, W * ld, ld, 1):
+        raise ValueError(f"{who}: out is a [{B}, {H}, {W}, {Cc}] channel slice of contiguous rows, got shape "
+                         f"{tuple(out.shape)} strides {out.stride()}")
+    return ld
+
+
+def unet_v2_gn_stats(z, G: int, eps: float, mean=None, invstd=None):
+    """(mean, invstd) float32 [B, G] of the GroupNorm of z [B, H, W, C] (see gcl_unet_v2_gn_stats)."""
+    B, HW, Cc = _v2_rows(z, "unet_v2_gn_stats", "z")
+    if mean is None:
+        mean = torch.empty(B, G, dtype=torch.float32, device=z.device)
+    if invstd is None:
+        invstd = torch.empty(B, G, dtype=torch.float32, device=z.device)
+    if G < 1 or Cc % G or any(tuple(t.shape) != (B, G) or not t.is_contiguous() for t in (mean, invstd)):
+        raise ValueError(f"unet_v2_gn_stats: G = {G} must divide C = {Cc}; mean and invstd are contiguous [{B}, {G}]")
+    _check(lib().gcl_unet_v2_gn_stats(_p(z), B, HW, Cc, int(G), float(eps), _p(mean), _p(invstd), _stream()))
+    return mean, invstd
+
+
+def unet_v2_gn_gelu(z, gamma, beta, mean, invstd, out=None):
+    """out = gelu(GroupNorm(z)) from the statistics [B, G] (see gcl_unet_v2_gn_gelu)."""
+    B, HW, Cc = _v2_rows(z, "unet_v2_gn_gelu", "z")
+    if out is None:
+        out = torch.empty_like(z)
+    G = mean.shape[-1]
+    if (tuple(out.shape) != tuple(z.shape) or not out.is_contiguous() or out.data_ptr() == z.data_ptr()
+            or tuple(mean.shape) != (B, G) or tuple(invstd.shape) != (B, G) or Cc % G or gamma.numel() != Cc
+            or beta.numel() != Cc or not all(t.is_contiguous() for t in (mean, invstd, gamma, beta))):
+        raise ValueError(f"unet_v2_gn_gelu: out of z's shape (not z itself), statistics [{B}, G] and affine vectors of "
+                         f"{Cc} values expected")
+    _check(lib().gcl_unet_v2_gn_gelu(_p(z), _p(gamma), _p(beta), _p(mean), _p(invstd), _p(out), B, HW, Cc, G, _stream()))
+    return out
+
+
+def unet_v2_conv1x1(src: UnetSrc, w, out, Cin: int, bias=None, res=None):
+    """out [B, H, W, Cout] (a channel slice of contiguous rows is allowed) = the 1x1 convolution of the source with
+    w [Cout, Cin], + bias, + res [B, H, W, Cout]; w None: the identity (see gcl_unet_v2_conv1x1)."""
+    if out.dim() != 4:
+        raise ValueError("unet_v2_conv1x1: out is a [B, H, W, Cout] tensor")
+    B, H, W, Cout = out.shape
+    ld = _v2_slice(out, out.shape, "unet_v2_conv1x1")
+    if w is not None and (tuple(w.shape) != (Cout, int(Cin)) or not w.is_contiguous()):
+        raise ValueError(f"unet_v2_conv1x1: w is a contiguous [{Cout}, {Cin}] tensor, got {tuple(w.shape)}")
+    if bias is not None and (bias.numel() != Cout or not bias.is_contiguous()):
+        raise ValueError(f"unet_v2_conv1x1: bias holds {Cout} values")
+    if res is not None and (tuple(res.shape) != (B, H, W, Cout) or not res.is_contiguous()):
+        raise ValueError(f"unet_v2_conv1x1: res is a contiguous [{B}, {H}, {W}, {Cout}] tensor")
+    _check(lib().gcl_unet_v2_conv1x1(C.byref(src), _p(w), _p(bias), _p(res), _p(out), ld, B, H, W, int(Cin), Cout,
+                                     _stream()))
+    return out
+
+
+def unet_v2_tail_ws_bytes(B: int, HW: int, Cc: int) -> int:
+    return int(lib().gcl_unet_v2_tail_ws_bytes(B, HW, Cc))
+
+
+def unet_v2_block_tail(z, gamma, beta, mean, invstd, skip, w1, b1, w2, b2, out=None, ws=None):
+    """out = u * sigmoid(w2 gelu(w1 mean_hw(u) + b1) + b2), u = gelu(GroupNorm(z)) + skip (see gcl_unet_v2_block_tail).
+    ws: a float64 tensor of unet_v2_tail_ws_bytes(B, H * W, C) bytes, or None for the shared workspace."""
+    B, HW, Cc = _v2_rows(z, "unet_v2_block_tail", "z")
+    if out is None:
+        out = torch.empty_like(z)
+    G, hid = mean.shape[-1], w1.shape[0]
+    if (tuple(skip.shape) != tuple(z.shape) or tuple(out.shape) != tuple(z.shape) or not (skip.is_contiguous() and out.is_contiguous())
+            or tuple(mean.shape) != (B, G) or tuple(invstd.shape) != (B, G) or Cc % G or gamma.numel() != Cc or beta.numel() != Cc
+            or tuple(w1.shape) != (hid, Cc) or tuple(w2.shape) != (Cc, hid) or b1.numel() != hid or b2.numel() != Cc
+            or not all(t.is_contiguous() for t in (mean, invstd, gamma, beta, w1, b1, w2, b2))):
+        raise ValueError(f"unet_v2_block_tail: skip / out of z's shape {tuple(z.shape)}, statistics [{B}, G], affine vectors of "
+                         f"{Cc}, w1 [hidden, {Cc}], b1 [hidden], w2 [{Cc}, hidden], b2 [{Cc}] expected")
+    wp, wb = _ws_for(unet_v2_tail_ws_bytes(B, HW, Cc), ws, z.device)
+    _check(lib().gcl_unet_v2_block_tail(_p(z), _p(gamma), _p(beta), _p(mean), _p(invstd), _p(skip), _p(w1), _p(b1), _p(w2),
+                                        _p(b2), _p(out), B, HW, Cc, G, hid, wp, wb, _stream()))
+    return out
+
+
+def unet_v2_layernorm(x, gamma, beta, eps: float, out=None):
+    """nn.LayerNorm over the last dimension of the contiguous x [..., C] (see gcl_unet_v2_layernorm)."""
+    n, Cc = _rows(x, "unet_v2_layernorm")
+    if out is None:
+        out = torch.empty_like(x)
+    if tuple(out.shape) != tuple(x.shape) or not out.is_contiguous() or gamma.numel() != Cc or beta.numel() != Cc \
+            or not (gamma.is_contiguous() and beta.is_contiguous()):
+        raise ValueError(f"unet_v2_layernorm: out of x's shape and affine vectors of {Cc} values expected")
+    _check(lib().gcl_unet_v2_layernorm(_p(x), _p(gamma), _p(beta), float(eps), _p(out), n, Cc, _stream()))
+    return out
+
+
+def unet_v2_attention(qkv, heads: int, out=None):
+    """qkv [B, N, 3 * C] (split as [3, heads, C / heads]) -> out [B, N, C] (see gcl_unet_v2_attention)."""
+    if qkv.dim() != 3 or not qkv.is_contiguous() or heads < 1 or qkv.shape[2] % (3 * heads):
+        raise ValueError(f"unet_v2_attention: a contiguous qkv [B, N, 3 * heads * head_dim] expected, got {tuple(qkv.shape)}")
+    B, N, C3 = qkv.shape
+    if N > 4096:
+        raise ValueError(f"unet_v2_attention: at most 4096 tokens, got {N}")
+    Cc = C3 // 3
+    if out is None:
+        out = torch.empty(B, N, Cc, dtype=torch.float32, device=qkv.device)
+    if out.numel() != B * N * Cc or not out.is_contiguous():
+        raise ValueError(f"unet_v2_attention: out is a contiguous [{B}, {N}, {Cc}] tensor")
+    _check(lib().gcl_unet_v2_attention(_p(qkv), _p(out), B, N, int(heads), Cc // heads, _stream()))
+    return out
+
+
+def spectral_modes(Hb: int, Wb: int, modes_h: int, modes_w: int):
+    """(mh, mw) of model_v2.py:111-112: the kept modes on an Hb x Wb grid."""
+    return min(int(modes_h), Hb), min(int(modes_w), Wb // 2 + 1)
+
+
+def unet_v2_spectral_pack(w_re, w_im, mh: int, mw: int, out=None):
+    """weights_re / weights_im [Cin, Cout, modes_h, modes_w] -> [mh * mw, Cin, Cout, 2] (see gcl_unet_v2_spectral_pack)."""
+    if w_re.dim() != 4 or tuple(w_im.shape) != tuple(w_re.shape) or not (w_re.is_contiguous() and w_im.is_contiguous()):
+        raise ValueError("unet_v2_spectral_pack: two contiguous [Cin, Cout, modes_h, modes_w] tensors expected")
+    Cin, Cout, MH, MW = w_re.shape
+    if not (1 <= mh <= MH and 1 <= mw <= MW):
+        raise ValueError(f"unet_v2_spectral_pack: {mh} x {mw} modes of {MH} x {MW}")
+    if out is None:
+        out = torch.empty(mh * mw, Cin, Cout, 2, dtype=torch.float32, device=w_re.device)
+    if out.numel() != mh * mw * Cin * Cout * 2 or not out.is_contiguous():
+        raise ValueError(f"unet_v2_spectral_pack: out holds {out.numel()} floats, {mh * mw * Cin * Cout * 2} expected")
+    _check(lib().gcl_unet_v2_spectral_pack(_p(w_re), _p(w_im), Cin, Cout, MH, MW, int(mh), int(mw), _p(out), _stream()))
+    return out
+
+
+def unet_v2_spectral_fwd(x, mh: int, mw: int, out=None):
+    """x [B, Hb, Wb, C] -> X [B, mh * mw, C, 2] (see gcl_unet_v2_spectral_fwd)."""
+    if x.dim() != 4 or not x.is_contiguous():
+        raise ValueError("unet_v2_spectral_fwd: x is a contiguous [B, Hb, Wb, C] tensor")
+    B, Hb, Wb, Cc = x.shape
+    if out is None:
+        out = torch.empty(B, mh * mw, Cc, 2, dtype=torch.float32, device=x.device)
+    if out.numel() != B * mh * mw * Cc * 2 or not out.is_contiguous():
+        raise ValueError(f"unet_v2_spectral_fwd: out is a contiguous [{B}, {mh * mw}, {Cc}, 2] tensor")
+    _check(lib().gcl_unet_v2_spectral_fwd(_p(x), _p(out), B, Hb, Wb, Cc, int(mh), int(mw), _stream()))
+    return out
+
+
+def unet_v2_spectral_mix(X, packed, out=None):
+    """X [B, modes, Cin, 2] times packed [modes, Cin, Cout, 2] -> O [B, modes, Cout, 2] (see gcl_unet_v2_spectral_mix)."""
+    if X.dim() != 4 or packed.dim() != 4 or X.shape[3] != 2 or packed.shape[3] != 2 or X.shape[1] != packed.shape[0] \
+            or X.shape[2] != packed.shape[1] or not (X.is_contiguous() and packed.is_contiguous()):
+        raise ValueError(f"unet_v2_spectral_mix: contiguous X [B, modes, Cin, 2] and packed [modes, Cin, Cout, 2] expected, got "
+                         f"{tuple(X.shape)} and {tuple(packed.shape)}")
+    B, nm, Cin, _ = X.shape
+    Cout = packed.shape[2]
+    if out is None:
+        out = torch.empty(B, nm, Cout, 2, dtype=torch.float32, device=X.device)
+    if out.numel() != B * nm * Cout * 2 or not out.is_contiguous():
+        raise ValueError(f"unet_v2_spectral_mix: out is a contiguous [{B}, {nm}, {Cout}, 2] tensor")
+    _check(lib().gcl_unet_v2_spectral_mix(_p(X), _p(packed), _p(out), B, nm, Cin, Cout, _stream()))
+    return out
+
+
+def unet_v2_spectral_inv(O, out, mh: int, mw: int):
+    """O [B, mh * mw, C, 2] -> out [B, Hb, Wb, C] (a channel slice of contiguous rows is allowed; see
+    gcl_unet_v2_spectral_inv)."""
+    if out.dim() != 4:
+        raise ValueError("unet_v2_spectral_inv: out is a [B, Hb, Wb, C] tensor")
+    B, Hb, Wb, Cc = out.shape
+    ld = _v2_slice(out, out.shape, "unet_v2_spectral_inv")
+    if tuple(O.shape) != (B, mh * mw, Cc, 2) or not O.is_contiguous():
+        raise ValueError(f"unet_v2_spectral_inv: O is a contiguous [{B}, {mh * mw}, {Cc}, 2] tensor, got {tuple(O.shape)}")
+    _check(lib().gcl_unet_v2_spectral_inv(_p(O), _p(out), ld, B, Hb, Wb, Cc, int(mh), int(mw), _stream()))
+    return out

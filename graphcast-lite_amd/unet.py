@@ -409,9 +409,10 @@ class TrainableUNet(WeatherUNet):
 
 class CapturedUNet(Captured):
     """`model(x, residual_from=...)` replayed from a hipGraph (capture.Captured): the bits of the eager forward.  The
-    packed weights are refreshed before a replay when a weight has changed; the graph keeps pointing at them."""
+    packed weights are refreshed before a replay when a weight has changed; the graph keeps pointing at them.  `model`: a
+    `WeatherUNet` or a `unet_v2.WeatherUNetV2`."""
 
-    def __init__(self, model: WeatherUNet, use_graph=None, residual_from=None, required: bool = False):
+    def __init__(self, model: nn.Module, use_graph=None, residual_from=None, required: bool = False):
         super().__init__(use_graph=graph_enabled(use_graph), required=required)
         self.model, self.residual_from = model, residual_from
 

@@ -1481,6 +1481,70 @@ size_t gcl_unet_conv1x1_out_bwd_ws_bytes(int32_t B, int32_t H, int32_t W, int32_
 int gcl_unet_conv1x1_out_bwd(const float* dY, const float* a, const float* w, float* dA, float* dW, float* db, int32_t B,
                              int32_t H, int32_t W, int32_t F, int32_t Cout, void* ws, size_t ws_bytes, gcl_stream_t stream);
 
+/* ---- WeatherUNetV2 inference (csrc/unet_v2.hip) ----
+ * What src/unet/model_v2.py has around its 3x3 convolutions (those are gcl_unet_conv3x3 with gamma == NULL): GroupNorm,
+ * the residual 1x1 skip, the squeeze-and-excitation gate, self-attention over the bottleneck pixels and the Fourier-mode
+ * convolution.  Activations are channels-last [B,H,W,C] float32 (HW = H * W pixels, a token of the attention is a
+ * pixel).  No entry point allocates, synchronises or reads back; no atomics; every sum has an order fixed by the layer's
+ * shape, never by B or a sample's place in the batch, so a sample's bits repeat; a NaN or Inf stays in its sample.  This
+ * section's launch counter is its own: gcl_unet_launches does not see these launches. */
+int64_t gcl_unet_v2_launches(void);
+/* GroupNorm statistics of z [B,HW,C], G groups of C / G adjacent channels: mean [B,G] and invstd [B,G] =
+ * 1 / sqrt(biased variance + eps).  One block per (sample, group): the mean first, then the second moment about it, both
+ * summed in float64 (thread-strided partial sums, then a fixed tree), so |mean| >> spread costs nothing.  HW * C < 2^31.
+ * One launch. */
+int gcl_unet_v2_gn_stats(const float* z, int32_t B, int32_t HW, int32_t C, int32_t G, float eps, float* mean, float* invstd,
+                         gcl_stream_t stream);
+/* out = gelu(((z - mean[b,g]) * invstd[b,g]) * gamma[c] + beta[c]), the erf GELU; out is not z.  C % 4 == 0; z and
+ * out 16-byte aligned.  One launch. */
+int gcl_unet_v2_gn_gelu(const float* z, const float* gamma, const float* beta, const float* mean, const float* invstd,
+                        float* out, int32_t B, int32_t HW, int32_t C, int32_t G, gcl_stream_t stream);
+/* The 1x1 convolution of a source of any kind (the input is read as gcl_unet_conv3x3 reads it, never materialised):
+ * out[b,y,x,co] = sum over ci (ascending, one fmaf chain) of w[co,ci] * in(b,y,x,ci), then + bias[co] when bias is given,
+ * then res[b,y,x,co] + that when res (contiguous [B,H,W,Cout]) is given.  Pixels of out are ldo floats apart (ldo >= Cout:
+ * a channel slice of wider rows), so out is the pointer to the slice's first channel.  w == NULL: the identity (Cin ==
+ * Cout, no bias, no res): out = the source.  Cout % 4 == 0, ldo % 4 == 0, out 16-byte aligned.  With a ROWS source of
+ * H x W = N x 1 tokens this is nn.Linear.  One launch. */
+int gcl_unet_v2_conv1x1(const gcl_unet_src_t* src, const float* w, const float* bias, const float* res, float* out,
+                        int64_t ldo, int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout, gcl_stream_t stream);
+/* The tail of a ResConvBlock (model_v2.py:35-37,60): u = gelu(GroupNorm(z)) + skip; m[b,c] = mean over the pixels of u;
+ * gate = sigmoid(w2 gelu(w1 m + b1) + b2), w1 [hidden,C], w2 [C,hidden]; out = u * gate.  Two launches: the first writes
+ * u and, per chunk of pixels (gcl_unet_v2_tail_chunks(HW) chunks, at most 256, a function of HW alone), the float64
+ * channel sums; every block of the second adds the chunks in ascending order, forms the gate itself and scales its own
+ * chunk of out in place.  C % 4 == 0, C <= 2048, hidden <= 512, HW * C < 2^31; z, skip, out 16-byte aligned; out may be z
+ * or skip.  ws: gcl_unet_v2_tail_ws_bytes(B, HW, C) bytes, 8-byte aligned. */
+int32_t gcl_unet_v2_tail_chunks(int32_t HW);
+size_t gcl_unet_v2_tail_ws_bytes(int32_t B, int32_t HW, int32_t C);
+int gcl_unet_v2_block_tail(const float* z, const float* gamma, const float* beta, const float* mean, const float* invstd,
+                           const float* skip, const float* w1, const float* b1, const float* w2, const float* b2,
+                           float* out, int32_t B, int32_t HW, int32_t C, int32_t G, int32_t hidden, void* ws,
+                           size_t ws_bytes, gcl_stream_t stream);
+/* nn.LayerNorm over the last dimension of x [rows,C] (biased variance about the mean), a wave per row.  One launch. */
+int gcl_unet_v2_layernorm(const float* x, const float* gamma, const float* beta, float eps, float* out, int64_t rows,
+                          int32_t C, gcl_stream_t stream);
+/* model_v2.py:81-87: qkv [B,N,3,heads,head_dim] -> out [B,N,heads*head_dim] = softmax(q k^T head_dim^-1/2) v per (sample,
+ * head).  A wave per query: the row maximum first, then exp(score - max) key by key, the value sum in ascending key
+ * order, divided by the sum of the exponentials at the end.  Any N <= 4096 (written for N <= 64).  One launch. */
+int gcl_unet_v2_attention(const float* qkv, float* out, int32_t B, int32_t N, int32_t heads, int32_t head_dim,
+                          gcl_stream_t stream);
+/* SpectralConv2d (model_v2.py:95-122) on x [B,Hb,Wb,C] by direct sums over the kept modes kh < mh <= Hb, kw < mw <=
+ * Wb / 2 + 1 (mode = kh * mw + kw), with theta = 2 pi (kh h / Hb + kw w / Wb) formed from (kh h mod Hb, kw w mod Wb):
+ *   pack  w_re, w_im [Cin,Cout,modes_h,modes_w] -> packed [mode][Cin][Cout] complex (re, im interleaved);
+ *   fwd   X[b,mode,i] = (Hb Wb)^-1/2 sum over the pixels (ascending) of x[b,h,w,i] exp(-i theta), complex [B,modes,C];
+ *   mix   O[b,mode,o] = sum over i of X[b,mode,i] * packed[mode,i,o]: eight waves take an eighth of Cin each in ascending
+ *         i, their sums are added as a fixed tree; the weights are read once per four samples;
+ *   inv   y[b,h,w,o] = (Hb Wb)^-1/2 sum over the modes (ascending) of c_kw Re(O[b,mode,o] exp(+i theta)), c_kw = 1 for
+ *         kw = 0 and for kw = Wb / 2 when Wb is even, else 2; pixels of y are ldo floats apart.
+ * Hb, Wb <= 32768, Hb * Wb <= 2^24, at most 1024 modes.  X, packed, O 8-byte aligned.  One launch each. */
+int gcl_unet_v2_spectral_pack(const float* w_re, const float* w_im, int32_t Cin, int32_t Cout, int32_t modes_h,
+                              int32_t modes_w, int32_t mh, int32_t mw, float* packed, gcl_stream_t stream);
+int gcl_unet_v2_spectral_fwd(const float* x, float* X, int32_t B, int32_t Hb, int32_t Wb, int32_t C, int32_t mh, int32_t mw,
+                             gcl_stream_t stream);
+int gcl_unet_v2_spectral_mix(const float* X, const float* packed, float* O, int32_t B, int32_t nmodes, int32_t Cin,
+                             int32_t Cout, gcl_stream_t stream);
+int gcl_unet_v2_spectral_inv(const float* O, float* out, int64_t ldo, int32_t B, int32_t Hb, int32_t Wb, int32_t C,
+                             int32_t mh, int32_t mw, gcl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
