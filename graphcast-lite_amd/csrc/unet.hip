@@ -6,7 +6,7 @@
 //   block = 4 waves; it owns 4 x 8 output pixels of one sample (the 32 rows of one MFMA tile) and 32 output channels;
 //   Cin is walked in chunks of 32 channels: the 6 x 10 input pixels (tile + one-pixel halo) of the chunk are staged in
 //   LDS ONCE, through the source kind (planar / rows / pooled / upsampled + concatenated), zero outside the image and
-//   past Cin; the nine taps are nine shifted 16-byte LDS reads of that image;
+//   past Cin (unet_src.h: stage_halo); the nine taps are nine shifted 16-byte LDS reads of that image;
 //   wave w takes channels 8w .. 8w+7 of every chunk - four MFMAs per tap - so the four waves split K between them and
 //   nothing but the staged image is shared; a wave's B operands come straight from the packed weights, one 16-byte
 //   load per lane and (tap, 8 channels): a weight is used by one wave of the block, LDS would add a trip;
@@ -31,14 +31,16 @@ namespace {
 using gcl::mfma_io::d_row;
 using gcl::mfma_io::f32x16;
 using gcl::unet_src::gelu_erf;
-using gcl::unet_src::src_read;
-using gcl::unet_src::Vec;
+using gcl::unet_src::kHP;
+using gcl::unet_src::kHW;
+using gcl::unet_src::kTH;
+using gcl::unet_src::kTW;
+using gcl::unet_src::Src;
+using gcl::unet_src::stage_halo;
 
 std::atomic<int64_t> g_launches{0};
 
-constexpr int kTH = 4, kTW = 8;              // output pixels of a block
-constexpr int kHH = kTH + 2, kHW = kTW + 2;  // with the halo
-constexpr int kHP = kHH * kHW;               // 60 staged pixels
+// a block owns one tile of unet_src.h (kTH x kTW output pixels, kHP staged ones)
 // channels per chunk: 8 per wave; floats between staged pixels (144 / 272 B: 16-byte aligned, 4 banks apart)
 constexpr int chunk_of(int NW) { return 8 * NW; }
 constexpr int pitch_of(int NW) { return 8 * NW + 4; }
@@ -47,15 +49,12 @@ constexpr int kTN = 32;                      // output channels of a block
 constexpr int kRP = kTN + 1;                 // row pitch of the partial tiles
 
 struct ConvArgs {
-  const float* a;
-  const float* b;
-  int32_t C1, C2, Hs, Ws;
-  float sy, sx;  // UPCAT: (in - 1) / (out - 1) per axis, in float32 as torch forms it
+  Src src;
   const float* packed;
   const float *gamma, *beta, *mean, *var;
   float eps;
   float* y;
-  int32_t H, W, Cin, Cout, G, NT, TX;
+  int32_t Cout, G, NT, TX;
 };
 
 template <int KIND, int V, int NW>
@@ -77,7 +76,7 @@ __global__ __launch_bounds__(64 * NW) void unet_conv3x3_kernel(const ConvArgs s)
   const float* ap = Xs + ((p >> 3) * kHW + (p & 7)) * kXP + 8 * wave + 4 * h;
   const float4* wp = reinterpret_cast<const float4*>(s.packed) + ((int64_t)nt * 9 * s.G) * 64 + lane;
 
-  const int nchunks = (s.Cin + kKC - 1) / kKC;
+  const int nchunks = (s.src.Cin + kKC - 1) / kKC;
   for (int ch = 0; ch < nchunks; ++ch) {
     const int g = ch * NW + wave;
     const bool live = g < s.G;  // wave-uniform
@@ -85,23 +84,7 @@ __global__ __launch_bounds__(64 * NW) void unet_conv3x3_kernel(const ConvArgs s)
 #pragma unroll
     for (int t = 0; t < 9; ++t) bw[t] = live ? wp[((int64_t)t * s.G + g) * 64] : make_float4(0.f, 0.f, 0.f, 0.f);
 
-    // stage the chunk: kHP pixels x kKC channels, V channels per item
-    constexpr int kPer = kKC / V;
-    for (int idx = tid; idx < kHP * kPer; idx += 64 * NW) {
-      const int px = idx / kPer, cc = (idx % kPer) * V;
-      const int y = y0 - 1 + px / kHW, x = x0 - 1 + px % kHW;
-      const int c = ch * kKC + cc;
-      Vec<V> v;
-#pragma unroll
-      for (int i = 0; i < V; ++i) v.v[i] = 0.f;
-      if (y >= 0 && y < s.H && x >= 0 && x < s.W && c < s.Cin) v = src_read<KIND, V>(s, b, y, x, c);
-      float* d = Xs + px * kXP + cc;
-      if constexpr (V == 4) {
-        *reinterpret_cast<float4*>(d) = make_float4(v.v[0], v.v[1], v.v[2], v.v[3]);
-      } else {
-        *d = v.v[0];
-      }
-    }
+    stage_halo<KIND, V, 64 * NW>(Xs, kXP, s.src, b, y0, x0, ch * kKC, kKC, tid);
     __syncthreads();
     if (live) {
 #pragma unroll
@@ -123,7 +106,7 @@ __global__ __launch_bounds__(64 * NW) void unet_conv3x3_kernel(const ConvArgs s)
   const int op = tid >> 3, j0 = (tid & 7) * 4;
   const int oy = y0 + (op >> 3), ox = x0 + (op & 7);
   const int co = nt * kTN + j0;
-  if (tid < 256 && oy < s.H && ox < s.W && co < s.Cout) {  // Cout % 4 == 0: four channels are inside or outside together
+  if (tid < 256 && oy < s.src.H && ox < s.src.W && co < s.Cout) {  // Cout % 4 == 0: four channels are inside or outside together
     float o[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -136,7 +119,7 @@ __global__ __launch_bounds__(64 * NW) void unet_conv3x3_kernel(const ConvArgs s)
       }
       o[k] = v;
     }
-    *reinterpret_cast<float4*>(s.y + ((b * s.H + oy) * s.W + ox) * s.Cout + co) = make_float4(o[0], o[1], o[2], o[3]);
+    *reinterpret_cast<float4*>(s.y + ((b * s.src.H + oy) * s.src.W + ox) * s.Cout + co) = make_float4(o[0], o[1], o[2], o[3]);
   }
 }
 
@@ -291,7 +274,7 @@ void launch_conv_nw(const ConvArgs& a, bool vec, dim3 grid, hipStream_t st) {
 // the block shape is a function of Cin alone: the order of every sum stays a function of the layer's shape
 template <int KIND>
 void launch_conv(const ConvArgs& a, bool vec, dim3 grid, hipStream_t st) {
-  if (a.Cin >= kLongCin) launch_conv_nw<KIND, 8>(a, vec, grid, st);
+  if (a.src.Cin >= kLongCin) launch_conv_nw<KIND, 8>(a, vec, grid, st);
   else launch_conv_nw<KIND, 4>(a, vec, grid, st);
 }
 
@@ -320,47 +303,25 @@ int gcl_unet_pack_weights(const float* w, int32_t Cin, int32_t Cout, float* pack
 int gcl_unet_conv3x3(const gcl_unet_src_t* src, const float* packed, const float* gamma, const float* beta,
                      const float* mean, const float* var, float eps, float* y, int32_t B, int32_t H, int32_t W,
                      int32_t Cin, int32_t Cout, gcl_stream_t stream) {
-  GCL_CHECK_ARG(src && src->a && packed && y, "gcl_unet_conv3x3: null pointer");
+  GCL_CHECK_ARG(packed && y, "gcl_unet_conv3x3: null pointer");
   GCL_CHECK_ARG(B >= 1 && B <= 65535 && H >= 1 && W >= 1 && Cin >= 1 && Cout >= 4 && Cout % 4 == 0,
                 "gcl_unet_conv3x3: B %d, H %d, W %d, Cin %d, Cout %d (Cout must be a multiple of 4, B <= 65535)", B, H, W,
                 Cin, Cout);
   GCL_CHECK_ARG(gcl::aligned16(y) && gcl::aligned16(packed), "gcl_unet_conv3x3: y and packed must be 16-byte aligned");
   GCL_CHECK_ARG(!gamma || (beta && mean && var), "gcl_unet_conv3x3: gamma without beta / mean / var");
   ConvArgs a{};
-  a.a = src->a, a.b = src->b, a.C1 = src->C1, a.C2 = src->C2, a.Hs = src->Hs, a.Ws = src->Ws;
-  a.packed = packed, a.gamma = gamma, a.beta = beta, a.mean = mean, a.var = var, a.eps = eps, a.y = y;
-  a.H = H, a.W = W, a.Cin = Cin, a.Cout = Cout;
+  bool vec;
+  if (const int rc = gcl::unet_src::bind(src, H, W, Cin, "gcl_unet_conv3x3", a.src, vec)) return rc;
+  a.packed = packed, a.gamma = gamma, a.beta = beta, a.mean = mean, a.var = var, a.eps = eps, a.y = y, a.Cout = Cout;
   a.G = (int)gcl::cdiv(Cin, 8), a.NT = (int)gcl::cdiv(Cout, kTN), a.TX = (int)gcl::cdiv(W, kTW);
   const int64_t blocks = gcl::cdiv(H, kTH) * a.TX * a.NT;
   GCL_CHECK_ARG(blocks <= 0x7fffffff, "gcl_unet_conv3x3: %lld blocks per sample", (long long)blocks);
   const dim3 grid((unsigned)blocks, (unsigned)B);
-  const hipStream_t st = (hipStream_t)stream;
-  bool vec = Cin % 4 == 0 && gcl::aligned16(src->a);
-  switch (src->kind) {
-    case GCL_UNET_SRC_PLANAR:
-      launch_conv<GCL_UNET_SRC_PLANAR>(a, false, grid, st);
-      break;
-    case GCL_UNET_SRC_ROWS:
-      launch_conv<GCL_UNET_SRC_ROWS>(a, vec, grid, st);
-      break;
-    case GCL_UNET_SRC_POOL:
-      GCL_CHECK_ARG(src->Hs / 2 == H && src->Ws / 2 == W, "gcl_unet_conv3x3: POOL source %d x %d does not halve to %d x %d",
-                    src->Hs, src->Ws, H, W);
-      launch_conv<GCL_UNET_SRC_POOL>(a, vec, grid, st);
-      break;
-    case GCL_UNET_SRC_UPCAT:
-      GCL_CHECK_ARG(src->b && src->C1 >= 1 && src->C2 >= 1 && src->C1 + src->C2 == Cin,
-                    "gcl_unet_conv3x3: UPCAT needs b and C1 + C2 == Cin (C1 %d, C2 %d, Cin %d)", src->C1, src->C2, Cin);
-      GCL_CHECK_ARG(src->Hs >= 1 && src->Ws >= 1 && 2 * src->Hs <= H && 2 * src->Ws <= W,
-                    "gcl_unet_conv3x3: UPCAT low tensor %d x %d does not fit %d x %d", src->Hs, src->Ws, H, W);
-      a.sy = (float)(src->Hs - 1) / (float)(2 * src->Hs - 1);
-      a.sx = (float)(src->Ws - 1) / (float)(2 * src->Ws - 1);
-      vec = src->C1 % 4 == 0 && src->C2 % 4 == 0 && gcl::aligned16(src->a) && gcl::aligned16(src->b);
-      launch_conv<GCL_UNET_SRC_UPCAT>(a, vec, grid, st);
-      break;
-    default:
-      GCL_CHECK_ARG(false, "gcl_unet_conv3x3: source kind %d", src->kind);
-  }
+  const int rc = gcl::unet_src::with_kind(src->kind, [&](auto K) {
+    launch_conv<decltype(K)::value>(a, vec, grid, (hipStream_t)stream);
+    return GCL_OK;
+  });
+  if (rc) return rc;
   GCL_CHECK_LAUNCH();
   ++g_launches;
   return GCL_OK;

@@ -9,8 +9,8 @@
 //   block = 1 wave; it owns one (32 co, 32 ci) tile of dW for all nine taps - nine accumulator tiles, 144 registers - and
 //   a chunk of consecutive 4 x 8 pixel tiles (numbered sample-major over the batch);
 //   per pixel tile the 32 x 32 dZ tile and the 6 x 10 pixels (tile + one-pixel halo) of the 32 input channels are
-//   staged in LDS, the input through the source kind exactly as the forward reads it (zero outside the image, past Cin
-//   and past Cout), then 16 k-steps of two pixels (lane half h supplies pixel 2 s + h) x 9 taps: the A operand is one
+//   staged in LDS, the input by the forward's own unet_src.h::stage_halo (zero outside the image, past Cin and past
+//   Cout), then 16 k-steps of two pixels (lane half h supplies pixel 2 s + h) x 9 taps: the A operand is one
 //   LDS word of the dZ tile, the B operand one word of the shifted input image - lanes 0 .. 31 read 32 consecutive
 //   words, the two halves never conflict;
 //   the chunk's partial tiles go to the workspace [chunk][Cout][Cin][9]; unet_wgrad_sum_kernel adds the chunks of an
@@ -28,18 +28,19 @@ namespace {
 using gcl::mfma_io::d_row;
 using gcl::mfma_io::f32x16;
 using gcl::unet_src::gelu_erf;
+using gcl::unet_src::kHP;
+using gcl::unet_src::kHW;
+using gcl::unet_src::kTH;
+using gcl::unet_src::kTW;
 using gcl::unet_src::lerp_of;
 using gcl::unet_src::Lerp;
 using gcl::unet_src::pool_take;
 using gcl::unet_src::pool_takes;
-using gcl::unet_src::src_read;
-using gcl::unet_src::Vec;
+using gcl::unet_src::Src;
+using gcl::unet_src::stage_halo;
 
 std::atomic<int64_t> g_launches{0};
 
-constexpr int kTH = 4, kTW = 8;              // pixels of a tile: the forward's
-constexpr int kHH = kTH + 2, kHW = kTW + 2;  // with the halo
-constexpr int kHP = kHH * kHW;               // 60 staged pixels
 constexpr int kTC = 32;                      // channels of a dW tile, each way
 constexpr int kWgradBlocks = 1024;           // blocks a weight gradient aims at: one wave each, 4 SIMDs x 256 CUs
 constexpr int kWgradMaxChunks = 256;         // bounds the workspace: at most 256 partial copies of dW
@@ -390,13 +391,10 @@ bool wgrad_plan(int B, int H, int W, int Cin, int Cout, WgradPlan& p) {
 }
 
 struct WgradArgs {
-  const float* a;
-  const float* b;
-  int32_t C1, C2, Hs, Ws;
-  float sy, sx;
+  Src src;
   const float* dz;
   float* part;
-  int32_t H, W, Cin, Cout, TX, T, NT, tpc, NCi;
+  int32_t Cout, TX, T, NT, tpc, NCi;
 };
 
 template <int KIND, int V>
@@ -425,26 +423,11 @@ __global__ __launch_bounds__(64) void unet_wgrad_kernel(const WgradArgs s) {
       const int p = idx >> 3, cc = (idx & 7) * 4;
       const int y = y0 + (p >> 3), x = x0 + (p & 7), co = cot * kTC + cc;
       float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (y < s.H && x < s.W && co < s.Cout) v = gcl::ld4(s.dz + ((b * s.H + y) * s.W + x) * s.Cout + co);
+      if (y < s.src.H && x < s.src.W && co < s.Cout) v = gcl::ld4(s.dz + ((b * s.src.H + y) * s.src.W + x) * s.Cout + co);
       gcl::st4(Zs + p * kTC + cc, v);
     }
     // the input image: 60 pixels x 32 input channels through the source kind
-    constexpr int kPer = kTC / V;
-    for (int idx = lane; idx < kHP * kPer; idx += 64) {
-      const int px = idx / kPer, cc = (idx % kPer) * V;
-      const int y = y0 - 1 + px / kHW, x = x0 - 1 + px % kHW;
-      const int c = cit * kTC + cc;
-      Vec<V> v;
-#pragma unroll
-      for (int i = 0; i < V; ++i) v.v[i] = 0.f;
-      if (y >= 0 && y < s.H && x >= 0 && x < s.W && c < s.Cin) v = src_read<KIND, V>(s, b, y, x, c);
-      float* d = Xs + px * kTC + cc;
-      if constexpr (V == 4) {
-        gcl::st4(d, make_float4(v.v[0], v.v[1], v.v[2], v.v[3]));
-      } else {
-        *d = v.v[0];
-      }
-    }
+    stage_halo<KIND, V, 64>(Xs, kTC, s.src, b, y0, x0, cit * kTC, kTC, lane);
     __syncthreads();
 #pragma unroll
     for (int st = 0; st < 16; ++st) {
@@ -460,12 +443,12 @@ __global__ __launch_bounds__(64) void unet_wgrad_kernel(const WgradArgs s) {
   }
 
   const int ci = cit * kTC + j;
-  float* out = s.part + (int64_t)chunk * s.Cout * s.Cin * 9;
+  float* out = s.part + (int64_t)chunk * s.Cout * s.src.Cin * 9;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
     const int co = cot * kTC + d_row(r, lane);
-    if (co < s.Cout && ci < s.Cin) {
-      float* o = out + ((int64_t)co * s.Cin + ci) * 9;
+    if (co < s.Cout && ci < s.src.Cin) {
+      float* o = out + ((int64_t)co * s.src.Cin + ci) * 9;
 #pragma unroll
       for (int t = 0; t < 9; ++t) o[t] = acc[t][r];
     }
@@ -591,7 +574,7 @@ size_t gcl_unet_wgrad_ws_bytes(int32_t B, int32_t H, int32_t W, int32_t Cin, int
 
 int gcl_unet_conv3x3_wgrad(const gcl_unet_src_t* src, const float* dZ, float* dW, int32_t B, int32_t H, int32_t W,
                            int32_t Cin, int32_t Cout, void* ws, size_t ws_bytes, gcl_stream_t stream) {
-  GCL_CHECK_ARG(src && src->a && dZ && dW && ws, "gcl_unet_conv3x3_wgrad: null pointer");
+  GCL_CHECK_ARG(dZ && dW && ws, "gcl_unet_conv3x3_wgrad: null pointer");
   WgradPlan p;
   GCL_CHECK_ARG(wgrad_plan(B, H, W, Cin, Cout, p),
                 "gcl_unet_conv3x3_wgrad: B %d, H %d, W %d, Cin %d, Cout %d (Cout must be a multiple of 4)", B, H, W, Cin, Cout);
@@ -602,37 +585,17 @@ int gcl_unet_conv3x3_wgrad(const gcl_unet_src_t* src, const float* dZ, float* dW
     return GCL_ENOMEM;
   }
   WgradArgs a{};
-  a.a = src->a, a.b = src->b, a.C1 = src->C1, a.C2 = src->C2, a.Hs = src->Hs, a.Ws = src->Ws;
+  bool vec;
+  if (const int rc = gcl::unet_src::bind(src, H, W, Cin, "gcl_unet_conv3x3_wgrad", a.src, vec)) return rc;
   a.dz = dZ, a.part = static_cast<float*>(ws);
-  a.H = H, a.W = W, a.Cin = Cin, a.Cout = Cout, a.TX = p.TX, a.T = p.T, a.NT = p.NT, a.tpc = p.tpc, a.NCi = p.NCi;
+  a.Cout = Cout, a.TX = p.TX, a.T = p.T, a.NT = p.NT, a.tpc = p.tpc, a.NCi = p.NCi;
   const dim3 grid((unsigned)(p.NCo * p.NCi), (unsigned)p.nchunk);
   const hipStream_t st = (hipStream_t)stream;
-  bool vec = Cin % 4 == 0 && gcl::aligned16(src->a);
-  switch (src->kind) {
-    case GCL_UNET_SRC_PLANAR:
-      launch_wgrad<GCL_UNET_SRC_PLANAR>(a, false, grid, st);
-      break;
-    case GCL_UNET_SRC_ROWS:
-      launch_wgrad<GCL_UNET_SRC_ROWS>(a, vec, grid, st);
-      break;
-    case GCL_UNET_SRC_POOL:
-      GCL_CHECK_ARG(src->Hs / 2 == H && src->Ws / 2 == W, "gcl_unet_conv3x3_wgrad: POOL source %d x %d does not halve to %d x %d",
-                    src->Hs, src->Ws, H, W);
-      launch_wgrad<GCL_UNET_SRC_POOL>(a, vec, grid, st);
-      break;
-    case GCL_UNET_SRC_UPCAT:
-      GCL_CHECK_ARG(src->b && src->C1 >= 1 && src->C2 >= 1 && src->C1 + src->C2 == Cin,
-                    "gcl_unet_conv3x3_wgrad: UPCAT needs b and C1 + C2 == Cin (C1 %d, C2 %d, Cin %d)", src->C1, src->C2, Cin);
-      GCL_CHECK_ARG(src->Hs >= 1 && src->Ws >= 1 && 2 * src->Hs <= H && 2 * src->Ws <= W,
-                    "gcl_unet_conv3x3_wgrad: UPCAT low tensor %d x %d does not fit %d x %d", src->Hs, src->Ws, H, W);
-      a.sy = gcl::unet_src::upcat_scale(src->Hs);
-      a.sx = gcl::unet_src::upcat_scale(src->Ws);
-      vec = src->C1 % 4 == 0 && src->C2 % 4 == 0 && gcl::aligned16(src->a) && gcl::aligned16(src->b);
-      launch_wgrad<GCL_UNET_SRC_UPCAT>(a, vec, grid, st);
-      break;
-    default:
-      GCL_CHECK_ARG(false, "gcl_unet_conv3x3_wgrad: source kind %d", src->kind);
-  }
+  const int rc = gcl::unet_src::with_kind(src->kind, [&](auto K) {
+    launch_wgrad<decltype(K)::value>(a, vec, grid, st);
+    return GCL_OK;
+  });
+  if (rc) return rc;
   GCL_CHECK_LAUNCH();
   hipLaunchKernelGGL(unet_wgrad_sum_kernel, dim3(gcl::grid_for(p.elems)), dim3(256), 0, st, a.part, dW, p.elems, p.nchunk);
   GCL_CHECK_LAUNCH();

@@ -25,6 +25,7 @@
 namespace {
 
 using gcl::unet_src::gelu_erf;
+using gcl::unet_src::Src;
 using gcl::unet_src::src_read;
 
 std::atomic<int64_t> g_launches{0};
@@ -114,11 +115,7 @@ constexpr int kPP = 16, kPC = 64, kPK = 32;  // pixels, output channels of a blo
 constexpr int kPWP = kPC + 4;                // pitch of the staged weights (16-byte aligned rows)
 
 struct PwArgs {
-  const float* a;
-  const float* b;
-  int32_t C1, C2, Hs, Ws;
-  float sy, sx;
-  int32_t H, W, Cin;
+  Src src;
   const float *w, *bias, *res;
   float* out;
   int64_t ldo;
@@ -132,21 +129,21 @@ __global__ __launch_bounds__(256) void pw_kernel(const PwArgs s) {
   const int tid = threadIdx.x;
   const int ct = blockIdx.x % s.NT, pix0 = (blockIdx.x / s.NT) * kPP;
   const int64_t b = blockIdx.y;
-  const int HW = s.H * s.W;
+  const int HW = s.src.H * s.src.W;
   const int p = tid >> 4, cq = tid & 15;
   float acc[4] = {0.f, 0.f, 0.f, 0.f};
-  for (int k0 = 0; k0 < s.Cin; k0 += kPK) {
+  for (int k0 = 0; k0 < s.src.Cin; k0 += kPK) {
     for (int idx = tid; idx < kPP * kPK; idx += 256) {
       const int px = idx >> 5, cc = idx & 31;
       const int pix = pix0 + px, c = k0 + cc;
       float v = 0.f;
-      if (pix < HW && c < s.Cin) v = src_read<KIND, 1>(s, b, pix / s.W, pix % s.W, c).v[0];
+      if (pix < HW && c < s.src.Cin) v = src_read<KIND, 1>(s.src, b, pix / s.src.W, pix % s.src.W, c).v[0];
       Xs[px][cc] = v;
     }
     for (int idx = tid; idx < kPC * kPK; idx += 256) {
       const int col = idx >> 5, cc = idx & 31;
       const int co = ct * kPC + col, c = k0 + cc;
-      Wt[cc][col] = (co < s.Cout && c < s.Cin) ? s.w[(int64_t)co * s.Cin + c] : 0.f;
+      Wt[cc][col] = (co < s.Cout && c < s.src.Cin) ? s.w[(int64_t)co * s.src.Cin + c] : 0.f;
     }
     __syncthreads();
 #pragma unroll 8
@@ -175,22 +172,22 @@ __global__ __launch_bounds__(256) void pw_kernel(const PwArgs s) {
 // w == NULL: the identity skip, out = the source's own channels
 template <int KIND>
 __global__ __launch_bounds__(256) void pw_copy_kernel(const PwArgs s, int64_t total) {
-  const int HW = s.H * s.W;
+  const int HW = s.src.H * s.src.W;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-    const int c = (int)(i % s.Cin);
-    const int64_t row = i / s.Cin;
+    const int c = (int)(i % s.src.Cin);
+    const int64_t row = i / s.src.Cin;
     const int pix = (int)(row % HW);
-    s.out[row * s.ldo + c] = src_read<KIND, 1>(s, row / HW, pix / s.W, pix % s.W, c).v[0];
+    s.out[row * s.ldo + c] = src_read<KIND, 1>(s.src, row / HW, pix / s.src.W, pix % s.src.W, c).v[0];
   }
 }
 
 template <int KIND>
 void launch_pw(const PwArgs& a, int B, hipStream_t st) {
-  const int HW = a.H * a.W;
+  const int HW = a.src.H * a.src.W;
   if (a.w) {
     hipLaunchKernelGGL((pw_kernel<KIND>), dim3((unsigned)(gcl::cdiv(HW, kPP) * a.NT), (unsigned)B), dim3(256), 0, st, a);
   } else {
-    const int64_t total = (int64_t)B * HW * a.Cin;
+    const int64_t total = (int64_t)B * HW * a.src.Cin;
     hipLaunchKernelGGL((pw_copy_kernel<KIND>), dim3(gcl::grid_for(total)), dim3(256), 0, st, a, total);
   }
 }
@@ -540,7 +537,7 @@ int gcl_unet_v2_gn_gelu(const float* z, const float* gamma, const float* beta, c
 
 int gcl_unet_v2_conv1x1(const gcl_unet_src_t* src, const float* w, const float* bias, const float* res, float* out,
                         int64_t ldo, int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout, gcl_stream_t stream) {
-  GCL_CHECK_ARG(src && src->a && out, "gcl_unet_v2_conv1x1: null pointer");
+  GCL_CHECK_ARG(out, "gcl_unet_v2_conv1x1: null pointer");
   GCL_CHECK_ARG(B >= 1 && B <= 65535 && H >= 1 && W >= 1 && Cin >= 1 && Cout >= 4 && Cout % 4 == 0 && ldo >= Cout &&
                     ldo % 4 == 0 && (int64_t)H * W <= 0x7fffffff / kPP,
                 "gcl_unet_v2_conv1x1: B %d, H %d, W %d, Cin %d, Cout %d, ldo %lld (Cout and ldo multiples of 4, ldo >= Cout)",
@@ -548,34 +545,14 @@ int gcl_unet_v2_conv1x1(const gcl_unet_src_t* src, const float* w, const float* 
   GCL_CHECK_ARG(gcl::aligned16(out), "gcl_unet_v2_conv1x1: out must be 16-byte aligned");
   GCL_CHECK_ARG(w || (Cin == Cout && !bias && !res), "gcl_unet_v2_conv1x1: w == NULL is the identity (Cin == Cout, no bias, no res)");
   PwArgs a{};
-  a.a = src->a, a.b = src->b, a.C1 = src->C1, a.C2 = src->C2, a.Hs = src->Hs, a.Ws = src->Ws;
-  a.H = H, a.W = W, a.Cin = Cin, a.w = w, a.bias = bias, a.res = res, a.out = out, a.ldo = ldo, a.Cout = Cout;
-  a.NT = (int)gcl::cdiv(Cout, kPC);
-  const hipStream_t st = (hipStream_t)stream;
-  switch (src->kind) {
-    case GCL_UNET_SRC_PLANAR:
-      launch_pw<GCL_UNET_SRC_PLANAR>(a, B, st);
-      break;
-    case GCL_UNET_SRC_ROWS:
-      launch_pw<GCL_UNET_SRC_ROWS>(a, B, st);
-      break;
-    case GCL_UNET_SRC_POOL:
-      GCL_CHECK_ARG(src->Hs / 2 == H && src->Ws / 2 == W, "gcl_unet_v2_conv1x1: POOL source %d x %d does not halve to %d x %d",
-                    src->Hs, src->Ws, H, W);
-      launch_pw<GCL_UNET_SRC_POOL>(a, B, st);
-      break;
-    case GCL_UNET_SRC_UPCAT:
-      GCL_CHECK_ARG(src->b && src->C1 >= 1 && src->C2 >= 1 && src->C1 + src->C2 == Cin,
-                    "gcl_unet_v2_conv1x1: UPCAT needs b and C1 + C2 == Cin (C1 %d, C2 %d, Cin %d)", src->C1, src->C2, Cin);
-      GCL_CHECK_ARG(src->Hs >= 1 && src->Ws >= 1 && 2 * src->Hs <= H && 2 * src->Ws <= W,
-                    "gcl_unet_v2_conv1x1: UPCAT low tensor %d x %d does not fit %d x %d", src->Hs, src->Ws, H, W);
-      a.sy = gcl::unet_src::upcat_scale(src->Hs);
-      a.sx = gcl::unet_src::upcat_scale(src->Ws);
-      launch_pw<GCL_UNET_SRC_UPCAT>(a, B, st);
-      break;
-    default:
-      GCL_CHECK_ARG(false, "gcl_unet_v2_conv1x1: source kind %d", src->kind);
-  }
+  bool vec;  // the pointwise kernels read scalars only
+  if (const int rc = gcl::unet_src::bind(src, H, W, Cin, "gcl_unet_v2_conv1x1", a.src, vec)) return rc;
+  a.w = w, a.bias = bias, a.res = res, a.out = out, a.ldo = ldo, a.Cout = Cout, a.NT = (int)gcl::cdiv(Cout, kPC);
+  const int rc = gcl::unet_src::with_kind(src->kind, [&](auto K) {
+    launch_pw<decltype(K)::value>(a, B, (hipStream_t)stream);
+    return GCL_OK;
+  });
+  if (rc) return rc;
   GCL_CHECK_LAUNCH();
   ++g_launches;
   return GCL_OK;

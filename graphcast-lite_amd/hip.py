@@ -2572,18 +2572,31 @@ def unet_launches() -> int:
     return int(lib().gcl_unet_launches())
 
 
+def _out(out, shape, like, who, name="out", exact=False):
+    """`out`, or when None a new float32 tensor of `shape` on like's device.  A given one is contiguous and holds shape's
+    elements (exact: has that shape)."""
+    if out is None:
+        return torch.empty(*shape, dtype=torch.float32, device=like.device)
+    if not out.is_contiguous() or (tuple(out.shape) != tuple(shape) if exact else out.numel() != torch.Size(shape).numel()):
+        raise ValueError(f"{who}: {name} is a contiguous {list(shape)} tensor, got {tuple(out.shape)}")
+    return out
+
+
+def _pack3x3(w, out, dgrad: bool):
+    who = "unet_pack_weights_dgrad" if dgrad else "unet_pack_weights"
+    if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3) or not w.is_contiguous():
+        raise ValueError(f"{who}: a contiguous [Cout, Cin, 3, 3] weight expected, got {tuple(w.shape)}")
+    Cout, Cin = w.shape[0], w.shape[1]
+    # the data gradient is the transposed convolution: Cin' = Cout, Cout' = Cin
+    n = int(lib().gcl_unet_packed_floats(Cout, Cin) if dgrad else lib().gcl_unet_packed_floats(Cin, Cout))
+    out = _out(out, (n,), w, who)
+    _check(getattr(lib(), "gcl_" + who)(_p(w), Cin, Cout, _p(out), _stream()))
+    return out
+
+
 def unet_pack_weights(w, out=None):
     """torch's [Cout, Cin, 3, 3] convolution weight in the order gcl_unet_conv3x3 streams."""
-    if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3) or not w.is_contiguous():
-        raise ValueError(f"unet_pack_weights: a contiguous [Cout, Cin, 3, 3] weight expected, got {tuple(w.shape)}")
-    Cout, Cin = w.shape[0], w.shape[1]
-    n = int(lib().gcl_unet_packed_floats(Cin, Cout))
-    if out is None:
-        out = torch.empty(n, dtype=torch.float32, device=w.device)
-    elif out.numel() != n or not out.is_contiguous():
-        raise ValueError(f"unet_pack_weights: out holds {out.numel()} floats, {n} expected")
-    _check(lib().gcl_unet_pack_weights(_p(w), Cin, Cout, _p(out), _stream()))
-    return out
+    return _pack3x3(w, out, False)
 
 
 def unet_conv3x3(src: UnetSrc, packed, norm, eps: float, y, Cin: int):
@@ -2664,9 +2677,11 @@ def _ws_for(need: int, ws, device):
     return ws.data_ptr(), ws.numel() * ws.element_size()
 
 
-def _rows(t, who):
-    if t.dim() < 2 or not t.is_contiguous():
-        raise ValueError(f"{who}: a contiguous [..., C] tensor expected, got {tuple(t.shape)}")
+def _rows(t, who, name="the input", dims=None):
+    """(rows, C) of the contiguous [..., C] tensor t, which has `dims` dimensions when given."""
+    if t.dim() < 2 or (dims is not None and t.dim() != dims) or not t.is_contiguous():
+        raise ValueError(f"{who}: {name} is a contiguous {'[B, H, W, C]' if dims == 4 else '[..., C]'} tensor, got "
+                         f"{tuple(t.shape)}")
     return t.numel() // t.shape[-1], t.shape[-1]
 
 
@@ -2725,10 +2740,7 @@ def unet_conv3x3_wgrad(src: UnetSrc, dZ, Cin: int, dW=None, ws=None):
     if dZ.dim() != 4 or not dZ.is_contiguous():
         raise ValueError("unet_conv3x3_wgrad: dZ is a contiguous [B, H, W, Cout] tensor")
     B, H, W, Cout = dZ.shape
-    if dW is None:
-        dW = torch.empty(Cout, int(Cin), 3, 3, dtype=torch.float32, device=dZ.device)
-    elif tuple(dW.shape) != (Cout, int(Cin), 3, 3) or not dW.is_contiguous():
-        raise ValueError(f"unet_conv3x3_wgrad: dW is a contiguous [{Cout}, {Cin}, 3, 3] tensor")
+    dW = _out(dW, (Cout, int(Cin), 3, 3), dZ, "unet_conv3x3_wgrad", "dW", exact=True)
     wp, wb = _ws_for(unet_wgrad_ws_bytes(B, H, W, int(Cin), Cout), ws, dZ.device)
     _check(lib().gcl_unet_conv3x3_wgrad(C.byref(src), _p(dZ), _p(dW), B, H, W, int(Cin), Cout, wp, wb, _stream()))
     return dW
@@ -2737,16 +2749,7 @@ def unet_conv3x3_wgrad(src: UnetSrc, dZ, Cin: int, dW=None, ws=None):
 def unet_pack_weights_dgrad(w, out=None):
     """torch's [Cout, Cin, 3, 3] weight transposed and tap-flipped, in the order gcl_unet_conv3x3 streams: the data
     gradient is unet_conv3x3(unet_src(UNET_ROWS, dZ), packed, None, eps, dX [B, H, W, Cin], Cout)."""
-    if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3) or not w.is_contiguous():
-        raise ValueError(f"unet_pack_weights_dgrad: a contiguous [Cout, Cin, 3, 3] weight expected, got {tuple(w.shape)}")
-    Cout, Cin = w.shape[0], w.shape[1]
-    n = int(lib().gcl_unet_packed_floats(Cout, Cin))
-    if out is None:
-        out = torch.empty(n, dtype=torch.float32, device=w.device)
-    elif out.numel() != n or not out.is_contiguous():
-        raise ValueError(f"unet_pack_weights_dgrad: out holds {out.numel()} floats, {n} expected")
-    _check(lib().gcl_unet_pack_weights_dgrad(_p(w), Cin, Cout, _p(out), _stream()))
-    return out
+    return _pack3x3(w, out, True)
 
 
 def unet_pool_bwd(act, dpooled, dA, skip=None):
@@ -2784,12 +2787,8 @@ def unet_conv1x1_out_bwd(dY, a, w, dA, dW=None, db=None, ws=None):
     if tuple(dY.shape) != (B, Cout, H, W) or tuple(dA.shape) != (B, H, W, F) or tuple(w.shape) != (Cout, F) or not (
             dY.is_contiguous() and a.is_contiguous() and w.is_contiguous() and dA.is_contiguous()):
         raise ValueError(f"unet_conv1x1_out_bwd: contiguous dY [{B}, {Cout}, {H}, {W}], a / dA [B, H, W, F], w [Cout, F] expected")
-    if dW is None:
-        dW = torch.empty(Cout, F, dtype=torch.float32, device=a.device)
-    if db is None:
-        db = torch.empty(Cout, dtype=torch.float32, device=a.device)
-    if dW.numel() != Cout * F or db.numel() != Cout or not (dW.is_contiguous() and db.is_contiguous()):
-        raise ValueError("unet_conv1x1_out_bwd: dW [Cout, F] and db [Cout] expected")
+    dW = _out(dW, (Cout, F), a, "unet_conv1x1_out_bwd", "dW")
+    db = _out(db, (Cout,), a, "unet_conv1x1_out_bwd", "db")
     wp, wb = _ws_for(int(lib().gcl_unet_conv1x1_out_bwd_ws_bytes(B, H, W, F, Cout)), ws, a.device)
     _check(lib().gcl_unet_conv1x1_out_bwd(_p(dY), _p(a), _p(w), _p(dA), _p(dW), _p(db), B, H, W, F, Cout, wp, wb, _stream()))
     return dA, dW, db
@@ -2801,12 +2800,6 @@ def unet_conv1x1_out_bwd(dY, a, w, dA, dW=None, db=None, ws=None):
 def unet_v2_launches() -> int:
     """Kernels launched by the entry points of csrc/unet_v2.hip in this process."""
     return int(lib().gcl_unet_v2_launches())
-
-
-def _v2_rows(t, who, name):
-    if t.dim() != 4 or not t.is_contiguous():
-        raise ValueError(f"{who}: {name} is a contiguous [B, H, W, C] tensor, got {tuple(t.shape)}")
-    return t.shape[0], t.shape[1] * t.shape[2], t.shape[3]
 
 
 def _v2_slice(out, shape, who):
@@ -2821,20 +2814,20 @@ def _v2_slice(out, shape, who):
 
 def unet_v2_gn_stats(z, G: int, eps: float, mean=None, invstd=None):
     """(mean, invstd) float32 [B, G] of the GroupNorm of z [B, H, W, C] (see gcl_unet_v2_gn_stats)."""
-    B, HW, Cc = _v2_rows(z, "unet_v2_gn_stats", "z")
-    if mean is None:
-        mean = torch.empty(B, G, dtype=torch.float32, device=z.device)
-    if invstd is None:
-        invstd = torch.empty(B, G, dtype=torch.float32, device=z.device)
-    if G < 1 or Cc % G or any(tuple(t.shape) != (B, G) or not t.is_contiguous() for t in (mean, invstd)):
-        raise ValueError(f"unet_v2_gn_stats: G = {G} must divide C = {Cc}; mean and invstd are contiguous [{B}, {G}]")
+    n, Cc = _rows(z, "unet_v2_gn_stats", "z", 4)
+    B, HW = z.shape[0], n // z.shape[0]
+    if G < 1 or Cc % G:
+        raise ValueError(f"unet_v2_gn_stats: G = {G} must divide C = {Cc}")
+    mean = _out(mean, (B, G), z, "unet_v2_gn_stats", "mean", exact=True)
+    invstd = _out(invstd, (B, G), z, "unet_v2_gn_stats", "invstd", exact=True)
     _check(lib().gcl_unet_v2_gn_stats(_p(z), B, HW, Cc, int(G), float(eps), _p(mean), _p(invstd), _stream()))
     return mean, invstd
 
 
 def unet_v2_gn_gelu(z, gamma, beta, mean, invstd, out=None):
     """out = gelu(GroupNorm(z)) from the statistics [B, G] (see gcl_unet_v2_gn_gelu)."""
-    B, HW, Cc = _v2_rows(z, "unet_v2_gn_gelu", "z")
+    n, Cc = _rows(z, "unet_v2_gn_gelu", "z", 4)
+    B, HW = z.shape[0], n // z.shape[0]
     if out is None:
         out = torch.empty_like(z)
     G = mean.shape[-1]
@@ -2872,7 +2865,8 @@ def unet_v2_tail_ws_bytes(B: int, HW: int, Cc: int) -> int:
 def unet_v2_block_tail(z, gamma, beta, mean, invstd, skip, w1, b1, w2, b2, out=None, ws=None):
     """out = u * sigmoid(w2 gelu(w1 mean_hw(u) + b1) + b2), u = gelu(GroupNorm(z)) + skip (see gcl_unet_v2_block_tail).
     ws: a float64 tensor of unet_v2_tail_ws_bytes(B, H * W, C) bytes, or None for the shared workspace."""
-    B, HW, Cc = _v2_rows(z, "unet_v2_block_tail", "z")
+    n, Cc = _rows(z, "unet_v2_block_tail", "z", 4)
+    B, HW = z.shape[0], n // z.shape[0]
     if out is None:
         out = torch.empty_like(z)
     G, hid = mean.shape[-1], w1.shape[0]
@@ -2891,11 +2885,9 @@ def unet_v2_block_tail(z, gamma, beta, mean, invstd, skip, w1, b1, w2, b2, out=N
 def unet_v2_layernorm(x, gamma, beta, eps: float, out=None):
     """nn.LayerNorm over the last dimension of the contiguous x [..., C] (see gcl_unet_v2_layernorm)."""
     n, Cc = _rows(x, "unet_v2_layernorm")
-    if out is None:
-        out = torch.empty_like(x)
-    if tuple(out.shape) != tuple(x.shape) or not out.is_contiguous() or gamma.numel() != Cc or beta.numel() != Cc \
-            or not (gamma.is_contiguous() and beta.is_contiguous()):
-        raise ValueError(f"unet_v2_layernorm: out of x's shape and affine vectors of {Cc} values expected")
+    out = _out(out, x.shape, x, "unet_v2_layernorm", exact=True)
+    if gamma.numel() != Cc or beta.numel() != Cc or not (gamma.is_contiguous() and beta.is_contiguous()):
+        raise ValueError(f"unet_v2_layernorm: affine vectors of {Cc} values expected")
     _check(lib().gcl_unet_v2_layernorm(_p(x), _p(gamma), _p(beta), float(eps), _p(out), n, Cc, _stream()))
     return out
 
@@ -2908,10 +2900,7 @@ def unet_v2_attention(qkv, heads: int, out=None):
     if N > 4096:
         raise ValueError(f"unet_v2_attention: at most 4096 tokens, got {N}")
     Cc = C3 // 3
-    if out is None:
-        out = torch.empty(B, N, Cc, dtype=torch.float32, device=qkv.device)
-    if out.numel() != B * N * Cc or not out.is_contiguous():
-        raise ValueError(f"unet_v2_attention: out is a contiguous [{B}, {N}, {Cc}] tensor")
+    out = _out(out, (B, N, Cc), qkv, "unet_v2_attention")
     _check(lib().gcl_unet_v2_attention(_p(qkv), _p(out), B, N, int(heads), Cc // heads, _stream()))
     return out
 
@@ -2928,10 +2917,7 @@ def unet_v2_spectral_pack(w_re, w_im, mh: int, mw: int, out=None):
     Cin, Cout, MH, MW = w_re.shape
     if not (1 <= mh <= MH and 1 <= mw <= MW):
         raise ValueError(f"unet_v2_spectral_pack: {mh} x {mw} modes of {MH} x {MW}")
-    if out is None:
-        out = torch.empty(mh * mw, Cin, Cout, 2, dtype=torch.float32, device=w_re.device)
-    if out.numel() != mh * mw * Cin * Cout * 2 or not out.is_contiguous():
-        raise ValueError(f"unet_v2_spectral_pack: out holds {out.numel()} floats, {mh * mw * Cin * Cout * 2} expected")
+    out = _out(out, (mh * mw, Cin, Cout, 2), w_re, "unet_v2_spectral_pack")
     _check(lib().gcl_unet_v2_spectral_pack(_p(w_re), _p(w_im), Cin, Cout, MH, MW, int(mh), int(mw), _p(out), _stream()))
     return out
 
@@ -2941,10 +2927,7 @@ def unet_v2_spectral_fwd(x, mh: int, mw: int, out=None):
     if x.dim() != 4 or not x.is_contiguous():
         raise ValueError("unet_v2_spectral_fwd: x is a contiguous [B, Hb, Wb, C] tensor")
     B, Hb, Wb, Cc = x.shape
-    if out is None:
-        out = torch.empty(B, mh * mw, Cc, 2, dtype=torch.float32, device=x.device)
-    if out.numel() != B * mh * mw * Cc * 2 or not out.is_contiguous():
-        raise ValueError(f"unet_v2_spectral_fwd: out is a contiguous [{B}, {mh * mw}, {Cc}, 2] tensor")
+    out = _out(out, (B, mh * mw, Cc, 2), x, "unet_v2_spectral_fwd")
     _check(lib().gcl_unet_v2_spectral_fwd(_p(x), _p(out), B, Hb, Wb, Cc, int(mh), int(mw), _stream()))
     return out
 
@@ -2957,10 +2940,7 @@ def unet_v2_spectral_mix(X, packed, out=None):
                          f"{tuple(X.shape)} and {tuple(packed.shape)}")
     B, nm, Cin, _ = X.shape
     Cout = packed.shape[2]
-    if out is None:
-        out = torch.empty(B, nm, Cout, 2, dtype=torch.float32, device=X.device)
-    if out.numel() != B * nm * Cout * 2 or not out.is_contiguous():
-        raise ValueError(f"unet_v2_spectral_mix: out is a contiguous [{B}, {nm}, {Cout}, 2] tensor")
+    out = _out(out, (B, nm, Cout, 2), X, "unet_v2_spectral_mix")
     _check(lib().gcl_unet_v2_spectral_mix(_p(X), _p(packed), _p(out), B, nm, Cin, Cout, _stream()))
     return out
 

@@ -60,8 +60,104 @@ class Up(_Part):
         return self.conv.convs()
 
 
-class WeatherUNet(nn.Module):
+# The 14 convolutions in forward order: their names, the pooling level they run at (output width f << level), and how
+# the ones that do not read the previous activation find their input
+_NAMES = ["inc.0", "inc.3", "down1.0", "down1.3", "down2.0", "down2.3", "down3.0", "down3.3", "up1.0", "up1.3", "up2.0",
+          "up2.3", "up3.0", "up3.3"]
+_LEVEL = [0, 0, 1, 1, 2, 2, 3, 3, 2, 2, 1, 1, 0, 0]
+_UPCAT = {8: (5, 7), 10: (3, 9), 12: (1, 11)}  # convolution -> (skip activation, low activation)
+_POOL = {2: 1, 4: 3, 6: 5}                      # convolution -> pooled activation
+_SKIP_OF = {5: 8, 3: 10, 1: 12}                 # activation -> the UPCAT convolution that also read it
+
+
+def _levels(H, W):
+    sizes = [(H, W)]
+    for _ in range(3):
+        sizes.append((sizes[-1][0] // 2, sizes[-1][1] // 2))
+    return sizes
+
+
+def _conv_outputs(f, B, H, W, device):
+    """One channels-last float32 buffer per convolution output."""
+    sizes = _levels(H, W)
+    return [torch.empty(B, *sizes[lv], f << lv, dtype=torch.float32, device=device) for lv in _LEVEL]
+
+
+def _pack_cached(cache, key, weights, pack):
+    """cache[key]: pack(*weights, out=...) of the detached contiguous weights, redone when the (data_ptr, _version) of one
+    of them changed - into the old buffer while the device stays, because a captured graph may hold it."""
+    stamp = tuple((w.data_ptr(), w._version) for w in weights)
+    cur = cache.get(key)
+    if cur is None or cur[0] != stamp:
+        buf = cur[1] if cur is not None and cur[1].device == weights[0].device else None
+        cur = cache[key] = (stamp, pack(*(w.detach().contiguous() for w in weights), out=buf))
+    return cur[1]
+
+
+class _UNetBase(nn.Module):
+    """What `WeatherUNet` and `unet_v2.WeatherUNetV2` share: the input checks, the per-shape workspaces and the
+    inference forward over `launch_plan`.  A subclass sets in_channels / out_channels, `_INFERENCE_ONLY` (its refusal of
+    training mode) and `launch_plan(x, y, residual_from)`."""
+
+    _INFERENCE_ONLY = ""
+
+    def __init__(self):
+        super().__init__()
+        self._ws = {}  # (what, device, B, H, W) -> the buffers of that shape
+
+    @property
+    def num_params(self):
+        return sum(p.numel() for p in self.parameters() if p.requires_grad)
+
+    def _workspace_for(self, key, make):
+        ws = self._ws.get(key)
+        if ws is None:
+            ws = self._ws[key] = make()
+        return ws
+
+    def _check_shape(self, x):
+        """A subclass's own conditions on the [B, in_channels, H, W] input (ValueError)."""
+
+    def _check_input(self, x, residual_from=None):
+        who = type(self).__name__
+        if x.dim() != 4 or x.shape[1] != self.in_channels:
+            raise ValueError(f"{who}: input [B, {self.in_channels}, H, W] expected, got {tuple(x.shape)}")
+        B, _, H, W = x.shape
+        if H < MIN_GRID or W < MIN_GRID:
+            raise ValueError(f"{who}: the grid must be at least {MIN_GRID} x {MIN_GRID} (three poolings), got {H} x {W}")
+        self._check_shape(x)
+        if B < 1:
+            raise ValueError(f"{who}: empty batch")
+        if residual_from is not None:
+            c0, c1 = residual_from
+            if not (0 <= c0 < c1 <= self.in_channels and c1 - c0 == self.out_channels):
+                raise ValueError(f"{who}: residual_from {residual_from} is not a slice of {self.out_channels} of the "
+                                 f"{self.in_channels} input channels")
+        if x.dtype != torch.float32:
+            raise RuntimeError(f"{who} needs float32 tensors, got {x.dtype} (there is no CPU fallback)")
+        if not x.is_cuda:
+            raise RuntimeError(f"{who} needs GPU tensors (there is no CPU fallback)")
+
+    def forward(self, x, residual_from=None):
+        """x float32 [B, in_channels, H, W] on the GPU -> [B, out_channels, H, W].  residual_from = (c0, c1): the channel
+        slice x[:, c0:c1] is added to the output in the last launch (the x_last of predict_cascade.py:357-359 and
+        predict_v2.py:137-139)."""
+        if self.training:
+            raise NotImplementedError(self._INFERENCE_ONLY)
+        self._check_input(x, residual_from)
+        with torch.no_grad():
+            x = x.detach().contiguous()
+            y = torch.empty(x.shape[0], self.out_channels, *x.shape[2:], dtype=torch.float32, device=x.device)
+            for _, launch in self.launch_plan(x, y, residual_from):
+                launch()
+        return y
+
+
+class WeatherUNet(_UNetBase):
     """`WeatherUNet(in_channels, out_channels, base_filters=64)` of model.py:59-102, forward in eval mode only."""
+
+    _INFERENCE_ONLY = ("WeatherUNet: the HIP path is inference-only (no backward, no BatchNorm in training mode); call "
+                       ".eval(), and train with the reference's torch module through downscale.fit_downscaler")
 
     def __init__(self, in_channels: int, out_channels: int, base_filters: int = 64):
         super().__init__()
@@ -79,12 +175,7 @@ class WeatherUNet(nn.Module):
         self.up2 = Up(f * 4 + f * 2, f * 2)
         self.up3 = Up(f * 2 + f, f)
         self.out_conv = nn.Conv2d(f, out_channels, 1)
-        self._packed = {}  # conv index -> (data_ptr, _version, packed weights)
-        self._acts = {}    # (device, B, H, W) -> the activations of the 14 convolutions
-
-    @property
-    def num_params(self):
-        return sum(p.numel() for p in self.parameters() if p.requires_grad)
+        self._packed = {}  # conv index -> (stamp, packed weights) of _pack_cached
 
     def _conv_list(self):
         return [cb for blk in (self.inc, self.down1, self.down2, self.down3, self.up1, self.up2, self.up3)
@@ -92,61 +183,28 @@ class WeatherUNet(nn.Module):
 
     def _ensure_packed(self):
         """Packed copies of the 14 convolution weights, rebuilt for every weight that changed since its last pack."""
-        out = []
-        for i, (conv, _) in enumerate(self._conv_list()):
-            w = conv.weight
-            key = (w.data_ptr(), w._version)
-            cur = self._packed.get(i)
-            if cur is None or cur[0] != key:
-                buf = cur[1] if cur is not None and cur[1].device == w.device else None  # same place: a graph may hold it
-                cur = (key, hip.unet_pack_weights(w.detach().contiguous(), out=buf))
-                self._packed[i] = cur
-            out.append(cur[1])
-        return out
+        return [_pack_cached(self._packed, i, (conv.weight,), hip.unet_pack_weights)
+                for i, (conv, _) in enumerate(self._conv_list())]
 
     def _activations(self, B, H, W, device):
-        key = (str(device), B, H, W)
-        acts = self._acts.get(key)
-        if acts is None:
-            f = self.base_filters
-            sizes = [(H, W)]
-            for _ in range(3):
-                sizes.append((sizes[-1][0] // 2, sizes[-1][1] // 2))
-            plan = [(0, f), (0, f), (1, 2 * f), (1, 2 * f), (2, 4 * f), (2, 4 * f), (3, 8 * f), (3, 8 * f),
-                    (2, 4 * f), (2, 4 * f), (1, 2 * f), (1, 2 * f), (0, f), (0, f)]
-            acts = [torch.empty(B, sizes[lv][0], sizes[lv][1], c, dtype=torch.float32, device=device) for lv, c in plan]
-            self._acts[key] = acts
-        return acts
+        return self._workspace_for(("acts", str(device), B, H, W),
+                                   lambda: _conv_outputs(self.base_filters, B, H, W, device))
 
-    def forward(self, x, residual_from=None):
-        """x float32 [B, in_channels, H, W] on the GPU -> [B, out_channels, H, W].  residual_from = (c0, c1): the channel
-        slice x[:, c0:c1] is added to the output in the last launch (the x_last of predict_cascade.py:357-359)."""
-        if self.training:
-            raise NotImplementedError(
-                "WeatherUNet: the HIP path is inference-only (no backward, no BatchNorm in training mode); call .eval(), "
-                "and train with the reference's torch module through downscale.fit_downscaler")
-        if x.dim() != 4 or x.shape[1] != self.in_channels:
-            raise ValueError(f"WeatherUNet: input [B, {self.in_channels}, H, W] expected, got {tuple(x.shape)}")
-        B, _, H, W = x.shape
-        if H < MIN_GRID or W < MIN_GRID:
-            raise ValueError(f"WeatherUNet: the grid must be at least {MIN_GRID} x {MIN_GRID} (three poolings), got {H} x {W}")
-        if B < 1:
-            raise ValueError("WeatherUNet: empty batch")
-        if residual_from is not None:
-            c0, c1 = residual_from
-            if not (0 <= c0 < c1 <= self.in_channels and c1 - c0 == self.out_channels):
-                raise ValueError(f"WeatherUNet: residual_from {residual_from} is not a slice of {self.out_channels} of the "
-                                 f"{self.in_channels} input channels")
-        if x.dtype != torch.float32:
-            raise RuntimeError(f"WeatherUNet needs float32 tensors, got {x.dtype} (there is no CPU fallback)")
-        if not x.is_cuda:
-            raise RuntimeError("WeatherUNet needs GPU tensors (there is no CPU fallback)")
-        with torch.no_grad():
-            x = x.detach().contiguous()
-            y = torch.empty(B, self.out_channels, H, W, dtype=torch.float32, device=x.device)
-            for _, launch in self.launch_plan(x, y, residual_from):
-                launch()
-        return y
+    def _sources(self, x, a):
+        """[(name, source, Cin)] of the 14 convolutions reading the planar x and the activations a."""
+        S = hip.unet_src
+        out = []
+        for i, name in enumerate(_NAMES):
+            if i == 0:
+                src, cin = S(hip.UNET_PLANAR, x), x.shape[1]
+            elif i in _UPCAT:
+                skip, low = a[_UPCAT[i][0]], a[_UPCAT[i][1]]
+                src, cin = S(hip.UNET_UPCAT, skip, low), skip.shape[3] + low.shape[3]
+            else:
+                t = a[_POOL.get(i, i - 1)]
+                src, cin = S(hip.UNET_POOL if i in _POOL else hip.UNET_ROWS, t), t.shape[3]
+            out.append((name, src, cin))
+        return out
 
     def launch_plan(self, x, y, residual_from=None):
         """The 15 launches of a forward of the contiguous x into y, in order: [(name, callable)].  (tools/bench_unet.py
@@ -155,16 +213,9 @@ class WeatherUNet(nn.Module):
         packed = self._ensure_packed()
         a = self._activations(B, H, W, x.device)
         convs = self._conv_list()
-        S, f = hip.unet_src, self.base_filters
-        sources = [("inc.0", S(hip.UNET_PLANAR, x), self.in_channels), ("inc.3", S(hip.UNET_ROWS, a[0]), f),
-                   ("down1.0", S(hip.UNET_POOL, a[1]), f), ("down1.3", S(hip.UNET_ROWS, a[2]), 2 * f),
-                   ("down2.0", S(hip.UNET_POOL, a[3]), 2 * f), ("down2.3", S(hip.UNET_ROWS, a[4]), 4 * f),
-                   ("down3.0", S(hip.UNET_POOL, a[5]), 4 * f), ("down3.3", S(hip.UNET_ROWS, a[6]), 8 * f),
-                   ("up1.0", S(hip.UNET_UPCAT, a[5], a[7]), 12 * f), ("up1.3", S(hip.UNET_ROWS, a[8]), 4 * f),
-                   ("up2.0", S(hip.UNET_UPCAT, a[3], a[9]), 6 * f), ("up2.3", S(hip.UNET_ROWS, a[10]), 2 * f),
-                   ("up3.0", S(hip.UNET_UPCAT, a[1], a[11]), 3 * f), ("up3.3", S(hip.UNET_ROWS, a[12]), f)]
+        f = self.base_filters
         plan = []
-        for i, (name, src, cin) in enumerate(sources):
+        for i, (name, src, cin) in enumerate(self._sources(x, a)):
             bn = convs[i][1]
             norm = (bn.weight, bn.bias, bn.running_mean, bn.running_var)  # read at the call: no folded copy to go stale
             plan.append((name, lambda src=src, i=i, norm=norm, eps=bn.eps, cin=cin: hip.unet_conv3x3(
@@ -177,40 +228,21 @@ class WeatherUNet(nn.Module):
         return plan
 
 
-def _levels(H, W):
-    sizes = [(H, W)]
-    for _ in range(3):
-        sizes.append((sizes[-1][0] // 2, sizes[-1][1] // 2))
-    return sizes
-
-
 class _TrainWorkspace:
     """What one training step of one shape keeps between forward and backward: per convolution the raw output z, the
     activation a, the batch mean and invstd and the gradient buffer dA (dZ overwrites it); per pooled or concatenated
     convolution the data gradient at the convolution's own input size.  `step` counts the forwards that wrote it."""
 
-    def __init__(self, f, cin, B, H, W, device):
-        sizes = _levels(H, W)
-        lv = [0, 0, 1, 1, 2, 2, 3, 3, 2, 2, 1, 1, 0, 0]
-        cout = [f, f, 2 * f, 2 * f, 4 * f, 4 * f, 8 * f, 8 * f, 4 * f, 4 * f, 2 * f, 2 * f, f, f]
-        self.cin = [cin, f, f, 2 * f, 2 * f, 4 * f, 4 * f, 8 * f, 12 * f, 4 * f, 6 * f, 2 * f, 3 * f, f]
-
-        def rows(k, c):
-            return torch.empty(B, sizes[k][0], sizes[k][1], c, dtype=torch.float32, device=device)
-
-        self.z = [rows(k, c) for k, c in zip(lv, cout)]
-        self.a = [rows(k, c) for k, c in zip(lv, cout)]
-        self.dA = [rows(k, c) for k, c in zip(lv, cout)]
-        self.mean = [torch.empty(c, dtype=torch.float32, device=device) for c in cout]
-        self.invstd = [torch.empty(c, dtype=torch.float32, device=device) for c in cout]
-        # the data gradients that are not a dA: POOL layers 2, 4, 6 (at the pooled size), UPCAT layers 8, 10, 12
-        self.dX = {i: rows(lv[i], self.cin[i]) for i in (2, 4, 6, 8, 10, 12)}
+    def __init__(self, f, B, H, W, device):
+        self.z, self.a, self.dA = (_conv_outputs(f, B, H, W, device) for _ in range(3))
+        self.mean = [torch.empty(f << lv, dtype=torch.float32, device=device) for lv in _LEVEL]
+        self.invstd = [torch.empty(f << lv, dtype=torch.float32, device=device) for lv in _LEVEL]
+        # the data gradients that are not a dA: POOL layers 2, 4, 6 (at the pooled size), UPCAT layers 8, 10, 12; each has
+        # its convolution's output size and the channels of the activations the convolution read
+        self.dX = {i: torch.empty(*self.a[i].shape[:3], sum(self.a[k].shape[3] for k in reads), dtype=torch.float32,
+                                  device=device)
+                   for i, reads in [(i, (k,)) for i, k in _POOL.items()] + list(_UPCAT.items())}
         self.step = 0
-
-
-_UPCAT = {8: (5, 7), 10: (3, 9), 12: (1, 11)}  # convolution -> (skip activation, low activation)
-_POOL = {2: 1, 4: 3, 6: 5}                      # convolution -> pooled activation
-_SKIP_OF = {5: 8, 3: 10, 1: 12}                 # activation -> the UPCAT convolution that also read it
 
 
 class _UNetTrainStep(torch.autograd.Function):
@@ -256,55 +288,35 @@ class TrainableUNet(WeatherUNet):
 
     def __init__(self, in_channels: int, out_channels: int, base_filters: int = 64):
         super().__init__(in_channels, out_channels, base_filters)
-        self._packed_dgrad = {}  # conv index -> ((data_ptr, _version), transposed tap-flipped pack)
-        self._train_ws = {}      # (device, B, H, W) -> _TrainWorkspace; the most recent shape only
+        self._packed_dgrad = {}  # conv index -> (stamp, transposed tap-flipped pack) of _pack_cached
 
     def _ensure_packed_dgrad(self):
         """The data-gradient packs of convolutions 1 .. 13, rebuilt for every weight that changed since its last pack."""
-        out = {}
-        for i, (conv, _) in enumerate(self._conv_list()):
-            if i == 0:
-                continue
-            w = conv.weight
-            key = (w.data_ptr(), w._version)
-            cur = self._packed_dgrad.get(i)
-            if cur is None or cur[0] != key:
-                buf = cur[1] if cur is not None and cur[1].device == w.device else None
-                cur = (key, hip.unet_pack_weights_dgrad(w.detach().contiguous(), out=buf))
-                self._packed_dgrad[i] = cur
-            out[i] = cur[1]
-        return out
+        return {i: _pack_cached(self._packed_dgrad, i, (conv.weight,), hip.unet_pack_weights_dgrad)
+                for i, (conv, _) in enumerate(self._conv_list()) if i}
 
     def _train_workspace(self, B, H, W, device):
-        key = (str(device), B, H, W)
-        ws = self._train_ws.get(key)
-        if ws is None:
+        key = ("train", str(device), B, H, W)
+        if key not in self._ws:
             # one shape at a time (about 0.55 GB at 41 x 61, f = 64, B = 32): a new shape replaces the old one, whose
             # memory is freed once no pending backward holds it
-            ws = _TrainWorkspace(self.base_filters, self.in_channels, B, H, W, device)
-            self._train_ws = {key: ws}
-        return ws
+            self._ws = {k: v for k, v in self._ws.items() if k[0] != "train"}
+        return self._workspace_for(key, lambda: _TrainWorkspace(self.base_filters, B, H, W, device))
 
     def release_workspaces(self):
         """Drop the training workspace and the inference activations (they are rebuilt on the next forward)."""
-        self._train_ws, self._acts = {}, {}
+        self._ws = {}
 
-    def _sources(self, x, a):
-        S = hip.unet_src
-        names = ["inc.0", "inc.3", "down1.0", "down1.3", "down2.0", "down2.3", "down3.0", "down3.3", "up1.0", "up1.3",
-                 "up2.0", "up2.3", "up3.0", "up3.3"]
-        out = []
-        for i, name in enumerate(names):
-            if i == 0:
-                src = S(hip.UNET_PLANAR, x)
-            elif i in _UPCAT:
-                src = S(hip.UNET_UPCAT, a[_UPCAT[i][0]], a[_UPCAT[i][1]])
-            elif i in _POOL:
-                src = S(hip.UNET_POOL, a[_POOL[i]])
-            else:
-                src = S(hip.UNET_ROWS, a[i - 1])
-            out.append((name, src))
-        return out
+    def _check_shape(self, x):
+        if not self.training:
+            return
+        B, _, H, W = x.shape
+        if B * (H // 8) * (W // 8) < 2:
+            raise ValueError(f"TrainableUNet: expected more than 1 value per channel when training, got "
+                             f"{B} x {H // 8} x {W // 8} at the deepest level")
+        if x.requires_grad:
+            raise ValueError("TrainableUNet: an input that requires grad is not supported (there is no gradient with "
+                             "respect to x)")
 
     def forward(self, x, residual_from=None):
         """Eval mode: `WeatherUNet.forward`.  Training mode: x float32 [B, in_channels, H, W] on the GPU (not requiring
@@ -315,21 +327,7 @@ class TrainableUNet(WeatherUNet):
         if residual_from is not None:
             raise ValueError("TrainableUNet: residual_from is an inference option; in training the loss adds x_last "
                              "(downscaler_loss(..., X=X, residual=True))")
-        if x.dim() != 4 or x.shape[1] != self.in_channels:
-            raise ValueError(f"TrainableUNet: input [B, {self.in_channels}, H, W] expected, got {tuple(x.shape)}")
-        B, _, H, W = x.shape
-        if H < MIN_GRID or W < MIN_GRID:
-            raise ValueError(f"TrainableUNet: the grid must be at least {MIN_GRID} x {MIN_GRID} (three poolings), got {H} x {W}")
-        if B * (H // 8) * (W // 8) < 2:
-            raise ValueError(f"TrainableUNet: expected more than 1 value per channel when training, got "
-                             f"{B} x {H // 8} x {W // 8} at the deepest level")
-        if x.requires_grad:
-            raise ValueError("TrainableUNet: an input that requires grad is not supported (there is no gradient with "
-                             "respect to x)")
-        if x.dtype != torch.float32:
-            raise RuntimeError(f"TrainableUNet needs float32 tensors, got {x.dtype} (there is no CPU fallback)")
-        if not x.is_cuda:
-            raise RuntimeError("TrainableUNet needs GPU tensors (there is no CPU fallback)")
+        self._check_input(x)
         for _, bn in self._conv_list():
             if bn.momentum is None or not bn.track_running_stats:
                 raise ValueError("TrainableUNet: BatchNorm2d with a momentum and running statistics expected")
@@ -340,9 +338,9 @@ class TrainableUNet(WeatherUNet):
         packed = self._ensure_packed()
         convs = self._conv_list()
         plan = []
-        for i, (name, src) in enumerate(self._sources(x, ws.a)):
+        for i, (name, src, cin) in enumerate(self._sources(x, ws.a)):
             bn = convs[i][1]
-            plan.append((name, lambda src=src, i=i, eps=bn.eps: hip.unet_conv3x3(src, packed[i], None, eps, ws.z[i], ws.cin[i])))
+            plan.append((name, lambda src=src, i=i, eps=bn.eps, cin=cin: hip.unet_conv3x3(src, packed[i], None, eps, ws.z[i], cin)))
             plan.append((name + ".bn_stats", lambda i=i, bn=bn: hip.unet_bn_stats(
                 ws.z[i], bn.eps, bn.momentum, ws.mean[i], ws.invstd[i], bn.running_mean, bn.running_var,
                 bn.num_batches_tracked)))
@@ -375,7 +373,7 @@ class TrainableUNet(WeatherUNet):
 
         plan.append(("out_conv.bwd", out_bwd))
         for i in range(13, -1, -1):
-            name, src = sources[i]
+            name, src, cin = sources[i]
             conv, bn = convs[i]
 
             def bn_bwd(i=i, bn=bn):
@@ -386,8 +384,8 @@ class TrainableUNet(WeatherUNet):
 
             plan.append((name + ".bn_gelu_bwd", bn_bwd))
             if wanted(conv.weight):
-                def wgrad(i=i, src=src, conv=conv):
-                    grads[id(conv.weight)] = hip.unet_conv3x3_wgrad(src, ws.dA[i], ws.cin[i])
+                def wgrad(i=i, src=src, conv=conv, cin=cin):
+                    grads[id(conv.weight)] = hip.unet_conv3x3_wgrad(src, ws.dA[i], cin)
 
                 plan.append((name + ".wgrad", wgrad))
             if i == 0:

@@ -23,7 +23,7 @@ import torch
 import torch.nn as nn
 
 from . import hip
-from .unet import MIN_GRID, _levels, _Part
+from .unet import _levels, _pack_cached, _Part, _UNetBase
 
 MAX_TOKENS = 4096  # bottleneck pixels the attention kernel takes
 
@@ -122,11 +122,13 @@ class _Workspace:
         self.X, self.O = new(B, nmodes, C, 2), new(B, nmodes, C, 2)
 
 
-class WeatherUNetV2(nn.Module):
+class WeatherUNetV2(_UNetBase):
     """`WeatherUNetV2(in_channels, out_channels, base_filters=64, attn_heads=4, spectral_modes=4)` of
     model_v2.py:153-224, forward in eval mode only: 72 launches (see the module's docstring)."""
 
     LAUNCHES = 72
+    _INFERENCE_ONLY = ("WeatherUNetV2: the HIP path is inference-only (no backward through GroupNorm, the attention or "
+                       "the spectral layer); call .eval()")
 
     def __init__(self, in_channels: int, out_channels: int, base_filters: int = 64, attn_heads: int = 4,
                  spectral_modes: int = 4):
@@ -152,93 +154,38 @@ class WeatherUNetV2(nn.Module):
         self.up2 = Up(f * 4 + f * 2, f * 2)
         self.up3 = Up(f * 2 + f, f)
         self.out_conv = nn.Conv2d(f, out_channels, 1)
-        self._packed = {}       # conv index -> ((data_ptr, _version), packed weights)
-        self._packed_spec = {}  # (mh, mw) -> ((ptrs and versions of weights_re / weights_im), packed complex weights)
-        self._ws = {}           # (device, B, H, W) -> _Workspace
-
-    @property
-    def num_params(self):
-        return sum(p.numel() for p in self.parameters() if p.requires_grad)
+        self._packed = {}       # conv index -> (stamp, packed weights) of _pack_cached
+        self._packed_spec = {}  # (mh, mw) -> (stamp, packed complex weights) of _pack_cached
 
     def _blocks(self):
         return [self.inc, self.down1.conv, self.down2.conv, self.down3.conv, self.bottleneck_mix, self.up1.conv,
                 self.up2.conv, self.up3.conv]
 
-    def _spectral_key(self):
-        sp = self.bottleneck_spectral
-        return tuple(v for w in (sp.weights_re, sp.weights_im) for v in (w.data_ptr(), w._version))
-
     def _pack_spectral(self, mh, mw):
         sp = self.bottleneck_spectral
-        key = self._spectral_key()
-        cur = self._packed_spec.get((mh, mw))
-        if cur is None or cur[0] != key:
-            buf = cur[1] if cur is not None and cur[1].device == sp.weights_re.device else None
-            cur = (key, hip.unet_v2_spectral_pack(sp.weights_re.detach().contiguous(), sp.weights_im.detach().contiguous(),
-                                                  mh, mw, out=buf))
-            self._packed_spec[(mh, mw)] = cur
-        return cur[1]
+        return _pack_cached(self._packed_spec, (mh, mw), (sp.weights_re, sp.weights_im),
+                            lambda re, im, out: hip.unet_v2_spectral_pack(re, im, mh, mw, out=out))
 
     def _ensure_packed(self, modes=None):
         """Packed copies of the 16 convolution weights and of the spectral weights for every mode count in use (and for
         `modes` = (mh, mw)), rebuilt for every weight that changed since its last pack."""
-        out = []
-        for i, blk in enumerate(self._blocks()):
-            for j in (0, 3):
-                w = blk.conv[j].weight
-                idx = 2 * i + (j == 3)
-                key = (w.data_ptr(), w._version)
-                cur = self._packed.get(idx)
-                if cur is None or cur[0] != key:
-                    buf = cur[1] if cur is not None and cur[1].device == w.device else None  # a graph may hold it
-                    cur = (key, hip.unet_pack_weights(w.detach().contiguous(), out=buf))
-                    self._packed[idx] = cur
-                out.append(cur[1])
+        out = [_pack_cached(self._packed, 2 * i + (j == 3), (blk.conv[j].weight,), hip.unet_pack_weights)
+               for i, blk in enumerate(self._blocks()) for j in (0, 3)]
         for m in list(self._packed_spec):
             self._pack_spectral(*m)
         spec = self._pack_spectral(*modes) if modes is not None else None
         return out, spec
 
     def _workspace(self, B, H, W, device, nmodes):
-        key = (str(device), B, H, W)
-        ws = self._ws.get(key)
-        if ws is None:
-            groups = [blk.conv[1].num_groups for blk in self._blocks()]
-            ws = _Workspace(self.base_filters, groups, nmodes, B, H, W, device)
-            self._ws[key] = ws
-        return ws
+        groups = [blk.conv[1].num_groups for blk in self._blocks()]
+        return self._workspace_for((str(device), B, H, W),
+                                   lambda: _Workspace(self.base_filters, groups, nmodes, B, H, W, device))
 
-    def forward(self, x, residual_from=None):
-        """x float32 [B, in_channels, H, W] on the GPU -> [B, out_channels, H, W].  residual_from = (c0, c1): the channel
-        slice x[:, c0:c1] is added to the output in the last launch (the x_last + delta of predict_v2.py:137-139)."""
-        if self.training:
-            raise NotImplementedError("WeatherUNetV2: the HIP path is inference-only (no backward through GroupNorm, the "
-                                      "attention or the spectral layer); call .eval()")
-        if x.dim() != 4 or x.shape[1] != self.in_channels:
-            raise ValueError(f"WeatherUNetV2: input [B, {self.in_channels}, H, W] expected, got {tuple(x.shape)}")
-        B, _, H, W = x.shape
-        if H < MIN_GRID or W < MIN_GRID:
-            raise ValueError(f"WeatherUNetV2: the grid must be at least {MIN_GRID} x {MIN_GRID} (three poolings), got {H} x {W}")
-        if B < 1:
-            raise ValueError("WeatherUNetV2: empty batch")
+    def _check_shape(self, x):
+        H, W = x.shape[2:]
         if (H // 8) * (W // 8) > MAX_TOKENS:
             raise ValueError(f"WeatherUNetV2: the attention takes at most {MAX_TOKENS} bottleneck pixels, "
                              f"{H} x {W} gives {(H // 8) * (W // 8)}")
-        if residual_from is not None:
-            c0, c1 = residual_from
-            if not (0 <= c0 < c1 <= self.in_channels and c1 - c0 == self.out_channels):
-                raise ValueError(f"WeatherUNetV2: residual_from {residual_from} is not a slice of {self.out_channels} of "
-                                 f"the {self.in_channels} input channels")
-        if x.dtype != torch.float32:
-            raise RuntimeError(f"WeatherUNetV2 needs float32 tensors, got {x.dtype} (there is no CPU fallback)")
-        if not x.is_cuda:
-            raise RuntimeError("WeatherUNetV2 needs GPU tensors (there is no CPU fallback)")
-        with torch.no_grad():
-            x = x.detach().contiguous()
-            y = torch.empty(B, self.out_channels, H, W, dtype=torch.float32, device=x.device)
-            for _, launch in self.launch_plan(x, y, residual_from):
-                launch()
-        return y
 
     def _block_plan(self, plan, name, k, blk, src, cin, lv, out, packed, ws):
         """The 9 launches of ResConvBlock k reading `src` (cin channels) into `out` at level lv."""

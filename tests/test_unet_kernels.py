@@ -16,7 +16,7 @@ import torch.nn.functional as F
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
 import unet_case as UC  # noqa: E402
-from layouts import NAN, SENT, Guarded, same_bits  # noqa: E402
+from layouts import NAN, SENT, Guarded, launched, same_bits, targs  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -165,6 +165,94 @@ def test_conv_refuses_bad_shapes(hip):
     with pytest.raises(RuntimeError, match="does not fit"):
         hip.unet_conv3x3(hip.unet_src(hip.UNET_UPCAT, a[..., :4].contiguous(), a[..., 4:].contiguous()), p, None, EPS,
                          torch.zeros(1, 4, 4, 8, device=DEV), 8)
+
+
+def _call_entry(hip, entry, src, H, W, Cin):
+    """`entry` reading `src` as the Cin channels of a 1 x H x W input, every other operand a valid one (Cout = 8)."""
+    y = torch.zeros(1, H, W, 8, device=DEV)
+    if entry == "unet_conv3x3":
+        hip.unet_conv3x3(src, torch.zeros(int(hip.lib().gcl_unet_packed_floats(Cin, 8)), device=DEV), None, EPS, y, Cin)
+    elif entry == "unet_conv3x3_wgrad":
+        hip.unet_conv3x3_wgrad(src, y, Cin)
+    else:
+        hip.unet_v2_conv1x1(src, torch.zeros(8, Cin, device=DEV), y, Cin)
+
+
+@pytest.mark.parametrize("entry", ["unet_conv3x3", "unet_conv3x3_wgrad", "unet_v2_conv1x1"])
+def test_source_refusals_at_every_entry(hip, entry):
+    """Every entry point that takes a gcl_unet_src_t refuses a descriptor that does not describe its input, names itself
+    in the message, and launches nothing."""
+    a = torch.zeros(1, 4, 4, 8, device=DEV)
+    skip, low = a[..., :4].contiguous(), a[..., 4:].contiguous()
+    cases = [("does not halve", hip.unet_src(hip.UNET_POOL, a), 3, 2, 8),
+             ("does not fit", hip.unet_src(hip.UNET_UPCAT, skip, low), 4, 4, 8),
+             (r"C1 \+ C2", hip.unet_src(hip.UNET_UPCAT, skip, low), 4, 4, 12),
+             ("UPCAT needs b", hip.UnetSrc(skip.data_ptr(), None, hip.UNET_UPCAT, 4, 4, 2, 2), 4, 4, 8),
+             ("source kind", hip.UnetSrc(a.data_ptr(), None, 7, 0, 0, 0, 0), 4, 4, 8)]
+    counters = (hip.unet_launches, hip.unet_train_launches, hip.unet_v2_launches)
+    before = [c() for c in counters]
+    for fragment, src, H, W, Cin in cases:
+        with pytest.raises(RuntimeError, match=f"gcl_{entry}: .*{fragment}"):
+            _call_entry(hip, entry, src, H, W, Cin)
+    assert [c() for c in counters] == before, "a refused call launched a kernel"
+
+
+def _one_float_in(t):
+    """A contiguous copy of t that starts one float into a flat buffer: 4 bytes past a 16-byte boundary."""
+    buf = torch.empty(t.numel() + 1, device=DEV)
+    view = buf[1:1 + t.numel()].view(t.shape)
+    view.copy_(t)
+    assert view.is_contiguous() and view.data_ptr() % 16 == 4
+    return view
+
+
+@pytest.mark.parametrize("kind", ["rows", "pool", "upcat"])
+def test_scalar_and_16_byte_staging_give_the_same_values(hip, kind):
+    """A source whose channels come in fours is staged with 16-byte reads when its operands are 16-byte aligned and
+    element by element when one of them is not.  ROWS and POOL reads do no arithmetic: the convolution and the weight
+    gradient give the same bits either way.  The UPCAT read interpolates, and the compiler contracts the bilinear
+    expression differently in the two loops: there both results are held to the bound of the other
+    convolution tests against float64.  B = 2, 6 x 11: two tiles across, tiles cut by both edges."""
+    B, H, W, Cin, Cout = 2, 6, 11, 8, 8
+    if kind == "upcat":  # a 6 x 11 x 4 skip and a 3 x 5 x 4 low tensor (padded in w); only the low tensor moves
+        cpu = [rnd(B, H, W, 4, seed=61), rnd(B, 3, 5, 4, seed=62)]
+    else:
+        cpu = [rnd(B, *((13, 22) if kind == "pool" else (H, W)), Cin, seed=60)]
+    ops = [t.to(DEV) for t in cpu]
+    K = {"rows": hip.UNET_ROWS, "pool": hip.UNET_POOL, "upcat": hip.UNET_UPCAT}[kind]
+    aligned = hip.unet_src(K, *ops)
+    moved = ops[:-1] + [_one_float_in(ops[-1])]
+    shifted = hip.unet_src(K, *moved)
+    assert all(t.data_ptr() % 16 == 0 for t in ops)
+    w, dZ = rnd(Cout, Cin, 3, 3, seed=63, scale=0.2), rnd(B, H, W, Cout, seed=64)
+    packed, dZd = hip.unet_pack_weights(w.to(DEV)), dZ.to(DEV)
+
+    def conv(src):
+        return hip.unet_conv3x3(src, packed, None, EPS, torch.empty(B, H, W, Cout, device=DEV), Cin).permute(0, 3, 1, 2)
+
+    def conv_oracle(dtype):
+        planar = [t.permute(0, 3, 1, 2).to(dtype) for t in cpu]
+        return conv_ref(virtual_input(kind, *planar, size=(H, W)), w, None, dtype)
+
+    def wgrad_oracle(dtype):
+        planar = [t.permute(0, 3, 1, 2).to(dtype) for t in cpu]
+        wz = torch.zeros(Cout, Cin, 3, 3, dtype=dtype, requires_grad=True)
+        F.conv2d(virtual_input(kind, *planar, size=(H, W)), wz, padding=1).backward(dZ.permute(0, 3, 1, 2).to(dtype))
+        return wz.grad
+
+    for what, kern, run, oracle in (("conv3x3", "unet_conv3x3_kernel", conv, conv_oracle),
+                                    ("wgrad", "unet_wgrad_kernel", lambda src: hip.unet_conv3x3_wgrad(src, dZd, Cin), wgrad_oracle)):
+        (vec, one), names = launched(lambda: (run(aligned), run(shifted)))
+        assert sorted(t[1] for t in targs(names, kern)) == ["1", "4"], f"{what}: both read widths were to run, got {names}"
+        differ = int((vec != one).sum())
+        print(f"[unet] {kind} {what}: {differ} of {vec.numel()} elements differ between the read widths, "
+              f"max |difference| {float((vec - one).abs().max()):.3e}")
+        if kind == "upcat":
+            y64, y32 = oracle(torch.float64), oracle(torch.float32)
+            UC.check(vec.cpu(), y64, y32, f"upcat {what}, 16-byte reads")
+            UC.check(one.cpu(), y64, y32, f"upcat {what}, scalar reads")
+        else:
+            assert not vec.isnan().any() and same_bits(vec, one), f"{kind} {what}: the two read widths differ"
 
 
 # ---------------------------------------------------------------------------------------------------------------------
