@@ -126,6 +126,7 @@ __device__ __forceinline__ void stage_panel(float* Wl, const float* __restrict__
 // Per-wave LDS region (floats): tile / output staging [TILE_F] | sink [64] | rowptr [36] | ecol [256] | ew [256]
 // ---------------------------------------------------------------------------------------------
 constexpr int kStagger = 2;  // x s_sleep(64) = 2 x 4096 cycles per wave group
+constexpr int kStaggerMinItems = 16;  // split-operand form: a wave with fewer items does not sleep (GCL_GCN_EDGE_PIPE=0: every wave does)
 constexpr int kSinkF = 64, kRpF = 36, kMetaF = kRpF + 2 * 32 * gcl::kEll;
 
 struct TileMeta {  // next tile's metadata in flight
@@ -385,52 +386,60 @@ __device__ __forceinline__ void stage_panel_x3(unsigned char* Wimg, const float*
 // acc[c] += At[32][K] x W[c*32..+31][K]^T on the bf16 pipe (x3.h): the fp32 tile is read in the bf16 operand layout
 // (lane (r, h): 8 consecutive k of row r = four 8-byte reads, conflict-free on the KP = K + 2 stride), split in
 // registers into hi / mid / lo fragments, and multiplied with the weight piece fragments (ds_read_b128) in three
-// passes, smallest products first.  K % 16 == 0.
-template <int NS>
-__device__ __forceinline__ void mfma_tile_x3(f32x16 (&acc)[NS], const float* __restrict__ At, int KP,
-                                             const unsigned char* __restrict__ Wimg, int nks) {
+// passes, smallest products first.  K = 16 * NKS.
+// NKS is a compile-time constant so that the chain is straight-line code: with `if (s < nks)` around every k-step the
+// chain had thirteen control-flow joins per tile, and at each the compiler copied both accumulators (32 v_mov that wait
+// for the matrix pipe to drain) - 388 copies per tile with two column blocks, more than half of the dense part's time
+// on the 64-wide layers.
+template <int NS, int NKS>
+__device__ __forceinline__ void mfma_chain_x3(f32x16 (&acc)[NS], const float* __restrict__ At, int KP,
+                                              const unsigned char* __restrict__ Wimg) {
   const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
   const float* ap = At + r * KP + 8 * h;
   const int pieceB = NS * 32 * kWRowB;
   const unsigned char* wp = Wimg + r * kWRowB + h * 16;
-  bf16x8 ah[4], am[4], al[4];
+  bf16x8 ah[NKS], am[NKS], al[NKS];
 #pragma unroll
-  for (int s = 0; s < 4; ++s) {
-    if (s < nks) {
-      const float2 f0 = *reinterpret_cast<const float2*>(ap + 16 * s), f1 = *reinterpret_cast<const float2*>(ap + 16 * s + 2);
-      const float2 f2 = *reinterpret_cast<const float2*>(ap + 16 * s + 4), f3 = *reinterpret_cast<const float2*>(ap + 16 * s + 6);
-      const Pk3 p0 = split2(f0.x, f0.y), p1 = split2(f1.x, f1.y), p2 = split2(f2.x, f2.y), p3 = split2(f3.x, f3.y);
-      typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-      ah[s] = __builtin_bit_cast(bf16x8, u32x4_t{p0.h, p1.h, p2.h, p3.h});
-      am[s] = __builtin_bit_cast(bf16x8, u32x4_t{p0.m, p1.m, p2.m, p3.m});
-      al[s] = __builtin_bit_cast(bf16x8, u32x4_t{p0.l, p1.l, p2.l, p3.l});
-    }
+  for (int s = 0; s < NKS; ++s) {
+    const float2 f0 = *reinterpret_cast<const float2*>(ap + 16 * s), f1 = *reinterpret_cast<const float2*>(ap + 16 * s + 2);
+    const float2 f2 = *reinterpret_cast<const float2*>(ap + 16 * s + 4), f3 = *reinterpret_cast<const float2*>(ap + 16 * s + 6);
+    const Pk3 p0 = split2(f0.x, f0.y), p1 = split2(f1.x, f1.y), p2 = split2(f2.x, f2.y), p3 = split2(f3.x, f3.y);
+    typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
+    ah[s] = __builtin_bit_cast(bf16x8, u32x4_t{p0.h, p1.h, p2.h, p3.h});
+    am[s] = __builtin_bit_cast(bf16x8, u32x4_t{p0.m, p1.m, p2.m, p3.m});
+    al[s] = __builtin_bit_cast(bf16x8, u32x4_t{p0.l, p1.l, p2.l, p3.l});
   }
   auto wfrag = [&](int c, int s, int p) {
     return *reinterpret_cast<const bf16x8*>(wp + p * pieceB + c * 32 * kWRowB + s * 32);
   };
 #pragma unroll
-  for (int s = 0; s < 4; ++s)
-    if (s < nks)
+  for (int s = 0; s < NKS; ++s)
 #pragma unroll
-      for (int c = 0; c < NS; ++c) {
-        acc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[s], wfrag(c, s, 0), acc[c], 0, 0, 0);
-        acc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[s], wfrag(c, s, 2), acc[c], 0, 0, 0);
-        acc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am[s], wfrag(c, s, 1), acc[c], 0, 0, 0);
-      }
+    for (int c = 0; c < NS; ++c) {
+      acc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[s], wfrag(c, s, 0), acc[c], 0, 0, 0);
+      acc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[s], wfrag(c, s, 2), acc[c], 0, 0, 0);
+      acc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am[s], wfrag(c, s, 1), acc[c], 0, 0, 0);
+    }
 #pragma unroll
-  for (int s = 0; s < 4; ++s)
-    if (s < nks)
+  for (int s = 0; s < NKS; ++s)
 #pragma unroll
-      for (int c = 0; c < NS; ++c) {
-        acc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am[s], wfrag(c, s, 0), acc[c], 0, 0, 0);
-        acc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[s], wfrag(c, s, 1), acc[c], 0, 0, 0);
-      }
+    for (int c = 0; c < NS; ++c) {
+      acc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am[s], wfrag(c, s, 0), acc[c], 0, 0, 0);
+      acc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[s], wfrag(c, s, 1), acc[c], 0, 0, 0);
+    }
 #pragma unroll
-  for (int s = 0; s < 4; ++s)
-    if (s < nks)
+  for (int s = 0; s < NKS; ++s)
 #pragma unroll
-      for (int c = 0; c < NS; ++c) acc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[s], wfrag(c, s, 0), acc[c], 0, 0, 0);
+    for (int c = 0; c < NS; ++c) acc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[s], wfrag(c, s, 0), acc[c], 0, 0, 0);
+}
+// ONE branch on the number of k-steps (K = 16, 32, 48 or 64), in front of the chain
+template <int NS>
+__device__ __forceinline__ void mfma_tile_x3(f32x16 (&acc)[NS], const float* __restrict__ At, int KP,
+                                             const unsigned char* __restrict__ Wimg, int nks) {
+  if (nks >= 4) mfma_chain_x3<NS, 4>(acc, At, KP, Wimg);
+  else if (nks == 3) mfma_chain_x3<NS, 3>(acc, At, KP, Wimg);
+  else if (nks == 2) mfma_chain_x3<NS, 2>(acc, At, KP, Wimg);
+  else mfma_chain_x3<NS, 1>(acc, At, KP, Wimg);
 }
 
 // Transpose the 32 x (NS*32) accumulator tile through the wave's LDS region Ot[32][NS*32] and write whole
@@ -485,7 +494,7 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void gcn_fwd_kernel(
     const int32_t* __restrict__ ecol, const float* __restrict__ ew, const float* __restrict__ X, int64_t ldx,
     int64_t bsx, const float* __restrict__ slope_p, const float* __restrict__ W, const float* __restrict__ bias,
     float* __restrict__ Y, int64_t ldy, int64_t bsy, int32_t n, int32_t B, int32_t K, int32_t N, int32_t Nst,
-    int32_t nRT, int32_t n_out, float* __restrict__ Yb, int64_t ldb, int64_t bsb, int32_t head) {
+    int32_t nRT, int32_t n_out, float* __restrict__ Yb, int64_t ldb, int64_t bsb, int32_t head, int32_t stag_min) {
   extern __shared__ __align__(16) float smem[];
   const int KP = K + 2;  // K % 4 == 0: even stride with KP/2 odd -> conflict-free 8-byte fragment reads
   float* Wl = smem;      // fp32: [NS*32][KP]; X3: three bf16 piece images [NS*32][kWRowB bytes]
@@ -523,7 +532,9 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void gcn_fwd_kernel(
   // Stagger: the waves run the same program, so without it they fall into lockstep - all twelve gather at once
   // (the CU's load path is shared, each crawls), then all want the matrix pipe at once.  Wave groups 1 and 2
   // start a third / two thirds of a tile period later; equal periods keep the offset.  (Speed only.)
-  {
+  // A wave with fewer than stag_min items starts at once: the sleep is about one item, and on the encoder and decoder
+  // graphs of the 64x32 grid a wave runs 2 - 7 items (the mesh, where the stagger was tuned: about 80).
+  if (sc.left >= stag_min) {
     const int grp = __builtin_amdgcn_readfirstlane(wave) >> 2;
     for (int i = 0; i < grp * kStagger; ++i) __builtin_amdgcn_s_sleep(64);
   }
@@ -971,7 +982,7 @@ using gcl::plan::GcnForm;
 static gcl::plan::GcnSwitches gcn_switches() {
   static const int bpc_env = gcl::env_int("GCL_GCN_HALO_BPC", 0);
   return {gcl::env_int("GCL_GCN_HALO", 1) != 0, gcl::env_int("GCL_X3", 1) && gcl::env_int("GCL_X3_GCN", 1),
-          gcl::env_int("GCL_GCN_HALO_FORM", 1) != 0, bpc_env};
+          gcl::env_int("GCL_GCN_HALO_FORM", 1) != 0, bpc_env, gcl::env_int("GCL_GCN_EDGE_PIPE", 1) != 0};
 }
 
 // Source-tile forms of the layer (gcn_halo_fwd_kernel): graphs with a tile layout (mesh rows in tile order), 64-wide rows,
@@ -1055,8 +1066,8 @@ static int layer_fwd_impl(const gcl_graph_t* g, const float* x, int64_t ldx, int
   const int64_t ldb = sp ? sp->ldb : 0, bsb = sp ? sp->bsb : 0;
   const int32_t head = sp ? sp->head : 0;
   // present: the form with the output-row predicate, where it exists; storing every row is always right too
-  const gcl::plan::GcnPlan p = gcl::plan::plan_gcn_layer(
-      *g, {ldx, bsx, ldy, B, Fin, rows_out, 0, false, present != nullptr, sp != nullptr}, gcn_switches());
+  const gcl::plan::GcnSwitches sw = gcn_switches();
+  const gcl::plan::GcnPlan p = gcl::plan::plan_gcn_layer(*g, {ldx, bsx, ldy, B, Fin, rows_out, 0, false, present != nullptr, sp != nullptr}, sw);
   GCL_CHECK_ARG(p.form != GcnForm::kRefused, "%s", p.why);
   if (gcl::plan::is_tile(p.form))
     return launch_gcn_tile(g, p, x, ldx, bsx, nullptr, act, slope, W, bias, y, ldy, bsy, B, Fin, Fout, Fout_store, st,
@@ -1074,11 +1085,12 @@ static int layer_fwd_impl(const gcl_graph_t* g, const float* x, int64_t ldx, int
   int64_t grid = gcl::kNumCU;
   if (tiles < grid * NWr) grid = gcl::cdiv(tiles, NWr);
   if (B >= gcl::kNumXCD) grid = gcl::cdiv(grid, gcl::kNumXCD) * gcl::kNumXCD;  // XCD-aware schedule needs a multiple of 8
+  const int32_t stag_min = x3 && sw.edge_pipe ? kStaggerMinItems : 0;  // (speed only: the waves' start times)
   const int ewidth = g->ell_cover;  // smallest prefix width that covers (almost) every row: the fix-up loop is the slow path
   auto launch = [&](auto kern, int nw) {
     GCL_ENSURE_DYN_LDS(kern, gcl::kLdsBytes);
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(nw * 64), lds, st, g->rowptr, g->col, g->w, g->ecol, g->ew, x, ldx, bsx,
-                       slope, W, bias, y, ldy, bsy, n, B, Fin, Fout, Fout_store, nRT, rows_out, yb, ldb, bsb, head);
+                       slope, W, bias, y, ldy, bsy, n, B, Fin, Fout, Fout_store, nRT, rows_out, yb, ldb, bsb, head, stag_min);
     return (int)GCL_OK;
   };
   using gcl::plan::pick;

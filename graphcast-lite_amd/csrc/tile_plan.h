@@ -99,7 +99,11 @@ struct GcnCall {
   bool present = false;  // gcl_gcn_layer_fwd_present
   bool two_part = false; // gcl_gcn_layer_fwd_split (ldy: the first part's)
 };
-struct GcnSwitches { bool halo, x3, form; int bpc; };  // GCL_GCN_HALO, GCL_X3 && GCL_X3_GCN, GCL_GCN_HALO_FORM (per call); GCL_GCN_HALO_BPC
+struct GcnSwitches {
+  bool halo, x3, form;    // GCL_GCN_HALO, GCL_X3 && GCL_X3_GCN, GCL_GCN_HALO_FORM (per call)
+  int bpc;                // GCL_GCN_HALO_BPC
+  bool edge_pipe = true;  // GCL_GCN_EDGE_PIPE (per call): kEdgeX3's waves with few items start without the stagger; no form depends on it
+};
 struct GcnPlan {
   GcnForm form = GcnForm::kRefused;
   const char* why = "";  // kRefused

@@ -103,19 +103,27 @@ def main():
         us, mn = timeit(lambda: agg(True), args.iters)
         row(f"aggregate bwd {tag} (transpose)", us, mn, B * per, 2 * B * gr.e * F)
 
-    # one-kernel GCNConv layer (aggregate-first): the same per-layer algorithmic bytes as the aggregation
-    for ei, nn_, tag in () if "gcn" not in only else ((m.processor_graph(), M, "mesh E_M (tile order)"), (m.encoding_graph, n, "enc E_G2M"), (m.decoding_graph, n, "dec E_M2G")):
+    # one-kernel GCNConv layer (aggregate-first): the same per-layer algorithmic bytes as the aggregation.  The last two
+    # are the graphs the compact pipeline runs the layer on (models.py::_compact_setup): the encoder graph on
+    # G + Md + r rows, 64 -> 64, and the decoder graph on G + U rows, 64 -> 48 (use --ring 4).
+    gcn_shapes = ()
+    if "gcn" in only:
+        gcn_shapes = [(m.processor_graph(), M, "mesh E_M (tile order)", F), (m.encoding_graph, n, "enc E_G2M", F), (m.decoding_graph, n, "dec E_M2G", F)]
+        if m._compact_eligible():
+            c = m._compact_setup(dev)
+            gcn_shapes += [(c.enc_graph, m._fold_setup(c, B, dev).ne, "enc compact", F), (c.dec_graph, G + c.U, "dec compact", 48)]
+    for ei, nn_, tag, Fo in gcn_shapes:
         gr = _graphs.get(ei, nn_, hip.GRAPH_GCN)
-        W, bias = rnd(F, F) * 0.1, rnd(F)
-        xs, outs, k = [rnd(B, nn_, F) for _ in range(args.ring)], [torch.empty(B, nn_, F, device=dev) for _ in range(args.ring)], [0]
+        W, bias = rnd(Fo, F) * 0.1, rnd(Fo)
+        xs, outs, k = [rnd(B, nn_, F) for _ in range(args.ring)], [torch.empty(B, nn_, Fo, device=dev) for _ in range(args.ring)], [0]
 
         def layer(act):
             k[0] = (k[0] + 1) % args.ring
             hip.gcn_layer_fwd(gr, xs[k[0]], act, slope if act else None, W, bias, out=outs[k[0]])
-        per = 4 * nn_ * 2 * F + 4 * gr.e + 4 * (nn_ + 1) + 4 * nn_
+        per = 4 * nn_ * (F + Fo) + 4 * gr.e + 4 * (nn_ + 1) + 4 * nn_
         for act, an in ((hip.ACT_NONE, "none"), (hip.ACT_PRELU, "prelu")):
             us, mn = timeit(lambda: layer(act), args.iters)
-            row(f"gcn_layer_fwd {tag} act={an} F={F}", us, mn, B * per, 2 * B * nn_ * F * F + 2 * B * gr.e * F)
+            row(f"gcn_layer_fwd {tag} n={nn_} act={an} {F}->{Fo}", us, mn, B * per, 2 * B * nn_ * F * Fo + 2 * B * gr.e * F)
 
     # GATConv / SparseGATConv attention aggregation on the mesh graph (H = 1 head of C = F channels, as configs[2]/[4])
     if "gat" in only:
