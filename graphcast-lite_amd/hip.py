@@ -276,6 +276,11 @@ _SIGNATURES = {
     "gcl_unet_v2_spectral_fwd": (C.c_int, [_vp, _vp] + [_i32] * 6 + [_vp]),
     "gcl_unet_v2_spectral_mix": (C.c_int, [_vp] * 3 + [_i32] * 4 + [_vp]),
     "gcl_unet_v2_spectral_inv": (C.c_int, [_vp, _vp, _i64] + [_i32] * 6 + [_vp]),
+    "gcl_unet_forecast_launches": (_i64, []),
+    "gcl_grid_window_pack": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _vp]),
+    "gcl_grid_forecast_step_ws_bytes": (_sz, [_i32] * 4),
+    "gcl_grid_forecast_step": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp] + [_i32] * 4
+                               + [_vp] * 5 + [_i32, _vp, _sz, _vp]),
 }
 
 
@@ -2956,3 +2961,63 @@ def unet_v2_spectral_inv(O, out, mh: int, mw: int):
         raise ValueError(f"unet_v2_spectral_inv: O is a contiguous [{B}, {mh * mw}, {Cc}, 2] tensor, got {tuple(O.shape)}")
     _check(lib().gcl_unet_v2_spectral_inv(_p(O), _p(out), ld, B, Hb, Wb, Cc, int(mh), int(mw), _stream()))
     return out
+
+
+# ======================================================================================================================
+# The regional U-Net forecaster's loop around its network (csrc/unet_forecast.hip)
+# ======================================================================================================================
+def unet_forecast_launches() -> int:
+    """Kernels launched by the entry points of csrc/unet_forecast.hip in this process."""
+    return int(lib().gcl_unet_forecast_launches())
+
+
+def _grid_series(series, t0, who):
+    if series.dim() != 4 or not series.is_cuda or series.dtype != torch.float16 or not series.is_contiguous():
+        raise ValueError(f"{who}: series is a contiguous float16 [T, n_lon, n_lat, Ct] GPU tensor")
+    if t0.dim() != 1 or t0.numel() < 1:
+        raise ValueError(f"{who}: t0 holds one window start per sample")
+    return series.shape
+
+
+def grid_window_pack(series, t0, mean, std, obs: int, out=None):
+    """X [B, obs * C, H = n_lat, W = n_lon] of the windows starting at t0 (int64 [B] on the device) of the fp16 series
+    [T, n_lon, n_lat, Ct], C = mean.numel() <= Ct (see gcl_grid_window_pack).  out: the tensor to fill."""
+    T, n_lon, n_lat, Ct = _grid_series(series, t0, "grid_window_pack")
+    Cc, B = mean.numel(), t0.numel()
+    if std.numel() != Cc or not 1 <= Cc <= Ct or obs < 1:
+        raise ValueError(f"grid_window_pack: mean and std of C <= {Ct} values and obs >= 1 expected")
+    X = _out(out, (B, obs * Cc, n_lat, n_lon), series, "grid_window_pack", exact=True)
+    _check(lib().gcl_grid_window_pack(_ph(series), T, n_lon, n_lat, Ct, _pl(t0), _p(mean), _p(std), Cc, int(obs), _p(X), B,
+                                      _stream()))
+    return X
+
+
+def grid_forecast_step(out, X, series, t0, chan_kind, mean, std, step: int, X_next, state, acc_count, count, pred=None,
+                       ws=None):
+    """One autoregressive step around the network (see gcl_grid_forecast_step): out [B, C, H, W] (residual applied) and the
+    window X [B, obs * C, H, W] -> X_next (not X), pred (optional) and the scores of `step` added to state float64
+    [AR, C, 5], acc_count int64 [AR, C] and count int64 [AR].  chan_kind: uint8 [C] on the device (0 dynamic, 1 static,
+    2 forcing); t0: int64 [B] on the device, a negative entry skips its sample."""
+    T, n_lon, n_lat, Ct = _grid_series(series, t0, "grid_forecast_step")
+    if out.dim() != 4 or X.dim() != 4:
+        raise ValueError("grid_forecast_step: out [B, C, H, W] and X [B, obs * C, H, W] expected")
+    B, Cc, H, W = out.shape
+    if (H, W) != (n_lat, n_lon) or X.shape[0] != B or tuple(X.shape[2:]) != (H, W) or X.shape[1] % Cc or X.shape[1] < Cc:
+        raise ValueError(f"grid_forecast_step: out [B, C, {n_lat}, {n_lon}] and X [B, obs * C, {n_lat}, {n_lon}] expected, got "
+                         f"{tuple(out.shape)} and {tuple(X.shape)}")
+    obs = X.shape[1] // Cc
+    if tuple(X_next.shape) != tuple(X.shape) or (pred is not None and tuple(pred.shape) != tuple(out.shape)):
+        raise ValueError("grid_forecast_step: X_next has X's shape and pred has out's")
+    if not all(t.is_contiguous() for t in (out, X, X_next) + ((pred,) if pred is not None else ())) or t0.numel() != B:
+        raise ValueError("grid_forecast_step: contiguous fields and t0 of B values expected")
+    if chan_kind.dtype != torch.uint8 or chan_kind.numel() != Cc or not chan_kind.is_cuda or mean.numel() != Cc \
+            or std.numel() != Cc:
+        raise ValueError(f"grid_forecast_step: chan_kind uint8 [{Cc}] on the device and mean / std of {Cc} values expected")
+    if state.dim() != 3 or tuple(state.shape[1:]) != (Cc, 5) or tuple(acc_count.shape) != tuple(state.shape[:2]) \
+            or count.numel() != state.shape[0]:
+        raise ValueError(f"grid_forecast_step: state [AR, {Cc}, 5], acc_count [AR, {Cc}] and count [AR] expected")
+    ws_ptr, ws_bytes = _ws_for(int(lib().gcl_grid_forecast_step_ws_bytes(B, H, W, Cc)), ws, out.device)
+    _check(lib().gcl_grid_forecast_step(_p(out), _p(X), _ph(series), T, n_lon, n_lat, Ct, _pl(t0), chan_kind.data_ptr(),
+                                        _p(mean), _p(std), Cc, obs, int(step), state.shape[0], _p(X_next), _p(pred),
+                                        _pd(state), _pl(acc_count), _pl(count), B, ws_ptr, ws_bytes, _stream()))
+    return X_next

@@ -1545,6 +1545,52 @@ int gcl_unet_v2_spectral_mix(const float* X, const float* packed, float* O, int3
 int gcl_unet_v2_spectral_inv(const float* O, float* out, int64_t ldo, int32_t B, int32_t Hb, int32_t Wb, int32_t C,
                              int32_t mh, int32_t mw, gcl_stream_t stream);
 
+/* ---- The regional U-Net forecaster's loop around its network (csrc/unet_forecast.hip) ----
+ * src/unet/predict.py and predict_v2.py (the same script but for the model built): the window as a planar 2-D grid and one
+ * autoregressive step's carry-forward, shift and scores, batched over B window starts t0[b] (device int64).  No entry
+ * point allocates, synchronises or reads back; no atomics; every sum has an order fixed by (H, W, C) alone, never by B or
+ * a sample's place in the batch; a NaN or Inf stays in its sample.  series: IEEE binary16 [T, n_lon, n_lat, Ct]; the
+ * planar tensors are [.., H = n_lat, W = n_lon] float32, so every read of the series is a transpose, staged through LDS
+ * in tiles of 32 columns x 8 rows: 16-byte reads of the series, and 16-byte accesses of the planes when W % 4 == 0 (one
+ * float per lane otherwise).  mean, std: float32 [C], C <= Ct.  This section's launch counter is its own. */
+int64_t gcl_unet_forecast_launches(void);
+/* src/data/dataloader_chunked.py:202-218 followed by Grid2DDataset.__getitem__ (predict_v2.py:36-40), the input half:
+ * X [B, obs*C, H, W], channel o*C + c at (h, w) = ((float)series[t0+o, w, h, c] - mean[c]) / std[c], bit-identical to
+ * the numpy loader (the contract of gcl_window_pack, planar).  A sample whose window [t0, t0 + obs) is not inside [0, T)
+ * is filled with NaN.  B, obs <= 65535.  One launch. */
+int gcl_grid_window_pack(const uint16_t* series /* IEEE binary16 */, int64_t T, int32_t n_lon, int32_t n_lat, int32_t Ct,
+                         const int64_t* t0, const float* mean, const float* stdv, int32_t C, int32_t obs,
+                         float* X /*[B,obs*C,H,W]*/, int32_t B, gcl_stream_t stream);
+/* predict_v2.py:138-180 for B samples at autoregressive step `step` (0 <= step < AR).  out [B,C,H,W]: the network's
+ * planar output with x_last added (residual_from); X [B,obs*C,H,W]: the current window; chan_kind uint8 [C]: 0 dynamic,
+ * 1 static, 2 forcing (a channel in both of the script's lists is forcing, its later assignment).
+ *   carry    out' = out (dynamic), X[:, (obs-1)*C + c] (static, :142-144), or the normalised truth
+ *            ((float)series[t0+obs+step, w, h, c] - mean[c]) / std[c] (forcing, :145-148); bit-exact in all three;
+ *   shift    X_next [B,obs*C,H,W] = channels C .. obs*C of X, then out' (:180); X_next is not X.  pred [B,C,H,W] (may be
+ *            NULL) receives out' alone;
+ *   scores   per (sample, channel), with g = the normalised truth frame t0+obs+step and bl = the normalised frame
+ *            t0+obs-1, both read from the series: sum (out'*std+mean - (g*std+mean))^2, the same for bl (:156-160),
+ *            sum (out'-g)^2 and sum (bl-g)^2 (:162-163) - products, sums, differences and squares in float32 one by one
+ *            as numpy forms them, the sums over the pixels in float64; the field means of out' and g in float64, then
+ *            about them sum p^2, sum t^2 and sum p t in float64 (a second pass: |mean| >> spread costs nothing) and
+ *            corr = sum p t / (sqrt(sum p^2) * sqrt(sum t^2)), counted when both norms exceed 1e-8 (:166-175);
+ *   state    float64 [AR,C,5] (se_phys, se_base_phys, se_norm, se_base_norm, acc_sum), acc_count int64 [AR,C], count
+ *            int64 [AR]: state[step] += the samples' values one after the other in batch order, so that the batch size
+ *            does not reach the bits (the rule of gcl_cascade_scores); count[step] += H*W per sample scored.
+ * A sample whose t0 < 0 or whose truth frame is outside [0, T) is skipped: nothing is scored and its X_next / pred stay
+ * unwritten (a fixed-B graph takes a tail batch with t0 = -1 rows).  B <= 65535, obs <= 4096; with W % 4 == 0
+ * out, X, X_next and pred are 16-byte aligned.  ws: gcl_grid_forecast_step_ws_bytes(B, H, W, C) bytes, 8-byte aligned;
+ * on return it holds, for the samples scored, float64 [B][C][6][n] (the four squared-error sums, sum out', sum g) followed
+ * by [B][C][3][n] (sum p^2, sum t^2, sum p t about the means), n = the byte count / (72 B C) chunks of tiles to be added.
+ * Three launches: carry + shift + the squared errors and field sums per chunk of tiles; the centred sums per chunk of
+ * tiles; the chunks of a (sample, channel) in a fixed order into the state. */
+size_t gcl_grid_forecast_step_ws_bytes(int32_t B, int32_t H, int32_t W, int32_t C);
+int gcl_grid_forecast_step(const float* out, const float* X, const uint16_t* series /* IEEE binary16 */, int64_t T,
+                           int32_t n_lon, int32_t n_lat, int32_t Ct, const int64_t* t0, const uint8_t* chan_kind,
+                           const float* mean, const float* stdv, int32_t C, int32_t obs, int32_t step, int32_t AR,
+                           float* X_next, float* pred, double* state, int64_t* acc_count, int64_t* count, int32_t B,
+                           void* ws, size_t ws_bytes, gcl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
